@@ -8,7 +8,10 @@ A step = one pass of the hot path over one batch: every block of the workload is
          Phred ~ N(34,5) clipped to [2,41]; own seed) in the reference's default -R 256 blocks (4 blocks of 256 MiB)
          with ONE sample's tables (first 128 MiB of rank 0's reads, broadcast as bytes).  The units (blocks) are
          independent given the tables and are sharded over the ranks: work per GPU fixed, "scaling": "weak".
-`strong_config2_MBps`  (every N, after the timed region) BASELINE.json configs[2], the reference's scaling config:
+A plain run sets up, warms up, times `--steps` steps, writes the outputs of the last timed step when `--dump-outputs DIR`
+         is given, and prints the line: `value` and `ms_per_step` with the workload's description and stream sizes.
+         Everything below that is measured or checked after the timed region runs only with `--full`.
+`strong_config2_MBps`  (--full, every N, after the timed region) BASELINE.json configs[2], the reference's scaling config:
          ONE 1 GiB job cut into 64 MiB blocks (16 of them), block b coded by rank b mod N, tables from the job's
          first 128 MiB: total work fixed (two blocks per GPU at N = 8).  At N = 1 the same number is also printed as
          `encode_config3_MBps` (16 x 64 MiB on one GPU).  `--layout strong` makes THIS the timed `value` instead.
@@ -17,8 +20,9 @@ A step = one pass of the hot path over one batch: every block of the workload is
          exits with their worst exit code; it refuses (exit 2) when fewer than N devices are visible.
 One process per GPU; no data-path collective and no RCCL call anywhere: the table broadcast, the barriers and the
 max-over-ranks of the elapsed time go over gloo.
-value = raw FASTQ bytes all ranks coded per second (max-over-ranks time).  After the timed region
-(not part of `value`): a whole timed block is byte-compared with the CPU oracle (also the source of
+value = raw FASTQ bytes all ranks coded per second (max-over-ranks time).  With --full, after the timed region
+(not part of `value`): the roofline of the dominant kernel group (HIP events in one extra untimed step and around
+that group in the timed steps), a whole timed block is byte-compared with the CPU oracle (also the source of
 `ratio_vs_reference`), decode of the same archive (configs[4]: blocks dealt over the N ranks), the
 CPU baselines, the host-pointer path incl. PCIe, other data (binned / constant / configs[3] / tiled REAL reads).
 One JSON line on rank 0.
@@ -33,11 +37,12 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # up to 8 blocks in flight x (seq, qual) streams, one hardware queue each
 
 import numpy as np  # noqa: E402
 
 MB = 1e6
+DUMP_STREAMS = ("seq", "qual", "readlens", "n_count", "n_pos")   # what fqgpu_dblock_fetch hands a caller per block
+DUMP_ELEMS = 12 << 20   # float32 elements over all dumped streams of the job: 48 MiB, under the 64 MB a dump may take
 PROFILE_TRAFFIC = "r04_traffic.json"  # counters and rocprof launch times of this round (tools/refresh_profiles.py)
 
 
@@ -381,6 +386,35 @@ def cpu_baseline(blocks, sft, qft, seconds_budget=24.0):
     return enc, dec
 
 
+def dump_outputs(out_dir, fetched, block_ids, job_blocks, seed=2828):
+    """--dump-outputs: what a caller of the timed path receives for every block of the last timed step (fetched: one
+    DBlock.fetch() dict per block, block_ids: their indices in the job).  Writes <out_dir>/block<b>_<stream>.npy, float32:
+    the whole stream while it has at most `cap` elements (cap keeps the job's dump within DUMP_ELEMS), else the elements at
+    `cap` sorted positions drawn by a generator seeded with (seed, b, stream); an empty stream (n_pos of reads without N)
+    gets no file.  And <out_dir>/block<b>_summary.npy, float64, one row per stream of DUMP_STREAMS: its length, then its
+    sha256 as 16 little-endian 16-bit words, so that two dumps agree there only when every byte of every stream agrees
+    (an empty stream included).  -> bytes of array data written"""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = max(1, DUMP_ELEMS // (max(1, job_blocks) * len(DUMP_STREAMS)))
+    written = 0
+    for bid, got in zip(block_ids, fetched):
+        summary = np.zeros((len(DUMP_STREAMS), 17), dtype=np.float64)
+        for si, name in enumerate(DUMP_STREAMS):
+            a = np.ascontiguousarray(got[name])
+            summary[si, 0] = a.size
+            summary[si, 1:] = np.frombuffer(hashlib.sha256(a.tobytes()).digest(), dtype="<u2")
+            if a.size == 0:
+                continue
+            if a.size > cap:
+                a = a[np.sort(np.random.default_rng((seed, bid, si)).integers(0, a.size, cap))]
+            a = a.astype(np.float32)
+            np.save(os.path.join(out_dir, "block%d_%s.npy" % (bid, name)), a)
+            written += a.nbytes
+        np.save(os.path.join(out_dir, "block%d_summary.npy" % bid), summary)
+        written += summary.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -409,7 +443,15 @@ def main():
                     "host-pointer path, other data); by default they run at N = 1 only")
     ap.add_argument("--skip-other-data", action="store_true", help="no binned / constant / configs[3] runs after the timed region")
     ap.add_argument("--skip-strong", action="store_true", help="no configs[2] run (ONE job in 64 MiB blocks dealt over the ranks) after the timed region")
+    ap.add_argument("--full", action="store_true", help="everything after the timed region as well: roofline and kernel table (HIP events), oracle check, "
+                    "decode, configs[2], host-pointer path, C++ farm, other data, CPU baselines (the --skip-* options leave parts out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the streams the last timed step produced to DIR/*.npy (float32, seeded sample of long streams, sha256 of each stream)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:   # a plain run: the timed region and its line only
+        args.skip_cpu = args.skip_decode = args.skip_host = args.skip_farm = args.skip_other_data = args.skip_strong = True
 
     # `--gpus N` without a launcher: N fresh processes of this script, before anything here touches a GPU
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -424,10 +466,13 @@ def main():
         sys.stderr.write("bench.py: note: --gpus %d but the launcher started %d rank(s); the launcher's count is used\n" % (args.gpus, world))
     dist = farm.init_dist()  # gloo; before anything touches the GPU
     import torch
+    import fqcomp28_amd as F
+    # Loaded before torch initialises HIP, so that the library's load-time constructor can ask for 16 hardware queues (up to
+    # 8 blocks in flight x (seq, qual) streams, one queue each) unless the environment already sets a count (api.hip).
+    F.lib()
     if args.all_on_gpu0:
         local = 0
     torch.cuda.set_device(local)
-    import fqcomp28_amd as F
     assert F.device_count() > local, "bench.py needs a GPU (no CPU fallback)"
     device = local
     layout = args.layout if args.layout != "auto" else ("config1" if world == 1 else "weak")
@@ -449,7 +494,8 @@ def main():
         if rank == 0:
             sft, qft = sample_tables(F, job, args.sample_mib << 20, device)
         sft, qft = farm.broadcast_tables(sft, qft, dist)
-        blocks = [job[b] for b in farm.shard_blocks(len(job), rank, world)]
+        block_ids = farm.shard_blocks(len(job), rank, world)
+        blocks = [job[b] for b in block_ids]
         job_blocks = len(job)
         del job
     else:
@@ -462,6 +508,7 @@ def main():
         else:
             sft, qft = sample_tables(F, blocks, args.sample_mib << 20, device)
         job_blocks = len(blocks) * world
+        block_ids = [rank * len(blocks) + b for b in range(len(blocks))]
     ctx = F.Context(sft, qft, device=device)
     ctx.set_lanes(max(0, min(args.lanes, 8)))
     ctx.set_chain_params(args.segment, seq_generic=args.seq_mode == "generic", seq_segment=args.seq_segment)
@@ -475,35 +522,36 @@ def main():
         for b in dblocks:
             b.encode()
 
-    # Warm-up, then ONE more untimed step with HIP events around EVERY kernel group: it gives the
-    # table of all groups (kernels_ms) and names the dominant one.  The timed steps then carry events
+    # Warm-up; with --full then ONE more untimed step with HIP events around EVERY kernel group: it gives
+    # the table of all groups (kernels_ms) and names the dominant one.  The timed steps then carry events
     # around that group only (two per launch, on the stream it is launched on): events between all
-    # kernels of a stream cost 2-3 % of the step.
+    # kernels of a stream cost 2-3 % of the step.  A plain run times the steps without events.
     def spans_of():
         tot_ms, spans = ctx.last_timing()
         return {name: ms / max(n, 1) for name, ms, n in spans}, {name: n for name, ms, n in spans}
     for _ in range(args.warmup):
         step()
     ctx.sync()
-    ctx.enable_timing(True)
-    step()
-    ctx.sync()
-    kern_all, _ = spans_of()
-    # The roofline kernel is the one the PROFILE names: largest total rocprofv3 duration in the committed kernel-trace
-    # summary of this device code (profiles/<round>_traffic.json, bound by the hash over the device sources).  The
-    # HIP-event table of this one untimed step only decides without such a profile: with four blocks in flight its
-    # spans move by +-30 % from run to run.
-    profile = load_profile(block_mib)
-    dom_from = "largest total rocprofv3 duration in profiles/%s (same device code)" % PROFILE_TRAFFIC
-    dom_name = None
-    if profile:
-        ranked = sorted(((k, v.get("rocprof_total_ms", 0.0)) for k, v in profile["kernels"].items() if k in kern_all), key=lambda kv: -kv[1])
-        if ranked and ranked[0][1] > 0:
-            dom_name = ranked[0][0]
-    if dom_name is None:
-        dom_name = max(kern_all.items(), key=lambda kv: kv[1])[0] if kern_all else None
-        dom_from = "HIP-event spans of one untimed step (no committed profile of this device code)"
-    ctx.enable_timing(True, only=None if os.environ.get("FQ_BENCH_ALL_EVENTS") else dom_name)
+    if args.full:
+        ctx.enable_timing(True)
+        step()
+        ctx.sync()
+        kern_all, _ = spans_of()
+        # The roofline kernel is the one the PROFILE names: largest total rocprofv3 duration in the committed kernel-trace
+        # summary of this device code (profiles/<round>_traffic.json, bound by the hash over the device sources).  The
+        # HIP-event table of this one untimed step only decides without such a profile: with four blocks in flight its
+        # spans move by +-30 % from run to run.
+        profile = load_profile(block_mib)
+        dom_from = "largest total rocprofv3 duration in profiles/%s (same device code)" % PROFILE_TRAFFIC
+        dom_name = None
+        if profile:
+            ranked = sorted(((k, v.get("rocprof_total_ms", 0.0)) for k, v in profile["kernels"].items() if k in kern_all), key=lambda kv: -kv[1])
+            if ranked and ranked[0][1] > 0:
+                dom_name = ranked[0][0]
+        if dom_name is None:
+            dom_name = max(kern_all.items(), key=lambda kv: kv[1])[0] if kern_all else None
+            dom_from = "HIP-event spans of one untimed step (no committed profile of this device code)"
+        ctx.enable_timing(True, only=None if os.environ.get("FQ_BENCH_ALL_EVENTS") else dom_name)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -511,11 +559,12 @@ def main():
     ctx.sync()
     barrier()
     elapsed = time.perf_counter() - t0
-    # device time of the dominant group over the timed steps (or of every group without a warm-up step)
-    kern_timed, calls = spans_of()
-    kern = dict(kern_all)
-    kern.update(kern_timed)
-    ctx.enable_timing(False)
+    if args.full:
+        # device time of the dominant group over the timed steps (or of every group without a warm-up step)
+        kern_timed, calls = spans_of()
+        kern = dict(kern_all)
+        kern.update(kern_timed)
+        ctx.enable_timing(False)
     elapsed = farm.reduce_max(elapsed, dist)
     total_raw = farm.reduce_sum(float(raw_bytes), dist)
     enc_MBps = total_raw * args.steps / elapsed / MB
@@ -529,6 +578,8 @@ def main():
     qual_bytes = sum(s["qual_len"] for s in sizes)
     npos_bytes = 2 * sum(s["n_pos_len"] for s in sizes)
     longest = [b.longest_chain() for b in dblocks]
+    if args.dump_outputs:   # before the --full legs wipe and re-encode the blocks
+        dump_outputs(args.dump_outputs, [b.fetch() for b in dblocks], block_ids, job_blocks)
 
     # ---- the timed output against the oracle (rank 0): one WHOLE block of the last timed step, byte
     # for byte; the size ratio against the reference coder follows from the same oracle run
@@ -550,51 +601,53 @@ def main():
 
     # ---- roofline of the dominant kernel: algorithmic bytes of ONE block's
     # stream = symbols read once + stream bytes written once; the whole-block figure alongside
-    last = sizes[-1]
-    last_raw = blocks[-1][0].size
-    last_bases = int(blocks[-1][1]["len"].sum())
-    alg_block = last_raw + last["seq_len"] + last["qual_len"] + 2 * len(blocks[-1][1]) * 2 + 2 * last["n_pos_len"]
-    # the group named by the warm-up table, with its duration over the TIMED steps
-    if dom_name and dom_name in kern_timed:
-        dom = (dom_name, kern_timed[dom_name])
-    else:
-        dom = max(kern.items(), key=lambda kv: kv[1]) if kern else ("none", 0.0)
-    stream_out = last["qual_len"] if dom[0].startswith("qual") else last["seq_len"]
-    alg_dom = last_bases + stream_out if "." in dom[0] else alg_block
-    dom_s = dom[1] / 1e3
-    achieved = alg_dom / dom_s / 1e9 if dom_s > 0 else 0.0
-    # HBM bytes of that kernel: bench.py cannot collect counters itself (separate rocprofv3 --pmc
-    # passes of this script, tools/refresh_profiles.py).  The committed figure is quoted only while
-    # the device code is the code it was measured on; otherwise null.
-    traffic, rocprof_avg_ms = None, None
-    traffic_src = profile_stamp()
-    if profile:
-        k = profile["kernels"].get(dom[0])
-        if k:
-            traffic = k.get("traffic_bytes_per_launch")
-            rocprof_avg_ms = k.get("rocprof_avg_launch_ms")
-        traffic_src["block_traffic_bytes"] = profile.get("block_traffic_bytes")
-    # One figure per key: `achieved` / `frac` divide by the kernel's own duration -- the rocprofv3 launch
-    # time of the committed profile while the device code is the code it was taken on, else (null
-    # profile) the HIP-event span measured here; the span (which also holds the wait for room on a chip
-    # busy with the other lanes' kernels) is always given beside it as frac_event_span.
-    span_achieved = achieved
-    if rocprof_avg_ms:
-        achieved = alg_dom / (rocprof_avg_ms / 1e3) / 1e9
-    roofline = {"bound": "hbm", "kernel": dom[0], "kernel_chosen_by": dom_from,
-                "rocprof_kernel": (profile["kernels"].get(dom[0], {}).get("rocprof_kernel") if profile else None),
-                "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
-                "frac": round(achieved / 8000.0, 5), "frac_from": "rocprofv3 launch time of the committed profile (same device code)" if rocprof_avg_ms
-                else "HIP-event span of this run (no committed profile of this device code)",
-                "frac_event_span": round(span_achieved / 8000.0, 5), "achieved_event_span": round(span_achieved, 2),
-                "traffic": traffic, "traffic_from_committed_profile": traffic_src,
-                "rocprof_avg_launch_ms": rocprof_avg_ms,
-                "event_span_ms": round(dom[1], 4), "algorithmic_bytes_per_launch": int(alg_dom),
-                "launches_timed": calls.get(dom[0], 0),
-                "job_GBps": round(alg_block * len(blocks) * args.steps / elapsed / 1e9, 2),
-                "job_frac": round(alg_block * len(blocks) * args.steps / elapsed / 1e9 / 8000.0, 5),
-                "kernels_ms_from": "one untimed step after the warm-up (events around every kernel group); the roofline kernel: the timed steps",
-                "kernels_ms": {k: round(v, 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])}}
+    roofline = None
+    if args.full:
+        last = sizes[-1]
+        last_raw = blocks[-1][0].size
+        last_bases = int(blocks[-1][1]["len"].sum())
+        alg_block = last_raw + last["seq_len"] + last["qual_len"] + 2 * len(blocks[-1][1]) * 2 + 2 * last["n_pos_len"]
+        # the group named by the warm-up table, with its duration over the TIMED steps
+        if dom_name and dom_name in kern_timed:
+            dom = (dom_name, kern_timed[dom_name])
+        else:
+            dom = max(kern.items(), key=lambda kv: kv[1]) if kern else ("none", 0.0)
+        stream_out = last["qual_len"] if dom[0].startswith("qual") else last["seq_len"]
+        alg_dom = last_bases + stream_out if "." in dom[0] else alg_block
+        dom_s = dom[1] / 1e3
+        achieved = alg_dom / dom_s / 1e9 if dom_s > 0 else 0.0
+        # HBM bytes of that kernel: bench.py cannot collect counters itself (separate rocprofv3 --pmc
+        # passes of this script, tools/refresh_profiles.py).  The committed figure is quoted only while
+        # the device code is the code it was measured on; otherwise null.
+        traffic, rocprof_avg_ms = None, None
+        traffic_src = profile_stamp()
+        if profile:
+            k = profile["kernels"].get(dom[0])
+            if k:
+                traffic = k.get("traffic_bytes_per_launch")
+                rocprof_avg_ms = k.get("rocprof_avg_launch_ms")
+            traffic_src["block_traffic_bytes"] = profile.get("block_traffic_bytes")
+        # One figure per key: `achieved` / `frac` divide by the kernel's own duration -- the rocprofv3 launch
+        # time of the committed profile while the device code is the code it was taken on, else (null
+        # profile) the HIP-event span measured here; the span (which also holds the wait for room on a chip
+        # busy with the other lanes' kernels) is always given beside it as frac_event_span.
+        span_achieved = achieved
+        if rocprof_avg_ms:
+            achieved = alg_dom / (rocprof_avg_ms / 1e3) / 1e9
+        roofline = {"bound": "hbm", "kernel": dom[0], "kernel_chosen_by": dom_from,
+                    "rocprof_kernel": (profile["kernels"].get(dom[0], {}).get("rocprof_kernel") if profile else None),
+                    "achieved": round(achieved, 2), "peak": 8000.0, "unit": "GB/s",
+                    "frac": round(achieved / 8000.0, 5), "frac_from": "rocprofv3 launch time of the committed profile (same device code)" if rocprof_avg_ms
+                    else "HIP-event span of this run (no committed profile of this device code)",
+                    "frac_event_span": round(span_achieved / 8000.0, 5), "achieved_event_span": round(span_achieved, 2),
+                    "traffic": traffic, "traffic_from_committed_profile": traffic_src,
+                    "rocprof_avg_launch_ms": rocprof_avg_ms,
+                    "event_span_ms": round(dom[1], 4), "algorithmic_bytes_per_launch": int(alg_dom),
+                    "launches_timed": calls.get(dom[0], 0),
+                    "job_GBps": round(alg_block * len(blocks) * args.steps / elapsed / 1e9, 2),
+                    "job_frac": round(alg_block * len(blocks) * args.steps / elapsed / 1e9 / 8000.0, 5),
+                    "kernels_ms_from": "one untimed step after the warm-up (events around every kernel group); the roofline kernel: the timed steps",
+                    "kernels_ms": {k: round(v, 4) for k, v in sorted(kern.items(), key=lambda kv: -kv[1])}}
 
     extra = {}
     # ---- decode (after the timed region): the same archive, blocks dealt over the ranks exactly as
@@ -689,7 +742,7 @@ def main():
         b.close()
     dblocks = []
     # The timed handle goes before the next one comes: a handle created behind another shares the first one's hardware
-    # queues (GPU_MAX_HW_QUEUES = 16: streams on one queue run back to back) and runs 5-9 % slower for it -- until round 4's
+    # queues (GPU_MAX_HW_QUEUES of them: streams on one queue run back to back) and runs 5-9 % slower for it -- until round 4's
     # last day every later leg of this process paid that (tools/second_handle_probe.py).
     ctx.close()
     ctx = None
@@ -840,6 +893,7 @@ def main():
                            "longest_serial_chain": [list(r) for r in longest]},
             "oracle_check": check, "kernel_sources_sha": kernel_sources_sha(),
             "roofline": roofline, "cpu_baseline": cpu, "cpu_baseline_decode": cpu_dec, "setup_s": round(setup_s, 1),
+            "full": args.full,
         }
         line.update(extra)
         if cpu:

@@ -82,17 +82,29 @@ def test_synthetic_generator_is_deterministic_and_well_formed(F, mode):
         assert 0.005 < isn.mean() < 0.02 and (quals[isn] == 2).all()
 
 
+_NO_GPU_CHECK = """
+import os, sys
+import pytest
+import fqcomp28_amd as F
+import oracle_lib as O
+assert F.device_count() == 0
+raw, recs = O.load_fastq(os.path.join(sys.argv[1], "SRR065390_1_first5.fastq"))
+with pytest.raises(F.FqgpuError) as ei:
+    F.freq_tables(raw, recs)
+assert ei.value.code == -5
+_, _, sft, qft = O.freq_tables(raw, recs)
+with pytest.raises(F.FqgpuError) as ei:
+    F.Context(sft, qft)
+assert ei.value.code == -5
+print("loud")
+"""
+
+
 def test_no_gpu_means_loud_failure_not_fallback(F, golden_dir):
-    if F.device_count() > 0:
-        pytest.skip("a GPU is visible")
-    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_1_first5.fastq"))
-    with pytest.raises(F.FqgpuError) as ei:
-        F.freq_tables(raw, recs)
-    assert ei.value.code == -5
-    _, _, sft, qft = O.freq_tables(raw, recs)
-    with pytest.raises(F.FqgpuError) as ei:
-        F.Context(sft, qft)
-    assert ei.value.code == -5
+    """in a fresh process that is shown no device (HIP_VISIBLE_DEVICES=-1), so that a machine with a GPU checks it too"""
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="-1", PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "tests")]))
+    r = subprocess.run([sys.executable, "-s", "-c", _NO_GPU_CHECK, golden_dir], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and r.stdout.strip() == "loud", r.stdout + r.stderr[-2000:]
 
 
 def test_product_never_imports_the_oracle():
@@ -231,3 +243,32 @@ def test_bench_quotes_a_profile_only_for_the_device_code_it_was_taken_on(tmp_pat
     assert bench.load_profile(64) is None                       # another block size: not this profile's kernels
     (tmp_path / "fqcomp28_amd" / "csrc" / "a.hip").write_text("kernel v2")
     assert bench.load_profile(256) is None and bench.profile_stamp()["kernel_sources_sha"] == sha != bench.profile_stamp()["current_kernel_sources_sha"]
+
+
+def test_bench_dump_outputs_is_seeded_bounded_and_catches_every_byte(tmp_path):
+    """`bench.py --dump-outputs DIR`: the same streams give the same files; a job of configs[1]'s stream sizes stays under
+    64 MB; short streams are dumped whole, long ones as a sample, empty ones not at all (their length and hash are in the
+    summary); a one-byte change anywhere shows in the summary."""
+    bench = _bench()
+    rng = np.random.default_rng(7)
+    base_seq, base_qual = rng.integers(0, 256, 30 << 20, dtype=np.uint8), rng.integers(0, 256, 62 << 20, dtype=np.uint8)   # shared by the blocks
+    got = [dict(seq=base_seq, qual=base_qual, readlens=np.full(800_000, 150, np.uint16), n_count=np.zeros(800_000, np.uint16),
+                n_pos=np.arange(5, dtype=np.uint16)) for _ in range(4)]
+    got[0]["n_pos"] = np.zeros(0, np.uint16)   # reads without N
+    n = bench.dump_outputs(str(tmp_path / "a"), got, [0, 1, 2, 3], 4)
+    assert n == sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) and n < 64e6
+    assert sorted(os.listdir(tmp_path / "a")) == sorted("block%d_%s.npy" % (b, s) for b in range(4) for s in bench.DUMP_STREAMS + ("summary",)
+                                                        if (b, s) != (0, "n_pos"))
+    assert all(np.load(tmp_path / "a" / f).size > 0 for f in os.listdir(tmp_path / "a"))
+    assert np.load(tmp_path / "a" / "block0_summary.npy")[bench.DUMP_STREAMS.index("n_pos"), 0] == 0
+    assert np.array_equal(np.load(tmp_path / "a" / "block3_n_pos.npy"), np.arange(5, dtype=np.float32))
+    seq = np.load(tmp_path / "a" / "block1_seq.npy")
+    pos = np.sort(np.random.default_rng((2828, 1, 0)).integers(0, got[1]["seq"].size, seq.size))   # (seed, block, stream)
+    assert seq.dtype == np.float32 and 0 < seq.size < got[1]["seq"].size and np.array_equal(seq, got[1]["seq"][pos])
+    got[2]["qual"] = base_qual.copy()
+    got[2]["qual"][12345] ^= 1
+    bench.dump_outputs(str(tmp_path / "b"), got, [0, 1, 2, 3], 4)
+    dumps = {f: (np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)) for f in os.listdir(tmp_path / "a")}
+    assert all(a.dtype in (np.float32, np.float64) for a, _ in dumps.values())
+    changed = {f for f, (a, b) in dumps.items() if not np.array_equal(a, b)}
+    assert "block2_summary.npy" in changed and changed <= {"block2_summary.npy", "block2_qual.npy"}, changed

@@ -1,5 +1,5 @@
 """The timed encode loop alone on one kind of data, for profilers:
-    rocprofv3 --kernel-trace --stats -- python3 tools/encode_loop.py [synth|real|binned|constant|config3|config4] [steps] [lanes] [quality segment] [sequence segment]
+    rocprofv3 --kernel-trace --stats -d build/rocprof -- python3 tools/encode_loop.py [synth|real|binned|constant|config3|config4] [steps] [lanes] [quality segment] [sequence segment]
 (lanes 0 = the library's default; segments 0 = the library's defaults)"""
 import os
 import sys

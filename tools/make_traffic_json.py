@@ -1,6 +1,6 @@
 """Builds profiles/<tag>_traffic.json from the rocprofv3 passes of tools/profile_round.sh <tag> (gpurun_out/<tag>_prof4,
-_prof1, _pmc_f, _pmc_w).  Runs ON THE GPU BOX, between the profile passes and the default bench.py run of the same
-call, so that the default line quotes the file of ITS OWN round (round 3's default line quoted an earlier file than
+_prof1, _pmc_f, _pmc_w).  Runs ON THE GPU BOX, between the profile passes and the `bench.py --full` run of the same
+call, so that the full line quotes the file of ITS OWN round (round 3's default line quoted an earlier file than
 the one committed); a copy goes to gpurun_out/ (the only directory that travels back).
     python3 tools/make_traffic_json.py [tag]
 bench.py quotes the file only while the hash over the device sources is the one stamped here."""
@@ -102,7 +102,7 @@ for span, names in SPAN_KERNELS.items():
                          "rocprof_calls": sum(four_calls.get(n, 0) for n in names),
                          "rocprof_avg_launch_ms_one_lane": round(sum(one.get(n, 0.0) for n in names), 4)}
 json.dump({"commit": commit, "kernel_sources_sha": sha, "block_mib": 256, "block_traffic_bytes": int(block_mb * 1e6), "kernels": kernels,
-           "note": "separate --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py --steps 1 --warmup 1 --skip-cpu --skip-decode --skip-host "
+           "note": "separate --pmc FETCH_SIZE / --pmc WRITE_SIZE passes of bench.py --full --steps 1 --warmup 1 --skip-cpu --skip-decode --skip-host "
                    "(256 MiB blocks); FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 reports half the bytes of wide coalesced reads); "
                    "average launch times from the --kernel-trace --stats passes of the same commit"},
           open(R + "profiles/%s_traffic.json" % TAG, "w"), indent=1)

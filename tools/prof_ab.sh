@@ -10,7 +10,7 @@ for nv in "$@"; do
   n=${nv%%=*}; l=${nv#*=}
   export FQGPU_LIB=$R/$l
   rm -rf $O/${T}_${n}_4 $O/${T}_${n}_1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_${n}_4 -o p -- python3 $R/bench.py --skip-cpu --skip-decode --skip-host --skip-other-data --skip-strong > $O/${T}_${n}_4.log 2>&1 || exit 1
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_${n}_1 -o p -- python3 $R/bench.py --skip-cpu --skip-decode --skip-host --skip-other-data --skip-strong --lanes 1 --steps 2 > $O/${T}_${n}_1.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_${n}_4 -o p -- python3 $R/bench.py --full --skip-cpu --skip-decode --skip-host --skip-other-data --skip-strong > $O/${T}_${n}_4.log 2>&1 || exit 1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/${T}_${n}_1 -o p -- python3 $R/bench.py --full --skip-cpu --skip-decode --skip-host --skip-other-data --skip-strong --lanes 1 --steps 2 > $O/${T}_${n}_1.log 2>&1 || exit 1
   echo "$n done"
 done

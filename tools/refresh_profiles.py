@@ -1,5 +1,5 @@
-"""Runs HERE after the call: copies the rocprofv3 summaries of tools/profile_round.sh <tag> (gpurun_out/<tag>_*) and the default bench
-line (gpurun_out/<tag>_bench_default.log) into profiles/ and prints the figures DESIGN.md quotes.
+"""Runs HERE after the call: copies the rocprofv3 summaries of tools/profile_round.sh <tag> (<tag>_* in the call's output folder) and
+the line of its `bench.py --full` run (<tag>_bench_default.log there) into profiles/ and prints the figures DESIGN.md quotes.
     python tools/refresh_profiles.py [tag, default r03]
 Everything is stamped with the commit it was measured on and with the hash of the device code
 (bench.py quotes `traffic` only while that hash is unchanged)."""
@@ -50,7 +50,7 @@ f4 = newest(R + "gpurun_out/%s_" % TAG + "prof4/**/*kernel_stats.csv")
 f1 = newest(R + "gpurun_out/%s_" % TAG + "prof1/**/*kernel_stats.csv")
 shutil.copy(f4, R + "profiles/%s_bench_encode_kernel_stats.csv" % TAG)
 shutil.copy(f1, R + "profiles/%s_encode_one_lane_kernel_stats.csv" % TAG)
-# the traffic file the box wrote BEFORE its default bench run (tools/make_traffic_json.py): the one the default line quotes
+# the traffic file the box wrote BEFORE its `bench.py --full` run (tools/make_traffic_json.py): the one that line quotes
 shutil.copy(R + "gpurun_out/%s_traffic.json" % TAG, R + "profiles/%s_traffic.json" % TAG)
 shutil.copy(R + "gpurun_out/%s_pmc_hbm_traffic_per_launch.csv" % TAG, R + "profiles/%s_pmc_hbm_traffic_per_launch.csv" % TAG)
 tj = json.load(open(R + "profiles/%s_traffic.json" % TAG))
@@ -105,7 +105,7 @@ json.dump(e, open(R + "profiles/%s_bench_encode_line.json" % TAG, "w"), indent=1
 box_sha = e.get("kernel_sources_sha")
 print("commit", commit, "kernel sources sha", sha, "(profiled box saw %s)" % box_sha)
 assert box_sha in (None, sha), "the profiles were taken on other device code than this checkout's"
-# the default line must quote THIS round's file, number for number, and name the kernel the kernel-trace summary names
+# the --full line must quote THIS round's file, number for number, and name the kernel the kernel-trace summary names
 rk = d["roofline"]["kernel"]
 assert d["roofline"]["traffic_from_committed_profile"]["kernel_sources_sha"] == sha
 assert d["roofline"]["rocprof_avg_launch_ms"] == tj["kernels"][rk]["rocprof_avg_launch_ms"], (d["roofline"]["rocprof_avg_launch_ms"], tj["kernels"][rk])
