@@ -89,6 +89,10 @@ _PROTOS = {
     "fqgpu_decode_block_indexed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
                                              C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "fqgpu_decode_chunk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                     C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_void_p)]),
     "fqgpu_dblock_create_from_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -332,6 +336,13 @@ class DBlock:
                                                _p(n_count), _p(n_pos), n_pos.size), "load_streams")
 
 
+class _HeaderStreams(C.Structure):
+    """fqgpu_header_streams"""
+    _fields_ = [("field_types", C.c_void_p), ("separators", C.c_char_p), ("n_fields", C.c_uint),
+                ("first_header", C.c_void_p), ("first_header_len", C.c_size_t), ("sizes", C.c_void_p),
+                ("streams", C.POINTER(C.c_void_p))]
+
+
 class Context:
     """fqgpu_ctx: the device-side equivalent of a reference Compression/DecompressionWorkspace."""
 
@@ -489,6 +500,35 @@ class Context:
                 hdr["index"].append(idx)
         return dict(rc=rc, seq=seq, qual=qual, readlens=readlens, n_count=n_count, n_pos=n_pos, raw_after=raw,
                     recs=table, used_len=used.value, n_bases=nb.value, **hdr)
+
+    def decode_chunk(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, index=None):
+        """Both decode passes on the device (fqgpu_decode_chunk): headers decoded from their field streams, the chunk
+        laid out, sequence and quality decoded.  header_format = (types, separators, first_header) and header_fields =
+        [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
+        -> dict(rc, raw, recs, laid_out_len, bad_record); bad_record is None unless the layout was refused."""
+        types, seps, first = header_format
+        types = np.ascontiguousarray(types, dtype=np.uint8)
+        first = np.frombuffer(bytes(first), dtype=np.uint8)
+        parts = [np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8)) for f in header_fields for x in f]
+        sizes = np.array([[len(x) for x in f] for f in header_fields], dtype=np.uint32).reshape(-1, 3)
+        ptrs = (C.c_void_p * max(len(parts), 1))(*[x.ctypes.data if x.size else None for x in parts])
+        hs = _HeaderStreams(types.ctypes.data, bytes(seps), len(types), first.ctypes.data, first.size,
+                            sizes.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p)))
+        readlens = np.ascontiguousarray(readlens, dtype=np.uint16)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        n_count = np.ascontiguousarray(n_count, dtype=np.uint16)
+        n_pos = np.ascontiguousarray(n_pos, dtype=np.uint16)
+        si, qi = (np.ascontiguousarray(x, dtype=np.uint8) for x in index) if index is not None else (np.zeros(0, np.uint8),) * 2
+        raw = np.zeros(raw_len, dtype=np.uint8)
+        recs = np.zeros(len(readlens), dtype=REC_DTYPE)
+        laid, bad = C.c_size_t(0), C.c_size_t(0)
+        rc = lib().fqgpu_decode_chunk(self.h, C.byref(hs), _p(readlens), len(readlens), _p(seq), seq.size, _p(qual), qual.size,
+                                      _p(n_count), n_count.size, _p(n_pos) if n_pos.size else None, n_pos.size,
+                                      _p(si) if si.size else None, si.size, _p(qi) if qi.size else None, qi.size,
+                                      _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
+        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value,
+                    bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
 
     def decode_block(self, seq, qual, n_count, n_pos, recs, raw_skeleton, index=None):
         """index = (sequence index, quality index) as encode_raw(flags=F_DECODE_INDEX) returns them:

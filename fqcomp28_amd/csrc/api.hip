@@ -530,6 +530,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   for (DevBuf *b : bufs) b->release();
   ctx->hp_parse.release();  // the device parser's scratch (fqgpu_ctx_reserve / fqgpu_encode_begin without a record table)
   ctx->hp_hdr.release();
+  ctx->hp_chunk.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1255,25 +1256,14 @@ extern "C" int fqgpu_encode_block(fqgpu_ctx *ctx, uint8_t *raw, size_t raw_len, 
                           n_pos_cap, n_pos_len);
 }
 
-static int hp_decode(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len, const uint16_t *n_count,
-                     size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out,
-                     size_t raw_len, const uint8_t *const index[2], const size_t index_len[2]) {
-  if (!ctx || !seq || !qual || !n_count || !recs || !raw_out || !seq_len || !qual_len) return FQGPU_E_ARG;
-  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;
-  int rc = use_device(ctx->device);
-  if (rc) return rc;
-  size_t n_bases = 0;
-  if ((rc = check_recs(recs, n_recs, raw_len, &n_bases))) return rc;
-  if ((rc = fqgpu_sync(ctx))) return rc;
-  fqgpu_dblock *b = nullptr;
-  const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
-  const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
-  if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
-  // raw_out holds the skeleton the first decode pass laid out (headers, newlines, '+')
-  // everything on the handle's stream (the decode kernels run there too): no host wait in between
+// The common part of the host-pointer decodes, once the staging block holds the layout: uploads the streams, decodes,
+// and copies the chunk (and the record table, recs_out != NULL) back when the kernels are through.
+static int hp_decode_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                             const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len, uint8_t *raw_out,
+                             size_t raw_len, fqgpu_rec *recs_out, const uint8_t *const index[2], const size_t index_len[2]) {
+  int rc;
+  const size_t n_recs = b->n_recs;
   hipStream_t st = ctx->stream;
-  FQ_HIP_HP(hipMemcpyAsync(b->raw, raw_out, raw_len, hipMemcpyHostToDevice, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, st));
   FQ_HIP_HP(hipMemsetAsync(b->seq + seq_len, 0, 16, st));  // the bit reader loads whole dwords
   FQ_HIP_HP(hipMemsetAsync(b->qual + qual_len, 0, 16, st));
   FQ_HIP_HP(hipMemcpyAsync(b->seq, seq, seq_len, hipMemcpyHostToDevice, st));
@@ -1300,12 +1290,36 @@ static int hp_decode(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const u
   FQ_HIP_HP(hipStreamSynchronize(st));
   FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
   FQ_HIP_HP(hipMemcpyAsync(raw_out, b->raw, raw_len, hipMemcpyDeviceToHost, st));
+  if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs, n_recs * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
   FQ_HIP_HP(hipStreamSynchronize(st));
   b->host_result = *ctx->hp_result;
   b->result_pulled = true;
   if (b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol) return FQGPU_E_ARG;
   if (b->host_result.s[0].corrupt || b->host_result.s[1].corrupt) return FQGPU_E_CORRUPT;
   return FQGPU_OK;
+}
+
+static int hp_decode(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len, const uint16_t *n_count,
+                     size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out,
+                     size_t raw_len, const uint8_t *const index[2], const size_t index_len[2]) {
+  if (!ctx || !seq || !qual || !n_count || !recs || !raw_out || !seq_len || !qual_len) return FQGPU_E_ARG;
+  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;
+  int rc = use_device(ctx->device);
+  if (rc) return rc;
+  size_t n_bases = 0;
+  if ((rc = check_recs(recs, n_recs, raw_len, &n_bases))) return rc;
+  if ((rc = fqgpu_sync(ctx))) return rc;
+  fqgpu_dblock *b = nullptr;
+  const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
+  const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
+  if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
+  // raw_out holds the skeleton the first decode pass laid out (headers, newlines, '+')
+  // everything on the handle's stream (the decode kernels run there too): no host wait in between
+  hipStream_t st = ctx->stream;
+  FQ_HIP_HP(hipMemcpyAsync(b->raw, raw_out, raw_len, hipMemcpyHostToDevice, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, st));
+  return hp_decode_streams(ctx, b, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, raw_out, raw_len, nullptr,
+                           index, index_len);
 }
 
 extern "C" int fqgpu_decode_block(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const uint8_t *qual,
@@ -1327,4 +1341,47 @@ extern "C" int fqgpu_decode_block_indexed(fqgpu_ctx *ctx, const uint8_t *seq, si
   const uint8_t *const index[2] = {seq_index, qual_index};
   const size_t index_len[2] = {seq_index_len, qual_index_len};
   return hp_decode(ctx, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, recs, n_recs, raw_out, raw_len, index, index_len);
+}
+
+// Both passes of decodeChunk on the device (decode_headers.hip, then the decode above): only the side streams go up.
+extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                  const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                  const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                  const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
+                                  uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
+  if (bad_record) *bad_record = (size_t)-1;
+  if (laid_out_len) *laid_out_len = 0;
+  if (!ctx || !hdr || !readlens || !n_recs || !seq || !qual || !n_count || !raw_out || !laid_out_len || !bad_record || !seq_len || !qual_len)
+    return FQGPU_E_ARG;
+  if ((n_pos_len && !n_pos) || (seq_index_len && !seq_index) || (qual_index_len && !qual_index)) return FQGPU_E_ARG;
+  if (raw_len >= ((size_t)1 << 32) || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  size_t n_bases = 0;
+  for (size_t r = 0; r < n_recs; r++) {
+    if (readlens[r] < 3) return FQGPU_E_SHORT_READ;  // as check_recs
+    n_bases += readlens[r];
+  }
+  if (n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
+  int rc = use_device(ctx->device);
+  if (rc) return rc;
+  if ((rc = fq_chunk_prepare(hdr, readlens, n_recs, raw_len, ctx->hp_chunk))) return rc;
+  if ((rc = fqgpu_sync(ctx))) return rc;
+  fqgpu_dblock *b = nullptr;
+  const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
+  const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
+  if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
+  unsigned long long bad = 0, total = 0;
+  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b->raw, b->recs, &bad, &total))) return hp_fail(ctx, rc);
+  // the decode kernels are never launched on a bad layout
+  if (bad != ~0ull) {
+    *bad_record = (size_t)bad;
+    return FQGPU_E_CORRUPT;
+  }
+  if (total > raw_len) return FQGPU_E_CORRUPT;  // (reported with its record above; kept as a guard)
+  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;  // (behind the layout, in the host's order)
+  *laid_out_len = (size_t)total;
+  if (total < raw_len) FQ_HIP_HP(hipMemsetAsync(b->raw + total, 0, raw_len - total, ctx->stream));
+  const uint8_t *const index[2] = {seq_index, qual_index};
+  const size_t index_len[2] = {seq_index_len, qual_index_len};
+  return hp_decode_streams(ctx, b, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, raw_out, raw_len, recs_out,
+                           index, index_len);
 }

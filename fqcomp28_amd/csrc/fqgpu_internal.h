@@ -6,6 +6,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <new>
+
 #include "../../include/fqgpu.h"
 
 #define FQ_WAVE 64
@@ -173,6 +175,46 @@ struct EncLane {
   EncScratch enc[2];
 };
 
+// Header decode and chunk layout (decode_headers.hip, fqgpu_decode_chunk): the format, the dataset's first header and
+// the offsets of every stream in ONE staging buffer (this struct first, then readlens, the first header, per field
+// flags | content | lengths, each 16-byte aligned)
+struct FqChunkField {
+  unsigned long long flags, content, lengths;  // byte offsets in the stage
+  uint32_t n_flags, n_content, n_lengths;
+  uint32_t first_off, first_len;  // this field of the dataset's first header: offset in it, length
+  int32_t first_val;              // ... its value (NUMERIC)
+  uint32_t type;                  // 0 = NUMERIC, 1 = STRING
+  uint32_t sep;                   // separator behind the field (none behind the last)
+};
+struct FqChunkFmt {
+  uint32_t n_fields, n_recs, n_tiles, pad;
+  unsigned long long raw_len, stage_len, readlens, first;  // first: offset of the first header in the stage
+  FqChunkField f[FQGPU_HDR_MAX_FIELDS];
+};
+struct FqChunkResult {
+  unsigned long long bad;    // first record the host decoder throws on (~0: none)
+  unsigned long long total;  // bytes laid out
+};
+struct ChunkScratch {
+  DevBuf stage, agg, cls, clp, hlen, tlen, toff, res, scan_tmp;
+  uint8_t *host = nullptr;  // host stage (grow-only, pageable: small copies stay out of the DMA queues' way)
+  size_t host_cap = 0, stage_len = 0;
+  unsigned n_fields = 0, n_tiles = 0;
+  bool host_grow(size_t n) {
+    if (n <= host_cap) return true;
+    delete[] host;
+    host = new (std::nothrow) uint8_t[n + n / 8];
+    host_cap = host ? n + n / 8 : 0;
+    return host != nullptr;
+  }
+  void release() {
+    for (DevBuf *b : {&stage, &agg, &cls, &clp, &hlen, &tlen, &toff, &res, &scan_tmp}) b->release();
+    delete[] host;
+    host = nullptr;
+    host_cap = 0;
+  }
+};
+
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
@@ -212,6 +254,7 @@ struct fqgpu_ctx {
   hipStream_t hp_done = nullptr;      // the stream its last kernel runs on
   size_t hp_used = 0;                 // bytes of the chunk up to its last complete record
   HdrScratch hp_hdr;                  // fqgpu_encode_headers_*: the header fields of the block in flight
+  ChunkScratch hp_chunk;              // fqgpu_decode_chunk: header decode and layout
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -297,6 +340,9 @@ size_t fq_headers_bound(size_t raw_len, size_t n_recs, size_t n_bases, unsigned 
 int fq_headers_launch(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs, size_t n_bases,
                       const uint8_t *field_types, const char *separators, unsigned n_fields, const uint8_t *first_header,
                       size_t first_header_len, HdrScratch &hs);
+int fq_chunk_prepare(const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, size_t raw_len, ChunkScratch &cs);
+int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, unsigned long long *bad,
+                    unsigned long long *total);
 int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, ParseScratch &ps, fqgpu_rec *recs_dev,
                      size_t n_recs, size_t *n_bases, size_t *n_n, size_t *used_len);
 

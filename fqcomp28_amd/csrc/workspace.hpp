@@ -21,6 +21,8 @@
 // fqgpu_strerror().  Header-only; link with libfqgpu.so.
 #pragma once
 
+#include <algorithm>
+
 #include <chrono>
 #include <cstddef>
 #include <cstdio>
@@ -467,9 +469,14 @@ public:
   explicit DecompressionWorkspace(const DatasetMeta *meta, int device = 0) : Workspace(meta, device) {}
 
   /** Both passes of decodeChunk (src/workspace.cpp:47-88): the first lays the chunk out
-   *  (headers decoded on the host, lengths from readlens, '+' and newlines), the second fills the
-   *  sequence and quality lines on the GPU */
+   *  (headers decoded, lengths from readlens, '+' and newlines), the second fills the sequence and quality lines.
+   *  Both run on the GPU (fqgpu_decode_chunk: only the side streams go up, no skeleton).  FQGPU_SHIM_HOST_HEADERS=1
+   *  keeps the host layout (headers.hpp) in front of fqgpu_decode_block_indexed; a chunk the device refuses (a header
+   *  stream that runs out, a chunk too small for its records, a format it does not take) goes through the host path
+   *  as well, so that the error is the host's. */
   void decodeChunk(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
+    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
+    if (!host_headers && decodeChunkOnDevice(chunk, cbs)) return;
     StageClock clk;
     chunk.clear();  // prepareFastqChunk (src/workspace.h:127-133)
     chunk.idx = cbs.chunk_idx;
@@ -537,6 +544,66 @@ public:
   }
 
 private:
+  /** decodeChunk through fqgpu_decode_chunk; false: the device refused the chunk (the host path decides) */
+  bool decodeChunkOnDevice(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
+    StageClock clk;
+    chunk.clear();
+    chunk.idx = cbs.chunk_idx;
+    if (chunk.raw_data.capacity() < cbs.original_size.total) chunk.raw_data.reserve(cbs.original_size.total + cbs.original_size.total / 16 + 4096);
+    chunk.raw_data.resize(cbs.original_size.total);
+    clk.lap("resize");
+    decompressMiscBuffers(cbs);
+    clk.lap("misc");
+    const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
+    if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
+    std::vector<fqgpu_field_sizes> sizes(nf);
+    std::vector<const uint8_t *> streams(3 * nf);
+    for (std::size_t i = 0; i < nf; ++i) {
+      const auto &f = cbs.header_fields[i];
+      sizes[i] = {static_cast<uint32_t>(f.isDifferentFlag.size()), static_cast<uint32_t>(f.content.size()),
+                  static_cast<uint32_t>(f.contentLength.size())};
+      streams[3 * i] = reinterpret_cast<const uint8_t *>(f.isDifferentFlag.data());
+      streams[3 * i + 1] = reinterpret_cast<const uint8_t *>(f.content.data());
+      streams[3 * i + 2] = reinterpret_cast<const uint8_t *>(f.contentLength.data());
+    }
+    const fqgpu_header_streams hdr{field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(nf),
+                                   reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size(),
+                                   sizes.data(), streams.data()};
+    RecordTable recs(n);
+    std::size_t laid_out = 0, bad = 0;
+    const int rc = fqgpu_decode_chunk(ctx_, &hdr, reinterpret_cast<const uint16_t *>(cbs.readlens.data()), n,
+                                      reinterpret_cast<const uint8_t *>(cbs.seq.data()), cbs.seq.size(),
+                                      reinterpret_cast<const uint8_t *>(cbs.qual.data()), cbs.qual.size(),
+                                      reinterpret_cast<const uint16_t *>(cbs.n_count.data()), cbs.index.n_count / sizeof(uint16_t),
+                                      reinterpret_cast<const uint16_t *>(cbs.n_pos.data()), cbs.index.n_pos / sizeof(uint16_t),
+                                      reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), cbs.decode_index[0].size(),
+                                      reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data()), cbs.decode_index[1].size(),
+                                      reinterpret_cast<uint8_t *>(chunk.raw_data.data()), chunk.raw_data.size(), recs.data(),
+                                      &laid_out, &bad);
+    clk.lap("gpu");
+    // a damaged sequence / quality stream (no record named) or a runtime failure: the host path would end the same way
+    if ((rc == FQGPU_E_CORRUPT && bad == static_cast<std::size_t>(-1)) || rc == FQGPU_E_HIP || rc == FQGPU_E_NOMEM ||
+        rc == FQGPU_E_NO_DEVICE)
+      fqgpuCheck(rc, "decodeChunk");
+    if (rc != FQGPU_OK) return false;
+    // the stream cursors where the host decoder leaves them: every stream consumed up to the chunk's last header
+    for (std::size_t i = 0; i < nf; ++i) {
+      auto &f = cbs.header_fields[i];
+      f.index = {};
+      if (fmt_.field_types[i] == headers::FieldType::NUMERIC) {
+        f.index.contentPos = n * sizeof(headers::numeric_t);
+        continue;
+      }
+      f.index.isDifferentPos = n;
+      f.index.contentLengthPos = n - static_cast<std::size_t>(std::count(f.isDifferentFlag.begin(), f.isDifferentFlag.begin() + n, std::byte{0}));
+      for (std::size_t j = 0; j < f.index.contentLengthPos; ++j) f.index.contentPos += static_cast<unsigned char>(f.contentLength[j]);
+    }
+    CompressionWorkspace::recordViews(chunk, recs);
+    clk.lap("table");
+    clk.done(chunk.idx);
+    return true;
+  }
+
   /** decodeHeader with the output bound checked: near the end of the chunk the header goes through
    *  a local buffer, since the field decoders may write up to FIELDLEN_MAX bytes per field */
   unsigned decodeHeaderChecked(char *dst, char *end, CompressedBuffersSrc &cbs) {

@@ -304,6 +304,35 @@ size_t fqgpu_synth_fastq(uint8_t *dst, size_t cap, int mode, uint64_t seed, uint
                          uint64_t *n_reads_out);
 
 
+/* ---- chunk decode: both passes of DecompressionWorkspace::decodeChunk (src/workspace.cpp:47-88) on the device.
+ * The read headers are decoded from their field streams (decodeHeader, src/workspace.cpp:128-157), the chunk is laid
+ * out (header, '\n', sequence, "\n+\n", quality, '\n' per record; zeros behind the last record up to raw_len), the
+ * record table is built and the sequence and quality lines are decoded: no skeleton goes up.
+ * hdr: the format as fqgpu_encode_headers_begin takes it, the dataset's first header ('@' included), and per field
+ * its three streams (isDifferentFlag, content, contentLength: streams[3 i .. 3 i + 2]) with their sizes.
+ * recs_out (may be NULL) receives the record table; *laid_out_len the bytes up to the end of the last record.
+ * Returns
+ *   FQGPU_E_CORRUPT with *bad_record = the first record whose header the host decoder throws out_of_range on (a stream
+ *                   exhausted, or the record ending behind raw_len); raw_out is not written
+ *   FQGPU_E_CORRUPT with *bad_record = (size_t)-1: a damaged sequence / quality stream, as fqgpu_decode_block
+ *   FQGPU_E_ARG     n_fields 0 or above FQGPU_HDR_MAX_FIELDS, raw_len >= 2^32, no records, a NULL where data is
+ *                   required, a first header the host coder does not take
+ * seq_index / qual_index: as fqgpu_decode_block_indexed (NULL / 0: none). */
+typedef struct {
+  const uint8_t *field_types;  /* n_fields: 0 = NUMERIC, 1 = STRING */
+  const char *separators;      /* n_fields - 1 */
+  unsigned n_fields;
+  const uint8_t *first_header;
+  size_t first_header_len;
+  const fqgpu_field_sizes *sizes;  /* n_fields */
+  const uint8_t *const *streams;   /* 3 n_fields */
+} fqgpu_header_streams;
+int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                       const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                       const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                       const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
+                       uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

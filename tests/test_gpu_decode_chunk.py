@@ -1,0 +1,394 @@
+"""Header decode and chunk layout on the device (fqgpu_decode_chunk, fqcomp28_amd/csrc/decode_headers.hip): both passes
+of DecompressionWorkspace::decodeChunk without a skeleton upload.  Checked against the input chunk (encode_raw ->
+decode_chunk), against oracle/headers_oracle.py (field streams coded on the CPU) and against `restate`, a Python
+restatement of the host layout (workspace.hpp decodeChunk over headers.hpp decodeHeader) that raises where the host
+throws out_of_range; and end to end through fqc_tool on both shim paths."""
+import os
+import struct
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import oracle_lib as O
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import fqc_archive as A  # noqa: E402
+import headers_oracle as HO  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+
+E_CORRUPT, E_ARG = -3, -4
+FIXTURES = ["SRR065390_sub_1", "without_ns", "SRR065390_sub_2", "SRR065390_1_first5"]
+
+
+class Refused(Exception):
+    def __init__(self, record):
+        super().__init__(record)
+        self.record = record
+
+
+def restate(first_header, fields, reads, raw_len):
+    """the host's decodeChunk layout: -> (chunk bytes, record table) or Refused(first failing record).
+    fields = [(flags, content, lengths)], reads = [(sequence, quality)]"""
+    types, seps = HO.format_from_header(first_header)
+    prev = [HO.parse_numeric(f) if t == HO.NUMERIC else f for f, t in zip(HO.split_header(first_header, seps), types)]
+    cur = [[0, 0, 0] for _ in types]
+    out, recs = bytearray(), []
+    for r, (seq, qual) in enumerate(reads):
+        h = bytearray(b"@")
+        for i, t in enumerate(types):
+            flags, content, lengths = (bytes(x) for x in fields[i])
+            c = cur[i]
+            if t == HO.NUMERIC:
+                if c[1] + 4 > len(content):
+                    raise Refused(r)
+                (d,) = struct.unpack_from("<I", content, c[1]); c[1] += 4
+                v = (prev[i] + d) & 0xFFFFFFFF
+                prev[i] = v - (1 << 32) if v >= 1 << 31 else v
+                h += str(prev[i]).encode()
+            else:
+                if c[0] >= len(flags):
+                    raise Refused(r)
+                flag = flags[c[0]]; c[0] += 1
+                if flag:
+                    if c[2] >= len(lengths):
+                        raise Refused(r)
+                    ln = lengths[c[2]]; c[2] += 1
+                    if c[1] + ln > len(content):
+                        raise Refused(r)
+                    prev[i] = content[c[1]: c[1] + ln]; c[1] += ln
+                h += prev[i]
+            if i + 1 < len(types):
+                h.append(seps[i])
+        if len(out) + len(h) + 2 * len(seq) + 5 > raw_len:
+            raise Refused(r)
+        out += h + b"\n"
+        s_off = len(out)
+        out += seq + b"\n+\n"
+        q_off = len(out)
+        out += qual + b"\n"
+        recs.append((s_off, q_off, len(seq)))
+    return bytes(out) + bytes(raw_len - len(out)), recs
+
+
+def reads_of(raw, recs):
+    b = raw.tobytes()
+    return [(b[int(r["seq_off"]): int(r["seq_off"]) + int(r["len"])], b[int(r["qual_off"]): int(r["qual_off"]) + int(r["len"])])
+            for r in recs]
+
+
+def fmt_of(first_header):
+    types, seps = HO.format_from_header(first_header)
+    return ([0 if t == HO.NUMERIC else 1 for t in types], bytes(seps), first_header)
+
+
+@pytest.fixture(scope="module")
+def F():
+    import fqcomp28_amd as F
+    assert F.device_count() >= 1, "no GPU visible: the product path has no CPU fallback"
+    return F
+
+
+def encode(F, ctx, raw, first_header, index):
+    g = ctx.encode_raw(raw, flags=F.F_DECODE_INDEX if index else 0, header_format=fmt_of(first_header))
+    assert g["rc"] == 0 and g["headers_rc"] == 0, g.get("rc")
+    return g
+
+
+def decode(ctx, g, first_header, fields=None, raw_len=None, readlens=None):
+    return ctx.decode_chunk(fmt_of(first_header), g["header_fields"] if fields is None else fields,
+                            g["readlens"] if readlens is None else readlens, g["seq"], g["qual"], g["n_count"], g["n_pos"],
+                            g["used_len"] if raw_len is None else raw_len, index=g.get("index"))
+
+
+def round_trip(F, ctx, raw, first_header, index):
+    g = encode(F, ctx, raw, first_header, index)
+    d = decode(ctx, g, first_header)
+    assert d["rc"] == 0 and d["bad_record"] is None, (d["rc"], d["bad_record"])
+    assert d["laid_out_len"] == raw.size
+    assert np.array_equal(d["raw"], raw), int(np.argmax(d["raw"] != raw))
+    assert np.array_equal(d["recs"], F.parse_fastq(raw))
+    return g
+
+
+@pytest.mark.parametrize("name", FIXTURES)
+@pytest.mark.parametrize("index", [False, True])
+def test_round_trip_golden_fixtures(F, golden_dir, name, index):
+    raw, recs = O.load_fastq(os.path.join(golden_dir, name + ".fastq"))
+    _, _, sft, qft = O.freq_tables(raw, recs)
+    ctx = F.Context(sft, qft)
+    try:
+        round_trip(F, ctx, raw, A.headers_of(raw, recs[:1])[0], index)
+    finally:
+        ctx.close()
+
+
+def test_first_header_of_the_dataset_is_not_the_chunks_first(F, golden_dir):
+    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_sub_2.fastq"))
+    _, _, sft, qft = O.freq_tables(raw, recs)
+    first = b"@SRR065390.1 HWUSI-EAS687_61DAJ:1:1:1055:3384 length=100"
+    ctx = F.Context(sft, qft)
+    try:
+        for index in (False, True):
+            round_trip(F, ctx, raw, first, index)
+    finally:
+        ctx.close()
+
+
+def synth_ctx(F, raw):
+    recs = F.parse_fastq(raw)
+    sft, qft = F.freq_tables(raw, recs)
+    return F.Context(sft, qft), recs
+
+
+@pytest.mark.parametrize("mode", [1, 2, 3, 4, 5, 6])
+def test_round_trip_synth_32mib(F, mode):
+    raw, _ = F.synth_fastq(32 << 20, mode, seed=40 + mode)
+    ctx, recs = synth_ctx(F, raw)
+    try:
+        round_trip(F, ctx, raw, A.headers_of(raw, recs[:1])[0], index=mode % 2 == 0)
+    finally:
+        ctx.close()
+
+
+def test_round_trip_one_256mib_block(F):
+    raw, _ = F.synth_fastq(256 << 20, 2, seed=7)
+    ctx, recs = synth_ctx(F, raw)
+    try:
+        round_trip(F, ctx, raw, A.headers_of(raw, recs[:1])[0], index=True)
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------- field streams from the CPU oracle
+@pytest.fixture(scope="module")
+def gctx(F, golden_dir):
+    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_sub_1.fastq"))
+    _, _, sft, qft = O.freq_tables(raw, recs)
+    c = F.Context(sft, qft)
+    c.golden_reads = reads_of(raw, recs)
+    yield c
+    c.close()
+
+
+def chunk_of(reads, headers):
+    return np.frombuffer(b"".join(h + b"\n" + reads[i % len(reads)][0] + b"\n+\n" + reads[i % len(reads)][1] + b"\n"
+                                  for i, h in enumerate(headers)), dtype=np.uint8)
+
+
+def check_against_oracle(F, ctx, headers, first_header):
+    """the reads go through the GPU encode; the header fields come from the CPU oracle"""
+    reads = [ctx.golden_reads[i % len(ctx.golden_reads)] for i in range(len(headers))]
+    raw = chunk_of(ctx.golden_reads, headers)
+    g = ctx.encode_raw(raw)
+    assert g["rc"] == 0
+    types, _, streams = HO.encode_headers(headers, first_header)
+    fields = [(bytes(s.flags), bytes(s.content), bytes(s.lengths)) for s in streams]
+    decoded = HO.decode_headers(len(headers), first_header, streams)
+    want, want_recs = restate(first_header, fields, reads, sum(len(h) for h in decoded) + sum(2 * len(s) + 5 for s, _ in reads))
+    d = decode(ctx, g, first_header, fields=fields, raw_len=len(want))
+    assert d["rc"] == 0, (d["rc"], d["bad_record"])
+    got = d["raw"].tobytes()
+    assert got == want
+    assert A.headers_of(d["raw"], d["recs"]) == decoded
+    assert [tuple(int(x) for x in r) for r in d["recs"]] == [tuple(int(x) for x in r) for r in want_recs]
+
+
+def test_oracle_strings_numbers_wrapping_missing_fields(F, gctx):
+    rng = np.random.default_rng(11)
+    names = [b"EAS687", b"EAS688", b"TIOBDUREN", b"B", b"", b"x" * 254, b"y" * 100, b"-lead"]
+    nums = [b"5", b"4", b"2147483647", b"-2147483648", b"0", b"33808546", b"-7", b"12ab", b"007", b"-0"]
+    hdrs = [b"@EAS687.1 5 length=50/1"]
+    for i in range(2999):
+        a = names[int(rng.integers(len(names)))] if rng.random() < 0.3 else hdrs[-1][1:].split(b".")[0]
+        b = nums[int(rng.integers(len(nums)))] if rng.random() < 0.5 else b"%d" % int(rng.integers(0, 2**31))
+        c = b"length" if rng.random() < 0.9 else b"len"
+        h = b"@%s.%d %s %s=%d/%d" % (a, i + 2, b, c, 50 + i % 251, 1 + i % 2)
+        if i % 97 == 0:
+            h = h[: int(rng.integers(2, len(h)))]
+            if not h[-1:].isdigit():
+                h = b"@q.1 2 z=3/4"
+        try:  # (a cut header whose numeric field ended up empty cannot be coded)
+            HO.encode_headers([h], hdrs[0])
+        except ValueError:
+            continue
+        hdrs.append(h)
+    check_against_oracle(F, gctx, hdrs, b"@EAS687.1 5 length=50/1")
+
+
+def test_oracle_one_field_and_sixty_four_fields(F, gctx):
+    check_against_oracle(F, gctx, [b"@%d" % (i * 7919 % 1000 - 500) for i in range(700)], b"@12")
+    first = b"@" + b":".join(b"f%d" % k if k % 2 else b"%d" % k for k in range(64))
+    hdrs = []
+    for i in range(600):
+        hdrs.append(b"@" + b":".join((b"f%d" % (k + (i // 3 if k % 4 == 1 else 0))) if k % 2 else b"%d" % (k * i - 300)
+                                     for k in range(64)))
+    assert len(HO.format_from_header(first)[0]) == 64
+    check_against_oracle(F, gctx, hdrs, first)
+
+
+def test_oracle_every_value_new_and_every_value_same(F, gctx):
+    first = b"@A.1 x"
+    check_against_oracle(F, gctx, [b"@A.1 x"] * 1500, first)  # nothing new: the first header all the way
+    check_against_oracle(F, gctx, [b"@%s.%d %s" % (b"Q" * (1 + i % 254), i, b"z" * (i % 7 + 1)) for i in range(1500)], first)
+
+
+# ---------------------------------------------------------------- damaged streams
+def damaged_cases(fields, types):
+    s = next(i for i, t in enumerate(types) if t == 1)
+    n = next(i for i, t in enumerate(types) if t == 0)
+
+    def with_field(i, k, val):
+        out = [list(f) for f in fields]
+        out[i][k] = val
+        return [tuple(f) for f in out]
+
+    fl, co, le = fields[s]
+    ones = [k for k, x in enumerate(fl) if x]
+    yield "flags short", with_field(s, 0, fl[:-1])
+    yield "lengths short", with_field(s, 2, le[:-1])
+    yield "content short", with_field(s, 1, co[:-1])
+    yield "numeric content short", with_field(n, 1, fields[n][1][:-4])
+    yield "numeric content one byte short", with_field(n, 1, fields[n][1][:-1])
+    f2 = bytearray(fl)
+    for k in ones[::2]:
+        f2[k] = 2
+    for k in ones[1::2]:
+        f2[k] = 0xFF
+    yield "flag bytes 2 and 0xFF", with_field(s, 0, bytes(f2))
+    f3 = bytearray(fl)
+    f3[len(f3) // 2] = 1 if f3[len(f3) // 2] == 0 else 0
+    yield "a flag flipped", with_field(s, 0, bytes(f3))
+
+
+def test_damaged_streams_agree_with_the_host_and_leave_the_handle_usable(F, golden_dir):
+    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_sub_1.fastq"))
+    _, _, sft, qft = O.freq_tables(raw, recs)
+    ctx = F.Context(sft, qft)
+    try:
+        first = A.headers_of(raw, recs[:1])[0]
+        types = fmt_of(first)[0]
+        g = encode(F, ctx, raw, first, index=False)
+        fields = [tuple(x.tobytes() for x in f) for f in g["header_fields"]]
+        reads = reads_of(raw, recs)
+        seen_refusal = seen_accept = False
+        for what, bad_fields in damaged_cases(fields, types):
+            try:
+                want, _ = restate(first, bad_fields, reads, raw.size)
+            except Refused as e:
+                want = e
+            d = decode(ctx, g, first, fields=bad_fields)
+            if isinstance(want, Refused):
+                seen_refusal = True
+                assert (d["rc"], d["bad_record"]) == (E_CORRUPT, want.record), what
+                assert not d["raw"].any(), what  # nothing written on a refusal
+            else:
+                seen_accept = True
+                assert d["rc"] == 0 and d["bad_record"] is None, (what, d["rc"])
+                assert d["raw"].tobytes() == want, what
+            round_trip(F, ctx, raw, first, index=False)  # the handle decodes a good block right afterwards
+        assert seen_refusal and seen_accept
+        # raw_len one byte too small: the last record does not fit
+        d = decode(ctx, g, first, raw_len=raw.size - 1)
+        assert (d["rc"], d["bad_record"]) == (E_CORRUPT, len(recs) - 1)
+        with pytest.raises(Refused):
+            restate(first, fields, reads, raw.size - 1)
+        # far too small: the first record already
+        d = decode(ctx, g, first, raw_len=10)
+        assert (d["rc"], d["bad_record"]) == (E_CORRUPT, 0)
+        # larger than needed: accepted, zero tail, exact laid-out length
+        d = decode(ctx, g, first, raw_len=raw.size + 1000)
+        assert d["rc"] == 0 and d["laid_out_len"] == raw.size
+        assert np.array_equal(d["raw"][: raw.size], raw) and not d["raw"][raw.size:].any()
+        # 65 fields / no fields: a format the call does not take
+        many = b"@" + b":".join(b"%d" % k for k in range(65))
+        d = ctx.decode_chunk(fmt_of(many), [(b"", b"\0" * 4 * len(recs), b"")] * 65, g["readlens"], g["seq"], g["qual"],
+                             g["n_count"], g["n_pos"], raw.size)
+        assert d["rc"] == E_ARG and d["bad_record"] is None
+        d = ctx.decode_chunk(([], b"", b"@"), [], g["readlens"], g["seq"], g["qual"], g["n_count"], g["n_pos"], raw.size)
+        assert d["rc"] == E_ARG
+        # a damaged quality stream: FQGPU_E_CORRUPT without a record
+        q = g["qual"].copy()
+        q[q.size // 2] ^= 0x10
+        d = ctx.decode_chunk(fmt_of(first), g["header_fields"], g["readlens"], g["seq"], q, g["n_count"], g["n_pos"], raw.size)
+        assert d["rc"] != 0 and d["bad_record"] is None
+        round_trip(F, ctx, raw, first, index=False)
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------- through the farm
+@pytest.fixture(scope="module")
+def tool(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("farm") / "fqc_tool")
+    subprocess.run(["g++", "-std=c++17", "-O2", "-Wall", "-o", exe, os.path.join(ROOT, "tools", "fqc_tool.cpp"),
+                    "-L" + os.path.join(ROOT, "fqcomp28_amd"), "-lfqgpu", "-Wl,-rpath," + os.path.join(ROOT, "fqcomp28_amd"),
+                    "-lpthread"], check=True)
+    return exe
+
+
+def tool_run(tool, args, host_headers):
+    env = dict(os.environ)
+    env.pop("FQGPU_SHIM_HOST_HEADERS", None)
+    if host_headers:
+        env["FQGPU_SHIM_HOST_HEADERS"] = "1"
+    return subprocess.run([tool] + [str(a) for a in args], capture_output=True, text=True, timeout=600, env=env)
+
+
+def test_farm_restores_on_both_paths(F, tool, tmp_path):
+    raw, _ = F.synth_fastq(12 << 20, 4, seed=5)
+    src = tmp_path / "in.fastq"
+    raw.tofile(src)
+    for index in (False, True):
+        arc = tmp_path / ("i.fqc" if index else "p.fqc")
+        r = tool_run(tool, ["c", src, arc, "-t", 2, "-R", 2, "-S", 2] + (["--index"] if index else []), False)
+        assert r.returncode == 0, r.stderr
+        for host in (False, True):
+            back = tmp_path / "back.fastq"
+            r = tool_run(tool, ["d", arc, back, "-t", 3], host)
+            assert r.returncode == 0, (index, host, r.stderr)
+            assert open(back, "rb").read() == raw.tobytes(), (index, host)
+            os.remove(back)
+
+
+def test_farm_restores_an_oracle_written_archive(F, tool, tmp_path, golden_dir):
+    import test_archive as TA
+    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_sub_1.fastq"))
+    arc = tmp_path / "o.fqc"
+    TA.oracle_archive(F, str(arc), raw, recs, 3)
+    for host in (False, True):
+        back = tmp_path / "back.fastq"
+        r = tool_run(tool, ["d", arc, back, "-t", 2], host)
+        assert r.returncode == 0, (host, r.stderr)
+        assert open(back, "rb").read() == raw.tobytes()
+        os.remove(back)
+
+
+def test_farm_inconsistent_header_streams_fail_alike_on_both_paths(F, tool, tmp_path, golden_dir):
+    import test_archive as TA
+    raw, recs = O.load_fastq(os.path.join(golden_dir, "SRR065390_sub_1.fastq"))
+    arc = tmp_path / "ok.fqc"
+    parts, encs, blocks, (sft, qft) = TA.oracle_archive(F, str(arc), raw, recs, 3)
+    comp = lambda d: F.memcompress(np.frombuffer(d, dtype=np.uint8)).tobytes()  # noqa: E731
+    first = A.headers_of(raw, recs[:1])[0]
+    types = fmt_of(first)[0]
+    braw, brecs = parts[1]
+    _, _, streams = HO.encode_headers(A.headers_of(braw, brecs), first)
+    s = next(i for i, t in enumerate(types) if t == 1)
+    flags = bytes(streams[s].flags)[:-1]  # valid misc stream, one flag short
+    blocks[1].fields[s][0] = (len(flags), comp(flags))
+    bad = tmp_path / "bad.fqc"
+    A.write_archive(str(bad), first, sft.tobytes(), qft.tobytes(), blocks)
+    errs = []
+    for host in (False, True):
+        out = tmp_path / "bad.fastq"
+        r = tool_run(tool, ["d", bad, out, "-t", 2], host)
+        assert r.returncode == 1, (host, r.stdout, r.stderr)
+        line = [x for x in r.stderr.splitlines() if x.startswith("fqc_tool:")]
+        assert line, r.stderr
+        errs.append(line[-1])
+        assert not os.path.exists(out) and not os.path.exists(str(out) + ".part")
+    assert errs[0] == errs[1]
