@@ -93,6 +93,11 @@ _PROTOS = {
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fqgpu_decode_chunk_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p,
+                                           C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_void_p)]),
     "fqgpu_dblock_create_from_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -528,6 +533,51 @@ class Context:
                                       _p(si) if si.size else None, si.size, _p(qi) if qi.size else None, qi.size,
                                       _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
         return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value,
+                    bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
+
+    def decode_chunk_range(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, first, end,
+                           index=None, out_cap=None):
+        """Records [first, end) of a chunk (fqgpu_decode_chunk_range), arguments as decode_chunk.  out_cap None: a buffer
+        of the range's size (asked for first); 0: the size query alone (raw is None).  -> dict(rc, raw, recs, out_len,
+        bad_record); raw holds out_len bytes on success, recs the range's records relative to raw."""
+        types, seps, first_hdr = header_format
+        types = np.ascontiguousarray(types, dtype=np.uint8)
+        first_hdr = np.frombuffer(bytes(first_hdr), dtype=np.uint8)
+        parts = [np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8)) for f in header_fields for x in f]
+        sizes = np.array([[len(x) for x in f] for f in header_fields], dtype=np.uint32).reshape(-1, 3)
+        ptrs = (C.c_void_p * max(len(parts), 1))(*[x.ctypes.data if x.size else None for x in parts])
+        hs = _HeaderStreams(types.ctypes.data, bytes(seps), len(types), first_hdr.ctypes.data, first_hdr.size,
+                            sizes.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p)))
+        readlens = np.ascontiguousarray(readlens, dtype=np.uint16)
+        seq = np.ascontiguousarray(seq, dtype=np.uint8)
+        qual = np.ascontiguousarray(qual, dtype=np.uint8)
+        n_count = np.ascontiguousarray(n_count, dtype=np.uint16)
+        n_pos = np.ascontiguousarray(n_pos, dtype=np.uint16)
+        si, qi = (np.ascontiguousarray(x, dtype=np.uint8) for x in index) if index is not None else (np.zeros(0, np.uint8),) * 2
+        olen, bad = C.c_size_t(0), C.c_size_t(0)
+
+        def call(out, cap, recs):
+            return lib().fqgpu_decode_chunk_range(
+                self.h, C.byref(hs), _p(readlens), len(readlens), _p(seq), seq.size, _p(qual), qual.size, _p(n_count),
+                n_count.size, _p(n_pos) if n_pos.size else None, n_pos.size, _p(si) if si.size else None, si.size,
+                _p(qi) if qi.size else None, qi.size, raw_len, first, end, _p(out) if out is not None else None, cap,
+                C.byref(olen), _p(recs) if recs is not None else None, C.byref(bad))
+
+        n_out = max(end - first, 0)
+        if out_cap is None:
+            rc = call(None, 0, None)
+            if rc != 0:
+                return dict(rc=rc, raw=None, recs=None, out_len=olen.value,
+                            bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
+            out_cap = olen.value
+        raw = recs = None
+        if out_cap:
+            raw = np.zeros(out_cap, dtype=np.uint8)
+            recs = np.zeros(n_out, dtype=REC_DTYPE)
+        rc = call(raw, out_cap, recs)
+        if raw is not None and rc == 0:
+            raw = raw[:olen.value]
+        return dict(rc=rc, raw=raw, recs=recs, out_len=olen.value,
                     bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
 
     def decode_block(self, seq, qual, n_count, n_pos, recs, raw_skeleton, index=None):

@@ -2,6 +2,7 @@
 // kernels of tables.hip / encode.hip / decode.hip.  Host code only.
 #include "fqgpu_internal.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -600,15 +601,23 @@ extern "C" int fqgpu_dblock_fetch_index(fqgpu_ctx *ctx, const fqgpu_dblock *b, i
 // an index for this block's stream: its header must describe the block; room for it on the device.  (The decode checks
 // that every stride consumes exactly the bits between two snapshots; the states in a snapshot are taken as they are:
 // a container that stores an index protects it with a checksum -- archive.hpp's DecodeIndexFile does.)
-static int index_accept(fqgpu_dblock *b, int stream, const void *data, size_t len) {
+// the header of a decode index of a block of n_bases symbols, if it describes the index's size
+static int index_header(int stream, size_t n_bases, const void *data, size_t len, FqIndexHeader *out) {
   const unsigned B = stream ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS;
   FqIndexHeader h;
   if (len < sizeof(h)) return FQGPU_E_CORRUPT;
   memcpy(&h, data, sizeof(h));
   if (h.magic != FQ_INDEX_MAGIC || h.stream != (uint32_t)stream || h.stride == 0 || (h.stride & 65535u) ||
-      h.n_sym != b->n_bases || h.n_snap != (h.n_sym ? (uint32_t)((h.n_sym - 1) / h.stride) : 0u) ||
+      h.n_sym != n_bases || h.n_snap != (h.n_sym ? (uint32_t)((h.n_sym - 1) / h.stride) : 0u) ||
       len != sizeof(h) + (size_t)h.n_snap * fq_index_snap_bytes(B))
     return FQGPU_E_CORRUPT;
+  if (out) *out = h;
+  return FQGPU_OK;
+}
+
+static int index_accept(fqgpu_dblock *b, int stream, const void *data, size_t len) {
+  const int rc = index_header(stream, b->n_bases, data, len, nullptr);
+  if (rc) return rc;
   if (len > b->index_cap[stream]) {
     if (b->index[stream]) (void)hipFree(b->index[stream]);
     b->index[stream] = fq_dev_alloc<uint8_t>(len + 64);
@@ -1384,4 +1393,136 @@ extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hd
   const size_t index_len[2] = {seq_index_len, qual_index_len};
   return hp_decode_streams(ctx, b, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, raw_out, raw_len, recs_out,
                            index, index_len);
+}
+
+// fqgpu_decode_chunk_range's plan for the records [first, end) of a chunk.  rs: rec_start (n + 1 entries, strictly
+// increasing: every read has 3 bases or more).  With both decode indexes (ix != NULL, each with a snapshot) stream s
+// decodes its strides k_lo[s] .. k_hi[s] -- the ones that hold a symbol of [rs[first], rs[end]), the rule of
+// fq_decode_launch -- and [w0, w1) are the records those strides write to: a stride of encode indices [e_lo, e_hi) walks
+// from the record of symbol e_hi - 1 down to the record of symbol e_lo.  Without, the window is the whole chunk.
+struct RangePlan {
+  bool indexed;
+  unsigned k_lo[2], k_hi[2];
+  size_t w0, w1;
+};
+static RangePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t end, const FqIndexHeader *ix) {
+  RangePlan p = {false, {0, 0}, {0, 0}, 0, n};
+  if (!ix || !ix[0].n_snap || !ix[1].n_snap) return p;
+  const auto record_of = [&](uint64_t e) { return (size_t)(std::upper_bound(rs, rs + n, (uint32_t)e) - rs) - 1; };
+  const uint64_t s0 = rs[first], s1 = rs[end];
+  uint64_t lo = s0, hi = s1;
+  for (int s = 0; s < 2; s++) {
+    const uint64_t stride = ix[s].stride;
+    p.k_lo[s] = (unsigned)(s0 / stride);
+    p.k_hi[s] = (unsigned)((s1 - 1) / stride);
+    lo = std::min(lo, p.k_lo[s] * stride);
+    hi = std::max(hi, std::min<uint64_t>((p.k_hi[s] + 1) * stride, ix[s].n_sym));
+  }
+  p.indexed = true;
+  p.w0 = record_of(lo);
+  p.w1 = record_of(hi - 1) + 1;
+  return p;
+}
+
+// Records [first, end) of a chunk (include/fqgpu.h): the layout passes of fqgpu_decode_chunk over the whole chunk, the
+// write pass for a window of records, the walk over the strides that hold the range (or over the whole streams), the
+// N pass for the window, and the range's bytes and record table back.
+extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                        const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                        const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                        const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index,
+                                        size_t qual_index_len, size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap,
+                                        size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
+  if (bad_record) *bad_record = (size_t)-1;
+  if (out_len) *out_len = 0;
+  if (!ctx || !hdr || !readlens || !n_recs || !seq || !qual || !n_count || !out_len || !bad_record || !seq_len || !qual_len)
+    return FQGPU_E_ARG;
+  if ((n_pos_len && !n_pos) || (seq_index_len && !seq_index) || (qual_index_len && !qual_index)) return FQGPU_E_ARG;
+  if (raw_len >= ((size_t)1 << 32) || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  if (first >= end || end > n_recs) return FQGPU_E_ARG;
+  std::vector<uint32_t> rs(n_recs + 1);
+  size_t n_bases = 0;
+  for (size_t r = 0; r < n_recs; r++) {
+    if (readlens[r] < 3) return FQGPU_E_SHORT_READ;  // as check_recs
+    rs[r] = (uint32_t)n_bases;
+    n_bases += readlens[r];
+  }
+  if (n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
+  rs[n_recs] = (uint32_t)n_bases;
+  int rc = use_device(ctx->device);
+  if (rc) return rc;
+  // (a damaged index is reported as fqgpu_decode_chunk reports it: behind the layout's verdict)
+  FqIndexHeader ix[2];
+  const uint8_t *const index[2] = {seq_index, qual_index};
+  const size_t index_len[2] = {seq_index_len, qual_index_len};
+  int index_rc = FQGPU_OK;
+  for (int s = 0; s < 2; s++)
+    if (index_len[s] && (rc = index_header(s, n_bases, index[s], index_len[s], &ix[s])) && !index_rc) index_rc = rc;
+  const bool both = !index_rc && seq_index_len && qual_index_len;
+  const RangePlan plan = range_plan(rs.data(), n_recs, first, end, both ? ix : nullptr);
+  if ((rc = fq_chunk_prepare(hdr, readlens, n_recs, raw_len, ctx->hp_chunk))) return rc;
+  if ((rc = fqgpu_sync(ctx))) return rc;
+  fqgpu_dblock *b = nullptr;
+  if (out) {
+    const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
+    const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
+    if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
+  }
+  const unsigned q[4] = {(unsigned)plan.w0, (unsigned)first, (unsigned)end, (unsigned)plan.w1};
+  unsigned long long bad = 0, total = 0, at[4];
+  if ((rc = fq_chunk_layout_range(ctx->stream, ctx->hp_chunk, b ? b->raw : nullptr, b ? b->recs : nullptr, q, b != nullptr, &bad,
+                                  &total, at)))
+    return hp_fail(ctx, rc);
+  if (bad != ~0ull) {
+    *bad_record = (size_t)bad;
+    return FQGPU_E_CORRUPT;
+  }
+  if (total > raw_len) return FQGPU_E_CORRUPT;  // (reported with its record above; kept as a guard)
+  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;
+  if (index_rc) return index_rc;
+  const size_t len = (size_t)(at[2] - at[1]), skip = (size_t)(at[1] - at[0]);  // the range's bytes, where they start in the window
+  *out_len = len;
+  if (!out) return FQGPU_OK;
+  if (out_cap < len) return FQGPU_E_OVERFLOW;
+
+  hipStream_t st = ctx->stream;
+  FQ_HIP_HP(hipMemsetAsync(b->seq + seq_len, 0, 16, st));  // the bit reader loads whole dwords
+  FQ_HIP_HP(hipMemsetAsync(b->qual + qual_len, 0, 16, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->seq, seq, seq_len, hipMemcpyHostToDevice, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->qual, qual, qual_len, hipMemcpyHostToDevice, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->n_count, n_count + (n_count_len - n_recs), n_recs * 2, hipMemcpyHostToDevice, st));
+  if (n_pos_len) FQ_HIP_HP(hipMemcpyAsync(b->n_pos, n_pos, n_pos_len * 2, hipMemcpyHostToDevice, st));
+  for (int s = 0; s < 2; s++)
+    if (index_len[s]) {
+      if ((rc = index_accept(b, s, index[s], index_len[s]))) return hp_fail(ctx, rc);
+      FQ_HIP_HP(hipMemcpyAsync(b->index[s], index[s], index_len[s], hipMemcpyHostToDevice, st));
+      b->index_bytes[s] = index_len[s];
+    }
+  b->seq_len = seq_len; b->qual_len = qual_len; b->n_pos_len = n_pos_len;
+  b->last_op = 2;
+  b->result_pulled = false;
+  if (plan.indexed) {
+    if ((rc = fq_decode_strides_launch(ctx, b, plan.k_lo, plan.k_hi, rs.data())) ||
+        (rc = fq_npatch_window(ctx, b, (unsigned)plan.w0, (unsigned)plan.w1)))
+      return hp_fail(ctx, rc);
+  } else {
+    fqgpu_dblock *one[1] = {b};  // the window is the whole chunk
+    if ((rc = fq_decode_launch(ctx, one, 1))) return hp_fail(ctx, rc);
+  }
+  if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
+  FQ_HIP_HP(hipStreamSynchronize(st));  // (the copies back only behind the kernels: hp_decode_streams says why)
+  FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
+  FQ_HIP_HP(hipMemcpyAsync(out, b->raw + skip, len, hipMemcpyDeviceToHost, st));
+  if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs + first, (end - first) * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
+  FQ_HIP_HP(hipStreamSynchronize(st));
+  if (recs_out)
+    for (size_t i = 0; i < end - first; i++) {
+      recs_out[i].seq_off -= (uint32_t)skip;
+      recs_out[i].qual_off -= (uint32_t)skip;
+    }
+  b->host_result = *ctx->hp_result;
+  b->result_pulled = true;
+  if (b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol) return FQGPU_E_ARG;
+  if (b->host_result.s[0].corrupt || b->host_result.s[1].corrupt) return FQGPU_E_CORRUPT;
+  return FQGPU_OK;
 }

@@ -221,6 +221,13 @@ public:
     if (aborted_.load()) return false;
     const std::size_t k = next_.fetch_add(1);
     if (k >= index_.size()) return false;
+    readBlockAt(k, cb);
+    return true;
+  }
+  /** Block k in input order (chunk k), whatever readBlock has handed out.  Thread-safe. */
+  void readBlockAt(std::size_t k, CompressedBuffersSrc &cb) const {
+    cb.clear();
+    if (k >= index_.size()) throw std::out_of_range("readBlockAt: no block " + std::to_string(k));
     const BlockRef &ref = index_[k];
     std::vector<uint8_t> image(ref.end - ref.offset);
     file_.readAt(ref.offset, image.data(), image.size());
@@ -236,7 +243,6 @@ public:
       if (orig) *orig = cur.u32();
       cur.bytes(data);
     });
-    return true;
   }
 
   /** the index behind the last block, then the block count at offset 0 */
@@ -277,6 +283,17 @@ public:
       at[k + 1] = at[k] + total;
     }
     return at;
+  }
+
+  /** The number of records of every chunk (entry k: chunk k): the second word of a block. */
+  [[nodiscard]] std::vector<uint32_t> recordCounts() const {
+    std::vector<uint32_t> n(index_.size(), 0);
+    for (std::size_t k = 0; k < index_.size(); ++k) {
+      uint32_t head[2] = {0, 0};
+      file_.readAt(index_[k].offset, head, sizeof(head));
+      n[k] = head[1];
+    }
+    return n;
   }
 
 private:

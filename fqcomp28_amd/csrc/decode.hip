@@ -692,6 +692,15 @@ int fq_wipe_launch(fqgpu_ctx *ctx, fqgpu_dblock *b) {
   return FQGPU_OK;
 }
 
+static int dec_stream2_ensure(fqgpu_ctx *ctx) {
+  if (!ctx->dec_stream2) {
+    FQ_HIP(hipStreamCreateWithFlags(&ctx->dec_stream2, hipStreamNonBlocking));
+    FQ_HIP(hipEventCreateWithFlags(&ctx->dec_fork, hipEventDisableTiming));
+    FQ_HIP(hipEventCreateWithFlags(&ctx->dec_join, hipEventDisableTiming));
+  }
+  return FQGPU_OK;
+}
+
 int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks) {
   hipStream_t st = ctx->stream;
   if (!n_blocks) return FQGPU_OK;
@@ -768,11 +777,7 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   TabView ts = {ctx->tab[0].logs, ctx->tab[0].log_prefix, ctx->tab[0].dt, ctx->tab[0].dt_off};
   TabView tq = {ctx->tab[1].logs, ctx->tab[1].log_prefix, ctx->tab[1].dt, ctx->tab[1].dt_off};
   // the sequence streams run beside the quality streams on a second stream
-  if (!ctx->dec_stream2) {
-    FQ_HIP(hipStreamCreateWithFlags(&ctx->dec_stream2, hipStreamNonBlocking));
-    FQ_HIP(hipEventCreateWithFlags(&ctx->dec_fork, hipEventDisableTiming));
-    FQ_HIP(hipEventCreateWithFlags(&ctx->dec_join, hipEventDisableTiming));
-  }
+  if ((rc = dec_stream2_ensure(ctx))) return rc;
   hipStream_t st2 = ctx->dec_stream2;
   fq_timer_span_begin(ctx, "decode", st);
   FQ_HIP(hipEventRecord(ctx->dec_fork, st));
@@ -802,6 +807,59 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     return rc;
   hipLaunchKernelGGL(k_npatch, dim3(gx ? gx : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
                      ctx->n_off.as<uint32_t>());
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipGetLastError());
+  return FQGPU_OK;
+}
+
+// fqgpu_decode_chunk_range: strides k_lo[s] .. k_hi[s] of stream s (0 = sequence) of one block that holds both decode
+// indexes, with the kernels and the placement rule of fq_decode_launch.  rec_start: the block's (host, n_recs + 1
+// entries).  The walk writes only the records those strides touch, through b->recs[r] and into b->raw; the N pass is
+// the caller's.
+int fq_decode_strides_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, const unsigned k_lo[2], const unsigned k_hi[2],
+                             const uint32_t *rec_start) {
+  hipStream_t st = ctx->stream;
+  int rc = fqgpu_sync(ctx);
+  if (rc) return rc;
+  DecJob j;
+  j.seq = b->seq;   j.seq_len = (unsigned)b->seq_len;
+  j.qual = b->qual; j.qual_len = (unsigned)b->qual_len;
+  j.recs = b->recs; j.n_recs = (unsigned)b->n_recs;
+  j.n_count = b->n_count;
+  j.n_pos = b->n_pos; j.n_pos_len = (unsigned)b->n_pos_len;
+  j.raw = b->raw;
+  j.res = b->result;
+  j.rec_base = 0;
+  j.index[0] = b->index[0]; j.index[1] = b->index[1];
+  std::vector<DecChunk> chunks;  // quality strides | sequence strides, each from the last
+  for (unsigned k = k_hi[1] + 1; k-- > k_lo[1];) chunks.push_back(DecChunk{0u, 1u, k});
+  const size_t n_qual_chunks = chunks.size();
+  for (unsigned k = k_hi[0] + 1; k-- > k_lo[0];) chunks.push_back(DecChunk{0u, 0u, k});
+  if ((rc = ctx->dec_desc.reserve(sizeof(DecJob))) || (rc = ctx->dec_chunks.reserve(chunks.size() * sizeof(DecChunk))) ||
+      (rc = ctx->dec_recstart.reserve((b->n_recs + 1) * 4 + 64)))
+    return rc;
+  j.rec_start = ctx->dec_recstart.as<uint32_t>();
+  FQ_HIP(hipMemcpyAsync(ctx->dec_recstart.p, rec_start, (b->n_recs + 1) * 4, hipMemcpyHostToDevice, st));
+  FQ_HIP(hipMemcpyAsync(ctx->dec_chunks.p, chunks.data(), chunks.size() * sizeof(DecChunk), hipMemcpyHostToDevice, st));
+  hipError_t he = hipMemcpyAsync(ctx->dec_desc.p, &j, sizeof(DecJob), hipMemcpyHostToDevice, st);
+  if (he == hipSuccess) he = hipStreamSynchronize(st);  // the host copies die with this call
+  if (he != hipSuccess) return fq_hip_error(he, __FILE__, __LINE__);
+  FQ_HIP(hipMemsetAsync(b->result, 0, sizeof(BlockResult), st));
+  const DecJob *jobs = ctx->dec_desc.as<DecJob>();
+  const DecChunk *dch = ctx->dec_chunks.as<DecChunk>();
+  TabView ts = {ctx->tab[0].logs, ctx->tab[0].log_prefix, ctx->tab[0].dt, ctx->tab[0].dt_off};
+  TabView tq = {ctx->tab[1].logs, ctx->tab[1].log_prefix, ctx->tab[1].dt, ctx->tab[1].dt_off};
+  if ((rc = dec_stream2_ensure(ctx))) return rc;
+  hipStream_t st2 = ctx->dec_stream2;
+  fq_timer_span_begin(ctx, "decode", st);
+  FQ_HIP(hipEventRecord(ctx->dec_fork, st));
+  FQ_HIP(hipStreamWaitEvent(st2, ctx->dec_fork, 0));
+  if (n_qual_chunks > 2 * (size_t)ctx->n_cus) hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
+  else if (n_qual_chunks) hipLaunchKernelGGL((k_decode_chunks<QualModel, false>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
+  if (chunks.size() > n_qual_chunks)
+    hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)(chunks.size() - n_qual_chunks)), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
+  FQ_HIP(hipEventRecord(ctx->dec_join, st2));
+  FQ_HIP(hipStreamWaitEvent(st, ctx->dec_join, 0));
   fq_timer_span_end(ctx, st);
   FQ_HIP(hipGetLastError());
   return FQGPU_OK;

@@ -15,6 +15,8 @@
 //                   record lengths (then fq_scan_u32_to_u64 over the workgroups: every record's offset)
 //   k_chunk_write   layout check against raw_len; only when every check passed: the record table, the fixed
 //                   bytes and the headers (built in LDS, stored by consecutive lanes to consecutive bytes)
+// fqgpu_decode_chunk_range runs the same passes, then k_chunk_pick (the offsets of a few records) and the WINDOW
+// instance of k_chunk_write, which writes only the records of a window, rebased to the window's first byte.
 // The host's out_of_range cases are checked record by record and the first failing record wins
 // (atomicMin): flags, contentLength or content exhausted, numeric content short, laid-out end > raw_len.
 // Every stream read is bounds-checked; content bytes are read only by the write pass, which runs only on a good
@@ -208,11 +210,20 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_measure(const FqChunkFmt *
   if (threadIdx.x == 0) tlen[t] = (uint32_t)tot;
 }
 
+// WINDOW (fqgpu_decode_chunk_range): only the records [win.w0, win.w1) are written -- record table entries at their
+// numbers in the chunk, bytes at offsets relative to the window's first byte (*win.base) -- while the check against
+// raw_len still covers every record.  A workgroup without window records returns at once when the chunk fits.
+struct ChunkWindow {
+  unsigned w0, w1;
+  const unsigned long long *base;  // device: the offset of record w0 in the whole chunk (k_chunk_pick)
+};
+
+template <bool WINDOW>
 __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__restrict__ fmt, const uint8_t *__restrict__ stage,
                                                             const uint32_t *__restrict__ agg, const unsigned long long *__restrict__ clp,
                                                             const uint32_t *__restrict__ hlen_in, const unsigned long long *__restrict__ toff,
                                                             FqChunkResult *__restrict__ res, uint8_t *__restrict__ raw,
-                                                            fqgpu_rec *__restrict__ recs) {
+                                                            fqgpu_rec *__restrict__ recs, ChunkWindow win) {
   __shared__ FieldLds lds;
   __shared__ uint8_t hbuf[CL_STAGE_BYTES];
   __shared__ uint32_t s_hoff[CL_THREADS + 1];
@@ -222,6 +233,12 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   const unsigned r = t * CL_THREADS + threadIdx.x;
   const bool in = r < fmt->n_recs;
   const unsigned long long raw_len = fmt->raw_len, total = toff[nt];
+  if (WINDOW && (t * CL_THREADS + CL_THREADS <= win.w0 || t * CL_THREADS >= win.w1) && total <= raw_len) {
+    if (t == 0 && threadIdx.x == 0) res->total = total;
+    return;
+  }
+  const bool win_rec = WINDOW ? in && r >= win.w0 && r < win.w1 : in;
+  const unsigned long long base = WINDOW ? *win.base : 0ull;
   const uint16_t *readlens = reinterpret_cast<const uint16_t *>(stage + fmt->readlens);
   const uint32_t hlen = in ? hlen_in[r] : 0u, rl = in ? readlens[r] : 0u;
   const uint32_t rlen = in ? hlen + 2u * rl + 5u : 0u;
@@ -234,8 +251,9 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   if (threadIdx.x == 0) s_ok = total <= raw_len && __hip_atomic_load(&res->bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ~0ull;
   __syncthreads();
   if (!s_ok) return;
-  if (in) {
-    const uint32_t seq_off = (uint32_t)(roff + hlen + 1), qual_off = seq_off + rl + 3u;
+  const unsigned long long wroff = WINDOW ? (win_rec ? roff - base : 0ull) : roff;  // where the record goes
+  if (win_rec) {
+    const uint32_t seq_off = (uint32_t)(wroff + hlen + 1), qual_off = seq_off + rl + 3u;
     fqgpu_rec rec;
     rec.seq_off = seq_off; rec.qual_off = qual_off; rec.len = rl;
     recs[r] = rec;
@@ -244,13 +262,13 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
     raw[qual_off + rl] = '\n';
   }
   unsigned long long htot;
-  const unsigned long long hex = cl_block_excl(hlen, &htot);
+  const unsigned long long hex = cl_block_excl(win_rec ? hlen : 0u, &htot);
   const bool staged = htot <= CL_STAGE_BYTES;  // (uniform)
   s_hoff[threadIdx.x] = (uint32_t)hex;
-  s_roff[threadIdx.x] = roff;
+  s_roff[threadIdx.x] = wroff;
   if (threadIdx.x == 0) s_hoff[CL_THREADS] = (uint32_t)htot;
-  uint8_t *dst = staged ? hbuf + hex : raw + roff;
-  if (in) dst[0] = '@';
+  uint8_t *dst = staged ? hbuf + hex : raw + wroff;
+  if (win_rec) dst[0] = '@';
   uint32_t p = 1;
   const unsigned long long stage_len = fmt->stage_len;
   for (unsigned f = 0; f < nf; f++) {
@@ -258,7 +276,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
     unsigned long long src;
     bool bad = false;
     cl_field(fmt, stage, f, t, r, in, agg, clp, lds, len, src, bad);
-    if (!in) continue;
+    if (!win_rec) continue;
     if (fmt->f[f].type == 1) {
       if (src + len <= stage_len)
         for (uint32_t i = 0; i < len; i++) dst[p + i] = stage[src + i];
@@ -272,13 +290,35 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   if (!staged) return;
   // consecutive lanes -> consecutive bytes of one header (mostly)
   for (uint32_t k = threadIdx.x; k < (uint32_t)htot; k += CL_THREADS) {
-    unsigned lo = 0, hi = CL_THREADS - 1;  // the last record whose header starts at or before k
+    unsigned lo = 0, hi = CL_THREADS - 1;  // the last record whose header starts at or before k (WINDOW: records
+                                           // outside the window have empty headers in front of or behind it)
     while (lo < hi) {
       const unsigned mid = (lo + hi + 1) >> 1;
       if (s_hoff[mid] <= k) lo = mid; else hi = mid - 1;
     }
     raw[s_roff[lo] + (k - s_hoff[lo])] = hbuf[k];
   }
+}
+
+// the offset of record q.r[i] in the whole chunk (n_recs: the end of the last record) -> at[i]; one workgroup per record
+struct ChunkPicks {
+  unsigned r[4];
+};
+__global__ __launch_bounds__(CL_THREADS) void k_chunk_pick(const FqChunkFmt *__restrict__ fmt, const uint8_t *__restrict__ stage,
+                                                           const uint32_t *__restrict__ hlen_in, const unsigned long long *__restrict__ toff,
+                                                           ChunkPicks q, unsigned long long *__restrict__ at) {
+  const unsigned rq = q.r[blockIdx.x], nt = fmt->n_tiles, t = rq / CL_THREADS;
+  if (t >= nt) {  // rq = n_recs, a multiple of 256
+    if (threadIdx.x == 0) at[blockIdx.x] = toff[nt];
+    return;
+  }
+  const unsigned r = t * CL_THREADS + threadIdx.x;
+  const bool in = r < fmt->n_recs;
+  const uint16_t *readlens = reinterpret_cast<const uint16_t *>(stage + fmt->readlens);
+  const uint32_t rlen = in ? hlen_in[r] + 2u * readlens[r] + 5u : 0u;
+  unsigned long long tmp;
+  const unsigned long long ex = cl_block_excl(rlen, &tmp);
+  if (r == rq) at[blockIdx.x] = toff[t] + ex;
 }
 
 }  // namespace
@@ -349,11 +389,9 @@ int fq_chunk_prepare(const fqgpu_header_streams *hdr, const uint16_t *readlens, 
   return FQGPU_OK;
 }
 
-// Uploads the stage, decodes and lays out the chunk into raw_dev / recs_dev, waits, and reports: *bad = the first
-// failing record (~0: none), *total = bytes laid out.  Nothing is written to raw_dev / recs_dev unless *bad is ~0 and
-// *total <= raw_len.
-int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, unsigned long long *bad,
-                    unsigned long long *total) {
+// Uploads the stage and runs the passes every record's offset depends on: per-workgroup counts and sums, their scans,
+// the measure pass, the scan of the record offsets.
+static int chunk_prefix(hipStream_t st, ChunkScratch &cs) {
   const unsigned nt = cs.n_tiles, nf = cs.n_fields;
   int rc;
   if ((rc = cs.stage.reserve(cs.stage_len)) || (rc = cs.agg.reserve((size_t)nf * nt * 4)) ||
@@ -377,13 +415,60 @@ int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_re
                        cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(), cs.tlen.as<uint32_t>(), res);
     FQ_HIP(hipGetLastError());
     if ((rc = fq_scan_u32_to_u64(st, cs.tlen.as<uint32_t>(), nt, cs.toff.as<unsigned long long>(), cs.scan_tmp))) return rc;
-    hipLaunchKernelGGL(k_chunk_write, dim3(nt), dim3(CL_THREADS), 0, st, fmt, stage, cs.agg.as<uint32_t>(),
-                       cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(), res, raw_dev,
-                       recs_dev);
+  }
+  return FQGPU_OK;
+}
+
+// Uploads the stage, decodes and lays out the chunk into raw_dev / recs_dev, waits, and reports: *bad = the first
+// failing record (~0: none), *total = bytes laid out.  Nothing is written to raw_dev / recs_dev unless *bad is ~0 and
+// *total <= raw_len.
+int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, unsigned long long *bad,
+                    unsigned long long *total) {
+  const unsigned nt = cs.n_tiles;
+  int rc;
+  if ((rc = chunk_prefix(st, cs))) return rc;
+  FqChunkResult *res = cs.res.as<FqChunkResult>();
+  if (nt) {
+    hipLaunchKernelGGL(k_chunk_write<false>, dim3(nt), dim3(CL_THREADS), 0, st, cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(),
+                       cs.agg.as<uint32_t>(), cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(),
+                       cs.toff.as<unsigned long long>(), res, raw_dev, recs_dev, ChunkWindow{});
     FQ_HIP(hipGetLastError());
   }
   FqChunkResult h;
   FQ_HIP(hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  *bad = h.bad;
+  *total = h.total;
+  return FQGPU_OK;
+}
+
+// The same for the records [q[0], q[3]) alone (fqgpu_decode_chunk_range): at[i] = the offset of record q[i] in the
+// whole chunk (q[i] = n_recs: its end); with `write`, the window's records go to recs_dev[r] and to raw_dev at offsets
+// relative to at[0] (only the window's bytes are written).  Without, nothing is written and the layout is still judged.
+int fq_chunk_layout_range(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
+                          unsigned long long *bad, unsigned long long *total, unsigned long long at[4]) {
+  const unsigned nt = cs.n_tiles;
+  int rc;
+  if ((rc = chunk_prefix(st, cs)) || (rc = cs.pick.reserve(4 * sizeof(unsigned long long)))) return rc;
+  FqChunkResult *res = cs.res.as<FqChunkResult>();
+  unsigned long long *pick = cs.pick.as<unsigned long long>();
+  if (nt) {
+    const FqChunkFmt *fmt = cs.stage.as<FqChunkFmt>();
+    const uint8_t *stage = cs.stage.as<uint8_t>();
+    hipLaunchKernelGGL(k_chunk_pick, dim3(4), dim3(CL_THREADS), 0, st, fmt, stage, cs.hlen.as<uint32_t>(),
+                       cs.toff.as<unsigned long long>(), ChunkPicks{{q[0], q[1], q[2], q[3]}}, pick);
+    FQ_HIP(hipGetLastError());
+    const ChunkWindow win{write ? q[0] : 0u, write ? q[3] : 0u, pick};
+    hipLaunchKernelGGL(k_chunk_write<true>, dim3(nt), dim3(CL_THREADS), 0, st, fmt, stage, cs.agg.as<uint32_t>(),
+                       cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(), res, raw_dev,
+                       recs_dev, win);
+    FQ_HIP(hipGetLastError());
+  } else {
+    FQ_HIP(hipMemsetAsync(pick, 0, 4 * sizeof(unsigned long long), st));
+  }
+  FqChunkResult h;
+  FQ_HIP(hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipMemcpyAsync(at, pick, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   FQ_HIP(hipStreamSynchronize(st));
   *bad = h.bad;
   *total = h.total;

@@ -245,10 +245,9 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
   return decompressFarm(meta, [&](CompressedBuffersSrc &c) { return !stopped.load() && next_block(c); }, write_chunk, [&] { stopped.store(true); }, set);
 }
 
-/** processArchiveParts (src/process.cpp:84-105): archive in, file out (chunks in original order) */
-inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &mates1_out, const Settings &set) {
-  Archive archive(archive_path);
-  FastqWriter writer(mates1_out, archive.chunkOffsets());
+namespace detail {
+/** the archive's decode index file, if one lies beside it and was written for it */
+inline std::unique_ptr<DecodeIndexFile> openDecodeIndex(const path_t &archive_path) {
   std::unique_ptr<DecodeIndexFile> sidecar;
   if (std::filesystem::exists(DecodeIndexFile::pathFor(archive_path))) {
     sidecar = std::make_unique<DecodeIndexFile>(DecodeIndexFile::pathFor(archive_path), PosFile::Mode::Read);
@@ -257,6 +256,15 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
       sidecar.reset();
     }
   }
+  return sidecar;
+}
+}  // namespace detail
+
+/** processArchiveParts (src/process.cpp:84-105): archive in, file out (chunks in original order) */
+inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &mates1_out, const Settings &set) {
+  Archive archive(archive_path);
+  FastqWriter writer(mates1_out, archive.chunkOffsets());
+  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
   FarmReport rep = decompressFarm(
       archive.meta(),
       [&](CompressedBuffersSrc &cbs) {
@@ -266,6 +274,96 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
       },
       [&](const FastqChunk &chunk) { writer.writeChunk(chunk); }, [&] { archive.abort(); }, set);
   writer.flush();
+  return rep;
+}
+
+/** Extension: a part of one chunk to restore -- records [first, end) of block `block` (whole: all of them) */
+struct RangePiece {
+  std::size_t block = 0, first = 0, end = 0;
+  bool whole = false;
+};
+/** Records [a, b) of an archive (numbered from 0 across it, in input order) as pieces of the blocks they overlap, in
+ *  order; counts: records per block (Archive::recordCounts).  Throws std::invalid_argument unless a < b <= the total. */
+inline std::vector<RangePiece> planRecordRange(const std::vector<uint32_t> &counts, std::size_t a, std::size_t b) {
+  std::size_t total = 0;
+  for (const uint32_t n : counts) total += n;
+  if (a >= b || b > total)
+    throw std::invalid_argument("records " + std::to_string(a) + ":" + std::to_string(b) + ": not a range of the archive's " +
+                                std::to_string(total) + " records");
+  std::vector<RangePiece> pieces;
+  std::size_t at = 0;  // first record of block k
+  for (std::size_t k = 0; k < counts.size() && at < b; at += counts[k], ++k) {
+    const std::size_t lo = std::max(a, at), hi = std::min(b, at + counts[k]);
+    if (lo >= hi) continue;
+    pieces.push_back(RangePiece{k, lo - at, hi - at, lo == at && hi == at + counts[k]});
+  }
+  return pieces;
+}
+
+/** Extension: `d --records A:B` -- records [a, b) of the archive into a file of their own.  Only the blocks that
+ *  overlap the range are read and decoded: the middle ones whole (decodeChunk), the one or two at the edges through
+ *  decodeChunkRange (with the block's decode index, only the strides that hold the range).  The pieces' sizes are
+ *  known before the farm starts -- a whole block's from its first word, an edge piece's from the layout passes
+ *  (rangeSize) -- so FastqWriter places them as they finish.  b = SIZE_MAX: to the last record. */
+inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &mates1_out, std::size_t a, std::size_t b,
+                                      const Settings &set) {
+  Archive archive(archive_path);
+  const std::vector<uint32_t> counts = archive.recordCounts();
+  if (b == SIZE_MAX) {
+    b = 0;
+    for (const uint32_t n : counts) b += n;
+  }
+  const std::vector<RangePiece> pieces = planRecordRange(counts, a, b);
+  const std::vector<uint64_t> chunk_at = archive.chunkOffsets();
+  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(pieces.size())));
+  if (set.devices.empty()) throw std::invalid_argument("processArchiveRange: no device");
+  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
+  detail::runWorkers(T, [&](unsigned t) { wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]); });
+  const auto t0 = std::chrono::steady_clock::now();
+  std::vector<uint64_t> out_at(pieces.size() + 1, 0);
+  for (std::size_t p = 0; p < pieces.size(); ++p) {
+    const RangePiece &pc = pieces[p];
+    std::size_t size = chunk_at[pc.block + 1] - chunk_at[pc.block];
+    if (!pc.whole) {
+      CompressedBuffersSrc cbs;
+      archive.readBlockAt(pc.block, cbs);
+      size = wksp[0]->rangeSize(cbs, pc.first, pc.end);
+    }
+    out_at[p + 1] = out_at[p] + size;
+  }
+  FastqWriter writer(mates1_out, out_at);
+  std::vector<InputStats> istats(T);
+  FarmReport rep;
+  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
+  std::atomic<std::size_t> next{0};
+  std::atomic<bool> stopped{false};
+  detail::runWorkers(T, [&](unsigned t) {
+    CompressedBuffersSrc cbs;
+    FastqChunk chunk;
+    for (;;) {
+      const std::size_t p = next.fetch_add(1);
+      if (stopped.load() || p >= pieces.size()) break;
+      const RangePiece &pc = pieces[p];
+      StageClock clk;
+      archive.readBlockAt(pc.block, cbs);
+      if (sidecar) (void)sidecar->get(cbs);
+      clk.lap("read");
+      if (pc.whole) wksp[t]->decodeChunk(chunk, cbs);
+      else wksp[t]->decodeChunkRange(chunk, cbs, pc.first, pc.end);
+      clk.lap("decode");
+      chunk.idx = static_cast<unsigned>(p);  // (the writer places pieces, not chunks)
+      istats[t].raw += chunk.raw_data.size();
+      istats[t].n_records += chunk.records.size();
+      rep.blocks_per_worker[t]++;
+      writer.writeChunk(chunk);
+      clk.lap("write");
+      clk.done(static_cast<unsigned>(pc.block));
+    }
+  }, [&] { stopped.store(true); });
+  writer.flush();
+  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
   return rep;
 }
 

@@ -526,6 +526,37 @@ public:
     clk.done(chunk.idx);
   }
 
+  /** Extension: records [first, end) of the chunk into piece -- exactly the bytes decodeChunk lays out for them
+   *  (fqgpu_decode_chunk_range: with the block's decode indexes only the strides that hold the range are decoded);
+   *  piece.idx = cbs.chunk_idx.  A chunk the device refuses, or FQGPU_SHIM_HOST_HEADERS=1: decodeChunk, then the slice,
+   *  so that the errors are the host's. */
+  void decodeChunkRange(FastqChunk &piece, CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
+    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
+    if (first >= end || end > cbs.original_size.n_records) throw std::invalid_argument("decodeChunkRange: bad record range");
+    std::size_t len = 0;
+    if (!host_headers && rangeOnDevice(cbs, first, end, &piece, &len)) return;
+    decodeChunk(whole_, cbs);
+    const RecordTable all = DatasetMeta::toRecordTable(whole_);
+    const std::size_t lo = all[first].seq_off - 1 - whole_.records[first].header_length;
+    const std::size_t hi = static_cast<std::size_t>(all[end - 1].qual_off) + all[end - 1].len + 1;
+    piece.clear();
+    piece.idx = cbs.chunk_idx;
+    piece.raw_data.assign(whole_.raw_data.begin() + lo, whole_.raw_data.begin() + hi);
+    RecordTable recs(all.begin() + first, all.begin() + end);
+    for (auto &r : recs) { r.seq_off -= static_cast<uint32_t>(lo); r.qual_off -= static_cast<uint32_t>(lo); }
+    CompressionWorkspace::recordViews(piece, recs);
+  }
+  /** The size of records [first, end) of the chunk as decodeChunkRange restores them (on the device: the layout passes
+   *  only) */
+  std::size_t rangeSize(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
+    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
+    std::size_t len = 0;
+    if (first < end && end <= cbs.original_size.n_records && !host_headers && rangeOnDevice(cbs, first, end, nullptr, &len)) return len;
+    FastqChunk piece;
+    decodeChunkRange(piece, cbs, first, end);
+    return piece.raw_data.size();
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */
@@ -556,19 +587,9 @@ private:
     clk.lap("misc");
     const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
     if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
-    std::vector<fqgpu_field_sizes> sizes(nf);
-    std::vector<const uint8_t *> streams(3 * nf);
-    for (std::size_t i = 0; i < nf; ++i) {
-      const auto &f = cbs.header_fields[i];
-      sizes[i] = {static_cast<uint32_t>(f.isDifferentFlag.size()), static_cast<uint32_t>(f.content.size()),
-                  static_cast<uint32_t>(f.contentLength.size())};
-      streams[3 * i] = reinterpret_cast<const uint8_t *>(f.isDifferentFlag.data());
-      streams[3 * i + 1] = reinterpret_cast<const uint8_t *>(f.content.data());
-      streams[3 * i + 2] = reinterpret_cast<const uint8_t *>(f.contentLength.data());
-    }
-    const fqgpu_header_streams hdr{field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(nf),
-                                   reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size(),
-                                   sizes.data(), streams.data()};
+    std::vector<fqgpu_field_sizes> sizes;
+    std::vector<const uint8_t *> streams;
+    const fqgpu_header_streams hdr = headerStreams(cbs, sizes, streams);
     RecordTable recs(n);
     std::size_t laid_out = 0, bad = 0;
     const int rc = fqgpu_decode_chunk(ctx_, &hdr, reinterpret_cast<const uint16_t *>(cbs.readlens.data()), n,
@@ -604,6 +625,67 @@ private:
     return true;
   }
 
+  /** the header field streams of cbs (decompressed) as the C ABI takes them; sizes / streams hold what it points to */
+  fqgpu_header_streams headerStreams(const CompressedBuffersSrc &cbs, std::vector<fqgpu_field_sizes> &sizes,
+                                     std::vector<const uint8_t *> &streams) const {
+    const std::size_t nf = fmt_.n_fields();
+    sizes.resize(nf);
+    streams.resize(3 * nf);
+    for (std::size_t i = 0; i < nf; ++i) {
+      const auto &f = cbs.header_fields[i];
+      sizes[i] = {static_cast<uint32_t>(f.isDifferentFlag.size()), static_cast<uint32_t>(f.content.size()),
+                  static_cast<uint32_t>(f.contentLength.size())};
+      streams[3 * i] = reinterpret_cast<const uint8_t *>(f.isDifferentFlag.data());
+      streams[3 * i + 1] = reinterpret_cast<const uint8_t *>(f.content.data());
+      streams[3 * i + 2] = reinterpret_cast<const uint8_t *>(f.contentLength.data());
+    }
+    return fqgpu_header_streams{field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(nf),
+                                reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size(),
+                                sizes.data(), streams.data()};
+  }
+
+  /** fqgpu_decode_chunk_range: the size query (*len), then, with a piece, the decode into it.  false: the device
+   *  refused the chunk (the host path decides) */
+  bool rangeOnDevice(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end, FastqChunk *piece, std::size_t *len) {
+    StageClock clk;
+    decompressMiscBuffers(cbs);
+    clk.lap("misc");
+    const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
+    if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
+    std::vector<fqgpu_field_sizes> sizes;
+    std::vector<const uint8_t *> streams;
+    const fqgpu_header_streams hdr = headerStreams(cbs, sizes, streams);
+    const auto call = [&](uint8_t *out, std::size_t cap, fqgpu_rec *recs) {
+      std::size_t bad = 0;
+      const int rc = fqgpu_decode_chunk_range(
+          ctx_, &hdr, reinterpret_cast<const uint16_t *>(cbs.readlens.data()), n, reinterpret_cast<const uint8_t *>(cbs.seq.data()),
+          cbs.seq.size(), reinterpret_cast<const uint8_t *>(cbs.qual.data()), cbs.qual.size(),
+          reinterpret_cast<const uint16_t *>(cbs.n_count.data()), cbs.index.n_count / sizeof(uint16_t),
+          reinterpret_cast<const uint16_t *>(cbs.n_pos.data()), cbs.index.n_pos / sizeof(uint16_t),
+          reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), cbs.decode_index[0].size(),
+          reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data()), cbs.decode_index[1].size(), cbs.original_size.total,
+          first, end, out, cap, len, recs, &bad);
+      // as decodeChunkOnDevice: a damaged sequence / quality stream or a runtime failure ends here (and an overflow: the
+      // size was asked for first)
+      if ((rc == FQGPU_E_CORRUPT && bad == static_cast<std::size_t>(-1)) || rc == FQGPU_E_HIP || rc == FQGPU_E_NOMEM ||
+          rc == FQGPU_E_NO_DEVICE || rc == FQGPU_E_OVERFLOW)
+        fqgpuCheck(rc, "decodeChunkRange");
+      return rc == FQGPU_OK;
+    };
+    if (!call(nullptr, 0, nullptr)) return false;
+    clk.lap("gpu size");
+    if (!piece) return true;
+    piece->clear();
+    piece->idx = cbs.chunk_idx;
+    piece->raw_data.resize(*len);
+    RecordTable recs(end - first);
+    if (!call(reinterpret_cast<uint8_t *>(piece->raw_data.data()), piece->raw_data.size(), recs.data())) return false;
+    clk.lap("gpu");
+    CompressionWorkspace::recordViews(*piece, recs);
+    clk.done(cbs.chunk_idx);
+    return true;
+  }
+
   /** decodeHeader with the output bound checked: near the end of the chunk the header goes through
    *  a local buffer, since the field decoders may write up to FIELDLEN_MAX bytes per field */
   unsigned decodeHeaderChecked(char *dst, char *end, CompressedBuffersSrc &cbs) {
@@ -620,6 +702,7 @@ private:
     return n;
   }
   std::vector<char> tail_;
+  FastqChunk whole_;  // decodeChunkRange on the host path: the whole chunk, sliced
 };
 
 /** The host parser (FastqReader::parseRecords, src/fastq_io.cpp:67-125) on top of fqgpu_parse_fastq: fills

@@ -333,6 +333,25 @@ int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const ui
                        const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
                        uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record);
 
+/* Extension: records [first, end) of a chunk -- exactly the bytes fqgpu_decode_chunk would lay out for them, and
+ * nothing else.  Inputs as fqgpu_decode_chunk; raw_len is the chunk's recorded size and judges the layout as there.
+ * out == NULL: only *out_len (the range's size) is reported, after the layout passes, and no stream is decoded.
+ * recs_out (may be NULL): end - first records, offsets relative to out.  With both decode indexes, only the strides
+ * that hold symbols of the range are decoded; without them, every stream is walked whole (the format's pace).
+ * Returns
+ *   FQGPU_E_ARG       first >= end, end > n_recs, or any argument fqgpu_decode_chunk refuses
+ *   FQGPU_E_OVERFLOW  out_cap below the range's size: nothing is written to out, *out_len holds the size needed
+ *   the other codes as fqgpu_decode_chunk (the layout is judged over the whole chunk: same rc, same *bad_record).
+ * A decoded stride must consume exactly its bits and a patched record must keep its N positions inside the read;
+ * a damaged stride that is not decoded goes unseen (a whole-chunk decode still finds it).  Uses the handle's
+ * staging block like the other host-pointer calls: one call per handle at a time. */
+int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                             const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                             const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                             const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
+                             size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap, size_t *out_len,
+                             fqgpu_rec *recs_out, size_t *bad_record);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap
