@@ -165,6 +165,34 @@ def _check(rc, where):
         raise FqgpuError(rc, where)
 
 
+def _bad(bad_record):
+    """*bad_record of a C call: None when it names no record"""
+    return None if bad_record.value == (1 << 64) - 1 else bad_record.value
+
+
+def _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index):
+    """The arguments fqgpu_decode_chunk and fqgpu_decode_chunk_range share, from hdr to qual_index_len, and the
+    objects they point into (to be kept until the call has returned)."""
+    types, seps, first = header_format
+    types = np.ascontiguousarray(types, dtype=np.uint8)
+    first = np.frombuffer(bytes(first), dtype=np.uint8)
+    parts = [np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8)) for f in header_fields for x in f]
+    sizes = np.array([[len(x) for x in f] for f in header_fields], dtype=np.uint32).reshape(-1, 3)
+    ptrs = (C.c_void_p * max(len(parts), 1))(*[x.ctypes.data if x.size else None for x in parts])
+    hs = _HeaderStreams(types.ctypes.data, bytes(seps), len(types), first.ctypes.data, first.size,
+                        sizes.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p)))
+    readlens = np.ascontiguousarray(readlens, dtype=np.uint16)
+    seq = np.ascontiguousarray(seq, dtype=np.uint8)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8)
+    n_count = np.ascontiguousarray(n_count, dtype=np.uint16)
+    n_pos = np.ascontiguousarray(n_pos, dtype=np.uint16)
+    si, qi = (np.ascontiguousarray(x, dtype=np.uint8) for x in index) if index is not None else (np.zeros(0, np.uint8),) * 2
+    args = (C.byref(hs), _p(readlens), len(readlens), _p(seq), seq.size, _p(qual), qual.size, _p(n_count), n_count.size,
+            _p(n_pos) if n_pos.size else None, n_pos.size, _p(si) if si.size else None, si.size,
+            _p(qi) if qi.size else None, qi.size)
+    return args, (types, first, parts, sizes, ptrs, hs, readlens, seq, qual, n_count, n_pos, si, qi)
+
+
 def device_count():
     return lib().fqgpu_device_count()
 
@@ -511,64 +539,30 @@ class Context:
         laid out, sequence and quality decoded.  header_format = (types, separators, first_header) and header_fields =
         [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
         -> dict(rc, raw, recs, laid_out_len, bad_record); bad_record is None unless the layout was refused."""
-        types, seps, first = header_format
-        types = np.ascontiguousarray(types, dtype=np.uint8)
-        first = np.frombuffer(bytes(first), dtype=np.uint8)
-        parts = [np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8)) for f in header_fields for x in f]
-        sizes = np.array([[len(x) for x in f] for f in header_fields], dtype=np.uint32).reshape(-1, 3)
-        ptrs = (C.c_void_p * max(len(parts), 1))(*[x.ctypes.data if x.size else None for x in parts])
-        hs = _HeaderStreams(types.ctypes.data, bytes(seps), len(types), first.ctypes.data, first.size,
-                            sizes.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p)))
-        readlens = np.ascontiguousarray(readlens, dtype=np.uint16)
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        qual = np.ascontiguousarray(qual, dtype=np.uint8)
-        n_count = np.ascontiguousarray(n_count, dtype=np.uint16)
-        n_pos = np.ascontiguousarray(n_pos, dtype=np.uint16)
-        si, qi = (np.ascontiguousarray(x, dtype=np.uint8) for x in index) if index is not None else (np.zeros(0, np.uint8),) * 2
+        args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
         raw = np.zeros(raw_len, dtype=np.uint8)
         recs = np.zeros(len(readlens), dtype=REC_DTYPE)
         laid, bad = C.c_size_t(0), C.c_size_t(0)
-        rc = lib().fqgpu_decode_chunk(self.h, C.byref(hs), _p(readlens), len(readlens), _p(seq), seq.size, _p(qual), qual.size,
-                                      _p(n_count), n_count.size, _p(n_pos) if n_pos.size else None, n_pos.size,
-                                      _p(si) if si.size else None, si.size, _p(qi) if qi.size else None, qi.size,
-                                      _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
-        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value,
-                    bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
+        rc = lib().fqgpu_decode_chunk(self.h, *args, _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
+        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad))
 
     def decode_chunk_range(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, first, end,
                            index=None, out_cap=None):
         """Records [first, end) of a chunk (fqgpu_decode_chunk_range), arguments as decode_chunk.  out_cap None: a buffer
         of the range's size (asked for first); 0: the size query alone (raw is None).  -> dict(rc, raw, recs, out_len,
         bad_record); raw holds out_len bytes on success, recs the range's records relative to raw."""
-        types, seps, first_hdr = header_format
-        types = np.ascontiguousarray(types, dtype=np.uint8)
-        first_hdr = np.frombuffer(bytes(first_hdr), dtype=np.uint8)
-        parts = [np.ascontiguousarray(np.frombuffer(bytes(x), dtype=np.uint8)) for f in header_fields for x in f]
-        sizes = np.array([[len(x) for x in f] for f in header_fields], dtype=np.uint32).reshape(-1, 3)
-        ptrs = (C.c_void_p * max(len(parts), 1))(*[x.ctypes.data if x.size else None for x in parts])
-        hs = _HeaderStreams(types.ctypes.data, bytes(seps), len(types), first_hdr.ctypes.data, first_hdr.size,
-                            sizes.ctypes.data, C.cast(ptrs, C.POINTER(C.c_void_p)))
-        readlens = np.ascontiguousarray(readlens, dtype=np.uint16)
-        seq = np.ascontiguousarray(seq, dtype=np.uint8)
-        qual = np.ascontiguousarray(qual, dtype=np.uint8)
-        n_count = np.ascontiguousarray(n_count, dtype=np.uint16)
-        n_pos = np.ascontiguousarray(n_pos, dtype=np.uint16)
-        si, qi = (np.ascontiguousarray(x, dtype=np.uint8) for x in index) if index is not None else (np.zeros(0, np.uint8),) * 2
+        args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
         olen, bad = C.c_size_t(0), C.c_size_t(0)
 
         def call(out, cap, recs):
-            return lib().fqgpu_decode_chunk_range(
-                self.h, C.byref(hs), _p(readlens), len(readlens), _p(seq), seq.size, _p(qual), qual.size, _p(n_count),
-                n_count.size, _p(n_pos) if n_pos.size else None, n_pos.size, _p(si) if si.size else None, si.size,
-                _p(qi) if qi.size else None, qi.size, raw_len, first, end, _p(out) if out is not None else None, cap,
-                C.byref(olen), _p(recs) if recs is not None else None, C.byref(bad))
+            return lib().fqgpu_decode_chunk_range(self.h, *args, raw_len, first, end, _p(out) if out is not None else None, cap,
+                                                  C.byref(olen), _p(recs) if recs is not None else None, C.byref(bad))
 
         n_out = max(end - first, 0)
         if out_cap is None:
             rc = call(None, 0, None)
             if rc != 0:
-                return dict(rc=rc, raw=None, recs=None, out_len=olen.value,
-                            bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
+                return dict(rc=rc, raw=None, recs=None, out_len=olen.value, bad_record=_bad(bad))
             out_cap = olen.value
         raw = recs = None
         if out_cap:
@@ -577,8 +571,7 @@ class Context:
         rc = call(raw, out_cap, recs)
         if raw is not None and rc == 0:
             raw = raw[:olen.value]
-        return dict(rc=rc, raw=raw, recs=recs, out_len=olen.value,
-                    bad_record=None if bad.value == (1 << 64) - 1 else bad.value)
+        return dict(rc=rc, raw=raw, recs=recs, out_len=olen.value, bad_record=_bad(bad))
 
     def decode_block(self, seq, qual, n_count, n_pos, recs, raw_skeleton, index=None):
         """index = (sequence index, quality index) as encode_raw(flags=F_DECODE_INDEX) returns them:

@@ -1265,32 +1265,53 @@ extern "C" int fqgpu_encode_block(fqgpu_ctx *ctx, uint8_t *raw, size_t raw_len, 
                           n_pos_cap, n_pos_len);
 }
 
-// The common part of the host-pointer decodes, once the staging block holds the layout: uploads the streams, decodes,
-// and copies the chunk (and the record table, recs_out != NULL) back when the kernels are through.
-static int hp_decode_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
-                             const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len, uint8_t *raw_out,
-                             size_t raw_len, fqgpu_rec *recs_out, const uint8_t *const index[2], const size_t index_len[2]) {
+// The coded streams of one block as the host-pointer decodes take them; index: the decode indexes (NULL / 0: none)
+struct DecStreams {
+  const uint8_t *seq;  size_t seq_len;
+  const uint8_t *qual; size_t qual_len;
+  const uint16_t *n_count; size_t n_count_len;
+  const uint16_t *n_pos;   size_t n_pos_len;
+  const uint8_t *index[2]; size_t index_len[2];
+  bool ok() const {
+    return seq && qual && n_count && seq_len && qual_len && (index[0] || !index_len[0]) && (index[1] || !index_len[1]);
+  }
+};
+
+// The staging block for a decode of these streams, once the handle is idle
+static int hp_decode_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size_t n_bases, const DecStreams &s, fqgpu_dblock **b) {
+  const int rc = fqgpu_sync(ctx);
+  if (rc) return rc;
+  const size_t seq_cap = s.seq_len > fqgpu_bound_seq(n_bases) ? s.seq_len : fqgpu_bound_seq(n_bases);
+  const size_t qual_cap = s.qual_len > fqgpu_bound_qual(n_bases) ? s.qual_len : fqgpu_bound_qual(n_bases);
+  return hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, s.n_pos_len, b);
+}
+
+// The common part of the host-pointer decodes, once the staging block holds the layout: uploads the streams, decodes
+// (plan != NULL: its strides and window alone) and, when the kernels are through, copies back len bytes of the block from
+// offset skip and, recs_out != NULL, the records [first, first + n_out) with their offsets relative to skip.
+static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s, const FqStridePlan *plan, uint8_t *out, size_t skip,
+                            size_t len, fqgpu_rec *recs_out, size_t first, size_t n_out) {
   int rc;
   const size_t n_recs = b->n_recs;
   hipStream_t st = ctx->stream;
-  FQ_HIP_HP(hipMemsetAsync(b->seq + seq_len, 0, 16, st));  // the bit reader loads whole dwords
-  FQ_HIP_HP(hipMemsetAsync(b->qual + qual_len, 0, 16, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->seq, seq, seq_len, hipMemcpyHostToDevice, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->qual, qual, qual_len, hipMemcpyHostToDevice, st));
+  FQ_HIP_HP(hipMemsetAsync(b->seq + s.seq_len, 0, 16, st));  // the bit reader loads whole dwords
+  FQ_HIP_HP(hipMemsetAsync(b->qual + s.qual_len, 0, 16, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->seq, s.seq, s.seq_len, hipMemcpyHostToDevice, st));
+  FQ_HIP_HP(hipMemcpyAsync(b->qual, s.qual, s.qual_len, hipMemcpyHostToDevice, st));
   // the reference pops from the END of n_count (src/fse_sequence.cpp:115-126)
-  FQ_HIP_HP(hipMemcpyAsync(b->n_count, n_count + (n_count_len - n_recs), n_recs * 2, hipMemcpyHostToDevice, st));
-  if (n_pos_len) FQ_HIP_HP(hipMemcpyAsync(b->n_pos, n_pos, n_pos_len * 2, hipMemcpyHostToDevice, st));
-  for (int s = 0; s < 2; s++)  // (hp_block_acquire has dropped whatever index the staging block held)
-    if (index[s] && index_len[s]) {
-      if ((rc = index_accept(b, s, index[s], index_len[s]))) return hp_fail(ctx, rc);
-      FQ_HIP_HP(hipMemcpyAsync(b->index[s], index[s], index_len[s], hipMemcpyHostToDevice, st));
-      b->index_bytes[s] = index_len[s];
+  FQ_HIP_HP(hipMemcpyAsync(b->n_count, s.n_count + (s.n_count_len - n_recs), n_recs * 2, hipMemcpyHostToDevice, st));
+  if (s.n_pos_len) FQ_HIP_HP(hipMemcpyAsync(b->n_pos, s.n_pos, s.n_pos_len * 2, hipMemcpyHostToDevice, st));
+  for (int k = 0; k < 2; k++)  // (hp_block_acquire has dropped whatever index the staging block held)
+    if (s.index[k] && s.index_len[k]) {
+      if ((rc = index_accept(b, k, s.index[k], s.index_len[k]))) return hp_fail(ctx, rc);
+      FQ_HIP_HP(hipMemcpyAsync(b->index[k], s.index[k], s.index_len[k], hipMemcpyHostToDevice, st));
+      b->index_bytes[k] = s.index_len[k];
     }
-  b->seq_len = seq_len; b->qual_len = qual_len; b->n_pos_len = n_pos_len;
+  b->seq_len = s.seq_len; b->qual_len = s.qual_len; b->n_pos_len = s.n_pos_len;
   b->last_op = 2;
   b->result_pulled = false;
   fqgpu_dblock *one[1] = {b};
-  if ((rc = fq_decode_launch(ctx, one, 1))) return hp_fail(ctx, rc);
+  if ((rc = fq_decode_launch(ctx, one, 1, plan))) return hp_fail(ctx, rc);
   if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
   // The copies back are issued only when the kernels are through: a copy that waits in a DMA
   // engine's queue for a 13 s decode kernel holds that engine, and the uploads of the next workers'
@@ -1298,9 +1319,13 @@ static int hp_decode_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const uint8_t *seq
   // the third worker's fifth hipMemcpyAsync returning after 12.8 s).
   FQ_HIP_HP(hipStreamSynchronize(st));
   FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
-  FQ_HIP_HP(hipMemcpyAsync(raw_out, b->raw, raw_len, hipMemcpyDeviceToHost, st));
-  if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs, n_recs * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
+  FQ_HIP_HP(hipMemcpyAsync(out, b->raw + skip, len, hipMemcpyDeviceToHost, st));
+  if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs + first, n_out * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
   FQ_HIP_HP(hipStreamSynchronize(st));
+  for (size_t i = 0; recs_out && skip && i < n_out; i++) {
+    recs_out[i].seq_off -= (uint32_t)skip;
+    recs_out[i].qual_off -= (uint32_t)skip;
+  }
   b->host_result = *ctx->hp_result;
   b->result_pulled = true;
   if (b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol) return FQGPU_E_ARG;
@@ -1308,36 +1333,29 @@ static int hp_decode_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const uint8_t *seq
   return FQGPU_OK;
 }
 
-static int hp_decode(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len, const uint16_t *n_count,
-                     size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out,
-                     size_t raw_len, const uint8_t *const index[2], const size_t index_len[2]) {
-  if (!ctx || !seq || !qual || !n_count || !recs || !raw_out || !seq_len || !qual_len) return FQGPU_E_ARG;
-  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;
+static int hp_decode(fqgpu_ctx *ctx, const DecStreams &s, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out, size_t raw_len) {
+  if (!ctx || !s.ok() || !recs || !raw_out) return FQGPU_E_ARG;
+  if (s.n_count_len < n_recs) return FQGPU_E_CORRUPT;
   int rc = use_device(ctx->device);
   if (rc) return rc;
   size_t n_bases = 0;
   if ((rc = check_recs(recs, n_recs, raw_len, &n_bases))) return rc;
-  if ((rc = fqgpu_sync(ctx))) return rc;
   fqgpu_dblock *b = nullptr;
-  const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
-  const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
-  if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
+  if ((rc = hp_decode_acquire(ctx, raw_len, n_recs, n_bases, s, &b))) return rc;
   // raw_out holds the skeleton the first decode pass laid out (headers, newlines, '+')
   // everything on the handle's stream (the decode kernels run there too): no host wait in between
   hipStream_t st = ctx->stream;
   FQ_HIP_HP(hipMemcpyAsync(b->raw, raw_out, raw_len, hipMemcpyHostToDevice, st));
   FQ_HIP_HP(hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, st));
-  return hp_decode_streams(ctx, b, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, raw_out, raw_len, nullptr,
-                           index, index_len);
+  return hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, nullptr, 0, n_recs);
 }
 
 extern "C" int fqgpu_decode_block(fqgpu_ctx *ctx, const uint8_t *seq, size_t seq_len, const uint8_t *qual,
                                   size_t qual_len, const uint16_t *n_count, size_t n_count_len,
                                   const uint16_t *n_pos, size_t n_pos_len, const fqgpu_rec *recs,
                                   size_t n_recs, uint8_t *raw_out, size_t raw_len) {
-  const uint8_t *const index[2] = {nullptr, nullptr};
-  const size_t index_len[2] = {0, 0};
-  return hp_decode(ctx, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, recs, n_recs, raw_out, raw_len, index, index_len);
+  return hp_decode(ctx, {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {nullptr, nullptr}, {0, 0}}, recs, n_recs,
+                   raw_out, raw_len);
 }
 
 // The same with the decode index the block's encode left (FQGPU_F_DECODE_INDEX, fqgpu_encode_index): each stream is
@@ -1346,10 +1364,40 @@ extern "C" int fqgpu_decode_block_indexed(fqgpu_ctx *ctx, const uint8_t *seq, si
                                           const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
                                           const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out, size_t raw_len,
                                           const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len) {
-  if ((seq_index_len && !seq_index) || (qual_index_len && !qual_index)) return FQGPU_E_ARG;
-  const uint8_t *const index[2] = {seq_index, qual_index};
-  const size_t index_len[2] = {seq_index_len, qual_index_len};
-  return hp_decode(ctx, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, recs, n_recs, raw_out, raw_len, index, index_len);
+  return hp_decode(ctx, {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
+                         {seq_index_len, qual_index_len}},
+                   recs, n_recs, raw_out, raw_len);
+}
+
+// The front of the chunk decodes: the arguments both refuse, the pass over readlens -- *n_bases and, rec_start != NULL, the
+// encode index of every record's first symbol (n_recs + 1 entries) --, the header streams into the handle's stage.
+static int chunk_front(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, const DecStreams &s,
+                       size_t raw_len, std::vector<uint32_t> *rec_start, size_t *n_bases) {
+  if (!ctx || !hdr || !readlens || !n_recs || !s.ok() || (s.n_pos_len && !s.n_pos)) return FQGPU_E_ARG;
+  if (raw_len >= ((size_t)1 << 32) || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  if (rec_start) rec_start->resize(n_recs + 1);
+  size_t tot = 0;
+  for (size_t r = 0; r < n_recs; r++) {
+    if (readlens[r] < 3) return FQGPU_E_SHORT_READ;  // as check_recs
+    if (rec_start) (*rec_start)[r] = (uint32_t)tot;
+    tot += readlens[r];
+  }
+  if (tot >= 0xFFF00000ull) return FQGPU_E_ARG;
+  if (rec_start) (*rec_start)[n_recs] = (uint32_t)tot;
+  *n_bases = tot;
+  const int rc = use_device(ctx->device);
+  return rc ? rc : fq_chunk_prepare(hdr, readlens, n_recs, raw_len, ctx->hp_chunk);
+}
+
+// What the layout passes found, in the host decoder's order: the first record it throws on, then an n_count too short
+static int layout_verdict(unsigned long long bad, unsigned long long total, size_t raw_len, size_t n_count_len, size_t n_recs,
+                          size_t *bad_record) {
+  if (bad != ~0ull) {  // (the decode kernels are never launched on a bad layout)
+    *bad_record = (size_t)bad;
+    return FQGPU_E_CORRUPT;
+  }
+  if (total > raw_len) return FQGPU_E_CORRUPT;  // (reported with its record above; kept as a guard)
+  return n_count_len < n_recs ? FQGPU_E_CORRUPT : FQGPU_OK;
 }
 
 // Both passes of decodeChunk on the device (decode_headers.hip, then the decode above): only the side streams go up.
@@ -1360,54 +1408,32 @@ extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hd
                                   uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
   if (bad_record) *bad_record = (size_t)-1;
   if (laid_out_len) *laid_out_len = 0;
-  if (!ctx || !hdr || !readlens || !n_recs || !seq || !qual || !n_count || !raw_out || !laid_out_len || !bad_record || !seq_len || !qual_len)
-    return FQGPU_E_ARG;
-  if ((n_pos_len && !n_pos) || (seq_index_len && !seq_index) || (qual_index_len && !qual_index)) return FQGPU_E_ARG;
-  if (raw_len >= ((size_t)1 << 32) || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  if (!raw_out || !laid_out_len || !bad_record) return FQGPU_E_ARG;
+  const DecStreams s = {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
+                        {seq_index_len, qual_index_len}};
   size_t n_bases = 0;
-  for (size_t r = 0; r < n_recs; r++) {
-    if (readlens[r] < 3) return FQGPU_E_SHORT_READ;  // as check_recs
-    n_bases += readlens[r];
-  }
-  if (n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
-  int rc = use_device(ctx->device);
+  int rc = chunk_front(ctx, hdr, readlens, n_recs, s, raw_len, nullptr, &n_bases);
   if (rc) return rc;
-  if ((rc = fq_chunk_prepare(hdr, readlens, n_recs, raw_len, ctx->hp_chunk))) return rc;
-  if ((rc = fqgpu_sync(ctx))) return rc;
   fqgpu_dblock *b = nullptr;
-  const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
-  const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
-  if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
+  if ((rc = hp_decode_acquire(ctx, raw_len, n_recs, n_bases, s, &b))) return rc;
   unsigned long long bad = 0, total = 0;
-  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b->raw, b->recs, &bad, &total))) return hp_fail(ctx, rc);
-  // the decode kernels are never launched on a bad layout
-  if (bad != ~0ull) {
-    *bad_record = (size_t)bad;
-    return FQGPU_E_CORRUPT;
-  }
-  if (total > raw_len) return FQGPU_E_CORRUPT;  // (reported with its record above; kept as a guard)
-  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;  // (behind the layout, in the host's order)
+  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b->raw, b->recs, nullptr, true, &bad, &total, nullptr))) return hp_fail(ctx, rc);
+  if ((rc = layout_verdict(bad, total, raw_len, n_count_len, n_recs, bad_record))) return rc;
   *laid_out_len = (size_t)total;
   if (total < raw_len) FQ_HIP_HP(hipMemsetAsync(b->raw + total, 0, raw_len - total, ctx->stream));
-  const uint8_t *const index[2] = {seq_index, qual_index};
-  const size_t index_len[2] = {seq_index_len, qual_index_len};
-  return hp_decode_streams(ctx, b, seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, raw_out, raw_len, recs_out,
-                           index, index_len);
+  return hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, recs_out, 0, n_recs);
 }
 
 // fqgpu_decode_chunk_range's plan for the records [first, end) of a chunk.  rs: rec_start (n + 1 entries, strictly
 // increasing: every read has 3 bases or more).  With both decode indexes (ix != NULL, each with a snapshot) stream s
 // decodes its strides k_lo[s] .. k_hi[s] -- the ones that hold a symbol of [rs[first], rs[end]), the rule of
 // fq_decode_launch -- and [w0, w1) are the records those strides write to: a stride of encode indices [e_lo, e_hi) walks
-// from the record of symbol e_hi - 1 down to the record of symbol e_lo.  Without, the window is the whole chunk.
-struct RangePlan {
-  bool indexed;
-  unsigned k_lo[2], k_hi[2];
-  size_t w0, w1;
-};
-static RangePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t end, const FqIndexHeader *ix) {
-  RangePlan p = {false, {0, 0}, {0, 0}, 0, n};
-  if (!ix || !ix[0].n_snap || !ix[1].n_snap) return p;
+// from the record of symbol e_hi - 1 down to the record of symbol e_lo.  Without (*indexed = false), the window is the
+// whole chunk and the streams are walked whole.
+static FqStridePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t end, const FqIndexHeader *ix, bool *indexed) {
+  FqStridePlan p = {{0, 0}, {0, 0}, 0, (unsigned)n, rs};
+  *indexed = ix && ix[0].n_snap && ix[1].n_snap;
+  if (!*indexed) return p;
   const auto record_of = [&](uint64_t e) { return (size_t)(std::upper_bound(rs, rs + n, (uint32_t)e) - rs) - 1; };
   const uint64_t s0 = rs[first], s1 = rs[end];
   uint64_t lo = s0, hi = s1;
@@ -1418,9 +1444,8 @@ static RangePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t e
     lo = std::min(lo, p.k_lo[s] * stride);
     hi = std::max(hi, std::min<uint64_t>((p.k_hi[s] + 1) * stride, ix[s].n_sym));
   }
-  p.indexed = true;
-  p.w0 = record_of(lo);
-  p.w1 = record_of(hi - 1) + 1;
+  p.w0 = (unsigned)record_of(lo);
+  p.w1 = (unsigned)record_of(hi - 1) + 1;
   return p;
 }
 
@@ -1435,94 +1460,32 @@ extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_strea
                                         size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
   if (bad_record) *bad_record = (size_t)-1;
   if (out_len) *out_len = 0;
-  if (!ctx || !hdr || !readlens || !n_recs || !seq || !qual || !n_count || !out_len || !bad_record || !seq_len || !qual_len)
-    return FQGPU_E_ARG;
-  if ((n_pos_len && !n_pos) || (seq_index_len && !seq_index) || (qual_index_len && !qual_index)) return FQGPU_E_ARG;
-  if (raw_len >= ((size_t)1 << 32) || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  if (first >= end || end > n_recs) return FQGPU_E_ARG;
-  std::vector<uint32_t> rs(n_recs + 1);
+  if (!out_len || !bad_record || first >= end || end > n_recs) return FQGPU_E_ARG;
+  const DecStreams s = {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
+                        {seq_index_len, qual_index_len}};
+  std::vector<uint32_t> rs;
   size_t n_bases = 0;
-  for (size_t r = 0; r < n_recs; r++) {
-    if (readlens[r] < 3) return FQGPU_E_SHORT_READ;  // as check_recs
-    rs[r] = (uint32_t)n_bases;
-    n_bases += readlens[r];
-  }
-  if (n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
-  rs[n_recs] = (uint32_t)n_bases;
-  int rc = use_device(ctx->device);
+  int rc = chunk_front(ctx, hdr, readlens, n_recs, s, raw_len, &rs, &n_bases);
   if (rc) return rc;
   // (a damaged index is reported as fqgpu_decode_chunk reports it: behind the layout's verdict)
   FqIndexHeader ix[2];
-  const uint8_t *const index[2] = {seq_index, qual_index};
-  const size_t index_len[2] = {seq_index_len, qual_index_len};
   int index_rc = FQGPU_OK;
-  for (int s = 0; s < 2; s++)
-    if (index_len[s] && (rc = index_header(s, n_bases, index[s], index_len[s], &ix[s])) && !index_rc) index_rc = rc;
-  const bool both = !index_rc && seq_index_len && qual_index_len;
-  const RangePlan plan = range_plan(rs.data(), n_recs, first, end, both ? ix : nullptr);
-  if ((rc = fq_chunk_prepare(hdr, readlens, n_recs, raw_len, ctx->hp_chunk))) return rc;
-  if ((rc = fqgpu_sync(ctx))) return rc;
+  for (int k = 0; k < 2; k++)
+    if (s.index_len[k] && (rc = index_header(k, n_bases, s.index[k], s.index_len[k], &ix[k])) && !index_rc) index_rc = rc;
+  bool indexed;
+  const FqStridePlan plan = range_plan(rs.data(), n_recs, first, end, !index_rc && seq_index_len && qual_index_len ? ix : nullptr, &indexed);
+  // the size query has no staging block: nothing is written, nothing goes up
   fqgpu_dblock *b = nullptr;
-  if (out) {
-    const size_t seq_cap = seq_len > fqgpu_bound_seq(n_bases) ? seq_len : fqgpu_bound_seq(n_bases);
-    const size_t qual_cap = qual_len > fqgpu_bound_qual(n_bases) ? qual_len : fqgpu_bound_qual(n_bases);
-    if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, n_pos_len, &b))) return rc;
-  }
-  const unsigned q[4] = {(unsigned)plan.w0, (unsigned)first, (unsigned)end, (unsigned)plan.w1};
+  if ((rc = out ? hp_decode_acquire(ctx, raw_len, n_recs, n_bases, s, &b) : fqgpu_sync(ctx))) return rc;
+  const unsigned q[4] = {plan.w0, (unsigned)first, (unsigned)end, plan.w1};
   unsigned long long bad = 0, total = 0, at[4];
-  if ((rc = fq_chunk_layout_range(ctx->stream, ctx->hp_chunk, b ? b->raw : nullptr, b ? b->recs : nullptr, q, b != nullptr, &bad,
-                                  &total, at)))
+  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b ? b->raw : nullptr, b ? b->recs : nullptr, q, b != nullptr, &bad, &total, at)))
     return hp_fail(ctx, rc);
-  if (bad != ~0ull) {
-    *bad_record = (size_t)bad;
-    return FQGPU_E_CORRUPT;
-  }
-  if (total > raw_len) return FQGPU_E_CORRUPT;  // (reported with its record above; kept as a guard)
-  if (n_count_len < n_recs) return FQGPU_E_CORRUPT;
+  if ((rc = layout_verdict(bad, total, raw_len, n_count_len, n_recs, bad_record))) return rc;
   if (index_rc) return index_rc;
   const size_t len = (size_t)(at[2] - at[1]), skip = (size_t)(at[1] - at[0]);  // the range's bytes, where they start in the window
   *out_len = len;
   if (!out) return FQGPU_OK;
   if (out_cap < len) return FQGPU_E_OVERFLOW;
-
-  hipStream_t st = ctx->stream;
-  FQ_HIP_HP(hipMemsetAsync(b->seq + seq_len, 0, 16, st));  // the bit reader loads whole dwords
-  FQ_HIP_HP(hipMemsetAsync(b->qual + qual_len, 0, 16, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->seq, seq, seq_len, hipMemcpyHostToDevice, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->qual, qual, qual_len, hipMemcpyHostToDevice, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->n_count, n_count + (n_count_len - n_recs), n_recs * 2, hipMemcpyHostToDevice, st));
-  if (n_pos_len) FQ_HIP_HP(hipMemcpyAsync(b->n_pos, n_pos, n_pos_len * 2, hipMemcpyHostToDevice, st));
-  for (int s = 0; s < 2; s++)
-    if (index_len[s]) {
-      if ((rc = index_accept(b, s, index[s], index_len[s]))) return hp_fail(ctx, rc);
-      FQ_HIP_HP(hipMemcpyAsync(b->index[s], index[s], index_len[s], hipMemcpyHostToDevice, st));
-      b->index_bytes[s] = index_len[s];
-    }
-  b->seq_len = seq_len; b->qual_len = qual_len; b->n_pos_len = n_pos_len;
-  b->last_op = 2;
-  b->result_pulled = false;
-  if (plan.indexed) {
-    if ((rc = fq_decode_strides_launch(ctx, b, plan.k_lo, plan.k_hi, rs.data())) ||
-        (rc = fq_npatch_window(ctx, b, (unsigned)plan.w0, (unsigned)plan.w1)))
-      return hp_fail(ctx, rc);
-  } else {
-    fqgpu_dblock *one[1] = {b};  // the window is the whole chunk
-    if ((rc = fq_decode_launch(ctx, one, 1))) return hp_fail(ctx, rc);
-  }
-  if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
-  FQ_HIP_HP(hipStreamSynchronize(st));  // (the copies back only behind the kernels: hp_decode_streams says why)
-  FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
-  FQ_HIP_HP(hipMemcpyAsync(out, b->raw + skip, len, hipMemcpyDeviceToHost, st));
-  if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs + first, (end - first) * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
-  FQ_HIP_HP(hipStreamSynchronize(st));
-  if (recs_out)
-    for (size_t i = 0; i < end - first; i++) {
-      recs_out[i].seq_off -= (uint32_t)skip;
-      recs_out[i].qual_off -= (uint32_t)skip;
-    }
-  b->host_result = *ctx->hp_result;
-  b->result_pulled = true;
-  if (b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol) return FQGPU_E_ARG;
-  if (b->host_result.s[0].corrupt || b->host_result.s[1].corrupt) return FQGPU_E_CORRUPT;
-  return FQGPU_OK;
+  return hp_decode_staged(ctx, b, s, indexed ? &plan : nullptr, out, skip, len, recs_out, first, end - first);
 }

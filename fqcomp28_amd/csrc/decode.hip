@@ -642,8 +642,11 @@ k_gather_ncount(const DecJob *__restrict__ jobs, uint32_t *__restrict__ cnt32) {
 // N restoration (tail of SequenceDecoder::decodeRecord, src/fse_sequence.cpp:138-142).
 // The reference pops counts and deltas from the END of n_count / n_pos while walking the
 // records backwards, which equals forward indexing from (n_pos_len - total N of the block).
+// Records [w0, min(w1, n_recs)) of every block (a whole block: 0, ~0u).  Where a record's N positions start depends on
+// every record in front of it, so `off` and the check of the total cover the whole block whatever the window is; records
+// outside the window are neither patched nor looked up in recs (a range restore has laid out the window alone).
 __global__ void __launch_bounds__(256)
-k_npatch(const DecJob *__restrict__ jobs, const uint32_t *__restrict__ off) {
+k_npatch(const DecJob *__restrict__ jobs, const uint32_t *__restrict__ off, unsigned w0, unsigned w1) {
   const DecJob j = jobs[blockIdx.y];
   const unsigned first = off[j.rec_base], total = off[j.rec_base + j.n_recs] - first;
   if (total > j.n_pos_len) {
@@ -651,7 +654,8 @@ k_npatch(const DecJob *__restrict__ jobs, const uint32_t *__restrict__ off) {
     return;
   }
   const unsigned shift = j.n_pos_len - total;
-  for (unsigned r = blockIdx.x * blockDim.x + threadIdx.x; r < j.n_recs; r += gridDim.x * blockDim.x) {
+  w1 = min(w1, j.n_recs);
+  for (unsigned r = w0 + blockIdx.x * blockDim.x + threadIdx.x; r < w1; r += gridDim.x * blockDim.x) {
     const unsigned cnt = j.n_count[r];
     if (!cnt) continue;
     const fqgpu_rec rec = j.recs[r];
@@ -701,7 +705,8 @@ static int dec_stream2_ensure(fqgpu_ctx *ctx) {
   return FQGPU_OK;
 }
 
-int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks) {
+// plan (fqgpu_decode_chunk_range): ONE block that holds both decode indexes, walked over the plan's strides alone
+int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan) {
   hipStream_t st = ctx->stream;
   if (!n_blocks) return FQGPU_OK;
   int rcs = fqgpu_sync(ctx);  // blocks may still be in an encode lane
@@ -719,6 +724,9 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   const size_t n_plain = blocks.size();
   for (size_t i = 0; i < n_blocks; i++)
     if (snaps_of(blocks_in[i], 0) && snaps_of(blocks_in[i], 1)) blocks.push_back(blocks_in[i]);
+  if (plan && (n_blocks != 1 || n_plain || plan->k_hi[0] > snaps_of(blocks[0], 0) || plan->k_hi[1] > snaps_of(blocks[0], 1) ||
+               plan->w0 > plan->w1 || plan->w1 > blocks[0]->n_recs))
+    return FQGPU_E_ARG;
 
   std::vector<DecJob> host(n_blocks);
   std::vector<DecChunk> chunks, seq_chunks;  // quality strides | sequence strides
@@ -755,12 +763,19 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
       uint32_t *rs = ctx->dec_recstart.as<uint32_t>() + at;
       j.rec_start = rs;
       at += b->n_recs + 1;
-      // lengths -> n_cnt32 (free until the N pass), exclusive scan -> rec_start
-      hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
-                         ctx->n_cnt32.as<uint32_t>());
-      if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp))) return rc;
-      for (size_t k = snaps_of(b, 1) + 1; k-- > 0;) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
-      for (size_t k = snaps_of(b, 0) + 1; k-- > 0;) seq_chunks.push_back(DecChunk{(unsigned)i, 0u, (unsigned)k});
+      if (plan) {  // (b->recs is laid out inside the plan's window alone: nothing to scan)
+        FQ_HIP(hipMemcpyAsync(rs, plan->rec_start, (b->n_recs + 1) * 4, hipMemcpyHostToDevice, st));
+      } else {
+        // lengths -> n_cnt32 (free until the N pass), exclusive scan -> rec_start
+        hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
+                           ctx->n_cnt32.as<uint32_t>());
+        if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp))) return rc;
+      }
+      // every stride of a stream from the last, or the plan's k_lo .. k_hi
+      const size_t lo[2] = {plan ? plan->k_lo[0] : 0u, plan ? plan->k_lo[1] : 0u};
+      const size_t hi[2] = {plan ? plan->k_hi[0] : snaps_of(b, 0), plan ? plan->k_hi[1] : snaps_of(b, 1)};
+      for (size_t k = hi[1] + 1; k-- > lo[1];) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
+      for (size_t k = hi[0] + 1; k-- > lo[0];) seq_chunks.push_back(DecChunk{(unsigned)i, 0u, (unsigned)k});
     }
     n_qual_chunks = chunks.size();
     chunks.insert(chunks.end(), seq_chunks.begin(), seq_chunks.end());
@@ -799,67 +814,16 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   FQ_HIP(hipStreamWaitEvent(st, ctx->dec_join, 0));
   fq_timer_span_end(ctx, st);
   fq_timer_span_begin(ctx, "npatch", st);
-  const unsigned gx = (unsigned)min((r_max + 255) / 256, (size_t)4096);
+  // the N counts are gathered and scanned over whole blocks; the patch covers whole blocks or the plan's window
+  const size_t n_patch = plan ? plan->w1 - plan->w0 : r_max;
+  const unsigned gx = (unsigned)min((r_max + 255) / 256, (size_t)4096), gp = (unsigned)min((n_patch + 255) / 256, (size_t)4096);
   hipLaunchKernelGGL(k_gather_ncount, dim3(gx ? gx : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
                      ctx->n_cnt32.as<uint32_t>());
   if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), r_tot, ctx->n_off.as<uint32_t>(),
                                ctx->scan_tmp)))
     return rc;
-  hipLaunchKernelGGL(k_npatch, dim3(gx ? gx : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
-                     ctx->n_off.as<uint32_t>());
-  fq_timer_span_end(ctx, st);
-  FQ_HIP(hipGetLastError());
-  return FQGPU_OK;
-}
-
-// fqgpu_decode_chunk_range: strides k_lo[s] .. k_hi[s] of stream s (0 = sequence) of one block that holds both decode
-// indexes, with the kernels and the placement rule of fq_decode_launch.  rec_start: the block's (host, n_recs + 1
-// entries).  The walk writes only the records those strides touch, through b->recs[r] and into b->raw; the N pass is
-// the caller's.
-int fq_decode_strides_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, const unsigned k_lo[2], const unsigned k_hi[2],
-                             const uint32_t *rec_start) {
-  hipStream_t st = ctx->stream;
-  int rc = fqgpu_sync(ctx);
-  if (rc) return rc;
-  DecJob j;
-  j.seq = b->seq;   j.seq_len = (unsigned)b->seq_len;
-  j.qual = b->qual; j.qual_len = (unsigned)b->qual_len;
-  j.recs = b->recs; j.n_recs = (unsigned)b->n_recs;
-  j.n_count = b->n_count;
-  j.n_pos = b->n_pos; j.n_pos_len = (unsigned)b->n_pos_len;
-  j.raw = b->raw;
-  j.res = b->result;
-  j.rec_base = 0;
-  j.index[0] = b->index[0]; j.index[1] = b->index[1];
-  std::vector<DecChunk> chunks;  // quality strides | sequence strides, each from the last
-  for (unsigned k = k_hi[1] + 1; k-- > k_lo[1];) chunks.push_back(DecChunk{0u, 1u, k});
-  const size_t n_qual_chunks = chunks.size();
-  for (unsigned k = k_hi[0] + 1; k-- > k_lo[0];) chunks.push_back(DecChunk{0u, 0u, k});
-  if ((rc = ctx->dec_desc.reserve(sizeof(DecJob))) || (rc = ctx->dec_chunks.reserve(chunks.size() * sizeof(DecChunk))) ||
-      (rc = ctx->dec_recstart.reserve((b->n_recs + 1) * 4 + 64)))
-    return rc;
-  j.rec_start = ctx->dec_recstart.as<uint32_t>();
-  FQ_HIP(hipMemcpyAsync(ctx->dec_recstart.p, rec_start, (b->n_recs + 1) * 4, hipMemcpyHostToDevice, st));
-  FQ_HIP(hipMemcpyAsync(ctx->dec_chunks.p, chunks.data(), chunks.size() * sizeof(DecChunk), hipMemcpyHostToDevice, st));
-  hipError_t he = hipMemcpyAsync(ctx->dec_desc.p, &j, sizeof(DecJob), hipMemcpyHostToDevice, st);
-  if (he == hipSuccess) he = hipStreamSynchronize(st);  // the host copies die with this call
-  if (he != hipSuccess) return fq_hip_error(he, __FILE__, __LINE__);
-  FQ_HIP(hipMemsetAsync(b->result, 0, sizeof(BlockResult), st));
-  const DecJob *jobs = ctx->dec_desc.as<DecJob>();
-  const DecChunk *dch = ctx->dec_chunks.as<DecChunk>();
-  TabView ts = {ctx->tab[0].logs, ctx->tab[0].log_prefix, ctx->tab[0].dt, ctx->tab[0].dt_off};
-  TabView tq = {ctx->tab[1].logs, ctx->tab[1].log_prefix, ctx->tab[1].dt, ctx->tab[1].dt_off};
-  if ((rc = dec_stream2_ensure(ctx))) return rc;
-  hipStream_t st2 = ctx->dec_stream2;
-  fq_timer_span_begin(ctx, "decode", st);
-  FQ_HIP(hipEventRecord(ctx->dec_fork, st));
-  FQ_HIP(hipStreamWaitEvent(st2, ctx->dec_fork, 0));
-  if (n_qual_chunks > 2 * (size_t)ctx->n_cus) hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
-  else if (n_qual_chunks) hipLaunchKernelGGL((k_decode_chunks<QualModel, false>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
-  if (chunks.size() > n_qual_chunks)
-    hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)(chunks.size() - n_qual_chunks)), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
-  FQ_HIP(hipEventRecord(ctx->dec_join, st2));
-  FQ_HIP(hipStreamWaitEvent(st, ctx->dec_join, 0));
+  hipLaunchKernelGGL(k_npatch, dim3(gp ? gp : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
+                     ctx->n_off.as<uint32_t>(), plan ? plan->w0 : 0u, plan ? plan->w1 : ~0u);
   fq_timer_span_end(ctx, st);
   FQ_HIP(hipGetLastError());
   return FQGPU_OK;

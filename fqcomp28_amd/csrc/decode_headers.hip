@@ -422,53 +422,35 @@ static int chunk_prefix(hipStream_t st, ChunkScratch &cs) {
 // Uploads the stage, decodes and lays out the chunk into raw_dev / recs_dev, waits, and reports: *bad = the first
 // failing record (~0: none), *total = bytes laid out.  Nothing is written to raw_dev / recs_dev unless *bad is ~0 and
 // *total <= raw_len.
-int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, unsigned long long *bad,
-                    unsigned long long *total) {
-  const unsigned nt = cs.n_tiles;
-  int rc;
-  if ((rc = chunk_prefix(st, cs))) return rc;
-  FqChunkResult *res = cs.res.as<FqChunkResult>();
-  if (nt) {
-    hipLaunchKernelGGL(k_chunk_write<false>, dim3(nt), dim3(CL_THREADS), 0, st, cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(),
-                       cs.agg.as<uint32_t>(), cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(),
-                       cs.toff.as<unsigned long long>(), res, raw_dev, recs_dev, ChunkWindow{});
-    FQ_HIP(hipGetLastError());
-  }
-  FqChunkResult h;
-  FQ_HIP(hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  *bad = h.bad;
-  *total = h.total;
-  return FQGPU_OK;
-}
-
-// The same for the records [q[0], q[3]) alone (fqgpu_decode_chunk_range): at[i] = the offset of record q[i] in the
-// whole chunk (q[i] = n_recs: its end); with `write`, the window's records go to recs_dev[r] and to raw_dev at offsets
+// q != NULL (fqgpu_decode_chunk_range): the records [q[0], q[3]) alone; at[i] = the offset of record q[i] in the whole
+// chunk (q[i] = n_recs: its end); with `write`, the window's records go to recs_dev[r] and to raw_dev at offsets
 // relative to at[0] (only the window's bytes are written).  Without, nothing is written and the layout is still judged.
-int fq_chunk_layout_range(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
-                          unsigned long long *bad, unsigned long long *total, unsigned long long at[4]) {
+int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
+                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4]) {
   const unsigned nt = cs.n_tiles;
   int rc;
-  if ((rc = chunk_prefix(st, cs)) || (rc = cs.pick.reserve(4 * sizeof(unsigned long long)))) return rc;
+  if ((rc = chunk_prefix(st, cs)) || (q && (rc = cs.pick.reserve(4 * sizeof(unsigned long long))))) return rc;
   FqChunkResult *res = cs.res.as<FqChunkResult>();
   unsigned long long *pick = cs.pick.as<unsigned long long>();
-  if (nt) {
-    const FqChunkFmt *fmt = cs.stage.as<FqChunkFmt>();
-    const uint8_t *stage = cs.stage.as<uint8_t>();
-    hipLaunchKernelGGL(k_chunk_pick, dim3(4), dim3(CL_THREADS), 0, st, fmt, stage, cs.hlen.as<uint32_t>(),
-                       cs.toff.as<unsigned long long>(), ChunkPicks{{q[0], q[1], q[2], q[3]}}, pick);
+  const auto write_pass = [&](auto kernel, ChunkWindow win) {
+    hipLaunchKernelGGL(kernel, dim3(nt), dim3(CL_THREADS), 0, st, cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(),
+                       cs.agg.as<uint32_t>(), cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(),
+                       cs.toff.as<unsigned long long>(), res, raw_dev, recs_dev, win);
+    return hipGetLastError();
+  };
+  if (nt && q) {
+    hipLaunchKernelGGL(k_chunk_pick, dim3(4), dim3(CL_THREADS), 0, st, cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(),
+                       cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(), ChunkPicks{{q[0], q[1], q[2], q[3]}}, pick);
     FQ_HIP(hipGetLastError());
-    const ChunkWindow win{write ? q[0] : 0u, write ? q[3] : 0u, pick};
-    hipLaunchKernelGGL(k_chunk_write<true>, dim3(nt), dim3(CL_THREADS), 0, st, fmt, stage, cs.agg.as<uint32_t>(),
-                       cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(), res, raw_dev,
-                       recs_dev, win);
-    FQ_HIP(hipGetLastError());
-  } else {
+    FQ_HIP(write_pass(k_chunk_write<true>, ChunkWindow{write ? q[0] : 0u, write ? q[3] : 0u, pick}));
+  } else if (nt) {
+    FQ_HIP(write_pass(k_chunk_write<false>, ChunkWindow{}));
+  } else if (q) {
     FQ_HIP(hipMemsetAsync(pick, 0, 4 * sizeof(unsigned long long), st));
   }
   FqChunkResult h;
   FQ_HIP(hipMemcpyAsync(&h, res, sizeof(h), hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipMemcpyAsync(at, pick, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+  if (q) FQ_HIP(hipMemcpyAsync(at, pick, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   FQ_HIP(hipStreamSynchronize(st));
   *bad = h.bad;
   *total = h.total;

@@ -197,7 +197,7 @@ struct FqChunkResult {
 };
 struct ChunkScratch {
   DevBuf stage, agg, cls, clp, hlen, tlen, toff, res, scan_tmp;
-  DevBuf pick;  // fq_chunk_layout_range: u64 [4] record offsets
+  DevBuf pick;  // fq_chunk_layout of a window: u64 [4] record offsets
   uint8_t *host = nullptr;  // host stage (grow-only, pageable: small copies stay out of the DMA queues' way)
   size_t host_cap = 0, stage_len = 0;
   unsigned n_fields = 0, n_tiles = 0;
@@ -332,10 +332,16 @@ int fq_seq_pow_ensure(hipStream_t st, DevTables &t, unsigned n_models, unsigned 
 int fq_encode_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned flags, hipEvent_t wait = nullptr,
                      hipStream_t *done = nullptr, bool reserve_only = false);
 int fq_probe_lds_atomic_order(hipStream_t st, bool *ordered);
-int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks);
-int fq_decode_strides_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, const unsigned k_lo[2], const unsigned k_hi[2],
-                             const uint32_t *rec_start);
-int fq_npatch_window(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned w0, unsigned w1);
+// Part of one block that holds both decode indexes (fqgpu_decode_chunk_range): stream s (0 = sequence) walks its strides
+// k_lo[s] .. k_hi[s] alone, with the kernels and the placement rule of a whole decode, and the N pass patches the records
+// [w0, w1), the ones those strides write (through b->recs[r], into b->raw).  rec_start: the encode index of every
+// record's first symbol (host, n_recs + 1 entries).
+struct FqStridePlan {
+  unsigned k_lo[2], k_hi[2];
+  unsigned w0, w1;
+  const uint32_t *rec_start;
+};
+int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks, const FqStridePlan *plan = nullptr);
 int fq_wipe_launch(fqgpu_ctx *ctx, fqgpu_dblock *b);
 int fq_qual_counts_sorted(hipStream_t st, const uint8_t *raw_dev, const fqgpu_rec *recs_dev, size_t n_recs, size_t n_bases,
                           uint32_t *counts_dev, uint32_t *err_dev);
@@ -345,10 +351,8 @@ int fq_headers_launch(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, co
                       const uint8_t *field_types, const char *separators, unsigned n_fields, const uint8_t *first_header,
                       size_t first_header_len, HdrScratch &hs);
 int fq_chunk_prepare(const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, size_t raw_len, ChunkScratch &cs);
-int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, unsigned long long *bad,
-                    unsigned long long *total);
-int fq_chunk_layout_range(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
-                          unsigned long long *bad, unsigned long long *total, unsigned long long at[4]);
+int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
+                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4]);
 int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, ParseScratch &ps, fqgpu_rec *recs_dev,
                      size_t n_recs, size_t *n_bases, size_t *n_n, size_t *used_len);
 

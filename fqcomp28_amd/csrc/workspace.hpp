@@ -475,8 +475,7 @@ public:
    *  stream that runs out, a chunk too small for its records, a format it does not take) goes through the host path
    *  as well, so that the error is the host's. */
   void decodeChunk(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
-    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
-    if (!host_headers && decodeChunkOnDevice(chunk, cbs)) return;
+    if (!hostHeaders() && decodeChunkOnDevice(chunk, cbs)) return;
     StageClock clk;
     chunk.clear();  // prepareFastqChunk (src/workspace.h:127-133)
     chunk.idx = cbs.chunk_idx;
@@ -512,15 +511,10 @@ public:
     clk.lap("table");
     // (with cbs.decode_index -- an extension, empty in a reference archive -- every stream is decoded from all its
     // snapshots at once; without, by one lane from its end: the format's own pace)
-    fqgpuCheck(fqgpu_decode_block_indexed(ctx_, reinterpret_cast<const uint8_t *>(cbs.seq.data()), cbs.seq.size(),
-                                          reinterpret_cast<const uint8_t *>(cbs.qual.data()), cbs.qual.size(),
-                                          reinterpret_cast<const uint16_t *>(cbs.n_count.data()),
-                                          cbs.index.n_count / sizeof(uint16_t),
-                                          reinterpret_cast<const uint16_t *>(cbs.n_pos.data()),
-                                          cbs.index.n_pos / sizeof(uint16_t), recs.data(), recs.size(),
-                                          reinterpret_cast<uint8_t *>(chunk.raw_data.data()), chunk.raw_data.size(),
-                                          reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), cbs.decode_index[0].size(),
-                                          reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data()), cbs.decode_index[1].size()),
+    const StreamArgs s(cbs);
+    fqgpuCheck(fqgpu_decode_block_indexed(ctx_, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len, s.n_pos, s.n_pos_len,
+                                          recs.data(), recs.size(), reinterpret_cast<uint8_t *>(chunk.raw_data.data()),
+                                          chunk.raw_data.size(), s.index[0], s.index_len[0], s.index[1], s.index_len[1]),
                "decodeChunk");
     clk.lap("gpu");
     clk.done(chunk.idx);
@@ -531,10 +525,9 @@ public:
    *  piece.idx = cbs.chunk_idx.  A chunk the device refuses, or FQGPU_SHIM_HOST_HEADERS=1: decodeChunk, then the slice,
    *  so that the errors are the host's. */
   void decodeChunkRange(FastqChunk &piece, CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
-    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
     if (first >= end || end > cbs.original_size.n_records) throw std::invalid_argument("decodeChunkRange: bad record range");
     std::size_t len = 0;
-    if (!host_headers && rangeOnDevice(cbs, first, end, &piece, &len)) return;
+    if (!hostHeaders() && rangeOnDevice(cbs, first, end, &piece, &len)) return;
     decodeChunk(whole_, cbs);
     const RecordTable all = DatasetMeta::toRecordTable(whole_);
     const std::size_t lo = all[first].seq_off - 1 - whole_.records[first].header_length;
@@ -549,9 +542,8 @@ public:
   /** The size of records [first, end) of the chunk as decodeChunkRange restores them (on the device: the layout passes
    *  only) */
   std::size_t rangeSize(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
-    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
     std::size_t len = 0;
-    if (first < end && end <= cbs.original_size.n_records && !host_headers && rangeOnDevice(cbs, first, end, nullptr, &len)) return len;
+    if (first < end && end <= cbs.original_size.n_records && !hostHeaders() && rangeOnDevice(cbs, first, end, nullptr, &len)) return len;
     FastqChunk piece;
     decodeChunkRange(piece, cbs, first, end);
     return piece.raw_data.size();
@@ -583,30 +575,19 @@ private:
     if (chunk.raw_data.capacity() < cbs.original_size.total) chunk.raw_data.reserve(cbs.original_size.total + cbs.original_size.total / 16 + 4096);
     chunk.raw_data.resize(cbs.original_size.total);
     clk.lap("resize");
-    decompressMiscBuffers(cbs);
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) return false;
     clk.lap("misc");
-    const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
-    if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
-    std::vector<fqgpu_field_sizes> sizes;
-    std::vector<const uint8_t *> streams;
-    const fqgpu_header_streams hdr = headerStreams(cbs, sizes, streams);
+    const std::size_t n = a.n_recs, nf = fmt_.n_fields();
     RecordTable recs(n);
     std::size_t laid_out = 0, bad = 0;
-    const int rc = fqgpu_decode_chunk(ctx_, &hdr, reinterpret_cast<const uint16_t *>(cbs.readlens.data()), n,
-                                      reinterpret_cast<const uint8_t *>(cbs.seq.data()), cbs.seq.size(),
-                                      reinterpret_cast<const uint8_t *>(cbs.qual.data()), cbs.qual.size(),
-                                      reinterpret_cast<const uint16_t *>(cbs.n_count.data()), cbs.index.n_count / sizeof(uint16_t),
-                                      reinterpret_cast<const uint16_t *>(cbs.n_pos.data()), cbs.index.n_pos / sizeof(uint16_t),
-                                      reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), cbs.decode_index[0].size(),
-                                      reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data()), cbs.decode_index[1].size(),
+    const StreamArgs &s = a.s;
+    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, n, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len, s.n_pos,
+                                      s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1],
                                       reinterpret_cast<uint8_t *>(chunk.raw_data.data()), chunk.raw_data.size(), recs.data(),
                                       &laid_out, &bad);
     clk.lap("gpu");
-    // a damaged sequence / quality stream (no record named) or a runtime failure: the host path would end the same way
-    if ((rc == FQGPU_E_CORRUPT && bad == static_cast<std::size_t>(-1)) || rc == FQGPU_E_HIP || rc == FQGPU_E_NOMEM ||
-        rc == FQGPU_E_NO_DEVICE)
-      fqgpuCheck(rc, "decodeChunk");
-    if (rc != FQGPU_OK) return false;
+    if (!deviceTook(rc, bad, "decodeChunk")) return false;
     // the stream cursors where the host decoder leaves them: every stream consumed up to the chunk's last header
     for (std::size_t i = 0; i < nf; ++i) {
       auto &f = cbs.header_fields[i];
@@ -625,52 +606,84 @@ private:
     return true;
   }
 
-  /** the header field streams of cbs (decompressed) as the C ABI takes them; sizes / streams hold what it points to */
-  fqgpu_header_streams headerStreams(const CompressedBuffersSrc &cbs, std::vector<fqgpu_field_sizes> &sizes,
-                                     std::vector<const uint8_t *> &streams) const {
-    const std::size_t nf = fmt_.n_fields();
-    sizes.resize(nf);
-    streams.resize(3 * nf);
+  /** FQGPU_SHIM_HOST_HEADERS=1: the host coder lays the chunks out */
+  static bool hostHeaders() {
+    static const bool host_headers = std::getenv("FQGPU_SHIM_HOST_HEADERS") != nullptr;
+    return host_headers;
+  }
+
+  /** the coded streams of cbs (misc buffers decompressed) as the C ABI's decode calls take them */
+  struct StreamArgs {
+    const uint8_t *seq = nullptr, *qual = nullptr;
+    const uint16_t *n_count = nullptr, *n_pos = nullptr;
+    std::size_t seq_len = 0, qual_len = 0, n_count_len = 0, n_pos_len = 0;
+    const uint8_t *index[2] = {nullptr, nullptr};
+    std::size_t index_len[2] = {0, 0};
+    StreamArgs() = default;
+    explicit StreamArgs(const CompressedBuffersSrc &cbs)
+        : seq(reinterpret_cast<const uint8_t *>(cbs.seq.data())), qual(reinterpret_cast<const uint8_t *>(cbs.qual.data())),
+          n_count(reinterpret_cast<const uint16_t *>(cbs.n_count.data())), n_pos(reinterpret_cast<const uint16_t *>(cbs.n_pos.data())),
+          seq_len(cbs.seq.size()), qual_len(cbs.qual.size()), n_count_len(cbs.index.n_count / sizeof(uint16_t)),
+          n_pos_len(cbs.index.n_pos / sizeof(uint16_t)),
+          index{reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data())},
+          index_len{cbs.decode_index[0].size(), cbs.decode_index[1].size()} {}
+  };
+  /** a chunk as the device's chunk decodes take it; sizes / streams hold what hdr points to */
+  struct ChunkArgs {
+    std::vector<fqgpu_field_sizes> sizes;
+    std::vector<const uint8_t *> streams;
+    fqgpu_header_streams hdr;
+    const uint16_t *readlens;
+    std::size_t n_recs;
+    StreamArgs s;
+  };
+  /** the misc pass, then cbs as the device takes it; false: streams that do not match the format (the host path throws) */
+  bool chunkArgs(CompressedBuffersSrc &cbs, ChunkArgs &a) const {
+    decompressMiscBuffers(cbs);
+    const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
+    if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
+    a.sizes.resize(nf);
+    a.streams.resize(3 * nf);
     for (std::size_t i = 0; i < nf; ++i) {
       const auto &f = cbs.header_fields[i];
-      sizes[i] = {static_cast<uint32_t>(f.isDifferentFlag.size()), static_cast<uint32_t>(f.content.size()),
-                  static_cast<uint32_t>(f.contentLength.size())};
-      streams[3 * i] = reinterpret_cast<const uint8_t *>(f.isDifferentFlag.data());
-      streams[3 * i + 1] = reinterpret_cast<const uint8_t *>(f.content.data());
-      streams[3 * i + 2] = reinterpret_cast<const uint8_t *>(f.contentLength.data());
+      a.sizes[i] = {static_cast<uint32_t>(f.isDifferentFlag.size()), static_cast<uint32_t>(f.content.size()),
+                    static_cast<uint32_t>(f.contentLength.size())};
+      a.streams[3 * i] = reinterpret_cast<const uint8_t *>(f.isDifferentFlag.data());
+      a.streams[3 * i + 1] = reinterpret_cast<const uint8_t *>(f.content.data());
+      a.streams[3 * i + 2] = reinterpret_cast<const uint8_t *>(f.contentLength.data());
     }
-    return fqgpu_header_streams{field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(nf),
-                                reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size(),
-                                sizes.data(), streams.data()};
+    a.hdr = fqgpu_header_streams{field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(nf),
+                                 reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size(),
+                                 a.sizes.data(), a.streams.data()};
+    a.readlens = reinterpret_cast<const uint16_t *>(cbs.readlens.data());
+    a.n_recs = n;
+    a.s = StreamArgs(cbs);
+    return true;
+  }
+  /** What a chunk decode's return code means.  Throws where the host path would end the same way: a damaged sequence /
+   *  quality stream (no record named), a runtime failure, an overflow (the size was asked for first).  false: the device
+   *  refused the chunk (the host path decides) */
+  static bool deviceTook(int rc, std::size_t bad, const char *where) {
+    if ((rc == FQGPU_E_CORRUPT && bad == static_cast<std::size_t>(-1)) || rc == FQGPU_E_HIP || rc == FQGPU_E_NOMEM ||
+        rc == FQGPU_E_NO_DEVICE || rc == FQGPU_E_OVERFLOW)
+      fqgpuCheck(rc, where);
+    return rc == FQGPU_OK;
   }
 
   /** fqgpu_decode_chunk_range: the size query (*len), then, with a piece, the decode into it.  false: the device
    *  refused the chunk (the host path decides) */
   bool rangeOnDevice(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end, FastqChunk *piece, std::size_t *len) {
     StageClock clk;
-    decompressMiscBuffers(cbs);
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) return false;
     clk.lap("misc");
-    const std::size_t n = cbs.original_size.n_records, nf = fmt_.n_fields();
-    if (cbs.header_fields.size() != nf || cbs.readlens.size() < n * sizeof(readlen_t)) return false;
-    std::vector<fqgpu_field_sizes> sizes;
-    std::vector<const uint8_t *> streams;
-    const fqgpu_header_streams hdr = headerStreams(cbs, sizes, streams);
     const auto call = [&](uint8_t *out, std::size_t cap, fqgpu_rec *recs) {
       std::size_t bad = 0;
-      const int rc = fqgpu_decode_chunk_range(
-          ctx_, &hdr, reinterpret_cast<const uint16_t *>(cbs.readlens.data()), n, reinterpret_cast<const uint8_t *>(cbs.seq.data()),
-          cbs.seq.size(), reinterpret_cast<const uint8_t *>(cbs.qual.data()), cbs.qual.size(),
-          reinterpret_cast<const uint16_t *>(cbs.n_count.data()), cbs.index.n_count / sizeof(uint16_t),
-          reinterpret_cast<const uint16_t *>(cbs.n_pos.data()), cbs.index.n_pos / sizeof(uint16_t),
-          reinterpret_cast<const uint8_t *>(cbs.decode_index[0].data()), cbs.decode_index[0].size(),
-          reinterpret_cast<const uint8_t *>(cbs.decode_index[1].data()), cbs.decode_index[1].size(), cbs.original_size.total,
-          first, end, out, cap, len, recs, &bad);
-      // as decodeChunkOnDevice: a damaged sequence / quality stream or a runtime failure ends here (and an overflow: the
-      // size was asked for first)
-      if ((rc == FQGPU_E_CORRUPT && bad == static_cast<std::size_t>(-1)) || rc == FQGPU_E_HIP || rc == FQGPU_E_NOMEM ||
-          rc == FQGPU_E_NO_DEVICE || rc == FQGPU_E_OVERFLOW)
-        fqgpuCheck(rc, "decodeChunkRange");
-      return rc == FQGPU_OK;
+      const StreamArgs &s = a.s;
+      const int rc = fqgpu_decode_chunk_range(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count,
+                                              s.n_count_len, s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1],
+                                              s.index_len[1], cbs.original_size.total, first, end, out, cap, len, recs, &bad);
+      return deviceTook(rc, bad, "decodeChunkRange");
     };
     if (!call(nullptr, 0, nullptr)) return false;
     clk.lap("gpu size");

@@ -1,5 +1,5 @@
-"""Records [first, end) of a chunk (fqgpu_decode_chunk_range, fqcomp28_amd/csrc/decode_range.hip and the WINDOW pass of
-decode_headers.hip) and of an archive (fqc_tool d --records A:B): byte-equal to the input's records and to the matching
+"""Records [first, end) of a chunk (fqgpu_decode_chunk_range, the windowed N pass of fqcomp28_amd/csrc/decode.hip and the
+WINDOW pass of decode_headers.hip) and of an archive (fqc_tool d --records A:B): byte-equal to the input's records and to the matching
 slice of decode_chunk, with only the strides that hold the range decoded when both decode indexes are there."""
 import os
 import struct
