@@ -93,6 +93,10 @@ _PROTOS = {
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                      C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fqgpu_decode_chunk_indexing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "fqgpu_decode_index": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_decode_chunk_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
@@ -107,6 +111,7 @@ _PROTOS = {
     "fqgpu_dblock_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint]),
     "fqgpu_dblock_wipe": (C.c_int, [C.c_void_p, C.c_void_p]),
     "fqgpu_dblocks_decode": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]),
+    "fqgpu_dblocks_decode_indexing": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_size_t]),
     "fqgpu_sync": (C.c_int, [C.c_void_p]),
     "fqgpu_dblock_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t),
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -441,6 +446,12 @@ class Context:
         arr = (C.c_void_p * len(blocks))(*[b.h for b in blocks])
         _check(lib().fqgpu_dblocks_decode(self.h, arr, len(blocks)), "dblocks_decode")
 
+    def decode_dblocks_indexing(self, blocks):
+        """fqgpu_dblocks_decode_indexing: decodes the blocks from their streams alone and leaves both decode indexes on
+        each (DBlock.fetch_index); a damaged block shows in its status()"""
+        arr = (C.c_void_p * len(blocks))(*[b.h for b in blocks])
+        _check(lib().fqgpu_dblocks_decode_indexing(self.h, arr, len(blocks)), "dblocks_decode_indexing")
+
     @staticmethod
     def host_buffers(n_recs, n_bases, seq_cap=None, qual_cap=None):
         """Output buffers a worker keeps across chunks (the reference reuses its CompressedBuffersDst)."""
@@ -534,15 +545,30 @@ class Context:
         return dict(rc=rc, seq=seq, qual=qual, readlens=readlens, n_count=n_count, n_pos=n_pos, raw_after=raw,
                     recs=table, used_len=used.value, n_bases=nb.value, **hdr)
 
-    def decode_chunk(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, index=None):
+    def decode_chunk(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, index=None,
+                     build_index=False, want_raw=True):
         """Both decode passes on the device (fqgpu_decode_chunk): headers decoded from their field streams, the chunk
         laid out, sequence and quality decoded.  header_format = (types, separators, first_header) and header_fields =
         [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
-        -> dict(rc, raw, recs, laid_out_len, bad_record); bad_record is None unless the layout was refused."""
+        -> dict(rc, raw, recs, laid_out_len, bad_record); bad_record is None unless the layout was refused.
+        build_index=True (index must be None): fqgpu_decode_chunk_indexing, the decode builds the chunk's decode indexes
+        on the way -> also "index": (seq, qual), two empty arrays after a failure; want_raw=False: index only, raw is None."""
         args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
-        raw = np.zeros(raw_len, dtype=np.uint8)
+        raw = np.zeros(raw_len, dtype=np.uint8) if want_raw or not build_index else None
         recs = np.zeros(len(readlens), dtype=REC_DTYPE)
         laid, bad = C.c_size_t(0), C.c_size_t(0)
+        if build_index:
+            assert index is None, "an indexing decode takes no index"
+            rc = lib().fqgpu_decode_chunk_indexing(self.h, *args[:11], _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
+            built = []
+            for s in (0, 1):
+                n_idx = C.c_size_t(0)
+                lib().fqgpu_decode_index(self.h, s, None, 0, C.byref(n_idx))
+                idx = np.zeros(n_idx.value, dtype=np.uint8)
+                if idx.size:
+                    _check(lib().fqgpu_decode_index(self.h, s, _p(idx), idx.size, C.byref(n_idx)), "fqgpu_decode_index")
+                built.append(idx)
+            return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), index=tuple(built))
         rc = lib().fqgpu_decode_chunk(self.h, *args, _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
         return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad))
 

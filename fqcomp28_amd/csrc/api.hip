@@ -527,7 +527,8 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
 #endif
   free_tables(ctx->tab[0]);
   free_tables(ctx->tab[1]);
-  DevBuf *bufs[] = {&ctx->n_cnt32, &ctx->n_off, &ctx->scan_tmp, &ctx->dec_desc, &ctx->dec_chunks, &ctx->dec_recstart};
+  DevBuf *bufs[] = {&ctx->n_cnt32, &ctx->n_off, &ctx->scan_tmp, &ctx->dec_desc, &ctx->dec_chunks, &ctx->dec_recstart,
+                     &ctx->dec_idx, &ctx->dec_entries};
   for (DevBuf *b : bufs) b->release();
   ctx->hp_parse.release();  // the device parser's scratch (fqgpu_ctx_reserve / fqgpu_encode_begin without a record table)
   ctx->hp_hdr.release();
@@ -929,7 +930,7 @@ extern "C" int fqgpu_dblock_load_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const 
   return FQGPU_OK;
 }
 
-extern "C" int fqgpu_dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks) {
+static int dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks, bool build_index) {
   if (!ctx || (!blocks && n_blocks)) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
@@ -947,7 +948,29 @@ extern "C" int fqgpu_dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks,
     if (!b->seq_len || !b->qual_len) return FQGPU_E_ARG;
   }
   for (size_t i = 0; i < n_blocks; i++) { blocks[i]->last_op = 2; blocks[i]->result_pulled = false; }
-  return fq_decode_launch(ctx, blocks, n_blocks);
+  return fq_decode_launch(ctx, blocks, n_blocks, nullptr, build_index);
+}
+
+extern "C" int fqgpu_dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks) {
+  return dblocks_decode(ctx, blocks, n_blocks, false);
+}
+
+// The same decode by the indexing walk: every block is left with both decode indexes.  Waits for the batch (a block whose
+// streams turn out corrupt keeps no index); the blocks' status is reported by fqgpu_dblock_status as after fqgpu_dblocks_decode.
+extern "C" int fqgpu_dblocks_decode_indexing(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks) {
+  int rc = dblocks_decode(ctx, blocks, n_blocks, true);
+  if (rc) {
+    for (size_t i = 0; blocks && i < n_blocks; i++)
+      if (blocks[i]) blocks[i]->index_bytes[0] = blocks[i]->index_bytes[1] = 0;
+    return rc;
+  }
+  if ((rc = fqgpu_sync(ctx))) return rc;
+  for (size_t i = 0; i < n_blocks; i++) {
+    const int brc = pull_result(blocks[i], false);
+    if (brc) blocks[i]->index_bytes[0] = blocks[i]->index_bytes[1] = 0;
+    if (brc && brc != FQGPU_E_CORRUPT && brc != FQGPU_E_ARG) return brc;  // (a HIP error; the block's own verdict is its status)
+  }
+  return FQGPU_OK;
 }
 
 // ------------------------------------------------------------------ host-pointer convenience calls
@@ -992,6 +1015,7 @@ static int hp_block_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size_
   b->seq_alloc = ctx->hp_seq; b->qual_alloc = ctx->hp_qual;
   b->seq_len = b->qual_len = b->n_pos_len = 0;
   b->index_bytes[0] = b->index_bytes[1] = 0;
+  ctx->hp_index_built = false;
   b->last_op = 0;
   b->result_pulled = true;
   memset(&b->host_result, 0, sizeof(b->host_result));
@@ -1272,6 +1296,7 @@ struct DecStreams {
   const uint16_t *n_count; size_t n_count_len;
   const uint16_t *n_pos;   size_t n_pos_len;
   const uint8_t *index[2]; size_t index_len[2];
+  bool build_index = false;  // decode by the indexing walk: the staging block is left with both indexes (index / index_len: none)
   bool ok() const {
     return seq && qual && n_count && seq_len && qual_len && (index[0] || !index_len[0]) && (index[1] || !index_len[1]);
   }
@@ -1288,7 +1313,8 @@ static int hp_decode_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size
 
 // The common part of the host-pointer decodes, once the staging block holds the layout: uploads the streams, decodes
 // (plan != NULL: its strides and window alone) and, when the kernels are through, copies back len bytes of the block from
-// offset skip and, recs_out != NULL, the records [first, first + n_out) with their offsets relative to skip.
+// offset skip (out == NULL: nothing of the block) and, recs_out != NULL, the records [first, first + n_out) with their
+// offsets relative to skip.
 static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s, const FqStridePlan *plan, uint8_t *out, size_t skip,
                             size_t len, fqgpu_rec *recs_out, size_t first, size_t n_out) {
   int rc;
@@ -1311,7 +1337,7 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
   b->last_op = 2;
   b->result_pulled = false;
   fqgpu_dblock *one[1] = {b};
-  if ((rc = fq_decode_launch(ctx, one, 1, plan))) return hp_fail(ctx, rc);
+  if ((rc = fq_decode_launch(ctx, one, 1, plan, s.build_index))) return hp_fail(ctx, rc);
   if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
   // The copies back are issued only when the kernels are through: a copy that waits in a DMA
   // engine's queue for a 13 s decode kernel holds that engine, and the uploads of the next workers'
@@ -1319,7 +1345,7 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
   // the third worker's fifth hipMemcpyAsync returning after 12.8 s).
   FQ_HIP_HP(hipStreamSynchronize(st));
   FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
-  FQ_HIP_HP(hipMemcpyAsync(out, b->raw + skip, len, hipMemcpyDeviceToHost, st));
+  if (out) FQ_HIP_HP(hipMemcpyAsync(out, b->raw + skip, len, hipMemcpyDeviceToHost, st));
   if (recs_out) FQ_HIP_HP(hipMemcpyAsync(recs_out, b->recs + first, n_out * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, st));
   FQ_HIP_HP(hipStreamSynchronize(st));
   for (size_t i = 0; recs_out && skip && i < n_out; i++) {
@@ -1328,9 +1354,14 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
   }
   b->host_result = *ctx->hp_result;
   b->result_pulled = true;
-  if (b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol) return FQGPU_E_ARG;
-  if (b->host_result.s[0].corrupt || b->host_result.s[1].corrupt) return FQGPU_E_CORRUPT;
-  return FQGPU_OK;
+  const int verdict = b->host_result.s[0].bad_symbol || b->host_result.s[1].bad_symbol ? FQGPU_E_ARG
+                      : b->host_result.s[0].corrupt || b->host_result.s[1].corrupt     ? FQGPU_E_CORRUPT
+                                                                                         : FQGPU_OK;
+  if (s.build_index) {
+    if (verdict) b->index_bytes[0] = b->index_bytes[1] = 0;
+    ctx->hp_index_built = !verdict;
+  }
+  return verdict;
 }
 
 static int hp_decode(fqgpu_ctx *ctx, const DecStreams &s, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out, size_t raw_len) {
@@ -1401,16 +1432,14 @@ static int layout_verdict(unsigned long long bad, unsigned long long total, size
 }
 
 // Both passes of decodeChunk on the device (decode_headers.hip, then the decode above): only the side streams go up.
-extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
-                                  const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
-                                  const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
-                                  const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
-                                  uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
+// s.build_index: by the indexing walk, raw_out may be NULL (nothing of the chunk comes back).
+static int decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, const DecStreams &s,
+                        uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
+  const size_t n_count_len = s.n_count_len;
+  if (ctx && s.build_index) ctx->hp_index_built = false;
   if (bad_record) *bad_record = (size_t)-1;
   if (laid_out_len) *laid_out_len = 0;
-  if (!raw_out || !laid_out_len || !bad_record) return FQGPU_E_ARG;
-  const DecStreams s = {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
-                        {seq_index_len, qual_index_len}};
+  if ((!raw_out && !s.build_index) || !laid_out_len || !bad_record) return FQGPU_E_ARG;
   size_t n_bases = 0;
   int rc = chunk_front(ctx, hdr, readlens, n_recs, s, raw_len, nullptr, &n_bases);
   if (rc) return rc;
@@ -1422,6 +1451,42 @@ extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hd
   *laid_out_len = (size_t)total;
   if (total < raw_len) FQ_HIP_HP(hipMemsetAsync(b->raw + total, 0, raw_len - total, ctx->stream));
   return hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, recs_out, 0, n_recs);
+}
+
+extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                  const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                  const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                  const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
+                                  uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
+  return decode_chunk(ctx, hdr, readlens, n_recs, {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len,
+                                                   {seq_index, qual_index}, {seq_index_len, qual_index_len}},
+                      raw_out, raw_len, recs_out, laid_out_len, bad_record);
+}
+
+// fqgpu_decode_chunk from the streams alone, by the indexing walk: the chunk's decode indexes stay on the staging block
+// for fqgpu_decode_index.
+extern "C" int fqgpu_decode_chunk_indexing(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                           const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                           const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                           uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len,
+                                           size_t *bad_record) {
+  return decode_chunk(ctx, hdr, readlens, n_recs, {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len,
+                                                   {nullptr, nullptr}, {0, 0}, true},
+                      raw_out, raw_len, recs_out, laid_out_len, bad_record);
+}
+
+// The decode index fqgpu_decode_chunk_indexing built, until the handle's next host-pointer call.
+extern "C" int fqgpu_decode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len) {
+  if (len) *len = 0;
+  if (!ctx || !ctx->hp_block || stream < 0 || stream > 1 || !len || !ctx->hp_index_built) return FQGPU_E_ARG;
+  const fqgpu_dblock *b = ctx->hp_block;
+  *len = b->index_bytes[stream];
+  if (!out || !*len) return FQGPU_OK;
+  if (cap < *len) { *len = 0; return FQGPU_E_ARG; }
+  int rc = use_device(ctx->device);
+  if (!rc && hipMemcpy(out, b->index[stream], *len, hipMemcpyDeviceToHost) != hipSuccess) rc = FQGPU_E_HIP;
+  if (rc) *len = 0;
+  return rc;
 }
 
 // fqgpu_decode_chunk_range's plan for the records [first, end) of a chunk.  rs: rec_start (n + 1 entries, strictly

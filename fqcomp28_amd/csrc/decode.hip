@@ -631,6 +631,212 @@ k_decode_both(const DecJob *__restrict__ jobs, unsigned n_blocks, TabView seq_ta
   else decode_stream<SeqModel, false>(jobs[blockIdx.x - n_blocks], seq_tab, ce, bitbuf);
 }
 
+// ---- the indexing walk (extension): a decode that leaves the decode index behind ----------------
+// A decoder that walks a stream from its end passes through every snapshot point and has there what a
+// snapshot holds: the bit position, the bytes the model has just seen, the state of every context.  So
+// this is decode_stream with decode_chunk's bookkeeping: strides n_snap, n_snap - 1, .. 0 in ONE
+// workgroup, the LDS slots and the bit reader carried over from stride to stride instead of loaded
+// from a snapshot.  Each time the symbols [k stride, n_sym) are done, snapshot k is taken.
+//
+// The walk keeps no states, only the DTable ENTRY of every context's current state (CtxEntry), and
+// step() is left alone: at a boundary the refills in flight are drained and the B entries go to a
+// scratch row as they are; k_resolve_states, behind the walks and wide, finds the state whose table
+// word is that entry.  The bit position goes straight to the index; header and `prev` bytes are
+// written behind the N restoration by k_dindex_meta, from the RESTORED block, exactly as the
+// encoder's k_index_meta writes them from the block it coded.  (An index from a device encode WITH
+// N -> A write-back holds 'A' where this one holds 'N' in `prev`; both seed the model alike.)
+struct IdxJob {
+  uint32_t *entries[2];  // per stream [n_snap][B] entries of the contexts at every snapshot
+  uint8_t *index[2];     // the decode index being built (header + n_snap snapshots)
+  unsigned n_sym, stride, n_snap;
+};
+typedef FQ_GLOBAL uint32_t g_u32;
+
+// the history decode_chunk seeds from a snapshot's `prev` (bytes p-1 .. p-4, 0xFF in front of the read)
+template <class M>
+__device__ __forceinline__ void seed_history(CtxHist<M> &h, unsigned prev) {
+  h.start();
+  if constexpr (M::STREAM == 0) {
+    for (int b = 3; b >= 0; b--) {
+      const unsigned ch = (prev >> (8 * b)) & 0xFFu;
+      if (ch != 0xFFu) h.seed(fq_base_code(ch) * 8u);
+    }
+  } else {
+    const unsigned a = prev & 0xFFu, b = (prev >> 8) & 0xFFu, c = (prev >> 16) & 0xFFu;
+    h.set(a != 0xFFu ? ((a - 33u) & 63u) * 8u : 0u, b != 0xFFu ? ((b - 33u) & 63u) * 8u : 0u,
+          c != 0xFFu ? ((c - 33u) & 63u) * 8u : 0u);
+  }
+}
+
+template <class M>
+__device__ void decode_stream_indexing(const DecJob &j, const IdxJob &x, const TabView &tab, CtxEntry *ce, uint32_t *bitbuf) {
+  constexpr unsigned B = M::B;
+  const uint8_t *src = M::STREAM == 0 ? j.seq : j.qual;
+  const unsigned len = M::STREAM == 0 ? j.seq_len : j.qual_len;
+  StreamResult *res = &j.res->s[M::STREAM];
+  const unsigned lane = threadIdx.x;
+  g_cu32 *w = (g_cu32 *)reinterpret_cast<const uint32_t *>(src);
+  g_crec *recs = (g_crec *)j.recs;
+  g_cu32 *rec_start = (g_cu32 *)j.rec_start;
+  g_u8 *raw = (g_u8 *)j.raw;
+  g_u32 *rows = (g_u32 *)x.entries[M::STREAM];
+  g_u8 *snaps = (g_u8 *)x.index[M::STREAM] + sizeof(FqIndexHeader);
+  const unsigned stride = x.stride;
+  const lds_CtxEntry *lce = (const lds_CtxEntry *)ce;
+
+  // the checks and the state load of decode_stream
+  if (__ballot(1) != ~0ull) { res->corrupt = 1; return; }
+  const unsigned last = len ? src[len - 1] : 0u;
+  if (last == 0) { if (lane == 0) res->corrupt = 1; return; }
+  const long long p0 = (long long)(len - 1) * 8 + (31 - __clz((int)last));
+  const unsigned sum_logs = tab.log_prefix[B];
+  if (p0 < (long long)sum_logs) { if (lane == 0) res->corrupt = 1; return; }
+  for (unsigned c = lane; c < B; c += 64) {
+    const unsigned lg = tab.logs[c];
+    const long long lo = p0 - (long long)(sum_logs - tab.log_prefix[c]);
+    const uint32_t table = tab.dt_off[c] + 1u;
+    set_slot(ce, c, table, tab.dt[table + peek_bits(w, lo, lg)]);
+  }
+  __syncthreads();
+  WalkT<false> wk;
+  wk.init(ce, tab.dt, tab.dt_off);
+  LdsBits br;
+  br.init(w, p0 - (long long)sum_logs, bitbuf, (len + 3) / 4);
+
+  unsigned k = fq_uniform(x.n_snap);  // the next snapshot to take: behind symbol k * stride (0: none left)
+  for (unsigned r = j.n_recs; r > 0 && !br.underflow; r--) {  // records last -> first
+    fqgpu_rec rec;
+    rec.seq_off = recs[r - 1].seq_off; rec.qual_off = recs[r - 1].qual_off; rec.len = recs[r - 1].len;
+    const unsigned rs = fq_uniform(rec_start[r - 1]);  // position i of the record has encode index rs + len - 1 - i
+    g_u8 *line = raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
+    CtxHist<M> h;
+    h.start();
+    unsigned i0 = 0;
+    // a boundary inside this record (k * stride < rs + len holds: the symbols behind are done): the record is walked in pieces
+    while (k && (unsigned long long)k * stride >= rs) {
+      const unsigned i1 = rs + rec.len - k * stride;  // one past the position of symbol k * stride
+      h.uniform();
+      walk_positions<M, false>(wk, br, line, i0, i1, h);
+      if (br.underflow) break;
+      // snapshot k: every refill has landed (the compiler does not know of them), no slot is left marked; the entries
+      // as they are, all lanes
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      g_u32 *row = rows + (size_t)(k - 1) * B;
+      unsigned pending = 0;
+      for (unsigned c = lane; c < B; c += 64) {
+        const uint32_t e = lce[c].entry;
+        pending |= (unsigned)(e == FQ_ENTRY_PENDING);
+        row[c] = e;
+      }
+      const bool any_pending = __ballot(pending != 0) != 0ull;
+      if (lane == 0) {
+        *reinterpret_cast<FQ_GLOBAL unsigned long long *>(snaps + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B)) = (unsigned long long)br.pos();
+        if (any_pending) res->corrupt = 1;
+      }
+      // the model's history in front of position i1, from the bytes just decoded (their stores are through: vmcnt(0)
+      // above; read past this CU's vector cache, which may hold the line from before)
+      unsigned prev = 0;
+      for (unsigned i = 0; i < 4; i++)
+        prev |= (i1 >= i + 1 ? (unsigned)__hip_atomic_load(line + (i1 - 1u - i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFu) << (8 * i);
+      seed_history<M>(h, fq_uniform(prev));
+      i0 = i1;
+      k--;
+    }
+    if (br.underflow) break;
+    h.uniform();
+    walk_positions<M, false>(wk, br, line, i0, rec.len, h);
+  }
+  if (lane == 0) {
+    if (br.pos() != 0) res->corrupt = 1;
+    res->total_bits = (unsigned long long)(p0 - (long long)sum_logs);
+  }
+}
+
+// one workgroup per block: stream M of every block of the batch, resident form (an indexing pass has few chains;
+// a batch with more chains than places queues)
+template <class M>
+__global__ void __launch_bounds__(64)
+k_decode_indexing(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, TabView tab) {
+  __shared__ CtxEntry ce[M::B];
+  __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
+  decode_stream_indexing<M>(jobs[blockIdx.x], ijobs[blockIdx.x], tab, ce, bitbuf);
+}
+
+// both streams in one launch (grid = 2 * n_blocks, the quality streams first), as k_decode_both: one launch places a
+// quality and a sequence chain per CU and does not depend on two HIP streams running side by side
+__global__ void __launch_bounds__(64)
+k_decode_indexing_both(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, unsigned n_blocks, TabView seq_tab, TabView qual_tab) {
+  __shared__ CtxEntry ce[QualModel::B];
+  __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
+  if (blockIdx.x < n_blocks) decode_stream_indexing<QualModel>(jobs[blockIdx.x], ijobs[blockIdx.x], qual_tab, ce, bitbuf);
+  else decode_stream_indexing<SeqModel>(jobs[blockIdx.x - n_blocks], ijobs[blockIdx.x - n_blocks], seq_tab, ce, bitbuf);
+}
+
+// State of (snapshot, context) from its entry: the x with dt[dt_off[c] + 1 + x] == entry.  Inside one valid DTable the
+// entries are pairwise distinct (the occurrences of a symbol map to disjoint sub-ranges of the states, so newState
+// differs; different symbols differ in the symbol field), a degenerate table is decided by the LOWEST such x (a context
+// without symbols in the block gets 0, as k_index_states writes) and no match at all is a corrupt stream.
+// One wave per (context, 64 snapshots of a block): lane = snapshot; the context's table is read once, 64 words at
+// a time and coalesced, and handed round the wave word by word.  Reads stay inside [dt_off[c] + 1, dt_off[c] + 1 + (1 << log)).
+template <class M>
+__global__ void __launch_bounds__(64)
+k_resolve_states(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, TabView tab) {
+  constexpr unsigned B = M::B;
+  const unsigned c = blockIdx.x, lane = threadIdx.x;
+  const IdxJob x = ijobs[blockIdx.z];
+  if (blockIdx.y * 64u >= x.n_snap) return;
+  const unsigned k = blockIdx.y * 64u + lane + 1u;
+  const bool have = k <= x.n_snap;
+  const uint32_t entry = have ? x.entries[M::STREAM][(size_t)(k - 1) * B + c] : 0u;
+  const unsigned size = 1u << tab.logs[c];
+  const uint32_t *t = tab.dt + tab.dt_off[c] + 1u;
+  unsigned best = ~0u;
+  for (unsigned x0 = 0; x0 < size; x0 += 64) {
+    const uint32_t word = x0 + lane < size ? t[x0 + lane] : FQ_ENTRY_PENDING;  // (no entry: never equal to one the walk let through)
+#pragma unroll
+    for (int i = 0; i < 64; i++) {
+      const uint32_t wi = (uint32_t)__builtin_amdgcn_readlane((int)word, i);
+      if (wi == entry) best = min(best, x0 + (unsigned)i);
+    }
+  }
+  if (!have) return;
+  if (best >= size) {
+    jobs[blockIdx.z].res->s[M::STREAM].corrupt = 1;
+    best = 0;
+  }
+  reinterpret_cast<uint16_t *>(x.index[M::STREAM] + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B) +
+                               FQ_INDEX_SNAP_HEAD)[c] = (uint16_t)best;
+}
+
+// Header and `prev` bytes of the index being built, behind the N restoration: what the encoder's k_index_meta
+// (enc_index.h) writes, from the restored block.  The bit positions are the walk's.
+template <class M>
+__global__ void __launch_bounds__(256)
+k_dindex_meta(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs) {
+  const DecJob j = jobs[blockIdx.y];
+  const IdxJob x = ijobs[blockIdx.y];
+  uint8_t *index = x.index[M::STREAM];
+  const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;  // 0: header, 1 .. n_snap: snapshots
+  if (k == 0) {
+    FqIndexHeader h;
+    h.magic = FQ_INDEX_MAGIC; h.stream = M::STREAM; h.stride = x.stride; h.n_snap = x.n_snap;
+    h.n_sym = x.n_sym; h.reserved = 0;
+    *reinterpret_cast<FqIndexHeader *>(index) = h;
+    return;
+  }
+  if (k > x.n_snap) return;
+  const unsigned e = k * x.stride;
+  uint8_t *snap = index + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)M::B);
+  const unsigned r = fq_locate(j.rec_start, 0, j.n_recs - 1, e - 1);  // symbol e - 1: record r, position p
+  const fqgpu_rec rec = j.recs[r];
+  const unsigned p = rec.len - 1u - (e - 1u - j.rec_start[r]);
+  const uint8_t *line = j.raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
+  unsigned packed = 0;
+  for (unsigned i = 0; i < 4; i++) packed |= (p >= i + 1 ? (unsigned)line[p - 1 - i] : 0xFFu) << (8 * i);
+  reinterpret_cast<uint32_t *>(snap)[2] = packed;
+  reinterpret_cast<uint32_t *>(snap)[3] = 0;
+}
+
 // batch-wide record arrays: N counts widened for the scan
 __global__ void __launch_bounds__(256)
 k_gather_ncount(const DecJob *__restrict__ jobs, uint32_t *__restrict__ cnt32) {
@@ -706,11 +912,14 @@ static int dec_stream2_ensure(fqgpu_ctx *ctx) {
 }
 
 // plan (fqgpu_decode_chunk_range): ONE block that holds both decode indexes, walked over the plan's strides alone
-int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan) {
+int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan, bool build_index) {
   hipStream_t st = ctx->stream;
   if (!n_blocks) return FQGPU_OK;
+  if (build_index && plan) return FQGPU_E_ARG;
   int rcs = fqgpu_sync(ctx);  // blocks may still be in an encode lane
   if (rcs) return rcs;
+  if (build_index)  // (an index the block holds is ignored and replaced: every block goes the plain way below)
+    for (size_t i = 0; i < n_blocks; i++) blocks_in[i]->index_bytes[0] = blocks_in[i]->index_bytes[1] = 0;
   // blocks with a decode index (both streams, at least one snapshot) go to the chunk kernel, the
   // others to the one-lane-per-stream kernel: plain blocks first in the job array
   auto snaps_of = [](const fqgpu_dblock *b, int stream) -> size_t {
@@ -746,7 +955,7 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     j.rec_start = nullptr;
     r_tot += b->n_recs;
     if (b->n_recs > r_max) r_max = b->n_recs;
-    if (i >= n_plain) rs_tot += b->n_recs + 1;
+    if (i >= n_plain || build_index) rs_tot += b->n_recs + 1;
   }
   int rc;
   size_t n_qual_chunks = 0;
@@ -782,6 +991,50 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     if ((rc = ctx->dec_chunks.reserve(chunks.size() * sizeof(DecChunk)))) return rc;
     FQ_HIP(hipMemcpyAsync(ctx->dec_chunks.p, chunks.data(), chunks.size() * sizeof(DecChunk), hipMemcpyHostToDevice, st));
   }
+  // the indexing decode: room for both indexes on every block and for the entries at every snapshot, rec_start as above
+  std::vector<IdxJob> ihost;
+  unsigned snap_max = 0;
+  if (build_index) {
+    const unsigned stride = ctx->index_stride;
+    ihost.resize(n_blocks);
+    size_t words = 0;
+    for (size_t i = 0; i < n_blocks; i++) {
+      fqgpu_dblock *b = blocks[i];
+      if (!b->n_bases || b->n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
+      IdxJob &x = ihost[i];
+      x.n_sym = (unsigned)b->n_bases; x.stride = stride; x.n_snap = (x.n_sym - 1) / stride;
+      snap_max = x.n_snap > snap_max ? x.n_snap : snap_max;
+      for (int s = 0; s < 2; s++) {
+        const size_t bytes = sizeof(FqIndexHeader) + (size_t)x.n_snap * fq_index_snap_bytes(s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
+        if (bytes > b->index_cap[s]) {
+          if (b->index[s]) FQ_HIP(hipFree(b->index[s]));
+          b->index[s] = fq_dev_alloc<uint8_t>(bytes + 64);
+          b->index_cap[s] = b->index[s] ? bytes : 0;
+          if (!b->index[s]) return FQGPU_E_NOMEM;
+        }
+        x.index[s] = b->index[s];
+      }
+      words += (size_t)x.n_snap * (FQGPU_SEQ_MODELS + FQGPU_QUAL_MODELS);
+    }
+    if ((rc = ctx->dec_idx.reserve(n_blocks * sizeof(IdxJob)))) return rc;
+    if ((rc = ctx->dec_entries.reserve(words * 4 + 64))) return rc;
+    if ((rc = ctx->dec_recstart.reserve(rs_tot * 4 + 64))) return rc;
+    size_t at = 0, wat = 0;
+    for (size_t i = 0; i < n_blocks; i++) {
+      const fqgpu_dblock *b = blocks[i];
+      IdxJob &x = ihost[i];
+      x.entries[0] = ctx->dec_entries.as<uint32_t>() + wat;
+      x.entries[1] = x.entries[0] + (size_t)x.n_snap * FQGPU_SEQ_MODELS;
+      wat += (size_t)x.n_snap * (FQGPU_SEQ_MODELS + FQGPU_QUAL_MODELS);
+      uint32_t *rs = ctx->dec_recstart.as<uint32_t>() + at;
+      host[i].rec_start = rs;
+      at += b->n_recs + 1;
+      hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
+                         ctx->n_cnt32.as<uint32_t>());
+      if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp))) return rc;
+    }
+    FQ_HIP(hipMemcpyAsync(ctx->dec_idx.p, ihost.data(), n_blocks * sizeof(IdxJob), hipMemcpyHostToDevice, st));
+  }
   hipError_t he = hipMemcpyAsync(ctx->dec_desc.p, host.data(), n_blocks * sizeof(DecJob), hipMemcpyHostToDevice, st);
   if (he == hipSuccess) he = hipStreamSynchronize(st);  // the host vectors die with this call
   if (he != hipSuccess) return fq_hip_error(he, __FILE__, __LINE__);
@@ -798,7 +1051,13 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   FQ_HIP(hipEventRecord(ctx->dec_fork, st));
   FQ_HIP(hipStreamWaitEvent(st2, ctx->dec_fork, 0));
   const DecChunk *dch = ctx->dec_chunks.as<DecChunk>();
-  if (n_plain && 2 * n_plain <= 2 * (size_t)ctx->n_cus) {
+  const IdxJob *ijobs = ctx->dec_idx.as<IdxJob>();
+  if (build_index && n_blocks <= (size_t)ctx->n_cus) {  // (the placement rule of the plain decode)
+    hipLaunchKernelGGL(k_decode_indexing_both, dim3((unsigned)(2 * n_blocks)), dim3(64), 0, st, jobs, ijobs, (unsigned)n_blocks, ts, tq);
+  } else if (build_index) {
+    hipLaunchKernelGGL(k_decode_indexing<QualModel>, dim3((unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, tq);
+    hipLaunchKernelGGL(k_decode_indexing<SeqModel>, dim3((unsigned)n_blocks), dim3(64), 0, st2, jobs, ijobs, ts);
+  } else if (n_plain && 2 * n_plain <= 2 * (size_t)ctx->n_cus) {
     hipLaunchKernelGGL(k_decode_both, dim3((unsigned)(2 * n_plain)), dim3(64), 0, st, jobs, (unsigned)n_plain, ts, tq);
   } else if (n_plain) {
     // more quality chains than places for the resident form (two 66 KB workgroups per CU): the compact form
@@ -825,6 +1084,21 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   hipLaunchKernelGGL(k_npatch, dim3(gp ? gp : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
                      ctx->n_off.as<uint32_t>(), plan ? plan->w0 : 0u, plan ? plan->w1 : ~0u);
   fq_timer_span_end(ctx, st);
+  if (build_index) {
+    fq_timer_span_begin(ctx, "dindex", st);
+    const dim3 gm(snap_max / 256 + 1, (unsigned)n_blocks);
+    hipLaunchKernelGGL(k_dindex_meta<SeqModel>, gm, dim3(256), 0, st, jobs, ijobs);
+    hipLaunchKernelGGL(k_dindex_meta<QualModel>, gm, dim3(256), 0, st, jobs, ijobs);
+    if (snap_max) {
+      const unsigned gy = (snap_max + 63) / 64;
+      hipLaunchKernelGGL(k_resolve_states<SeqModel>, dim3(FQGPU_SEQ_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, ts);
+      hipLaunchKernelGGL(k_resolve_states<QualModel>, dim3(FQGPU_QUAL_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, tq);
+    }
+    fq_timer_span_end(ctx, st);
+    for (size_t i = 0; i < n_blocks; i++)
+      for (int s = 0; s < 2; s++)
+        blocks[i]->index_bytes[s] = sizeof(FqIndexHeader) + (size_t)ihost[i].n_snap * fq_index_snap_bytes(s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
+  }
   FQ_HIP(hipGetLastError());
   return FQGPU_OK;
 }

@@ -243,6 +243,7 @@ struct fqgpu_ctx {
   DevBuf n_cnt32, n_off, scan_tmp;
   DevBuf dec_desc;    // decode job descriptors
   DevBuf dec_chunks, dec_recstart;  // chunk list and per-block rec_start of the indexed decode
+  DevBuf dec_idx, dec_entries;      // indexing decode: its job descriptors, the contexts' entries at every snapshot
   KernelTimer *timer = nullptr;
   // staging block of the host-pointer calls, kept between calls (grow-only device buffers)
   fqgpu_dblock *hp_block = nullptr;
@@ -256,6 +257,7 @@ struct fqgpu_ctx {
   size_t hp_used = 0;                 // bytes of the chunk up to its last complete record
   HdrScratch hp_hdr;                  // fqgpu_encode_headers_*: the header fields of the block in flight
   ChunkScratch hp_chunk;              // fqgpu_decode_chunk: header decode and layout
+  bool hp_index_built = false;        // the staging block holds the indexes fqgpu_decode_chunk_indexing built (fqgpu_decode_index)
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -341,7 +343,11 @@ struct FqStridePlan {
   unsigned w0, w1;
   const uint32_t *rec_start;
 };
-int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks, const FqStridePlan *plan = nullptr);
+// build_index (no plan): every block is walked from its streams' ends by the indexing walk, whatever index it holds, and
+// is left with both decode indexes, stride ctx->index_stride (index_bytes set; a caller that finds the block's streams
+// corrupt drops them)
+int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks, const FqStridePlan *plan = nullptr,
+                     bool build_index = false);
 int fq_wipe_launch(fqgpu_ctx *ctx, fqgpu_dblock *b);
 int fq_qual_counts_sorted(hipStream_t st, const uint8_t *raw_dev, const fqgpu_rec *recs_dev, size_t n_recs, size_t n_bases,
                           uint32_t *counts_dev, uint32_t *err_dev);

@@ -21,6 +21,7 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 
 #include "archive.hpp"
 
@@ -46,6 +47,11 @@ struct Settings {  // the part of src/settings.h:36-50 this path needs, plus the
    *  about 2 % of the archive's size); decompress uses the file whenever it lies beside the archive. */
   bool decode_index = false;
   unsigned index_stride = 0;  // symbols between two snapshots of a decode index (multiple of 64 Ki; 0 = 1 Mi)
+  /** Extension: decompress of an archive WITHOUT a usable `<archive>.fqx` builds one while it restores (one serial pass,
+   *  at the pace the format dictates anyway: DecompressionWorkspace::setBuildIndex); every later restore and every
+   *  --records query then runs at the indexed pace.  With a usable file nothing is built. */
+  bool build_index = false;
+  bool index_only = false;  // ... and nothing is restored (processArchiveIndex sets it)
 };
 
 struct InputStats {  // src/report.h
@@ -61,6 +67,9 @@ struct FarmReport {
   CompressedStats out;
   double seconds = 0;          // wall clock over the worker threads (tables and handles built before)
   std::vector<unsigned> blocks_per_worker;
+  // decode indexes: blocks decoded from one and the bytes read (index_built false), or blocks given one and the bytes written
+  std::size_t indexed_blocks = 0, index_bytes = 0;
+  bool index_built = false;
 };
 
 namespace detail {
@@ -213,7 +222,10 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
   const unsigned T = std::max(1u, set.n_threads);
   if (set.devices.empty()) throw std::invalid_argument("decompressFarm: no device");
   std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
-  detail::runWorkers(T, [&](unsigned t) { wksp[t] = std::make_unique<DecompressionWorkspace>(&meta, set.devices[t % set.devices.size()]); });
+  detail::runWorkers(T, [&](unsigned t) {
+    wksp[t] = std::make_unique<DecompressionWorkspace>(&meta, set.devices[t % set.devices.size()]);
+    wksp[t]->setBuildIndex(set.build_index, set.index_stride, set.index_only);
+  });
   std::vector<InputStats> istats(T);
   FarmReport rep;
   rep.blocks_per_worker.assign(T, 0);
@@ -228,9 +240,11 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
       wksp[t]->decodeChunk(chunk, cbs);
       clk.lap("decodeChunk");
       istats[t].raw += chunk.raw_data.size();
-      istats[t].n_records += chunk.records.size();
+      istats[t].n_records += cbs.original_size.n_records;
       rep.blocks_per_worker[t]++;
-      write_chunk(chunk);
+      // (a sink that also takes the block's buffers sees the decode indexes the workspace built)
+      if constexpr (std::is_invocable_v<Sink &, const FastqChunk &, const CompressedBuffersSrc &>) write_chunk(chunk, cbs);
+      else write_chunk(chunk);
       clk.lap("write");
       clk.done(chunk.idx);
     }
@@ -260,20 +274,97 @@ inline std::unique_ptr<DecodeIndexFile> openDecodeIndex(const path_t &archive_pa
 }
 }  // namespace detail
 
-/** processArchiveParts (src/process.cpp:84-105): archive in, file out (chunks in original order) */
+namespace detail {
+/** A decode index file in the making: `<archive>.fqx.part` until every block's indexes are in it, then closed for the
+ *  archive and renamed over whatever `<archive>.fqx` was; a build that does not get there leaves no file (FastqWriter
+ *  works the same way) and the old one untouched. */
+class DecodeIndexBuilder {
+public:
+  explicit DecodeIndexBuilder(const path_t &archive_path)
+      : archive_(archive_path), final_(DecodeIndexFile::pathFor(archive_path)), part_(final_.string() + ".part"),
+        file_(std::make_unique<DecodeIndexFile>(part_, PosFile::Mode::Create)) {}
+  ~DecodeIndexBuilder() {
+    if (done_) return;
+    file_.reset();
+    std::error_code ec;
+    std::filesystem::remove(part_, ec);
+  }
+  /** thread-safe */
+  void put(const CompressedBuffersSrc &cbs) {
+    if (cbs.decode_index[0].empty() || cbs.decode_index[1].empty())
+      throw std::runtime_error("no decode index was built for chunk " + std::to_string(cbs.chunk_idx));
+    file_->put(cbs);
+    blocks_.fetch_add(1);
+    bytes_.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
+  }
+  void finish(FarmReport &rep) {
+    file_->close(DecodeIndexFile::identityOf(archive_));
+    file_.reset();
+    std::filesystem::rename(part_, final_);
+    done_ = true;
+    rep.index_built = true;
+    rep.indexed_blocks = blocks_.load();
+    rep.index_bytes = bytes_.load();
+  }
+
+private:
+  path_t archive_, final_, part_;
+  std::unique_ptr<DecodeIndexFile> file_;
+  std::atomic<std::size_t> blocks_{0}, bytes_{0};
+  bool done_ = false;
+};
+}  // namespace detail
+
+/** processArchiveParts (src/process.cpp:84-105): archive in, file out (chunks in original order).  set.build_index: an
+ *  archive without a usable decode index file gets one on the way (and the report says so); with one, it is used as always
+ *  and nothing is built. */
 inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &mates1_out, const Settings &set) {
   Archive archive(archive_path);
   FastqWriter writer(mates1_out, archive.chunkOffsets());
   std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  std::unique_ptr<detail::DecodeIndexBuilder> builder;
+  Settings farm = set;
+  farm.build_index = set.build_index && !sidecar;
+  farm.index_only = false;
+  if (farm.build_index) builder = std::make_unique<detail::DecodeIndexBuilder>(archive_path);
+  std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
   FarmReport rep = decompressFarm(
       archive.meta(),
       [&](CompressedBuffersSrc &cbs) {
         if (!archive.readBlock(cbs)) return false;
-        if (sidecar) (void)sidecar->get(cbs);  // (a chunk the file has no entry for is decoded without)
+        if (sidecar && sidecar->get(cbs)) {  // (a chunk the file has no entry for is decoded without)
+          used_blocks.fetch_add(1);
+          used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
+        }
         return true;
       },
-      [&](const FastqChunk &chunk) { writer.writeChunk(chunk); }, [&] { archive.abort(); }, set);
+      [&](const FastqChunk &chunk, const CompressedBuffersSrc &cbs) {
+        writer.writeChunk(chunk);
+        if (builder) builder->put(cbs);
+      },
+      [&] { archive.abort(); }, farm);
   writer.flush();
+  rep.indexed_blocks = used_blocks.load();
+  rep.index_bytes = used_bytes.load();
+  if (builder) builder->finish(rep);
+  return rep;
+}
+
+/** Extension: `x` -- the decode index file of an existing archive, and nothing else: every block is walked once from its
+ *  streams' ends, only its indexes come back from the device, no FASTQ is written.  Always builds afresh: a stale,
+ *  foreign, unclosed or damaged `<archive>.fqx` is not opened and is replaced when the last block has succeeded. */
+inline FarmReport processArchiveIndex(const path_t &archive_path, const Settings &set) {
+  Archive archive(archive_path);
+  detail::DecodeIndexBuilder builder(archive_path);
+  Settings farm = set;
+  farm.build_index = farm.index_only = true;
+  FarmReport rep = decompressFarm(
+      archive.meta(),
+      [&](CompressedBuffersSrc &cbs) {
+        return archive.readBlock(cbs);  // (without decode indexes: readBlock clears the buffers)
+      },
+      [&](const FastqChunk &, const CompressedBuffersSrc &cbs) { builder.put(cbs); }, [&] { archive.abort(); }, farm);
+  builder.finish(rep);
   return rep;
 }
 
@@ -336,7 +427,7 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
   std::vector<InputStats> istats(T);
   FarmReport rep;
   rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0};
+  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
   std::atomic<bool> stopped{false};
   detail::runWorkers(T, [&](unsigned t) {
     CompressedBuffersSrc cbs;
@@ -347,7 +438,10 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
       const RangePiece &pc = pieces[p];
       StageClock clk;
       archive.readBlockAt(pc.block, cbs);
-      if (sidecar) (void)sidecar->get(cbs);
+      if (sidecar && sidecar->get(cbs)) {
+        used_blocks.fetch_add(1);
+        used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
+      }
       clk.lap("read");
       if (pc.whole) wksp[t]->decodeChunk(chunk, cbs);
       else wksp[t]->decodeChunkRange(chunk, cbs, pc.first, pc.end);
@@ -364,6 +458,8 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
   writer.flush();
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
+  rep.indexed_blocks = used_blocks.load();
+  rep.index_bytes = used_bytes.load();
   return rep;
 }
 

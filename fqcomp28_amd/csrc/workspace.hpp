@@ -468,6 +468,16 @@ class DecompressionWorkspace : public Workspace {
 public:
   explicit DecompressionWorkspace(const DatasetMeta *meta, int device = 0) : Workspace(meta, device) {}
 
+  /** Extension, the decode-side twin of CompressionWorkspace::setDecodeIndex: decodeChunk of a chunk that arrives WITHOUT
+   *  decode indexes builds them on the way (fqgpu_decode_chunk_indexing: one serial decode, at the pace the format dictates
+   *  anyway) and leaves them in cbs.decode_index; a chunk that arrives with its indexes is decoded from them as always.
+   *  index_only: such a chunk is not restored at all -- chunk.raw_data stays empty, nothing but the indexes comes back. */
+  void setBuildIndex(bool on, unsigned stride_symbols = 0, bool index_only = false) {
+    build_index_ = on;
+    index_only_ = on && index_only;
+    if (on && stride_symbols) fqgpuCheck(fqgpu_ctx_set_index_stride(ctx_, stride_symbols), "setBuildIndex");
+  }
+
   /** Both passes of decodeChunk (src/workspace.cpp:47-88): the first lays the chunk out
    *  (headers decoded, lengths from readlens, '+' and newlines), the second fills the sequence and quality lines.
    *  Both run on the GPU (fqgpu_decode_chunk: only the side streams go up, no skeleton).  FQGPU_SHIM_HOST_HEADERS=1
@@ -475,7 +485,8 @@ public:
    *  stream that runs out, a chunk too small for its records, a format it does not take) goes through the host path
    *  as well, so that the error is the host's. */
   void decodeChunk(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
-    if (!hostHeaders() && decodeChunkOnDevice(chunk, cbs)) return;
+    // (an index is built by the device path alone: FQGPU_SHIM_HOST_HEADERS does not apply to a chunk that is to get one)
+    if ((!hostHeaders() || buildsIndexFor(cbs)) && decodeChunkOnDevice(chunk, cbs)) return;
     StageClock clk;
     chunk.clear();  // prepareFastqChunk (src/workspace.h:127-133)
     chunk.idx = cbs.chunk_idx;
@@ -570,10 +581,13 @@ private:
   /** decodeChunk through fqgpu_decode_chunk; false: the device refused the chunk (the host path decides) */
   bool decodeChunkOnDevice(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
     StageClock clk;
+    const bool build = buildsIndexFor(cbs), restore = !(build && index_only_);
     chunk.clear();
     chunk.idx = cbs.chunk_idx;
-    if (chunk.raw_data.capacity() < cbs.original_size.total) chunk.raw_data.reserve(cbs.original_size.total + cbs.original_size.total / 16 + 4096);
-    chunk.raw_data.resize(cbs.original_size.total);
+    if (restore) {
+      if (chunk.raw_data.capacity() < cbs.original_size.total) chunk.raw_data.reserve(cbs.original_size.total + cbs.original_size.total / 16 + 4096);
+      chunk.raw_data.resize(cbs.original_size.total);
+    }
     clk.lap("resize");
     ChunkArgs a;
     if (!chunkArgs(cbs, a)) return false;
@@ -582,12 +596,25 @@ private:
     RecordTable recs(n);
     std::size_t laid_out = 0, bad = 0;
     const StreamArgs &s = a.s;
-    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, n, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len, s.n_pos,
-                                      s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1],
-                                      reinterpret_cast<uint8_t *>(chunk.raw_data.data()), chunk.raw_data.size(), recs.data(),
-                                      &laid_out, &bad);
+    uint8_t *raw_out = restore ? reinterpret_cast<uint8_t *>(chunk.raw_data.data()) : nullptr;
+    const int rc = build ? fqgpu_decode_chunk_indexing(ctx_, &a.hdr, a.readlens, n, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count,
+                                                       s.n_count_len, s.n_pos, s.n_pos_len, raw_out, cbs.original_size.total, recs.data(),
+                                                       &laid_out, &bad)
+                         : fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, n, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
+                                              s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], raw_out,
+                                              chunk.raw_data.size(), recs.data(), &laid_out, &bad);
     clk.lap("gpu");
     if (!deviceTook(rc, bad, "decodeChunk")) return false;
+    for (int k = 0; k < 2 && build; ++k) {
+      std::size_t len = 0;
+      fqgpuCheck(fqgpu_decode_index(ctx_, k, nullptr, 0, &len), "decodeChunk");
+      cbs.decode_index[k].resize(len);
+      fqgpuCheck(fqgpu_decode_index(ctx_, k, reinterpret_cast<uint8_t *>(cbs.decode_index[k].data()), len, &len), "decodeChunk");
+    }
+    if (!restore) {  // (no bytes to point into: the chunk names its position alone)
+      clk.done(chunk.idx);
+      return true;
+    }
     // the stream cursors where the host decoder leaves them: every stream consumed up to the chunk's last header
     for (std::size_t i = 0; i < nf; ++i) {
       auto &f = cbs.header_fields[i];
@@ -604,6 +631,12 @@ private:
     clk.lap("table");
     clk.done(chunk.idx);
     return true;
+  }
+
+  bool build_index_ = false, index_only_ = false;
+  /** setBuildIndex is on and this chunk came without indexes */
+  bool buildsIndexFor(const CompressedBuffersSrc &cbs) const {
+    return build_index_ && cbs.decode_index[0].empty() && cbs.decode_index[1].empty();
   }
 
   /** FQGPU_SHIM_HOST_HEADERS=1: the host coder lays the chunks out */

@@ -236,6 +236,17 @@ int fqgpu_dblock_encode(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned flags);
 int fqgpu_dblock_wipe(fqgpu_ctx *ctx, fqgpu_dblock *b);
 /* decodes every block of the batch from its own device-resident streams */
 int fqgpu_dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks);
+/* Extension: extends fqgpu_dblocks_decode for blocks that have no decode index (archives written without
+ * FQGPU_F_DECODE_INDEX, by another writer of the format, or whose sidecar is lost).  Decodes every block from its own
+ * streams exactly as fqgpu_dblocks_decode does without an index -- an index already loaded on a block is ignored and
+ * replaced -- and, on the way, leaves both decode indexes on the block (stride: fqgpu_ctx_set_index_stride), byte for
+ * byte what the block's encode with FQGPU_F_DECODE_INDEX leaves: fqgpu_dblock_index_bytes / _fetch_index hand them out,
+ * a following fqgpu_dblocks_decode uses them.  (The bytes in front of a snapshot are taken from the restored block:
+ * an index from fqgpu_dblock_encode WITH FQGPU_F_WRITE_BACK_N holds 'A' where this one holds 'N'; both seed the model
+ * alike.)  Unlike fqgpu_dblocks_decode the call waits for the batch.  Returns the codes of fqgpu_dblocks_decode; a block
+ * with a damaged stream reports FQGPU_E_CORRUPT through fqgpu_dblock_status as there and keeps no index (index_bytes 0
+ * for both streams); a block of at most `stride` symbols gets the 32-byte header alone. */
+int fqgpu_dblocks_decode_indexing(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks);
 int fqgpu_sync(fqgpu_ctx *ctx);
 /* status/sizes of the last encode/decode of this block.  If that operation is still in flight the
  * call waits for the block's handle first (the lanes run on non-blocking streams), so it never
@@ -332,6 +343,19 @@ int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const ui
                        const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
                        const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index, size_t qual_index_len,
                        uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record);
+
+/* Extension: fqgpu_decode_chunk for a chunk without decode indexes, which builds them while it decodes (as
+ * fqgpu_dblocks_decode_indexing; stride: fqgpu_ctx_set_index_stride).  The arguments of fqgpu_decode_chunk without the four
+ * index arguments; raw_out == NULL: index only -- nothing of the chunk comes back, *laid_out_len, recs_out and *bad_record
+ * as usual.  Afterwards fqgpu_decode_index(stream 0 / 1) hands the index of the chunk just decoded out, shaped like
+ * fqgpu_encode_index (out == NULL: *len alone), until the handle's next host-pointer call.
+ * Returns the codes of fqgpu_decode_chunk; after a failure no index is kept: fqgpu_decode_index then returns FQGPU_E_ARG
+ * with *len = 0 (also for cap < *len). */
+int fqgpu_decode_chunk_indexing(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record);
+int fqgpu_decode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len);
 
 /* Extension: records [first, end) of a chunk -- exactly the bytes fqgpu_decode_chunk would lay out for them, and
  * nothing else.  Inputs as fqgpu_decode_chunk; raw_len is the chunk's recorded size and judges the layout as there.

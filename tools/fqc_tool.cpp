@@ -1,10 +1,17 @@
 // fqc_tool -- the reference's two commands over the GPU block farm (fqcomp28_amd/csrc/process.hpp):
 //   fqc_tool c <in.fastq> <out.fqc> [-t threads] [-R block MiB] [-S sample MiB] [-d dev,dev,...] [--accumulate-n]
 //              [--index [--index-stride Ki symbols, a multiple of 64]]   (extension: decode indexes in <out.fqc>.fqx)
-//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--records A:B]
+//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--records A:B] [--index [--index-stride Ki]]
 //              (extension: --records restores records A .. B-1 only, numbered from 0 across the archive; A: = to the end)
+//              (extension: --index also leaves <in.fqc>.fqx behind if no usable one lies there: restore and index in one pass;
+//               --records never builds)
+//   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
+//              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
+//               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
+//               builds afresh and replaces the old file once the last block has succeeded)
 // (fqcomp28 c --i1 in.fastq -o out.fqc -t N / fqcomp28 d -i out.fqc --o1 out.fastq, src/app.cpp:29-76.)
-// Prints one JSON line with sizes, seconds and blocks per worker.  Needs a GPU: no CPU fallback.
+// Prints one JSON line with sizes, seconds and blocks per worker; d and x also say how many blocks were decoded from a decode
+// index ("index": "used") or were given one ("built"), and its bytes.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -14,14 +21,16 @@
 using namespace fqcomp28;
 
 int main(int argc, char **argv) {
-  if (argc < 4 || (strcmp(argv[1], "c") && strcmp(argv[1], "d"))) {
-    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--records A:B]\n");
+  const bool index_cmd = argc >= 2 && !strcmp(argv[1], "x");
+  if (argc < (index_cmd ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !index_cmd)) {
+    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--records A:B]\n"
+                         "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n");
     return 2;
   }
   Settings set;
   bool range = false;
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
-  for (int i = 4; i < argc; ++i) {
+  for (int i = index_cmd ? 3 : 4; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
     if (a == "-t") set.n_threads = (unsigned)std::atoi(val());
@@ -52,19 +61,28 @@ int main(int argc, char **argv) {
     } else if (a == "-d") {
       set.devices.clear();
       for (const char *p = val(); *p;) { set.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p) ++p; }
-    } else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); return 2; }
+    } else { std::fprintf(stderr, "unknown option %s\nusage: fqc_tool c|d <in> <out> [options] | fqc_tool x <in.fqc> [options]\n", a.c_str()); return 2; }
   }
   try {
     const bool comp = argv[1][0] == 'c';
-    const FarmReport r = comp    ? processReads(argv[2], argv[3], set)
-                         : range ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
-                                 : processArchiveParts(argv[2], argv[3], set);
+    if (!comp) {  // --index on the way back: build, not write
+      set.build_index = set.decode_index && !range;
+      set.decode_index = false;
+    }
+    const FarmReport r = index_cmd ? processArchiveIndex(argv[2], set)
+                         : comp    ? processReads(argv[2], argv[3], set)
+                         : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
+                                   : processArchiveParts(argv[2], argv[3], set);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
                 "\"seq_bytes\": %zu, \"qual_bytes\": %zu, \"misc_bytes\": %zu, \"seconds\": %.6f, \"blocks_per_worker\": [",
                 argv[1], set.n_threads, set.devices.size(), r.in.raw, r.in.n_records, comp ? r.out.n_blocks : (std::size_t)0,
                 r.out.seq, r.out.qual, r.out.misc, r.seconds);
     for (std::size_t i = 0; i < r.blocks_per_worker.size(); ++i) std::printf("%s%u", i ? ", " : "", r.blocks_per_worker[i]);
-    std::printf("]}\n");
+    std::printf("]");
+    if (!comp)
+      std::printf(", \"index\": \"%s\", \"indexed_blocks\": %zu, \"index_bytes\": %zu", r.index_built ? "built" : r.indexed_blocks ? "used" : "none",
+                  r.indexed_blocks, r.index_bytes);
+    std::printf("}\n");
   } catch (const std::exception &e) {
     std::fprintf(stderr, "fqc_tool: %s\n", e.what());
     return 1;
