@@ -609,8 +609,7 @@ static int index_header(int stream, size_t n_bases, const void *data, size_t len
   if (len < sizeof(h)) return FQGPU_E_CORRUPT;
   memcpy(&h, data, sizeof(h));
   if (h.magic != FQ_INDEX_MAGIC || h.stream != (uint32_t)stream || h.stride == 0 || (h.stride & 65535u) ||
-      h.n_sym != n_bases || h.n_snap != (h.n_sym ? (uint32_t)((h.n_sym - 1) / h.stride) : 0u) ||
-      len != sizeof(h) + (size_t)h.n_snap * fq_index_snap_bytes(B))
+      h.n_sym != n_bases || h.n_snap != fq_index_n_snap(h.n_sym, h.stride) || len != fq_index_bytes(h.n_snap, B))
     return FQGPU_E_CORRUPT;
   if (out) *out = h;
   return FQGPU_OK;
@@ -618,14 +617,7 @@ static int index_header(int stream, size_t n_bases, const void *data, size_t len
 
 static int index_accept(fqgpu_dblock *b, int stream, const void *data, size_t len) {
   const int rc = index_header(stream, b->n_bases, data, len, nullptr);
-  if (rc) return rc;
-  if (len > b->index_cap[stream]) {
-    if (b->index[stream]) (void)hipFree(b->index[stream]);
-    b->index[stream] = fq_dev_alloc<uint8_t>(len + 64);
-    b->index_cap[stream] = b->index[stream] ? len : 0;
-    if (!b->index[stream]) return FQGPU_E_NOMEM;
-  }
-  return FQGPU_OK;
+  return rc ? rc : fq_index_reserve(b, stream, len, false);
 }
 
 extern "C" int fqgpu_dblock_load_index(fqgpu_ctx *ctx, fqgpu_dblock *b, int stream, const void *data, size_t len) {
@@ -1249,19 +1241,30 @@ extern "C" int fqgpu_encode_end(fqgpu_ctx *ctx, uint8_t *raw, uint8_t *seq_out, 
   return FQGPU_OK;
 }
 
+// The staging block's decode index of stream s: its size to *len and, if there is an `out` and anything to bring, its bytes
+// (cap < *len: FQGPU_E_ARG) -- behind the stream `st`, or with a synchronous copy (st = nullptr).  *he: what the copy said.
+static int hp_index_fetch(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len, hipStream_t st, hipError_t *he) {
+  const fqgpu_dblock *b = ctx->hp_block;
+  *he = hipSuccess;
+  *len = b->index_bytes[stream];
+  if (!out || !*len) return FQGPU_OK;
+  if (cap < *len) return FQGPU_E_ARG;
+  const int rc = use_device(ctx->device);
+  if (rc) return rc;
+  if (!st) *he = hipMemcpy(out, b->index[stream], *len, hipMemcpyDeviceToHost);
+  else if ((*he = hipMemcpyAsync(out, b->index[stream], *len, hipMemcpyDeviceToHost, st)) == hipSuccess) *he = hipStreamSynchronize(st);
+  return FQGPU_OK;
+}
+
 // The decode index of the block fqgpu_encode_begin coded with FQGPU_F_DECODE_INDEX: after fqgpu_encode_wait or _end,
 // until the handle's next host-pointer call.
 extern "C" int fqgpu_encode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len) {
   if (!ctx || !ctx->hp_block || stream < 0 || stream > 1 || !len) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
-  if (b->last_op != 1 || !b->result_pulled) return FQGPU_E_ARG;
-  *len = b->index_bytes[stream];
-  if (!out || !*len) return FQGPU_OK;
-  if (cap < *len) return FQGPU_E_ARG;
-  int rc = use_device(ctx->device);
+  if (ctx->hp_block->last_op != 1 || !ctx->hp_block->result_pulled) return FQGPU_E_ARG;
+  hipError_t he;
+  const int rc = hp_index_fetch(ctx, stream, out, cap, len, ctx->hp_done, &he);
   if (rc) return rc;
-  FQ_HIP(hipMemcpyAsync(out, b->index[stream], *len, hipMemcpyDeviceToHost, ctx->hp_done));
-  FQ_HIP(hipStreamSynchronize(ctx->hp_done));
+  FQ_HIP(he);
   return FQGPU_OK;
 }
 
@@ -1479,12 +1482,9 @@ extern "C" int fqgpu_decode_chunk_indexing(fqgpu_ctx *ctx, const fqgpu_header_st
 extern "C" int fqgpu_decode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len) {
   if (len) *len = 0;
   if (!ctx || !ctx->hp_block || stream < 0 || stream > 1 || !len || !ctx->hp_index_built) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
-  *len = b->index_bytes[stream];
-  if (!out || !*len) return FQGPU_OK;
-  if (cap < *len) { *len = 0; return FQGPU_E_ARG; }
-  int rc = use_device(ctx->device);
-  if (!rc && hipMemcpy(out, b->index[stream], *len, hipMemcpyDeviceToHost) != hipSuccess) rc = FQGPU_E_HIP;
+  hipError_t he;
+  int rc = hp_index_fetch(ctx, stream, out, cap, len, nullptr, &he);
+  if (!rc && he != hipSuccess) rc = FQGPU_E_HIP;
   if (rc) *len = 0;
   return rc;
 }

@@ -449,9 +449,73 @@ __device__ __forceinline__ void walk_positions(WalkT<COMPACT> &wk, LdsBits &br, 
 __device__ __forceinline__ void set_slot(CtxEntry *ce, unsigned c, uint32_t table, uint32_t entry) { ce[c].table = table * 4u; ce[c].entry = entry; }
 __device__ __forceinline__ void set_slot(uint32_t *ce, unsigned c, uint32_t, uint32_t entry) { ce[c] = entry; }
 
-template <class M, bool COMPACT>
-__device__ void decode_stream(const DecJob &j, const TabView &tab, typename WalkT<COMPACT>::Slots *ce, uint32_t *bitbuf) {
+// Opens stream M of a job at its end mark: the bit position in front of the last-coded symbol, the entry of every context's
+// state in its slot (behind the caller's __syncthreads()).  -1: no such stream, reported as corrupt.
+template <class M, class Slots>
+__device__ __forceinline__ long long open_at_end(const DecJob &j, const TabView &tab, Slots *ce) {
   constexpr unsigned B = M::B;
+  const uint8_t *src = M::STREAM == 0 ? j.seq : j.qual;
+  const unsigned len = M::STREAM == 0 ? j.seq_len : j.qual_len;
+  StreamResult *res = &j.res->s[M::STREAM];
+  const unsigned lane = threadIdx.x;
+  g_cu32 *w = (g_cu32 *)reinterpret_cast<const uint32_t *>(src);
+  // BIT_initDStream: the highest set bit of the last byte is the end mark
+  const unsigned last = len ? src[len - 1] : 0u;
+  if (last == 0) { if (lane == 0) res->corrupt = 1; return -1; }
+  const long long p0 = (long long)(len - 1) * 8 + (31 - __clz((int)last));
+  const unsigned sum_logs = tab.log_prefix[B];
+  if (p0 < (long long)sum_logs) { if (lane == 0) res->corrupt = 1; return -1; }
+  // FSE_initDState for ctx B-1 .. 0 (src/fse_common.hpp:134-138): ctx c sits at a fixed
+  // offset below the end mark, so all of them load in parallel
+  for (unsigned c = lane; c < B; c += 64) {
+    const unsigned lg = tab.logs[c];
+    const long long lo = p0 - (long long)(sum_logs - tab.log_prefix[c]);
+    const uint32_t table = tab.dt_off[c] + 1u;  // behind the table's header word
+    set_slot(ce, c, table, tab.dt[table + peek_bits(w, lo, lg)]);
+  }
+  return p0 - (long long)sum_logs;
+}
+
+// the history a walk that starts inside a read begins with: the model has seen a snapshot's `prev` (bytes p-1 .. p-4, 0xFF
+// in front of the read)
+template <class M>
+__device__ __forceinline__ void seed_history(CtxHist<M> &h, unsigned prev) {
+  h.start();
+  if constexpr (M::STREAM == 0) {
+    for (int b = 3; b >= 0; b--) {
+      const unsigned ch = (prev >> (8 * b)) & 0xFFu;
+      if (ch != 0xFFu) h.seed(fq_base_code(ch) * 8u);
+    }
+  } else {
+    const unsigned a = prev & 0xFFu, b = (prev >> 8) & 0xFFu, c = (prev >> 16) & 0xFFu;
+    h.set(a != 0xFFu ? ((a - 33u) & 63u) * 8u : 0u, b != 0xFFu ? ((b - 33u) & 63u) * 8u : 0u,
+          c != 0xFFu ? ((c - 33u) & 63u) * 8u : 0u);
+  }
+}
+
+// ---- a decode that leaves the decode index behind (extension) ------------------------------------
+// A decoder that walks a stream from its end passes through every snapshot point and has there what a
+// snapshot holds: the bit position, the bytes the model has just seen, the state of every context.  So
+// the whole-stream walk optionally TAKES SNAPSHOTS: each time the symbols [k stride, n_sym) are done it
+// stops inside the record, LDS slots and bit reader as they are, and writes snapshot k.
+//
+// The walk keeps no states, only the DTable ENTRY of every context's current state (CtxEntry), and
+// step() is left alone: at a boundary the refills in flight are drained and the B entries go to a
+// scratch row as they are; k_resolve_states, behind the walks and wide, finds the state whose table
+// word is that entry.  The bit position goes straight to the index; header and `prev` bytes are
+// written behind the N restoration by k_dindex_meta, from the RESTORED block, by the function the
+// encoder's k_index_meta writes them with from the block it coded.  (An index from a device encode WITH
+// N -> A write-back holds 'A' where this one holds 'N' in `prev`; both seed the model alike.)
+struct IdxJob {
+  uint32_t *entries[2];  // per stream [n_snap][B] entries of the contexts at every snapshot
+  uint8_t *index[2];     // the decode index being built (header + n_snap snapshots)
+  unsigned n_sym, stride, n_snap;
+};
+typedef FQ_GLOBAL uint32_t g_u32;
+
+// A whole stream from its end, record by record.  SNAP: taking the snapshots of *x on the way (x, j.rec_start: SNAP only).
+template <class M, bool COMPACT, bool SNAP>
+__device__ void decode_stream(const DecJob &j, const IdxJob *x, const TabView &tab, typename WalkT<COMPACT>::Slots *ce, uint32_t *bitbuf) {
   const uint8_t *src = M::STREAM == 0 ? j.seq : j.qual;
   const unsigned len = M::STREAM == 0 ? j.seq_len : j.qual_len;
   StreamResult *res = &j.res->s[M::STREAM];
@@ -461,40 +525,70 @@ __device__ void decode_stream(const DecJob &j, const TabView &tab, typename Walk
   g_u8 *raw = (g_u8 *)j.raw;
 
   if (__ballot(1) != ~0ull) { res->corrupt = 1; return; }  // (the refill's assembly sets EXEC to all ones: a partial wave must not get there)
-  // BIT_initDStream: the highest set bit of the last byte is the end mark
-  const unsigned last = len ? src[len - 1] : 0u;
-  if (last == 0) { if (lane == 0) res->corrupt = 1; return; }
-  const long long p0 = (long long)(len - 1) * 8 + (31 - __clz((int)last));
-  const unsigned sum_logs = tab.log_prefix[B];
-  if (p0 < (long long)sum_logs) { if (lane == 0) res->corrupt = 1; return; }
-  // FSE_initDState for ctx B-1 .. 0 (src/fse_common.hpp:134-138): ctx c sits at a fixed
-  // offset below the end mark, so all of them load in parallel
-  for (unsigned c = lane; c < B; c += 64) {
-    const unsigned lg = tab.logs[c];
-    const long long lo = p0 - (long long)(sum_logs - tab.log_prefix[c]);
-    const uint32_t table = tab.dt_off[c] + 1u;  // behind the table's header word
-    set_slot(ce, c, table, tab.dt[table + peek_bits(w, lo, lg)]);
-  }
+  const long long pos0 = open_at_end<M>(j, tab, ce);
+  if (pos0 < 0) return;
   __syncthreads();
   WalkT<COMPACT> wk;
   wk.init(ce, tab.dt, tab.dt_off);
 
   LdsBits br;
-  br.init(w, p0 - (long long)sum_logs, bitbuf, (len + 3) / 4);
+  br.init(w, pos0, bitbuf, (len + 3) / 4);
+  unsigned k = 0, stride = 0;  // SNAP: the next snapshot to take, behind symbol k * stride (0: none left)
+  if constexpr (SNAP) { k = fq_uniform(x->n_snap); stride = x->stride; }
   fqgpu_rec nxt;
   nxt.seq_off = recs[j.n_recs - 1].seq_off; nxt.qual_off = recs[j.n_recs - 1].qual_off; nxt.len = recs[j.n_recs - 1].len;
   for (unsigned r = j.n_recs; r > 0; r--) {  // records last -> first (src/workspace.cpp:84-87)
     const fqgpu_rec rec = nxt;
     if (r > 1) { nxt.seq_off = recs[r - 2].seq_off; nxt.qual_off = recs[r - 2].qual_off; nxt.len = recs[r - 2].len; }  // lands while this record is walked
+    // SNAP: position i of the record has encode index rs + len - 1 - i (loaded in front of the history: behind h.start()
+    // the compiler gives up on the kernel, "illegal VGPR to SGPR copy")
+    unsigned rs = 0;
+    if constexpr (SNAP) rs = fq_uniform(((g_cu32 *)j.rec_start)[r - 1]);
+    g_u8 *line = raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
     CtxHist<M> h;
     h.start();
-    walk_positions<M, COMPACT>(wk, br, raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off), 0u, rec.len, h);
+    unsigned i0 = 0;
+    if constexpr (SNAP) {
+      // a boundary inside this record (k * stride < rs + len holds: the symbols behind are done): the record is walked in pieces
+      while (k && (unsigned long long)k * stride >= rs) {
+        const unsigned i1 = rs + rec.len - k * stride;  // one past the position of symbol k * stride
+        h.uniform();
+        walk_positions<M, COMPACT>(wk, br, line, i0, i1, h);
+        if (br.underflow) break;
+        // snapshot k: every refill has landed (the compiler does not know of them), no slot is left marked; the entries
+        // as they are, all lanes
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        g_u32 *row = (g_u32 *)x->entries[M::STREAM] + (size_t)(k - 1) * M::B;
+        unsigned pending = 0;
+        for (unsigned c = lane; c < M::B; c += 64) {
+          const uint32_t e = *wk.entry_at(8u * c);
+          pending |= (unsigned)(e == FQ_ENTRY_PENDING);
+          row[c] = e;
+        }
+        const bool any_pending = __ballot(pending != 0) != 0ull;
+        if (lane == 0) {
+          *reinterpret_cast<FQ_GLOBAL unsigned long long *>(fq_index_snap((g_u8 *)x->index[M::STREAM], M::B, k)) = (unsigned long long)br.pos();
+          if (any_pending) res->corrupt = 1;
+        }
+        // the model's history in front of position i1, from the bytes just decoded (their stores are through: vmcnt(0)
+        // above; read past this CU's vector cache, which may hold the line from before)
+        unsigned prev = 0;
+        for (unsigned i = 0; i < 4; i++)
+          prev |= (i1 >= i + 1 ? (unsigned)__hip_atomic_load(line + (i1 - 1u - i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFu) << (8 * i);
+        seed_history<M>(h, fq_uniform(prev));
+        i0 = i1;
+        k--;
+      }
+      if (br.underflow) break;
+      h.uniform();
+    }
+    walk_positions<M, COMPACT>(wk, br, line, i0, rec.len, h);
     if (br.underflow) break;
   }
   // BIT_endOfDStream (src/fse_common.hpp:141): every bit consumed, none invented
   if (lane == 0) {
     if (br.pos() != 0) res->corrupt = 1;
-    res->total_bits = (unsigned long long)(p0 - (long long)sum_logs);
+    res->total_bits = (unsigned long long)pos0;
   }
 #ifdef FQGPU_EXPERIMENTS
   // (make experiments: how often the walk finds an entry pending, and what that costs)
@@ -518,9 +612,8 @@ __device__ void decode_chunk(const DecJob &j, unsigned chunk, const TabView &tab
   g_crec *recs = (g_crec *)j.recs;
   g_cu32 *rec_start = (g_cu32 *)j.rec_start;
   g_u8 *raw = (g_u8 *)j.raw;
-  const FqIndexHeader hdr = *reinterpret_cast<const FqIndexHeader *>(j.index[M::STREAM]);
-  const size_t snap_bytes = FQ_INDEX_SNAP_HEAD + 2 * (size_t)B;
-  const uint8_t *snaps = j.index[M::STREAM] + sizeof(FqIndexHeader);
+  const uint8_t *index = j.index[M::STREAM];
+  const FqIndexHeader hdr = *reinterpret_cast<const FqIndexHeader *>(index);
   const unsigned n_sym = (unsigned)hdr.n_sym, stride = hdr.stride;
   const unsigned e_lo = chunk * stride, e_hi = min(e_lo + stride, n_sym);
   const bool from_end = chunk == hdr.n_snap;  // the last stride starts at the stream's end mark
@@ -529,21 +622,12 @@ __device__ void decode_chunk(const DecJob &j, unsigned chunk, const TabView &tab
   long long pos;
   unsigned prev = 0xFFFFFFFFu;
   if (from_end) {
-    const unsigned last = len ? src[len - 1] : 0u;
-    if (last == 0) { if (lane == 0) res->corrupt = 1; return; }
-    const long long p0 = (long long)(len - 1) * 8 + (31 - __clz((int)last));
-    const unsigned sum_logs = tab.log_prefix[B];
-    if (p0 < (long long)sum_logs) { if (lane == 0) res->corrupt = 1; return; }
-    for (unsigned c = lane; c < B; c += 64) {
-      const long long lo = p0 - (long long)(sum_logs - tab.log_prefix[c]);
-      const uint32_t table = tab.dt_off[c] + 1u;
-      set_slot(ce, c, table, tab.dt[table + peek_bits(w, lo, tab.logs[c])]);
-    }
-    pos = p0 - (long long)sum_logs;
+    pos = open_at_end<M>(j, tab, ce);
+    if (pos < 0) return;
     if (lane == 0) res->total_bits = (unsigned long long)pos;
   } else {
-    const uint8_t *snap = snaps + (size_t)chunk * snap_bytes;  // snapshot chunk + 1 sits at e_hi
-    const uint16_t *st = reinterpret_cast<const uint16_t *>(snap + FQ_INDEX_SNAP_HEAD);
+    const uint8_t *snap = fq_index_snap(index, B, chunk + 1);  // snapshot chunk + 1 sits at e_hi
+    const uint16_t *st = fq_index_states(index, B, chunk + 1);
     for (unsigned c = lane; c < B; c += 64) {
       const uint32_t table = tab.dt_off[c] + 1u;
       set_slot(ce, c, table, tab.dt[table + ((unsigned)st[c] & ((1u << tab.logs[c]) - 1u))]);  // a damaged index must not leave the table
@@ -555,7 +639,7 @@ __device__ void decode_chunk(const DecJob &j, unsigned chunk, const TabView &tab
   __syncthreads();
   // every bit of this stride consumed, none invented: the walk must end where the previous
   // snapshot (or the start of the stream) says
-  const long long pos_end = chunk == 0 ? 0ll : (long long)*reinterpret_cast<const unsigned long long *>(snaps + (size_t)(chunk - 1) * snap_bytes);
+  const long long pos_end = chunk == 0 ? 0ll : (long long)*reinterpret_cast<const unsigned long long *>(fq_index_snap(index, B, chunk));
 
   LdsBits br;
   br.init(w, pos, bitbuf, (len + 3) / 4);
@@ -572,18 +656,7 @@ __device__ void decode_chunk(const DecJob &j, unsigned chunk, const TabView &tab
     const unsigned i1 = rs >= e_lo ? rec.len : rec.len - (e_lo - rs);  // one past the last position
     CtxHist<M> h;
     h.start();
-    if (first && !from_end) {  // the stride starts inside a read: the model has seen the bytes in front
-      if constexpr (M::STREAM == 0) {
-        for (int b = 3; b >= 0; b--) {
-          const unsigned ch = (prev >> (8 * b)) & 0xFFu;
-          if (ch != 0xFFu) h.seed(fq_base_code(ch) * 8u);
-        }
-      } else {
-        const unsigned a = prev & 0xFFu, b = (prev >> 8) & 0xFFu, c = (prev >> 16) & 0xFFu;
-        h.set(a != 0xFFu ? ((a - 33u) & 63u) * 8u : 0u, b != 0xFFu ? ((b - 33u) & 63u) * 8u : 0u,
-              c != 0xFFu ? ((c - 33u) & 63u) * 8u : 0u);
-      }
-    }
+    if (first && !from_end) seed_history<M>(h, prev);  // the stride starts inside a read: the model has seen the bytes in front
     h.uniform();
     walk_positions<M, COMPACT>(wk, br, raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off), i0, i1, h);
     first = false;
@@ -612,164 +685,26 @@ k_lens_of(const fqgpu_rec *__restrict__ recs, unsigned n, uint32_t *__restrict__
   if (r < n) lens32[r] = recs[r].len;
 }
 
-// one workgroup per block: stream M of every block of the batch
-template <class M, bool COMPACT>
+// one workgroup per block: stream M of every block of the batch (ijobs: SNAP only; an indexing pass has few chains and
+// runs in the resident form, a batch with more chains than places queues)
+template <class M, bool COMPACT, bool SNAP>
 __global__ void __launch_bounds__(64)
-k_decode(const DecJob *__restrict__ jobs, TabView tab) {
+k_decode(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, TabView tab) {
   __shared__ typename WalkT<COMPACT>::Slots ce[M::B];
   __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
-  decode_stream<M, COMPACT>(jobs[blockIdx.x], tab, ce, bitbuf);
+  decode_stream<M, COMPACT, SNAP>(jobs[blockIdx.x], ijobs + blockIdx.x, tab, ce, bitbuf);
 }
 // both streams in one launch (grid = 2 * n_blocks, the quality streams first): for batches whose
 // chains all find a place at once (two workgroups of 66 KB per CU) -- then the placement of one
-// launch, a quality and a sequence chain per CU, is the better one (256 x 1 MiB blocks: 5.0 against 4.6 GB/s)
+// launch, a quality and a sequence chain per CU, is the better one (256 x 1 MiB blocks: 5.0 against 4.6 GB/s),
+// and it does not depend on two HIP streams running side by side
+template <bool SNAP>
 __global__ void __launch_bounds__(64)
-k_decode_both(const DecJob *__restrict__ jobs, unsigned n_blocks, TabView seq_tab, TabView qual_tab) {
+k_decode_both(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, unsigned n_blocks, TabView seq_tab, TabView qual_tab) {
   __shared__ CtxEntry ce[QualModel::B];
   __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
-  if (blockIdx.x < n_blocks) decode_stream<QualModel, false>(jobs[blockIdx.x], qual_tab, ce, bitbuf);
-  else decode_stream<SeqModel, false>(jobs[blockIdx.x - n_blocks], seq_tab, ce, bitbuf);
-}
-
-// ---- the indexing walk (extension): a decode that leaves the decode index behind ----------------
-// A decoder that walks a stream from its end passes through every snapshot point and has there what a
-// snapshot holds: the bit position, the bytes the model has just seen, the state of every context.  So
-// this is decode_stream with decode_chunk's bookkeeping: strides n_snap, n_snap - 1, .. 0 in ONE
-// workgroup, the LDS slots and the bit reader carried over from stride to stride instead of loaded
-// from a snapshot.  Each time the symbols [k stride, n_sym) are done, snapshot k is taken.
-//
-// The walk keeps no states, only the DTable ENTRY of every context's current state (CtxEntry), and
-// step() is left alone: at a boundary the refills in flight are drained and the B entries go to a
-// scratch row as they are; k_resolve_states, behind the walks and wide, finds the state whose table
-// word is that entry.  The bit position goes straight to the index; header and `prev` bytes are
-// written behind the N restoration by k_dindex_meta, from the RESTORED block, exactly as the
-// encoder's k_index_meta writes them from the block it coded.  (An index from a device encode WITH
-// N -> A write-back holds 'A' where this one holds 'N' in `prev`; both seed the model alike.)
-struct IdxJob {
-  uint32_t *entries[2];  // per stream [n_snap][B] entries of the contexts at every snapshot
-  uint8_t *index[2];     // the decode index being built (header + n_snap snapshots)
-  unsigned n_sym, stride, n_snap;
-};
-typedef FQ_GLOBAL uint32_t g_u32;
-
-// the history decode_chunk seeds from a snapshot's `prev` (bytes p-1 .. p-4, 0xFF in front of the read)
-template <class M>
-__device__ __forceinline__ void seed_history(CtxHist<M> &h, unsigned prev) {
-  h.start();
-  if constexpr (M::STREAM == 0) {
-    for (int b = 3; b >= 0; b--) {
-      const unsigned ch = (prev >> (8 * b)) & 0xFFu;
-      if (ch != 0xFFu) h.seed(fq_base_code(ch) * 8u);
-    }
-  } else {
-    const unsigned a = prev & 0xFFu, b = (prev >> 8) & 0xFFu, c = (prev >> 16) & 0xFFu;
-    h.set(a != 0xFFu ? ((a - 33u) & 63u) * 8u : 0u, b != 0xFFu ? ((b - 33u) & 63u) * 8u : 0u,
-          c != 0xFFu ? ((c - 33u) & 63u) * 8u : 0u);
-  }
-}
-
-template <class M>
-__device__ void decode_stream_indexing(const DecJob &j, const IdxJob &x, const TabView &tab, CtxEntry *ce, uint32_t *bitbuf) {
-  constexpr unsigned B = M::B;
-  const uint8_t *src = M::STREAM == 0 ? j.seq : j.qual;
-  const unsigned len = M::STREAM == 0 ? j.seq_len : j.qual_len;
-  StreamResult *res = &j.res->s[M::STREAM];
-  const unsigned lane = threadIdx.x;
-  g_cu32 *w = (g_cu32 *)reinterpret_cast<const uint32_t *>(src);
-  g_crec *recs = (g_crec *)j.recs;
-  g_cu32 *rec_start = (g_cu32 *)j.rec_start;
-  g_u8 *raw = (g_u8 *)j.raw;
-  g_u32 *rows = (g_u32 *)x.entries[M::STREAM];
-  g_u8 *snaps = (g_u8 *)x.index[M::STREAM] + sizeof(FqIndexHeader);
-  const unsigned stride = x.stride;
-  const lds_CtxEntry *lce = (const lds_CtxEntry *)ce;
-
-  // the checks and the state load of decode_stream
-  if (__ballot(1) != ~0ull) { res->corrupt = 1; return; }
-  const unsigned last = len ? src[len - 1] : 0u;
-  if (last == 0) { if (lane == 0) res->corrupt = 1; return; }
-  const long long p0 = (long long)(len - 1) * 8 + (31 - __clz((int)last));
-  const unsigned sum_logs = tab.log_prefix[B];
-  if (p0 < (long long)sum_logs) { if (lane == 0) res->corrupt = 1; return; }
-  for (unsigned c = lane; c < B; c += 64) {
-    const unsigned lg = tab.logs[c];
-    const long long lo = p0 - (long long)(sum_logs - tab.log_prefix[c]);
-    const uint32_t table = tab.dt_off[c] + 1u;
-    set_slot(ce, c, table, tab.dt[table + peek_bits(w, lo, lg)]);
-  }
-  __syncthreads();
-  WalkT<false> wk;
-  wk.init(ce, tab.dt, tab.dt_off);
-  LdsBits br;
-  br.init(w, p0 - (long long)sum_logs, bitbuf, (len + 3) / 4);
-
-  unsigned k = fq_uniform(x.n_snap);  // the next snapshot to take: behind symbol k * stride (0: none left)
-  for (unsigned r = j.n_recs; r > 0 && !br.underflow; r--) {  // records last -> first
-    fqgpu_rec rec;
-    rec.seq_off = recs[r - 1].seq_off; rec.qual_off = recs[r - 1].qual_off; rec.len = recs[r - 1].len;
-    const unsigned rs = fq_uniform(rec_start[r - 1]);  // position i of the record has encode index rs + len - 1 - i
-    g_u8 *line = raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
-    CtxHist<M> h;
-    h.start();
-    unsigned i0 = 0;
-    // a boundary inside this record (k * stride < rs + len holds: the symbols behind are done): the record is walked in pieces
-    while (k && (unsigned long long)k * stride >= rs) {
-      const unsigned i1 = rs + rec.len - k * stride;  // one past the position of symbol k * stride
-      h.uniform();
-      walk_positions<M, false>(wk, br, line, i0, i1, h);
-      if (br.underflow) break;
-      // snapshot k: every refill has landed (the compiler does not know of them), no slot is left marked; the entries
-      // as they are, all lanes
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      g_u32 *row = rows + (size_t)(k - 1) * B;
-      unsigned pending = 0;
-      for (unsigned c = lane; c < B; c += 64) {
-        const uint32_t e = lce[c].entry;
-        pending |= (unsigned)(e == FQ_ENTRY_PENDING);
-        row[c] = e;
-      }
-      const bool any_pending = __ballot(pending != 0) != 0ull;
-      if (lane == 0) {
-        *reinterpret_cast<FQ_GLOBAL unsigned long long *>(snaps + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B)) = (unsigned long long)br.pos();
-        if (any_pending) res->corrupt = 1;
-      }
-      // the model's history in front of position i1, from the bytes just decoded (their stores are through: vmcnt(0)
-      // above; read past this CU's vector cache, which may hold the line from before)
-      unsigned prev = 0;
-      for (unsigned i = 0; i < 4; i++)
-        prev |= (i1 >= i + 1 ? (unsigned)__hip_atomic_load(line + (i1 - 1u - i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0xFFu) << (8 * i);
-      seed_history<M>(h, fq_uniform(prev));
-      i0 = i1;
-      k--;
-    }
-    if (br.underflow) break;
-    h.uniform();
-    walk_positions<M, false>(wk, br, line, i0, rec.len, h);
-  }
-  if (lane == 0) {
-    if (br.pos() != 0) res->corrupt = 1;
-    res->total_bits = (unsigned long long)(p0 - (long long)sum_logs);
-  }
-}
-
-// one workgroup per block: stream M of every block of the batch, resident form (an indexing pass has few chains;
-// a batch with more chains than places queues)
-template <class M>
-__global__ void __launch_bounds__(64)
-k_decode_indexing(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, TabView tab) {
-  __shared__ CtxEntry ce[M::B];
-  __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
-  decode_stream_indexing<M>(jobs[blockIdx.x], ijobs[blockIdx.x], tab, ce, bitbuf);
-}
-
-// both streams in one launch (grid = 2 * n_blocks, the quality streams first), as k_decode_both: one launch places a
-// quality and a sequence chain per CU and does not depend on two HIP streams running side by side
-__global__ void __launch_bounds__(64)
-k_decode_indexing_both(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs, unsigned n_blocks, TabView seq_tab, TabView qual_tab) {
-  __shared__ CtxEntry ce[QualModel::B];
-  __shared__ uint32_t bitbuf[FQ_BITBUF_DW];
-  if (blockIdx.x < n_blocks) decode_stream_indexing<QualModel>(jobs[blockIdx.x], ijobs[blockIdx.x], qual_tab, ce, bitbuf);
-  else decode_stream_indexing<SeqModel>(jobs[blockIdx.x - n_blocks], ijobs[blockIdx.x - n_blocks], seq_tab, ce, bitbuf);
+  if (blockIdx.x < n_blocks) decode_stream<QualModel, false, SNAP>(jobs[blockIdx.x], ijobs + blockIdx.x, qual_tab, ce, bitbuf);
+  else decode_stream<SeqModel, false, SNAP>(jobs[blockIdx.x - n_blocks], ijobs + (blockIdx.x - n_blocks), seq_tab, ce, bitbuf);
 }
 
 // State of (snapshot, context) from its entry: the x with dt[dt_off[c] + 1 + x] == entry.  Inside one valid DTable the
@@ -804,37 +739,18 @@ k_resolve_states(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijo
     jobs[blockIdx.z].res->s[M::STREAM].corrupt = 1;
     best = 0;
   }
-  reinterpret_cast<uint16_t *>(x.index[M::STREAM] + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B) +
-                               FQ_INDEX_SNAP_HEAD)[c] = (uint16_t)best;
+  fq_index_states(x.index[M::STREAM], B, k)[c] = (uint16_t)best;
 }
 
-// Header and `prev` bytes of the index being built, behind the N restoration: what the encoder's k_index_meta
-// (enc_index.h) writes, from the restored block.  The bit positions are the walk's.
+// Header and `prev` bytes of the index being built, behind the N restoration: from the restored block what the encoder's
+// k_index_meta (enc_index.h) writes from the block it coded.  The bit positions are the walk's.
 template <class M>
 __global__ void __launch_bounds__(256)
 k_dindex_meta(const DecJob *__restrict__ jobs, const IdxJob *__restrict__ ijobs) {
   const DecJob j = jobs[blockIdx.y];
   const IdxJob x = ijobs[blockIdx.y];
-  uint8_t *index = x.index[M::STREAM];
   const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;  // 0: header, 1 .. n_snap: snapshots
-  if (k == 0) {
-    FqIndexHeader h;
-    h.magic = FQ_INDEX_MAGIC; h.stream = M::STREAM; h.stride = x.stride; h.n_snap = x.n_snap;
-    h.n_sym = x.n_sym; h.reserved = 0;
-    *reinterpret_cast<FqIndexHeader *>(index) = h;
-    return;
-  }
-  if (k > x.n_snap) return;
-  const unsigned e = k * x.stride;
-  uint8_t *snap = index + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)M::B);
-  const unsigned r = fq_locate(j.rec_start, 0, j.n_recs - 1, e - 1);  // symbol e - 1: record r, position p
-  const fqgpu_rec rec = j.recs[r];
-  const unsigned p = rec.len - 1u - (e - 1u - j.rec_start[r]);
-  const uint8_t *line = j.raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
-  unsigned packed = 0;
-  for (unsigned i = 0; i < 4; i++) packed |= (p >= i + 1 ? (unsigned)line[p - 1 - i] : 0xFFu) << (8 * i);
-  reinterpret_cast<uint32_t *>(snap)[2] = packed;
-  reinterpret_cast<uint32_t *>(snap)[3] = 0;
+  (void)fq_index_write_meta<M>(x.index[M::STREAM], k, x.n_sym, x.stride, j.raw, j.recs, j.rec_start, j.n_recs);
 }
 
 // batch-wide record arrays: N counts widened for the scan
@@ -911,134 +827,191 @@ static int dec_stream2_ensure(fqgpu_ctx *ctx) {
   return FQGPU_OK;
 }
 
+// ---- fq_decode_launch, step by step ------------------------------------------------------------
+namespace {
+
+size_t snaps_of(const fqgpu_dblock *b, int stream) {
+  const size_t sb = fq_index_snap_bytes(stream ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
+  return b->index_bytes[stream] >= sizeof(FqIndexHeader) ? (b->index_bytes[stream] - sizeof(FqIndexHeader)) / sb : 0;
+}
+// blocks with a decode index (both streams, at least one snapshot) go to the chunk kernel, the
+// others to the one-lane-per-stream kernel
+bool indexed(const fqgpu_dblock *b) { return snaps_of(b, 0) && snaps_of(b, 1); }
+
+DecJob dec_job_of(const fqgpu_dblock *b, size_t rec_base) {
+  DecJob j;
+  j.seq = b->seq;   j.seq_len = (unsigned)b->seq_len;
+  j.qual = b->qual; j.qual_len = (unsigned)b->qual_len;
+  j.recs = b->recs; j.n_recs = (unsigned)b->n_recs;
+  j.n_count = b->n_count;
+  j.n_pos = b->n_pos; j.n_pos_len = (unsigned)b->n_pos_len;
+  j.raw = b->raw;
+  j.res = b->result;
+  j.rec_base = (unsigned)rec_base;
+  j.index[0] = j.index[1] = nullptr;
+  j.rec_start = nullptr;
+  return j;
+}
+
+// rs[n_recs + 1] <- the encode index of the first symbol of every record of b: the plan's host copy (b->recs is laid out
+// inside the plan's window alone: nothing to scan), or lengths -> n_cnt32 (free until the N pass), exclusive scan
+int rec_start_build(fqgpu_ctx *ctx, const fqgpu_dblock *b, const FqStridePlan *plan, uint32_t *rs) {
+  hipStream_t st = ctx->stream;
+  if (plan) {
+    FQ_HIP(hipMemcpyAsync(rs, plan->rec_start, (b->n_recs + 1) * 4, hipMemcpyHostToDevice, st));
+    return FQGPU_OK;
+  }
+  hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
+                     ctx->n_cnt32.as<uint32_t>());
+  return fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp);
+}
+
+// the indexing decode: room for both indexes on every block and for the entries at every snapshot
+int idx_jobs_prepare(fqgpu_ctx *ctx, const std::vector<fqgpu_dblock *> &blocks, std::vector<IdxJob> &ihost, unsigned *snap_max) {
+  constexpr size_t ROW = FQGPU_SEQ_MODELS + FQGPU_QUAL_MODELS;  // entries of one snapshot, both streams
+  int rc;
+  size_t snaps = 0;
+  ihost.resize(blocks.size());
+  for (size_t i = 0; i < blocks.size(); i++) {
+    fqgpu_dblock *b = blocks[i];
+    if (!b->n_bases || b->n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
+    IdxJob &x = ihost[i];
+    x.n_sym = (unsigned)b->n_bases; x.stride = ctx->index_stride; x.n_snap = fq_index_n_snap(x.n_sym, x.stride);
+    *snap_max = x.n_snap > *snap_max ? x.n_snap : *snap_max;
+    for (int s = 0; s < 2; s++) {
+      if ((rc = fq_index_reserve(b, s, fq_index_bytes(x.n_snap, s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS), true))) return rc;
+      x.index[s] = b->index[s];
+    }
+    snaps += x.n_snap;
+  }
+  if ((rc = ctx->dec_idx.reserve(blocks.size() * sizeof(IdxJob)))) return rc;
+  if ((rc = ctx->dec_entries.reserve(snaps * ROW * 4 + 64))) return rc;
+  uint32_t *row = ctx->dec_entries.as<uint32_t>();
+  for (IdxJob &x : ihost) {
+    x.entries[0] = row;
+    x.entries[1] = row + (size_t)x.n_snap * FQGPU_SEQ_MODELS;
+    row += (size_t)x.n_snap * ROW;
+  }
+  return FQGPU_OK;
+}
+
+// The placement rules.  A batch whose whole-stream chains all find a place at once -- two workgroups of 66 KB per CU --
+// goes out as one launch, a quality and a sequence chain per CU; otherwise the sequence chains run beside the quality
+// chains on the second stream.  More quality chains than places for the resident form: the compact form.
+bool all_placed(const fqgpu_ctx *ctx, size_t n) { return 2 * n <= 2 * (size_t)ctx->n_cus; }
+bool crowded(const fqgpu_ctx *ctx, size_t chains) { return chains > 2 * (size_t)ctx->n_cus; }
+
+// the streams of jobs[0 .. n) from their ends; SNAP: taking the snapshots of ijobs (resident form only)
+template <bool SNAP>
+void launch_whole_streams(fqgpu_ctx *ctx, const DecJob *jobs, const IdxJob *ijobs, size_t n, const TabView &ts, const TabView &tq) {
+  const dim3 grid((unsigned)n), wave(64);
+  if (all_placed(ctx, n)) {
+    hipLaunchKernelGGL(k_decode_both<SNAP>, dim3((unsigned)(2 * n)), wave, 0, ctx->stream, jobs, ijobs, (unsigned)n, ts, tq);
+    return;
+  }
+  if (!SNAP && crowded(ctx, n)) hipLaunchKernelGGL((k_decode<QualModel, true, false>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
+  else hipLaunchKernelGGL((k_decode<QualModel, false, SNAP>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
+  hipLaunchKernelGGL((k_decode<SeqModel, false, SNAP>), grid, wave, 0, ctx->dec_stream2, jobs, ijobs, ts);
+}
+
+// N restoration: the N counts are gathered and scanned over whole blocks; the patch covers whole blocks or the plan's window
+int launch_n_pass(fqgpu_ctx *ctx, const DecJob *jobs, size_t n_blocks, size_t r_tot, size_t r_max, const FqStridePlan *plan) {
+  hipStream_t st = ctx->stream;
+  const size_t n_patch = plan ? plan->w1 - plan->w0 : r_max;
+  const unsigned gx = (unsigned)min((r_max + 255) / 256, (size_t)4096), gp = (unsigned)min((n_patch + 255) / 256, (size_t)4096);
+  hipLaunchKernelGGL(k_gather_ncount, dim3(gx ? gx : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
+                     ctx->n_cnt32.as<uint32_t>());
+  const int rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), r_tot, ctx->n_off.as<uint32_t>(), ctx->scan_tmp);
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_npatch, dim3(gp ? gp : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
+                     ctx->n_off.as<uint32_t>(), plan ? plan->w0 : 0u, plan ? plan->w1 : ~0u);
+  return FQGPU_OK;
+}
+
+// what the walks left of the indexes: header and `prev` bytes from the restored blocks, the states from the entries
+void launch_index_finish(fqgpu_ctx *ctx, const DecJob *jobs, const IdxJob *ijobs, size_t n_blocks, unsigned snap_max, const TabView &ts,
+                         const TabView &tq) {
+  hipStream_t st = ctx->stream;
+  const dim3 gm(snap_max / 256 + 1, (unsigned)n_blocks);
+  hipLaunchKernelGGL(k_dindex_meta<SeqModel>, gm, dim3(256), 0, st, jobs, ijobs);
+  hipLaunchKernelGGL(k_dindex_meta<QualModel>, gm, dim3(256), 0, st, jobs, ijobs);
+  if (!snap_max) return;
+  const unsigned gy = (snap_max + 63) / 64;
+  hipLaunchKernelGGL(k_resolve_states<SeqModel>, dim3(FQGPU_SEQ_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, ts);
+  hipLaunchKernelGGL(k_resolve_states<QualModel>, dim3(FQGPU_QUAL_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, tq);
+}
+
+}  // namespace
+
 // plan (fqgpu_decode_chunk_range): ONE block that holds both decode indexes, walked over the plan's strides alone
 int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan, bool build_index) {
   hipStream_t st = ctx->stream;
   if (!n_blocks) return FQGPU_OK;
   if (build_index && plan) return FQGPU_E_ARG;
-  int rcs = fqgpu_sync(ctx);  // blocks may still be in an encode lane
-  if (rcs) return rcs;
+  int rc = fqgpu_sync(ctx);  // blocks may still be in an encode lane
+  if (rc) return rc;
   if (build_index)  // (an index the block holds is ignored and replaced: every block goes the plain way below)
     for (size_t i = 0; i < n_blocks; i++) blocks_in[i]->index_bytes[0] = blocks_in[i]->index_bytes[1] = 0;
-  // blocks with a decode index (both streams, at least one snapshot) go to the chunk kernel, the
-  // others to the one-lane-per-stream kernel: plain blocks first in the job array
-  auto snaps_of = [](const fqgpu_dblock *b, int stream) -> size_t {
-    const size_t sb = fq_index_snap_bytes(stream ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
-    return b->index_bytes[stream] >= sizeof(FqIndexHeader) ? (b->index_bytes[stream] - sizeof(FqIndexHeader)) / sb : 0;
-  };
+  // plain blocks first in the job array
   std::vector<fqgpu_dblock *> blocks;
   blocks.reserve(n_blocks);
   for (size_t i = 0; i < n_blocks; i++)
-    if (!(snaps_of(blocks_in[i], 0) && snaps_of(blocks_in[i], 1))) blocks.push_back(blocks_in[i]);
+    if (!indexed(blocks_in[i])) blocks.push_back(blocks_in[i]);
   const size_t n_plain = blocks.size();
   for (size_t i = 0; i < n_blocks; i++)
-    if (snaps_of(blocks_in[i], 0) && snaps_of(blocks_in[i], 1)) blocks.push_back(blocks_in[i]);
+    if (indexed(blocks_in[i])) blocks.push_back(blocks_in[i]);
   if (plan && (n_blocks != 1 || n_plain || plan->k_hi[0] > snaps_of(blocks[0], 0) || plan->k_hi[1] > snaps_of(blocks[0], 1) ||
                plan->w0 > plan->w1 || plan->w1 > blocks[0]->n_recs))
     return FQGPU_E_ARG;
 
+  // rec_start: for the strides of an indexed block and for the snapshots of an indexing walk
+  auto wants_rec_start = [&](size_t i) { return i >= n_plain || build_index; };
   std::vector<DecJob> host(n_blocks);
-  std::vector<DecChunk> chunks, seq_chunks;  // quality strides | sequence strides
   size_t r_tot = 0, r_max = 0, rs_tot = 0;
   for (size_t i = 0; i < n_blocks; i++) {
     const fqgpu_dblock *b = blocks[i];
-    DecJob &j = host[i];
-    j.seq = b->seq;   j.seq_len = (unsigned)b->seq_len;
-    j.qual = b->qual; j.qual_len = (unsigned)b->qual_len;
-    j.recs = b->recs; j.n_recs = (unsigned)b->n_recs;
-    j.n_count = b->n_count;
-    j.n_pos = b->n_pos; j.n_pos_len = (unsigned)b->n_pos_len;
-    j.raw = b->raw;
-    j.res = b->result;
-    j.rec_base = (unsigned)r_tot;
-    j.index[0] = j.index[1] = nullptr;
-    j.rec_start = nullptr;
+    host[i] = dec_job_of(b, r_tot);
     r_tot += b->n_recs;
     if (b->n_recs > r_max) r_max = b->n_recs;
-    if (i >= n_plain || build_index) rs_tot += b->n_recs + 1;
+    if (wants_rec_start(i)) rs_tot += b->n_recs + 1;
   }
-  int rc;
-  size_t n_qual_chunks = 0;
   if ((rc = ctx->dec_desc.reserve(n_blocks * sizeof(DecJob)))) return rc;
   if ((rc = ctx->n_cnt32.reserve((r_tot + 1) * 4))) return rc;
   if ((rc = ctx->n_off.reserve((r_tot + 1) * 4))) return rc;
+  std::vector<IdxJob> ihost;
+  unsigned snap_max = 0;
+  if (build_index && (rc = idx_jobs_prepare(ctx, blocks, ihost, &snap_max))) return rc;
+  if (rs_tot && (rc = ctx->dec_recstart.reserve(rs_tot * 4 + 64))) return rc;
+  std::vector<DecChunk> chunks, seq_chunks;  // quality strides | sequence strides
+  size_t at = 0;
+  for (size_t i = 0; i < n_blocks; i++) {
+    if (!wants_rec_start(i)) continue;
+    const fqgpu_dblock *b = blocks[i];
+    uint32_t *rs = ctx->dec_recstart.as<uint32_t>() + at;
+    at += b->n_recs + 1;
+    host[i].rec_start = rs;
+    if ((rc = rec_start_build(ctx, b, plan, rs))) return rc;
+    if (i < n_plain) continue;
+    host[i].index[0] = b->index[0]; host[i].index[1] = b->index[1];
+    // every stride of a stream from the last, or the plan's k_lo .. k_hi
+    const size_t lo[2] = {plan ? plan->k_lo[0] : 0u, plan ? plan->k_lo[1] : 0u};
+    const size_t hi[2] = {plan ? plan->k_hi[0] : snaps_of(b, 0), plan ? plan->k_hi[1] : snaps_of(b, 1)};
+    for (size_t k = hi[1] + 1; k-- > lo[1];) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
+    for (size_t k = hi[0] + 1; k-- > lo[0];) seq_chunks.push_back(DecChunk{(unsigned)i, 0u, (unsigned)k});
+  }
+  const size_t n_qual_chunks = chunks.size(), n_seq_chunks = seq_chunks.size();
+  chunks.insert(chunks.end(), seq_chunks.begin(), seq_chunks.end());
   if (n_plain < n_blocks) {
-    if ((rc = ctx->dec_recstart.reserve(rs_tot * 4 + 64))) return rc;
-    size_t at = 0;
-    for (size_t i = n_plain; i < n_blocks; i++) {
-      const fqgpu_dblock *b = blocks[i];
-      DecJob &j = host[i];
-      j.index[0] = b->index[0]; j.index[1] = b->index[1];
-      uint32_t *rs = ctx->dec_recstart.as<uint32_t>() + at;
-      j.rec_start = rs;
-      at += b->n_recs + 1;
-      if (plan) {  // (b->recs is laid out inside the plan's window alone: nothing to scan)
-        FQ_HIP(hipMemcpyAsync(rs, plan->rec_start, (b->n_recs + 1) * 4, hipMemcpyHostToDevice, st));
-      } else {
-        // lengths -> n_cnt32 (free until the N pass), exclusive scan -> rec_start
-        hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
-                           ctx->n_cnt32.as<uint32_t>());
-        if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp))) return rc;
-      }
-      // every stride of a stream from the last, or the plan's k_lo .. k_hi
-      const size_t lo[2] = {plan ? plan->k_lo[0] : 0u, plan ? plan->k_lo[1] : 0u};
-      const size_t hi[2] = {plan ? plan->k_hi[0] : snaps_of(b, 0), plan ? plan->k_hi[1] : snaps_of(b, 1)};
-      for (size_t k = hi[1] + 1; k-- > lo[1];) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
-      for (size_t k = hi[0] + 1; k-- > lo[0];) seq_chunks.push_back(DecChunk{(unsigned)i, 0u, (unsigned)k});
-    }
-    n_qual_chunks = chunks.size();
-    chunks.insert(chunks.end(), seq_chunks.begin(), seq_chunks.end());
     if ((rc = ctx->dec_chunks.reserve(chunks.size() * sizeof(DecChunk)))) return rc;
     FQ_HIP(hipMemcpyAsync(ctx->dec_chunks.p, chunks.data(), chunks.size() * sizeof(DecChunk), hipMemcpyHostToDevice, st));
   }
-  // the indexing decode: room for both indexes on every block and for the entries at every snapshot, rec_start as above
-  std::vector<IdxJob> ihost;
-  unsigned snap_max = 0;
-  if (build_index) {
-    const unsigned stride = ctx->index_stride;
-    ihost.resize(n_blocks);
-    size_t words = 0;
-    for (size_t i = 0; i < n_blocks; i++) {
-      fqgpu_dblock *b = blocks[i];
-      if (!b->n_bases || b->n_bases >= 0xFFF00000ull) return FQGPU_E_ARG;
-      IdxJob &x = ihost[i];
-      x.n_sym = (unsigned)b->n_bases; x.stride = stride; x.n_snap = (x.n_sym - 1) / stride;
-      snap_max = x.n_snap > snap_max ? x.n_snap : snap_max;
-      for (int s = 0; s < 2; s++) {
-        const size_t bytes = sizeof(FqIndexHeader) + (size_t)x.n_snap * fq_index_snap_bytes(s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
-        if (bytes > b->index_cap[s]) {
-          if (b->index[s]) FQ_HIP(hipFree(b->index[s]));
-          b->index[s] = fq_dev_alloc<uint8_t>(bytes + 64);
-          b->index_cap[s] = b->index[s] ? bytes : 0;
-          if (!b->index[s]) return FQGPU_E_NOMEM;
-        }
-        x.index[s] = b->index[s];
-      }
-      words += (size_t)x.n_snap * (FQGPU_SEQ_MODELS + FQGPU_QUAL_MODELS);
-    }
-    if ((rc = ctx->dec_idx.reserve(n_blocks * sizeof(IdxJob)))) return rc;
-    if ((rc = ctx->dec_entries.reserve(words * 4 + 64))) return rc;
-    if ((rc = ctx->dec_recstart.reserve(rs_tot * 4 + 64))) return rc;
-    size_t at = 0, wat = 0;
-    for (size_t i = 0; i < n_blocks; i++) {
-      const fqgpu_dblock *b = blocks[i];
-      IdxJob &x = ihost[i];
-      x.entries[0] = ctx->dec_entries.as<uint32_t>() + wat;
-      x.entries[1] = x.entries[0] + (size_t)x.n_snap * FQGPU_SEQ_MODELS;
-      wat += (size_t)x.n_snap * (FQGPU_SEQ_MODELS + FQGPU_QUAL_MODELS);
-      uint32_t *rs = ctx->dec_recstart.as<uint32_t>() + at;
-      host[i].rec_start = rs;
-      at += b->n_recs + 1;
-      hipLaunchKernelGGL(k_lens_of, dim3((unsigned)((b->n_recs + 255) / 256)), dim3(256), 0, st, b->recs, (unsigned)b->n_recs,
-                         ctx->n_cnt32.as<uint32_t>());
-      if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), b->n_recs, rs, ctx->scan_tmp))) return rc;
-    }
-    FQ_HIP(hipMemcpyAsync(ctx->dec_idx.p, ihost.data(), n_blocks * sizeof(IdxJob), hipMemcpyHostToDevice, st));
-  }
+  if (build_index) FQ_HIP(hipMemcpyAsync(ctx->dec_idx.p, ihost.data(), n_blocks * sizeof(IdxJob), hipMemcpyHostToDevice, st));
   hipError_t he = hipMemcpyAsync(ctx->dec_desc.p, host.data(), n_blocks * sizeof(DecJob), hipMemcpyHostToDevice, st);
   if (he == hipSuccess) he = hipStreamSynchronize(st);  // the host vectors die with this call
   if (he != hipSuccess) return fq_hip_error(he, __FILE__, __LINE__);
   const DecJob *jobs = ctx->dec_desc.as<DecJob>();
+  const DecChunk *dch = ctx->dec_chunks.as<DecChunk>();
+  const IdxJob *ijobs = ctx->dec_idx.as<IdxJob>();
 
   for (size_t i = 0; i < n_blocks; i++)
     FQ_HIP(hipMemsetAsync(blocks[i]->result, 0, sizeof(BlockResult), st));
@@ -1050,54 +1023,24 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   fq_timer_span_begin(ctx, "decode", st);
   FQ_HIP(hipEventRecord(ctx->dec_fork, st));
   FQ_HIP(hipStreamWaitEvent(st2, ctx->dec_fork, 0));
-  const DecChunk *dch = ctx->dec_chunks.as<DecChunk>();
-  const IdxJob *ijobs = ctx->dec_idx.as<IdxJob>();
-  if (build_index && n_blocks <= (size_t)ctx->n_cus) {  // (the placement rule of the plain decode)
-    hipLaunchKernelGGL(k_decode_indexing_both, dim3((unsigned)(2 * n_blocks)), dim3(64), 0, st, jobs, ijobs, (unsigned)n_blocks, ts, tq);
-  } else if (build_index) {
-    hipLaunchKernelGGL(k_decode_indexing<QualModel>, dim3((unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, tq);
-    hipLaunchKernelGGL(k_decode_indexing<SeqModel>, dim3((unsigned)n_blocks), dim3(64), 0, st2, jobs, ijobs, ts);
-  } else if (n_plain && 2 * n_plain <= 2 * (size_t)ctx->n_cus) {
-    hipLaunchKernelGGL(k_decode_both, dim3((unsigned)(2 * n_plain)), dim3(64), 0, st, jobs, (unsigned)n_plain, ts, tq);
-  } else if (n_plain) {
-    // more quality chains than places for the resident form (two 66 KB workgroups per CU): the compact form
-    if (n_plain > 2 * (size_t)ctx->n_cus) hipLaunchKernelGGL((k_decode<QualModel, true>), dim3((unsigned)n_plain), dim3(64), 0, st, jobs, tq);
-    else hipLaunchKernelGGL((k_decode<QualModel, false>), dim3((unsigned)n_plain), dim3(64), 0, st, jobs, tq);
-    hipLaunchKernelGGL((k_decode<SeqModel, false>), dim3((unsigned)n_plain), dim3(64), 0, st2, jobs, ts);
-  }
-  if (n_qual_chunks > 2 * (size_t)ctx->n_cus) hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
+  if (build_index) launch_whole_streams<true>(ctx, jobs, ijobs, n_plain, ts, tq);
+  else if (n_plain) launch_whole_streams<false>(ctx, jobs, nullptr, n_plain, ts, tq);
+  if (crowded(ctx, n_qual_chunks)) hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
   else if (n_qual_chunks) hipLaunchKernelGGL((k_decode_chunks<QualModel, false>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
-  if (chunks.size() > n_qual_chunks)
-    hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)(chunks.size() - n_qual_chunks)), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
+  if (n_seq_chunks) hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
   FQ_HIP(hipEventRecord(ctx->dec_join, st2));
   FQ_HIP(hipStreamWaitEvent(st, ctx->dec_join, 0));
   fq_timer_span_end(ctx, st);
   fq_timer_span_begin(ctx, "npatch", st);
-  // the N counts are gathered and scanned over whole blocks; the patch covers whole blocks or the plan's window
-  const size_t n_patch = plan ? plan->w1 - plan->w0 : r_max;
-  const unsigned gx = (unsigned)min((r_max + 255) / 256, (size_t)4096), gp = (unsigned)min((n_patch + 255) / 256, (size_t)4096);
-  hipLaunchKernelGGL(k_gather_ncount, dim3(gx ? gx : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
-                     ctx->n_cnt32.as<uint32_t>());
-  if ((rc = fq_scan_u32_to_u32(st, ctx->n_cnt32.as<uint32_t>(), r_tot, ctx->n_off.as<uint32_t>(),
-                               ctx->scan_tmp)))
-    return rc;
-  hipLaunchKernelGGL(k_npatch, dim3(gp ? gp : 1, (unsigned)n_blocks), dim3(256), 0, st, jobs,
-                     ctx->n_off.as<uint32_t>(), plan ? plan->w0 : 0u, plan ? plan->w1 : ~0u);
+  if ((rc = launch_n_pass(ctx, jobs, n_blocks, r_tot, r_max, plan))) return rc;
   fq_timer_span_end(ctx, st);
   if (build_index) {
     fq_timer_span_begin(ctx, "dindex", st);
-    const dim3 gm(snap_max / 256 + 1, (unsigned)n_blocks);
-    hipLaunchKernelGGL(k_dindex_meta<SeqModel>, gm, dim3(256), 0, st, jobs, ijobs);
-    hipLaunchKernelGGL(k_dindex_meta<QualModel>, gm, dim3(256), 0, st, jobs, ijobs);
-    if (snap_max) {
-      const unsigned gy = (snap_max + 63) / 64;
-      hipLaunchKernelGGL(k_resolve_states<SeqModel>, dim3(FQGPU_SEQ_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, ts);
-      hipLaunchKernelGGL(k_resolve_states<QualModel>, dim3(FQGPU_QUAL_MODELS, gy, (unsigned)n_blocks), dim3(64), 0, st, jobs, ijobs, tq);
-    }
+    launch_index_finish(ctx, jobs, ijobs, n_blocks, snap_max, ts, tq);
     fq_timer_span_end(ctx, st);
     for (size_t i = 0; i < n_blocks; i++)
       for (int s = 0; s < 2; s++)
-        blocks[i]->index_bytes[s] = sizeof(FqIndexHeader) + (size_t)ihost[i].n_snap * fq_index_snap_bytes(s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
+        blocks[i]->index_bytes[s] = fq_index_bytes(ihost[i].n_snap, s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
   }
   FQ_HIP(hipGetLastError());
   return FQGPU_OK;

@@ -12,28 +12,9 @@ __global__ void __launch_bounds__(256)
 k_index_meta(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs,
              const uint32_t *__restrict__ rec_start, unsigned R, unsigned n_sym, unsigned stride,
              const unsigned long long *__restrict__ tile_bit_base, unsigned bit_base_unit, uint8_t *__restrict__ index) {
-  const unsigned n_snap = n_sym ? (n_sym - 1) / stride : 0u;
   const unsigned k = blockIdx.x * blockDim.x + threadIdx.x;  // 0: header, 1 .. n_snap: snapshots
-  if (k == 0) {
-    FqIndexHeader h;
-    h.magic = FQ_INDEX_MAGIC; h.stream = M::STREAM; h.stride = stride; h.n_snap = n_snap;
-    h.n_sym = n_sym; h.reserved = 0;
-    *reinterpret_cast<FqIndexHeader *>(index) = h;
-    return;
-  }
-  if (k > n_snap) return;
-  const unsigned e = k * stride;
-  uint8_t *snap = index + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)M::B);
-  *reinterpret_cast<unsigned long long *>(snap) = tile_bit_base[e / bit_base_unit];  // stride is a multiple of both the packing tile and the sorted tile
-  // symbol e - 1: record r, position p (encode order walks a record from its last position)
-  const unsigned r = fq_locate(rec_start, 0, R - 1, e - 1);
-  const fqgpu_rec rec = recs[r];
-  const unsigned p = rec.len - 1u - (e - 1u - rec_start[r]);
-  const uint8_t *line = raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
-  unsigned packed = 0;
-  for (unsigned i = 0; i < 4; i++) packed |= (p >= i + 1 ? (unsigned)line[p - 1 - i] : 0xFFu) << (8 * i);
-  reinterpret_cast<uint32_t *>(snap)[2] = packed;
-  reinterpret_cast<uint32_t *>(snap)[3] = 0;
+  uint8_t *snap = fq_index_write_meta<M>(index, k, n_sym, stride, raw, recs, rec_start, R);
+  if (snap) *reinterpret_cast<unsigned long long *>(snap) = tile_bit_base[(k * stride) / bit_base_unit];  // stride is a multiple of both the packing tile and the sorted tile
 }
 
 template <class M>
@@ -46,13 +27,11 @@ k_index_states(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restric
   extern __shared__ uint32_t lds[];
   constexpr unsigned B = M::B;
   const unsigned c = blockIdx.x;
-  const unsigned n_snap = n_sym ? (n_sym - 1) / stride : 0u;
+  const unsigned n_snap = fq_index_n_snap(n_sym, stride);
   const unsigned k = blockIdx.y * 64 + fq_lane() + 1;
   const unsigned n = arrays[c], run0 = arrays[B + c];
   if (n == 0) {  // (uniform) a context without symbols keeps its initial state: decoder state 0
-    if (k <= n_snap)
-      reinterpret_cast<uint16_t *>(index + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B) +
-                                   FQ_INDEX_SNAP_HEAD)[c] = 0;
+    if (k <= n_snap) fq_index_states(index, B, k)[c] = 0;
     return;
   }
   const LdsCTable t = stage_ctable<M>(lds, ct + ct_off[c]);
@@ -71,7 +50,5 @@ k_index_states(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restric
       for (unsigned i = seg * S; i < rel; i++) (void)chain_step(t, x, sym[i] & (unsigned)(M::A - 1));
     }
   }
-  uint16_t *st = reinterpret_cast<uint16_t *>(index + sizeof(FqIndexHeader) + (size_t)(k - 1) * (FQ_INDEX_SNAP_HEAD + 2 * (size_t)B) +
-                                              FQ_INDEX_SNAP_HEAD);
-  st[c] = (uint16_t)(x - size);
+  fq_index_states(index, B, k)[c] = (uint16_t)(x - size);
 }

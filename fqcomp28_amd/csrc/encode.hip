@@ -425,14 +425,9 @@ int encode_stream(fqgpu_ctx *ctx, EncLane &lane, hipStream_t st, fqgpu_dblock *b
   b->index_bytes[M::STREAM] = 0;
   if ((flags & FQGPU_F_DECODE_INDEX) && !dbg_mask) {
     const unsigned stride = ctx->index_stride;
-    const unsigned n_snap = n_sym ? (n_sym - 1) / stride : 0u;
-    const size_t bytes = sizeof(FqIndexHeader) + (size_t)n_snap * fq_index_snap_bytes(B);
-    if (bytes > b->index_cap[M::STREAM]) {
-      if (b->index[M::STREAM]) FQ_HIP(hipFree(b->index[M::STREAM]));
-      b->index[M::STREAM] = fq_dev_alloc<uint8_t>(bytes + 64);
-      b->index_cap[M::STREAM] = b->index[M::STREAM] ? bytes : 0;
-      if (!b->index[M::STREAM]) return FQGPU_E_NOMEM;
-    }
+    const unsigned n_snap = fq_index_n_snap(n_sym, stride);
+    const size_t bytes = fq_index_bytes(n_snap, B);
+    if ((rc = fq_index_reserve(b, M::STREAM, bytes, true))) return rc;
     FQ_SPAN_BEGIN(M::STREAM ? "qual.index" : "seq.index");
     hipLaunchKernelGGL(k_index_meta<M>, dim3(n_snap / 256 + 1), dim3(256), 0, st, b->raw, b->recs, rec_start, R, n_sym,
                        stride, sc.tile_bit_base.as<unsigned long long>(), tile_path ? TS_TILE : PACK_TILE, b->index[M::STREAM]);

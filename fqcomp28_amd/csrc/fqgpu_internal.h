@@ -318,7 +318,33 @@ struct FqIndexHeader {
 //   u32 reserved
 //   u16 state[B]   decoder state (encoder state - table size) of every context at that point
 constexpr unsigned FQ_INDEX_MAGIC = 0x58495146u, FQ_INDEX_SNAP_HEAD = 16;
-static inline size_t fq_index_snap_bytes(unsigned B) { return FQ_INDEX_SNAP_HEAD + 2 * (size_t)B; }
+// The layout's arithmetic, host and device, here and nowhere else (B = contexts of the stream's model).
+#if defined(__HIPCC__)
+#define FQ_HD __host__ __device__
+#else
+#define FQ_HD
+#endif
+template <class N> FQ_HD static inline unsigned fq_index_n_snap(N n_sym, unsigned stride) { return n_sym ? (unsigned)((n_sym - 1) / stride) : 0u; }
+FQ_HD static inline size_t fq_index_snap_bytes(unsigned B) { return FQ_INDEX_SNAP_HEAD + 2 * (size_t)B; }
+FQ_HD static inline size_t fq_index_bytes(size_t n_snap, unsigned B) { return sizeof(FqIndexHeader) + n_snap * fq_index_snap_bytes(B); }
+// snapshot k = 1 .. n_snap (u64 bitpos first) and its u16 state[B]
+template <class P> FQ_HD static inline P *fq_index_snap(P *index, unsigned B, unsigned k) { return index + fq_index_bytes(k - 1, B); }
+FQ_HD static inline uint16_t *fq_index_states(uint8_t *index, unsigned B, unsigned k) {
+  return reinterpret_cast<uint16_t *>(fq_index_snap(index, B, k) + FQ_INDEX_SNAP_HEAD);
+}
+FQ_HD static inline const uint16_t *fq_index_states(const uint8_t *index, unsigned B, unsigned k) { return fq_index_states(const_cast<uint8_t *>(index), B, k); }
+// room on the device for `bytes` of the block's decode index of stream s (never shrinks); check_free: a failing hipFree of
+// the outgrown buffer is an error
+static inline int fq_index_reserve(fqgpu_dblock *b, int s, size_t bytes, bool check_free) {
+  if (bytes <= b->index_cap[s]) return FQGPU_OK;
+  if (b->index[s]) {
+    const hipError_t e = hipFree(b->index[s]);
+    if (check_free) FQ_HIP(e);
+  }
+  b->index[s] = fq_dev_alloc<uint8_t>(bytes + 64);
+  b->index_cap[s] = b->index[s] ? bytes : 0;
+  return b->index[s] ? FQGPU_OK : FQGPU_E_NOMEM;
+}
 
 // ---------------------------------------------------------------- launches (encode.hip / decode.hip / tables.hip)
 int fq_build_freq_tables(int device, hipStream_t st, const uint8_t *raw_dev, const fqgpu_rec *recs_dev,
@@ -461,6 +487,35 @@ __device__ __forceinline__ unsigned fq_locate(const uint32_t *__restrict__ rec_s
     if (rec_start[mid] <= e) lo = mid; else hi = mid - 1;
   }
   return lo;
+}
+
+// Decode index of stream M of a block as it lies in raw / recs (the block the encoder coded, or the restored one), everything
+// but bit positions and states.  k = 0: the header.  k = 1 .. n_snap: the `prev` bytes of snapshot k -- symbol k stride - 1 is
+// position p of record r (encode order walks a record from its last position), the four bytes in front of it -- and the
+// reserved word; returns the snapshot.  nullptr: nothing left for the caller to write.
+template <class M>
+__device__ __forceinline__ uint8_t *fq_index_write_meta(uint8_t *index, unsigned k, unsigned n_sym, unsigned stride, const uint8_t *raw,
+                                                        const fqgpu_rec *recs, const uint32_t *rec_start, unsigned R) {
+  const unsigned n_snap = fq_index_n_snap(n_sym, stride);
+  if (k == 0) {
+    FqIndexHeader h;
+    h.magic = FQ_INDEX_MAGIC; h.stream = M::STREAM; h.stride = stride; h.n_snap = n_snap;
+    h.n_sym = n_sym; h.reserved = 0;
+    *reinterpret_cast<FqIndexHeader *>(index) = h;
+    return nullptr;
+  }
+  if (k > n_snap) return nullptr;
+  const unsigned e = k * stride;
+  uint8_t *snap = fq_index_snap(index, M::B, k);
+  const unsigned r = fq_locate(rec_start, 0, R - 1, e - 1);
+  const fqgpu_rec rec = recs[r];
+  const unsigned p = rec.len - 1u - (e - 1u - rec_start[r]);
+  const uint8_t *line = raw + (M::STREAM == 0 ? rec.seq_off : rec.qual_off);
+  unsigned packed = 0;
+  for (unsigned i = 0; i < 4; i++) packed |= (p >= i + 1 ? (unsigned)line[p - 1 - i] : 0xFFu) << (8 * i);
+  reinterpret_cast<uint32_t *>(snap)[2] = packed;
+  reinterpret_cast<uint32_t *>(snap)[3] = 0;
+  return snap;
 }
 
 // ---- (context, symbol) of position p of a record, encode-side definition, in two halves so
