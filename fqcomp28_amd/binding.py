@@ -132,6 +132,10 @@ _PROTOS = {
     "fqgpu_ctx_enable_timing": (C.c_int, [C.c_void_p, C.c_int]),
     "fqgpu_ctx_last_timing": (C.c_int, [C.c_void_p, C.POINTER(Timing)]),
     "fqgpu_ctx_timing_only": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "fqgpu_chunk_crc32": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+    "fqgpu_dblock_crc32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
+    "fqgpu_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
+    "fqgpu_ctx_set_check_only": (C.c_int, [C.c_void_p, C.c_int]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -237,6 +241,11 @@ def memdecompress(cdata, original_size):
     return out[:0] if cdata.size == 0 else out
 
 
+def crc32_combine(crc_a, crc_b, len_b):
+    """fqgpu_crc32_combine: the zlib CRC-32 of A || B from the digests of A and B and the length of B"""
+    return lib().fqgpu_crc32_combine(crc_a, crc_b, len_b)
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -329,6 +338,13 @@ class DBlock:
     def wipe(self):
         _check(lib().fqgpu_dblock_wipe(self.ctx.h, self.h), "dblock_wipe")
 
+    def crc32(self, want_len=False):
+        """fqgpu_dblock_crc32: zlib CRC-32 of the canonical bytes of the raw block as it lies on the device
+        (want_len: -> (crc, canonical length))"""
+        crc, n = C.c_uint32(0), C.c_size_t(0)
+        _check(lib().fqgpu_dblock_crc32(self.ctx.h, self.h, C.byref(crc), C.byref(n)), "dblock_crc32")
+        return (crc.value, n.value) if want_len else crc.value
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -419,6 +435,17 @@ class Context:
     def sync(self):
         _check(lib().fqgpu_sync(self.h), "sync")
 
+    def chunk_crc32(self):
+        """fqgpu_chunk_crc32 -> (rc, crc, len): the chunk on the staging block -- the one encode_raw has just coded, or
+        the one the last whole-chunk decode restored"""
+        crc, n = C.c_uint32(0), C.c_size_t(0)
+        rc = lib().fqgpu_chunk_crc32(self.h, C.byref(crc), C.byref(n))
+        return rc, crc.value, n.value
+
+    def set_check_only(self, on=True):
+        """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""
+        _check(lib().fqgpu_ctx_set_check_only(self.h, 1 if on else 0), "set_check_only")
+
     def enable_timing(self, on=True, only=None):
         """HIP-event spans around the kernel groups; only: restrict them to one group's label"""
         _check(lib().fqgpu_ctx_timing_only(self.h, only.encode() if only else None), "timing_only")
@@ -479,13 +506,14 @@ class Context:
         return dict(rc=rc, seq=bufs["seq"][:sl].copy(), qual=bufs["qual"][:ql].copy(), readlens=bufs["readlens"],
                     n_count=bufs["n_count"], n_pos=bufs["n_pos"][:nn].copy(), raw_after=raw)
 
-    def encode_raw(self, raw, flags=0, recs=None, header_format=None):
+    def encode_raw(self, raw, flags=0, recs=None, header_format=None, want_crc=False):
         """The two-halves call on an UNPARSED chunk (fqgpu_encode_begin / _records / _wait / _end): the
         record table comes back from the GPU.  -> dict like encode_block's, plus recs and used_len.
         header_format = (types, separators, first_header) -- types[i] 0 = NUMERIC / 1 = STRING, separators as bytes,
         first_header with its '@' -- also codes the header fields on the device (fqgpu_encode_headers_*):
         `header_fields` = [(flags, content, lengths) per field] or, for a header that cannot be coded,
-        `headers_rc` = FQGPU_E_HEADER and `bad_record`."""
+        `headers_rc` = FQGPU_E_HEADER and `bad_record`.  want_crc: fqgpu_chunk_crc32 between begin and end ->
+        `crc32`, `crc_len`."""
         raw = np.array(raw, dtype=np.uint8, copy=True)
         n, nb, used = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
         if recs is not None:
@@ -495,6 +523,13 @@ class Context:
         if rc:
             return dict(rc=rc)
         hdr = {}
+        if want_crc:
+            crc, crc_len = C.c_uint32(0), C.c_size_t(0)
+            rc = lib().fqgpu_chunk_crc32(self.h, C.byref(crc), C.byref(crc_len))
+            if rc:
+                lib().fqgpu_encode_cancel(self.h)
+                return dict(rc=rc)
+            hdr["crc32"], hdr["crc_len"] = crc.value, crc_len.value
         if header_format is not None:
             types, seps, first = header_format
             types = np.ascontiguousarray(types, dtype=np.uint8)
@@ -552,9 +587,11 @@ class Context:
         [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
         -> dict(rc, raw, recs, laid_out_len, bad_record); bad_record is None unless the layout was refused.
         build_index=True (index must be None): fqgpu_decode_chunk_indexing, the decode builds the chunk's decode indexes
-        on the way -> also "index": (seq, qual), two empty arrays after a failure; want_raw=False: index only, raw is None."""
+        on the way -> also "index": (seq, qual), two empty arrays after a failure; want_raw=False: raw is None and
+        raw_out == NULL goes down -- index only with build_index, or a decode that only checks on a handle in checking
+        mode (set_check_only); without either the call is refused (FQGPU_E_ARG)."""
         args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
-        raw = np.zeros(raw_len, dtype=np.uint8) if want_raw or not build_index else None
+        raw = np.zeros(raw_len, dtype=np.uint8) if want_raw else None  # (None: index only, or a handle that only checks)
         recs = np.zeros(len(readlens), dtype=REC_DTYPE)
         laid, bad = C.c_size_t(0), C.c_size_t(0)
         if build_index:

@@ -533,6 +533,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->hp_parse.release();  // the device parser's scratch (fqgpu_ctx_reserve / fqgpu_encode_begin without a record table)
   ctx->hp_hdr.release();
   ctx->hp_chunk.release();
+  ctx->crc.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1008,6 +1009,7 @@ static int hp_block_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size_
   b->seq_len = b->qual_len = b->n_pos_len = 0;
   b->index_bytes[0] = b->index_bytes[1] = 0;
   ctx->hp_index_built = false;
+  ctx->hp_crc_what = 0;
   b->last_op = 0;
   b->result_pulled = true;
   memset(&b->host_result, 0, sizeof(b->host_result));
@@ -1040,6 +1042,7 @@ extern "C" int fqgpu_ctx_reserve(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, 
 // written by a copy that is still in flight.
 static int hp_fail(fqgpu_ctx *ctx, int rc) {
   ctx->hp_pending = false;
+  ctx->hp_crc_what = 0;
   (void)fqgpu_sync(ctx);
   return rc;
 }
@@ -1090,6 +1093,7 @@ static int hp_encode_begin(fqgpu_ctx *ctx, const uint8_t *raw, size_t raw_len, c
   ctx->hp_flags = flags;
   ctx->hp_done = st;
   ctx->hp_used = used;
+  ctx->hp_crc_what = 1;
   if (n_recs_out) *n_recs_out = n_recs;
   if (n_bases_out) *n_bases_out = n_bases;
   if (used_len) *used_len = used;
@@ -1141,6 +1145,7 @@ extern "C" int fqgpu_encode_cancel(fqgpu_ctx *ctx) {
   int rc = use_device(ctx->device);
   if (rc) return rc;
   ctx->hp_pending = false;
+  ctx->hp_crc_what = 0;
   ctx->hp_hdr.pending = ctx->hp_hdr.collected = false;
   return fqgpu_sync(ctx);
 }
@@ -1364,10 +1369,15 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
     if (verdict) b->index_bytes[0] = b->index_bytes[1] = 0;
     ctx->hp_index_built = !verdict;
   }
+  if (!verdict && !plan) {  // a whole block, restored: fqgpu_chunk_crc32 may digest it
+    ctx->hp_crc_what = 2;
+    ctx->hp_crc_len = b->raw_len;
+  }
   return verdict;
 }
 
 static int hp_decode(fqgpu_ctx *ctx, const DecStreams &s, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out, size_t raw_len) {
+  if (ctx) ctx->hp_crc_what = 0;  // (whatever becomes of this decode, the chunk before it is no longer what the handle answers for)
   if (!ctx || !s.ok() || !recs || !raw_out) return FQGPU_E_ARG;
   if (s.n_count_len < n_recs) return FQGPU_E_CORRUPT;
   int rc = use_device(ctx->device);
@@ -1435,14 +1445,15 @@ static int layout_verdict(unsigned long long bad, unsigned long long total, size
 }
 
 // Both passes of decodeChunk on the device (decode_headers.hip, then the decode above): only the side streams go up.
-// s.build_index: by the indexing walk, raw_out may be NULL (nothing of the chunk comes back).
+// s.build_index: by the indexing walk, raw_out may be NULL (nothing of the chunk comes back); so it may on a handle that only checks.
 static int decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, const DecStreams &s,
                         uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
   const size_t n_count_len = s.n_count_len;
   if (ctx && s.build_index) ctx->hp_index_built = false;
+  if (ctx) ctx->hp_crc_what = 0;  // (as hp_decode: also a call that is refused for its arguments ends the last chunk's digest)
   if (bad_record) *bad_record = (size_t)-1;
   if (laid_out_len) *laid_out_len = 0;
-  if ((!raw_out && !s.build_index) || !laid_out_len || !bad_record) return FQGPU_E_ARG;
+  if ((!raw_out && !s.build_index && !(ctx && ctx->check_only)) || !laid_out_len || !bad_record) return FQGPU_E_ARG;
   size_t n_bases = 0;
   int rc = chunk_front(ctx, hdr, readlens, n_recs, s, raw_len, nullptr, &n_bases);
   if (rc) return rc;
@@ -1453,7 +1464,9 @@ static int decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const u
   if ((rc = layout_verdict(bad, total, raw_len, n_count_len, n_recs, bad_record))) return rc;
   *laid_out_len = (size_t)total;
   if (total < raw_len) FQ_HIP_HP(hipMemsetAsync(b->raw + total, 0, raw_len - total, ctx->stream));
-  return hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, recs_out, 0, n_recs);
+  rc = hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, recs_out, 0, n_recs);
+  if (!rc) ctx->hp_crc_len = (size_t)total;  // (zeros behind the last record are no part of the chunk)
+  return rc;
 }
 
 extern "C" int fqgpu_decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
@@ -1525,6 +1538,7 @@ extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_strea
                                         size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
   if (bad_record) *bad_record = (size_t)-1;
   if (out_len) *out_len = 0;
+  if (ctx) ctx->hp_crc_what = 0;  // (a range is never digested)
   if (!out_len || !bad_record || first >= end || end > n_recs) return FQGPU_E_ARG;
   const DecStreams s = {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
                         {seq_index_len, qual_index_len}};
@@ -1552,5 +1566,50 @@ extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_strea
   *out_len = len;
   if (!out) return FQGPU_OK;
   if (out_cap < len) return FQGPU_E_OVERFLOW;
-  return hp_decode_staged(ctx, b, s, indexed ? &plan : nullptr, out, skip, len, recs_out, first, end - first);
+  rc = hp_decode_staged(ctx, b, s, indexed ? &plan : nullptr, out, skip, len, recs_out, first, end - first);
+  ctx->hp_crc_what = 0;  // (without indexes the whole chunk was decoded; it still is a range that was asked for)
+  return rc;
+}
+
+// ------------------------------------------------------------------ CRC-32 of a chunk in HBM (crc.hip)
+extern "C" int fqgpu_ctx_set_check_only(fqgpu_ctx *ctx, int on) {
+  if (!ctx) return FQGPU_E_ARG;
+  ctx->check_only = on != 0;
+  return FQGPU_OK;
+}
+
+// The chunk on the staging block, on the handle's copy stream: the chunk in flight arrived there and its record table was
+// uploaded or built there, so the digest runs beside the lane's encode kernels and waits for none of them; after a decode
+// the stream is idle.
+extern "C" int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len) {
+  if (crc) *crc = 0;
+  if (len) *len = 0;
+  int rc = use_device(ctx ? ctx->device : 0);
+  if (rc) return rc;
+  if (!ctx || !crc || !len || !ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
+  const fqgpu_dblock *b = ctx->hp_block;
+  uint32_t c = 0;
+  size_t n = ctx->hp_crc_len;
+  rc = ctx->hp_crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n)
+                             : fq_crc_bytes(ctx, ctx->stream, b->raw, n, &c);
+  if (rc) return rc;
+  *crc = c;
+  *len = n;
+  return FQGPU_OK;
+}
+
+extern "C" int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_t *crc, size_t *len) {
+  if (crc) *crc = 0;
+  if (len) *len = 0;
+  int rc = use_device(ctx ? ctx->device : 0);
+  if (rc) return rc;
+  if (!ctx || !b || !crc || !len || b->device != ctx->device) return FQGPU_E_ARG;
+  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
+  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  uint32_t c = 0;
+  size_t n = 0;
+  if ((rc = fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n))) return rc;
+  *crc = c;
+  *len = n;
+  return FQGPU_OK;
 }

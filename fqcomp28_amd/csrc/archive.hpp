@@ -610,6 +610,139 @@ private:
   Identity identity_;               // reading: the archive the file was written for
 };
 
+/** The digests of an archive's chunks, in a file of their own beside it (`<archive>.fqs`): an extension -- the format has
+ *  no content checksum -- so the .fqc file stays exactly what the reference reads and writes.  A chunk's digest is the
+ *  CRC-32 of zlib (fqgpu_chunk_crc32) of its canonical bytes, i.e. of what a restore lays out for it; the file's digest
+ *  is the chunks' digests combined in chunk order (fqgpu_crc32_combine): for input with bare '+' lines, zlib's CRC-32
+ *  of the FASTQ file.  A few bytes per block: kept in memory, written once (to `.part`, renamed when complete).
+ *  One layout, little-endian, 44 + 12 n bytes:
+ *    u32 "FQS1" | u32 n (blocks) | n x { u32 crc32, u32 canonical length, u32 n_records }, in chunk order |
+ *    u32 crc32 of the whole file | u64 length of the whole file | u64 size of the archive |
+ *    u64 fnv1a-64 of the archive's first 64 KiB (DecodeIndexFile::identityOf) | u32 zlib CRC-32 of every byte in
+ *    front of this word | u32 "FQS1"
+ *  The hash ties the file to ITS archive (belongsTo); the archive's size is recorded but is no part of that match: an
+ *  archive that grew or shrank behind its sums is damage to report (archiveSize), not a foreign file to ignore. */
+class ChunkSumsFile {
+public:
+  static path_t pathFor(const path_t &archive_path) { return path_t(archive_path.string() + ".fqs"); }
+  static constexpr uint32_t MAGIC = 0x31535146u;  // "FQS1"
+  static constexpr std::size_t HEAD = 8, ENTRY = 12, TAIL = 36;
+  struct Sum {
+    uint32_t crc32 = 0, length = 0, n_records = 0;
+    friend bool operator==(const Sum &a, const Sum &b) { return a.crc32 == b.crc32 && a.length == b.length && a.n_records == b.n_records; }
+  };
+
+  ChunkSumsFile() = default;  // to collect (put) and write
+
+  /** Thread-safe.  A chunk's canonical length is below 2^32 like its size in the container. */
+  void put(uint32_t chunk_idx, const Sum &sum) {
+    const std::lock_guard<std::mutex> guard(m_);
+    if (chunk_idx >= sums_.size()) { sums_.resize(chunk_idx + 1u); have_.resize(chunk_idx + 1u, false); }
+    sums_[chunk_idx] = sum;
+    have_[chunk_idx] = true;
+  }
+  /** after the last put and when the archive is complete */
+  void write(const path_t &archive_path) {
+    for (std::size_t i = 0; i < have_.size(); ++i)
+      if (!have_[i]) throw std::runtime_error("chunk sums file: no digest for chunk " + std::to_string(i));
+    combine();
+    const DecodeIndexFile::Identity id = DecodeIndexFile::identityOf(archive_path);
+    archive_size_ = id.size;
+    archive_hash_ = id.hash;
+    std::vector<uint8_t> out(HEAD + ENTRY * sums_.size() + TAIL);
+    uint8_t *p = out.data();
+    le(p, MAGIC, 4);
+    le(p, sums_.size(), 4);
+    for (const Sum &s : sums_) { le(p, s.crc32, 4); le(p, s.length, 4); le(p, s.n_records, 4); }
+    le(p, file_crc32_, 4);
+    le(p, file_length_, 8);
+    le(p, archive_size_, 8);
+    le(p, archive_hash_, 8);
+    le(p, crc32Of(out.data(), static_cast<std::size_t>(p - out.data())), 4);
+    le(p, MAGIC, 4);
+    const path_t final = pathFor(archive_path), part = path_t(final.string() + ".part");
+    {
+      PosFile f(part, PosFile::Mode::Create);
+      f.writeAt(0, out.data(), out.size());
+    }
+    std::filesystem::rename(part, final);
+  }
+
+  /** an existing file; throws std::runtime_error ("chunk sums file: ...") for anything that is not a complete, undamaged one */
+  explicit ChunkSumsFile(const path_t &p) {
+    const PosFile f(p, PosFile::Mode::Read);
+    const uint64_t size = f.size();
+    if (size < HEAD + TAIL) throw std::runtime_error("chunk sums file: too short");
+    uint8_t ends[12];
+    f.readAt(0, ends, 8);
+    f.readAt(size - 4, ends + 8, 4);
+    const uint32_t magic = static_cast<uint32_t>(le(ends, 4)), n = static_cast<uint32_t>(le(ends + 4, 4)), magic2 = static_cast<uint32_t>(le(ends + 8, 4));
+    if (magic != MAGIC) throw std::runtime_error("chunk sums file: not one");
+    if (magic2 != MAGIC || size != HEAD + TAIL + ENTRY * uint64_t(n)) throw std::runtime_error("chunk sums file: damaged trailer (was it closed?)");
+    std::vector<uint8_t> in(static_cast<std::size_t>(size));  // (the size is what n says: nothing is read past the end)
+    f.readAt(0, in.data(), in.size());
+    const uint32_t sum = static_cast<uint32_t>(le(in.data() + in.size() - 8, 4));
+    if (crc32Of(in.data(), in.size() - 8) != sum) throw std::runtime_error("chunk sums file: its checksum does not hold");
+    sums_.resize(n);
+    have_.assign(n, true);
+    const uint8_t *q = in.data() + HEAD;
+    for (Sum &s : sums_) {
+      s = {static_cast<uint32_t>(le(q, 4)), static_cast<uint32_t>(le(q + 4, 4)), static_cast<uint32_t>(le(q + 8, 4))};
+      q += ENTRY;
+    }
+    file_crc32_ = static_cast<uint32_t>(le(q, 4));
+    file_length_ = le(q + 4, 8);
+    archive_size_ = le(q + 12, 8);
+    archive_hash_ = le(q + 20, 8);
+    const uint32_t recorded = file_crc32_;
+    const uint64_t recorded_length = file_length_;
+    combine();
+    if (file_crc32_ != recorded || file_length_ != recorded_length) throw std::runtime_error("chunk sums file: the file's digest is not that of its chunks");
+  }
+
+  [[nodiscard]] std::size_t size() const { return sums_.size(); }
+  [[nodiscard]] const Sum &at(std::size_t chunk_idx) const { return sums_.at(chunk_idx); }
+  [[nodiscard]] uint32_t fileCrc32() const { return file_crc32_; }
+  [[nodiscard]] uint64_t fileLength() const { return file_length_; }
+  [[nodiscard]] uint64_t archiveSize() const { return archive_size_; }
+  [[nodiscard]] uint64_t archiveHash() const { return archive_hash_; }
+  [[nodiscard]] bool belongsTo(const DecodeIndexFile::Identity &archive) const { return archive_hash_ == archive.hash; }
+
+  /** zlib's CRC-32 on the host (of the file's own bytes: a few per block) */
+  static uint32_t crc32Of(const uint8_t *p, std::size_t n) {
+    uint32_t c = 0xFFFFFFFFu;
+    for (std::size_t i = 0; i < n; ++i) {
+      c ^= p[i];
+      for (int k = 0; k < 8; ++k) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+    }
+    return c ^ 0xFFFFFFFFu;
+  }
+
+private:
+  /** every field of the file, byte by byte: little-endian whatever the host is */
+  static void le(uint8_t *&p, uint64_t v, int bytes) {
+    for (int i = 0; i < bytes; ++i) *p++ = static_cast<uint8_t>(v >> (8 * i));
+  }
+  static uint64_t le(const uint8_t *p, int bytes) {
+    uint64_t v = 0;
+    for (int i = 0; i < bytes; ++i) v |= static_cast<uint64_t>(p[i]) << (8 * i);
+    return v;
+  }
+  void combine() {
+    file_crc32_ = 0;
+    file_length_ = 0;
+    for (const Sum &s : sums_) {
+      file_crc32_ = fqgpu_crc32_combine(file_crc32_, s.crc32, s.length);
+      file_length_ += s.length;
+    }
+  }
+  std::mutex m_;
+  std::vector<Sum> sums_;
+  std::vector<bool> have_;
+  uint32_t file_crc32_ = 0;
+  uint64_t file_length_ = 0, archive_size_ = 0, archive_hash_ = 0;
+};
+
 /** Dataset analysis (src/prepare.cpp:42-47): the tables of the first sample_size_bytes of the file, on the GPU */
 inline DatasetMeta analyzeDataset(const path_t &fastq_file, std::size_t sample_size_bytes, int device = 0) {
   FastqChunk chunk;

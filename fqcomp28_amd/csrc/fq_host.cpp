@@ -3,6 +3,7 @@
 // FASTQ generator for the BASELINE.json configurations.  No GPU code.
 #include "../../include/fqgpu.h"
 
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 
@@ -36,6 +37,26 @@ extern "C" long fqgpu_parse_fastq(const uint8_t *raw, size_t len, fqgpu_rec *rec
     pos = p;
   }
   return n;
+}
+
+// CRC-32 (zlib) of A || B from the digests of A and B and the length of B: crc(A) x^(8 len_b) + crc(B) over GF(2),
+// in the CRC's bit order (bit 31 = x^0); the init and final-xor terms of the two digests cancel.
+static uint32_t crc_mul(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int i = 0; i < 32; i++) {
+    p ^= (a & 0x80000000u) ? b : 0u;
+    a <<= 1;
+    b = (b >> 1) ^ ((b & 1u) ? 0xEDB88320u : 0u);
+  }
+  return p;
+}
+extern "C" uint32_t fqgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b) {
+  uint32_t r = 0x80000000u, sq = 0x00800000u;  // x^0, x^8: the exponent counts bytes (any uint64 length, no overflow)
+  for (; len_b; len_b >>= 1) {
+    if (len_b & 1u) r = crc_mul(r, sq);
+    sq = crc_mul(sq, sq);
+  }
+  return crc_mul(crc_a, r) ^ crc_b;
 }
 
 namespace {

@@ -216,6 +216,15 @@ struct ChunkScratch {
   }
 };
 
+// CRC-32 of a chunk in HBM (crc.hip): multiplier tables (built once per handle), the slices' remainders, the result words
+// and, for a chunk with text behind its '+' lines, the canonical bytes gathered into `flat`
+struct CrcScratch {
+  DevBuf tab, rem, res, chk, clen, coff, flat, scan_tmp;
+  uint32_t *host = nullptr;  // page-locked landing place of {crc32, len lo, len hi, 0} and, behind them, the record check's verdict
+  bool tab_built = false;
+  void release();
+};
+
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
@@ -258,6 +267,12 @@ struct fqgpu_ctx {
   HdrScratch hp_hdr;                  // fqgpu_encode_headers_*: the header fields of the block in flight
   ChunkScratch hp_chunk;              // fqgpu_decode_chunk: header decode and layout
   bool hp_index_built = false;        // the staging block holds the indexes fqgpu_decode_chunk_indexing built (fqgpu_decode_index)
+  // fqgpu_chunk_crc32: what of the staging block may be digested -- 0 nothing, 1 the chunk fqgpu_encode_begin uploaded (its
+  // canonical bytes, by its record table), 2 the hp_crc_len bytes a whole-chunk decode has just restored
+  int hp_crc_what = 0;
+  size_t hp_crc_len = 0;
+  bool check_only = false;            // fqgpu_ctx_set_check_only: fqgpu_decode_chunk takes raw_out == NULL
+  CrcScratch crc;
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -387,6 +402,11 @@ int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_re
                     unsigned long long *bad, unsigned long long *total, unsigned long long at[4]);
 int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, ParseScratch &ps, fqgpu_rec *recs_dev,
                      size_t n_recs, size_t *n_bases, size_t *n_n, size_t *used_len);
+
+// CRC-32 of device bytes (crc.hip), on st, waited for: of data_dev[0, len) as it lies / of the canonical bytes of a chunk
+int fq_crc_bytes(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *data_dev, size_t len, uint32_t *crc);
+int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                     uint32_t *crc, size_t *len);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

@@ -52,6 +52,11 @@ struct Settings {  // the part of src/settings.h:36-50 this path needs, plus the
    *  --records query then runs at the indexed pace.  With a usable file nothing is built. */
   bool build_index = false;
   bool index_only = false;  // ... and nothing is restored (processArchiveIndex sets it)
+  /** Extension: compress also writes `<archive>.fqs`, the CRC-32 of every chunk (archive.hpp: ChunkSumsFile); decompress
+   *  verifies every restored chunk against the file whenever a usable one lies beside the archive. */
+  bool checksum = false;
+  bool verify = false;      // decompressFarm: the workspaces take every restored chunk's digest (the sink compares it)
+  bool check_only = false;  // ... and nothing is restored (processArchiveCheck sets both)
 };
 
 struct InputStats {  // src/report.h
@@ -70,6 +75,11 @@ struct FarmReport {
   // decode indexes: blocks decoded from one and the bytes read (index_built false), or blocks given one and the bytes written
   std::size_t indexed_blocks = 0, index_bytes = 0;
   bool index_built = false;
+  // chunk sums: "written" (compress), "used" / "none" / "unusable" (decompress, check); blocks whose digest was compared
+  // and held; the whole file's CRC-32 (written, or as the sums file records it)
+  const char *sums = "none";
+  std::size_t verified_blocks = 0;
+  uint32_t file_crc32 = 0;
 };
 
 namespace detail {
@@ -142,6 +152,7 @@ FarmReport compressFarm(const DatasetMeta &meta, Source &&next_chunk, Sink &&wri
     wksp[t] = std::make_unique<CompressionWorkspace>(&meta, set.devices[t % set.devices.size()]);
     wksp[t]->reserve(set.reading_chunk_size);
     wksp[t]->setDecodeIndex(set.decode_index, set.index_stride);
+    wksp[t]->setChecksum(set.checksum);
     chunks[t].raw_data.reserve(set.reading_chunk_size);
     buffers[t].seq.reserve(set.reading_chunk_size / 8 + (1u << 20));
     buffers[t].qual.reserve(set.reading_chunk_size / 3 + (1u << 20));
@@ -202,16 +213,30 @@ inline FarmReport processReads(const path_t &mates1, const path_t &archive_path,
     std::error_code ec;
     std::filesystem::remove(DecodeIndexFile::pathFor(archive_path), ec);
   }
+  ChunkSumsFile sums;
+  {  // what an earlier archive of this name left behind is not this one's
+    std::error_code ec;
+    std::filesystem::remove(ChunkSumsFile::pathFor(archive_path), ec);
+  }
   FarmReport rep = compressFarm(
       archive.meta(), [&](FastqChunk &c) { return reader.readNextChunk(c); },
       [&](const CompressedBuffersDst &cbs) {
         archive.writeBlock(cbs);
         if (sidecar) sidecar->put(cbs);
+        if (set.checksum) {
+          if (!cbs.digest.valid || cbs.digest.length >= (uint64_t(1) << 32)) throw std::logic_error("no digest was taken of chunk " + std::to_string(cbs.chunk_idx));
+          sums.put(cbs.chunk_idx, {cbs.digest.crc32, static_cast<uint32_t>(cbs.digest.length), cbs.original_size.n_records});
+        }
       },
       [&] { reader.abort(); }, set);
   archive.writeIndex();
   archive.flush();
   if (sidecar) sidecar->close(DecodeIndexFile::identityOf(archive_path));
+  if (set.checksum) {
+    sums.write(archive_path);
+    rep.sums = "written";
+    rep.file_crc32 = sums.fileCrc32();
+  }
   return rep;
 }
 
@@ -225,6 +250,8 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
   detail::runWorkers(T, [&](unsigned t) {
     wksp[t] = std::make_unique<DecompressionWorkspace>(&meta, set.devices[t % set.devices.size()]);
     wksp[t]->setBuildIndex(set.build_index, set.index_stride, set.index_only);
+    wksp[t]->setVerify(set.verify);
+    if (set.check_only) wksp[t]->setCheckOnly(true);
   });
   std::vector<InputStats> istats(T);
   FarmReport rep;
@@ -242,8 +269,11 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
       istats[t].raw += chunk.raw_data.size();
       istats[t].n_records += cbs.original_size.n_records;
       rep.blocks_per_worker[t]++;
-      // (a sink that also takes the block's buffers sees the decode indexes the workspace built)
-      if constexpr (std::is_invocable_v<Sink &, const FastqChunk &, const CompressedBuffersSrc &>) write_chunk(chunk, cbs);
+      // (a sink that also takes the block's buffers sees the decode indexes the workspace built; one that takes a digest
+      // too, what setVerify made of the restored chunk)
+      if constexpr (std::is_invocable_v<Sink &, const FastqChunk &, const CompressedBuffersSrc &, const ChunkDigest &>)
+        write_chunk(chunk, cbs, wksp[t]->lastDigest());
+      else if constexpr (std::is_invocable_v<Sink &, const FastqChunk &, const CompressedBuffersSrc &>) write_chunk(chunk, cbs);
       else write_chunk(chunk);
       clk.lap("write");
       clk.done(chunk.idx);
@@ -275,6 +305,69 @@ inline std::unique_ptr<DecodeIndexFile> openDecodeIndex(const path_t &archive_pa
 }  // namespace detail
 
 namespace detail {
+/** The archive's chunk sums file and what became of it.  strict (the `t` command, whose only job is checking): a file
+ *  that exists and cannot be used -- damaged, unclosed, written for another archive or for another number of blocks --
+ *  is an error, and so is, once every chunk has held, an archive of another size than the recorded one.  Otherwise it is reported on stderr and NOT used: an optional file
+ *  beside a good archive must never keep it from being restored (an archive whose size differs is still verified chunk
+ *  by chunk: the file is its own). */
+class ChunkVerifier {
+public:
+  ChunkVerifier(const path_t &archive_path, std::size_t n_blocks, bool strict) {
+    const path_t p = ChunkSumsFile::pathFor(archive_path);
+    if (!std::filesystem::exists(p)) {
+      if (strict) std::fprintf(stderr, "%s: no chunk sums file: the streams are decoded, nothing is compared\n", archive_path.string().c_str());
+      return;
+    }
+    std::string why;
+    try {
+      sums_ = std::make_unique<ChunkSumsFile>(p);
+      const DecodeIndexFile::Identity id = DecodeIndexFile::identityOf(archive_path);
+      if (!sums_->belongsTo(id)) why = "was written for another archive";
+      else if (sums_->size() != n_blocks) why = "holds " + std::to_string(sums_->size()) + " chunks, the archive " + std::to_string(n_blocks);
+      else if (sums_->archiveSize() != id.size) {  // (reported now; the chunks tell more, so they are still compared)
+        size_differs_ = archive_path.string() + ": the archive has " + std::to_string(id.size) + " bytes, its chunk sums file recorded " +
+                        std::to_string(sums_->archiveSize());
+        std::fprintf(stderr, "%s\n", size_differs_.c_str());
+      }
+    } catch (const std::runtime_error &e) {
+      why = e.what();
+    }
+    if (!why.empty()) {
+      if (strict) throw std::runtime_error(p.string() + ": " + why);
+      std::fprintf(stderr, "%s: %s: not used\n", p.string().c_str(), why.c_str());
+      sums_.reset();
+      state_ = "unusable";
+      return;
+    }
+    state_ = "used";
+  }
+  [[nodiscard]] bool on() const { return sums_ != nullptr; }
+  /** thread-safe; throws when the restored chunk is not the one the writer digested */
+  void check(const CompressedBuffersSrc &cbs, const ChunkDigest &d) {
+    if (!sums_) return;
+    const ChunkSumsFile::Sum &want = sums_->at(cbs.chunk_idx);
+    if (!d.valid || d.crc32 != want.crc32 || d.length != want.length || cbs.original_size.n_records != want.n_records) {
+      char buf[256];
+      std::snprintf(buf, sizeof(buf), "checksum of chunk %u does not hold: restored crc32 %08x, %zu bytes, %u records; recorded crc32 %08x, %u bytes, %u records",
+                    cbs.chunk_idx, d.crc32, d.length, cbs.original_size.n_records, want.crc32, want.length, want.n_records);
+      throw std::runtime_error(buf);
+    }
+    verified_.fetch_add(1);
+  }
+  void report(FarmReport &rep, bool strict = false) const {
+    if (strict && !size_differs_.empty()) throw std::runtime_error(size_differs_);
+    rep.sums = state_;
+    rep.verified_blocks = verified_.load();
+    if (sums_) rep.file_crc32 = sums_->fileCrc32();
+  }
+
+private:
+  std::unique_ptr<ChunkSumsFile> sums_;
+  const char *state_ = "none";
+  std::string size_differs_;
+  std::atomic<std::size_t> verified_{0};
+};
+
 /** A decode index file in the making: `<archive>.fqx.part` until every block's indexes are in it, then closed for the
  *  archive and renamed over whatever `<archive>.fqx` was; a build that does not get there leaves no file (FastqWriter
  *  works the same way) and the old one untouched. */
@@ -320,12 +413,16 @@ private:
  *  and nothing is built. */
 inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &mates1_out, const Settings &set) {
   Archive archive(archive_path);
-  FastqWriter writer(mates1_out, archive.chunkOffsets());
+  const std::vector<uint64_t> chunk_at = archive.chunkOffsets();
+  FastqWriter writer(mates1_out, chunk_at);
   std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
   std::unique_ptr<detail::DecodeIndexBuilder> builder;
+  detail::ChunkVerifier verifier(archive_path, chunk_at.size() - 1, false);
   Settings farm = set;
   farm.build_index = set.build_index && !sidecar;
   farm.index_only = false;
+  farm.verify = verifier.on();
+  farm.check_only = false;
   if (farm.build_index) builder = std::make_unique<detail::DecodeIndexBuilder>(archive_path);
   std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
   FarmReport rep = decompressFarm(
@@ -338,7 +435,8 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
         }
         return true;
       },
-      [&](const FastqChunk &chunk, const CompressedBuffersSrc &cbs) {
+      [&](const FastqChunk &chunk, const CompressedBuffersSrc &cbs, const ChunkDigest &digest) {
+        verifier.check(cbs, digest);  // (before the chunk reaches the file)
         writer.writeChunk(chunk);
         if (builder) builder->put(cbs);
       },
@@ -346,7 +444,39 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
   writer.flush();
   rep.indexed_blocks = used_blocks.load();
   rep.index_bytes = used_bytes.load();
+  verifier.report(rep);
   if (builder) builder->finish(rep);
+  return rep;
+}
+
+/** Extension: `t` -- every block decoded and judged, every chunk's digest compared with the archive's chunk sums file,
+ *  nothing restored and no file written.  Uses the decode index file when it lies there (the indexed pace).  Without a
+ *  chunk sums file the streams are still decoded (rep.sums "none", nothing compared); with one that cannot be used the
+ *  command fails: checking is all it does. */
+inline FarmReport processArchiveCheck(const path_t &archive_path, const Settings &set) {
+  Archive archive(archive_path);
+  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  detail::ChunkVerifier verifier(archive_path, archive.chunkOffsets().size() - 1, true);
+  Settings farm = set;
+  farm.build_index = farm.index_only = false;
+  farm.verify = verifier.on();
+  farm.check_only = true;
+  std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
+  FarmReport rep = decompressFarm(
+      archive.meta(),
+      [&](CompressedBuffersSrc &cbs) {
+        if (!archive.readBlock(cbs)) return false;
+        if (sidecar && sidecar->get(cbs)) {
+          used_blocks.fetch_add(1);
+          used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
+        }
+        return true;
+      },
+      [&](const FastqChunk &, const CompressedBuffersSrc &cbs, const ChunkDigest &digest) { verifier.check(cbs, digest); },
+      [&] { archive.abort(); }, farm);
+  rep.indexed_blocks = used_blocks.load();
+  rep.index_bytes = used_bytes.load();
+  verifier.report(rep, true);
   return rep;
 }
 

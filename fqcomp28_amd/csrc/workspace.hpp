@@ -161,11 +161,23 @@ template <class Buffers, class F> void miscStreams(Buffers &cbs, const headers::
   }
 }
 
+/** Extension: the CRC-32 (zlib's) of a chunk's canonical bytes -- what decodeChunk lays out for it -- and their number
+ *  (fqgpu_chunk_crc32); valid: one was taken */
+struct ChunkDigest {
+  uint32_t crc32 = 0;
+  std::size_t length = 0;
+  bool valid = false;
+};
+
 struct CompressedBuffersDst : CompressedBuffers {
   std::vector<headers::FieldStorageDst> header_fields;
+  /** Extension, not in the .fqc container: filled by encodeChunk when the workspace was asked to (setChecksum).  The
+   *  farm keeps it in a file beside the archive (archive.hpp: ChunkSumsFile). */
+  ChunkDigest digest;
   void clear() override {
     CompressedBuffers::clear();
     for (auto &hf : header_fields) hf.clear();
+    digest = {};
   }
 };
 struct CompressedBuffersSrc : CompressedBuffers {
@@ -323,6 +335,10 @@ public:
     if (on && stride_symbols) fqgpuCheck(fqgpu_ctx_set_index_stride(ctx_, stride_symbols), "setDecodeIndex");
   }
 
+  /** encodeChunk also leaves cbs.digest (extension): the chunk is digested where it lies, on the device, beside its
+   *  encode and before any N -> A reaches a copy of it; off, encodeChunk makes not one call more */
+  void setChecksum(bool on) { checksum_ = on; }
+
   /** Encodes reads into cbs, allocating memory in cbs as needed; mutates the chunk (N -> A).
    *  The chunk may come UNPARSED (records empty, as FastqReader hands it out): the GPU then finds the
    *  records, and chunk.records / the length sums are filled in from its table.  The header fields are coded on
@@ -354,6 +370,10 @@ public:
       fqgpuCheck(fqgpu_encode_headers_begin(ctx_, field_types_.data(), fmt_.separators.data(), static_cast<unsigned>(fmt_.n_fields()),
                                             reinterpret_cast<const uint8_t *>(meta_->first_header.data()), meta_->first_header.size()),
                  "encodeChunk");
+    if (checksum_) {
+      fqgpuCheck(fqgpu_chunk_crc32(ctx_, &cbs.digest.crc32, &cbs.digest.length), "encodeChunk");
+      cbs.digest.valid = true;
+    }
     clk.lap("begin");
     if (!parsed) {
       recs.resize(R);
@@ -425,7 +445,7 @@ public:
 
 private:
   stream_bytes_t header_stage_;  // page-locked landing place of the header field streams
-  bool decode_index_ = false;
+  bool decode_index_ = false, checksum_ = false;
 
 public:
   /** The misc pass (the reference's compressMiscBuffers, src/workspace.cpp:176-213): readlens, n_count,
@@ -478,6 +498,18 @@ public:
     if (on && stride_symbols) fqgpuCheck(fqgpu_ctx_set_index_stride(ctx_, stride_symbols), "setBuildIndex");
   }
 
+  /** Extension: decodeChunk takes the digest of every chunk it restores (fqgpu_chunk_crc32: of the restored bytes where
+   *  they lie on the device, on the device path and on the host-layout path alike); lastDigest() is that of the chunk
+   *  decoded last.  Comparing it with what the writer recorded is the caller's part (process.hpp). */
+  void setVerify(bool on) { verify_ = on; }
+  [[nodiscard]] const ChunkDigest &lastDigest() const { return last_digest_; }
+  /** Extension: decodeChunk decodes and judges everything and restores nothing -- chunk.raw_data stays empty (as with
+   *  setBuildIndex(..., index_only)) */
+  void setCheckOnly(bool on) {
+    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, on ? 1 : 0), "setCheckOnly");
+    check_only_ = on;
+  }
+
   /** Both passes of decodeChunk (src/workspace.cpp:47-88): the first lays the chunk out
    *  (headers decoded, lengths from readlens, '+' and newlines), the second fills the sequence and quality lines.
    *  Both run on the GPU (fqgpu_decode_chunk: only the side streams go up, no skeleton).  FQGPU_SHIM_HOST_HEADERS=1
@@ -485,6 +517,7 @@ public:
    *  stream that runs out, a chunk too small for its records, a format it does not take) goes through the host path
    *  as well, so that the error is the host's. */
   void decodeChunk(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
+    last_digest_ = {};
     // (an index is built by the device path alone: FQGPU_SHIM_HOST_HEADERS does not apply to a chunk that is to get one)
     if ((!hostHeaders() || buildsIndexFor(cbs)) && decodeChunkOnDevice(chunk, cbs)) return;
     StageClock clk;
@@ -527,6 +560,8 @@ public:
                                           recs.data(), recs.size(), reinterpret_cast<uint8_t *>(chunk.raw_data.data()),
                                           chunk.raw_data.size(), s.index[0], s.index_len[0], s.index[1], s.index_len[1]),
                "decodeChunk");
+    takeDigest();
+    if (check_only_) { chunk.raw_data.clear(); chunk.records.clear(); }  // (the host layout needs the chunk; the caller gets none)
     clk.lap("gpu");
     clk.done(chunk.idx);
   }
@@ -581,7 +616,7 @@ private:
   /** decodeChunk through fqgpu_decode_chunk; false: the device refused the chunk (the host path decides) */
   bool decodeChunkOnDevice(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
     StageClock clk;
-    const bool build = buildsIndexFor(cbs), restore = !(build && index_only_);
+    const bool build = buildsIndexFor(cbs), restore = !(build && index_only_) && !check_only_;
     chunk.clear();
     chunk.idx = cbs.chunk_idx;
     if (restore) {
@@ -602,9 +637,10 @@ private:
                                                        &laid_out, &bad)
                          : fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, n, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
                                               s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], raw_out,
-                                              chunk.raw_data.size(), recs.data(), &laid_out, &bad);
+                                              cbs.original_size.total, recs.data(), &laid_out, &bad);
     clk.lap("gpu");
     if (!deviceTook(rc, bad, "decodeChunk")) return false;
+    takeDigest();
     for (int k = 0; k < 2 && build; ++k) {
       std::size_t len = 0;
       fqgpuCheck(fqgpu_decode_index(ctx_, k, nullptr, 0, &len), "decodeChunk");
@@ -633,7 +669,14 @@ private:
     return true;
   }
 
-  bool build_index_ = false, index_only_ = false;
+  bool build_index_ = false, index_only_ = false, verify_ = false, check_only_ = false;
+  ChunkDigest last_digest_;
+  /** the digest of the chunk the handle has just restored */
+  void takeDigest() {
+    if (!verify_) return;
+    fqgpuCheck(fqgpu_chunk_crc32(ctx_, &last_digest_.crc32, &last_digest_.length), "decodeChunk");
+    last_digest_.valid = true;
+  }
   /** setBuildIndex is on and this chunk came without indexes */
   bool buildsIndexFor(const CompressedBuffersSrc &cbs) const {
     return build_index_ && cbs.decode_index[0].empty() && cbs.decode_index[1].empty();

@@ -376,6 +376,38 @@ int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, co
                              size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap, size_t *out_len,
                              fqgpu_rec *recs_out, size_t *bad_record);
 
+/* ---- Extension (nothing in the reference, whose format has no content checksum): CRC-32 of a chunk, taken where the
+ * chunk lies already -- in HBM.  The digest is the CRC-32 of zlib / gzip (reflected polynomial 0xEDB88320, initial value
+ * and final xor 0xFFFFFFFF: Python's zlib.crc32) of the chunk's CANONICAL bytes, which are exactly what fqgpu_decode_chunk
+ * lays out for it: per record the header line with its '\n', the sequence, "\n+\n", the quality line, '\n'.  For input
+ * whose '+' lines are bare these are the input bytes up to the end of the last complete record; text behind a '+', which
+ * the parsers accept and the format drops, is not part of the digest, so the digest of a chunk about to be encoded and
+ * that of the chunk restored from its streams agree.  N bases are digested as N (what a restore yields).
+ *   fqgpu_chunk_crc32    the chunk on the handle's staging block.  Valid (a) from fqgpu_encode_begin until the handle's
+ *                        next host-pointer call (fqgpu_encode_cancel ends it too): the chunk in flight, digested on the
+ *                        handle's copy stream beside the lane's encode, as the header fields are; *len = the canonical
+ *                        length (= *used_len for bare '+' lines).  The host-pointer encode never patches the device copy,
+ *                        so FQGPU_F_WRITE_BACK_N does not change the digest.  (b) after a SUCCESSFUL fqgpu_decode_chunk,
+ *                        fqgpu_decode_chunk_indexing (*len = *laid_out_len), fqgpu_decode_block or fqgpu_decode_block_indexed
+ *                        (*len = raw_len: the block as the caller laid it out, digested as it lies).  Everywhere else --
+ *                        after a failed decode (a call refused for its arguments included: every host-pointer decode
+ *                        ends the digest of the chunk before it), after fqgpu_decode_chunk_range, with no chunk on the handle --
+ *                        FQGPU_E_ARG with *crc = 0, *len = 0.
+ *   fqgpu_dblock_crc32   waits for the block's last operation as fqgpu_dblock_status does, then digests the canonical bytes
+ *                        of its raw block by its record table -- of WHATEVER the raw block holds when asked: after
+ *                        fqgpu_dblock_encode with FQGPU_F_WRITE_BACK_N that is 'A' where the input had 'N'; take the
+ *                        digest before such an encode (or after a decode) if it is to match a restore.
+ *   fqgpu_crc32_combine  host helper: the digest of A || B from those of A and B and the length of B.  A file's digest is
+ *                        its chunks' digests combined in chunk order.
+ *   fqgpu_ctx_set_check_only  on != 0: fqgpu_decode_chunk accepts raw_out == NULL -- everything is decoded and judged,
+ *                        nothing of the chunk comes back (recs_out, *laid_out_len, *bad_record as always), the digest is
+ *                        there to be asked for.  Off (the default) the call refuses NULL.
+ * Without a GPU the two digest calls return FQGPU_E_NO_DEVICE; the combine helper works. */
+int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len);
+int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_t *crc, size_t *len);
+uint32_t fqgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
+int fqgpu_ctx_set_check_only(fqgpu_ctx *ctx, int on);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -1,17 +1,28 @@
 // fqc_tool -- the reference's two commands over the GPU block farm (fqcomp28_amd/csrc/process.hpp):
 //   fqc_tool c <in.fastq> <out.fqc> [-t threads] [-R block MiB] [-S sample MiB] [-d dev,dev,...] [--accumulate-n]
 //              [--index [--index-stride Ki symbols, a multiple of 64]]   (extension: decode indexes in <out.fqc>.fqx)
+//              [--checksum]   (extension: the CRC-32 of every chunk and of the whole file in <out.fqc>.fqs; the archive itself
+//               is what it is without the option.  For input with bare '+' lines the file's value is zlib's CRC-32 of <in.fastq>)
 //   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--records A:B] [--index [--index-stride Ki]]
 //              (extension: --records restores records A .. B-1 only, numbered from 0 across the archive; A: = to the end)
 //              (extension: --index also leaves <in.fqc>.fqx behind if no usable one lies there: restore and index in one pass;
 //               --records never builds)
+//              (extension: with <in.fqc>.fqs beside the archive every restored chunk is verified before it is written: a chunk
+//               whose digest differs ends the command, exit 1, no output.  A .fqs that is damaged, unclosed or another archive's
+//               is reported and not used; --records never verifies)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
 //               builds afresh and replaces the old file once the last block has succeeded)
+//   fqc_tool t <in.fqc> [-t threads] [-d dev,dev,...]
+//              (extension: decodes every block, restores nothing, writes no file; compares every chunk with <in.fqc>.fqs --
+//               exit 1 at the first that differs, and when the .fqs is there but cannot be used or the archive's size is not
+//               the recorded one.  Without a .fqs the streams are still decoded: "sums": "none", a warning, exit 0.  Uses
+//               <in.fqc>.fqx when it lies there)
 // (fqcomp28 c --i1 in.fastq -o out.fqc -t N / fqcomp28 d -i out.fqc --o1 out.fastq, src/app.cpp:29-76.)
 // Prints one JSON line with sizes, seconds and blocks per worker; d and x also say how many blocks were decoded from a decode
-// index ("index": "used") or were given one ("built"), and its bytes.  Needs a GPU: no CPU fallback.
+// index ("index": "used") or were given one ("built"), and its bytes; "sums" / "verified" / "crc32": what became of the chunk
+// sums file, the blocks whose digest was compared and held, the whole file's CRC-32.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -21,24 +32,28 @@
 using namespace fqcomp28;
 
 int main(int argc, char **argv) {
+  const bool check_cmd = argc >= 2 && !strcmp(argv[1], "t");
   const bool index_cmd = argc >= 2 && !strcmp(argv[1], "x");
-  if (argc < (index_cmd ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !index_cmd)) {
-    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--records A:B]\n"
-                         "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n");
+  const bool one_arg = index_cmd || check_cmd;  // x and t take the archive alone
+  if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg)) {
+    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B]\n"
+                         "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
+                         "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n");
     return 2;
   }
   Settings set;
   bool range = false;
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
-  for (int i = index_cmd ? 3 : 4; i < argc; ++i) {
+  for (int i = one_arg ? 3 : 4; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
     if (a == "-t") set.n_threads = (unsigned)std::atoi(val());
     else if (a == "-R") set.reading_chunk_size = (std::size_t)std::atoll(val()) << 20;
     else if (a == "-S") set.sample_chunk_size = (std::size_t)std::atoll(val()) << 20;
     else if (a == "--accumulate-n") set.accumulate_n_buffers = true;
-    else if (a == "--index") set.decode_index = true;
-    else if (a == "--index-stride") { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
+    else if (a == "--index" && !check_cmd) set.decode_index = true;  // (t builds nothing)
+    else if (a == "--checksum" && argv[1][0] == 'c') set.checksum = true;
+    else if (a == "--index-stride" && !check_cmd) { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
       const std::string v = val();
@@ -61,7 +76,7 @@ int main(int argc, char **argv) {
     } else if (a == "-d") {
       set.devices.clear();
       for (const char *p = val(); *p;) { set.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p) ++p; }
-    } else { std::fprintf(stderr, "unknown option %s\nusage: fqc_tool c|d <in> <out> [options] | fqc_tool x <in.fqc> [options]\n", a.c_str()); return 2; }
+    } else { std::fprintf(stderr, "unknown option %s\nusage: fqc_tool c|d <in> <out> [options] | fqc_tool x|t <in.fqc> [options]\n", a.c_str()); return 2; }
   }
   try {
     const bool comp = argv[1][0] == 'c';
@@ -69,7 +84,8 @@ int main(int argc, char **argv) {
       set.build_index = set.decode_index && !range;
       set.decode_index = false;
     }
-    const FarmReport r = index_cmd ? processArchiveIndex(argv[2], set)
+    const FarmReport r = check_cmd ? processArchiveCheck(argv[2], set)
+                         : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
@@ -82,6 +98,11 @@ int main(int argc, char **argv) {
     if (!comp)
       std::printf(", \"index\": \"%s\", \"indexed_blocks\": %zu, \"index_bytes\": %zu", r.index_built ? "built" : r.indexed_blocks ? "used" : "none",
                   r.indexed_blocks, r.index_bytes);
+    if (comp && set.checksum) std::printf(", \"sums\": \"%s\", \"crc32\": \"%08x\"", r.sums, r.file_crc32);
+    if (!comp && argv[1][0] != 'x') {
+      std::printf(", \"sums\": \"%s\", \"verified\": %zu", r.sums, r.verified_blocks);
+      if (r.verified_blocks) std::printf(", \"crc32\": \"%08x\"", r.file_crc32);
+    }
     std::printf("}\n");
   } catch (const std::exception &e) {
     std::fprintf(stderr, "fqc_tool: %s\n", e.what());

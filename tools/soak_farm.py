@@ -8,6 +8,8 @@ random SHAPE (one to a dozen fields; names that change, numbers that walk, jump,
 number; one bare string) and every header field stream of every block is compared with oracle/headers_oracle.py --
 the header fields are coded on the GPU (headers.hip).  One file in twenty has ONE header that cannot be coded: the
 command must fail.  One in three is compressed with --index (decode indexes beside the archive, used by the restore).
+One in two is compressed with --checksum: the whole file's CRC-32 in the report must be zlib's of the input, the restore
+must have verified every block, and `fqc_tool t` must find every chunk to hold.
     python tools/soak_farm.py [cases, default 40] [first seed]"""
 import json
 import os
@@ -15,6 +17,7 @@ import subprocess
 import sys
 import tempfile
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -67,7 +70,7 @@ def main():
     subprocess.run(["g++", "-std=c++17", "-O2", "-o", exe, os.path.join(ROOT, "tools", "fqc_tool.cpp"), "-L" + os.path.join(ROOT, "fqcomp28_amd"),
                     "-lfqgpu", "-Wl,-rpath," + os.path.join(ROOT, "fqcomp28_amd"), "-lpthread"], check=True)
     t0 = time.time()
-    checked_blocks = refused = bad_headers = checked_fields = 0
+    checked_blocks = refused = bad_headers = checked_fields = checksummed = 0
     with tempfile.TemporaryDirectory(dir="/tmp") as tmp:
         for case in range(cases):
             rng = np.random.default_rng(seed0 + case)
@@ -94,6 +97,8 @@ def main():
                 args += ["-d", "0,0"]
             if rng.random() < 0.33:
                 args += ["--index"]
+            if rng.random() < 0.5:
+                args += ["--checksum"]
             arc, back = os.path.join(tmp, "a.fqc"), os.path.join(tmp, "back.fastq")
             c = subprocess.run([exe, "c", src, arc] + args, capture_output=True, text=True)
             if len(expect) == 0:
@@ -138,6 +143,19 @@ def main():
             assert d.returncode == 0, (case, args, d.stdout[-500:], d.stderr[-500:])
             got = open(back, "rb").read()
             assert got == expect, (case, args, len(got), len(expect))
+            n_blocks = json.loads(c.stdout.strip().splitlines()[-1])["blocks"]
+            d_rep = json.loads(d.stdout.strip().splitlines()[-1])
+            if "--checksum" in args:
+                c_rep = json.loads(c.stdout.strip().splitlines()[-1])
+                assert c_rep["sums"] == "written" and c_rep["crc32"] == "%08x" % zlib.crc32(expect), (case, args, c_rep)
+                assert d_rep["verified"] == n_blocks, (case, args, d_rep)
+                before = sorted(os.listdir(tmp))
+                t = subprocess.run([exe, "t", arc, "-t", str(int(rng.choice([1, 3])))], capture_output=True, text=True)
+                assert t.returncode == 0 and json.loads(t.stdout.strip().splitlines()[-1])["verified"] == n_blocks, (case, args, t.stdout[-300:], t.stderr[-300:])
+                assert sorted(os.listdir(tmp)) == before, (case, "t left a file")
+                checksummed += 1
+            else:
+                assert d_rep["verified"] == 0 and not os.path.exists(arc + ".fqs"), (case, args, d_rep)
             # the archive, read by the independent reader: every block's streams against the oracle
             if "--accumulate-n" not in args and len(expect) < (8 << 20):
                 first_header, seq_ft, qual_ft, blocks, _ = A.read_archive(arc)
@@ -167,7 +185,8 @@ def main():
             if case % 10 == 9:
                 print("case %d of %d, %d archive blocks checked against the oracle, %.0f s" % (case + 1, cases, checked_blocks, time.time() - t0), flush=True)
     print("farm soak: %d cases, %d refused by farm and oracle alike (capacity rule), %d refused for a header that cannot be coded, the rest round-tripped; "
-          "%d archive blocks equal to the oracle's, %d header field streams equal to the header oracle's" % (cases, refused, bad_headers, checked_blocks, checked_fields))
+          "%d archive blocks equal to the oracle's, %d header field streams equal to the header oracle's; %d archives with chunk sums: "
+          "file CRC-32 = zlib's, every restore verified, every `t` clean" % (cases, refused, bad_headers, checked_blocks, checked_fields, checksummed))
 
 
 if __name__ == "__main__":
