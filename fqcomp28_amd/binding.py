@@ -102,6 +102,11 @@ _PROTOS = {
                                            C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                            C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p,
                                            C.POINTER(C.c_size_t)]),
+    "fqgpu_decode_chunk_fasta": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                           C.c_size_t, C.c_size_t, C.c_size_t,
+                                           C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p,
+                                           C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                       C.POINTER(C.c_void_p)]),
     "fqgpu_dblock_create_from_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -615,11 +620,27 @@ class Context:
         of the range's size (asked for first); 0: the size query alone (raw is None).  -> dict(rc, raw, recs, out_len,
         bad_record); raw holds out_len bytes on success, recs the range's records relative to raw."""
         args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
+        return self._decode_range(lib().fqgpu_decode_chunk_range, args, raw_len, first, end, out_cap, out=None)
+
+    def decode_chunk_fasta(self, header_format, header_fields, readlens, seq, n_count, n_pos, raw_len, first, end,
+                           seq_index=None, out_cap=None, out=None):
+        """Records [first, end) of a chunk as FASTA, from the sequence stream alone (fqgpu_decode_chunk_fasta): arguments
+        as decode_chunk_range without the quality stream; seq_index: the chunk's sequence decode index or None; raw_len:
+        the chunk's FASTQ size.  out: a caller's uint8 buffer to decode into (its size is out_cap).  -> as
+        decode_chunk_range; recs hold seq_off into the FASTA bytes and qual_off 0."""
+        index = None if seq_index is None else (seq_index, np.zeros(0, np.uint8))
+        a, keep = _chunk_args(header_format, header_fields, readlens, seq, np.zeros(0, np.uint8), n_count, n_pos, index)
+        args = a[:5] + a[7:13]  # (no quality stream, no quality index)
+        if out is not None:
+            out_cap = out.size
+        return self._decode_range(lib().fqgpu_decode_chunk_fasta, args, raw_len, first, end, out_cap, out)
+
+    def _decode_range(self, fn, args, raw_len, first, end, out_cap, out):
         olen, bad = C.c_size_t(0), C.c_size_t(0)
 
         def call(out, cap, recs):
-            return lib().fqgpu_decode_chunk_range(self.h, *args, raw_len, first, end, _p(out) if out is not None else None, cap,
-                                                  C.byref(olen), _p(recs) if recs is not None else None, C.byref(bad))
+            return fn(self.h, *args, raw_len, first, end, _p(out) if out is not None else None, cap,
+                      C.byref(olen), _p(recs) if recs is not None else None, C.byref(bad))
 
         n_out = max(end - first, 0)
         if out_cap is None:
@@ -629,7 +650,7 @@ class Context:
             out_cap = olen.value
         raw = recs = None
         if out_cap:
-            raw = np.zeros(out_cap, dtype=np.uint8)
+            raw = out if out is not None else np.zeros(out_cap, dtype=np.uint8)
             recs = np.zeros(n_out, dtype=REC_DTYPE)
         rc = call(raw, out_cap, recs)
         if raw is not None and rc == 0:

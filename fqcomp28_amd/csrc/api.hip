@@ -1305,9 +1305,12 @@ struct DecStreams {
   const uint16_t *n_pos;   size_t n_pos_len;
   const uint8_t *index[2]; size_t index_len[2];
   bool build_index = false;  // decode by the indexing walk: the staging block is left with both indexes (index / index_len: none)
+  bool seq_only = false;     // fqgpu_decode_chunk_fasta: no quality stream, no quality index; records are placed as FASTA
   bool ok() const {
-    return seq && qual && n_count && seq_len && qual_len && (index[0] || !index_len[0]) && (index[1] || !index_len[1]);
+    return seq && n_count && seq_len && (seq_only ? !build_index : qual && qual_len) && (index[0] || !index_len[0]) &&
+           (index[1] || !index_len[1]);
   }
+  int n_streams() const { return seq_only ? 1 : 2; }
 };
 
 // The staging block for a decode of these streams, once the handle is idle
@@ -1315,37 +1318,39 @@ static int hp_decode_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size
   const int rc = fqgpu_sync(ctx);
   if (rc) return rc;
   const size_t seq_cap = s.seq_len > fqgpu_bound_seq(n_bases) ? s.seq_len : fqgpu_bound_seq(n_bases);
-  const size_t qual_cap = s.qual_len > fqgpu_bound_qual(n_bases) ? s.qual_len : fqgpu_bound_qual(n_bases);
+  const size_t qual_cap = s.seq_only ? 0 : s.qual_len > fqgpu_bound_qual(n_bases) ? s.qual_len : fqgpu_bound_qual(n_bases);
   return hp_block_acquire(ctx, raw_len, n_recs, n_bases, seq_cap, qual_cap, s.n_pos_len, b);
 }
 
 // The common part of the host-pointer decodes, once the staging block holds the layout: uploads the streams, decodes
 // (plan != NULL: its strides and window alone) and, when the kernels are through, copies back len bytes of the block from
 // offset skip (out == NULL: nothing of the block) and, recs_out != NULL, the records [first, first + n_out) with their
-// offsets relative to skip.
+// offsets relative to skip.  s.seq_only: the sequence stream alone goes up and is decoded.
 static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s, const FqStridePlan *plan, uint8_t *out, size_t skip,
                             size_t len, fqgpu_rec *recs_out, size_t first, size_t n_out) {
   int rc;
   const size_t n_recs = b->n_recs;
   hipStream_t st = ctx->stream;
   FQ_HIP_HP(hipMemsetAsync(b->seq + s.seq_len, 0, 16, st));  // the bit reader loads whole dwords
-  FQ_HIP_HP(hipMemsetAsync(b->qual + s.qual_len, 0, 16, st));
   FQ_HIP_HP(hipMemcpyAsync(b->seq, s.seq, s.seq_len, hipMemcpyHostToDevice, st));
-  FQ_HIP_HP(hipMemcpyAsync(b->qual, s.qual, s.qual_len, hipMemcpyHostToDevice, st));
+  if (!s.seq_only) {
+    FQ_HIP_HP(hipMemsetAsync(b->qual + s.qual_len, 0, 16, st));
+    FQ_HIP_HP(hipMemcpyAsync(b->qual, s.qual, s.qual_len, hipMemcpyHostToDevice, st));
+  }
   // the reference pops from the END of n_count (src/fse_sequence.cpp:115-126)
   FQ_HIP_HP(hipMemcpyAsync(b->n_count, s.n_count + (s.n_count_len - n_recs), n_recs * 2, hipMemcpyHostToDevice, st));
   if (s.n_pos_len) FQ_HIP_HP(hipMemcpyAsync(b->n_pos, s.n_pos, s.n_pos_len * 2, hipMemcpyHostToDevice, st));
-  for (int k = 0; k < 2; k++)  // (hp_block_acquire has dropped whatever index the staging block held)
+  for (int k = 0; k < s.n_streams(); k++)  // (hp_block_acquire has dropped whatever index the staging block held)
     if (s.index[k] && s.index_len[k]) {
       if ((rc = index_accept(b, k, s.index[k], s.index_len[k]))) return hp_fail(ctx, rc);
       FQ_HIP_HP(hipMemcpyAsync(b->index[k], s.index[k], s.index_len[k], hipMemcpyHostToDevice, st));
       b->index_bytes[k] = s.index_len[k];
     }
-  b->seq_len = s.seq_len; b->qual_len = s.qual_len; b->n_pos_len = s.n_pos_len;
+  b->seq_len = s.seq_len; b->qual_len = s.seq_only ? 0 : s.qual_len; b->n_pos_len = s.n_pos_len;
   b->last_op = 2;
   b->result_pulled = false;
   fqgpu_dblock *one[1] = {b};
-  if ((rc = fq_decode_launch(ctx, one, 1, plan, s.build_index))) return hp_fail(ctx, rc);
+  if ((rc = fq_decode_launch(ctx, one, 1, plan, s.build_index, s.seq_only ? FQ_DEC_SEQ : FQ_DEC_BOTH))) return hp_fail(ctx, rc);
   if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
   // The copies back are issued only when the kernels are through: a copy that waits in a DMA
   // engine's queue for a 13 s decode kernel holds that engine, and the uploads of the next workers'
@@ -1358,7 +1363,7 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
   FQ_HIP_HP(hipStreamSynchronize(st));
   for (size_t i = 0; recs_out && skip && i < n_out; i++) {
     recs_out[i].seq_off -= (uint32_t)skip;
-    recs_out[i].qual_off -= (uint32_t)skip;
+    if (!s.seq_only) recs_out[i].qual_off -= (uint32_t)skip;  // (a FASTA record has no quality line: 0)
   }
   b->host_result = *ctx->hp_result;
   b->result_pulled = true;
@@ -1369,7 +1374,7 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
     if (verdict) b->index_bytes[0] = b->index_bytes[1] = 0;
     ctx->hp_index_built = !verdict;
   }
-  if (!verdict && !plan) {  // a whole block, restored: fqgpu_chunk_crc32 may digest it
+  if (!verdict && !plan && !s.seq_only) {  // a whole block, restored: fqgpu_chunk_crc32 may digest it
     ctx->hp_crc_what = 2;
     ctx->hp_crc_len = b->raw_len;
   }
@@ -1507,15 +1512,16 @@ extern "C" int fqgpu_decode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size
 // decodes its strides k_lo[s] .. k_hi[s] -- the ones that hold a symbol of [rs[first], rs[end]), the rule of
 // fq_decode_launch -- and [w0, w1) are the records those strides write to: a stride of encode indices [e_lo, e_hi) walks
 // from the record of symbol e_hi - 1 down to the record of symbol e_lo.  Without (*indexed = false), the window is the
-// whole chunk and the streams are walked whole.
-static FqStridePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t end, const FqIndexHeader *ix, bool *indexed) {
+// whole chunk and the streams are walked whole.  n_streams = 1: the sequence stream alone, by its index alone.
+static FqStridePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_t end, const FqIndexHeader *ix, int n_streams,
+                               bool *indexed) {
   FqStridePlan p = {{0, 0}, {0, 0}, 0, (unsigned)n, rs};
-  *indexed = ix && ix[0].n_snap && ix[1].n_snap;
+  *indexed = ix && ix[0].n_snap && (n_streams < 2 || ix[1].n_snap);
   if (!*indexed) return p;
   const auto record_of = [&](uint64_t e) { return (size_t)(std::upper_bound(rs, rs + n, (uint32_t)e) - rs) - 1; };
   const uint64_t s0 = rs[first], s1 = rs[end];
   uint64_t lo = s0, hi = s1;
-  for (int s = 0; s < 2; s++) {
+  for (int s = 0; s < n_streams; s++) {
     const uint64_t stride = ix[s].stride;
     p.k_lo[s] = (unsigned)(s0 / stride);
     p.k_hi[s] = (unsigned)((s1 - 1) / stride);
@@ -1529,19 +1535,16 @@ static FqStridePlan range_plan(const uint32_t *rs, size_t n, size_t first, size_
 
 // Records [first, end) of a chunk (include/fqgpu.h): the layout passes of fqgpu_decode_chunk over the whole chunk, the
 // write pass for a window of records, the walk over the strides that hold the range (or over the whole streams), the
-// N pass for the window, and the range's bytes and record table back.
-extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
-                                        const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
-                                        const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
-                                        const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index,
-                                        size_t qual_index_len, size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap,
-                                        size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
+// N pass for the window, and the range's bytes and record table back.  s.seq_only: the same with FASTA records and the
+// sequence stream alone.
+static int decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                              const DecStreams &s, size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap,
+                              size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
+  const size_t n_count_len = s.n_count_len;
   if (bad_record) *bad_record = (size_t)-1;
   if (out_len) *out_len = 0;
   if (ctx) ctx->hp_crc_what = 0;  // (a range is never digested)
   if (!out_len || !bad_record || first >= end || end > n_recs) return FQGPU_E_ARG;
-  const DecStreams s = {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len, {seq_index, qual_index},
-                        {seq_index_len, qual_index_len}};
   std::vector<uint32_t> rs;
   size_t n_bases = 0;
   int rc = chunk_front(ctx, hdr, readlens, n_recs, s, raw_len, &rs, &n_bases);
@@ -1549,16 +1552,20 @@ extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_strea
   // (a damaged index is reported as fqgpu_decode_chunk reports it: behind the layout's verdict)
   FqIndexHeader ix[2];
   int index_rc = FQGPU_OK;
-  for (int k = 0; k < 2; k++)
+  bool have_index = true;
+  for (int k = 0; k < s.n_streams(); k++) {
     if (s.index_len[k] && (rc = index_header(k, n_bases, s.index[k], s.index_len[k], &ix[k])) && !index_rc) index_rc = rc;
+    have_index = have_index && s.index_len[k];
+  }
   bool indexed;
-  const FqStridePlan plan = range_plan(rs.data(), n_recs, first, end, !index_rc && seq_index_len && qual_index_len ? ix : nullptr, &indexed);
+  const FqStridePlan plan = range_plan(rs.data(), n_recs, first, end, !index_rc && have_index ? ix : nullptr, s.n_streams(), &indexed);
   // the size query has no staging block: nothing is written, nothing goes up
   fqgpu_dblock *b = nullptr;
   if ((rc = out ? hp_decode_acquire(ctx, raw_len, n_recs, n_bases, s, &b) : fqgpu_sync(ctx))) return rc;
   const unsigned q[4] = {plan.w0, (unsigned)first, (unsigned)end, plan.w1};
   unsigned long long bad = 0, total = 0, at[4];
-  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b ? b->raw : nullptr, b ? b->recs : nullptr, q, b != nullptr, &bad, &total, at)))
+  if ((rc = fq_chunk_layout(ctx->stream, ctx->hp_chunk, b ? b->raw : nullptr, b ? b->recs : nullptr, q, b != nullptr, &bad, &total, at,
+                            s.seq_only)))
     return hp_fail(ctx, rc);
   if ((rc = layout_verdict(bad, total, raw_len, n_count_len, n_recs, bad_record))) return rc;
   if (index_rc) return index_rc;
@@ -1569,6 +1576,32 @@ extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_strea
   rc = hp_decode_staged(ctx, b, s, indexed ? &plan : nullptr, out, skip, len, recs_out, first, end - first);
   ctx->hp_crc_what = 0;  // (without indexes the whole chunk was decoded; it still is a range that was asked for)
   return rc;
+}
+
+extern "C" int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                        const uint8_t *seq, size_t seq_len, const uint8_t *qual, size_t qual_len,
+                                        const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                                        const uint8_t *seq_index, size_t seq_index_len, const uint8_t *qual_index,
+                                        size_t qual_index_len, size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap,
+                                        size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record) {
+  return decode_chunk_range(ctx, hdr, readlens, n_recs, {seq, seq_len, qual, qual_len, n_count, n_count_len, n_pos, n_pos_len,
+                                                         {seq_index, qual_index}, {seq_index_len, qual_index_len}},
+                            raw_len, first, end, out, out_cap, out_len, recs_out, bad_record);
+}
+
+// The same range as FASTA, from the sequence stream alone (include/fqgpu.h): the chunk is judged on its FASTQ layout, the
+// records are placed as ">hdr\nSEQ\n", and no quality byte is asked for, uploaded or decoded.
+extern "C" int fqgpu_decode_chunk_fasta(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                                        const uint8_t *seq, size_t seq_len, const uint16_t *n_count, size_t n_count_len,
+                                        const uint16_t *n_pos, size_t n_pos_len, const uint8_t *seq_index, size_t seq_index_len,
+                                        size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap, size_t *out_len,
+                                        fqgpu_rec *recs_out, size_t *bad_record) {
+  if (bad_record) *bad_record = (size_t)-1;
+  if (out_len) *out_len = 0;
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;  // (no device: said before any argument is looked at)
+  return decode_chunk_range(ctx, hdr, readlens, n_recs, {seq, seq_len, nullptr, 0, n_count, n_count_len, n_pos, n_pos_len,
+                                                         {seq_index, nullptr}, {seq_index_len, 0}, false, true},
+                            raw_len, first, end, out, out_cap, out_len, recs_out, bad_record);
 }
 
 // ------------------------------------------------------------------ CRC-32 of a chunk in HBM (crc.hip)

@@ -37,9 +37,11 @@
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
+#include <condition_variable>
 #include <filesystem>
 #include <mutex>
 #include <system_error>
+#include <type_traits>
 
 #include <fcntl.h>
 #include <sys/stat.h>
@@ -76,8 +78,11 @@ public:
       if (got < 0 && errno == EINTR) continue;
       if (got <= 0) throw std::runtime_error(path_ + ": file ends inside a read of " + std::to_string(n) + " bytes at " + std::to_string(off));
       p += got; off += static_cast<uint64_t>(got); n -= static_cast<std::size_t>(got);
+      bytes_read_.fetch_add(static_cast<uint64_t>(got), std::memory_order_relaxed);
     }
   }
+  /** bytes readAt has delivered so far */
+  [[nodiscard]] uint64_t bytesRead() const { return bytes_read_.load(std::memory_order_relaxed); }
   void writeAt(uint64_t off, const void *src, std::size_t n) {
     const char *p = static_cast<const char *>(src);
     while (n) {
@@ -93,6 +98,7 @@ private:
   [[noreturn]] void fail(const char *what) const { throw std::system_error(errno, std::generic_category(), path_ + ": " + what); }
   std::string path_;
   int fd_ = -1;
+  mutable std::atomic<uint64_t> bytes_read_{0};
 };
 
 namespace blockfmt {
@@ -139,6 +145,30 @@ struct Cursor {
     if (n) std::memcpy(dst.data(), p, n);
     p += n;
   }
+};
+/** the same over the file itself, field by field: what is skipped is never read */
+struct FileCursor {
+  const PosFile &file;
+  uint64_t at, end;
+  uint32_t u32() {
+    if (end - at < 4) throw std::runtime_error("archive block: truncated");
+    uint32_t v;
+    file.readAt(at, &v, 4);
+    at += 4;
+    return v;
+  }
+  uint32_t sized() {
+    const uint32_t n = u32();
+    if (end - at < n) throw std::runtime_error("archive block: a field runs past the block");
+    return n;
+  }
+  template <class Bytes> void bytes(Bytes &dst) {
+    const uint32_t n = sized();
+    dst.resize(n);
+    if (n) file.readAt(at, dst.data(), n);
+    at += n;
+  }
+  void skip() { at += sized(); }
 };
 }  // namespace blockfmt
 
@@ -224,26 +254,25 @@ public:
     readBlockAt(k, cb);
     return true;
   }
-  /** Block k in input order (chunk k), whatever readBlock has handed out.  Thread-safe. */
-  void readBlockAt(std::size_t k, CompressedBuffersSrc &cb) const {
+  /** Block k in input order (chunk k), whatever readBlock has handed out.  Thread-safe.
+   *  with_qual false (a restore of the sequences alone): the quality stream's bytes are not read from the file -- the
+   *  size words are walked, every other field is read, the quality extent is skipped -- and cb.qual stays empty. */
+  void readBlockAt(std::size_t k, CompressedBuffersSrc &cb, bool with_qual = true) const {
     cb.clear();
     if (k >= index_.size()) throw std::out_of_range("readBlockAt: no block " + std::to_string(k));
     const BlockRef &ref = index_[k];
+    if (!with_qual) {
+      blockfmt::FileCursor cur{file_, ref.offset, ref.end};
+      takeBlock(cur, ref, cb, false);
+      return;
+    }
     std::vector<uint8_t> image(ref.end - ref.offset);
     file_.readAt(ref.offset, image.data(), image.size());
     blockfmt::Cursor cur{image.data(), image.data() + image.size()};
-    const auto &fmt = meta_.header_fmt;
-    cb.chunk_idx = ref.idx;
-    cb.original_size.total = cur.u32();
-    cb.original_size.n_records = cur.u32();
-    cb.original_size.header_fields.assign(fmt.n_fields(), {});
-    cb.compressed_header_fields.resize(fmt.n_fields());
-    cb.header_fields.resize(fmt.n_fields());
-    blockfmt::blockFields(cb, fmt, [&](uint32_t *orig, auto &data) {
-      if (orig) *orig = cur.u32();
-      cur.bytes(data);
-    });
+    takeBlock(cur, ref, cb, true);
   }
+  /** bytes read from the archive file so far (for tests: what a read leaves out shows here) */
+  [[nodiscard]] uint64_t bytesRead() const { return file_.bytesRead(); }
 
   /** the index behind the last block, then the block count at offset 0 */
   void writeIndex() {
@@ -297,6 +326,24 @@ public:
   }
 
 private:
+  /** the fields of a block, in file order, from a cursor over its extent */
+  template <class Cur> void takeBlock(Cur &cur, const BlockRef &ref, CompressedBuffersSrc &cb, bool with_qual) const {
+    const auto &fmt = meta_.header_fmt;
+    cb.chunk_idx = ref.idx;
+    cb.original_size.total = cur.u32();
+    cb.original_size.n_records = cur.u32();
+    cb.original_size.header_fields.assign(fmt.n_fields(), {});
+    cb.compressed_header_fields.resize(fmt.n_fields());
+    cb.header_fields.resize(fmt.n_fields());
+    blockfmt::blockFields(cb, fmt, [&](uint32_t *orig, auto &data) {
+      if (orig) *orig = cur.u32();
+      if constexpr (std::is_same_v<Cur, blockfmt::FileCursor>) {
+        if (!with_qual && static_cast<const void *>(&data) == static_cast<const void *>(&cb.qual)) return cur.skip();
+      }
+      cur.bytes(data);
+    });
+  }
+
   void load() {
     const uint64_t size = file_.size();
     uint8_t head[6];
@@ -472,6 +519,77 @@ private:
   PosFile file_;
   std::vector<uint64_t> at_;
   bool done_ = false;
+};
+
+/** A restored file whose pieces' sizes are known only when they are decoded (FASTA: the archive records FASTQ sizes), so
+ *  FastqWriter's placement by known offsets does not apply.  Piece k goes to the sum of the sizes of the pieces < k: a
+ *  worker that delivers piece k publishes its size, then waits until the sizes of all pieces in front are published, then
+ *  writes outside the lock.  Pieces must be handed out to the workers in order, so a waiter only ever waits for workers
+ *  that are already running.  Written to `<out>.part`; flush() sets the final size and renames; abort() releases every
+ *  waiter with an exception; a run that does not reach flush() leaves neither `<out>` nor `<out>.part`. */
+class OrderedPieceWriter {
+public:
+  /** what a waiter is released with by abort(): the failure is somebody else's */
+  struct Aborted : std::runtime_error {
+    using std::runtime_error::runtime_error;
+  };
+  OrderedPieceWriter(const path_t &out, std::size_t n_pieces)
+      : final_(out), part_(out.string() + ".part"), file_(part_, PosFile::Mode::Create), start_(n_pieces + 1, 0),
+        size_(n_pieces, 0), have_(n_pieces, false) {}
+  ~OrderedPieceWriter() {
+    if (!done_) { std::error_code ec; std::filesystem::remove(part_, ec); }
+  }
+  /** thread-safe; every piece once */
+  void writePiece(std::size_t k, const void *data, std::size_t n) {
+    uint64_t at = 0;
+    {
+      std::unique_lock<std::mutex> lock(m_);
+      if (k >= size_.size() || have_[k]) throw std::logic_error("OrderedPieceWriter: piece " + std::to_string(k) + " is none of this file's, or came twice");
+      size_[k] = n;
+      have_[k] = true;
+      while (known_ < size_.size() && have_[known_]) {  // start_[0 .. known_] are final
+        start_[known_ + 1] = start_[known_] + size_[known_];
+        ++known_;
+      }
+      cv_.notify_all();
+      cv_.wait(lock, [&] { return aborted_ || known_ >= k; });
+      if (aborted_) throw Aborted("OrderedPieceWriter: aborted while piece " + std::to_string(k) + " waited for its place");
+      at = start_[k];
+    }
+    try {
+      if (n) file_.writeAt(at, data, n);
+    } catch (...) {
+      abort();
+      throw;
+    }
+  }
+  /** a worker has failed: nobody waits for its piece any longer */
+  void abort() {
+    { const std::lock_guard<std::mutex> lock(m_); aborted_ = true; }
+    cv_.notify_all();
+  }
+  /** every piece is there: the file gets its size and its name */
+  void flush() {
+    if (done_) return;
+    {
+      const std::lock_guard<std::mutex> lock(m_);
+      if (aborted_ || known_ != size_.size()) throw std::runtime_error("OrderedPieceWriter: flush before every piece was delivered");
+    }
+    file_.resize(start_.back());
+    std::filesystem::rename(part_, final_);
+    done_ = true;
+  }
+  [[nodiscard]] uint64_t bytes() const { return start_.back(); }
+
+private:
+  path_t final_, part_;
+  PosFile file_;
+  std::mutex m_;
+  std::condition_variable cv_;
+  std::vector<uint64_t> start_, size_;
+  std::vector<bool> have_;
+  std::size_t known_ = 0;  // pieces [0, known_) have their sizes published
+  bool aborted_ = false, done_ = false;
 };
 
 /** The decode indexes of an archive's blocks, in a file of their own beside it (`<archive>.fqx`): an extension the

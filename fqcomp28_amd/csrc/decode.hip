@@ -834,9 +834,11 @@ size_t snaps_of(const fqgpu_dblock *b, int stream) {
   const size_t sb = fq_index_snap_bytes(stream ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS);
   return b->index_bytes[stream] >= sizeof(FqIndexHeader) ? (b->index_bytes[stream] - sizeof(FqIndexHeader)) / sb : 0;
 }
-// blocks with a decode index (both streams, at least one snapshot) go to the chunk kernel, the
+// blocks with a decode index (every stream that is decoded, at least one snapshot) go to the chunk kernel, the
 // others to the one-lane-per-stream kernel
-bool indexed(const fqgpu_dblock *b) { return snaps_of(b, 0) && snaps_of(b, 1); }
+bool indexed(const fqgpu_dblock *b, unsigned streams) {
+  return (!(streams & FQ_DEC_SEQ) || snaps_of(b, 0)) && (!(streams & FQ_DEC_QUAL) || snaps_of(b, 1));
+}
 
 DecJob dec_job_of(const fqgpu_dblock *b, size_t rec_base) {
   DecJob j;
@@ -944,10 +946,16 @@ void launch_index_finish(fqgpu_ctx *ctx, const DecJob *jobs, const IdxJob *ijobs
 }  // namespace
 
 // plan (fqgpu_decode_chunk_range): ONE block that holds both decode indexes, walked over the plan's strides alone
-int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan, bool build_index) {
+// streams == FQ_DEC_SEQ (fqgpu_decode_chunk_fasta): the sequence streams alone, on the handle's main stream -- a block
+// counts as indexed by its sequence index, the plan is honoured for stream 0, the N pass runs as ever, result->s[1]
+// stays zero and no quality byte is read.
+int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_blocks, const FqStridePlan *plan, bool build_index,
+                     unsigned streams) {
   hipStream_t st = ctx->stream;
   if (!n_blocks) return FQGPU_OK;
   if (build_index && plan) return FQGPU_E_ARG;
+  if (streams != FQ_DEC_BOTH && (streams != FQ_DEC_SEQ || build_index)) return FQGPU_E_ARG;
+  const bool seq_only = streams == FQ_DEC_SEQ;
   int rc = fqgpu_sync(ctx);  // blocks may still be in an encode lane
   if (rc) return rc;
   if (build_index)  // (an index the block holds is ignored and replaced: every block goes the plain way below)
@@ -956,11 +964,11 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   std::vector<fqgpu_dblock *> blocks;
   blocks.reserve(n_blocks);
   for (size_t i = 0; i < n_blocks; i++)
-    if (!indexed(blocks_in[i])) blocks.push_back(blocks_in[i]);
+    if (!indexed(blocks_in[i], streams)) blocks.push_back(blocks_in[i]);
   const size_t n_plain = blocks.size();
   for (size_t i = 0; i < n_blocks; i++)
-    if (indexed(blocks_in[i])) blocks.push_back(blocks_in[i]);
-  if (plan && (n_blocks != 1 || n_plain || plan->k_hi[0] > snaps_of(blocks[0], 0) || plan->k_hi[1] > snaps_of(blocks[0], 1) ||
+    if (indexed(blocks_in[i], streams)) blocks.push_back(blocks_in[i]);
+  if (plan && (n_blocks != 1 || n_plain || plan->k_hi[0] > snaps_of(blocks[0], 0) || (!seq_only && plan->k_hi[1] > snaps_of(blocks[0], 1)) ||
                plan->w0 > plan->w1 || plan->w1 > blocks[0]->n_recs))
     return FQGPU_E_ARG;
 
@@ -992,11 +1000,11 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     host[i].rec_start = rs;
     if ((rc = rec_start_build(ctx, b, plan, rs))) return rc;
     if (i < n_plain) continue;
-    host[i].index[0] = b->index[0]; host[i].index[1] = b->index[1];
+    host[i].index[0] = b->index[0]; host[i].index[1] = seq_only ? nullptr : b->index[1];
     // every stride of a stream from the last, or the plan's k_lo .. k_hi
     const size_t lo[2] = {plan ? plan->k_lo[0] : 0u, plan ? plan->k_lo[1] : 0u};
     const size_t hi[2] = {plan ? plan->k_hi[0] : snaps_of(b, 0), plan ? plan->k_hi[1] : snaps_of(b, 1)};
-    for (size_t k = hi[1] + 1; k-- > lo[1];) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
+    for (size_t k = hi[1] + 1; !seq_only && k-- > lo[1];) chunks.push_back(DecChunk{(unsigned)i, 1u, (unsigned)k});
     for (size_t k = hi[0] + 1; k-- > lo[0];) seq_chunks.push_back(DecChunk{(unsigned)i, 0u, (unsigned)k});
   }
   const size_t n_qual_chunks = chunks.size(), n_seq_chunks = seq_chunks.size();
@@ -1017,6 +1025,17 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     FQ_HIP(hipMemsetAsync(blocks[i]->result, 0, sizeof(BlockResult), st));
   TabView ts = {ctx->tab[0].logs, ctx->tab[0].log_prefix, ctx->tab[0].dt, ctx->tab[0].dt_off};
   TabView tq = {ctx->tab[1].logs, ctx->tab[1].log_prefix, ctx->tab[1].dt, ctx->tab[1].dt_off};
+  if (seq_only) {  // nothing to run beside: one stream
+    fq_timer_span_begin(ctx, "decode", st);
+    if (n_plain) hipLaunchKernelGGL((k_decode<SeqModel, false, false>), dim3((unsigned)n_plain), dim3(64), 0, st, jobs, nullptr, ts);
+    if (n_seq_chunks) hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st, jobs, dch, ts);
+    fq_timer_span_end(ctx, st);
+    fq_timer_span_begin(ctx, "npatch", st);
+    if ((rc = launch_n_pass(ctx, jobs, n_blocks, r_tot, r_max, plan))) return rc;
+    fq_timer_span_end(ctx, st);
+    FQ_HIP(hipGetLastError());
+    return FQGPU_OK;
+  }
   // the sequence streams run beside the quality streams on a second stream
   if ((rc = dec_stream2_ensure(ctx))) return rc;
   hipStream_t st2 = ctx->dec_stream2;

@@ -21,6 +21,11 @@
 // (atomicMin): flags, contentLength or content exhausted, numeric content short, laid-out end > raw_len.
 // Every stream read is bounds-checked; content bytes are read only by the write pass, which runs only on a good
 // verdict.
+// fqgpu_decode_chunk_fasta places the second record form, FastaForm (">hdr\nSEQ\n"), with the same kernels: the chunk
+// is still judged on the FASTQ layout -- same checks, same first failing record -- so measure, write and pick carry two
+// running sums where the forms differ, the FASTQ offsets to judge by and the FASTA offsets to place by.  The second sums
+// live behind the first in the same buffers (tlen[n_tiles ..], toff[n_tiles + 1 ..]): the kernels' arguments, and the
+// FASTQ instances with them, are what they were.
 #include "fqgpu_internal.h"
 
 #include <charconv>
@@ -79,6 +84,18 @@ __device__ __forceinline__ void cl_num_write(uint8_t *dst, uint32_t v, unsigned 
     m /= 10u;
   }
 }
+
+// The record forms the layout kernels place.  The chunk is judged on FastqForm whichever is placed.
+struct FastqForm {  // @hdr\nSEQ\n+\nQUAL\n
+  static constexpr bool FASTA = false;
+  static constexpr uint8_t LEAD = '@';
+  __device__ static uint32_t rec_len(uint32_t hlen, uint32_t len) { return hlen + 2u * len + 5u; }
+};
+struct FastaForm {  // >hdr\nSEQ\n
+  static constexpr bool FASTA = true;
+  static constexpr uint8_t LEAD = '>';
+  __device__ static uint32_t rec_len(uint32_t hlen, uint32_t len) { return hlen + len + 2u; }
+};
 
 struct FieldLds {
   unsigned long long off[CL_THREADS];  // content offset of the workgroup's k-th new value
@@ -185,6 +202,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_scan(const FqChunkFmt *__r
   if (threadIdx.x == 0) p[nt] = cc;
 }
 
+template <class FORM>
 __global__ __launch_bounds__(CL_THREADS) void k_chunk_measure(const FqChunkFmt *__restrict__ fmt, const uint8_t *__restrict__ stage,
                                                               const uint32_t *__restrict__ agg, const unsigned long long *__restrict__ clp,
                                                               uint32_t *__restrict__ hlen_out, uint32_t *__restrict__ tlen,
@@ -203,11 +221,15 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_measure(const FqChunkFmt *
   }
   if (in && bad) atomicMin(&res->bad, (unsigned long long)r);
   const uint16_t *readlens = reinterpret_cast<const uint16_t *>(stage + fmt->readlens);
-  const uint32_t rlen = in ? hlen + 2u * readlens[r] + 5u : 0u;
+  const uint32_t rlen = in ? FastqForm::rec_len(hlen, readlens[r]) : 0u;
   if (in) hlen_out[r] = hlen;
   unsigned long long tot;
   (void)cl_block_excl(rlen, &tot);
   if (threadIdx.x == 0) tlen[t] = (uint32_t)tot;
+  if constexpr (FORM::FASTA) {  // the sums to place by, behind the sums to judge by
+    (void)cl_block_excl(in ? FORM::rec_len(hlen, readlens[r]) : 0u, &tot);
+    if (threadIdx.x == 0) tlen[fmt->n_tiles + t] = (uint32_t)tot;
+  }
 }
 
 // WINDOW (fqgpu_decode_chunk_range): only the records [win.w0, win.w1) are written -- record table entries at their
@@ -218,7 +240,7 @@ struct ChunkWindow {
   const unsigned long long *base;  // device: the offset of record w0 in the whole chunk (k_chunk_pick)
 };
 
-template <bool WINDOW>
+template <bool WINDOW, class FORM>
 __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__restrict__ fmt, const uint8_t *__restrict__ stage,
                                                             const uint32_t *__restrict__ agg, const unsigned long long *__restrict__ clp,
                                                             const uint32_t *__restrict__ hlen_in, const unsigned long long *__restrict__ toff,
@@ -241,9 +263,11 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   const unsigned long long base = WINDOW ? *win.base : 0ull;
   const uint16_t *readlens = reinterpret_cast<const uint16_t *>(stage + fmt->readlens);
   const uint32_t hlen = in ? hlen_in[r] : 0u, rl = in ? readlens[r] : 0u;
-  const uint32_t rlen = in ? hlen + 2u * rl + 5u : 0u;
+  const uint32_t rlen = in ? FastqForm::rec_len(hlen, rl) : 0u;
   unsigned long long tmp;
   const unsigned long long roff = toff[t] + cl_block_excl(rlen, &tmp);
+  unsigned long long poff = roff;  // where the record lies in the form that is placed
+  if constexpr (FORM::FASTA) poff = toff[nt + 1 + t] + cl_block_excl(in ? FORM::rec_len(hlen, rl) : 0u, &tmp);
   // records only move forward: the first one that ends behind raw_len is the host's failing record
   if (in && roff + rlen > raw_len) atomicMin(&res->bad, (unsigned long long)r);
   if (t == 0 && threadIdx.x == 0) res->total = total;
@@ -251,15 +275,18 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   if (threadIdx.x == 0) s_ok = total <= raw_len && __hip_atomic_load(&res->bad, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == ~0ull;
   __syncthreads();
   if (!s_ok) return;
-  const unsigned long long wroff = WINDOW ? (win_rec ? roff - base : 0ull) : roff;  // where the record goes
+  const unsigned long long wroff = WINDOW ? (win_rec ? poff - base : 0ull) : poff;  // where the record goes
   if (win_rec) {
-    const uint32_t seq_off = (uint32_t)(wroff + hlen + 1), qual_off = seq_off + rl + 3u;
+    const uint32_t seq_off = (uint32_t)(wroff + hlen + 1), qual_off = FORM::FASTA ? 0u : seq_off + rl + 3u;
     fqgpu_rec rec;
     rec.seq_off = seq_off; rec.qual_off = qual_off; rec.len = rl;
     recs[r] = rec;
     raw[seq_off - 1] = '\n';
-    raw[seq_off + rl] = '\n'; raw[seq_off + rl + 1] = '+'; raw[seq_off + rl + 2] = '\n';
-    raw[qual_off + rl] = '\n';
+    raw[seq_off + rl] = '\n';
+    if constexpr (!FORM::FASTA) {
+      raw[seq_off + rl + 1] = '+'; raw[seq_off + rl + 2] = '\n';
+      raw[qual_off + rl] = '\n';
+    }
   }
   unsigned long long htot;
   const unsigned long long hex = cl_block_excl(win_rec ? hlen : 0u, &htot);
@@ -268,7 +295,7 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
   s_roff[threadIdx.x] = wroff;
   if (threadIdx.x == 0) s_hoff[CL_THREADS] = (uint32_t)htot;
   uint8_t *dst = staged ? hbuf + hex : raw + wroff;
-  if (win_rec) dst[0] = '@';
+  if (win_rec) dst[0] = FORM::LEAD;
   uint32_t p = 1;
   const unsigned long long stage_len = fmt->stage_len;
   for (unsigned f = 0; f < nf; f++) {
@@ -304,21 +331,23 @@ __global__ __launch_bounds__(CL_THREADS) void k_chunk_write(const FqChunkFmt *__
 struct ChunkPicks {
   unsigned r[4];
 };
+template <class FORM>
 __global__ __launch_bounds__(CL_THREADS) void k_chunk_pick(const FqChunkFmt *__restrict__ fmt, const uint8_t *__restrict__ stage,
                                                            const uint32_t *__restrict__ hlen_in, const unsigned long long *__restrict__ toff,
                                                            ChunkPicks q, unsigned long long *__restrict__ at) {
   const unsigned rq = q.r[blockIdx.x], nt = fmt->n_tiles, t = rq / CL_THREADS;
+  const unsigned long long *poff = FORM::FASTA ? toff + nt + 1 : toff;  // the offsets of the form that is placed
   if (t >= nt) {  // rq = n_recs, a multiple of 256
-    if (threadIdx.x == 0) at[blockIdx.x] = toff[nt];
+    if (threadIdx.x == 0) at[blockIdx.x] = poff[nt];
     return;
   }
   const unsigned r = t * CL_THREADS + threadIdx.x;
   const bool in = r < fmt->n_recs;
   const uint16_t *readlens = reinterpret_cast<const uint16_t *>(stage + fmt->readlens);
-  const uint32_t rlen = in ? hlen_in[r] + 2u * readlens[r] + 5u : 0u;
+  const uint32_t rlen = in ? FORM::rec_len(hlen_in[r], readlens[r]) : 0u;
   unsigned long long tmp;
   const unsigned long long ex = cl_block_excl(rlen, &tmp);
-  if (r == rq) at[blockIdx.x] = toff[t] + ex;
+  if (r == rq) at[blockIdx.x] = poff[t] + ex;
 }
 
 }  // namespace
@@ -390,14 +419,14 @@ int fq_chunk_prepare(const fqgpu_header_streams *hdr, const uint16_t *readlens, 
 }
 
 // Uploads the stage and runs the passes every record's offset depends on: per-workgroup counts and sums, their scans,
-// the measure pass, the scan of the record offsets.
-static int chunk_prefix(hipStream_t st, ChunkScratch &cs) {
+// the measure pass, the scan of the record offsets (fasta: of both forms' offsets).
+static int chunk_prefix(hipStream_t st, ChunkScratch &cs, bool fasta) {
   const unsigned nt = cs.n_tiles, nf = cs.n_fields;
   int rc;
   if ((rc = cs.stage.reserve(cs.stage_len)) || (rc = cs.agg.reserve((size_t)nf * nt * 4)) ||
       (rc = cs.cls.reserve((size_t)nf * nt * 4)) || (rc = cs.clp.reserve((size_t)nf * (nt + 1) * 8)) ||
-      (rc = cs.hlen.reserve((size_t)nt * CL_THREADS * 4)) || (rc = cs.tlen.reserve((size_t)nt * 4)) ||
-      (rc = cs.toff.reserve((size_t)(nt + 1) * 8)) || (rc = cs.res.reserve(sizeof(FqChunkResult))))
+      (rc = cs.hlen.reserve((size_t)nt * CL_THREADS * 4)) || (rc = cs.tlen.reserve((size_t)nt * 2 * 4)) ||
+      (rc = cs.toff.reserve((size_t)(nt + 1) * 2 * 8)) || (rc = cs.res.reserve(sizeof(FqChunkResult))))
     return rc;
   const FqChunkFmt *fmt = cs.stage.as<FqChunkFmt>();
   const uint8_t *stage = cs.stage.as<uint8_t>();
@@ -411,10 +440,13 @@ static int chunk_prefix(hipStream_t st, ChunkScratch &cs) {
     hipLaunchKernelGGL(k_chunk_scan, dim3(nf), dim3(CL_THREADS), 0, st, fmt, cs.agg.as<uint32_t>(), cs.cls.as<uint32_t>(),
                        cs.clp.as<unsigned long long>());
     FQ_HIP(hipGetLastError());
-    hipLaunchKernelGGL(k_chunk_measure, dim3(nt), dim3(CL_THREADS), 0, st, fmt, stage, cs.agg.as<uint32_t>(),
+    const auto measure = fasta ? k_chunk_measure<FastaForm> : k_chunk_measure<FastqForm>;
+    hipLaunchKernelGGL(measure, dim3(nt), dim3(CL_THREADS), 0, st, fmt, stage, cs.agg.as<uint32_t>(),
                        cs.clp.as<unsigned long long>(), cs.hlen.as<uint32_t>(), cs.tlen.as<uint32_t>(), res);
     FQ_HIP(hipGetLastError());
     if ((rc = fq_scan_u32_to_u64(st, cs.tlen.as<uint32_t>(), nt, cs.toff.as<unsigned long long>(), cs.scan_tmp))) return rc;
+    if (fasta && (rc = fq_scan_u32_to_u64(st, cs.tlen.as<uint32_t>() + nt, nt, cs.toff.as<unsigned long long>() + nt + 1, cs.scan_tmp)))
+      return rc;
   }
   return FQGPU_OK;
 }
@@ -425,11 +457,14 @@ static int chunk_prefix(hipStream_t st, ChunkScratch &cs) {
 // q != NULL (fqgpu_decode_chunk_range): the records [q[0], q[3]) alone; at[i] = the offset of record q[i] in the whole
 // chunk (q[i] = n_recs: its end); with `write`, the window's records go to recs_dev[r] and to raw_dev at offsets
 // relative to at[0] (only the window's bytes are written).  Without, nothing is written and the layout is still judged.
+// fasta (with q): the records are placed as FASTA -- at[] and the record table speak of that layout -- while *bad and
+// *total are still those of the FASTQ layout.
 int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
-                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4]) {
+                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4], bool fasta) {
   const unsigned nt = cs.n_tiles;
   int rc;
-  if ((rc = chunk_prefix(st, cs)) || (q && (rc = cs.pick.reserve(4 * sizeof(unsigned long long))))) return rc;
+  if (fasta && !q) return FQGPU_E_ARG;
+  if ((rc = chunk_prefix(st, cs, fasta)) || (q && (rc = cs.pick.reserve(4 * sizeof(unsigned long long))))) return rc;
   FqChunkResult *res = cs.res.as<FqChunkResult>();
   unsigned long long *pick = cs.pick.as<unsigned long long>();
   const auto write_pass = [&](auto kernel, ChunkWindow win) {
@@ -439,12 +474,14 @@ int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_re
     return hipGetLastError();
   };
   if (nt && q) {
-    hipLaunchKernelGGL(k_chunk_pick, dim3(4), dim3(CL_THREADS), 0, st, cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(),
-                       cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(), ChunkPicks{{q[0], q[1], q[2], q[3]}}, pick);
+    hipLaunchKernelGGL(fasta ? k_chunk_pick<FastaForm> : k_chunk_pick<FastqForm>, dim3(4), dim3(CL_THREADS), 0, st,
+                       cs.stage.as<FqChunkFmt>(), cs.stage.as<uint8_t>(), cs.hlen.as<uint32_t>(), cs.toff.as<unsigned long long>(),
+                       ChunkPicks{{q[0], q[1], q[2], q[3]}}, pick);
     FQ_HIP(hipGetLastError());
-    FQ_HIP(write_pass(k_chunk_write<true>, ChunkWindow{write ? q[0] : 0u, write ? q[3] : 0u, pick}));
+    const ChunkWindow win{write ? q[0] : 0u, write ? q[3] : 0u, pick};
+    FQ_HIP(fasta ? write_pass(k_chunk_write<true, FastaForm>, win) : write_pass(k_chunk_write<true, FastqForm>, win));
   } else if (nt) {
-    FQ_HIP(write_pass(k_chunk_write<false>, ChunkWindow{}));
+    FQ_HIP(write_pass(k_chunk_write<false, FastqForm>, ChunkWindow{}));
   } else if (q) {
     FQ_HIP(hipMemsetAsync(pick, 0, 4 * sizeof(unsigned long long), st));
   }

@@ -387,8 +387,11 @@ struct FqStridePlan {
 // build_index (no plan): every block is walked from its streams' ends by the indexing walk, whatever index it holds, and
 // is left with both decode indexes, stride ctx->index_stride (index_bytes set; a caller that finds the block's streams
 // corrupt drops them)
+// streams: which of a block's streams are decoded -- both, or the sequence stream alone (no plan entry, index or byte of
+// the quality stream is then looked at)
+constexpr unsigned FQ_DEC_SEQ = 1u, FQ_DEC_QUAL = 2u, FQ_DEC_BOTH = FQ_DEC_SEQ | FQ_DEC_QUAL;
 int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_blocks, const FqStridePlan *plan = nullptr,
-                     bool build_index = false);
+                     bool build_index = false, unsigned streams = FQ_DEC_BOTH);
 int fq_wipe_launch(fqgpu_ctx *ctx, fqgpu_dblock *b);
 int fq_qual_counts_sorted(hipStream_t st, const uint8_t *raw_dev, const fqgpu_rec *recs_dev, size_t n_recs, size_t n_bases,
                           uint32_t *counts_dev, uint32_t *err_dev);
@@ -399,7 +402,7 @@ int fq_headers_launch(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, co
                       size_t first_header_len, HdrScratch &hs);
 int fq_chunk_prepare(const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, size_t raw_len, ChunkScratch &cs);
 int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_rec *recs_dev, const unsigned q[4], bool write,
-                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4]);
+                    unsigned long long *bad, unsigned long long *total, unsigned long long at[4], bool fasta = false);
 int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, ParseScratch &ps, fqgpu_rec *recs_dev,
                      size_t n_recs, size_t *n_bases, size_t *n_n, size_t *used_len);
 

@@ -80,6 +80,7 @@ struct FarmReport {
   const char *sums = "none";
   std::size_t verified_blocks = 0;
   uint32_t file_crc32 = 0;
+  uint64_t archive_bytes_read = 0;  // processArchiveFasta: what was read of the archive file (the quality streams are not)
 };
 
 namespace detail {
@@ -590,6 +591,73 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
   for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
   rep.indexed_blocks = used_blocks.load();
   rep.index_bytes = used_bytes.load();
+  return rep;
+}
+
+/** Extension: `d --fasta [--records A:B]` -- the sequences alone, as FASTA (">hdr\nSEQ\n" per record, the header line
+ *  as in the FASTQ but for its first byte).  Serves the whole archive (a = 0, b = SIZE_MAX) and a record range alike, as
+ *  planRecordRange pieces that all go through decodeChunkFasta.  The quality streams are neither read from the archive
+ *  (readBlockAt without them) nor uploaded nor decoded; of a usable `<archive>.fqx` only the sequence indexes are passed
+ *  down.  Never builds an index and never verifies against `.fqs` (the sums describe FASTQ bytes): rep.sums "none".
+ *  FASTA sizes are not recorded in the archive, so the pieces go through OrderedPieceWriter: handed out in order, placed
+ *  by the sizes published so far. */
+inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &fasta_out, std::size_t a, std::size_t b,
+                                      const Settings &set) {
+  Archive archive(archive_path);
+  const std::vector<uint32_t> counts = archive.recordCounts();
+  if (b == SIZE_MAX) {
+    b = 0;
+    for (const uint32_t n : counts) b += n;
+  }
+  const std::vector<RangePiece> pieces = planRecordRange(counts, a, b);
+  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(pieces.size())));
+  if (set.devices.empty()) throw std::invalid_argument("processArchiveFasta: no device");
+  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
+  detail::runWorkers(T, [&](unsigned t) { wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]); });
+  const uint64_t read_before = archive.bytesRead();
+  const auto t0 = std::chrono::steady_clock::now();
+  OrderedPieceWriter writer(fasta_out, pieces.size());
+  std::vector<InputStats> istats(T);
+  FarmReport rep;
+  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
+  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
+  std::atomic<bool> stopped{false};
+  detail::runWorkers(T, [&](unsigned t) {
+    CompressedBuffersSrc cbs;
+    FastqChunk piece;
+    for (;;) {
+      const std::size_t p = next.fetch_add(1);  // (in order: whoever waits in the writer waits for pieces already taken)
+      if (stopped.load() || p >= pieces.size()) break;
+      const RangePiece &pc = pieces[p];
+      StageClock clk;
+      archive.readBlockAt(pc.block, cbs, false);
+      if (sidecar && sidecar->get(cbs)) {
+        cbs.decode_index[1].clear();  // (the entry is checked as a whole; the quality index has no use here)
+        used_blocks.fetch_add(1);
+        used_bytes.fetch_add(cbs.decode_index[0].size());
+      }
+      clk.lap("read");
+      wksp[t]->decodeChunkFasta(piece, cbs, pc.first, pc.end);
+      clk.lap("decode");
+      istats[t].raw += piece.raw_data.size();
+      istats[t].n_records += pc.end - pc.first;
+      rep.blocks_per_worker[t]++;
+      try {
+        writer.writePiece(p, piece.raw_data.data(), piece.raw_data.size());
+      } catch (const OrderedPieceWriter::Aborted &) {
+        break;  // (another worker has failed and says why)
+      }
+      clk.lap("write");
+      clk.done(static_cast<unsigned>(pc.block));
+    }
+  }, [&] { stopped.store(true); writer.abort(); });
+  writer.flush();
+  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
+  rep.indexed_blocks = used_blocks.load();
+  rep.index_bytes = used_bytes.load();
+  rep.archive_bytes_read = archive.bytesRead() - read_before;
   return rep;
 }
 

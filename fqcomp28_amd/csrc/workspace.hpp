@@ -595,6 +595,21 @@ public:
     return piece.raw_data.size();
   }
 
+  /** Extension: records [first, end) of the chunk as FASTA into piece.raw_data (fqgpu_decode_chunk_fasta: ">hdr\nSEQ\n"
+   *  per record, from the sequence stream alone; cbs.qual is not looked at and may be empty).  piece.idx = cbs.chunk_idx,
+   *  piece.records stays empty: a FASTA piece is bytes to be written.  There is no host fallback -- the host path would
+   *  need the qualities -- and FQGPU_SHIM_HOST_HEADERS does not apply: a chunk the device refuses throws
+   *  std::runtime_error naming the chunk and the record. */
+  void decodeChunkFasta(FastqChunk &piece, CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
+    if (first >= end || end > cbs.original_size.n_records) throw std::invalid_argument("decodeChunkFasta: bad record range");
+    (void)fastaOnDevice(cbs, first, end, &piece);
+  }
+  /** The size of records [first, end) of the chunk as decodeChunkFasta restores them (the layout passes only) */
+  std::size_t fastaSize(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end) {
+    if (first >= end || end > cbs.original_size.n_records) throw std::invalid_argument("fastaSize: bad record range");
+    return fastaOnDevice(cbs, first, end, nullptr);
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */
@@ -773,6 +788,42 @@ private:
     CompressionWorkspace::recordViews(*piece, recs);
     clk.done(cbs.chunk_idx);
     return true;
+  }
+
+  /** fqgpu_decode_chunk_fasta: the size query, then, with a piece, the decode into it; returns the size.  Every refusal
+   *  throws. */
+  std::size_t fastaOnDevice(CompressedBuffersSrc &cbs, std::size_t first, std::size_t end, FastqChunk *piece) {
+    StageClock clk;
+    ChunkArgs a;
+    const auto refused = [&](const std::string &what) {
+      return std::runtime_error("decodeChunkFasta: chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
+    };
+    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
+    clk.lap("misc");
+    std::size_t len = 0;
+    const auto call = [&](uint8_t *out, std::size_t cap) {
+      std::size_t bad = 0;
+      const StreamArgs &s = a.s;
+      const int rc = fqgpu_decode_chunk_fasta(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.n_count, s.n_count_len, s.n_pos,
+                                              s.n_pos_len, s.index[0], s.index_len[0], cbs.original_size.total, first, end, out, cap,
+                                              &len, nullptr, &bad);
+      if (rc == FQGPU_OK) return;
+      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
+                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
+    };
+    // a whole chunk is smaller as FASTA than its recorded FASTQ size: one call; a range asks for its size first
+    const bool whole = piece && first == 0 && end == a.n_recs;
+    if (!whole) call(nullptr, 0);
+    clk.lap("gpu size");
+    if (!piece) return len;
+    piece->clear();
+    piece->idx = cbs.chunk_idx;
+    piece->raw_data.resize(whole ? cbs.original_size.total : len);
+    call(reinterpret_cast<uint8_t *>(piece->raw_data.data()), piece->raw_data.size());
+    piece->raw_data.resize(len);
+    clk.lap("gpu");
+    clk.done(cbs.chunk_idx);
+    return len;
   }
 
   /** decodeHeader with the output bound checked: near the end of the chunk the header goes through

@@ -376,6 +376,32 @@ int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, co
                              size_t raw_len, size_t first, size_t end, uint8_t *out, size_t out_cap, size_t *out_len,
                              fqgpu_rec *recs_out, size_t *bad_record);
 
+/* Extension: records [first, end) of a chunk as FASTA -- per record ">hdr\nSEQ\n": the FASTQ header line byte for byte
+ * except for its first byte, the sequence on one line, N restored as N -- from the sequence stream alone.  The call takes
+ * no quality argument: the quality stream is not uploaded, not decoded and not looked at, so DAMAGE TO THE QUALITY STREAM
+ * IS NEVER SEEN here (a FASTQ decode of the chunk still finds it).  first = 0, end = n_recs is the whole chunk.
+ * Shaped like fqgpu_decode_chunk_range:
+ *   raw_len    the chunk's recorded FASTQ size.  The chunk is judged on its FASTQ layout exactly as fqgpu_decode_chunk
+ *              judges it: same rc, same *bad_record for the same header streams and readlens.
+ *   out == NULL: only *out_len (the FASTA size of the range) is reported, after the layout passes; no stream goes up.
+ *   recs_out (may be NULL): end - first records, seq_off relative to out (into the FASTA bytes), len, qual_off = 0.
+ *   seq_index  the chunk's sequence decode index (NULL / 0: none).  With it only the strides that hold symbols of the
+ *              range are decoded; without it the sequence stream is walked whole.
+ * Returns
+ *   FQGPU_E_ARG       first >= end, end > n_recs, or any argument fqgpu_decode_chunk_range refuses
+ *   FQGPU_E_OVERFLOW  out_cap below the range's size: nothing is written to out, *out_len holds the size needed
+ *   FQGPU_E_CORRUPT   with *bad_record: the layout, as fqgpu_decode_chunk; with *bad_record = (size_t)-1: a damaged sequence
+ *                     stride that was decoded, or (behind the layout's verdict) a damaged index
+ *   FQGPU_E_NO_DEVICE without a GPU, whatever the arguments.
+ * A FASTA piece is never digested (the digests describe FASTQ bytes): fqgpu_chunk_crc32 afterwards returns FQGPU_E_ARG with
+ * *crc = 0, *len = 0.  Uses the handle's staging block like the other host-pointer calls: one call per handle at a time. */
+int fqgpu_decode_chunk_fasta(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs,
+                             const uint8_t *seq, size_t seq_len,
+                             const uint16_t *n_count, size_t n_count_len, const uint16_t *n_pos, size_t n_pos_len,
+                             const uint8_t *seq_index, size_t seq_index_len,
+                             size_t raw_len, size_t first, size_t end,
+                             uint8_t *out, size_t out_cap, size_t *out_len, fqgpu_rec *recs_out, size_t *bad_record);
+
 /* ---- Extension (nothing in the reference, whose format has no content checksum): CRC-32 of a chunk, taken where the
  * chunk lies already -- in HBM.  The digest is the CRC-32 of zlib / gzip (reflected polynomial 0xEDB88320, initial value
  * and final xor 0xFFFFFFFF: Python's zlib.crc32) of the chunk's CANONICAL bytes, which are exactly what fqgpu_decode_chunk
@@ -391,7 +417,7 @@ int fqgpu_decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, co
  *                        fqgpu_decode_chunk_indexing (*len = *laid_out_len), fqgpu_decode_block or fqgpu_decode_block_indexed
  *                        (*len = raw_len: the block as the caller laid it out, digested as it lies).  Everywhere else --
  *                        after a failed decode (a call refused for its arguments included: every host-pointer decode
- *                        ends the digest of the chunk before it), after fqgpu_decode_chunk_range, with no chunk on the handle --
+ *                        ends the digest of the chunk before it), after fqgpu_decode_chunk_range or _fasta, with no chunk on the handle --
  *                        FQGPU_E_ARG with *crc = 0, *len = 0.
  *   fqgpu_dblock_crc32   waits for the block's last operation as fqgpu_dblock_status does, then digests the canonical bytes
  *                        of its raw block by its record table -- of WHATEVER the raw block holds when asked: after

@@ -10,6 +10,12 @@
 //              (extension: with <in.fqc>.fqs beside the archive every restored chunk is verified before it is written: a chunk
 //               whose digest differs ends the command, exit 1, no output.  A .fqs that is damaged, unclosed or another archive's
 //               is reported and not used; --records never verifies)
+//   fqc_tool d <in.fqc> <out.fasta> --fasta [-t threads] [-d dev,dev,...] [--records A:B]
+//              (extension: the sequences alone, as FASTA -- per record ">" + the header line without its '@', the bases on one
+//               line, N as N.  The quality streams are not read from the archive, not uploaded and not decoded, so damage to
+//               them goes unseen.  Uses <in.fqc>.fqx when it lies there (its sequence indexes); never builds one, never
+//               verifies: --fasta with --index or --index-stride, or with c, x or t, is a usage error.  A failed run leaves
+//               neither <out.fasta> nor <out.fasta>.part)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -22,7 +28,8 @@
 // (fqcomp28 c --i1 in.fastq -o out.fqc -t N / fqcomp28 d -i out.fqc --o1 out.fastq, src/app.cpp:29-76.)
 // Prints one JSON line with sizes, seconds and blocks per worker; d and x also say how many blocks were decoded from a decode
 // index ("index": "used") or were given one ("built"), and its bytes; "sums" / "verified" / "crc32": what became of the chunk
-// sums file, the blocks whose digest was compared and held, the whole file's CRC-32.  Needs a GPU: no CPU fallback.
+// sums file, the blocks whose digest was compared and held, the whole file's CRC-32; with --fasta also "form": "fasta" and the
+// bytes read of the archive.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -37,12 +44,13 @@ int main(int argc, char **argv) {
   const bool one_arg = index_cmd || check_cmd;  // x and t take the archive alone
   if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg)) {
     std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B]\n"
+                         "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n");
     return 2;
   }
   Settings set;
-  bool range = false;
+  bool range = false, fasta = false;
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
   for (int i = one_arg ? 3 : 4; i < argc; ++i) {
     const std::string a = argv[i];
@@ -51,6 +59,7 @@ int main(int argc, char **argv) {
     else if (a == "-R") set.reading_chunk_size = (std::size_t)std::atoll(val()) << 20;
     else if (a == "-S") set.sample_chunk_size = (std::size_t)std::atoll(val()) << 20;
     else if (a == "--accumulate-n") set.accumulate_n_buffers = true;
+    else if (a == "--fasta") fasta = true;
     else if (a == "--index" && !check_cmd) set.decode_index = true;  // (t builds nothing)
     else if (a == "--checksum" && argv[1][0] == 'c') set.checksum = true;
     else if (a == "--index-stride" && !check_cmd) { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
@@ -78,6 +87,10 @@ int main(int argc, char **argv) {
       for (const char *p = val(); *p;) { set.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p) ++p; }
     } else { std::fprintf(stderr, "unknown option %s\nusage: fqc_tool c|d <in> <out> [options] | fqc_tool x|t <in.fqc> [options]\n", a.c_str()); return 2; }
   }
+  if (fasta && (argv[1][0] != 'd' || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "--fasta goes with d alone, and builds no index: not with c, x, t, --index or --index-stride\n");
+    return 2;
+  }
   try {
     const bool comp = argv[1][0] == 'c';
     if (!comp) {  // --index on the way back: build, not write
@@ -87,6 +100,7 @@ int main(int argc, char **argv) {
     const FarmReport r = check_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
+                         : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
@@ -103,6 +117,7 @@ int main(int argc, char **argv) {
       std::printf(", \"sums\": \"%s\", \"verified\": %zu", r.sums, r.verified_blocks);
       if (r.verified_blocks) std::printf(", \"crc32\": \"%08x\"", r.file_crc32);
     }
+    if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
     std::printf("}\n");
   } catch (const std::exception &e) {
     std::fprintf(stderr, "fqc_tool: %s\n", e.what());
