@@ -141,6 +141,10 @@ _PROTOS = {
     "fqgpu_dblock_crc32": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]),
     "fqgpu_crc32_combine": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint64]),
     "fqgpu_ctx_set_check_only": (C.c_int, [C.c_void_p, C.c_int]),
+    "fqgpu_stats_words": (C.c_size_t, [C.c_uint]),
+    "fqgpu_chunk_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t]),
+    "fqgpu_dblock_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t]),
+    "fqgpu_stats_merge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -251,6 +255,41 @@ def crc32_combine(crc_a, crc_b, len_b):
     return lib().fqgpu_crc32_combine(crc_a, crc_b, len_b)
 
 
+def stats_words(positions):
+    """fqgpu_stats_words: uint64 words of a read summary with `positions` rows (0: positions out of range)"""
+    return lib().fqgpu_stats_words(positions)
+
+
+def stats_merge(dst, src):
+    """fqgpu_stats_merge: dst += src in place (two uint64 arrays) -> rc"""
+    assert dst.dtype == np.uint64 and src.dtype == np.uint64 and dst.flags.c_contiguous and src.flags.c_contiguous
+    return lib().fqgpu_stats_merge(_p(dst), dst.size, _p(src), src.size)
+
+
+STATS_HEAD_WORDS, STATS_MEANQ_AT, STATS_GC_AT = 176, 8, 72
+
+
+def stats_view(words):
+    """The parts of a read summary (include/fqgpu.h) as numpy views of `words`, a uint64 array of stats_words(P)."""
+    assert words.dtype == np.uint64 and words.ndim == 1
+    rows = int(words[5]) + 1
+    assert words.size == STATS_HEAD_WORDS + 70 * rows, "not a summary of the positions it names"
+    at = STATS_HEAD_WORDS
+    view = dict(n_records=words[0:1], n_bases=words[1:2], min_len=words[2:3], max_len=words[3:4], reads_with_n=words[4:5],
+                positions=words[5:6], meanq_hist=words[STATS_MEANQ_AT:STATS_MEANQ_AT + 64],
+                gc_hist=words[STATS_GC_AT:STATS_GC_AT + 101], len_hist=words[at:at + rows])
+    view["base_pos"] = words[at + rows:at + 6 * rows].reshape(rows, 5)
+    view["qual_pos"] = words[at + 6 * rows:at + 70 * rows].reshape(rows, 64)
+    return view
+
+
+def _stats_call(fn, positions, *front):
+    """-> (rc, words): a device summary call on a fresh uint64 array of the size `positions` asks for"""
+    out = np.zeros(max(stats_words(positions), 1), dtype=np.uint64)
+    rc = fn(*front, positions, _p(out), out.size)
+    return rc, out
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -350,6 +389,12 @@ class DBlock:
         _check(lib().fqgpu_dblock_crc32(self.ctx.h, self.h, C.byref(crc), C.byref(n)), "dblock_crc32")
         return (crc.value, n.value) if want_len else crc.value
 
+    def stats(self, positions):
+        """fqgpu_dblock_stats: the read summary of the raw block as it lies on the device -> uint64 array (stats_view)"""
+        rc, out = _stats_call(lib().fqgpu_dblock_stats, positions, self.ctx.h, self.h)
+        _check(rc, "dblock_stats")
+        return out
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -447,6 +492,10 @@ class Context:
         rc = lib().fqgpu_chunk_crc32(self.h, C.byref(crc), C.byref(n))
         return rc, crc.value, n.value
 
+    def chunk_stats(self, positions):
+        """fqgpu_chunk_stats -> (rc, words): the read summary of the chunk on the staging block, where chunk_crc32 is valid"""
+        return _stats_call(lib().fqgpu_chunk_stats, positions, self.h)
+
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""
         _check(lib().fqgpu_ctx_set_check_only(self.h, 1 if on else 0), "set_check_only")
@@ -511,14 +560,14 @@ class Context:
         return dict(rc=rc, seq=bufs["seq"][:sl].copy(), qual=bufs["qual"][:ql].copy(), readlens=bufs["readlens"],
                     n_count=bufs["n_count"], n_pos=bufs["n_pos"][:nn].copy(), raw_after=raw)
 
-    def encode_raw(self, raw, flags=0, recs=None, header_format=None, want_crc=False):
+    def encode_raw(self, raw, flags=0, recs=None, header_format=None, want_crc=False, want_stats=None):
         """The two-halves call on an UNPARSED chunk (fqgpu_encode_begin / _records / _wait / _end): the
         record table comes back from the GPU.  -> dict like encode_block's, plus recs and used_len.
         header_format = (types, separators, first_header) -- types[i] 0 = NUMERIC / 1 = STRING, separators as bytes,
         first_header with its '@' -- also codes the header fields on the device (fqgpu_encode_headers_*):
         `header_fields` = [(flags, content, lengths) per field] or, for a header that cannot be coded,
         `headers_rc` = FQGPU_E_HEADER and `bad_record`.  want_crc: fqgpu_chunk_crc32 between begin and end ->
-        `crc32`, `crc_len`."""
+        `crc32`, `crc_len`; want_stats=P: fqgpu_chunk_stats there too -> `stats`."""
         raw = np.array(raw, dtype=np.uint8, copy=True)
         n, nb, used = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
         if recs is not None:
@@ -535,6 +584,11 @@ class Context:
                 lib().fqgpu_encode_cancel(self.h)
                 return dict(rc=rc)
             hdr["crc32"], hdr["crc_len"] = crc.value, crc_len.value
+        if want_stats is not None:
+            rc, hdr["stats"] = self.chunk_stats(want_stats)
+            if rc:
+                lib().fqgpu_encode_cancel(self.h)
+                return dict(rc=rc)
         if header_format is not None:
             types, seps, first = header_format
             types = np.ascontiguousarray(types, dtype=np.uint8)
@@ -586,7 +640,7 @@ class Context:
                     recs=table, used_len=used.value, n_bases=nb.value, **hdr)
 
     def decode_chunk(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, index=None,
-                     build_index=False, want_raw=True):
+                     build_index=False, want_raw=True, want_stats=None):
         """Both decode passes on the device (fqgpu_decode_chunk): headers decoded from their field streams, the chunk
         laid out, sequence and quality decoded.  header_format = (types, separators, first_header) and header_fields =
         [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
@@ -594,7 +648,8 @@ class Context:
         build_index=True (index must be None): fqgpu_decode_chunk_indexing, the decode builds the chunk's decode indexes
         on the way -> also "index": (seq, qual), two empty arrays after a failure; want_raw=False: raw is None and
         raw_out == NULL goes down -- index only with build_index, or a decode that only checks on a handle in checking
-        mode (set_check_only); without either the call is refused (FQGPU_E_ARG)."""
+        mode (set_check_only); without either the call is refused (FQGPU_E_ARG).  want_stats=P: fqgpu_chunk_stats
+        behind the decode -> also "stats_rc", "stats"."""
         args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
         raw = np.zeros(raw_len, dtype=np.uint8) if want_raw else None  # (None: index only, or a handle that only checks)
         recs = np.zeros(len(readlens), dtype=REC_DTYPE)
@@ -610,9 +665,16 @@ class Context:
                 if idx.size:
                     _check(lib().fqgpu_decode_index(self.h, s, _p(idx), idx.size, C.byref(n_idx)), "fqgpu_decode_index")
                 built.append(idx)
-            return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), index=tuple(built))
+            return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), index=tuple(built),
+                        **self._want_stats(want_stats))
         rc = lib().fqgpu_decode_chunk(self.h, *args, _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
-        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad))
+        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), **self._want_stats(want_stats))
+
+    def _want_stats(self, positions):
+        if positions is None:
+            return {}
+        rc, words = self.chunk_stats(positions)
+        return dict(stats_rc=rc, stats=words)
 
     def decode_chunk_range(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, first, end,
                            index=None, out_cap=None):

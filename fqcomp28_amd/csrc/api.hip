@@ -534,6 +534,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->hp_hdr.release();
   ctx->hp_chunk.release();
   ctx->crc.release();
+  ctx->stats.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1645,4 +1646,33 @@ extern "C" int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_
   *crc = c;
   *len = n;
   return FQGPU_OK;
+}
+
+// ------------------------------------------------------------------ read summary of a chunk in HBM (stats.hip)
+// Shared front of the two calls: no device is said before any argument is looked at; an `out` that is large enough is zeroed
+// before anything else can fail.
+static int stats_args(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words) {
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  const size_t words = fqgpu_stats_words(positions);
+  if (!ctx || !out || !words) return FQGPU_E_ARG;
+  if (cap_words < words) return FQGPU_E_OVERFLOW;
+  memset(out, 0, words * sizeof(uint64_t));
+  return FQGPU_OK;
+}
+
+// As fqgpu_chunk_crc32: on the handle's copy stream, beside the lane's encode or behind the decode.
+extern "C" int fqgpu_chunk_stats(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words) {
+  if (const int rc = stats_args(ctx, positions, out, cap_words)) return rc;
+  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
+  const fqgpu_dblock *b = ctx->hp_block;
+  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
+}
+
+extern "C" int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigned positions, uint64_t *out, size_t cap_words) {
+  int rc = stats_args(ctx, positions, out, cap_words);
+  if (rc) return rc;
+  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
+  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
+  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
 }

@@ -59,6 +59,28 @@ extern "C" uint32_t fqgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t
   return crc_mul(crc_a, r) ^ crc_b;
 }
 
+// Read summaries (stats.hip fills them): the size of one for `positions` rows, and dst += src.
+extern "C" size_t fqgpu_stats_words(unsigned positions) {
+  return positions && positions <= 65535u ? 176u + 70u * ((size_t)positions + 1u) : 0u;
+}
+extern "C" int fqgpu_stats_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words) {
+  if (!dst || !src || !src_words || dst_words != src_words || src[5] > 65535u || src_words != fqgpu_stats_words((unsigned)src[5]))
+    return FQGPU_E_ARG;
+  const bool empty = dst[0] == 0;  // (a block of zeros is an empty summary of any P)
+  if (dst[5] != src[5] && !(empty && dst[5] == 0)) return FQGPU_E_ARG;
+  if (empty) {
+    memcpy(dst, src, src_words * sizeof(uint64_t));
+    return FQGPU_OK;
+  }
+  if (!src[0]) return FQGPU_OK;
+  const uint64_t lo = dst[2] < src[2] ? dst[2] : src[2], hi = dst[3] > src[3] ? dst[3] : src[3];
+  for (size_t i = 0; i < dst_words; i++) dst[i] += src[i];
+  dst[2] = lo;
+  dst[3] = hi;
+  dst[5] = src[5];
+  return FQGPU_OK;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

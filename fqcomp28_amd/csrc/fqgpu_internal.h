@@ -225,6 +225,15 @@ struct CrcScratch {
   void release();
 };
 
+// Read summary of a chunk in HBM (stats.hip): the u64 result table, the workgroups' u32 slabs, the "a byte that cannot be
+// counted" flag and its page-locked landing place; all grown on demand
+struct StatsScratch {
+  DevBuf out, slabs, bad;
+  unsigned *host_bad = nullptr;
+  bool attr_set = false;  // the count kernel's LDS size has been asked for
+  void release();
+};
+
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
@@ -273,6 +282,7 @@ struct fqgpu_ctx {
   size_t hp_crc_len = 0;
   bool check_only = false;            // fqgpu_ctx_set_check_only: fqgpu_decode_chunk takes raw_out == NULL
   CrcScratch crc;
+  StatsScratch stats;
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -410,6 +420,10 @@ int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, Par
 int fq_crc_bytes(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *data_dev, size_t len, uint32_t *crc);
 int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                      uint32_t *crc, size_t *len);
+
+// Read summary of a chunk in HBM (stats.hip), on st, waited for: out[0, fqgpu_stats_words(positions)) on the host
+int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                   unsigned positions, uint64_t *out);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

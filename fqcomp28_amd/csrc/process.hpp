@@ -57,6 +57,9 @@ struct Settings {  // the part of src/settings.h:36-50 this path needs, plus the
   bool checksum = false;
   bool verify = false;      // decompressFarm: the workspaces take every restored chunk's digest (the sink compares it)
   bool check_only = false;  // ... and nothing is restored (processArchiveCheck sets both)
+  /** Extension: rows of the read summary every worker takes of its chunks where they lie on the device (Workspace::setStats;
+   *  1 .. 65535); the report carries the merged result.  0: none.  compressFarm and processArchiveCheck look at it. */
+  unsigned stats_positions = 0;
 };
 
 struct InputStats {  // src/report.h
@@ -81,9 +84,17 @@ struct FarmReport {
   std::size_t verified_blocks = 0;
   uint32_t file_crc32 = 0;
   uint64_t archive_bytes_read = 0;  // processArchiveFasta: what was read of the archive file (the quality streams are not)
+  std::vector<uint64_t> stats;      // the read summary of every chunk, merged (fqgpu_stats_words(set.stats_positions) words; empty: none taken)
 };
 
 namespace detail {
+/** the workers' summaries into the report */
+template <class Workspaces> void mergeStats(FarmReport &rep, const Workspaces &wksp, unsigned positions) {
+  if (!positions) return;
+  rep.stats.assign(fqgpu_stats_words(positions), 0);
+  rep.stats[5] = positions;
+  for (const auto &w : wksp) fqgpuCheck(fqgpu_stats_merge(rep.stats.data(), rep.stats.size(), w->stats().data(), w->stats().size()), "stats");
+}
 inline std::size_t miscBytes(const CompressedBuffersDst &cbs) {
   std::size_t n = cbs.compressed_readlens.size() + cbs.compressed_n_count.size() + cbs.compressed_n_pos.size();
   for (const auto &f : cbs.compressed_header_fields) n += f.isDifferentFlag.size() + f.content.size() + f.contentLength.size();
@@ -154,6 +165,7 @@ FarmReport compressFarm(const DatasetMeta &meta, Source &&next_chunk, Sink &&wri
     wksp[t]->reserve(set.reading_chunk_size);
     wksp[t]->setDecodeIndex(set.decode_index, set.index_stride);
     wksp[t]->setChecksum(set.checksum);
+    wksp[t]->setStats(set.stats_positions);
     chunks[t].raw_data.reserve(set.reading_chunk_size);
     buffers[t].seq.reserve(set.reading_chunk_size / 8 + (1u << 20));
     buffers[t].qual.reserve(set.reading_chunk_size / 3 + (1u << 20));
@@ -195,6 +207,7 @@ FarmReport compressFarm(const DatasetMeta &meta, Source &&next_chunk, Sink &&wri
   }, stop);
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (unsigned t = 0; t < T; ++t) { rep.in += istats[t]; rep.out += cstats[t]; }
+  detail::mergeStats(rep, wksp, set.stats_positions);
   return rep;
 }
 template <class Source, class Sink>
@@ -253,6 +266,7 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
     wksp[t]->setBuildIndex(set.build_index, set.index_stride, set.index_only);
     wksp[t]->setVerify(set.verify);
     if (set.check_only) wksp[t]->setCheckOnly(true);
+    wksp[t]->setStats(set.stats_positions);
   });
   std::vector<InputStats> istats(T);
   FarmReport rep;
@@ -282,6 +296,7 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
   }, stop);
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
+  detail::mergeStats(rep, wksp, set.stats_positions);
   return rep;
 }
 template <class Source, class Sink>
@@ -424,6 +439,7 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
   farm.index_only = false;
   farm.verify = verifier.on();
   farm.check_only = false;
+  farm.stats_positions = 0;
   if (farm.build_index) builder = std::make_unique<detail::DecodeIndexBuilder>(archive_path);
   std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
   FarmReport rep = decompressFarm(
@@ -451,7 +467,8 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
 }
 
 /** Extension: `t` -- every block decoded and judged, every chunk's digest compared with the archive's chunk sums file,
- *  nothing restored and no file written.  Uses the decode index file when it lies there (the indexed pace).  Without a
+ *  nothing restored and no file written.  With set.stats_positions (`s`) every chunk is also summarised where its decode
+ *  left it, and the report carries the archive's read summary; everything else is the same.  Uses the decode index file when it lies there (the indexed pace).  Without a
  *  chunk sums file the streams are still decoded (rep.sums "none", nothing compared); with one that cannot be used the
  *  command fails: checking is all it does. */
 inline FarmReport processArchiveCheck(const path_t &archive_path, const Settings &set) {
@@ -489,6 +506,7 @@ inline FarmReport processArchiveIndex(const path_t &archive_path, const Settings
   detail::DecodeIndexBuilder builder(archive_path);
   Settings farm = set;
   farm.build_index = farm.index_only = true;
+  farm.stats_positions = 0;
   FarmReport rep = decompressFarm(
       archive.meta(),
       [&](CompressedBuffersSrc &cbs) {
@@ -661,4 +679,57 @@ inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &
   return rep;
 }
 
+
+/** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function
+ *  of the summary -- written as `<path>.part` and renamed when it is complete. */
+inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w) {
+  if (w.size() < 176 || w.size() != fqgpu_stats_words(static_cast<unsigned>(w[5]))) throw std::logic_error("writeStatsReport: not a read summary");
+  const std::size_t rows = static_cast<std::size_t>(w[5]) + 1;
+  const uint64_t *len = w.data() + 176, *base = len + rows, *qual = base + 5 * rows;
+  std::string out = "#fqgpu-stats 1\n";
+  const auto num = [&](uint64_t v) { out += std::to_string(v); };
+  const char *names[6] = {"records", "bases", "min_len", "max_len", "reads_with_n", "positions"};
+  for (int i = 0; i < 6; ++i) { out += names[i]; out += '\t'; num(w[i]); out += '\n'; }
+  const auto hist = [&](const char *tag, const uint64_t *h, std::size_t n) {
+    for (std::size_t i = 0; i < n; ++i)
+      if (h[i]) { out += tag; out += '\t'; num(i); out += '\t'; num(h[i]); out += '\n'; }
+  };
+  hist("len", len, rows);
+  hist("mq", w.data() + 8, 64);
+  hist("gc", w.data() + 72, 101);
+  std::size_t used = 0;  // rows 0 .. used - 1 are written
+  for (std::size_t r = 0; r < rows; ++r) {
+    bool any = false;
+    for (int c = 0; c < 5; ++c) any = any || base[5 * r + c];
+    for (int c = 0; c < 64; ++c) any = any || qual[64 * r + c];
+    if (any) used = r + 1;
+  }
+  const auto table = [&](const char *tag, const uint64_t *t, std::size_t cols) {
+    for (std::size_t r = 0; r < used; ++r) {
+      out += tag; out += '\t'; num(r);
+      for (std::size_t c = 0; c < cols; ++c) { out += '\t'; num(t[cols * r + c]); }
+      out += '\n';
+    }
+  };
+  table("base", base, 5);
+  table("qual", qual, 64);
+  const path_t part = path.string() + ".part";
+  std::FILE *f = std::fopen(part.string().c_str(), "wb");
+  const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
+  if ((f && std::fclose(f) != 0) || !ok) {
+    std::error_code ec;
+    std::filesystem::remove(part, ec);
+    throw std::runtime_error("cannot write " + part.string());
+  }
+  std::filesystem::rename(part, path);
+}
+/** total Phred of a read summary / its bases (0 without bases) */
+inline double statsMeanQuality(const std::vector<uint64_t> &w) {
+  const std::size_t rows = static_cast<std::size_t>(w[5]) + 1;
+  const uint64_t *qual = w.data() + 176 + 6 * rows;
+  uint64_t sum = 0;
+  for (std::size_t r = 0; r < rows; ++r)
+    for (unsigned q = 0; q < 64; ++q) sum += qual[64 * r + q] * q;
+  return w[1] ? static_cast<double>(sum) / static_cast<double>(w[1]) : 0.0;
+}
 }  // namespace fqcomp28

@@ -294,7 +294,25 @@ public:
   static std::size_t compressBoundSequence(std::size_t n) { return fqgpu_bound_seq(n); }
   static std::size_t compressBoundQuality(std::size_t n) { return fqgpu_bound_qual(n); }
 
+  /** Extension: every chunk this workspace encodes / decodes is also summarised where it lies on the device
+   *  (fqgpu_chunk_stats, `positions` rows; taken where the digest is taken) and added to stats(), the summary of all its
+   *  chunks so far (fqgpu_stats_merge).  positions 0: off, not one call more. */
+  void setStats(unsigned positions) {
+    stats_positions_ = positions;
+    stats_.assign(fqgpu_stats_words(positions), 0);
+    stats_chunk_.assign(stats_.size(), 0);
+    if (positions && stats_.empty()) throw std::invalid_argument("setStats: positions must be 1 .. 65535");
+    if (positions) stats_[5] = positions;  // (the empty summary of P: a worker that gets no chunk still has one to merge)
+  }
+  [[nodiscard]] const std::vector<uint64_t> &stats() const { return stats_; }
+
 protected:
+  /** the summary of the chunk on the handle, into stats() */
+  void takeStats(const char *what) {
+    if (!stats_positions_) return;
+    fqgpuCheck(fqgpu_chunk_stats(ctx_, stats_positions_, stats_chunk_.data(), stats_chunk_.size()), what);
+    fqgpuCheck(fqgpu_stats_merge(stats_.data(), stats_.size(), stats_chunk_.data(), stats_chunk_.size()), what);
+  }
   explicit Workspace(const DatasetMeta *meta, int device)
       : meta_(meta), fmt_(meta->header_fmt), first_header_fields_(headers::fromHeader(meta->first_header, fmt_)) {
     fqgpuCheck(fqgpu_ctx_create(device, meta->ft_seq.get(), meta->ft_qual.get(), &ctx_), "Workspace");
@@ -313,6 +331,10 @@ protected:
   headers::header_fields_t prev_header_fields_;
   std::vector<uint8_t> field_types_;  // fmt_.field_types as the C ABI takes them (0 = NUMERIC, 1 = STRING)
   fqgpu_ctx *ctx_ = nullptr;
+
+private:
+  unsigned stats_positions_ = 0;
+  std::vector<uint64_t> stats_, stats_chunk_;
 };
 
 class CompressionWorkspace : public Workspace {
@@ -374,6 +396,7 @@ public:
       fqgpuCheck(fqgpu_chunk_crc32(ctx_, &cbs.digest.crc32, &cbs.digest.length), "encodeChunk");
       cbs.digest.valid = true;
     }
+    takeStats("encodeChunk");
     clk.lap("begin");
     if (!parsed) {
       recs.resize(R);
@@ -561,6 +584,7 @@ public:
                                           chunk.raw_data.size(), s.index[0], s.index_len[0], s.index[1], s.index_len[1]),
                "decodeChunk");
     takeDigest();
+    takeStats("decodeChunk");
     if (check_only_) { chunk.raw_data.clear(); chunk.records.clear(); }  // (the host layout needs the chunk; the caller gets none)
     clk.lap("gpu");
     clk.done(chunk.idx);
@@ -656,6 +680,7 @@ private:
     clk.lap("gpu");
     if (!deviceTook(rc, bad, "decodeChunk")) return false;
     takeDigest();
+    takeStats("decodeChunk");
     for (int k = 0; k < 2 && build; ++k) {
       std::size_t len = 0;
       fqgpuCheck(fqgpu_decode_index(ctx_, k, nullptr, 0, &len), "decodeChunk");

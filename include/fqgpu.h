@@ -434,6 +434,43 @@ int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_t *crc, siz
 uint32_t fqgpu_crc32_combine(uint32_t crc_a, uint32_t crc_b, uint64_t len_b);
 int fqgpu_ctx_set_check_only(fqgpu_ctx *ctx, int on);
 
+/* ---- Extension (nothing in the reference): a read summary of a chunk, taken where the chunk lies already -- in HBM -- in
+ * one pass over its sequence and quality lines by its record table (fqgpu_rec; header lines and text behind a '+' play no
+ * part).  A summary is a flat block of fqgpu_stats_words(P) = 176 + 70 (P + 1) uint64_t counters; P = `positions`,
+ * 1 .. 65535, is the caller's choice.  Tables "by position" have P + 1 rows: row p < P is position p of a read (0-based),
+ * row P collects every position >= P, so that nothing is dropped:
+ *   word 0 n_records | 1 n_bases | 2 min_len | 3 max_len | 4 reads_with_n (reads with at least one N) | 5 positions | 6, 7 zero
+ *   8 .. 71    meanq_hist[64]   reads by floor(sum of Phred over the read / len), Phred = quality byte - 33
+ *   72 .. 172  gc_hist[101]     reads by floor(100 (#G + #C) / len); N counts in len
+ *   173 .. 175 zero
+ *   then P + 1       len_hist   reads by min(len, P)
+ *   then 5 (P + 1)   base_pos[row][A, C, G, T, N]
+ *   then 64 (P + 1)  qual_pos[row][Phred 0 .. 63]
+ * Integer arithmetic throughout: the summary is a pure function of the chunk's records.  A sequence byte outside ACGTN, a
+ * quality byte outside 33 .. 96 (as the analysis and the encoder judge them), a record that does not lie inside the chunk
+ * or a record of length 0 (which no parser here makes; it has no mean quality): FQGPU_E_ARG with `out` zeroed.
+ *   fqgpu_stats_words   host only: the size of a summary; 0 for positions == 0 or > 65535
+ *   fqgpu_chunk_stats   the chunk on the handle's staging block, in the states in which fqgpu_chunk_crc32 is valid: (a) from
+ *                       fqgpu_encode_begin until the handle's next host-pointer call, on the handle's copy stream beside the
+ *                       lane's encode, by the record table given or built by the device parser -- the host-pointer encode
+ *                       never patches the device copy, so N is counted as N with FQGPU_F_WRITE_BACK_N too; (b) after a
+ *                       SUCCESSFUL fqgpu_decode_chunk (check-only with raw_out == NULL included), fqgpu_decode_chunk_indexing,
+ *                       fqgpu_decode_block or fqgpu_decode_block_indexed.  Everywhere else -- after a failed or refused decode,
+ *                       after fqgpu_decode_chunk_range or _fasta, after fqgpu_encode_cancel, with no chunk on the handle --
+ *                       FQGPU_E_ARG with `out` zeroed.  May be called together with fqgpu_chunk_crc32, in either order.
+ *   fqgpu_dblock_stats  waits for the block's last operation as fqgpu_dblock_crc32 does, then summarises WHATEVER the raw
+ *                       block holds when asked: after fqgpu_dblock_encode with FQGPU_F_WRITE_BACK_N that is 'A' where the
+ *                       input had 'N'; take the summary before such an encode (or after a decode) if N is to be counted.
+ *   fqgpu_stats_merge   host only: dst += src.  Counters add, min_len / max_len take the min / max; a dst whose n_records
+ *                       is 0 (a block of zeros included) is empty and becomes a copy of src.  Different `positions`, or a
+ *                       length that is not fqgpu_stats_words(positions): FQGPU_E_ARG.
+ * cap_words below the size needed: FQGPU_E_OVERFLOW, nothing is written.  Bad positions or a NULL pointer: FQGPU_E_ARG.
+ * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; the two host helpers work. */
+size_t fqgpu_stats_words(unsigned positions);
+int fqgpu_chunk_stats(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words);
+int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigned positions, uint64_t *out, size_t cap_words);
+int fqgpu_stats_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

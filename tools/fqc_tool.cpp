@@ -25,11 +25,23 @@
 //               exit 1 at the first that differs, and when the .fqs is there but cannot be used or the archive's size is not
 //               the recorded one.  Without a .fqs the streams are still decoded: "sums": "none", a warning, exit 0.  Uses
 //               <in.fqc>.fqx when it lies there)
+//   fqc_tool s <in.fqc> <report.tsv> [-t threads] [-d dev,dev,...] [--positions P]
+//              (extension: everything t does -- same checks, same exit codes, <in.fqc>.fqx and <in.fqc>.fqs used when they lie
+//               there -- and a read summary of the archive, taken on the device where each chunk's decode left it: records,
+//               bases, read lengths, reads with N, and per position in the read (rows 0 .. P - 1, row P = every position >= P;
+//               default P 512) the counts of A C G T N and of every Phred value; histograms of the reads' mean quality and GC
+//               percentage.  Text, tab-separated, integers only; written as <report.tsv>.part and renamed on success, a failed
+//               run leaves neither)
+//   fqc_tool c <in.fastq> <out.fqc> ... --stats <report.tsv> [--positions P]
+//              (extension: the same report for the input, taken beside the encode; the archive is what it is without the
+//               option, and `s` on it gives the same bytes.  --stats with d, x or t, and --positions without a report to
+//               write, are usage errors)
 // (fqcomp28 c --i1 in.fastq -o out.fqc -t N / fqcomp28 d -i out.fqc --o1 out.fastq, src/app.cpp:29-76.)
 // Prints one JSON line with sizes, seconds and blocks per worker; d and x also say how many blocks were decoded from a decode
 // index ("index": "used") or were given one ("built"), and its bytes; "sums" / "verified" / "crc32": what became of the chunk
 // sums file, the blocks whose digest was compared and held, the whole file's CRC-32; with --fasta also "form": "fasta" and the
-// bytes read of the archive.  Needs a GPU: no CPU fallback.
+// bytes read of the archive; with a report "stats": its path, "bases" and "mean_quality" (total Phred / bases, the one
+// number that is no integer and in no report).  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -41,16 +53,21 @@ using namespace fqcomp28;
 int main(int argc, char **argv) {
   const bool check_cmd = argc >= 2 && !strcmp(argv[1], "t");
   const bool index_cmd = argc >= 2 && !strcmp(argv[1], "x");
+  const bool stats_cmd = argc >= 2 && !strcmp(argv[1], "s");
   const bool one_arg = index_cmd || check_cmd;  // x and t take the archive alone
-  if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg)) {
-    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B]\n"
+  if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg && !stats_cmd)) {
+    std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B] [--stats report.tsv [--positions P]]\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
-                         "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n");
+                         "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
+                         "       fqc_tool s <in.fqc> <report.tsv> [-t N] [-d 0,1,..] [--positions P]\n");
     return 2;
   }
   Settings set;
   bool range = false, fasta = false;
+  std::string stats_path = stats_cmd ? argv[3] : "";
+  bool stats_opt = false;
+  long positions = -1;
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
   for (int i = one_arg ? 3 : 4; i < argc; ++i) {
     const std::string a = argv[i];
@@ -60,9 +77,11 @@ int main(int argc, char **argv) {
     else if (a == "-S") set.sample_chunk_size = (std::size_t)std::atoll(val()) << 20;
     else if (a == "--accumulate-n") set.accumulate_n_buffers = true;
     else if (a == "--fasta") fasta = true;
-    else if (a == "--index" && !check_cmd) set.decode_index = true;  // (t builds nothing)
+    else if (a == "--stats") { stats_opt = true; stats_path = val(); }
+    else if (a == "--positions") positions = std::atol(val());
+    else if (a == "--index" && !check_cmd && !stats_cmd) set.decode_index = true;  // (t builds nothing)
     else if (a == "--checksum" && argv[1][0] == 'c') set.checksum = true;
-    else if (a == "--index-stride" && !check_cmd) { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
+    else if (a == "--index-stride" && !check_cmd && !stats_cmd) { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
       const std::string v = val();
@@ -91,18 +110,33 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--fasta goes with d alone, and builds no index: not with c, x, t, --index or --index-stride\n");
     return 2;
   }
+  // (said before any device is touched)
+  if (stats_opt && argv[1][0] != 'c') {
+    std::fprintf(stderr, "--stats goes with c alone (s <in.fqc> <report.tsv> summarises an archive): not with d, x, t or s\n");
+    return 2;
+  }
+  if (positions != -1 && stats_path.empty()) {
+    std::fprintf(stderr, "--positions needs a report to write: c --stats <report.tsv>, or s\n");
+    return 2;
+  }
+  if (positions != -1 && (positions < 1 || positions > 65535)) {
+    std::fprintf(stderr, "--positions %ld: expected 1 .. 65535\n", positions);
+    return 2;
+  }
+  if (!stats_path.empty()) set.stats_positions = positions == -1 ? 512u : static_cast<unsigned>(positions);
   try {
     const bool comp = argv[1][0] == 'c';
     if (!comp) {  // --index on the way back: build, not write
       set.build_index = set.decode_index && !range;
       set.decode_index = false;
     }
-    const FarmReport r = check_cmd ? processArchiveCheck(argv[2], set)
+    const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
+    if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
                 "\"seq_bytes\": %zu, \"qual_bytes\": %zu, \"misc_bytes\": %zu, \"seconds\": %.6f, \"blocks_per_worker\": [",
                 argv[1], set.n_threads, set.devices.size(), r.in.raw, r.in.n_records, comp ? r.out.n_blocks : (std::size_t)0,
@@ -116,6 +150,11 @@ int main(int argc, char **argv) {
     if (!comp && argv[1][0] != 'x') {
       std::printf(", \"sums\": \"%s\", \"verified\": %zu", r.sums, r.verified_blocks);
       if (r.verified_blocks) std::printf(", \"crc32\": \"%08x\"", r.file_crc32);
+    }
+    if (!stats_path.empty()) {  // ("records" above is the summary's count as well)
+      std::string quoted;
+      for (const char ch : stats_path) { if (ch == '"' || ch == '\\') quoted += '\\'; quoted += ch; }
+      std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
     }
     if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
     std::printf("}\n");
