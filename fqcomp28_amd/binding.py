@@ -145,6 +145,10 @@ _PROTOS = {
     "fqgpu_chunk_stats": (C.c_int, [C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t]),
     "fqgpu_dblock_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t]),
     "fqgpu_stats_merge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "fqgpu_filter_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                      C.c_void_p, C.c_void_p]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -290,6 +294,40 @@ def _stats_call(fn, positions, *front):
     return rc, out
 
 
+FILTER_NONE = 0xFFFFFFFF
+FILTER_REPORT_WORDS = 16
+FILTER_REPORT_NAMES = ("n_records", "n_kept", "bases_in", "bases_kept", "bytes_kept", "dropped_short", "dropped_long", "dropped_n",
+                       "dropped_mean_q", "dropped_low_q")
+
+
+def read_filter(min_len=0, max_len=FILTER_NONE, max_n=FILTER_NONE, min_mean_q=0, low_q=0, max_low_pct=0, reserved=(0, 0)):
+    """an fqgpu_filter (include/fqgpu.h) as a uint32 array of eight words; the defaults keep every read"""
+    return np.array([min_len, max_len, max_n, min_mean_q, low_q, max_low_pct, reserved[0], reserved[1]], dtype=np.uint32)
+
+
+def filter_check(flt):
+    """fqgpu_filter_check -> rc (host only)"""
+    return lib().fqgpu_filter_check(_p(flt))
+
+
+def _filter_call(fn, front, flt, n_recs, out_cap=None, want_keep=True, query=False):
+    """A device filter call -> dict(rc, out, out_len, report, keep).  out_cap None: the size is asked for first (out=NULL), then
+    the call is made with a buffer of that size -- query: the size is asked for and that is all; a number: ONE call with a
+    buffer of that many bytes."""
+    report = np.zeros(FILTER_REPORT_WORDS, dtype=np.uint64)
+    keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
+    n = C.c_size_t(0)
+    flt = np.ascontiguousarray(flt, dtype=np.uint32)
+    if out_cap is None:
+        rc = fn(*front, _p(flt), None, 0, C.byref(n), _p(report), _p(keep))
+        if rc != 0 or query:
+            return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep)
+        out_cap = n.value
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    rc = fn(*front, _p(flt), _p(out), out_cap, C.byref(n), _p(report), _p(keep))
+    return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep)
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -395,6 +433,11 @@ class DBlock:
         _check(rc, "dblock_stats")
         return out
 
+    def filter(self, flt, **kw):
+        """fqgpu_dblock_filter: the reads of the raw block, as it lies on the device, that pass `flt` (read_filter) ->
+        dict(rc, out, out_len, report, keep); see _filter_call"""
+        return _filter_call(lib().fqgpu_dblock_filter, (self.ctx.h, self.h), flt, self.n_recs, **kw)
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -495,6 +538,11 @@ class Context:
     def chunk_stats(self, positions):
         """fqgpu_chunk_stats -> (rc, words): the read summary of the chunk on the staging block, where chunk_crc32 is valid"""
         return _stats_call(lib().fqgpu_chunk_stats, positions, self.h)
+
+    def chunk_filter(self, flt, n_recs, **kw):
+        """fqgpu_chunk_filter: the reads of the chunk on the staging block (n_recs records) that pass `flt`, where chunk_stats
+        is valid -> dict(rc, out, out_len, report, keep); see _filter_call"""
+        return _filter_call(lib().fqgpu_chunk_filter, (self.h,), flt, n_recs, **kw)
 
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""

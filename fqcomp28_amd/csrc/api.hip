@@ -535,6 +535,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->hp_chunk.release();
   ctx->crc.release();
   ctx->stats.release();
+  ctx->filter.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1675,4 +1676,34 @@ extern "C" int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigne
   // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
   if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
   return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
+}
+
+// ------------------------------------------------------------------ the reads of a chunk in HBM that pass a filter (filter.hip)
+// Shared front of the two calls: no device is said before any argument is looked at; *out_len and the report are zeroed
+// before anything else can fail.
+static int filter_args(fqgpu_ctx *ctx, const fqgpu_filter *f, size_t *out_len, uint64_t *report) {
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  if (out_len) *out_len = 0;
+  if (report) memset(report, 0, FQGPU_FILTER_REPORT_WORDS * sizeof(uint64_t));
+  if (!ctx || !out_len || !report || fqgpu_filter_check(f) != FQGPU_OK) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
+// As fqgpu_chunk_stats: on the handle's copy stream, beside the lane's encode or behind the decode.
+extern "C" int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                                  uint64_t *report, uint8_t *keep_out) {
+  if (const int rc = filter_args(ctx, f, out_len, report)) return rc;
+  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
+  const fqgpu_dblock *b = ctx->hp_block;
+  return fq_filter_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, f, out, out_cap, out_len, report, keep_out);
+}
+
+extern "C" int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
+                                   size_t *out_len, uint64_t *report, uint8_t *keep_out) {
+  int rc = filter_args(ctx, f, out_len, report);
+  if (rc) return rc;
+  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
+  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
+  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  return fq_filter_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, f, out, out_cap, out_len, report, keep_out);
 }

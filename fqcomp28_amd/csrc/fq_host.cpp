@@ -81,6 +81,13 @@ extern "C" int fqgpu_stats_merge(uint64_t *dst, size_t dst_words, const uint64_t
   return FQGPU_OK;
 }
 
+// Read filters (filter.hip applies them): what a filter may say.
+extern "C" int fqgpu_filter_check(const fqgpu_filter *f) {
+  if (!f || f->min_len > f->max_len || f->min_mean_q > 63u || f->low_q > 64u || f->max_low_pct > 100u || f->reserved[0] || f->reserved[1])
+    return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

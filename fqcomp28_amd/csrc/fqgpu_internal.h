@@ -234,6 +234,15 @@ struct StatsScratch {
   void release();
 };
 
+// Selection of the reads that pass a filter from a chunk in HBM (filter.hip): per record the kept size and the start of its
+// header line, the keep bits, the offsets of the kept records in the output, the gathered output, the result words and their
+// page-locked landing place; all grown on demand
+struct FilterScratch {
+  DevBuf ksize, hstart, keep, koff, dst, res, scan_tmp;
+  void *host = nullptr;
+  void release();
+};
+
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
@@ -283,6 +292,7 @@ struct fqgpu_ctx {
   bool check_only = false;            // fqgpu_ctx_set_check_only: fqgpu_decode_chunk takes raw_out == NULL
   CrcScratch crc;
   StatsScratch stats;
+  FilterScratch filter;
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -424,6 +434,11 @@ int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, siz
 // Read summary of a chunk in HBM (stats.hip), on st, waited for: out[0, fqgpu_stats_words(positions)) on the host
 int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                    unsigned positions, uint64_t *out);
+
+// The reads of a chunk in HBM that pass *f (filter.hip; *f has passed fqgpu_filter_check), on st, waited for: report, *out_len,
+// keep_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes into out
+int fq_filter_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                    const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

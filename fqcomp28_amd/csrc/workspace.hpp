@@ -634,6 +634,53 @@ public:
     return fastaOnDevice(cbs, first, end, nullptr);
   }
 
+  /** Extension: the reads of the chunk that pass `filter`, as the canonical FASTQ bytes decodeChunk lays out for them, into
+   *  piece.raw_data (fqgpu_chunk_filter); `report` receives the chunk's FQGPU_FILTER_REPORT_WORDS counters.  The chunk is
+   *  decoded check-only -- nothing of it comes back -- with the block's decode indexes when present, its digest is taken
+   *  and kept for lastDigest() when setVerify is on (the digest of the WHOLE restored chunk, so the caller compares it with
+   *  the writer's as always), and only the kept bytes cross the link: one copy.  piece.idx = cbs.chunk_idx, piece.records
+   *  stays empty.  There is no host fallback and FQGPU_SHIM_HOST_HEADERS does not apply: a chunk the device refuses throws
+   *  std::runtime_error naming the chunk and the record. */
+  void decodeChunkFiltered(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_filter &filter, uint64_t *report) {
+    StageClock clk;
+    last_digest_ = {};
+    const auto refused = [&](const std::string &what) {
+      return std::runtime_error("decodeChunkFiltered: chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
+    };
+    if (fqgpu_filter_check(&filter) != FQGPU_OK) throw std::invalid_argument("decodeChunkFiltered: a filter fqgpu_filter_check refuses");
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
+    clk.lap("misc");
+    piece.clear();
+    piece.idx = cbs.chunk_idx;
+    // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
+    struct CheckOnly {
+      fqgpu_ctx *ctx;
+      bool restore;
+      ~CheckOnly() { if (restore) (void)fqgpu_ctx_set_check_only(ctx, 0); }
+    } mode{ctx_, !check_only_};
+    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, 1), "decodeChunkFiltered");
+    RecordTable recs(a.n_recs);
+    std::size_t laid_out = 0, bad = 0;
+    const StreamArgs &s = a.s;
+    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
+                                      s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], nullptr,
+                                      cbs.original_size.total, recs.data(), &laid_out, &bad);
+    if (rc != FQGPU_OK)
+      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
+                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
+    clk.lap("gpu");
+    takeDigest();
+    // the kept bytes are never more than the chunk: one call, no size query
+    piece.raw_data.resize(cbs.original_size.total);
+    std::size_t len = 0;
+    const int frc = fqgpu_chunk_filter(ctx_, &filter, reinterpret_cast<uint8_t *>(piece.raw_data.data()), piece.raw_data.size(), &len, report, nullptr);
+    if (frc != FQGPU_OK) throw refused(std::string("the filter: ") + fqgpu_strerror(frc));
+    piece.raw_data.resize(len);
+    clk.lap("filter");
+    clk.done(cbs.chunk_idx);
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */

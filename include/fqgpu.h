@@ -471,6 +471,47 @@ int fqgpu_chunk_stats(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t 
 int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigned positions, uint64_t *out, size_t cap_words);
 int fqgpu_stats_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words);
 
+/* ---- Extension (nothing in the reference): the reads of a chunk that pass a filter, selected where the chunk lies already
+ * -- in HBM -- so that only the kept bytes come down.  A read is judged by its length, its number of N, the sum of its
+ * Phred values (quality byte - 33) and the number of its Phred values below a level, the quantities the read summary
+ * counts; integer arithmetic throughout, so the result is a pure function of the chunk's records.  The output is the
+ * CANONICAL bytes of the kept records in input order (per record the header line with its '\n', the sequence, "\n+\n", the
+ * quality line, '\n': what fqgpu_chunk_crc32 digests and a restore lays out); text behind a '+' is dropped, N stays N.
+ *   report  FQGPU_FILTER_REPORT_WORDS uint64_t: 0 n_records | 1 n_kept | 2 bases_in | 3 bases_kept | 4 bytes_kept |
+ *           5 dropped_short | 6 dropped_long | 7 dropped_n | 8 dropped_mean_q | 9 dropped_low_q | 10 .. 15 zero.  A dropped
+ *           read is counted once, under its first failing criterion in that order.  Reports of several chunks add word by word.
+ *   out == NULL           size query: *out_len, report and keep_out are filled, nothing is copied
+ *   out_cap < *out_len    FQGPU_E_OVERFLOW: nothing is written to out, *out_len holds the size needed, report is valid
+ *   keep_out              NULL, or (n_recs + 7) / 8 bytes: bit r & 7 of byte r >> 3 is set iff record r is kept
+ * Only the lines a criterion needs are read: the sequence lines when max_n is on, the quality lines when min_mean_q or low_q
+ * is on; a length-only filter touches the record table alone.  The bytes of the lines that ARE read are judged as the read
+ * summary judges them -- a sequence byte outside ACGTN, a quality byte outside 33 .. 96: FQGPU_E_ARG -- and a byte of a line
+ * that is not read is not looked at.  A record that does not lie inside the chunk, or of length 0: FQGPU_E_ARG.  A filter
+ * fqgpu_filter_check refuses (min_len > max_len, min_mean_q > 63, low_q > 64, max_low_pct > 100, reserved not zero), a
+ * NULL where data is expected: FQGPU_E_ARG.  Every FQGPU_E_ARG comes with *out_len = 0 and a zeroed report.
+ *   fqgpu_filter_check   host only: FQGPU_OK or FQGPU_E_ARG
+ *   fqgpu_chunk_filter   the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_stats is valid,
+ *                        on the same stream; everywhere else FQGPU_E_ARG.  It leaves the chunk as it is: digest and summary
+ *                        taken before or after it are the same.  `out` receives ONE copy of *out_len bytes; nothing else of
+ *                        the chunk comes down.
+ *   fqgpu_dblock_filter  waits for the block's last operation as fqgpu_dblock_stats does, then selects from WHATEVER the raw
+ *                        block holds when asked.
+ * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_filter_check works. */
+#define FQGPU_FILTER_NONE 0xFFFFFFFFu
+typedef struct {
+  uint32_t min_len, max_len;   /* keep min_len <= len <= max_len; max_len FQGPU_FILTER_NONE = no upper limit */
+  uint32_t max_n;              /* keep #N <= max_n; FQGPU_FILTER_NONE = off */
+  uint32_t min_mean_q;         /* keep sum(Phred) >= min_mean_q * len, i.e. floor(mean) >= q as the summary bins it; 0 = off; <= 63 */
+  uint32_t low_q, max_low_pct; /* keep 100 * #(Phred < low_q) <= max_low_pct * len; low_q 0 = off; low_q <= 64, pct <= 100 */
+  uint32_t reserved[2];        /* zero */
+} fqgpu_filter;
+#define FQGPU_FILTER_REPORT_WORDS 16
+int fqgpu_filter_check(const fqgpu_filter *f);
+int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                       uint64_t *report, uint8_t *keep_out);
+int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
+                        size_t *out_len, uint64_t *report, uint8_t *keep_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -16,6 +16,14 @@
 //               them goes unseen.  Uses <in.fqc>.fqx when it lies there (its sequence indexes); never builds one, never
 //               verifies: --fasta with --index or --index-stride, or with c, x or t, is a usage error.  A failed run leaves
 //               neither <out.fasta> nor <out.fasta>.part)
+//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--min-len N] [--max-len N] [--max-n K] [--min-mean-q Q] [--max-low-q Q:PCT]
+//              (extension: any of these restores only the reads that pass, in input order, as the bytes a plain restore writes
+//               for them: length N .. N, at most K bases N, floor(mean Phred) at least Q, at most PCT percent of the Phred
+//               values below Q.  The reads are judged and gathered on the device where the decode left the chunk; only the kept
+//               bytes come down.  <in.fqc>.fqx is used and <in.fqc>.fqs verified -- against the whole chunk, before any of it is
+//               written -- when they lie there.  A filter with c, x, t or s, with --records, --fasta, --index or --index-stride,
+//               a value out of range and a malformed Q:PCT are usage errors.  A failed run leaves neither <out.fastq> nor
+//               <out.fastq>.part)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -41,7 +49,8 @@
 // index ("index": "used") or were given one ("built"), and its bytes; "sums" / "verified" / "crc32": what became of the chunk
 // sums file, the blocks whose digest was compared and held, the whole file's CRC-32; with --fasta also "form": "fasta" and the
 // bytes read of the archive; with a report "stats": its path, "bases" and "mean_quality" (total Phred / bases, the one
-// number that is no integer and in no report).  Needs a GPU: no CPU fallback.
+// number that is no integer and in no report); with a filter "filter": what was read, what was kept and what each
+// criterion dropped ("records" / "raw_bytes" of the line are then what was written).  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -57,6 +66,7 @@ int main(int argc, char **argv) {
   const bool one_arg = index_cmd || check_cmd;  // x and t take the archive alone
   if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg && !stats_cmd)) {
     std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B] [--stats report.tsv [--positions P]]\n"
+                         "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--min-len N] [--max-len N] [--max-n K] [--min-mean-q Q] [--max-low-q Q:PCT]\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
@@ -69,6 +79,14 @@ int main(int argc, char **argv) {
   bool stats_opt = false;
   long positions = -1;
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
+  fqgpu_filter filter = {0, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0, 0, 0, {0, 0}};
+  bool filtered = false;
+  // a decimal number of at most nine digits (so that it fits a uint32_t)
+  const auto u32 = [](const std::string &t, uint32_t &out) {
+    if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
+    out = static_cast<uint32_t>(std::stoul(t));
+    return true;
+  };
   for (int i = one_arg ? 3 : 4; i < argc; ++i) {
     const std::string a = argv[i];
     auto val = [&]() -> const char * { if (i + 1 >= argc) { std::fprintf(stderr, "%s needs a value\n", a.c_str()); std::exit(2); } return argv[++i]; };
@@ -82,6 +100,23 @@ int main(int argc, char **argv) {
     else if (a == "--index" && !check_cmd && !stats_cmd) set.decode_index = true;  // (t builds nothing)
     else if (a == "--checksum" && argv[1][0] == 'c') set.checksum = true;
     else if (a == "--index-stride" && !check_cmd && !stats_cmd) { set.decode_index = true; set.index_stride = static_cast<unsigned>(std::atoi(val())) << 10; }  // Ki symbols
+    else if (a == "--min-len" || a == "--max-len" || a == "--max-n" || a == "--min-mean-q") {
+      const std::string v = val();
+      uint32_t &field = a == "--min-len" ? filter.min_len : a == "--max-len" ? filter.max_len : a == "--max-n" ? filter.max_n : filter.min_mean_q;
+      if (!u32(v, field)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      filtered = true;
+    } else if (a == "--max-low-q") {
+      const std::string v = val();
+      const std::size_t colon = v.find(':');
+      if (colon == std::string::npos || !u32(v.substr(0, colon), filter.low_q) || !u32(v.substr(colon + 1), filter.max_low_pct)) {
+        std::fprintf(stderr, "--max-low-q %s: expected Q:PCT (at most PCT percent of a read's Phred values below Q)\n", v.c_str());
+        return 2;
+      }
+      filtered = true;
+    }
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
       const std::string v = val();
@@ -110,6 +145,14 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--fasta goes with d alone, and builds no index: not with c, x, t, --index or --index-stride\n");
     return 2;
   }
+  if (filtered && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "a read filter goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (filtered && fqgpu_filter_check(&filter) != FQGPU_OK) {
+    std::fprintf(stderr, "the read filter: expected --min-len <= --max-len, --min-mean-q 0 .. 63, --max-low-q Q:PCT with Q 0 .. 64 and PCT 0 .. 100\n");
+    return 2;
+  }
   // (said before any device is touched)
   if (stats_opt && argv[1][0] != 'c') {
     std::fprintf(stderr, "--stats goes with c alone (s <in.fqc> <report.tsv> summarises an archive): not with d, x, t or s\n");
@@ -133,6 +176,7 @@ int main(int argc, char **argv) {
     const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
+                         : filtered ? processArchiveFiltered(argv[2], argv[3], filter, set)
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
@@ -155,6 +199,12 @@ int main(int argc, char **argv) {
       std::string quoted;
       for (const char ch : stats_path) { if (ch == '"' || ch == '\\') quoted += '\\'; quoted += ch; }
       std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
+    }
+    if (filtered) {
+      const auto w = [&](unsigned i) { return (unsigned long long)r.filter[i]; };
+      std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
+                  "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
+                  w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
     }
     if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
     std::printf("}\n");
