@@ -21,13 +21,10 @@ constexpr unsigned TS_TILE = 32768;    // symbols per tile (lpos16 and the 16-bi
 constexpr unsigned TS_BATCH = 4096;    // symbols ranked between two workgroup barriers (K3: 72 KB of LDS, two workgroups per CU)
 constexpr unsigned TS_THREADS = 512;   // K3
 constexpr unsigned TS_WAVES = TS_THREADS / 64;
-#ifndef FQ_K6_THREADS
-#define FQ_K6_THREADS 512
-#endif
-constexpr unsigned TS_GP_THREADS = FQ_K6_THREADS;  // K6: 78 KB of LDS, two workgroups per CU = 16 waves (256 threads: 8 waves per CU, 2.6 % slower on the step)
-constexpr unsigned TS_GP_PPT = 4096 / TS_GP_THREADS;  // symbols a thread packs per round: 16 or 8
+constexpr unsigned TS_GP_THREADS = 512;  // K6: 78 KB of LDS, two workgroups per CU = 16 waves (256 threads: 8 waves per CU, 2.6 % slower on the step)
+constexpr unsigned TS_GP_PPT = 4096 / TS_GP_THREADS;  // symbols a thread packs per round
 constexpr unsigned TS_SUB = TS_GP_THREADS * TS_GP_PPT;  // symbols packed per round of K6 (4096)
-static_assert(TS_GP_PPT == 16 || TS_GP_PPT == 8, "K6 packs 16 or 8 symbols per thread and round");
+static_assert(TS_GP_THREADS == 512 && TS_GP_PPT == 8, "K6 is written for 512 threads: eight waves in its scans, eight symbols (96 bits at most) per thread and packing round");
 static_assert(TS_TILE % TS_BATCH == 0 && TS_TILE % TS_SUB == 0 && TS_SUB % PACK_TILE == 0, "tile geometry");
 
 // phase timing of the two kernels (experiments build only): g_ts_prof[8 * kernel + phase] += wall clock ticks of workgroup thread 0
@@ -482,6 +479,63 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
 // that were handed out before it, i.e. that are already running.
 constexpr unsigned long long TS_FLAG_AGG = 1ull << 62, TS_FLAG_INCL = 2ull << 62, TS_VAL_MASK = (1ull << 62) - 1ull;
 
+// K6's own scans.  (ts_block_scan is K3's as well, and K3's code is pinned by tests/test_build_invariants.py.)  The kernel is
+// bound by the instructions it issues, and it scans once per packing round: a __shfl_up step is a ds_bpermute_b32 -- an LDS
+// round trip the next step waits for -- plus a compare and a select; a DPP step is ONE v_add_u32 whose operand comes from
+// another lane on its way into the ALU.  v + (lane `ctrl` away, 0 where there is none or where the masks exclude the row / bank).
+template <unsigned CTRL, unsigned ROW_MASK, unsigned BANK_MASK>
+__device__ __forceinline__ unsigned k6_dpp_add(unsigned v) {
+  return v + (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, false);
+}
+// inclusive scan over the wave's 64 lanes: four steps inside the rows of 16, then lane 15 of rows 0 and 2 to rows 1 and 3,
+// then lane 31 to rows 2 and 3
+__device__ __forceinline__ unsigned k6_wave_scan(unsigned v) {
+  v = k6_dpp_add<0x111, 0xF, 0xF>(v);  // row_shr:1
+  v = k6_dpp_add<0x112, 0xF, 0xF>(v);  // row_shr:2
+  v = k6_dpp_add<0x114, 0xF, 0xE>(v);  // row_shr:4
+  v = k6_dpp_add<0x118, 0xF, 0xC>(v);  // row_shr:8
+  v = k6_dpp_add<0x142, 0xA, 0xF>(v);  // row_bcast:15
+  v = k6_dpp_add<0x143, 0xC, 0xF>(v);  // row_bcast:31
+  return v;
+}
+// popcount(x) + y as the ONE instruction it is (left to itself the compiler spreads the shift of the table lookup that follows
+// over both terms: three instructions instead of two)
+__device__ __forceinline__ unsigned k6_popc_add(unsigned x, unsigned y) {
+  unsigned r;
+  asm("v_bcnt_u32_b32 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y));
+  return r;
+}
+// lane `l`'s value (l uniform)
+__device__ __forceinline__ unsigned k6_readlane(unsigned v, unsigned l) { return (unsigned)__builtin_amdgcn_readlane((int)v, (int)fq_uniform(l)); }
+// exclusive scan of one value per thread over K6's 512 threads; *total = sum (all threads call).  The eight wave totals are
+// read by lanes 0 .. 7 of every wave (one LDS read), scanned in that row of eight, and picked with v_readlane.
+// ONE barrier: the caller has a barrier of its own between the reads of wsum here and the next call.
+__device__ __forceinline__ unsigned k6_block_scan(unsigned v, unsigned *wsum, unsigned *total) {
+  static_assert(TS_GP_THREADS / 64 == 8, "eight wave totals: one row of eight lanes");
+  const unsigned inc = k6_wave_scan(v);
+  if (fq_lane() == 63) wsum[threadIdx.x >> 6] = inc;
+  __syncthreads();
+  const unsigned s = wsum[fq_lane() & 7u];
+  unsigned t = k6_dpp_add<0x111, 0xF, 0xF>(s);
+  t = k6_dpp_add<0x112, 0xF, 0xF>(t);
+  t = k6_dpp_add<0x114, 0xF, 0xF>(t);
+  *total = k6_readlane(t, 7u);
+  return k6_readlane(t - s, threadIdx.x >> 6) + inc - v;
+}
+// run-start bitmap -> wpre (all threads; bm complete and visible)
+__device__ __forceinline__ void k6_build_wpre(TsRunMap &m, unsigned *wsum) {
+  constexpr unsigned WPT = TS_TILE / 32 / TS_GP_THREADS;  // bitmap words per thread: 2
+  unsigned c[WPT], sum = 0;
+#pragma unroll
+  for (unsigned k = 0; k < WPT; k++) { c[k] = __popc(m.bm[WPT * threadIdx.x + k]); sum += c[k]; }
+  unsigned tot;
+  unsigned ex = k6_block_scan(sum, wsum, &tot);
+#pragma unroll
+  for (unsigned k = 0; k < WPT; k++) { m.wpre[WPT * threadIdx.x + k] = (uint16_t)ex; ex += c[k]; }
+  __syncthreads();
+}
+template <bool V> struct TsFlag { static constexpr bool value = V; };
+
 template <class M>
 __global__ void __launch_bounds__(TS_GP_THREADS)
 k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict__ runs,
@@ -490,9 +544,18 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
                    const uint32_t *__restrict__ log_prefix, unsigned long long cap, uint32_t *__restrict__ out,
                    StreamResult *res, unsigned long long *__restrict__ tile_bit_base, uint4 *__restrict__ edges) {
   constexpr unsigned NW = TS_SUB * 12 / 32 + 4;
-  __shared__ uint16_t vals[TS_TILE];  // (nb, bits) of the tile in sorted order
-  __shared__ uint32_t words[NW];
-  __shared__ TsRunMap rm;
+  // One struct, so that the order is this one: the words (and the run deltas that live in them while the tile is gathered)
+  // and the run map in front -- every access to them in the gather is the thread's base register plus the instruction's
+  // 16-bit offset field --, the 64 KB of values behind them.
+  struct K6Shared {
+    uint32_t words[NW];
+    TsRunMap rm;
+    uint16_t vals[TS_TILE];  // (nb, bits) of the tile in sorted order
+  };
+  __shared__ __attribute__((aligned(16))) K6Shared sh;
+  uint32_t (&words)[NW] = sh.words;
+  TsRunMap &rm = sh.rm;
+  uint16_t (&vals)[TS_TILE] = sh.vals;
   __shared__ unsigned wsum[TS_GP_THREADS / 64], s_tile;
   __shared__ unsigned long long s_base;
   const unsigned tid = threadIdx.x, wave = tid >> 6, lane = fq_lane();
@@ -507,40 +570,84 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
   TS_PROF_DECL
   constexpr unsigned PS = M::STREAM == 1 ? 16 : 24; (void)PS;
   const unsigned e0 = tile * TS_TILE, nt = min(TS_TILE, n_sym - e0);
+  // Every tile of a stream but its last one is full: the gather and the packing rounds exist twice, and the full tile's
+  // copies have fixed trip counts and no bounds guard per symbol (uniform choice).
+  const bool full = nt == TS_TILE;
   const uint2 *rlist = runs + (size_t)tile * ts_run_stride<M>();
   const unsigned nr = run_count[tile];
-  // "global slot of local position p" = p + gd[run of p]; the deltas of the first NW runs sit in LDS
-  // (the packing buffer is idle until the tile's values are in), later runs are read from the list
+  // "BYTE offset in out16 of local position p" = 2 p + gd[1 + run of p] (the popcount that finds a run counts its own start: it
+  // is the run's number + 1; modulo 2^32, slots are below 2^31); the deltas of the first NW - 1 runs sit in LDS (the packing buffer is idle until the tile's values
+  // are in), later runs are read from the list
   uint32_t *gd = words;
   for (unsigned r = tid; r < nr; r += TS_GP_THREADS) {
     const uint2 e = rlist[r];
     const unsigned beg = e.y & 0xFFFFu;
-    if (r < NW) gd[r] = e.x - beg;
+    if (r + 1u < NW) gd[r + 1u] = (e.x - beg) << 1;
     atomicOr(&rm.bm[beg >> 5], 1u << (beg & 31u));
   }
   __syncthreads();
-  ts_build_wpre<TS_GP_THREADS>(rm, wsum);
+  k6_build_wpre(rm, wsum);
   TS_PROF(PS + 0);
-  // ---- the runs of (nb, bits): consecutive lanes on consecutive slots
-  unsigned bits = 0;
-  if (nr <= NW) {  // (uniform) every lookup stays in LDS: the loads of sixteen positions per thread are in flight together
-#pragma unroll 16
-    for (unsigned p = tid; p < nt; p += TS_GP_THREADS) {
-      const unsigned v = out16[p + gd[ts_run_of(rm, p)]];
-      vals[p] = (uint16_t)v;
-      bits += v >> 12;
+  // ---- the runs of (nb, bits): consecutive lanes on consecutive slots.  Thread t takes positions t, t + 512, ...: bit t & 31
+  // of map word (t >> 5) + 16 k -- the word pointers and the mask are the thread's own constants, the LDS addresses
+  // differ by the instruction's offset field alone; global addresses are a 32-bit byte offset from a uniform base.
+  const bool in_lds = nr < NW;  // (uniform) every lookup stays in LDS: the loads of sixteen positions per thread are in flight together
+  const char *out16_b = reinterpret_cast<const char *>(out16), *rlist_b = reinterpret_cast<const char *>(rlist);
+  auto gather = [&](auto full_tag) {
+    constexpr bool FULL = decltype(full_tag)::value;
+    unsigned bits = 0;
+    if (FULL) {
+      constexpr unsigned G = 16, STEP = TS_GP_THREADS / 32;  // positions in flight; map words between two positions of a thread
+      const uint32_t *bm_t = rm.bm + (tid >> 5);
+      const uint16_t *wpre_t = rm.wpre + (tid >> 5);
+      uint16_t *vals_t = vals + tid;
+      const uint32_t below = 0xFFFFFFFFu >> (31u - (tid & 31u));
+      unsigned p0 = tid;  // the first of the sixteen positions
+#pragma unroll 1
+      for (unsigned kk = 0; kk < TS_TILE / TS_GP_THREADS / G; kk++, bm_t += G * STEP, wpre_t += G * STEP, vals_t += G * TS_GP_THREADS, p0 += G * TS_GP_THREADS) {
+        unsigned v[G];
+        if (in_lds) {
+#pragma unroll
+          for (unsigned j = 0; j < G; j++) {
+            const unsigned run1 = k6_popc_add(bm_t[STEP * j] & below, wpre_t[STEP * j]);
+            v[j] = *reinterpret_cast<const uint16_t *>(out16_b + (2u * p0 + 2u * TS_GP_THREADS * j + gd[run1]));
+          }
+        } else {
+#pragma unroll
+          for (unsigned j = 0; j < G; j++) {
+            const unsigned run1 = k6_popc_add(bm_t[STEP * j] & below, wpre_t[STEP * j]);
+            const uint2 r = *reinterpret_cast<const uint2 *>(rlist_b + ((run1 << 3) - 8u));
+            const unsigned slot = r.x + (p0 + TS_GP_THREADS * j - (r.y & 0xFFFFu));
+            v[j] = *reinterpret_cast<const uint16_t *>(out16_b + (slot << 1));
+          }
+        }
+#pragma unroll
+        for (unsigned j = 0; j < G; j++) {
+          vals_t[TS_GP_THREADS * j] = (uint16_t)v[j];
+          bits += v[j] >> 12;
+        }
+      }
+    } else if (in_lds) {
+#pragma unroll 4
+      for (unsigned p = tid; p < nt; p += TS_GP_THREADS) {
+        const unsigned v = *reinterpret_cast<const uint16_t *>(out16_b + (2u * p + gd[ts_run_of(rm, p) + 1u]));
+        vals[p] = (uint16_t)v;
+        bits += v >> 12;
+      }
+    } else {
+#pragma unroll 4
+      for (unsigned p = tid; p < nt; p += TS_GP_THREADS) {
+        const uint2 r = rlist[ts_run_of(rm, p)];
+        const unsigned v = out16[r.x + (p - (r.y & 0xFFFFu))];
+        vals[p] = (uint16_t)v;
+        bits += v >> 12;
+      }
     }
-  } else {
-#pragma unroll 8
-    for (unsigned p = tid; p < nt; p += TS_GP_THREADS) {
-      const uint2 r = rlist[ts_run_of(rm, p)];
-      const unsigned v = out16[r.x + (p - (r.y & 0xFFFFu))];
-      vals[p] = (uint16_t)v;
-      bits += v >> 12;
-    }
-  }
+    return bits;
+  };
+  const unsigned bits = full ? gather(TsFlag<true>{}) : gather(TsFlag<false>{});
   unsigned tile_bits;
-  (void)ts_block_scan<TS_GP_THREADS>(bits, wsum, &tile_bits);  // (also the barrier behind the stores to vals)
+  (void)k6_block_scan(bits, wsum, &tile_bits);  // (also the barrier behind the stores to vals)
   TS_PROF(PS + 1);
   // ---- bit offset of the tile
   if (wave == 0) {
@@ -561,10 +668,12 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
         }
         const unsigned long long incl_mask = __ballot((st >> 62) == 2ull);
         const unsigned stop = incl_mask ? (unsigned)__ffsll((long long)incl_mask) - 1u : 64u;  // nearest inclusive total
-        unsigned long long v = lane <= stop ? (st & TS_VAL_MASK) : 0ull;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-        excl += v;
+        // the aggregates in front of it: a tile's total is below 2^19, sixty-four of them fit 32 bits; the inclusive total (62 bits) is one lane's
+        excl += (unsigned long long)k6_readlane(k6_wave_scan(lane < stop ? (unsigned)st : 0u), 63u);
+        if (incl_mask) {
+          const unsigned long long iv = st & TS_VAL_MASK;
+          excl += (unsigned long long)k6_readlane((unsigned)iv, stop) | ((unsigned long long)k6_readlane((unsigned)(iv >> 32), stop) << 32);
+        }
         if (incl_mask || first < 64) break;
         first -= 64;
       }
@@ -594,73 +703,74 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
   const unsigned first_word = (unsigned)(s_base >> 5);
   const bool first_shared = (s_base & 31ull) != 0;
   unsigned carry = 0;  // (uniform) this tile's bits in the word that holds bit `cursor`, when cursor is not on a word boundary
-  // ---- packing, TS_SUB symbols per round: thread t owns 16 consecutive symbols
+  // ---- packing, TS_SUB symbols per round: thread t owns 8 consecutive symbols
   // (the positions of the next round are requested before the current one is packed)
-  constexpr unsigned PPT = TS_GP_PPT, Q4 = PPT / 8;  // 16-byte pieces of positions per thread and round
-  const uint4 *lp4 = reinterpret_cast<const uint4 *>(lpos16 + e0 + tid * PPT);
-  uint4 nx[Q4];
+  auto pack_rounds = [&](auto full_tag) {
+    constexpr bool FULL = decltype(full_tag)::value;
+    constexpr unsigned PPT = TS_GP_PPT;
+    const unsigned n_here = FULL ? TS_TILE : nt;
+    const uint4 *lp4 = reinterpret_cast<const uint4 *>(lpos16 + e0 + tid * PPT);
+    uint4 nx = FULL || tid * PPT < nt ? lp4[0] : make_uint4(0, 0, 0, 0);
+#pragma unroll 1
+    for (unsigned s0 = 0; s0 < n_here; s0 += TS_SUB) {
+      for (unsigned i = tid; i < NW; i += TS_GP_THREADS) words[i] = i == 0 ? carry : 0u;
+      const unsigned el = s0 + tid * PPT;  // local encode index of the thread's first symbol
+      const uint4 c4 = nx;
+      if (FULL ? s0 + TS_SUB < TS_TILE : el + TS_SUB < nt) nx = lp4[(s0 + TS_SUB) / 8];
+      const unsigned lp[PPT] = {c4.x & 0xFFFFu, c4.x >> 16, c4.y & 0xFFFFu, c4.y >> 16, c4.z & 0xFFFFu, c4.z >> 16, c4.w & 0xFFFFu, c4.w >> 16};
+      unsigned v[PPT];
 #pragma unroll
-  for (unsigned q = 0; q < Q4; q++) nx[q] = tid * PPT < nt ? lp4[q] : make_uint4(0, 0, 0, 0);
-  for (unsigned s0 = 0; s0 < nt; s0 += TS_SUB) {
-    for (unsigned i = tid; i < NW; i += TS_GP_THREADS) words[i] = i == 0 ? carry : 0u;
-    const unsigned el = s0 + tid * PPT;  // local encode index of the thread's first symbol
-    unsigned v[PPT];
-    unsigned tb = 0;
-    {
-      uint4 cur4[Q4];
+      for (unsigned i = 0; i < PPT; i++) v[i] = FULL || el + i < nt ? (unsigned)vals[lp[i]] : 0u;
+      // The thread's eight codes as ONE string of at most 96 bits, with no test for a word crossing per symbol: pairs in
+      // 32 bits (at most 24), pairs of pairs in 64 (at most 48), the two halves in 96.  A code has no bit at or above its length.
+      unsigned pb[4], pn[4];
 #pragma unroll
-      for (unsigned q = 0; q < Q4; q++) cur4[q] = nx[q];
-      if (el + TS_SUB < nt) {
-        const uint4 *n4 = lp4 + (s0 + TS_SUB) / 8;
-#pragma unroll
-        for (unsigned q = 0; q < Q4; q++) nx[q] = n4[q];
+      for (unsigned j = 0; j < 4; j++) {
+        const unsigned n0 = v[2 * j] >> 12;
+        pb[j] = (v[2 * j] & 0xFFFu) | ((v[2 * j + 1] & 0xFFFu) << n0);
+        pn[j] = n0 + (v[2 * j + 1] >> 12);
       }
-#pragma unroll
-      for (unsigned i = 0; i < PPT; i++) {
-        const uint4 c4 = cur4[i >> 3];
-        const unsigned w2 = ((i >> 1) & 3u) == 0 ? c4.x : ((i >> 1) & 3u) == 1 ? c4.y : ((i >> 1) & 3u) == 2 ? c4.z : c4.w;
-        const unsigned lp = (w2 >> (16 * (i & 1))) & 0xFFFFu;
-        v[i] = el + i < nt ? (unsigned)vals[lp] : 0u;
-        tb += v[i] >> 12;
+      const unsigned long long q0 = (unsigned long long)pb[0] | ((unsigned long long)pb[1] << pn[0]);
+      const unsigned long long q1 = (unsigned long long)pb[2] | ((unsigned long long)pb[3] << pn[2]);
+      const unsigned qn0 = pn[0] + pn[1], tb = qn0 + pn[2] + pn[3];
+      const unsigned long long lo = q0 | (q1 << qn0);                        // bits 0 .. 63
+      const unsigned hi = (unsigned)((q1 >> 16) >> (48u - qn0));             // bits 64 .. 95 (q1 >> (64 - qn0), qn0 = 0 .. 48)
+      unsigned sub_bits;
+      unsigned off = k6_block_scan(tb, wsum, &sub_bits);  // (its barrier also orders the zeroing of words)
+      const unsigned long long b0 = cursor, b1 = cursor + sub_bits;
+      off += (unsigned)(b0 & 31ull);
+      // ... shifted to its place: four words of the round's buffer, each ORed in unless it is empty
+      // (OR-ing nothing is left out: on data that codes in a fraction of a bit per symbol all threads of a wave would meet on one word)
+      const unsigned sh = off & 31u, w = off >> 5;
+      const unsigned long long mid = ((unsigned long long)hi << 32) | (lo >> 32);
+      const unsigned long long x0 = lo << sh;
+      const unsigned o0 = (unsigned)x0, o1 = (unsigned)(x0 >> 32), o2 = (unsigned)((mid << sh) >> 32), o3 = (unsigned)(((unsigned long long)hi << sh) >> 32);
+      if (o0) atomicOr(&words[w], o0);
+      if (o1) atomicOr(&words[w + 1u], o1);
+      if (o2) atomicOr(&words[w + 2u], o2);
+      if (o3) atomicOr(&words[w + 3u], o3);
+      __syncthreads();
+      {
+        const unsigned long long gw0 = b0 >> 5;
+        const unsigned nw = (unsigned)(((b1 + 31ull) >> 5) - gw0);   // words that hold bits of this tile up to b1 (word 0: the carry's)
+        const bool tail_open = (b1 & 31ull) != 0;
+        const unsigned n_final = tail_open ? nw - 1u : nw;           // ... and are complete as far as this tile goes
+        const bool fits = (gw0 + nw) * 4ull <= cap + 32ull;  // (the buffer has 64 spare bytes; an overflowing stream is discarded)
+        const unsigned next_carry = tail_open ? words[nw - 1u] : 0u;
+        if (fits) {
+          for (unsigned i = tid; i < n_final; i += TS_GP_THREADS) {
+            const unsigned gw = (unsigned)gw0 + i;
+            if (gw == first_word && first_shared) { edges[tile].x = gw; edges[tile].y = words[i]; }  // (one thread, once per tile)
+            else out[gw] = words[i];
+          }
+        } else if (tid == 0) atomicOr(&res->overflow, 1u);
+        carry = next_carry;
       }
+      cursor = b1;
+      __syncthreads();  // words are rewritten by the next round
     }
-    unsigned sub_bits;
-    unsigned off = ts_block_scan<TS_GP_THREADS>(tb, wsum, &sub_bits);  // (its barriers also order the zeroing of words)
-    const unsigned long long b0 = cursor, b1 = cursor + sub_bits;
-    off += (unsigned)(b0 & 31ull);
-    unsigned long long acc = 0;
-    unsigned nacc = off & 31u, w = off >> 5;
-#pragma unroll
-    for (unsigned i = 0; i < PPT; i++) {
-      const unsigned nb = v[i] >> 12;
-      acc |= (unsigned long long)(v[i] & 0xFFFu) << nacc;
-      nacc += nb;
-      if (nacc >= 32) {
-        if ((uint32_t)acc) atomicOr(&words[w], (uint32_t)acc);  // (OR-ing nothing is left out: on data that codes in a fraction of a bit per
-        acc >>= 32; nacc -= 32; w++;                            //  symbol all threads of a wave would meet on one word)
-      }
-    }
-    if ((uint32_t)acc) atomicOr(&words[w], (uint32_t)acc);
-    __syncthreads();
-    {
-      const unsigned long long gw0 = b0 >> 5;
-      const unsigned nw = (unsigned)(((b1 + 31ull) >> 5) - gw0);   // words that hold bits of this tile up to b1 (word 0: the carry's)
-      const bool tail_open = (b1 & 31ull) != 0;
-      const unsigned n_final = tail_open ? nw - 1u : nw;           // ... and are complete as far as this tile goes
-      const bool fits = (gw0 + nw) * 4ull <= cap + 32ull;  // (the buffer has 64 spare bytes; an overflowing stream is discarded)
-      const unsigned next_carry = tail_open ? words[nw - 1u] : 0u;
-      if (fits) {
-        for (unsigned i = tid; i < n_final; i += TS_GP_THREADS) {
-          const unsigned gw = (unsigned)gw0 + i;
-          if (gw == first_word && first_shared) { edges[tile].x = gw; edges[tile].y = words[i]; }  // (one thread, once per tile)
-          else out[gw] = words[i];
-        }
-      } else if (tid == 0) atomicOr(&res->overflow, 1u);
-      carry = next_carry;
-    }
-    cursor = b1;
-    __syncthreads();  // words are rewritten by the next round
-  }
+  };
+  if (full) pack_rounds(TsFlag<true>{}); else pack_rounds(TsFlag<false>{});
   if (tid == 0 && (cursor & 31ull) != 0 && (cursor >> 5) * 4ull + 4ull <= cap + 32ull) {  // the open last word: shared with whatever follows
     const unsigned gw = (unsigned)(cursor >> 5);
     if (gw == first_word && first_shared) { edges[tile].x = gw; edges[tile].y = carry; }  // the whole tile inside one word
