@@ -149,6 +149,11 @@ _PROTOS = {
     "fqgpu_chunk_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                       C.c_void_p, C.c_void_p]),
+    "fqgpu_trim_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_trim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_trim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -328,6 +333,39 @@ def _filter_call(fn, front, flt, n_recs, out_cap=None, want_keep=True, query=Fal
     return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep)
 
 
+TRIM_REPORT_WORDS = 16
+TRIM_REPORT_NAMES = FILTER_REPORT_NAMES + ("reads_trimmed", "bases_cut_front", "bases_cut_tail", "reads_emptied")
+
+
+def read_trim(cut_front=0, cut_tail=0, q_front=0, q_tail=0, crop=FILTER_NONE, reserved=(0, 0, 0)):
+    """an fqgpu_trim (include/fqgpu.h) as a uint32 array of eight words; the defaults cut nothing"""
+    return np.array([cut_front, cut_tail, q_front, q_tail, crop, reserved[0], reserved[1], reserved[2]], dtype=np.uint32)
+
+
+def trim_check(trim):
+    """fqgpu_trim_check -> rc (host only)"""
+    return lib().fqgpu_trim_check(_p(trim))
+
+
+def _trim_call(fn, front, trim, flt, n_recs, out_cap=None, want_keep=True, want_win=True, query=False):
+    """A device trim call -> dict(rc, out, out_len, report, keep, win): _filter_call's dict plus the records' windows
+    (start | n << 16).  flt None: a NULL filter.  out_cap, query: as _filter_call."""
+    report = np.zeros(TRIM_REPORT_WORDS, dtype=np.uint64)
+    keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
+    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
+    n = C.c_size_t(0)
+    trim = np.ascontiguousarray(trim, dtype=np.uint32)
+    flt = None if flt is None else np.ascontiguousarray(flt, dtype=np.uint32)
+    if out_cap is None:
+        rc = fn(*front, _p(trim), _p(flt), None, 0, C.byref(n), _p(report), _p(keep), _p(win))
+        if rc != 0 or query:
+            return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep, win=win)
+        out_cap = n.value
+    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
+    rc = fn(*front, _p(trim), _p(flt), _p(out), out_cap, C.byref(n), _p(report), _p(keep), _p(win))
+    return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep, win=win)
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -438,6 +476,12 @@ class DBlock:
         dict(rc, out, out_len, report, keep); see _filter_call"""
         return _filter_call(lib().fqgpu_dblock_filter, (self.ctx.h, self.h), flt, self.n_recs, **kw)
 
+    def trim(self, trim, flt=None, **kw):
+        """fqgpu_dblock_trim: the reads of the raw block, as it lies on the device, trimmed by `trim` (read_trim) and then
+        judged by `flt` (read_filter; None: every read that is not emptied is kept) -> dict(rc, out, out_len, report, keep,
+        win); see _trim_call"""
+        return _trim_call(lib().fqgpu_dblock_trim, (self.ctx.h, self.h), trim, flt, self.n_recs, **kw)
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -543,6 +587,11 @@ class Context:
         """fqgpu_chunk_filter: the reads of the chunk on the staging block (n_recs records) that pass `flt`, where chunk_stats
         is valid -> dict(rc, out, out_len, report, keep); see _filter_call"""
         return _filter_call(lib().fqgpu_chunk_filter, (self.h,), flt, n_recs, **kw)
+
+    def chunk_trim(self, trim, n_recs, flt=None, **kw):
+        """fqgpu_chunk_trim: the reads of the chunk on the staging block (n_recs records) trimmed by `trim` and then judged by
+        `flt`, where chunk_filter is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
+        return _trim_call(lib().fqgpu_chunk_trim, (self.h,), trim, flt, n_recs, **kw)
 
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""

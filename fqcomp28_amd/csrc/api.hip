@@ -536,6 +536,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->crc.release();
   ctx->stats.release();
   ctx->filter.release();
+  ctx->trim.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1706,4 +1707,37 @@ extern "C" int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const 
   // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
   if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
   return fq_filter_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, f, out, out_cap, out_len, report, keep_out);
+}
+
+// ------------------------------------------------------------------ the reads of a chunk in HBM, trimmed and then filtered (trim.hip)
+// Shared front of the two calls, as filter_args; *keep: the filter to judge by (a NULL filter keeps everything).
+static int trim_args(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, size_t *out_len, uint64_t *report, fqgpu_filter *keep) {
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  if (out_len) *out_len = 0;
+  if (report) memset(report, 0, FQGPU_TRIM_REPORT_WORDS * sizeof(uint64_t));
+  if (!ctx || !out_len || !report || fqgpu_trim_check(t) != FQGPU_OK || (f && fqgpu_filter_check(f) != FQGPU_OK)) return FQGPU_E_ARG;
+  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
+  *keep = f ? *f : all;
+  return FQGPU_OK;
+}
+
+// As fqgpu_chunk_filter: on the handle's copy stream, beside the lane's encode or behind the decode.
+extern "C" int fqgpu_chunk_trim(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                                uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
+  fqgpu_filter keep;
+  if (const int rc = trim_args(ctx, t, f, out_len, report, &keep)) return rc;
+  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
+  const fqgpu_dblock *b = ctx->hp_block;
+  return fq_trim_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, t, &keep, out, out_cap, out_len, report, keep_out, win_out);
+}
+
+extern "C" int fqgpu_dblock_trim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out,
+                                 size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
+  fqgpu_filter keep;
+  int rc = trim_args(ctx, t, f, out_len, report, &keep);
+  if (rc) return rc;
+  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
+  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
+  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  return fq_trim_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, t, &keep, out, out_cap, out_len, report, keep_out, win_out);
 }

@@ -88,6 +88,14 @@ extern "C" int fqgpu_filter_check(const fqgpu_filter *f) {
   return FQGPU_OK;
 }
 
+// Read trimming (trim.hip applies it): what a trim may say.
+extern "C" int fqgpu_trim_check(const fqgpu_trim *t) {
+  if (!t || t->cut_front > 65535u || t->cut_tail > 65535u || t->q_front > 64u || t->q_tail > 64u || t->crop == 0u || t->reserved[0] ||
+      t->reserved[1] || t->reserved[2])
+    return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

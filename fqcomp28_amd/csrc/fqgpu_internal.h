@@ -243,6 +243,14 @@ struct FilterScratch {
   void release();
 };
 
+// Trimmed and filtered reads of a chunk in HBM (trim.hip): FilterScratch's buffers and the records' windows; its own, so that a
+// filter call and a trim call on one handle do not disturb each other
+struct TrimScratch {
+  DevBuf ksize, hstart, win, keep, koff, dst, res, scan_tmp;
+  void *host = nullptr;
+  void release();
+};
+
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
@@ -293,6 +301,7 @@ struct fqgpu_ctx {
   CrcScratch crc;
   StatsScratch stats;
   FilterScratch filter;
+  TrimScratch trim;
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -439,6 +448,12 @@ int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
 // keep_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes into out
 int fq_filter_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out);
+
+// The reads of a chunk in HBM trimmed by *t and then judged by *f (trim.hip; both have passed their checks), on st, waited for:
+// report (FQGPU_TRIM_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
+int fq_trim_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                  const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
+                  uint8_t *keep_out, uint32_t *win_out);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

@@ -681,6 +681,54 @@ public:
     clk.done(cbs.chunk_idx);
   }
 
+  /** Extension: the reads of the chunk trimmed by `trim` and then judged by `filter` (nullptr: every read that is not emptied
+   *  is kept), as trimmed canonical FASTQ bytes, into piece.raw_data (fqgpu_chunk_trim); `report` receives the chunk's
+   *  FQGPU_TRIM_REPORT_WORDS counters.  Works as decodeChunkFiltered does: the chunk is decoded check-only with the block's
+   *  decode indexes when present, the digest of the WHOLE restored chunk is taken first and kept for lastDigest() when
+   *  setVerify is on, and one call fills a buffer of the chunk's recorded size, which is always enough.  No host fallback: a
+   *  chunk the device refuses throws std::runtime_error naming the chunk and the record. */
+  void decodeChunkTrimmed(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim &trim, const fqgpu_filter *filter, uint64_t *report) {
+    StageClock clk;
+    last_digest_ = {};
+    const auto refused = [&](const std::string &what) {
+      return std::runtime_error("decodeChunkTrimmed: chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
+    };
+    if (fqgpu_trim_check(&trim) != FQGPU_OK) throw std::invalid_argument("decodeChunkTrimmed: a trim fqgpu_trim_check refuses");
+    if (filter && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument("decodeChunkTrimmed: a filter fqgpu_filter_check refuses");
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
+    clk.lap("misc");
+    piece.clear();
+    piece.idx = cbs.chunk_idx;
+    // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
+    struct CheckOnly {
+      fqgpu_ctx *ctx;
+      bool restore;
+      ~CheckOnly() { if (restore) (void)fqgpu_ctx_set_check_only(ctx, 0); }
+    } mode{ctx_, !check_only_};
+    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, 1), "decodeChunkTrimmed");
+    RecordTable recs(a.n_recs);
+    std::size_t laid_out = 0, bad = 0;
+    const StreamArgs &s = a.s;
+    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
+                                      s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], nullptr,
+                                      cbs.original_size.total, recs.data(), &laid_out, &bad);
+    if (rc != FQGPU_OK)
+      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
+                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
+    clk.lap("gpu");
+    takeDigest();
+    // a trimmed record is never longer than the record: one call, no size query
+    piece.raw_data.resize(cbs.original_size.total);
+    std::size_t len = 0;
+    const int trc = fqgpu_chunk_trim(ctx_, &trim, filter, reinterpret_cast<uint8_t *>(piece.raw_data.data()), piece.raw_data.size(), &len,
+                                     report, nullptr, nullptr);
+    if (trc != FQGPU_OK) throw refused(std::string("the trim: ") + fqgpu_strerror(trc));
+    piece.raw_data.resize(len);
+    clk.lap("trim");
+    clk.done(cbs.chunk_idx);
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */

@@ -512,6 +512,55 @@ int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size
 int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
                         size_t *out_len, uint64_t *report, uint8_t *keep_out);
 
+/* ---- Extension (nothing in the reference): the reads of a chunk TRIMMED, then filtered, where the chunk lies already -- in
+ * HBM.  What every QC tool does beside dropping reads: cut a fixed number of bases from either end, cut low-quality ends by
+ * the running-sum rule (BWA -q, cutadapt -q), crop to a maximum length; the criteria of an fqgpu_filter are then applied to
+ * what is left.  For a read of length L with Phred values p[i] = quality byte - 33, integer arithmetic throughout:
+ *   1 fixed cuts     f = min(cut_front, L), t = min(cut_tail, L - f): the interval [f, L - t)
+ *   2 front (q_front on)  start = f; walk i = f .. L-t-1 with s = 0, best = 0: s += q_front - p[i]; s < 0: stop;
+ *                    s > best (strictly): best = s, start = i + 1
+ *   3 tail (q_tail on)    stop = L - t; walk i = L-t-1 .. f downwards with s = 0, best = 0: s += q_tail - p[i]; s < 0: stop;
+ *                    s > best (strictly): best = s, stop = i
+ *   4 the two walks are independent, both over the interval of step 1.  start >= stop: the read is EMPTY, its window (0, 0).
+ *                    Otherwise n = min(stop - start, crop) and the read's window is (start, n)
+ *   5 the filter     judged on the trimmed read: its length n, the N of seq[start, start+n), Phred sum and low count of
+ *                    qual[start, start+n); comparisons and order of the first failing criterion as fqgpu_chunk_filter.  A NULL
+ *                    filter keeps everything.  An emptied read is always dropped: counted under dropped_short whatever
+ *                    min_len is, and under reads_emptied
+ * The output, in input order, per kept record: the header line byte for byte with its '\n', seq[start, start+n), "\n+\n",
+ * qual[start, start+n), '\n'; text behind a '+' is dropped, N stays N.  With a trim that cuts nothing (all fields off) the
+ * output, report words 0 .. 9 and the keep bits are those of fqgpu_*_filter with the same filter.
+ *   report  FQGPU_TRIM_REPORT_WORDS uint64_t: 0 .. 9 as the filter's report (bases_in counts untrimmed lengths, bases_kept the
+ *           n of kept reads) | 10 reads_trimmed (n != L, kept or not) | 11 bases_cut_front (sum of start) | 12 bases_cut_tail
+ *           (sum of L - start - n; all L of an emptied read) | 13 reads_emptied | 14, 15 zero.  Words 11 and 12 run over ALL
+ *           records: bases_in = word 11 + word 12 + the sum of n over all records.  Reports of several chunks add word by word.
+ *   out == NULL, out_cap < *out_len, keep_out   as fqgpu_chunk_filter
+ *   win_out               NULL, or n_recs words: start | n << 16 of every record, kept or not
+ * The sequence line is read iff max_n is on, the quality line iff q_front, q_tail, min_mean_q or low_q is on; a line that is
+ * read is judged over ALL L bytes, the cut ones too, by the filter's rules (ACGTN; 33 .. 96: FQGPU_E_ARG), a line that is not
+ * read is not looked at: fixed cuts and crop with length criteria alone touch the record table only.  A record outside the
+ * chunk, or of length 0: FQGPU_E_ARG.  A trim fqgpu_trim_check refuses (a cut above 65535, a cutoff above 64, crop 0,
+ * reserved not zero), a filter fqgpu_filter_check refuses, a NULL where data is expected: FQGPU_E_ARG.  Every FQGPU_E_ARG
+ * comes with *out_len = 0, a zeroed report and -- where the chunk itself is refused -- zeroed keep bits and windows.
+ *   fqgpu_trim_check    host only: FQGPU_OK or FQGPU_E_ARG
+ *   fqgpu_chunk_trim    the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_filter is valid,
+ *                       on the same stream.  It leaves the chunk as it is: digest, summary and a plain filter before or after
+ *                       give the same results, and it shares no scratch with the filter calls.
+ *   fqgpu_dblock_trim   waits for the block's last operation as fqgpu_dblock_filter does.
+ * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_trim_check works. */
+typedef struct {
+  uint32_t cut_front, cut_tail;  /* bases removed from the 5' / 3' end first; each <= 65535 */
+  uint32_t q_front, q_tail;      /* running-sum quality trim of the 5' / 3' end; 0 = off; <= 64 */
+  uint32_t crop;                 /* keep at most this many bases, counted from the new front; FQGPU_FILTER_NONE = off; 0 refused */
+  uint32_t reserved[3];          /* zero */
+} fqgpu_trim;
+#define FQGPU_TRIM_REPORT_WORDS 16
+int fqgpu_trim_check(const fqgpu_trim *t);
+int fqgpu_chunk_trim(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                     uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
+int fqgpu_dblock_trim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
+                      size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

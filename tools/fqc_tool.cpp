@@ -24,6 +24,13 @@
 //               written -- when they lie there.  A filter with c, x, t or s, with --records, --fasta, --index or --index-stride,
 //               a value out of range and a malformed Q:PCT are usage errors.  A failed run leaves neither <out.fastq> nor
 //               <out.fastq>.part)
+//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--cut-front N] [--cut-tail N] [--trim-q5 Q] [--trim-q3 Q] [--crop L]
+//              (extension: any of these restores the reads TRIMMED, with or without the filter options, which then judge what
+//               is left: N bases cut from the 5' / the 3' end first, then the low-quality 5' / 3' end cut by the running-sum
+//               rule of BWA -q / cutadapt -q with cutoff Q, then at most L bases kept from the new front.  A read of which
+//               nothing is left is dropped.  Trimmed and gathered on the device as the filter is, .fqx used and .fqs verified
+//               the same way.  A trim option with c, x, t or s, with --records, --fasta, --index or --index-stride, N above
+//               65535, Q above 64 and --crop 0 are usage errors.  A failed run leaves neither <out.fastq> nor <out.fastq>.part)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -50,7 +57,8 @@
 // sums file, the blocks whose digest was compared and held, the whole file's CRC-32; with --fasta also "form": "fasta" and the
 // bytes read of the archive; with a report "stats": its path, "bases" and "mean_quality" (total Phred / bases, the one
 // number that is no integer and in no report); with a filter "filter": what was read, what was kept and what each
-// criterion dropped ("records" / "raw_bytes" of the line are then what was written).  Needs a GPU: no CPU fallback.
+// criterion dropped ("records" / "raw_bytes" of the line are then what was written); with a trim "trim": the same and the
+// reads trimmed, the bases cut from either end and the reads emptied.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -67,6 +75,7 @@ int main(int argc, char **argv) {
   if (argc < (one_arg ? 3 : 4) || (strcmp(argv[1], "c") && strcmp(argv[1], "d") && !one_arg && !stats_cmd)) {
     std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B] [--stats report.tsv [--positions P]]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--min-len N] [--max-len N] [--max-n K] [--min-mean-q Q] [--max-low-q Q:PCT]\n"
+                         "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--cut-front N] [--cut-tail N] [--trim-q5 Q] [--trim-q3 Q] [--crop L] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
@@ -81,6 +90,8 @@ int main(int argc, char **argv) {
   std::size_t rec_a = 0, rec_b = SIZE_MAX;
   fqgpu_filter filter = {0, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0, 0, 0, {0, 0}};
   bool filtered = false;
+  fqgpu_trim trim = {0, 0, 0, 0, FQGPU_FILTER_NONE, {0, 0, 0}};
+  bool trimmed = false;
   // a decimal number of at most nine digits (so that it fits a uint32_t)
   const auto u32 = [](const std::string &t, uint32_t &out) {
     if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
@@ -116,6 +127,16 @@ int main(int argc, char **argv) {
         return 2;
       }
       filtered = true;
+    }
+    else if (a == "--cut-front" || a == "--cut-tail" || a == "--trim-q5" || a == "--trim-q3" || a == "--crop") {
+      const std::string v = val();
+      uint32_t &field = a == "--cut-front" ? trim.cut_front : a == "--cut-tail" ? trim.cut_tail : a == "--trim-q5" ? trim.q_front
+                        : a == "--trim-q3" ? trim.q_tail : trim.crop;
+      if (!u32(v, field)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      trimmed = true;
     }
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
@@ -153,6 +174,14 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "the read filter: expected --min-len <= --max-len, --min-mean-q 0 .. 63, --max-low-q Q:PCT with Q 0 .. 64 and PCT 0 .. 100\n");
     return 2;
   }
+  if (trimmed && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "read trimming goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (trimmed && fqgpu_trim_check(&trim) != FQGPU_OK) {
+    std::fprintf(stderr, "read trimming: expected --cut-front and --cut-tail 0 .. 65535, --trim-q5 and --trim-q3 0 .. 64, --crop 1 or more\n");
+    return 2;
+  }
   // (said before any device is touched)
   if (stats_opt && argv[1][0] != 'c') {
     std::fprintf(stderr, "--stats goes with c alone (s <in.fqc> <report.tsv> summarises an archive): not with d, x, t or s\n");
@@ -176,6 +205,7 @@ int main(int argc, char **argv) {
     const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
+                         : trimmed ? processArchiveTrimmed(argv[2], argv[3], trim, filtered ? &filter : nullptr, set)
                          : filtered ? processArchiveFiltered(argv[2], argv[3], filter, set)
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
@@ -201,10 +231,17 @@ int main(int argc, char **argv) {
       std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
     }
     if (filtered) {
-      const auto w = [&](unsigned i) { return (unsigned long long)r.filter[i]; };
+      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
       std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
                   "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
                   w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
+    }
+    if (trimmed) {
+      const auto w = [&](unsigned i) { return (unsigned long long)r.trim[i]; };
+      std::printf(", \"trim\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
+                  "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
+                  "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu}",
+                  w(0), w(1), w(2), w(3), w(4), w(5), w(6), w(7), w(8), w(9), w(10), w(11), w(12), w(13));
     }
     if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
     std::printf("}\n");
