@@ -419,7 +419,7 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
              const uint32_t *__restrict__ rec_start, unsigned R, unsigned n_sym, unsigned T,
              uint16_t *__restrict__ tile_hist_seq, uint8_t *__restrict__ ckey_seq,
              uint16_t *__restrict__ tile_hist_qual, uint16_t *__restrict__ ckey_qual, uint8_t *__restrict__ first_seq,
-             uint8_t *__restrict__ first_qual, uint32_t *__restrict__ n_cnt32, BlockResult *res) {
+             uint8_t *__restrict__ first_qual, uint32_t *__restrict__ tile_first_rec, uint32_t *__restrict__ n_cnt32, BlockResult *res) {
   constexpr unsigned BS = SeqModel::B, BQ = QualModel::B;
   __shared__ uint32_t hist_s[BS];
   __shared__ uint32_t hist_q[BQ / 2];  // 16-bit counters, two per word (T <= 32768: they cannot wrap)
@@ -437,6 +437,7 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
   if (wb < we) {
     RecCache4 &rc = rcache[wave];
     unsigned r0 = fq_locate(rec_start, 0, R - 1, wb);
+    if (wave == 0 && lane == 0) tile_first_rec[tile] = r0;  // the record that holds the tile's first encode index: K3 starts its patch of the records' first symbols there
     for (;;) {
       // ---- window of 64 records: starts, the quads of every record that fall into [wb, we), their prefix sums
       fq_lds_wave_sync();  // nobody still reads the old window

@@ -27,7 +27,9 @@ constexpr unsigned TS_SUB = TS_GP_THREADS * TS_GP_PPT;  // symbols packed per ro
 static_assert(TS_GP_THREADS == 512 && TS_GP_PPT == 8, "K6 is written for 512 threads: eight waves in its scans, eight symbols (96 bits at most) per thread and packing round");
 static_assert(TS_TILE % TS_BATCH == 0 && TS_TILE % TS_SUB == 0 && TS_SUB % PACK_TILE == 0, "tile geometry");
 
-// phase timing of the two kernels (experiments build only): g_ts_prof[8 * kernel + phase] += wall clock ticks of workgroup thread 0
+// phase timing of the two kernels (experiments build only): g_ts_prof[8 * kernel + phase] += wall clock ticks of workgroup thread 0.
+// K3's phases: 0 entry (until batch 0 is in LDS), 1 ranking, 5 wait for the position stores, 2 run list, 6 patch of the records'
+// first symbols, 7 run map, 3 output; 4 = the ranking wave's loop alone.  K6's: 0 run map, 1 gather, 2 look-back, 3 packing.
 #ifdef FQGPU_EXPERIMENTS
 #define TS_PROF_DECL unsigned long long ts_t_ = wall_clock64();
 #define TS_PROF(slot) do { if (threadIdx.x == 0) { const unsigned long long n_ = wall_clock64(); atomicAdd(&g_ts_prof[slot], n_ - ts_t_); ts_t_ = n_; } } while (0)
@@ -96,7 +98,8 @@ __device__ __forceinline__ void ts_clear_bitmap(TsRunMap &m) {
 // ------------------------------------------------------------------ K3: stable partition, one workgroup per tile
 // Wave 0 ranks (key read, one lane-ordered atomic on the context's cursor, symbol written to its sorted
 // place in LDS, position stored to lpos16 -- stores only, nothing in the loop ever waits for global
-// memory); the other seven waves bring in the next batch of keys.  Then all waves write
+// memory); the other seven waves bring in the next batch of keys.  Whatever can be asked of global memory from the tile
+// number alone is asked for at entry (every wait here is exposed, nothing else fits on the CU).  Then all waves write
 // the tile's runs: position-major, so that consecutive lanes store consecutive bytes.
 // DERIVED: the keys are the contexts alone, as the fused K1 (k_tile_hist2) leaves them -- two bytes per quality symbol, ONE per
 // base --, and the symbol at encode index e is taken from the context at e - 1 (its low six bits / its top two: the position
@@ -109,7 +112,8 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
                  const uint16_t *__restrict__ tile_hist, const uint32_t *__restrict__ tile_base,
                  uint8_t *__restrict__ sorted_sym, uint16_t *__restrict__ lpos16, uint2 *__restrict__ runs,
                  uint32_t *__restrict__ run_count, unsigned long long *__restrict__ k6_status, unsigned *__restrict__ k6_counter,
-                 const uint32_t *__restrict__ rec_start, unsigned R, const uint8_t *__restrict__ first_sym) {
+                 const uint32_t *__restrict__ rec_start, unsigned R, const uint8_t *__restrict__ first_sym,
+                 const uint32_t *__restrict__ tile_first_rec) {
   constexpr unsigned B = M::B;
   constexpr bool QUAL = M::STREAM == 1;
   constexpr bool K8 = DERIVED && !QUAL;  // one byte per key in memory
@@ -144,7 +148,7 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
   // behind the run map, once the batch buffers are dead: the first GD_CAP runs' offsets "global slot - local position"
   constexpr unsigned GD_CAP = (sizeof(stage_raw) - sizeof(TsRunMap)) / 4;
   uint32_t *gd = reinterpret_cast<uint32_t *>(stage_raw + sizeof(TsRunMap));
-  __shared__ unsigned wsum[TS_WAVES], s_cnt[NCHUNK < 2 ? 2 : NCHUNK], s_nruns, s_max;
+  __shared__ unsigned wsum[TS_WAVES], s_cnt[NCHUNK < 2 ? 2 : NCHUNK], s_nruns, s_max, s_more;
   __shared__ uint32_t dummy[64];  // where the lanes of the combining ranker that are no run heads send their (empty) atomics
   uint16_t *cur16 = reinterpret_cast<uint16_t *>(cursor32);
   const unsigned tile = fq_xcd_tile(blockIdx.x, gridDim.x), tid = threadIdx.x, wave = tid >> 6, lane = fq_lane();
@@ -154,35 +158,6 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
   TS_PROF_DECL
   constexpr unsigned PS = QUAL ? 0 : 8; (void)PS;
 
-  // ---- local start of every context = exclusive scan of the tile's histogram row
-  {
-    uint32_t *h32 = reinterpret_cast<uint32_t *>(lsym);  // B * 4 <= TS_TILE bytes
-    static_assert(B * 4 <= TS_TILE, "histogram row fits the symbol staging area");
-    for (unsigned c = tid; c < B; c += TS_THREADS) h32[c] = hrow[c];
-    if (tid == 0) s_max = 0;
-    if (tid < 64) dummy[tid] = 0;
-    __syncthreads();
-    constexpr unsigned CPT = B >= TS_THREADS ? B / TS_THREADS : 1;  // contexts per thread
-    const unsigned c0 = tid * CPT;
-    unsigned sum = 0, mx = 0;
-    if (c0 < B)
-#pragma unroll
-      for (unsigned k = 0; k < CPT; k++) { sum += h32[c0 + k]; mx = max(mx, h32[c0 + k]); }
-    if (mx * 8u >= nt) atomicMax(&s_max, mx);  // (rare: only a context that holds an eighth of the tile reports)
-    unsigned tot;
-    unsigned run = ts_block_scan<TS_THREADS>(sum, wsum, &tot);
-    if (c0 < B) {
-#pragma unroll
-      for (unsigned k = 0; k < CPT; k++) {
-        const unsigned n = h32[c0 + k];
-        cur16[c0 + k] = (uint16_t)run;  // (own contexts only: no two threads share a word when CPT is even; CPT = 1: 16-bit stores)
-        run += n;
-      }
-    }
-    __syncthreads();  // h32 is dead: lsym may be written
-  }
-
-  TS_PROF(PS + 0);
   // ---- ranking, batch by batch
   const unsigned nbatch = (nt + TS_BATCH - 1) / TS_BATCH;
   // the loading waves (448 threads): thread mt owns the 16-byte key pieces mt and mt + 448 (eight symbols each) of
@@ -216,15 +191,21 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
     return k;
   };
   // piece `piece` of the batch that starts at encode index eb: its keys (K8: in .x, .y) and the dword in front of them
+  // (no branch around the dword in front of the block's very first piece: it is read from the piece itself and dropped --
+  // behind a branch the load is waited for on the spot, with everything requested before it)
   auto load_piece = [&](unsigned eb, unsigned piece, uint4 &k, unsigned &prev, uint2 &sy) {
+    const bool head = eb + 8u * piece == 0u;
     if (K8) {
       const uint2 v = reinterpret_cast<const uint2 *>(ckey8 + eb)[piece];
       k = make_uint4(v.x, v.y, 0u, 0u);
-      prev = eb + 8u * piece ? reinterpret_cast<const uint32_t *>(ckey8 + eb)[2 * (int)piece - 1] : 0u;
+      const unsigned p = reinterpret_cast<const uint32_t *>(ckey8 + eb)[head ? 0 : 2 * (int)piece - 1];
+      prev = head ? 0u : p;
     } else {
       k = reinterpret_cast<const uint4 *>(ckey + eb)[piece];  // 16-byte aligned; arrays are padded by a batch
-      if (DERIVED) prev = eb + 8u * piece ? reinterpret_cast<const uint32_t *>(ckey + eb)[4 * (int)piece - 1] : 0u;
-      else if (QUAL) sy = reinterpret_cast<const uint2 *>(csym + eb)[piece];
+      if (DERIVED) {
+        const unsigned p = reinterpret_cast<const uint32_t *>(ckey + eb)[head ? 0 : 4 * (int)piece - 1];
+        prev = head ? 0u : p;
+      } else if (QUAL) sy = reinterpret_cast<const uint2 *>(csym + eb)[piece];
     }
   };
   auto request = [&](unsigned j) {  // batch j -> registers (loaders)
@@ -265,21 +246,103 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
     finish_piece(j, mt);
     if (two) finish_piece(j, mt + NL);
   };
-  // Barrier of the batch loop: LDS traffic only.  __syncthreads() also drains vmcnt, i.e. the loaders would wait at
-  // every barrier for the batch they have just requested and for their position stores (fire and forget).
+  // Barrier of the batch loop: LDS traffic only, said in so many words (what __syncthreads() waits for beside the LDS is the
+  // compiler's choice): the loaders never wait here for the batch they have just requested or for their position stores.
   auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  {  // batch 0 by everybody, straight to LDS
-    for (unsigned i = tid; i < TS_BATCH / 8; i += TS_THREADS) {
-      uint4 k;
-      unsigned prev = 0;
-      uint2 sy = make_uint2(0, 0);
-      load_piece(e0, i, k, prev, sy);
-      kb4[0][i] = keys16_of(k);
-      sb8[0][i] = syms_for(k, prev, sy);
+  // Barrier that also waits for the wave's own global stores (__syncthreads() waits for LDS only on this target): what
+  // another wave of the workgroup reads back from global memory behind it has arrived.
+  auto full_barrier = [] { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+
+  // ---- entry: everything whose address depends on the tile number alone is requested HERE, in front of any wait -- the
+  // histogram row, batch 0 (everybody), batch 1 (the loaders), and the starts and first symbols of the records that start
+  // in the tile.  One round trip to global memory (row -> barrier -> scan -> batch 0 were three in a row, the record
+  // search behind the ranking twenty more): no other workgroup's waves fit beside this one's to hide them.
+  static_assert(TS_BATCH / 8 == TS_THREADS, "batch 0: one piece per thread");
+  constexpr unsigned CPT = B >= TS_THREADS ? B / TS_THREADS : 1;  // contexts per thread
+  static_assert(CPT == 1 || CPT % 8 == 0, "histogram row: one entry per thread or 16-byte loads");
+  constexpr unsigned HQ = CPT == 1 ? 1 : CPT / 8;
+  const unsigned c0 = tid * CPT;
+  // DERIVED: record fr + tid, where fr holds the tile's first encode index (K1 had it in a register: tile_first_rec; without
+  // it, found here): a record that starts in the tile leaves local index and first symbol in pf.  Record fr itself may
+  // start in front of the tile, the later ones behind it: those leave nothing.
+  unsigned fr = 0, pf_e = 0xFFFFFFFFu, pf_s = 0;
+  if (DERIVED) fr = *(tile_first_rec != nullptr ? tile_first_rec + tile : rec_start);  // (one load either way; without the array the search below replaces it)
+  // (no branch around a load, and the order pinned: behind a branch hipcc waits for everything in flight, and it moves a
+  // dependent load -- the record's start needs fr -- in front of independent ones, which then wait for it)
+  auto pin = [] { asm volatile("" ::: "memory"); };
+  pin();
+  uint4 hq[HQ];
+  unsigned h1 = 0;
+  if (CPT == 1) h1 = hrow[min(c0, B - 1u)];
+  else
+#pragma unroll
+    for (unsigned k = 0; k < HQ; k++) hq[k] = reinterpret_cast<const uint4 *>(hrow + c0)[k];  // (the row is 2 B bytes, B a multiple of 8 * TS_THREADS)
+  uint4 bk;
+  unsigned bprev = 0;
+  uint2 bsy = make_uint2(0, 0);
+  load_piece(e0, tid, bk, bprev, bsy);
+  {  // batch 1 into the loaders' registers -- by everybody and always, for the same reason: the ranking wave and a tile of one
+    // batch read pieces of batch 0 again and drop them
+    const unsigned eb = e0 + (nbatch > 1 ? TS_BATCH : 0u), m0 = wave ? mt : 0u;
+    load_piece(eb, m0, rk0, rp0, rs0);
+    load_piece(eb, two && wave ? mt + NL : m0, rk1, rp1, rs1);
+  }
+  pin();
+
+  // ---- local start of every context = exclusive scan of the tile's histogram row (thread t: contexts CPT t ..)
+  {
+    if (tid == 0) s_max = 0;
+    if (tid < 64) dummy[tid] = 0;
+    unsigned h[CPT];
+    if (CPT == 1) h[0] = c0 < B ? h1 : 0u;
+    else
+#pragma unroll
+      for (unsigned k = 0; k < CPT; k++) {
+        const uint4 q = hq[k / 8];
+        const unsigned w = (k & 7u) < 2 ? q.x : (k & 7u) < 4 ? q.y : (k & 7u) < 6 ? q.z : q.w;
+        h[k] = (k & 1u) ? w >> 16 : w & 0xFFFFu;
+      }
+    unsigned sum = 0, mx = 0;
+#pragma unroll
+    for (unsigned k = 0; k < CPT; k++) { sum += h[k]; mx = max(mx, h[k]); }
+    if (DERIVED) {  // fr is here (it was asked for first): the record's start and first symbol travel while the row is scanned
+      if (tile_first_rec == nullptr) {  // (uniform)
+        unsigned lo = 0, hi = R;  // first record with rec_start >= e0
+        while (lo < hi) {
+          const unsigned mid = (lo + hi) >> 1;
+          if (rec_start[mid] < e0) lo = mid + 1; else hi = mid;
+        }
+        fr = lo;
+      }
+      const unsigned ri = min(fr + tid, R - 1u);
+      pin();
+      pf_e = rec_start[ri];
+      pf_s = first_sym[ri];
+      pin();
+      if (fr + tid >= R) pf_e = 0xFFFFFFFFu;
+    }
+    unsigned tot;
+    unsigned run = ts_block_scan<TS_THREADS>(sum, wsum, &tot);  // (its barriers: s_max and dummy are zero behind them)
+    if (mx * 8u >= nt) atomicMax(&s_max, mx);  // (rare: only a context that holds an eighth of the tile reports)
+    if (c0 < B) {
+#pragma unroll
+      for (unsigned k = 0; k < CPT; k++) {
+        cur16[c0 + k] = (uint16_t)run;  // (own contexts only: no two threads share a word when CPT is even; CPT = 1: 16-bit stores)
+        run += h[k];
+      }
     }
   }
-  if (wave != 0 && nbatch > 1) request(1);
-  __syncthreads();
+  // batch 0 to LDS
+  kb4[0][tid] = keys16_of(bk);
+  sb8[0][tid] = syms_for(bk, bprev, bsy);
+  unsigned pf = 0;  // bit 31: a record starts in this tile, at local index pf & 0xFFFF, with first symbol (pf >> 16) & 0xFF
+  if (DERIVED) {
+    const unsigned le = pf_e - e0;  // (in front of the tile: wraps to a huge number)
+    if (le < nt) pf = 0x80000000u | (pf_s << 16) | le;
+    if (tid == TS_THREADS - 1) s_more = pf_e < e0 + nt ? 1u : 0u;  // the last prefetched record still starts inside: more starts than threads
+  }
+  lds_barrier();  // (batch 1 stays in flight)
+  TS_PROF(PS + 0);
   // One context with an eighth of the tile or more: its symbols meet on ONE cursor, and same-address
   // LDS atomics of an instruction are served one lane after the other (binned qualities: the partition
   // of a tile took twice as long, one quality everywhere: sixteen times).  Such data comes in RUNS --
@@ -374,28 +437,29 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
   TS_PROF(PS + 1);
 
   // ---- the tile's runs, in context order: cur16[c] is now the END of context c's run
-  __syncthreads();  // (also drains the position stores) the batch buffers are dead: the run map takes their place
-  if (DERIVED) {
-    // the first symbol of every record that starts in this tile: its position comes back from lpos16 (this workgroup's own
-    // stores, complete behind the barrier above; read past the L1), its symbol from K1's side table
-    unsigned lo = 0, hi = R;  // first record with rec_start >= e0
-    while (lo < hi) {
-      const unsigned mid = (lo + hi) >> 1;
-      if (rec_start[mid] < e0) lo = mid + 1; else hi = mid;
-    }
-    for (unsigned r = lo + tid; r < R; r += TS_THREADS) {
-      const unsigned e = rec_start[r];
-      if (e >= e0 + nt) break;
-      const unsigned w = __hip_atomic_load(reinterpret_cast<const uint32_t *>(lpos16) + (e >> 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      lsym[(w >> (16u * (e & 1u))) & 0xFFFFu] = first_sym[r];
-    }
-    __syncthreads();
-  }
+  full_barrier();  // every wave's position stores have arrived (read back below); the batch buffers are dead: the run map takes their place
+  TS_PROF(PS + 5);
+  // DERIVED: the first symbol of every record that starts in this tile has to be patched in: its position comes back from
+  // lpos16 (this workgroup's own stores, read past the L1), its symbol came from K1's side table at entry.  The read-back is
+  // requested here and lands behind the run-list work, which does not touch lsym.
+  const uint32_t *lpos32 = reinterpret_cast<const uint32_t *>(lpos16);
+  unsigned pw = 0;
+  if (DERIVED && (pf >> 31)) pw = __hip_atomic_load(lpos32 + ((e0 + (pf & 0xFFFFu)) >> 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   ts_clear_bitmap<TS_THREADS>(rm);
-  unsigned long long my_mask[(NCHUNK + TS_WAVES - 1) / TS_WAVES];
-  unsigned my_beg[(NCHUNK + TS_WAVES - 1) / TS_WAVES], my_len[(NCHUNK + TS_WAVES - 1) / TS_WAVES];
+  constexpr unsigned CPW = (NCHUNK + TS_WAVES - 1) / TS_WAVES;  // chunks per wave
+  // global slot of every context's run: asked for whether the context has symbols in this tile or not -- 256 bytes per wave
+  // and chunk, all of a thread's loads in flight together across the chunk scan (behind the test for an empty context they
+  // were sixteen round trips in a row)
+  unsigned my_tb[CPW];
 #pragma unroll
-  for (unsigned k = 0; k < (NCHUNK + TS_WAVES - 1) / TS_WAVES; k++) {
+  for (unsigned k = 0; k < CPW; k++) {
+    const unsigned chunk = wave + k * TS_WAVES;
+    my_tb[k] = chunk < NCHUNK ? tb_row[chunk * 64 + lane] : 0u;
+  }
+  unsigned long long my_mask[CPW];
+  unsigned my_beg[CPW], my_len[CPW];
+#pragma unroll
+  for (unsigned k = 0; k < CPW; k++) {
     const unsigned chunk = wave + k * TS_WAVES;
     my_mask[k] = 0; my_beg[k] = 0; my_len[k] = 0;
     if (chunk < NCHUNK) {
@@ -406,7 +470,7 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
       if (lane == 0) s_cnt[chunk] = (unsigned)__popcll(my_mask[k]);
     }
   }
-  __syncthreads();
+  lds_barrier();
   if (wave == 0) {  // exclusive scan of the chunk counts (at most 128 chunks: two per lane)
     const unsigned a = 2 * lane < NCHUNK ? s_cnt[2 * lane] : 0u, b = 2 * lane + 1 < NCHUNK ? s_cnt[2 * lane + 1] : 0u;
     unsigned inc = a + b;
@@ -419,24 +483,39 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
     if (2 * lane + 1 < NCHUNK) s_cnt[2 * lane + 1] = inc - b;
     if (lane == 63) s_nruns = inc;
   }
-  __syncthreads();
+  lds_barrier();
   uint2 *rlist = runs + (size_t)tile * ts_run_stride<M>();
 #pragma unroll
-  for (unsigned k = 0; k < (NCHUNK + TS_WAVES - 1) / TS_WAVES; k++) {
+  for (unsigned k = 0; k < CPW; k++) {
     const unsigned chunk = wave + k * TS_WAVES;
     if (chunk < NCHUNK && my_len[k]) {
-      const unsigned c = chunk * 64 + lane;
       const unsigned slot = s_cnt[chunk] + fq_mbcnt(my_mask[k]);
-      const unsigned slot_base = tb_row[c];
+      const unsigned slot_base = my_tb[k];
       rlist[slot] = make_uint2(slot_base, my_beg[k] | (my_len[k] << 16));
       if (slot < GD_CAP) gd[slot] = slot_base - my_beg[k];  // "global slot of local position p" = p + gd[run of p]
       atomicOr(&rm.bm[my_beg[k] >> 5], 1u << (my_beg[k] & 31u));
     }
   }
-  __syncthreads();  // run list (global, this workgroup's own stores) and bitmap complete
+  TS_PROF(PS + 2);
+  // the patch lands: the symbols' places in lsym are final since the barrier behind the ranking, nobody reads them before
+  // the barriers of the run map's scan below
+  if (DERIVED) {
+    if (pf >> 31) lsym[(pw >> (16u * (pf & 1u))) & 0xFFFFu] = (uint8_t)(pf >> 16);  // (e0 is even: the parity of the index is the local one's)
+    if (s_more)  // (uniform, rare: reads shorter than 64 bases) the starts behind record fr + TS_THREADS - 1
+      for (unsigned r = fr + TS_THREADS + tid; r < R; r += TS_THREADS) {
+        const unsigned e = rec_start[r];
+        if (e >= e0 + nt) break;
+        const unsigned w = __hip_atomic_load(lpos32 + (e >> 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        lsym[(w >> (16u * (e & 1u))) & 0xFFFFu] = first_sym[r];
+      }
+  }
+  TS_PROF(PS + 6);
+  // run list (global; read back by this workgroup only where the tile has more runs than gd holds: then the stores are
+  // waited for), gd and bitmap complete
+  if (s_nruns > GD_CAP) full_barrier(); else lds_barrier();
   ts_build_wpre<TS_THREADS>(rm, wsum);
   if (tid == 0) run_count[tile] = s_nruns;
-  TS_PROF(PS + 2);
+  TS_PROF(PS + 7);
   // The sorted tile goes out in pieces of 16 positions per thread.  A piece that lies inside ONE run -- nearly all of them
   // for the sequence stream (runs of 128), most for the quality stream -- is one 16-byte LDS read, one run lookup and one
   // 16-byte store (round 3: a run lookup = two LDS reads and a global read, and a byte store, per POSITION); a piece with
@@ -467,7 +546,9 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
       }
     }
   }
-  __syncthreads();
+#ifdef FQGPU_EXPERIMENTS
+  __syncthreads();  // (the phase clock's only: nothing follows the stores)
+#endif
   TS_PROF(PS + 3);
 }
 
@@ -573,6 +654,10 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
   // Every tile of a stream but its last one is full: the gather and the packing rounds exist twice, and the full tile's
   // copies have fixed trip counts and no bounds guard per symbol (uniform choice).
   const bool full = nt == TS_TILE;
+  // the positions of the first packing round depend on the tile number alone: requested here, they are in their four registers
+  // when the gather and the look-back are over (asked for behind those, the first round began with a round trip to memory)
+  const uint4 *lp4 = reinterpret_cast<const uint4 *>(lpos16 + e0 + tid * TS_GP_PPT);
+  const uint4 lp_first = lp4[0];  // (no branch around it: behind the tile's end it reads the array's padding of a batch, and nobody uses that)
   const uint2 *rlist = runs + (size_t)tile * ts_run_stride<M>();
   const unsigned nr = run_count[tile];
   // "BYTE offset in out16 of local position p" = 2 p + gd[1 + run of p] (the popcount that finds a run counts its own start: it
@@ -709,8 +794,7 @@ k_tile_gather_pack(const uint16_t *__restrict__ lpos16, const uint2 *__restrict_
     constexpr bool FULL = decltype(full_tag)::value;
     constexpr unsigned PPT = TS_GP_PPT;
     const unsigned n_here = FULL ? TS_TILE : nt;
-    const uint4 *lp4 = reinterpret_cast<const uint4 *>(lpos16 + e0 + tid * PPT);
-    uint4 nx = FULL || tid * PPT < nt ? lp4[0] : make_uint4(0, 0, 0, 0);
+    uint4 nx = lp_first;
 #pragma unroll 1
     for (unsigned s0 = 0; s0 < n_here; s0 += TS_SUB) {
       for (unsigned i = tid; i < NW; i += TS_GP_THREADS) words[i] = i == 0 ? carry : 0u;
