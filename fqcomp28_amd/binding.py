@@ -315,22 +315,30 @@ def filter_check(flt):
     return lib().fqgpu_filter_check(_p(flt))
 
 
-def _filter_call(fn, front, flt, n_recs, out_cap=None, want_keep=True, query=False):
-    """A device filter call -> dict(rc, out, out_len, report, keep).  out_cap None: the size is asked for first (out=NULL), then
-    the call is made with a buffer of that size -- query: the size is asked for and that is all; a number: ONE call with a
-    buffer of that many bytes."""
+def _select_call(fn, front, specs, n_recs, more=(), out_cap=None, want_keep=True, query=False):
+    """A device filter or trim call -> dict(rc, out, out_len, report, keep).  specs: the call's trim and filter words in the order
+    of its arguments (None: NULL); more: the outputs it takes behind keep_out.  out_cap None: the size is asked for first
+    (out=NULL), then the call is made with a buffer of that size -- query: the size is asked for and that is all; a number: ONE
+    call with a buffer of that many bytes."""
     report = np.zeros(FILTER_REPORT_WORDS, dtype=np.uint64)
     keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
     n = C.c_size_t(0)
-    flt = np.ascontiguousarray(flt, dtype=np.uint32)
+    words = [None if s is None else np.ascontiguousarray(s, dtype=np.uint32) for s in specs]
+    specs = [_p(w) for w in words]
+    tail = (C.byref(n), _p(report), _p(keep)) + tuple(_p(m) for m in more)
     if out_cap is None:
-        rc = fn(*front, _p(flt), None, 0, C.byref(n), _p(report), _p(keep))
+        rc = fn(*front, *specs, None, 0, *tail)
         if rc != 0 or query:
             return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep)
         out_cap = n.value
     out = np.zeros(max(out_cap, 1), dtype=np.uint8)
-    rc = fn(*front, _p(flt), _p(out), out_cap, C.byref(n), _p(report), _p(keep))
+    rc = fn(*front, *specs, _p(out), out_cap, *tail)
     return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep)
+
+
+def _filter_call(fn, front, flt, n_recs, **kw):
+    """A device filter call -> dict(rc, out, out_len, report, keep); out_cap, want_keep, query: see _select_call"""
+    return _select_call(fn, front, (flt,), n_recs, **kw)
 
 
 TRIM_REPORT_WORDS = 16
@@ -347,23 +355,11 @@ def trim_check(trim):
     return lib().fqgpu_trim_check(_p(trim))
 
 
-def _trim_call(fn, front, trim, flt, n_recs, out_cap=None, want_keep=True, want_win=True, query=False):
+def _trim_call(fn, front, trim, flt, n_recs, want_win=True, **kw):
     """A device trim call -> dict(rc, out, out_len, report, keep, win): _filter_call's dict plus the records' windows
-    (start | n << 16).  flt None: a NULL filter.  out_cap, query: as _filter_call."""
-    report = np.zeros(TRIM_REPORT_WORDS, dtype=np.uint64)
-    keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
+    (start | n << 16).  flt None: a NULL filter.  out_cap, want_keep, query: see _select_call"""
     win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
-    n = C.c_size_t(0)
-    trim = np.ascontiguousarray(trim, dtype=np.uint32)
-    flt = None if flt is None else np.ascontiguousarray(flt, dtype=np.uint32)
-    if out_cap is None:
-        rc = fn(*front, _p(trim), _p(flt), None, 0, C.byref(n), _p(report), _p(keep), _p(win))
-        if rc != 0 or query:
-            return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep, win=win)
-        out_cap = n.value
-    out = np.zeros(max(out_cap, 1), dtype=np.uint8)
-    rc = fn(*front, _p(trim), _p(flt), _p(out), out_cap, C.byref(n), _p(report), _p(keep), _p(win))
-    return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep, win=win)
+    return dict(_select_call(fn, front, (trim, flt), n_recs, more=(win,), **kw), win=win)
 
 
 def pinned_empty(n_bytes):

@@ -535,8 +535,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->hp_chunk.release();
   ctx->crc.release();
   ctx->stats.release();
-  ctx->filter.release();
-  ctx->trim.release();
+  ctx->select.release();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -1614,16 +1613,33 @@ extern "C" int fqgpu_ctx_set_check_only(fqgpu_ctx *ctx, int on) {
   return FQGPU_OK;
 }
 
+// The two fronts of the calls on a chunk in HBM (digest, summary, filter, trim), behind their argument checks.
 // The chunk on the staging block, on the handle's copy stream: the chunk in flight arrived there and its record table was
-// uploaded or built there, so the digest runs beside the lane's encode kernels and waits for none of them; after a decode
-// the stream is idle.
+// uploaded or built there, so the call runs beside the lane's encode kernels and waits for none of them; after a decode
+// the stream is idle.  FQGPU_E_ARG: no chunk there.
+static int staged_block(const fqgpu_ctx *ctx, const fqgpu_dblock **b) {
+  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
+  *b = ctx->hp_block;
+  return FQGPU_OK;
+}
+
+// A caller's block behind its last operation, which may still write its raw block (a decode, an encode with
+// FQGPU_F_WRITE_BACK_N).  FQGPU_E_ARG: no block, or one of another device.
+static int settled_block(fqgpu_ctx *ctx, const fqgpu_dblock *b) {
+  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
+  int rc;
+  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  return FQGPU_OK;
+}
+
 extern "C" int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len) {
   if (crc) *crc = 0;
   if (len) *len = 0;
   int rc = use_device(ctx ? ctx->device : 0);
   if (rc) return rc;
-  if (!ctx || !crc || !len || !ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
+  const fqgpu_dblock *b = nullptr;
+  if (!ctx || !crc || !len) return FQGPU_E_ARG;
+  if ((rc = staged_block(ctx, &b))) return rc;
   uint32_t c = 0;
   size_t n = ctx->hp_crc_len;
   rc = ctx->hp_crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n)
@@ -1639,9 +1655,8 @@ extern "C" int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_
   if (len) *len = 0;
   int rc = use_device(ctx ? ctx->device : 0);
   if (rc) return rc;
-  if (!ctx || !b || !crc || !len || b->device != ctx->device) return FQGPU_E_ARG;
-  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
-  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
+  if (!ctx || !crc || !len) return FQGPU_E_ARG;
+  if ((rc = settled_block(ctx, b))) return rc;
   uint32_t c = 0;
   size_t n = 0;
   if ((rc = fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n))) return rc;
@@ -1651,93 +1666,60 @@ extern "C" int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_
 }
 
 // ------------------------------------------------------------------ read summary of a chunk in HBM (stats.hip)
-// Shared front of the two calls: no device is said before any argument is looked at; an `out` that is large enough is zeroed
-// before anything else can fail.
-static int stats_args(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words) {
+// The two calls (b: the caller's block; staged: the chunk on the staging block): no device is said before any argument is
+// looked at; an `out` that is large enough is zeroed before anything else can fail.
+static int stats_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, unsigned positions, uint64_t *out, size_t cap_words) {
   if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
   const size_t words = fqgpu_stats_words(positions);
   if (!ctx || !out || !words) return FQGPU_E_ARG;
   if (cap_words < words) return FQGPU_E_OVERFLOW;
   memset(out, 0, words * sizeof(uint64_t));
-  return FQGPU_OK;
+  if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
+  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
 }
 
-// As fqgpu_chunk_crc32: on the handle's copy stream, beside the lane's encode or behind the decode.
 extern "C" int fqgpu_chunk_stats(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words) {
-  if (const int rc = stats_args(ctx, positions, out, cap_words)) return rc;
-  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
-  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
+  return stats_call(ctx, nullptr, true, positions, out, cap_words);
 }
 
 extern "C" int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigned positions, uint64_t *out, size_t cap_words) {
-  int rc = stats_args(ctx, positions, out, cap_words);
-  if (rc) return rc;
-  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
-  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
-  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
-  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
+  return stats_call(ctx, b, false, positions, out, cap_words);
 }
 
-// ------------------------------------------------------------------ the reads of a chunk in HBM that pass a filter (filter.hip)
-// Shared front of the two calls: no device is said before any argument is looked at; *out_len and the report are zeroed
-// before anything else can fail.
-static int filter_args(fqgpu_ctx *ctx, const fqgpu_filter *f, size_t *out_len, uint64_t *report) {
+// ------------------------------------------------------------------ the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip)
+// The four calls (b, staged: as stats_call; trim: a trim call, which needs *t and takes a NULL filter for one that keeps
+// everything): no device is said before any argument is looked at; *out_len and the report are zeroed before anything else
+// can fail.
+static int select_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, bool trim, const fqgpu_trim *t, const fqgpu_filter *f,
+                       uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
+  static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one zeroing for both reports");
   if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
   if (out_len) *out_len = 0;
   if (report) memset(report, 0, FQGPU_FILTER_REPORT_WORDS * sizeof(uint64_t));
-  if (!ctx || !out_len || !report || fqgpu_filter_check(f) != FQGPU_OK) return FQGPU_E_ARG;
-  return FQGPU_OK;
+  if (!ctx || !out_len || !report || (trim && fqgpu_trim_check(t) != FQGPU_OK) || ((f || !trim) && fqgpu_filter_check(f) != FQGPU_OK))
+    return FQGPU_E_ARG;
+  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
+  if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
+  return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, trim ? t : nullptr, f ? f : &all, out, out_cap, out_len,
+                         report, keep_out, win_out);
 }
 
-// As fqgpu_chunk_stats: on the handle's copy stream, beside the lane's encode or behind the decode.
 extern "C" int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                                   uint64_t *report, uint8_t *keep_out) {
-  if (const int rc = filter_args(ctx, f, out_len, report)) return rc;
-  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
-  return fq_filter_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, f, out, out_cap, out_len, report, keep_out);
+  return select_call(ctx, nullptr, true, false, nullptr, f, out, out_cap, out_len, report, keep_out, nullptr);
 }
 
 extern "C" int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
                                    size_t *out_len, uint64_t *report, uint8_t *keep_out) {
-  int rc = filter_args(ctx, f, out_len, report);
-  if (rc) return rc;
-  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
-  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
-  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
-  return fq_filter_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, f, out, out_cap, out_len, report, keep_out);
+  return select_call(ctx, b, false, false, nullptr, f, out, out_cap, out_len, report, keep_out, nullptr);
 }
 
-// ------------------------------------------------------------------ the reads of a chunk in HBM, trimmed and then filtered (trim.hip)
-// Shared front of the two calls, as filter_args; *keep: the filter to judge by (a NULL filter keeps everything).
-static int trim_args(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, size_t *out_len, uint64_t *report, fqgpu_filter *keep) {
-  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
-  if (out_len) *out_len = 0;
-  if (report) memset(report, 0, FQGPU_TRIM_REPORT_WORDS * sizeof(uint64_t));
-  if (!ctx || !out_len || !report || fqgpu_trim_check(t) != FQGPU_OK || (f && fqgpu_filter_check(f) != FQGPU_OK)) return FQGPU_E_ARG;
-  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
-  *keep = f ? *f : all;
-  return FQGPU_OK;
-}
-
-// As fqgpu_chunk_filter: on the handle's copy stream, beside the lane's encode or behind the decode.
 extern "C" int fqgpu_chunk_trim(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                                 uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  fqgpu_filter keep;
-  if (const int rc = trim_args(ctx, t, f, out_len, report, &keep)) return rc;
-  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
-  const fqgpu_dblock *b = ctx->hp_block;
-  return fq_trim_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, t, &keep, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, nullptr, true, true, t, f, out, out_cap, out_len, report, keep_out, win_out);
 }
 
 extern "C" int fqgpu_dblock_trim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out,
                                  size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  fqgpu_filter keep;
-  int rc = trim_args(ctx, t, f, out_len, report, &keep);
-  if (rc) return rc;
-  if (!b || b->device != ctx->device) return FQGPU_E_ARG;
-  // the block's last operation may still write its raw block (a decode, an encode with FQGPU_F_WRITE_BACK_N)
-  if ((rc = fqgpu_sync(ctx)) || (b->owner && b->owner != ctx && (rc = fqgpu_sync(b->owner)))) return rc;
-  return fq_trim_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, t, &keep, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, b, false, true, t, f, out, out_cap, out_len, report, keep_out, win_out);
 }

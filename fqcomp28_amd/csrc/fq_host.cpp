@@ -81,14 +81,14 @@ extern "C" int fqgpu_stats_merge(uint64_t *dst, size_t dst_words, const uint64_t
   return FQGPU_OK;
 }
 
-// Read filters (filter.hip applies them): what a filter may say.
+// Read filters (select.hip applies them): what a filter may say.
 extern "C" int fqgpu_filter_check(const fqgpu_filter *f) {
   if (!f || f->min_len > f->max_len || f->min_mean_q > 63u || f->low_q > 64u || f->max_low_pct > 100u || f->reserved[0] || f->reserved[1])
     return FQGPU_E_ARG;
   return FQGPU_OK;
 }
 
-// Read trimming (trim.hip applies it): what a trim may say.
+// Read trimming (select.hip applies it): what a trim may say.
 extern "C" int fqgpu_trim_check(const fqgpu_trim *t) {
   if (!t || t->cut_front > 65535u || t->cut_tail > 65535u || t->q_front > 64u || t->q_tail > 64u || t->crop == 0u || t->reserved[0] ||
       t->reserved[1] || t->reserved[2])

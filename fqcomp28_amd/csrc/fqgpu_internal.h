@@ -235,18 +235,11 @@ struct StatsScratch {
   void release();
 };
 
-// Selection of the reads that pass a filter from a chunk in HBM (filter.hip): per record the kept size and the start of its
-// header line, the keep bits, the offsets of the kept records in the output, the gathered output, the result words and their
-// page-locked landing place; all grown on demand
-struct FilterScratch {
-  DevBuf ksize, hstart, keep, koff, dst, res, scan_tmp;
-  void *host = nullptr;
-  void release();
-};
-
-// Trimmed and filtered reads of a chunk in HBM (trim.hip): FilterScratch's buffers and the records' windows; its own, so that a
-// filter call and a trim call on one handle do not disturb each other
-struct TrimScratch {
+// Selection of the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip): per record the kept size, the
+// start of its header line and -- reserved by a trim call alone -- its window, the keep bits, the offsets of the kept records
+// in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
+// filter and trim calls: each is waited for before it returns.
+struct SelectScratch {
   DevBuf ksize, hstart, win, keep, koff, dst, res, scan_tmp;
   void *host = nullptr;
   void release();
@@ -301,8 +294,7 @@ struct fqgpu_ctx {
   bool check_only = false;            // fqgpu_ctx_set_check_only: fqgpu_decode_chunk takes raw_out == NULL
   CrcScratch crc;
   StatsScratch stats;
-  FilterScratch filter;
-  TrimScratch trim;
+  SelectScratch select;
 };
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
@@ -445,16 +437,13 @@ int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, siz
 int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                    unsigned positions, uint64_t *out);
 
-// The reads of a chunk in HBM that pass *f (filter.hip; *f has passed fqgpu_filter_check), on st, waited for: report, *out_len,
-// keep_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes into out
-int fq_filter_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                    const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out);
-
-// The reads of a chunk in HBM trimmed by *t and then judged by *f (trim.hip; both have passed their checks), on st, waited for:
-// report (FQGPU_TRIM_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
-int fq_trim_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                  const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
-                  uint8_t *keep_out, uint32_t *win_out);
+// The reads of a chunk in HBM trimmed by *t (nullptr: the filter alone, win_out is not looked at) and then judged by *f
+// (select.hip; both have passed their checks), on st, waited for: report (FQGPU_TRIM_REPORT_WORDS, which are
+// FQGPU_FILTER_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
+// into out
+int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                    const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
+                    uint8_t *keep_out, uint32_t *win_out);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

@@ -681,22 +681,27 @@ inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &
   return rep;
 }
 
-/** Extension: `d --min-len / --max-len / --max-n / --min-mean-q / --max-low-q` -- the reads that pass `filter`, in input
- *  order, as the FASTQ bytes a plain restore writes for them.  Every block is decoded on the device and judged there
- *  (decodeChunkFiltered); only the kept bytes come down and reach the file.  A usable `<archive>.fqx` is used, and with a
- *  usable `<archive>.fqs` every chunk is verified before any of it is written: the digest is of the WHOLE restored chunk, as
- *  the writer took it.  Never builds an index.  The kept sizes are known only after the decode, so the blocks go through
- *  OrderedPieceWriter as the FASTA pieces do: handed out in order, placed by the sizes published so far; a failed run
- *  leaves neither `<out>` nor `<out>.part`.  rep.in counts what was written, rep.filter what was read and why it was dropped. */
-inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_t &mates1_out, const fqgpu_filter &filter,
-                                         const Settings &set) {
-  if (fqgpu_filter_check(&filter) != FQGPU_OK) throw std::invalid_argument("processArchiveFiltered: a filter fqgpu_filter_check refuses");
+namespace detail {
+/** processArchiveFiltered (trim == nullptr; the filter is needed) and processArchiveTrimmed, `who` of the two: every block
+ *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed), only the kept bytes come down and
+ *  reach the file.  A usable `<archive>.fqx` is used, and with a usable `<archive>.fqs` every chunk is verified before any
+ *  of it is written: the digest is of the WHOLE restored chunk, as the writer took it.  Never builds an index.  The kept
+ *  sizes are known only after the decode, so the blocks go through OrderedPieceWriter as the FASTA pieces do: handed out in
+ *  order, placed by the sizes published so far; a failed run leaves neither `<out>` nor `<out>.part`.  rep.in counts what
+ *  was written; the chunks' reports, added word by word, go to rep.filter or rep.trim. */
+inline FarmReport processArchiveSelected(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim *trim,
+                                         const fqgpu_filter *filter, const Settings &set, const char *who) {
+  static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one report size for both");
+  constexpr unsigned W = FQGPU_FILTER_REPORT_WORDS;
+  const std::string name(who);
+  if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
+  if ((filter || !trim) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
   Archive archive(archive_path);
   const std::size_t n_blocks = archive.chunkOffsets().size() - 1;
   std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
   detail::ChunkVerifier verifier(archive_path, n_blocks, false);
   const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n_blocks, 1))));
-  if (set.devices.empty()) throw std::invalid_argument("processArchiveFiltered: no device");
+  if (set.devices.empty()) throw std::invalid_argument(name + ": no device");
   std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
   detail::runWorkers(T, [&](unsigned t) {
     wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]);
@@ -705,7 +710,7 @@ inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_
   const auto t0 = std::chrono::steady_clock::now();
   OrderedPieceWriter writer(mates1_out, n_blocks);
   std::vector<InputStats> istats(T);
-  std::vector<std::vector<uint64_t>> reports(T, std::vector<uint64_t>(FQGPU_FILTER_REPORT_WORDS, 0));
+  std::vector<std::vector<uint64_t>> reports(T, std::vector<uint64_t>(W, 0));
   FarmReport rep;
   rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
   std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
@@ -713,7 +718,7 @@ inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_
   detail::runWorkers(T, [&](unsigned t) {
     CompressedBuffersSrc cbs;
     FastqChunk piece;
-    uint64_t report[FQGPU_FILTER_REPORT_WORDS];
+    uint64_t report[W];
     for (;;) {
       const std::size_t k = next.fetch_add(1);  // (in order: whoever waits in the writer waits for blocks already taken)
       if (stopped.load() || k >= n_blocks) break;
@@ -724,10 +729,11 @@ inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_
         used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
       }
       clk.lap("read");
-      wksp[t]->decodeChunkFiltered(piece, cbs, filter, report);
+      if (trim) wksp[t]->decodeChunkTrimmed(piece, cbs, *trim, filter, report);
+      else wksp[t]->decodeChunkFiltered(piece, cbs, *filter, report);
       clk.lap("decode");
       verifier.check(cbs, wksp[t]->lastDigest());  // (before anything of the chunk reaches the file)
-      for (unsigned i = 0; i < FQGPU_FILTER_REPORT_WORDS; ++i) reports[t][i] += report[i];
+      for (unsigned i = 0; i < W; ++i) reports[t][i] += report[i];
       istats[t].raw += piece.raw_data.size();
       istats[t].n_records += static_cast<std::size_t>(report[1]);
       rep.blocks_per_worker[t]++;
@@ -742,88 +748,34 @@ inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_
   }, [&] { stopped.store(true); writer.abort(); });
   writer.flush();
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  rep.filter.assign(FQGPU_FILTER_REPORT_WORDS, 0);
+  std::vector<uint64_t> &sum = trim ? rep.trim : rep.filter;
+  sum.assign(W, 0);
   for (unsigned t = 0; t < T; ++t) {
     rep.in += istats[t];
-    for (unsigned i = 0; i < FQGPU_FILTER_REPORT_WORDS; ++i) rep.filter[i] += reports[t][i];
+    for (unsigned i = 0; i < W; ++i) sum[i] += reports[t][i];
   }
   rep.indexed_blocks = used_blocks.load();
   rep.index_bytes = used_bytes.load();
   verifier.report(rep);
   return rep;
 }
+}  // namespace detail
+
+/** Extension: `d --min-len / --max-len / --max-n / --min-mean-q / --max-low-q` -- the reads that pass `filter`, in input
+ *  order, as the FASTQ bytes a plain restore writes for them (detail::processArchiveSelected).  rep.in counts what was
+ *  written, rep.filter what was read and why it was dropped. */
+inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_t &mates1_out, const fqgpu_filter &filter,
+                                         const Settings &set) {
+  return detail::processArchiveSelected(archive_path, mates1_out, nullptr, &filter, set, "processArchiveFiltered");
+}
 
 /** Extension: `d --cut-front / --cut-tail / --trim-q5 / --trim-q3 / --crop`, with or without the filter options -- the reads
  *  trimmed by `trim` and then judged by `filter` (nullptr: every read that is not emptied is kept), in input order, as
- *  trimmed FASTQ.  Works as processArchiveFiltered does: every block decoded on the device and trimmed there
- *  (decodeChunkTrimmed), only the kept bytes come down; a usable `<archive>.fqx` is used, with a usable `<archive>.fqs`
- *  every WHOLE chunk is verified before any of it is written; never builds an index; ordered pieces through
- *  OrderedPieceWriter; a failed run leaves neither `<out>` nor `<out>.part`.  rep.in counts what was written, rep.trim what
- *  was read, what was cut and why reads were dropped. */
+ *  trimmed FASTQ (detail::processArchiveSelected).  rep.in counts what was written, rep.trim what was read, what was cut and
+ *  why reads were dropped. */
 inline FarmReport processArchiveTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim &trim,
                                         const fqgpu_filter *filter, const Settings &set) {
-  if (fqgpu_trim_check(&trim) != FQGPU_OK) throw std::invalid_argument("processArchiveTrimmed: a trim fqgpu_trim_check refuses");
-  if (filter && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument("processArchiveTrimmed: a filter fqgpu_filter_check refuses");
-  Archive archive(archive_path);
-  const std::size_t n_blocks = archive.chunkOffsets().size() - 1;
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
-  detail::ChunkVerifier verifier(archive_path, n_blocks, false);
-  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n_blocks, 1))));
-  if (set.devices.empty()) throw std::invalid_argument("processArchiveTrimmed: no device");
-  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
-  detail::runWorkers(T, [&](unsigned t) {
-    wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]);
-    wksp[t]->setVerify(verifier.on());
-  });
-  const auto t0 = std::chrono::steady_clock::now();
-  OrderedPieceWriter writer(mates1_out, n_blocks);
-  std::vector<InputStats> istats(T);
-  std::vector<std::vector<uint64_t>> reports(T, std::vector<uint64_t>(FQGPU_TRIM_REPORT_WORDS, 0));
-  FarmReport rep;
-  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
-  std::atomic<bool> stopped{false};
-  detail::runWorkers(T, [&](unsigned t) {
-    CompressedBuffersSrc cbs;
-    FastqChunk piece;
-    uint64_t report[FQGPU_TRIM_REPORT_WORDS];
-    for (;;) {
-      const std::size_t k = next.fetch_add(1);  // (in order: whoever waits in the writer waits for blocks already taken)
-      if (stopped.load() || k >= n_blocks) break;
-      StageClock clk;
-      archive.readBlockAt(k, cbs);
-      if (sidecar && sidecar->get(cbs)) {
-        used_blocks.fetch_add(1);
-        used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
-      }
-      clk.lap("read");
-      wksp[t]->decodeChunkTrimmed(piece, cbs, trim, filter, report);
-      clk.lap("decode");
-      verifier.check(cbs, wksp[t]->lastDigest());  // (before anything of the chunk reaches the file)
-      for (unsigned i = 0; i < FQGPU_TRIM_REPORT_WORDS; ++i) reports[t][i] += report[i];
-      istats[t].raw += piece.raw_data.size();
-      istats[t].n_records += static_cast<std::size_t>(report[1]);
-      rep.blocks_per_worker[t]++;
-      try {
-        writer.writePiece(k, piece.raw_data.data(), piece.raw_data.size());
-      } catch (const OrderedPieceWriter::Aborted &) {
-        break;  // (another worker has failed and says why)
-      }
-      clk.lap("write");
-      clk.done(static_cast<unsigned>(k));
-    }
-  }, [&] { stopped.store(true); writer.abort(); });
-  writer.flush();
-  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  rep.trim.assign(FQGPU_TRIM_REPORT_WORDS, 0);
-  for (unsigned t = 0; t < T; ++t) {
-    rep.in += istats[t];
-    for (unsigned i = 0; i < FQGPU_TRIM_REPORT_WORDS; ++i) rep.trim[i] += reports[t][i];
-  }
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
-  verifier.report(rep);
-  return rep;
+  return detail::processArchiveSelected(archive_path, mates1_out, &trim, filter, set, "processArchiveTrimmed");
 }
 
 /** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function

@@ -1,0 +1,744 @@
+// The reads of a chunk that lies in HBM which pass a filter (include/fqgpu.h: fqgpu_chunk_filter, fqgpu_dblock_filter), or which
+// are trimmed first and then judged by the filter (fqgpu_chunk_trim, fqgpu_dblock_trim), gathered on the device so that only
+// the kept bytes come down.  Extension: nothing in the reference.  Both are ONE judge, one scan, one gather and one host
+// driver; the flag TRIM is a template argument, so that the filter alone carries nothing of the trim: no walk, no window
+// store, no window mask, ten counters instead of fourteen.
+//
+// k_select_judge -- one pass over the lines the criteria need, by the chunk's device record table.  A wave takes 64
+// consecutive records: their table entries with ONE load, lane = record.  The bytes are then read by parts of the wave: eight
+// lanes to a record, eight records at a time, every lane an ALIGNED 16-byte word of a line per load (a line starts anywhere:
+// the bytes in front of it and behind it are masked off, and the 64 spare bytes every raw block has behind its chunk let the
+// chunk's last word be read whole), the words of the NEXT eight records on their way while those of the eight in hand are
+// judged -- so a wait is for the lines of eight records, not for one, and the kernel holds no LDS table, so a CU holds many
+// such waves.  The words are judged four bytes at a time (a byte >= 128 is refused first, which makes the packed compares
+// exact): the sum of a line's quality bytes by v_sad_u8, "N", "not a base", "Phred below the level", "not a quality" by
+// packed compares and a population count.  A record's eight lanes add up by shuffles and hand the counts back to the
+// record's own lane, which gives the verdict, the kept size (the canonical length of what is left, or 0), the start of the
+// record's header line, k_crc_check's verdict on the '+' lines and -- by one ballot per wave -- the keep bits.  The sequence
+// lines are not loaded at all when max_n is off, the quality lines not when min_mean_q, low_q and the quality trim are off: a
+// length-only filter reads the record table alone.  THE BYTES OF A LINE THAT IS NOT LOADED ARE NOT JUDGED: a sequence byte
+// outside ACGTN / a quality byte outside 33 .. 96 refuses the chunk only when a criterion reads that line; a line that is read
+// is judged over all its bytes, the cut ones too.  The report's counters are summed over the wave by shuffles, over the
+// workgroup in LDS, and reach global memory as one 64-bit atomic per counter and workgroup.
+//
+// TRIM puts a window in front of the verdict.  The fixed cuts leave the interval [f, L - t).  The two running-sum walks of the
+// quality trim (s += cutoff - Phred; stop at s < 0; the cut is behind the FIRST place of the largest s > 0) are done by all
+// eight lanes at once: a lane sums up its word, in walk order, as a PIECE -- total, smallest prefix, largest prefix and the
+// first place of that --, a prefix sum over the pieces gives every piece the sum the walk enters it with, the walk stops in the
+// first piece with entering + smallest prefix < 0, every piece in front of that one is valid as a whole (its candidate:
+// entering + largest prefix; equal candidates: the earlier piece), and only the piece the walk stops in is walked byte by
+// byte.  A request's two words are taken in walk order, and a word no record of the wave still needs is left out.  A
+// candidate travels as ONE 64-bit key -- the sum above, the place below, so that the larger key is the better AND the earlier
+// one -- and is reduced by shuffles.  With the window known, N, the Phred sum and the low count are taken over the window from
+// the words that are still in the registers, with a second set of byte masks.  A read whose line fits one request of its eight
+// lanes (256 bytes) loads no word twice; a longer one walks the requests forwards for the front walk, backwards for the tail
+// walk and forwards again for the counts, loading as it goes: a correctness path.  Without TRIM the window is the line, and a
+// long read is one loop over the rest of its requests.
+//
+// fq_scan_u32_to_u64 -- the kept sizes become the records' places in the output.
+//
+// k_select_gather -- the compacting copy, driven by the DESTINATION: a workgroup owns an aligned tile of the output, every
+// lane aligned 16-byte words of it, every store a full aligned 16-byte store.  The workgroup finds the records of its tile's
+// first and last byte (two uniform binary searches in the offsets).  Cuts and drops only take bytes away, so
+// hstart[r] - koff[r] never gets smaller with r: when the chunk's '+' lines are bare (there a whole record's canonical bytes
+// are one span of the chunk) and both records have the same shift and are whole, every record between them is kept whole and
+// the tile is ONE shifted copy, 16 bytes a lane from wherever the source lies -- every tile of a call that keeps everything,
+// most tiles behind long runs.  Otherwise every lane searches among the tile's records.  Without TRIM every kept record is
+// whole: a word inside one run is copied the same way and a word across a seam between two runs is put together byte by byte
+// from the runs' shifts alone.  With TRIM a kept record is FIVE pieces: its header line, the window of the sequence line, the
+// literal "\n+\n", the window of the quality line, the literal '\n'; a word inside a run of whole records or inside one piece is
+// one unaligned 16-byte load, a word across a seam is put together byte by byte; the '+' line is always the literal there, so
+// that form serves chunks with text behind a '+' as well.  k_select_gather_records is the filter's form for such chunks (one
+// wave per kept record, as k_crc_canon_write): a correctness path, kept because the five-piece form takes twice its time
+// there.
+//
+// All global stores are ordinary vector stores from plain C++.
+#include "fqgpu_internal.h"
+
+#include <string.h>
+
+namespace {
+
+constexpr unsigned SEL_THREADS = 256;        // threads of a judge workgroup: four waves
+constexpr unsigned SEL_WAVE_RECORDS = 64;    // consecutive records a wave takes: lane = record
+constexpr unsigned SEL_GROUP_LANES = 8;      // lanes that read one record's lines together
+constexpr unsigned SEL_UNROLL = 2;           // 16-byte words of a line a lane has in flight
+constexpr unsigned SEL_GATHER_THREADS = 256; // threads of a gather workgroup
+constexpr unsigned SEL_GATHER_WORDS = 4;     // 16-byte words of the output a gather lane writes
+constexpr unsigned SEL_ROUND_RECORDS = SEL_WAVE_RECORDS / SEL_GROUP_LANES;  // records a wave reads at a time
+constexpr unsigned SEL_STEP_BYTES = SEL_GROUP_LANES * 16 * SEL_UNROLL;      // bytes of a line a record's lanes ask for in one go
+constexpr unsigned SEL_TILE_BYTES = SEL_GATHER_THREADS * 16 * SEL_GATHER_WORDS;  // output bytes of a gather workgroup
+static_assert(SEL_WAVE_RECORDS == 64 && SEL_GROUP_LANES == 8 && SEL_ROUND_RECORDS == 8 && SEL_UNROLL == 2, "a wave's records sit in its lanes");
+
+// the result words on the device: the report (include/fqgpu.h; word 0 is filled in by the host) and the two flags
+static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one result struct serves both reports");
+struct SelectResult {
+  unsigned long long w[FQGPU_TRIM_REPORT_WORDS];
+  unsigned int bad;       // a byte that cannot be judged, a record outside the chunk or without symbols
+  unsigned int not_bare;  // k_crc_check's verdict: text behind a '+', or the last '\n' outside the chunk
+};
+constexpr unsigned R_KEPT = 1, R_BASES_IN = 2, R_BASES_KEPT = 3, R_BYTES_KEPT = 4, R_DROPPED = 5, R_TRIMMED = 10, R_CUT_FRONT = 11,
+                   R_CUT_TAIL = 12, R_EMPTIED = 13;
+template <bool TRIM> constexpr unsigned R_COUNTERS = TRIM ? 14 : 10;  // the words a judge counts
+
+constexpr unsigned SW_H = 0x80808080u, SW_L = 0x01010101u;
+// per byte of x (every byte < 128), 0 <= k <= 128: bit 7 set where the byte is >= k
+__device__ __forceinline__ unsigned sw_ge(unsigned x, unsigned k) { return ((x | SW_H) - k * SW_L) & SW_H; }
+// ... set where the byte equals c
+__device__ __forceinline__ unsigned sw_eq(unsigned x, unsigned c) { return ~sw_ge(x ^ (c * SW_L), 1u) & SW_H; }
+// 0xFF in the bytes [lo, hi) of a word, 0 <= lo, hi <= 4
+__device__ __forceinline__ unsigned sw_mask(int lo, int hi) {
+  lo = max(lo, 0);
+  hi = min(hi, 4);
+  if (lo >= hi) return 0u;
+  return (0xFFFFFFFFu >> (8 * (4 - hi))) & (0xFFFFFFFFu << (8 * lo));
+}
+// bit j set for the bytes lo <= j < hi of a 16-byte word (any lo, hi)
+__device__ __forceinline__ unsigned sel_bits(int lo, int hi) {
+  lo = min(max(lo, 0), 16);
+  hi = min(max(hi, 0), 16);
+  return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
+}
+
+// what a lane keeps of the record its group reads: the lines' places and the first words of both
+struct SelStage {
+  unsigned seq_off, qual_off, len;  // len 0: nothing to read (behind the table's end, or not a record of this chunk)
+  uint4 s[SEL_UNROLL], q[SEL_UNROLL];
+};
+
+// the lane's words of one line: word k of the lane is the aligned word 8 k + sub of the line, counted from the word that
+// holds the line's first byte; p0: bytes of the line (from that word on) in front of this request.  Every raw block has 64
+// spare bytes behind its chunk (api.hip), so the word that holds the chunk's last byte can be read whole; what it holds behind
+// the chunk is masked off by the callers.
+__device__ __forceinline__ void sel_load_line(uint4 (&v)[SEL_UNROLL], const uint8_t *__restrict__ raw, unsigned off, unsigned len, unsigned p0, unsigned sub) {
+  const unsigned lead = off & 15u, span = len ? lead + len : 0u;
+  const uint8_t *const line = raw + (off - lead);
+#pragma unroll
+  for (unsigned k = 0; k < SEL_UNROLL; k++) {
+    const unsigned rel = p0 + 16u * (SEL_GROUP_LANES * k + sub);
+    v[k] = rel < span ? *reinterpret_cast<const uint4 *>(line + rel) : make_uint4(0, 0, 0, 0);
+  }
+}
+
+struct SelCounts {
+  unsigned n, qsum, low;  // over the WINDOW: N of the sequence line; sum of the quality BYTES; quality bytes below the level
+  bool bad;               // over the whole line
+};
+
+// one word of a sequence line: [first, last) are its bytes inside the line, [wf, wl) those inside the window (TRIM; without,
+// the window is the line and is not looked at)
+template <bool TRIM>
+__device__ __forceinline__ void sel_judge_seq(SelCounts &c, const uint4 v, int first, int last, int wf, int wl) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned m = sw_mask(first - 4 * i, last - 4 * i), x = w[i] & m;
+    if (x & SW_H) c.bad = true;
+    const unsigned y = x & ~SW_H, is_n = sw_eq(y, 'N');
+    const unsigned base = sw_eq(y, 'A') | sw_eq(y, 'C') | sw_eq(y, 'G') | sw_eq(y, 'T') | is_n;
+    if ((base & m) != (SW_H & m)) c.bad = true;
+    unsigned wm = m;
+    if constexpr (TRIM) wm = sw_mask(wf - 4 * i, wl - 4 * i);
+    c.n += __popc(is_n & wm);
+  }
+}
+
+// one word of a quality line; level: the first byte value that is not "low" (33 + low_q)
+template <bool TRIM>
+__device__ __forceinline__ void sel_judge_qual(SelCounts &c, const uint4 v, int first, int last, int wf, int wl, unsigned level) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned m = sw_mask(first - 4 * i, last - 4 * i), x = w[i] & m;
+    if (x & SW_H) c.bad = true;
+    const unsigned y = x & ~SW_H;
+    if ((sw_ge(y, 33u) & m) != (SW_H & m) || (sw_ge(y, 97u) & m)) c.bad = true;
+    unsigned wm = m;
+    if constexpr (TRIM) wm = sw_mask(wf - 4 * i, wl - 4 * i);
+    c.qsum = __builtin_amdgcn_sad_u8(w[i] & wm, 0u, c.qsum);
+    c.low += __popc(~sw_ge(y, level) & SW_H & wm);
+  }
+}
+
+// ---- the running-sum walk.  A candidate is one key: the sum in the bits from 20 up (at most 64 x 65535 < 2^22), the place
+// below, turned so that of two keys with one sum the place the walk reaches FIRST is the larger.  0: no candidate.
+constexpr unsigned SEL_PLACE = 0xFFFFFu;
+template <bool FWD>
+__device__ __forceinline__ unsigned long long sel_key(int sum, int place) {
+  return ((unsigned long long)(unsigned)sum << 20) | (unsigned)(FWD ? (int)SEL_PLACE - place : place);
+}
+
+struct SelPiece {
+  int tot, minp, maxp;  // of the prefixes in walk order (the empty prefix, 0, among them)
+  int place;            // the cut the first largest prefix stands for (maxp > 0 only)
+};
+
+// The bytes `in` (a bit each) of a word as one piece of a walk; c: cutoff + 33, so that c - byte is the walk's increment;
+// pos0: the place in the line of the word's byte 0.  The front walk (FWD) reads byte 0 first and a byte at place i stands for
+// the cut "start = i + 1"; the tail walk reads byte 15 first and a byte at place i stands for "stop = i".
+template <bool FWD>
+__device__ __forceinline__ SelPiece sel_piece(const uint4 v, unsigned in, int c, int pos0) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  SelPiece p = {0, 0, 0, 0};
+  int s = 0;
+#pragma unroll
+  for (int jj = 0; jj < 16; jj++) {
+    const int j = FWD ? jj : 15 - jj;
+    const int byte = (int)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+    s += (in >> j) & 1u ? c - byte : 0;
+    p.minp = min(p.minp, s);
+    if (s > p.maxp) {
+      p.maxp = s;
+      p.place = pos0 + j + (FWD ? 1 : 0);
+    }
+  }
+  p.tot = s;
+  return p;
+}
+
+// The piece the walk stops in, byte by byte: s the sum the walk enters it with, best the best candidate in front of it.
+template <bool FWD>
+__device__ __forceinline__ unsigned long long sel_walk_piece(const uint4 v, unsigned in, int c, int pos0, int s, unsigned long long best) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  int top = (int)(best >> 20);
+  bool dead = false;
+#pragma unroll
+  for (int jj = 0; jj < 16; jj++) {
+    const int j = FWD ? jj : 15 - jj;
+    const int byte = (int)((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+    s += (in >> j) & 1u ? c - byte : 0;
+    dead = dead || s < 0;
+    if (!dead && s > top) {
+      top = s;
+      best = sel_key<FWD>(s, pos0 + j + (FWD ? 1 : 0));
+    }
+  }
+  return best;
+}
+
+// a walk on its way through a line; the same in the eight lanes of a record
+struct SelWalk {
+  int ent;                  // the sum it enters the next request with
+  unsigned long long best;  // the best candidate so far
+  bool stopped;
+};
+
+// One word of a request of a walk over the places [a, b) of a line: eight pieces, the word of lane sub at place pos0.  Every
+// lane of the record's eight calls this together.
+template <bool FWD>
+__device__ __forceinline__ void sel_walk_word(SelWalk &wk, const uint4 v, int pos0, unsigned sub, int a, int b, int c) {
+  const unsigned in = sel_bits(a - pos0, b - pos0);
+  const SelPiece pc = sel_piece<FWD>(v, in, c, pos0);
+  // the sum the walk enters the piece with: a prefix sum over the lanes, in walk order
+  int inc = pc.tot;
+#pragma unroll
+  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+    const int o = __shfl_up(inc, d, SEL_GROUP_LANES);
+    if (sub >= d) inc += o;
+  }
+  const int sum = __shfl(inc, SEL_GROUP_LANES - 1, SEL_GROUP_LANES);
+  const int e = wk.ent + (FWD ? inc - pc.tot : sum - inc);
+  const unsigned ord = FWD ? sub : SEL_GROUP_LANES - 1 - sub;  // the piece's turn in the walk
+  // the first piece the walk would stop in
+  unsigned stop_at = e + pc.minp < 0 ? ord : SEL_GROUP_LANES;
+#pragma unroll
+  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) stop_at = min(stop_at, (unsigned)__shfl_xor(stop_at, d, SEL_GROUP_LANES));
+  // the pieces in front of it are valid as a whole
+  unsigned long long key = pc.maxp > 0 && ord < stop_at ? sel_key<FWD>(e + pc.maxp, pc.place) : 0ull;
+#pragma unroll
+  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) key = max(key, (unsigned long long)__shfl_xor(key, d, SEL_GROUP_LANES));
+  const unsigned long long best = max(wk.best, key);
+  // the piece it stops in, byte by byte, by the lane that holds it (every lane walks its word: no lane waits for less)
+  const unsigned long long walked = sel_walk_piece<FWD>(v, in, c, pos0, e, best);
+  const unsigned at = min(stop_at, SEL_GROUP_LANES - 1);
+  const unsigned long long from_owner = __shfl(walked, FWD ? at : SEL_GROUP_LANES - 1 - at, SEL_GROUP_LANES);
+  if (!wk.stopped) {
+    wk.best = stop_at < SEL_GROUP_LANES ? from_owner : best;
+    wk.stopped = stop_at < SEL_GROUP_LANES;
+  }
+  wk.ent += sum;
+}
+
+// One request (word 8 k + sub in lane sub, k = 0, 1) of a walk over the places [a, b) of a line whose first byte sits at byte
+// `lead` of its first word: its words in walk order.  A word is left out when no record of the WAVE has anything for the walk
+// in it -- the walk has stopped, or the word lies behind the interval; most walks stop in the first word they meet.
+template <bool FWD>
+__device__ __forceinline__ void sel_walk_step(SelWalk &wk, const uint4 (&v)[SEL_UNROLL], unsigned p0, unsigned sub, int lead, int a, int b, int c) {
+#pragma unroll
+  for (unsigned kk = 0; kk < SEL_UNROLL; kk++) {
+    const unsigned k = FWD ? kk : SEL_UNROLL - 1 - kk;
+    const int first = (int)(p0 + 16u * SEL_GROUP_LANES * k) - lead;  // the place of the eight words' first byte
+    const bool idle = wk.stopped || (FWD ? first >= b : first + (int)(16u * SEL_GROUP_LANES) <= a);  // (the same in a record's lanes)
+    if (__all(idle)) continue;  // (uniform)
+    sel_walk_word<FWD>(wk, v[k], first + (int)(16u * sub), sub, a, b, c);
+  }
+}
+
+// TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at
+template <bool TRIM>
+__global__ void __launch_bounds__(SEL_THREADS)
+k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
+               const fqgpu_trim t, const fqgpu_filter f, uint32_t *__restrict__ ksize, uint32_t *__restrict__ hstart,
+               uint32_t *__restrict__ win, unsigned long long *__restrict__ keep, SelectResult *__restrict__ res) {
+  constexpr unsigned NC = R_COUNTERS<TRIM>;
+  __shared__ unsigned wg[NC];
+  if (threadIdx.x < NC) wg[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  const bool walk_f = TRIM && t.q_front != 0, walk_t = TRIM && t.q_tail != 0;
+  const bool need_seq = f.max_n != FQGPU_FILTER_NONE, need_qual = walk_f || walk_t || f.min_mean_q != 0 || f.low_q != 0;
+  const unsigned level = 33u + f.low_q;
+  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+  const unsigned long long r = r0 + lane;
+  const bool have = r < n_recs;
+  fqgpu_rec mine = {0u, 0u, 0u};
+  if (have) mine = recs[r];
+  // the start of the record's header line: behind the record in front (its entry sits in the lane in front)
+  unsigned h0 = __shfl_up(mine.qual_off + mine.len + 1u, 1);
+  if (lane == 0) h0 = have && r ? recs[r - 1].qual_off + recs[r - 1].len + 1u : 0u;
+  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len &&
+                  (unsigned long long)mine.qual_off + mine.len <= raw_len;
+  bool bad = have && !ok;
+  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read)
+
+  // the window of a read of `len` symbols left by the fixed cuts, and by the two walks' results
+  const auto cut_lo = [&](unsigned len) { return min(t.cut_front, len); };
+  const auto cut_hi = [&](unsigned len) { return len - min(t.cut_tail, len - min(t.cut_front, len)); };
+  const auto window = [&](unsigned start, unsigned stop) {  // -> start | n << 16
+    if (start >= stop) return 0u;
+    return start | min(stop - start, t.crop) << 16;
+  };
+
+  unsigned n_count = 0, q_bytes = 0, low_count = 0;
+  unsigned my_win = 0;
+  if constexpr (TRIM) my_win = window(cut_lo(read_len), cut_hi(read_len));  // (what holds when no line is read)
+  if (need_seq || need_qual) {  // (uniform)
+    // record j of the wave's 64, for the lanes of the group that reads it
+    const auto fetch = [&](SelStage &st, unsigned j) {
+      st.seq_off = __shfl(mine.seq_off, j);
+      st.qual_off = __shfl(mine.qual_off, j);
+      st.len = __shfl(read_len, j);
+      if (need_seq) sel_load_line(st.s, raw, st.seq_off, st.len, 0, sub);
+      if (need_qual) sel_load_line(st.q, raw, st.qual_off, st.len, 0, sub);
+    };
+    // the lane's words of the request at p0 of a line; [ws, we): the window, in places of the line (TRIM)
+    const auto judge_words = [&](SelCounts &c, const uint4 (&v)[SEL_UNROLL], unsigned off, unsigned len, unsigned p0, int ws, int we, bool is_seq) {
+      const int lead = (int)(off & 15u), span = lead + (int)len;
+#pragma unroll
+      for (unsigned k = 0; k < SEL_UNROLL; k++) {
+        const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
+        if (rel >= span) continue;
+        const int first = max(lead - rel, 0), last = min(span - rel, 16);
+        int wf = 0, wl = 0;
+        if constexpr (TRIM) {
+          wf = min(max(lead + ws - rel, 0), 16);
+          wl = min(max(lead + we - rel, 0), 16);
+        }
+        if (is_seq) sel_judge_seq<TRIM>(c, v[k], first, last, wf, wl);
+        else sel_judge_qual<TRIM>(c, v[k], first, last, wf, wl, level);
+      }
+    };
+    // steps (TRIM): the requests the longest line of the eight records in hand takes (the same in every lane of the wave, so
+    // that the eight lanes of a record stay together through the shuffles of a walk)
+    const auto consume = [&](const SelStage &st, unsigned steps) {
+      SelCounts c = {0u, 0u, 0u, false};
+      unsigned w = 0;
+      if constexpr (TRIM) {
+        const int a = (int)cut_lo(st.len), b = (int)cut_hi(st.len), lead_q = (int)(st.qual_off & 15u);
+        unsigned start = (unsigned)a, stop = (unsigned)b;
+        if (walk_f) {  // (uniform)
+          SelWalk wk = {0, 0ull, false};
+          sel_walk_step<true>(wk, st.q, 0, sub, lead_q, a, b, (int)t.q_front + 33);
+          for (unsigned s = 1; s < steps; s++) {  // a long read: the rest, not loaded ahead
+            uint4 q[SEL_UNROLL];
+            sel_load_line(q, raw, st.qual_off, st.len, s * SEL_STEP_BYTES, sub);
+            sel_walk_step<true>(wk, q, s * SEL_STEP_BYTES, sub, lead_q, a, b, (int)t.q_front + 33);
+          }
+          if (wk.best) start = SEL_PLACE - (unsigned)(wk.best & SEL_PLACE);
+        }
+        if (walk_t) {
+          SelWalk wk = {0, 0ull, false};
+          for (unsigned s = steps - 1; s >= 1; s--) {  // a long read: from its last request down
+            uint4 q[SEL_UNROLL];
+            sel_load_line(q, raw, st.qual_off, st.len, s * SEL_STEP_BYTES, sub);
+            sel_walk_step<false>(wk, q, s * SEL_STEP_BYTES, sub, lead_q, a, b, (int)t.q_tail + 33);
+          }
+          sel_walk_step<false>(wk, st.q, 0, sub, lead_q, a, b, (int)t.q_tail + 33);
+          if (wk.best) stop = (unsigned)(wk.best & SEL_PLACE);
+        }
+        w = window(start, stop);
+        const int ws = (int)(w & 0xFFFFu), we = ws + (int)(w >> 16);
+        if (need_seq) judge_words(c, st.s, st.seq_off, st.len, 0, ws, we, true);
+        if (need_qual) judge_words(c, st.q, st.qual_off, st.len, 0, ws, we, false);
+        for (unsigned s = 1; s < steps; s++) {
+          uint4 x[SEL_UNROLL];
+          if (need_seq) {
+            sel_load_line(x, raw, st.seq_off, st.len, s * SEL_STEP_BYTES, sub);
+            judge_words(c, x, st.seq_off, st.len, s * SEL_STEP_BYTES, ws, we, true);
+          }
+          if (need_qual) {
+            sel_load_line(x, raw, st.qual_off, st.len, s * SEL_STEP_BYTES, sub);
+            judge_words(c, x, st.qual_off, st.len, s * SEL_STEP_BYTES, ws, we, false);
+          }
+        }
+      } else {
+        // the words a line can touch, counted from the aligned word of its first byte: the two lines start at different places
+        const unsigned span_s = need_seq && st.len ? (st.seq_off & 15u) + st.len : 0u, span_q = need_qual && st.len ? (st.qual_off & 15u) + st.len : 0u;
+        if (span_s) judge_words(c, st.s, st.seq_off, st.len, 0, 0, 0, true);
+        if (span_q) judge_words(c, st.q, st.qual_off, st.len, 0, 0, 0, false);
+        for (unsigned p0 = SEL_STEP_BYTES; p0 < max(span_s, span_q); p0 += SEL_STEP_BYTES) {  // a long read: the rest, not loaded ahead
+          uint4 s[SEL_UNROLL], q[SEL_UNROLL];
+          if (p0 < span_s) sel_load_line(s, raw, st.seq_off, st.len, p0, sub);
+          if (p0 < span_q) sel_load_line(q, raw, st.qual_off, st.len, p0, sub);
+          if (p0 < span_s) judge_words(c, s, st.seq_off, st.len, p0, 0, 0, true);
+          if (p0 < span_q) judge_words(c, q, st.qual_off, st.len, p0, 0, 0, false);
+        }
+      }
+      // over the record's eight lanes; packed: N and low counts are at most 65535 each, the byte sum below 2^23
+      unsigned x = c.n | c.low << 16, y = c.qsum | (c.bad ? 0x80000000u : 0u);
+#pragma unroll
+      for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+        x += __shfl_xor(x, d);
+        const unsigned o = __shfl_xor(y, d);
+        y = ((y & 0x7FFFFFFFu) + (o & 0x7FFFFFFFu)) | ((y | o) & 0x80000000u);
+      }
+      return make_uint3(x, y, w);
+    };
+    // the requests a record's lines take
+    const unsigned my_span = max(need_seq ? (mine.seq_off & 15u) + read_len : 0u, need_qual ? (mine.qual_off & 15u) + read_len : 0u);
+    const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
+    SelStage cur, nxt;
+    fetch(cur, group);
+#pragma unroll 1
+    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
+      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+      unsigned steps = 1;
+      if constexpr (TRIM) {
+        if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
+          steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
+#pragma unroll
+          for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+          steps = fq_uniform(steps);
+        }
+      }
+      const uint3 got = consume(cur, steps);
+      // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
+      const unsigned from = (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES;
+      const unsigned x = __shfl(got.x, from), y = __shfl(got.y, from);
+      unsigned w = 0;
+      if constexpr (TRIM) w = __shfl(got.z, from);
+      if (lane / SEL_ROUND_RECORDS == k) {
+        n_count = x & 0xFFFFu;
+        low_count = x >> 16;
+        q_bytes = y & 0x7FFFFFFFu;
+        bad = bad || (y >> 31);
+        my_win = w;
+      }
+      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
+    }
+  }
+
+  // the verdict on what is left [start, start + n): 0 kept, 1 .. 5 the first criterion that fails; a read with nothing left
+  // is "short"
+  unsigned start = 0, n = mine.len;
+  if constexpr (TRIM) {
+    start = ok ? my_win & 0xFFFFu : 0u;
+    n = ok ? my_win >> 16 : 0u;
+  }
+  const bool emptied = TRIM && ok && n == 0;
+  unsigned verdict = 0;
+  if (ok) {
+    const unsigned long long phred = need_qual ? q_bytes - 33ull * n : 0ull;
+    if (emptied || n < f.min_len) verdict = 1;
+    else if (n > f.max_len) verdict = 2;
+    else if (need_seq && n_count > f.max_n) verdict = 3;
+    else if (f.min_mean_q && phred < (unsigned long long)f.min_mean_q * n) verdict = 4;
+    else if (f.low_q && 100ull * low_count > (unsigned long long)f.max_low_pct * n) verdict = 5;
+  }
+  const bool kept = ok && verdict == 0;
+  const unsigned hl = mine.seq_off > h0 ? mine.seq_off - h0 : 0u;
+  const unsigned long long size64 = (unsigned long long)hl + 2ull * n + 4ull;
+  if (kept && size64 > 0xFFFFFFFFull) bad = true;  // (a table that is not this chunk's)
+  const unsigned size = kept ? (unsigned)size64 : 0u;
+  bool odd = false;
+  if (have) {
+    ksize[r] = size;
+    hstart[r] = h0;
+    if constexpr (TRIM) win[r] = start | n << 16;
+    odd = mine.qual_off != mine.seq_off + mine.len + 3u || mine.seq_off < h0;
+    if (r == n_recs - 1u) odd = odd || (unsigned long long)mine.qual_off + mine.len + 1ull > raw_len;
+  }
+  const unsigned long long kept_mask = __ballot(kept);
+  if (lane == 0 && r0 < n_recs) keep[r0 / 64] = kept_mask;
+  if (__any(bad) && lane == 0) res->bad = 1u;           // (every writer stores the same value)
+  if (__any(odd) && lane == 0) res->not_bare = 1u;
+
+  // the report: over the wave, over the workgroup, one atomic per counter and workgroup
+  unsigned cnt[NC];
+#pragma unroll
+  for (unsigned i = 0; i < NC; i++) cnt[i] = 0;
+  cnt[R_KEPT] = kept;
+  cnt[R_BASES_IN] = ok ? mine.len : 0u;
+  cnt[R_BASES_KEPT] = kept ? n : 0u;
+#pragma unroll
+  for (unsigned v = 1; v <= 5; v++) cnt[R_DROPPED + v - 1] = verdict == v;
+  if constexpr (TRIM) {
+    cnt[R_TRIMMED] = ok && n != mine.len;
+    cnt[R_CUT_FRONT] = start;
+    cnt[R_CUT_TAIL] = ok ? mine.len - start - n : 0u;
+    cnt[R_EMPTIED] = emptied;
+  }
+  unsigned long long bytes = size;  // (64 records of up to 2^32 - 1 bytes)
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+#pragma unroll
+    for (unsigned i = 1; i < NC; i++)
+      if (i != R_BYTES_KEPT) cnt[i] += __shfl_xor(cnt[i], d);
+    bytes += __shfl_xor(bytes, d);
+  }
+  __shared__ unsigned long long wg_bytes;
+  if (threadIdx.x == 0) wg_bytes = 0;
+  __syncthreads();
+  if (lane == 0) {
+#pragma unroll
+    for (unsigned i = 1; i < NC; i++)
+      if (i != R_BYTES_KEPT && cnt[i]) atomicAdd(&wg[i], cnt[i]);
+    if (bytes) atomicAdd(&wg_bytes, bytes);
+  }
+  __syncthreads();
+  if (threadIdx.x < NC && threadIdx.x != 0) {
+    const unsigned long long v = threadIdx.x == R_BYTES_KEPT ? wg_bytes : wg[threadIdx.x];
+    if (v) atomicAdd(&res->w[threadIdx.x], v);
+  }
+}
+
+// the record that holds byte o of the output: the last r in [lo, hi] with koff[r] <= o (a dropped record has no byte, so
+// koff[r] == koff[r + 1] there and the search steps over it); the caller knows koff[lo] <= o
+__device__ __forceinline__ unsigned sel_find(const unsigned long long *__restrict__ koff, unsigned lo, unsigned hi, unsigned long long o) {
+  while (lo < hi) {
+    const unsigned mid = lo + ((hi - lo + 1) >> 1);
+    if (koff[mid] <= o) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+struct __attribute__((packed)) SelU128 { uint32_t a, b, c, d; };  // sixteen bytes at any address
+
+// a kept record as the gather sees it: where its pieces come from
+struct SelRec {
+  long long h0, seq, qual;  // the header line, the first kept byte of the sequence and of the quality line, in the chunk
+  unsigned hl, n;           // bytes of the header line with its '\n'; symbols of the window
+  bool whole;               // untrimmed
+};
+__device__ __forceinline__ SelRec sel_rec(const fqgpu_rec *__restrict__ recs, const uint32_t *__restrict__ hstart,
+                                          const uint32_t *__restrict__ win, unsigned r) {
+  const fqgpu_rec rec = recs[r];
+  const unsigned h0 = hstart[r], w = win[r];
+  SelRec c;
+  c.h0 = h0;
+  c.hl = rec.seq_off > h0 ? rec.seq_off - h0 : 0u;
+  c.n = w >> 16;
+  c.seq = (long long)rec.seq_off + (w & 0xFFFFu);
+  c.qual = (long long)rec.qual_off + (w & 0xFFFFu);
+  c.whole = c.n == rec.len;
+  return c;
+}
+// byte j of the record's trimmed canonical form
+__device__ __forceinline__ unsigned sel_byte(const uint8_t *__restrict__ raw, const SelRec &c, unsigned long long j) {
+  if (j < c.hl) return raw[c.h0 + (long long)j];
+  j -= c.hl;
+  if (j < c.n) return raw[c.seq + (long long)j];
+  j -= c.n;
+  if (j < 3) return j == 1 ? '+' : '\n';
+  j -= 3;
+  if (j < c.n) return raw[c.qual + (long long)j];
+  return '\n';
+}
+
+// TRIM: out[koff[r], koff[r + 1]) = header line | seq[start, start + n) | "\n+\n" | qual[start, start + n) | '\n' for every
+// kept record r; bare: the chunk's '+' lines are bare, so a whole record is one span of the chunk.  Without TRIM every kept
+// record is whole and the kernel is for bare '+' lines alone (k_select_gather_records takes the others): out[koff[r] + i] =
+// raw[hstart[r] + i]; recs, win and bare are not looked at.
+template <bool TRIM>
+__global__ void __launch_bounds__(SEL_GATHER_THREADS)
+k_select_gather(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs, const uint32_t *__restrict__ hstart,
+                const uint32_t *__restrict__ win, const unsigned long long *__restrict__ koff, unsigned n_recs, unsigned long long total,
+                const bool bare, uint8_t *__restrict__ dst) {
+  const unsigned long long t0 = (unsigned long long)blockIdx.x * SEL_TILE_BYTES;
+  if (t0 >= total) return;
+  const unsigned long long t1 = min(total, t0 + SEL_TILE_BYTES) - 1;  // the tile's last byte
+  // (uniform: the compiler keeps these searches in scalar registers)
+  const unsigned r_lo = sel_find(koff, 0, n_recs - 1, t0), r_hi = sel_find(koff, r_lo, n_recs - 1, t1);
+  const long long d_lo = (long long)hstart[r_lo] - (long long)koff[r_lo], d_hi = (long long)hstart[r_hi] - (long long)koff[r_hi];
+  // equal shifts: the records between are kept whole, or the source would have moved on without the output
+  bool one_run = d_lo == d_hi;
+  if constexpr (TRIM) one_run = bare && d_lo == d_hi && (win[r_lo] >> 16) == recs[r_lo].len && (win[r_hi] >> 16) == recs[r_hi].len;
+#pragma unroll
+  for (unsigned k = 0; k < SEL_GATHER_WORDS; k++) {
+    const unsigned long long o = t0 + 16ull * (k * SEL_GATHER_THREADS + threadIdx.x);
+    if (o >= total) continue;
+    const unsigned long long last = min(o + 15, total - 1);
+    long long src = (long long)o + d_lo;
+    bool copy = one_run;
+    unsigned ra = r_lo;
+    SelRec ca = {0, 0, 0, 0u, 0u, false};
+    if (!one_run) {  // (uniform)
+      ra = sel_find(koff, r_lo, r_hi, o);
+      const unsigned rb = sel_find(koff, ra, r_hi, last);
+      if constexpr (!TRIM) {
+        const long long delta = (long long)hstart[ra] - (long long)koff[ra];
+        copy = ra == rb || delta == (long long)hstart[rb] - (long long)koff[rb];  // inside one run
+        src = (long long)o + delta;
+      } else {
+        ca = sel_rec(recs, hstart, win, ra);
+        const unsigned long long j0 = o - koff[ra], j1 = last - koff[ra];
+        const unsigned long long q0 = (unsigned long long)ca.hl + ca.n + 3u;  // the quality window's first byte in the record
+        if (bare && ca.whole && (ra == rb || ((win[rb] >> 16) == recs[rb].len &&
+                                              ca.h0 - (long long)koff[ra] == (long long)hstart[rb] - (long long)koff[rb]))) {
+          copy = true;  // inside one run of whole records
+          src = ca.h0 + (long long)j0;
+        } else if (ra == rb && last == o + 15) {
+          if (j1 < ca.hl) {
+            copy = true;
+            src = ca.h0 + (long long)j0;
+          } else if (j0 >= ca.hl && j1 < (unsigned long long)ca.hl + ca.n) {
+            copy = true;
+            src = ca.seq + (long long)(j0 - ca.hl);
+          } else if (j0 >= q0 && j1 < q0 + ca.n) {
+            copy = true;
+            src = ca.qual + (long long)(j0 - q0);
+          }
+        }
+      }
+    }
+    uint4 v;
+    if (copy) {  // (sixteen bytes from a byte of the chunk: at most fifteen of the block's spare bytes behind it)
+      const SelU128 s = *reinterpret_cast<const SelU128 *>(raw + src);
+      v = make_uint4(s.a, s.b, s.c, s.d);
+    } else if constexpr (!TRIM) {  // across a seam between two runs: byte by byte, every byte by its run's shift
+      unsigned w[4] = {0, 0, 0, 0};
+      unsigned rr = ra;
+      unsigned long long next = koff[rr + 1];  // the first output byte that is no longer record rr's
+      long long dd = src - (long long)o;
+      for (unsigned i = 0; o + i <= last; i++) {
+        if (o + i >= next) {
+          rr = sel_find(koff, rr + 1, r_hi, o + i);
+          next = koff[rr + 1];
+          dd = (long long)hstart[rr] - (long long)koff[rr];
+        }
+        w[i >> 2] |= (unsigned)raw[(long long)(o + i) + dd] << (8 * (i & 3));
+      }
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {  // across a seam between two pieces or two records: byte by byte
+      unsigned w[4] = {0, 0, 0, 0};
+      unsigned rr = ra;
+      SelRec c = ca;
+      unsigned long long base = koff[rr], next = koff[rr + 1];
+      for (unsigned i = 0; o + i <= last; i++) {
+        if (o + i >= next) {
+          rr = sel_find(koff, rr + 1, r_hi, o + i);
+          c = sel_rec(recs, hstart, win, rr);
+          base = koff[rr];
+          next = koff[rr + 1];
+        }
+        w[i >> 2] |= sel_byte(raw, c, o + i - base) << (8 * (i & 3));
+      }
+      v = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    *reinterpret_cast<uint4 *>(dst + o) = v;  // (dst has room up to the next multiple of 16)
+  }
+}
+
+// a filter alone on a chunk with text behind a '+': one wave per kept record, the canonical form put together
+// (k_crc_canon_write); a correctness path, but twice as fast there as k_select_gather<true>'s pieces
+__global__ void __launch_bounds__(256)
+k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
+                        const uint32_t *__restrict__ ksize, const uint32_t *__restrict__ hstart,
+                        const unsigned long long *__restrict__ koff, uint8_t *__restrict__ dst) {
+  const unsigned waves = (gridDim.x * blockDim.x) >> 6, lane = fq_lane();
+  for (unsigned r = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; r < n_recs; r += waves) {
+    if (!ksize[r]) continue;  // (uniform)
+    const fqgpu_rec rec = recs[r];
+    const unsigned h0 = hstart[r], hl = rec.seq_off > h0 ? rec.seq_off - h0 : 0u;
+    uint8_t *d = dst + koff[r];
+    for (unsigned i = lane; i < hl; i += 64) d[i] = raw[h0 + i];  // (ends with the header's '\n')
+    d += hl;
+    for (unsigned i = lane; i < rec.len; i += 64) { d[i] = raw[rec.seq_off + i]; d[rec.len + 3 + i] = raw[rec.qual_off + i]; }
+    if (lane == 0) { d[rec.len] = '\n'; d[rec.len + 1] = '+'; d[rec.len + 2] = '\n'; d[2 * rec.len + 3] = '\n'; }
+  }
+}
+
+}  // namespace
+
+void SelectScratch::release() {
+  for (DevBuf *b : {&ksize, &hstart, &win, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
+  if (host) (void)hipHostFree(host);
+  host = nullptr;
+}
+
+// The reads of the chunk raw_dev[0, raw_len) with the record table recs_dev, trimmed by *t (nullptr: the filter alone) and
+// then judged by *f, on st, waited for.  Two waits: the judge's result words decide what is gathered and how much room it
+// needs; the gathered bytes come down in one copy.  FQGPU_E_ARG with *out_len = 0 and report, keep bits and windows zeroed: a
+// byte that cannot be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
+int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                    const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
+                    uint8_t *keep_out, uint32_t *win_out) {
+  *out_len = 0;
+  for (unsigned i = 0; i < FQGPU_TRIM_REPORT_WORDS; i++) report[i] = 0;
+  if (n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  if (!n_recs) return FQGPU_OK;
+  if (!t) win_out = nullptr;  // (a filter has no windows)
+  SelectScratch &ss = ctx->select;
+  const char *const span = t ? "trim" : "filter";
+  const unsigned R = (unsigned)n_recs;
+  const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
+  int rc;
+  if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
+      (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
+    return rc;
+  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
+  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
+  uint32_t *const win = t ? ss.win.as<uint32_t>() : nullptr;
+  FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
+  fq_timer_span_begin(ctx, span, st);
+  const auto judge = t ? &k_select_judge<true> : &k_select_judge<false>;
+  const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
+  hipLaunchKernelGGL(judge, dim3((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64))),
+                     dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
+                     ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>());
+  FQ_HIP(hipGetLastError());
+  if (out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
+    fq_timer_span_end(ctx, st);
+    return rc;
+  }
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipMemcpyAsync(ss.host, ss.res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  if (keep_out) FQ_HIP(hipMemcpyAsync(keep_out, ss.keep.p, (n_recs + 7) / 8, hipMemcpyDeviceToHost, st));
+  if (win_out) FQ_HIP(hipMemcpyAsync(win_out, win, n_recs * 4, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  if (res.bad) {
+    if (keep_out) memset(keep_out, 0, (n_recs + 7) / 8);
+    if (win_out) memset(win_out, 0, n_recs * 4);
+    return FQGPU_E_ARG;
+  }
+  for (unsigned i = 1; i < FQGPU_TRIM_REPORT_WORDS; i++) report[i] = res.w[i];
+  report[0] = n_recs;
+  const size_t total = (size_t)res.w[R_BYTES_KEPT];
+  *out_len = total;
+  if (!out || !total) return FQGPU_OK;
+  if (out_cap < total) return FQGPU_E_OVERFLOW;
+  if ((rc = ss.dst.reserve(total + 64))) return rc;
+  fq_timer_span_begin(ctx, span, st);
+  if (t || !res.not_bare)
+    hipLaunchKernelGGL(gather, dim3((unsigned)((total + SEL_TILE_BYTES - 1) / SEL_TILE_BYTES)), dim3(SEL_GATHER_THREADS), 0, st, raw_dev,
+                       recs_dev, ss.hstart.as<uint32_t>(), win, ss.koff.as<unsigned long long>(), R, (unsigned long long)total,
+                       res.not_bare == 0u, ss.dst.as<uint8_t>());
+  else
+    hipLaunchKernelGGL(k_select_gather_records, dim3((unsigned)min((n_recs + 3) / 4, (size_t)8192)), dim3(256), 0, st, raw_dev, recs_dev, R,
+                       ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), ss.koff.as<unsigned long long>(), ss.dst.as<uint8_t>());
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipGetLastError());
+  FQ_HIP(hipMemcpyAsync(out, ss.dst.p, total, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  return FQGPU_OK;
+}

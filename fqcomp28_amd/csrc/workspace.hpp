@@ -642,43 +642,7 @@ public:
    *  stays empty.  There is no host fallback and FQGPU_SHIM_HOST_HEADERS does not apply: a chunk the device refuses throws
    *  std::runtime_error naming the chunk and the record. */
   void decodeChunkFiltered(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_filter &filter, uint64_t *report) {
-    StageClock clk;
-    last_digest_ = {};
-    const auto refused = [&](const std::string &what) {
-      return std::runtime_error("decodeChunkFiltered: chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
-    };
-    if (fqgpu_filter_check(&filter) != FQGPU_OK) throw std::invalid_argument("decodeChunkFiltered: a filter fqgpu_filter_check refuses");
-    ChunkArgs a;
-    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
-    clk.lap("misc");
-    piece.clear();
-    piece.idx = cbs.chunk_idx;
-    // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
-    struct CheckOnly {
-      fqgpu_ctx *ctx;
-      bool restore;
-      ~CheckOnly() { if (restore) (void)fqgpu_ctx_set_check_only(ctx, 0); }
-    } mode{ctx_, !check_only_};
-    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, 1), "decodeChunkFiltered");
-    RecordTable recs(a.n_recs);
-    std::size_t laid_out = 0, bad = 0;
-    const StreamArgs &s = a.s;
-    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
-                                      s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], nullptr,
-                                      cbs.original_size.total, recs.data(), &laid_out, &bad);
-    if (rc != FQGPU_OK)
-      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
-                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
-    clk.lap("gpu");
-    takeDigest();
-    // the kept bytes are never more than the chunk: one call, no size query
-    piece.raw_data.resize(cbs.original_size.total);
-    std::size_t len = 0;
-    const int frc = fqgpu_chunk_filter(ctx_, &filter, reinterpret_cast<uint8_t *>(piece.raw_data.data()), piece.raw_data.size(), &len, report, nullptr);
-    if (frc != FQGPU_OK) throw refused(std::string("the filter: ") + fqgpu_strerror(frc));
-    piece.raw_data.resize(len);
-    clk.lap("filter");
-    clk.done(cbs.chunk_idx);
+    decodeChunkSelected(piece, cbs, nullptr, &filter, report, "decodeChunkFiltered");
   }
 
   /** Extension: the reads of the chunk trimmed by `trim` and then judged by `filter` (nullptr: every read that is not emptied
@@ -688,45 +652,7 @@ public:
    *  setVerify is on, and one call fills a buffer of the chunk's recorded size, which is always enough.  No host fallback: a
    *  chunk the device refuses throws std::runtime_error naming the chunk and the record. */
   void decodeChunkTrimmed(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim &trim, const fqgpu_filter *filter, uint64_t *report) {
-    StageClock clk;
-    last_digest_ = {};
-    const auto refused = [&](const std::string &what) {
-      return std::runtime_error("decodeChunkTrimmed: chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
-    };
-    if (fqgpu_trim_check(&trim) != FQGPU_OK) throw std::invalid_argument("decodeChunkTrimmed: a trim fqgpu_trim_check refuses");
-    if (filter && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument("decodeChunkTrimmed: a filter fqgpu_filter_check refuses");
-    ChunkArgs a;
-    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
-    clk.lap("misc");
-    piece.clear();
-    piece.idx = cbs.chunk_idx;
-    // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
-    struct CheckOnly {
-      fqgpu_ctx *ctx;
-      bool restore;
-      ~CheckOnly() { if (restore) (void)fqgpu_ctx_set_check_only(ctx, 0); }
-    } mode{ctx_, !check_only_};
-    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, 1), "decodeChunkTrimmed");
-    RecordTable recs(a.n_recs);
-    std::size_t laid_out = 0, bad = 0;
-    const StreamArgs &s = a.s;
-    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
-                                      s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], nullptr,
-                                      cbs.original_size.total, recs.data(), &laid_out, &bad);
-    if (rc != FQGPU_OK)
-      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
-                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
-    clk.lap("gpu");
-    takeDigest();
-    // a trimmed record is never longer than the record: one call, no size query
-    piece.raw_data.resize(cbs.original_size.total);
-    std::size_t len = 0;
-    const int trc = fqgpu_chunk_trim(ctx_, &trim, filter, reinterpret_cast<uint8_t *>(piece.raw_data.data()), piece.raw_data.size(), &len,
-                                     report, nullptr, nullptr);
-    if (trc != FQGPU_OK) throw refused(std::string("the trim: ") + fqgpu_strerror(trc));
-    piece.raw_data.resize(len);
-    clk.lap("trim");
-    clk.done(cbs.chunk_idx);
+    decodeChunkSelected(piece, cbs, &trim, filter, report, "decodeChunkTrimmed");
   }
 
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
@@ -747,6 +673,53 @@ public:
   }
 
 private:
+  /** decodeChunkFiltered (trim == nullptr; the filter is needed) and decodeChunkTrimmed, `who` of the two: the check-only
+   *  decode, the digest, then ONE fqgpu_chunk_filter / fqgpu_chunk_trim into a buffer of the chunk's recorded size -- the kept
+   *  bytes are never more than the chunk, so there is no size query */
+  void decodeChunkSelected(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim *trim, const fqgpu_filter *filter,
+                           uint64_t *report, const char *who) {
+    StageClock clk;
+    last_digest_ = {};
+    const std::string name(who), step(trim ? "trim" : "filter");
+    const auto refused = [&](const std::string &what) {
+      return std::runtime_error(name + ": chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
+    };
+    if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
+    if ((filter || !trim) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
+    clk.lap("misc");
+    piece.clear();
+    piece.idx = cbs.chunk_idx;
+    // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
+    struct CheckOnly {
+      fqgpu_ctx *ctx;
+      bool restore;
+      ~CheckOnly() { if (restore) (void)fqgpu_ctx_set_check_only(ctx, 0); }
+    } mode{ctx_, !check_only_};
+    fqgpuCheck(fqgpu_ctx_set_check_only(ctx_, 1), who);
+    RecordTable recs(a.n_recs);
+    std::size_t laid_out = 0, bad = 0;
+    const StreamArgs &s = a.s;
+    const int rc = fqgpu_decode_chunk(ctx_, &a.hdr, a.readlens, a.n_recs, s.seq, s.seq_len, s.qual, s.qual_len, s.n_count, s.n_count_len,
+                                      s.n_pos, s.n_pos_len, s.index[0], s.index_len[0], s.index[1], s.index_len[1], nullptr,
+                                      cbs.original_size.total, recs.data(), &laid_out, &bad);
+    if (rc != FQGPU_OK)
+      throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
+                                                         : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
+    clk.lap("gpu");
+    takeDigest();
+    piece.raw_data.resize(cbs.original_size.total);
+    uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
+    std::size_t len = 0;
+    const int src = trim ? fqgpu_chunk_trim(ctx_, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
+                         : fqgpu_chunk_filter(ctx_, filter, out, piece.raw_data.size(), &len, report, nullptr);
+    if (src != FQGPU_OK) throw refused("the " + step + ": " + fqgpu_strerror(src));
+    piece.raw_data.resize(len);
+    clk.lap(step.c_str());
+    clk.done(cbs.chunk_idx);
+  }
+
   /** decodeChunk through fqgpu_decode_chunk; false: the device refused the chunk (the host path decides) */
   bool decodeChunkOnDevice(FastqChunk &chunk, CompressedBuffersSrc &cbs) {
     StageClock clk;

@@ -545,7 +545,7 @@ int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filte
  *   fqgpu_trim_check    host only: FQGPU_OK or FQGPU_E_ARG
  *   fqgpu_chunk_trim    the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_filter is valid,
  *                       on the same stream.  It leaves the chunk as it is: digest, summary and a plain filter before or after
- *                       give the same results, and it shares no scratch with the filter calls.
+ *                       give the same results (every call is waited for before it returns).
  *   fqgpu_dblock_trim   waits for the block's last operation as fqgpu_dblock_filter does.
  * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_trim_check works. */
 typedef struct {

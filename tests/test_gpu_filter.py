@@ -1,4 +1,4 @@
-"""The read filter on the device (fqcomp28_amd/csrc/filter.hip behind fqgpu_chunk_filter / fqgpu_dblock_filter) against the
+"""The read filter on the device (fqcomp28_amd/csrc/select.hip behind fqgpu_chunk_filter / fqgpu_dblock_filter) against the
 numpy restatement in filter_ref.py: the kept bytes, the report and the keep bits.  Integer arithmetic: every comparison is exact."""
 import ctypes as C
 import os
@@ -39,10 +39,10 @@ def ctx(F, golden_dir):
 
 
 def filter_constants():
-    """the tiling of filter.hip, from its source"""
-    src = open(os.path.join(ROOT, "fqcomp28_amd", "csrc", "filter.hip")).read()
-    return {k: int(re.search(r"constexpr unsigned %s = (\d+);" % k, src).group(1))
-            for k in ("FILT_THREADS", "FILT_WAVE_RECORDS", "FILT_GROUP_LANES", "FILT_UNROLL", "FILT_GATHER_THREADS", "FILT_GATHER_WORDS")}
+    """the tiling of select.hip, from its source: its SEL_* constants under the names the tests here use"""
+    src = open(os.path.join(ROOT, "fqcomp28_amd", "csrc", "select.hip")).read()
+    return {"FILT_" + k: int(re.search(r"constexpr unsigned SEL_%s = (\d+);" % k, src).group(1))
+            for k in ("THREADS", "WAVE_RECORDS", "GROUP_LANES", "UNROLL", "GATHER_THREADS", "GATHER_WORDS")}
 
 
 def build(entries, seed=1):

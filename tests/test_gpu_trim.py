@@ -1,4 +1,4 @@
-"""Read trimming on the device (fqcomp28_amd/csrc/trim.hip behind fqgpu_chunk_trim / fqgpu_dblock_trim) against the numpy
+"""Read trimming on the device (fqcomp28_amd/csrc/select.hip behind fqgpu_chunk_trim / fqgpu_dblock_trim) against the numpy
 restatement in trim_ref.py: the kept bytes, the report, the keep bits and the windows, byte for byte.  Integer arithmetic:
 every comparison is exact."""
 import ctypes as C
@@ -43,10 +43,10 @@ def ctx(F, golden_dir):
 
 
 def trim_constants():
-    """the tiling of trim.hip, from its source"""
-    src = open(os.path.join(ROOT, "fqcomp28_amd", "csrc", "trim.hip")).read()
-    return {k: int(re.search(r"constexpr unsigned %s = (\d+);" % k, src).group(1))
-            for k in ("TRIM_THREADS", "TRIM_WAVE_RECORDS", "TRIM_GROUP_LANES", "TRIM_UNROLL", "TRIM_GATHER_THREADS", "TRIM_GATHER_WORDS")}
+    """the tiling of select.hip, from its source: its SEL_* constants under the names the tests here use"""
+    src = open(os.path.join(ROOT, "fqcomp28_amd", "csrc", "select.hip")).read()
+    return {"TRIM_" + k: int(re.search(r"constexpr unsigned SEL_%s = (\d+);" % k, src).group(1))
+            for k in ("THREADS", "WAVE_RECORDS", "GROUP_LANES", "UNROLL", "GATHER_THREADS", "GATHER_WORDS")}
 
 
 def chunk_of(hls, phreds, seed=1, n_rate=0.0, plus_repeats=False, n_at=None):
@@ -615,3 +615,67 @@ def test_the_launches_are_timed_as_trim(F, golden_dir):
     assert all(ms >= 0 for name, ms, _ in groups if name == "trim")
     b.close()
     c.close()
+
+
+# ---------------------------------------------------------------- 6. filter and trim calls share one scratch on a handle
+SHARED_COUNTS = (257, 1, 65)   # records of the chunks, in the order of the calls: the buffers grow, are far too large, then a little
+SHARED_FILTER = dict(min_mean_q=25)
+
+
+def shared_chunks():
+    """per count a chunk with bare '+' lines and one whose '+' lines repeat the header, reads of at most 300 bases -> [(what, raw,
+    recs, the filter's reference, the trim's reference)].  The inputs are checked here, on the host: the filter alone keeps some
+    but not all reads of a chunk, the trim cuts at least one.  A chunk of ONE read cannot keep some and not all: its read is kept
+    by the trim call, and by the filter alone in the bare chunk but not in the other (its low ends are cut first there), so
+    that both the empty and the one-record output are met."""
+    f, t = FR.flt(**SHARED_FILTER), R.trm(**Q20)
+    chunks = []
+    for n in SHARED_COUNTS:
+        for repeats in (False, True):
+            if n == 1:   # a clean plateau; a plateau between two low ends that pull the mean of the whole read below the level
+                rng = np.random.default_rng(40 + repeats)
+                raw, recs = chunk_of([9], [plateau(rng, 300, 100, 60) if repeats else plateau(rng, 299, 0, 5)], 42, plus_repeats=repeats)
+            else:
+                raw, recs = drawn(np.random.default_rng(30 + n + repeats).integers(3, 301, n), 50 + n + repeats, plus_repeats=repeats)
+            what = "%d records, %s" % (n, "'+' lines repeat the header" if repeats else "bare '+' lines")
+            want_f, want_t = FR.filter_records(raw, recs, f), R.trim_records(raw, recs, t, f)
+            kept_f, kept_t = int(want_f[1][FR.N_KEPT]), int(want_t[1][R.N_KEPT])
+            assert int(recs["len"].max()) <= 300 and len(recs) == n, what
+            assert int(want_t[1][R.READS_TRIMMED]) >= 1 and 0 < kept_t, what + ": the trim cuts nothing or nothing is left: a vacuous input"
+            assert (0 < kept_f < n and kept_t < n) if n > 1 else kept_f == (0 if repeats else 1), what + ": the filter keeps all or nothing: a vacuous input"
+            chunks.append((what, raw, recs, want_f, want_t))
+    return chunks
+
+
+def test_filter_and_trim_calls_in_turn_on_one_handle(F, ctx):
+    """one SelectScratch and one driver serve both calls: whatever a call leaves behind -- windows, flags of a refused chunk,
+    buffers sized for a larger chunk -- the next call's result is the reference's"""
+    f, t = FR.flt(**SHARED_FILTER), R.trm(**Q20)
+
+    def filter_holds(g, want, what):
+        assert g["rc"] == 0, (what, g["rc"])
+        assert g["report"].tolist() == want[1].tolist() and g["keep"].tolist() == want[2].tolist(), what
+        assert g["out_len"] == want[0].size and g["out"].tobytes() == want[0].tobytes(), what
+
+    for what, raw, recs, want_f, want_t in shared_chunks():
+        spoilt = raw.copy()
+        r = recs[len(recs) // 2]
+        spoilt[int(r["qual_off"]) + int(r["len"]) // 2] = 200
+        b, bad = ctx.dblock(raw, recs), ctx.dblock(spoilt, recs)
+        first = b.filter(f)
+        filter_holds(first, want_f, what + ": the filter")
+        holds(b.trim(t, f), want_t, what + ": the trim behind a filter")
+        again = b.filter(f)
+        filter_holds(again, want_f, what + ": the filter behind a trim")
+        keep = np.full((len(recs) + 7) // 8, 0xAA, dtype=np.uint8)
+        win = np.full(len(recs), 0xAAAAAAAA, dtype=np.uint32)
+        out = np.full(raw.size, 0x5A, dtype=np.uint8)
+        rc, n, report = raw_call(F, ctx, bad, t, f, out, out.size, keep, win)
+        assert rc == E_ARG and n == 0 and not report.any() and not keep.any() and not win.any() and (out == 0x5A).all(), what + ": a quality byte of 200"
+        last = b.filter(f)
+        filter_holds(last, want_f, what + ": the filter behind a refused call")
+        for g in (again, last):
+            assert all(np.array_equal(g[k], first[k]) for k in ("out", "report", "keep")) and g["out_len"] == first["out_len"], what
+        holds(b.trim(t, f), want_t, what + ": the trim behind all of them")
+        b.close()
+        bad.close()
