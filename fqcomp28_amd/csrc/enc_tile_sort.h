@@ -33,9 +33,24 @@ static_assert(TS_TILE % TS_BATCH == 0 && TS_TILE % TS_SUB == 0 && TS_SUB % PACK_
 #ifdef FQGPU_EXPERIMENTS
 #define TS_PROF_DECL unsigned long long ts_t_ = wall_clock64();
 #define TS_PROF(slot) do { if (threadIdx.x == 0) { const unsigned long long n_ = wall_clock64(); atomicAdd(&g_ts_prof[slot], n_ - ts_t_); ts_t_ = n_; } } while (0)
+// K3's loaders: a second clock on thread 64, summed in registers over the periods of the batch loop (an atomic per reading would
+// sit in the very memory queue whose wait is measured) and added to g_ts_prof[32 + 8 * (sequence ? 1 : 0) + leg] behind the
+// loop.  Legs: 0 the wait for the batch requested one period earlier -- taken at the TOP of the period in this build, in front
+// of finish(), where nothing younger than the request is in the queue; the product waits behind finish(), i.e. for
+// max(0, leg 0 - leg 1) --, 1 finish, 2 deposit, 3 request, 4 the barrier (waiting for the ranking wave).
+#define TS_LPROF_DECL unsigned long long ts_l_ = 0, ts_leg_[5] = {0, 0, 0, 0, 0};
+#define TS_LPROF_START do { if (threadIdx.x == 64) ts_l_ = wall_clock64(); } while (0)
+#define TS_LPROF(leg) do { if (threadIdx.x == 64) { const unsigned long long n_ = wall_clock64(); ts_leg_[leg] += n_ - ts_l_; ts_l_ = n_; } } while (0)
+#define TS_LPROF_WAIT do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); } while (0)
+#define TS_LPROF_FLUSH(base) do { if (threadIdx.x == 64) for (int l_ = 0; l_ < 5; l_++) atomicAdd(&g_ts_prof[(base) + l_], ts_leg_[l_]); } while (0)
 #else
 #define TS_PROF_DECL
 #define TS_PROF(slot) do { } while (0)
+#define TS_LPROF_DECL
+#define TS_LPROF_START do { } while (0)
+#define TS_LPROF(leg) do { } while (0)
+#define TS_LPROF_WAIT do { } while (0)
+#define TS_LPROF_FLUSH(base) do { } while (0)
 #endif
 
 // run r of a tile (runs are listed in context order = order of their local start):
@@ -351,6 +366,8 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
   // only for such tiles; the ranks are the same numbers either way.
   const bool combine = s_max * 8u >= nt;
   const unsigned long long lanes_le = (2ull << lane) - 1ull;
+  TS_LPROF_DECL
+  TS_LPROF_START;
   for (unsigned j = 0; j <= nbatch; j++) {  // (one period more than there are batches: the last batch is finished in it)
     if (wave == 0 && j < nbatch && combine) {
       const uint16_t *kb = reinterpret_cast<const uint16_t *>(kb4[j % NBUF]);
@@ -427,13 +444,20 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
       if (lane == 0) atomicAdd(&g_ts_prof[PS + 4], wall_clock64() - tr0);
 #endif
     } else if (wave != 0) {
+      TS_LPROF_WAIT;
+      TS_LPROF(0);
       if (j >= 1 && !combine) finish(j - 1);         // ranked in the period before
+      TS_LPROF(1);
       if (j >= 1 && j + 1 < nbatch) deposit(j + 1);  // requested one period ago, into the buffer finish() has just emptied
       if (j == 0 && nbatch > 1) deposit(1);
+      TS_LPROF(2);
       if (j + 2 < nbatch) request(j + 2);
+      TS_LPROF(3);
     }
     lds_barrier();
+    TS_LPROF(4);
   }
+  TS_LPROF_FLUSH(32 + (QUAL ? 0 : 8));
   TS_PROF(PS + 1);
 
   // ---- the tile's runs, in context order: cur16[c] is now the END of context c's run
@@ -518,32 +542,41 @@ k_tile_partition(const void *__restrict__ ckey_v, const uint8_t *__restrict__ cs
   TS_PROF(PS + 7);
   // The sorted tile goes out in pieces of 16 positions per thread.  A piece that lies inside ONE run -- nearly all of them
   // for the sequence stream (runs of 128), most for the quality stream -- is one 16-byte LDS read, one run lookup and one
-  // 16-byte store (round 3: a run lookup = two LDS reads and a global read, and a byte store, per POSITION); a piece with
-  // run boundaries inside walks its bytes, stepping to the next run where the boundary map says so.  +1.3 % on the step.
+  // 16-byte store (round 3: a run lookup = two LDS reads and a global read, and a byte store, per POSITION).  +1.3 % on the step.
   // (The same for K6's gather of the (nb, bits) LOST 11 %: there a piece with boundaries walks sixteen dependent global
   // loads where the position-major loop keeps sixteen independent ones in flight per thread.)
-  for (unsigned p0 = tid * 16u; p0 < nt; p0 += TS_THREADS * 16u) {
+  // A piece with a run boundary inside, or cut short by the tile's end, is not walked by its lane (sixteen steps of a branch,
+  // a run lookup and a byte store each, which the whole wave sat through for the one lane in nine that had such a piece): the
+  // wave takes the pieces its ballot names four at a time, lane 16 q + i byte i of the q-th of them -- one run lookup and
+  // one byte store per lane, consecutive lanes on consecutive bytes of a run.  The ballot is a scalar: the next four pieces
+  // come from four s_ff1, nothing goes through LDS and no other wave is waited for.
+  for (unsigned pb = wave * 1024u; pb < nt; pb += TS_THREADS * 16u) {  // (wave-uniform trip count: the ballot needs every lane)
+    const unsigned p0 = pb + lane * 16u;  // (below TS_TILE, whatever nt: map and lsym are there to be read)
     const unsigned wd = p0 >> 5, shb = p0 & 31u;  // (p0 is a multiple of 16: the piece is one half of a map word)
     const unsigned mw = rm.bm[wd];
     const unsigned starts = (mw >> shb) & 0xFFFFu;   // run starts at positions p0 .. p0 + 15
-    unsigned r = (unsigned)rm.wpre[wd] + __popc(mw & ((1u << shb) - 1u)) + (starts & 1u) - 1u;  // run of position p0
-    const uint4 v = *reinterpret_cast<const uint4 *>(lsym + p0);
-    const unsigned n = min(16u, nt - p0);
     auto delta_of = [&](unsigned run) {
       if (run < GD_CAP) return gd[run];
       const uint2 e = rlist[run];
       return e.x - (e.y & 0xFFFFu);
     };
-    unsigned delta = delta_of(r);
-    if ((starts & 0xFFFEu) == 0u && n == 16u) {
-      *reinterpret_cast<FqBytes16 *>(sorted_sym + p0 + delta) = FqBytes16{{v.x, v.y, v.z, v.w}};  // (16 bytes at any address)
-    } else {
-      const unsigned w4[4] = {v.x, v.y, v.z, v.w};
+    const bool whole = p0 + 16u <= nt && (starts & 0xFFFEu) == 0u;
+    if (whole) {
+      const unsigned r = (unsigned)rm.wpre[wd] + __popc(mw & ((1u << shb) - 1u)) + (starts & 1u) - 1u;  // run of position p0
+      const uint4 v = *reinterpret_cast<const uint4 *>(lsym + p0);
+      *reinterpret_cast<FqBytes16 *>(sorted_sym + p0 + delta_of(r)) = FqBytes16{{v.x, v.y, v.z, v.w}};  // (16 bytes at any address)
+    }
+    unsigned long long todo = __ballot(p0 < nt && !whole);
+    while (todo) {  // (uniform)
+      unsigned pc[4];
 #pragma unroll
-      for (unsigned i = 0; i < 16; i++) {
-        if (i && ((starts >> i) & 1u)) { r++; delta = delta_of(r); }
-        if (i < n) sorted_sym[p0 + i + delta] = (uint8_t)(w4[i >> 2] >> (8u * (i & 3u)));
+      for (unsigned q = 0; q < 4; q++) {
+        pc[q] = todo ? (unsigned)__ffsll((long long)todo) - 1u : 0xFFFFu;  // (none left: a piece behind any tile's end)
+        todo &= todo - 1ull;
       }
+      const unsigned q = lane >> 4;
+      const unsigned p = pb + (q == 0 ? pc[0] : q == 1 ? pc[1] : q == 2 ? pc[2] : pc[3]) * 16u + (lane & 15u);
+      if (p < nt) sorted_sym[p + delta_of(ts_run_of(rm, p))] = lsym[p];
     }
   }
 #ifdef FQGPU_EXPERIMENTS

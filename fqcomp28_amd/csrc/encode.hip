@@ -37,14 +37,17 @@
 #include <type_traits>
 
 #ifdef FQGPU_EXPERIMENTS
-__device__ unsigned long long g_ts_prof[32];
+__device__ unsigned long long g_ts_prof[48];  // [32 ..]: K3's loader clock (thread 64), eight slots per stream
 void fq_ts_prof_dump() {
-  unsigned long long h[32];
+  unsigned long long h[48];
   if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ts_prof), sizeof(h)) != hipSuccess) return;
   const char *names[4] = {"partition<Qual>", "partition<Seq>", "gather_pack<Qual>", "gather_pack<Seq>"};
   for (int k = 0; k < 4; k++)
     fprintf(stderr, "ts_prof %-18s phase ticks (100 MHz, summed over workgroups): %llu %llu %llu %llu | ranker alone %llu | K3: store wait %llu patch %llu run map %llu\n",
             names[k], h[8 * k], h[8 * k + 1], h[8 * k + 2], h[8 * k + 3], h[8 * k + 4], h[8 * k + 5], h[8 * k + 6], h[8 * k + 7]);
+  for (int k = 0; k < 2; k++)
+    fprintf(stderr, "ts_prof %-18s loader thread 64, ticks summed over workgroups: wait for the requested batch (taken in front of finish) %llu | finish %llu | deposit %llu | request %llu | barrier %llu\n",
+            names[k], h[32 + 8 * k], h[33 + 8 * k], h[34 + 8 * k], h[35 + 8 * k], h[36 + 8 * k]);
 }
 #endif
 
