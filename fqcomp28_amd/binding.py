@@ -154,6 +154,11 @@ _PROTOS = {
                                    C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_trim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
                                     C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_adapter_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t),
+                                   C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                    C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -362,6 +367,32 @@ def _trim_call(fn, front, trim, flt, n_recs, want_win=True, **kw):
     return dict(_select_call(fn, front, (trim, flt), n_recs, more=(win,), **kw), win=win)
 
 
+ADAPTER_MAX = 64
+CLIP_REPORT_NAMES = TRIM_REPORT_NAMES + ("reads_with_adapter", "bases_cut_adapter")
+
+
+def read_adapter(seq, min_overlap=5, max_err_pct=10, reserved=0, length=None):
+    """an fqgpu_adapter (include/fqgpu.h) as a uint32 array of twenty words: the sixty-four bytes of seq, zero behind it, then
+    len, min_overlap, max_err_pct, reserved.  seq: str or bytes, at most ADAPTER_MAX of it is stored; length: what len says
+    when it is not len(seq) (for the checks' tests)"""
+    seq = seq.encode() if isinstance(seq, str) else bytes(seq)
+    a = np.zeros(ADAPTER_MAX // 4 + 4, dtype=np.uint32)
+    a[:ADAPTER_MAX // 4].view(np.uint8)[:min(len(seq), ADAPTER_MAX)] = np.frombuffer(seq[:ADAPTER_MAX], dtype=np.uint8)
+    a[ADAPTER_MAX // 4:] = (len(seq) if length is None else length, min_overlap, max_err_pct, reserved)
+    return a
+
+
+def adapter_check(adapter):
+    """fqgpu_adapter_check -> rc (host only)"""
+    return lib().fqgpu_adapter_check(_p(adapter))
+
+
+def _clip_call(fn, front, adapter, trim, flt, n_recs, want_win=True, **kw):
+    """A device clip call -> dict(rc, out, out_len, report, keep, win) as _trim_call; adapter, trim, flt None: NULL"""
+    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
+    return dict(_select_call(fn, front, (adapter, trim, flt), n_recs, more=(win,), **kw), win=win)
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -478,6 +509,12 @@ class DBlock:
         win); see _trim_call"""
         return _trim_call(lib().fqgpu_dblock_trim, (self.ctx.h, self.h), trim, flt, self.n_recs, **kw)
 
+    def clip(self, adapter, trim=None, flt=None, **kw):
+        """fqgpu_dblock_clip: the reads of the raw block clipped at `adapter` (read_adapter; None: no adapter), trimmed by
+        `trim` (None: nothing beyond the clip) and then judged by `flt` -> dict(rc, out, out_len, report, keep, win); see
+        _trim_call"""
+        return _clip_call(lib().fqgpu_dblock_clip, (self.ctx.h, self.h), adapter, trim, flt, self.n_recs, **kw)
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -588,6 +625,11 @@ class Context:
         """fqgpu_chunk_trim: the reads of the chunk on the staging block (n_recs records) trimmed by `trim` and then judged by
         `flt`, where chunk_filter is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
         return _trim_call(lib().fqgpu_chunk_trim, (self.h,), trim, flt, n_recs, **kw)
+
+    def chunk_clip(self, adapter, n_recs, trim=None, flt=None, **kw):
+        """fqgpu_chunk_clip: the reads of the chunk on the staging block (n_recs records) clipped at `adapter`, trimmed by
+        `trim` and then judged by `flt`, where chunk_trim is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
+        return _clip_call(lib().fqgpu_chunk_clip, (self.h,), adapter, trim, flt, n_recs, **kw)
 
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""

@@ -96,6 +96,17 @@ extern "C" int fqgpu_trim_check(const fqgpu_trim *t) {
   return FQGPU_OK;
 }
 
+// Adapter clipping (select.hip applies it): what an adapter may say.
+extern "C" int fqgpu_adapter_check(const fqgpu_adapter *a) {
+  if (!a || a->len < 1u || a->len > FQGPU_ADAPTER_MAX || a->min_overlap < 1u || a->min_overlap > a->len || a->max_err_pct > 50u || a->reserved)
+    return FQGPU_E_ARG;
+  for (unsigned j = 0; j < FQGPU_ADAPTER_MAX; j++) {
+    const uint8_t c = a->seq[j];
+    if (j < a->len ? c != 'A' && c != 'C' && c != 'G' && c != 'T' : c != 0) return FQGPU_E_ARG;
+  }
+  return FQGPU_OK;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

@@ -236,11 +236,12 @@ struct StatsScratch {
 };
 
 // Selection of the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip): per record the kept size, the
-// start of its header line and -- reserved by a trim call alone -- its window, the keep bits, the offsets of the kept records
+// start of its header line and -- reserved by a trim call alone -- its window, beside it -- by a clip call alone -- its clip
+// place (a uint16_t: k_adapter_find writes it, the judge reads it), the keep bits, the offsets of the kept records
 // in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
 // filter and trim calls: each is waited for before it returns.
 struct SelectScratch {
-  DevBuf ksize, hstart, win, keep, koff, dst, res, scan_tmp;
+  DevBuf ksize, hstart, win, clip, keep, koff, dst, res, scan_tmp;
   void *host = nullptr;
   void release();
 };
@@ -437,13 +438,14 @@ int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, siz
 int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                    unsigned positions, uint64_t *out);
 
-// The reads of a chunk in HBM trimmed by *t (nullptr: the filter alone, win_out is not looked at) and then judged by *f
+// The reads of a chunk in HBM clipped at the adapter *a (nullptr: none; one needs a trim, which may cut nothing), trimmed by
+// *t (nullptr: the filter alone, win_out is not looked at) and then judged by *f
 // (select.hip; both have passed their checks), on st, waited for: report (FQGPU_TRIM_REPORT_WORDS, which are
 // FQGPU_FILTER_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
 // into out
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                    const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
-                    uint8_t *keep_out, uint32_t *win_out);
+                    const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

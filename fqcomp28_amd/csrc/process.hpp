@@ -682,20 +682,23 @@ inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &
 }
 
 namespace detail {
-/** processArchiveFiltered (trim == nullptr; the filter is needed) and processArchiveTrimmed, `who` of the two: every block
- *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed), only the kept bytes come down and
+/** processArchiveFiltered (trim == nullptr; the filter is needed), processArchiveTrimmed and processArchiveClipped (with an
+ *  adapter, trim and filter may both be nullptr; reported as a trim), `who` of the three: every block
+ *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed / decodeChunkClipped), only the kept bytes come down and
  *  reach the file.  A usable `<archive>.fqx` is used, and with a usable `<archive>.fqs` every chunk is verified before any
  *  of it is written: the digest is of the WHOLE restored chunk, as the writer took it.  Never builds an index.  The kept
  *  sizes are known only after the decode, so the blocks go through OrderedPieceWriter as the FASTA pieces do: handed out in
  *  order, placed by the sizes published so far; a failed run leaves neither `<out>` nor `<out>.part`.  rep.in counts what
  *  was written; the chunks' reports, added word by word, go to rep.filter or rep.trim. */
 inline FarmReport processArchiveSelected(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim *trim,
-                                         const fqgpu_filter *filter, const Settings &set, const char *who) {
+                                         const fqgpu_filter *filter, const Settings &set, const char *who,
+                                         const fqgpu_adapter *adapter = nullptr) {
   static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one report size for both");
   constexpr unsigned W = FQGPU_FILTER_REPORT_WORDS;
   const std::string name(who);
+  if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
   if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-  if ((filter || !trim) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+  if ((filter || !(trim || adapter)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
   Archive archive(archive_path);
   const std::size_t n_blocks = archive.chunkOffsets().size() - 1;
   std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
@@ -729,7 +732,8 @@ inline FarmReport processArchiveSelected(const path_t &archive_path, const path_
         used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
       }
       clk.lap("read");
-      if (trim) wksp[t]->decodeChunkTrimmed(piece, cbs, *trim, filter, report);
+      if (adapter) wksp[t]->decodeChunkClipped(piece, cbs, *adapter, trim, filter, report);
+      else if (trim) wksp[t]->decodeChunkTrimmed(piece, cbs, *trim, filter, report);
       else wksp[t]->decodeChunkFiltered(piece, cbs, *filter, report);
       clk.lap("decode");
       verifier.check(cbs, wksp[t]->lastDigest());  // (before anything of the chunk reaches the file)
@@ -748,7 +752,7 @@ inline FarmReport processArchiveSelected(const path_t &archive_path, const path_
   }, [&] { stopped.store(true); writer.abort(); });
   writer.flush();
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::vector<uint64_t> &sum = trim ? rep.trim : rep.filter;
+  std::vector<uint64_t> &sum = trim || adapter ? rep.trim : rep.filter;
   sum.assign(W, 0);
   for (unsigned t = 0; t < T; ++t) {
     rep.in += istats[t];
@@ -776,6 +780,16 @@ inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_
 inline FarmReport processArchiveTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim &trim,
                                         const fqgpu_filter *filter, const Settings &set) {
   return detail::processArchiveSelected(archive_path, mates1_out, &trim, filter, set, "processArchiveTrimmed");
+}
+
+/** Extension: `d --adapter SEQ [--adapter-overlap N] [--adapter-err PCT]`, with or without the trim and filter options -- the
+ *  reads clipped at the 3' adapter (fqgpu_chunk_clip's step 0), then trimmed by `trim` (nullptr: nothing more is cut) and
+ *  judged by `filter` (nullptr: every read that is not emptied is kept), in input order (detail::processArchiveSelected).
+ *  rep.in counts what was written; rep.trim is the trim's report with words 14 and 15, the reads in which the adapter was
+ *  found and the bases it took. */
+inline FarmReport processArchiveClipped(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter &adapter,
+                                        const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
+  return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveClipped", &adapter);
 }
 
 /** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function

@@ -35,6 +35,11 @@
 // walk and forwards again for the counts, loading as it goes: a correctness path.  Without TRIM the window is the line, and a
 // long read is one loop over the rest of its requests.
 //
+// k_adapter_find -- in front of the judge when an adapter is given (fqgpu_chunk_clip, fqgpu_dblock_clip): one pass over the
+// sequence lines in the judge's access pattern, the search itself bit-parallel -- a word's bases as four bit planes, every
+// place a shift, four ANDs with the adapter's planes and a population count.  It leaves one uint16_t per record, the clip
+// place, which the judge (its flag CLIP) takes for the read's length in the trim's steps; the gather sees only windows.
+//
 // fq_scan_u32_to_u64 -- the kept sizes become the records' places in the output.
 //
 // k_select_gather -- the compacting copy, driven by the DESTINATION: a workgroup owns an aligned tile of the output, every
@@ -80,6 +85,7 @@ struct SelectResult {
 constexpr unsigned R_KEPT = 1, R_BASES_IN = 2, R_BASES_KEPT = 3, R_BYTES_KEPT = 4, R_DROPPED = 5, R_TRIMMED = 10, R_CUT_FRONT = 11,
                    R_CUT_TAIL = 12, R_EMPTIED = 13;
 template <bool TRIM> constexpr unsigned R_COUNTERS = TRIM ? 14 : 10;  // the words a judge counts
+constexpr unsigned R_WITH_ADAPTER = 14, R_CUT_ADAPTER = 15, R_COUNTERS_CLIP = 16;  // ... behind an adapter search
 
 constexpr unsigned SW_H = 0x80808080u, SW_L = 0x01010101u;
 // per byte of x (every byte < 128), 0 <= k <= 128: bit 7 set where the byte is >= k
@@ -274,13 +280,212 @@ __device__ __forceinline__ void sel_walk_step(SelWalk &wk, const uint4 (&v)[SEL_
   }
 }
 
-// TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at
-template <bool TRIM>
+// ---- the adapter search.  A word's sixteen bases are four bit planes of sixteen bits (bit j: byte j of the word is that
+// base), two planes to a register: A below C, G below T.
+struct ClipWord {
+  unsigned ac, gt;
+};
+constexpr unsigned CLIP_GATHER = 0x00204081u;  // x * this: the bits 7, 15, 23, 31 of x side by side in the bits 28 .. 31
+
+// The planes of one word; `in`: a bit for each byte inside the line, the others come out as "no base".  bad: a byte inside
+// the line that is none of ACGTN.
+__device__ __forceinline__ ClipWord clip_planes(const uint4 v, unsigned in, bool &bad) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  unsigned pa = 0, pc = 0, pg = 0, pt = 0, fine = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned y = w[i] & ~SW_H;
+    const unsigned ea = sw_eq(y, 'A'), ec = sw_eq(y, 'C'), eg = sw_eq(y, 'G'), et = sw_eq(y, 'T');
+    pa |= (ea * CLIP_GATHER) >> 28 << (4 * i);
+    pc |= (ec * CLIP_GATHER) >> 28 << (4 * i);
+    pg |= (eg * CLIP_GATHER) >> 28 << (4 * i);
+    pt |= (et * CLIP_GATHER) >> 28 << (4 * i);
+    // one of ACGTN, and below 128 (the compares see the low seven bits alone)
+    fine |= (((ea | ec | eg | et | sw_eq(y, 'N')) & ~w[i]) * CLIP_GATHER) >> 28 << (4 * i);
+  }
+  if (~fine & in) bad = true;
+  ClipWord r;
+  r.ac = (pa & in) | (pc & in) << 16;
+  r.gt = (pg & in) | (pt & in) << 16;
+  return r;
+}
+
+// the adapter as the search takes it: its planes (bit j: A[j] is that base), its length and the two limits
+struct ClipAdapter {
+  unsigned long long a, c, g, t;
+  unsigned m, min_overlap, keep_pct;  // keep_pct: 100 - max_err_pct
+};
+
+// The sixteen places of one word: own, and the four words behind it (n[0] the next one), give the 80 bases a place can look
+// at; place0: the place in the line of the word's byte 0 (negative in front of the line), len: the line's length.  ->  a bit
+// for every place that is a hit.  The read's planes are zero outside the line and the adapter's behind its end, so the
+// population count IS the number of matches among the ov = min(m, len - p) bases compared.
+__device__ __forceinline__ unsigned clip_word_hits(const ClipWord own, const ClipWord (&n)[4], const ClipAdapter &ad, bool wide, int place0, int len) {
+  // per plane three registers: the bases 0 .. 31, 32 .. 63, 64 .. 79 from the word's first
+  const unsigned a0 = __builtin_amdgcn_perm(n[0].ac, own.ac, 0x05040100u), c0 = __builtin_amdgcn_perm(n[0].ac, own.ac, 0x07060302u);
+  const unsigned g0 = __builtin_amdgcn_perm(n[0].gt, own.gt, 0x05040100u), t0 = __builtin_amdgcn_perm(n[0].gt, own.gt, 0x07060302u);
+  const unsigned a1 = __builtin_amdgcn_perm(n[2].ac, n[1].ac, 0x05040100u), c1 = __builtin_amdgcn_perm(n[2].ac, n[1].ac, 0x07060302u);
+  const unsigned g1 = __builtin_amdgcn_perm(n[2].gt, n[1].gt, 0x05040100u), t1 = __builtin_amdgcn_perm(n[2].gt, n[1].gt, 0x07060302u);
+  const unsigned a2 = n[3].ac & 0xFFFFu, c2 = n[3].ac >> 16, g2 = n[3].gt & 0xFFFFu, t2 = n[3].gt >> 16;
+  const unsigned al = (unsigned)ad.a, cl = (unsigned)ad.c, gl = (unsigned)ad.g, tl = (unsigned)ad.t;
+  const unsigned ah = (unsigned)(ad.a >> 32), ch = (unsigned)(ad.c >> 32), gh = (unsigned)(ad.g >> 32), th = (unsigned)(ad.t >> 32);
+  unsigned hits = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    unsigned eq = (__builtin_amdgcn_alignbit(a1, a0, j) & al) | (__builtin_amdgcn_alignbit(c1, c0, j) & cl) |
+                  (__builtin_amdgcn_alignbit(g1, g0, j) & gl) | (__builtin_amdgcn_alignbit(t1, t0, j) & tl);
+    int matches = __popc(eq);
+    if (wide) {  // (uniform) an adapter of more than 32 bases
+      eq = (__builtin_amdgcn_alignbit(a2, a1, j) & ah) | (__builtin_amdgcn_alignbit(c2, c1, j) & ch) |
+           (__builtin_amdgcn_alignbit(g2, g1, j) & gh) | (__builtin_amdgcn_alignbit(t2, t1, j) & th);
+      matches += __popc(eq);
+    }
+    const int p = place0 + j, ov = min((int)ad.m, len - p);
+    // 100 * mism <= max_err_pct * ov, with mism = ov - matches
+    const bool hit = p >= 0 && ov >= (int)ad.min_overlap && 100 * matches >= (int)ad.keep_pct * ov;
+    hits |= hit ? 1u << j : 0u;
+  }
+  return hits;
+}
+
+// One request of a line (word 8 k + sub in lane sub, k = 0, 1) searched by the record's eight lanes together: x its planes,
+// nx those of the NEXT request's first word (zero when the line ends in this one; more: some record of the wave has a next
+// request), p0 and lead as in sel_load_line.  -> the smallest hit among the lane's places, or CLIP_NONE.
+constexpr unsigned CLIP_NONE = 0xFFFFFFFFu;
+__device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL], const ClipWord nx, bool more, const ClipAdapter &ad, bool wide,
+                                                 unsigned p0, unsigned sub, int lead, int len) {
+  // the four words behind each of the lane's two: from the lanes behind it, and past lane 7 from the next word of lane 0 on
+  ClipWord n0[4], n1[4];
+#pragma unroll
+  for (unsigned d = 1; d <= 4; d++) {
+    const unsigned src = (sub + d) & (SEL_GROUP_LANES - 1);
+    const bool wrap = sub + d >= SEL_GROUP_LANES;
+    ClipWord b0, b1, b2 = {0u, 0u};
+    b0.ac = __shfl(x[0].ac, src, SEL_GROUP_LANES);
+    b0.gt = __shfl(x[0].gt, src, SEL_GROUP_LANES);
+    b1.ac = __shfl(x[1].ac, src, SEL_GROUP_LANES);
+    b1.gt = __shfl(x[1].gt, src, SEL_GROUP_LANES);
+    if (more) {  // (uniform)
+      b2.ac = __shfl(nx.ac, src, SEL_GROUP_LANES);
+      b2.gt = __shfl(nx.gt, src, SEL_GROUP_LANES);
+    }
+    n0[d - 1] = wrap ? b1 : b0;
+    n1[d - 1] = wrap ? b2 : b1;
+  }
+  unsigned best = CLIP_NONE;
+#pragma unroll
+  for (unsigned kk = 0; kk < SEL_UNROLL; kk++) {
+    const unsigned k = SEL_UNROLL - 1 - kk;  // (the later word first: the earlier one's hit replaces its)
+    const int first = (int)(p0 + 16u * SEL_GROUP_LANES * k) - lead;  // the place of the eight words' first byte
+    if (__all(first >= len)) continue;  // (uniform) no record of the wave has a base there
+    const int place0 = first + (int)(16u * sub);
+    const unsigned hits = clip_word_hits(x[k], k ? n1 : n0, ad, wide, place0, len);
+    if (hits) best = (unsigned)(place0 + (int)__builtin_ctz(hits));
+  }
+  return best;
+}
+
+// clip[r] = the clip place of record r (include/fqgpu.h, step 0): the smallest place at which the adapter hits, or the
+// read's length.  The judge's access pattern -- a wave takes 64 records with one table load, eight lanes read a record's
+// sequence line as aligned 16-byte words, the next eight records' words in flight -- and nothing of its arithmetic: a word
+// becomes bit planes once, every place of it is then tested with shifts, ANDs and a population count, a lane taking the bases
+// behind its word from its neighbours' planes by shuffles.  The line is judged over all its bytes on the way (ACGTN), so the
+// judge behind this kernel does not read it again for that.  A read longer than one request walks the requests forwards with
+// the next request's planes in hand: a correctness path.
+__global__ void __launch_bounds__(SEL_THREADS)
+k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
+               unsigned long long plane_a, unsigned long long plane_c, unsigned long long plane_g, unsigned long long plane_t,
+               unsigned m, unsigned min_overlap, unsigned max_err_pct, uint16_t *__restrict__ clip, SelectResult *__restrict__ res) {
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  const ClipAdapter ad = {plane_a, plane_c, plane_g, plane_t, m, min_overlap, 100u - max_err_pct};
+  const bool wide = m > 32u;
+  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+  const unsigned long long r = r0 + lane;
+  const bool have = r < n_recs;
+  fqgpu_rec mine = {0u, 0u, 0u};
+  if (have) mine = recs[r];
+  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len;
+  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read; the judge refuses it)
+  const unsigned my_span = (mine.seq_off & 15u) + read_len;
+  const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
+
+  struct Stage {
+    unsigned off, len;
+    uint4 s[SEL_UNROLL];
+  };
+  const auto fetch = [&](Stage &st, unsigned j) {
+    st.off = __shfl(mine.seq_off, j);
+    st.len = __shfl(read_len, j);
+    sel_load_line(st.s, raw, st.off, st.len, 0, sub);
+  };
+  // the planes of the lane's words of the request at p0
+  const auto planes = [&](ClipWord (&x)[SEL_UNROLL], const uint4 (&v)[SEL_UNROLL], const Stage &st, unsigned p0, bool &bad) {
+    const int lead = (int)(st.off & 15u), span = st.len ? lead + (int)st.len : 0;
+#pragma unroll
+    for (unsigned k = 0; k < SEL_UNROLL; k++) {
+      const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
+      x[k] = clip_planes(v[k], sel_bits(lead - rel, span - rel), bad);
+    }
+  };
+  unsigned my_clip = read_len;
+  bool my_bad = false;
+  Stage cur, nxt;
+  fetch(cur, group);
+#pragma unroll 1
+  for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
+    if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+    unsigned steps = 1;
+    if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
+      steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+      steps = fq_uniform(steps);
+    }
+    const int lead = (int)(cur.off & 15u);
+    bool bad = false;
+    ClipWord x[SEL_UNROLL];
+    planes(x, cur.s, cur, 0, bad);
+    unsigned best = CLIP_NONE;
+    for (unsigned s = 0; s < steps; s++) {
+      ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
+      if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
+        uint4 v[SEL_UNROLL];
+        sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
+        planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
+      }
+      best = min(best, clip_request(x, y[0], s + 1 < steps, ad, wide, s * SEL_STEP_BYTES, sub, lead, (int)cur.len));
+#pragma unroll
+      for (unsigned i = 0; i < SEL_UNROLL; i++) x[i] = y[i];
+    }
+    // over the record's eight lanes: the smallest hit, and "a byte that cannot be judged" in the top bit
+    unsigned got = min(best, cur.len) | (bad ? 0x80000000u : 0u);
+#pragma unroll
+    for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+      const unsigned o = __shfl_xor(got, d);
+      got = min(got & 0x7FFFFFFFu, o & 0x7FFFFFFFu) | ((got | o) & 0x80000000u);
+    }
+    // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
+    const unsigned mine_got = __shfl(got, (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES);
+    if (lane / SEL_ROUND_RECORDS == k) {
+      my_clip = mine_got & 0x7FFFFFFFu;
+      my_bad = mine_got >> 31;
+    }
+    if (k + 1 < SEL_GROUP_LANES) cur = nxt;
+  }
+  if (have) clip[r] = (uint16_t)my_clip;
+  if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
+}
+
+// TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at.  CLIP (with TRIM): clip[r]
+// stands for the read's length in the trim's steps 1 to 4 (k_adapter_find has written it, and has judged the sequence line)
+template <bool TRIM, bool CLIP = false>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
                const fqgpu_trim t, const fqgpu_filter f, uint32_t *__restrict__ ksize, uint32_t *__restrict__ hstart,
-               uint32_t *__restrict__ win, unsigned long long *__restrict__ keep, SelectResult *__restrict__ res) {
-  constexpr unsigned NC = R_COUNTERS<TRIM>;
+               uint32_t *__restrict__ win, unsigned long long *__restrict__ keep, SelectResult *__restrict__ res,
+               const uint16_t *__restrict__ clip) {
+  static_assert(TRIM || !CLIP, "a clip is a trim's step 0");
+  constexpr unsigned NC = CLIP ? R_COUNTERS_CLIP : R_COUNTERS<TRIM>;
   __shared__ unsigned wg[NC];
   if (threadIdx.x < NC) wg[threadIdx.x] = 0;
   __syncthreads();
@@ -311,7 +516,9 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
 
   unsigned n_count = 0, q_bytes = 0, low_count = 0;
   unsigned my_win = 0;
-  if constexpr (TRIM) my_win = window(cut_lo(read_len), cut_hi(read_len));  // (what holds when no line is read)
+  unsigned eff_len = read_len;  // the length the trim sees: the clip place behind an adapter search
+  if constexpr (CLIP) eff_len = ok ? min((unsigned)clip[r], read_len) : 0u;
+  if constexpr (TRIM) my_win = window(cut_lo(eff_len), cut_hi(eff_len));  // (what holds when no line is read)
   if (need_seq || need_qual) {  // (uniform)
     // record j of the wave's 64, for the lanes of the group that reads it
     const auto fetch = [&](SelStage &st, unsigned j) {
@@ -340,11 +547,12 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
     };
     // steps (TRIM): the requests the longest line of the eight records in hand takes (the same in every lane of the wave, so
     // that the eight lanes of a record stay together through the shuffles of a walk)
-    const auto consume = [&](const SelStage &st, unsigned steps) {
+    const auto consume = [&](const SelStage &st, unsigned steps, unsigned eff) {  // eff: CLIP, the record's eff_len
       SelCounts c = {0u, 0u, 0u, false};
       unsigned w = 0;
       if constexpr (TRIM) {
-        const int a = (int)cut_lo(st.len), b = (int)cut_hi(st.len), lead_q = (int)(st.qual_off & 15u);
+        const unsigned cut_len = CLIP ? eff : st.len;
+        const int a = (int)cut_lo(cut_len), b = (int)cut_hi(cut_len), lead_q = (int)(st.qual_off & 15u);
         unsigned start = (unsigned)a, stop = (unsigned)b;
         if (walk_f) {  // (uniform)
           SelWalk wk = {0, 0ull, false};
@@ -412,6 +620,8 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
 #pragma unroll 1
     for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
       if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+      unsigned eff = 0;
+      if constexpr (CLIP) eff = __shfl(eff_len, SEL_ROUND_RECORDS * k + group);
       unsigned steps = 1;
       if constexpr (TRIM) {
         if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
@@ -421,7 +631,7 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
           steps = fq_uniform(steps);
         }
       }
-      const uint3 got = consume(cur, steps);
+      const uint3 got = consume(cur, steps, eff);
       // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
       const unsigned from = (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES;
       const unsigned x = __shfl(got.x, from), y = __shfl(got.y, from);
@@ -487,6 +697,10 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
     cnt[R_CUT_FRONT] = start;
     cnt[R_CUT_TAIL] = ok ? mine.len - start - n : 0u;
     cnt[R_EMPTIED] = emptied;
+  }
+  if constexpr (CLIP) {
+    cnt[R_WITH_ADAPTER] = ok && eff_len < mine.len;
+    cnt[R_CUT_ADAPTER] = ok ? mine.len - eff_len : 0u;
   }
   unsigned long long bytes = size;  // (64 records of up to 2^32 - 1 bytes)
 #pragma unroll
@@ -671,29 +885,31 @@ k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__rest
 }  // namespace
 
 void SelectScratch::release() {
-  for (DevBuf *b : {&ksize, &hstart, &win, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
+  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
   if (host) (void)hipHostFree(host);
   host = nullptr;
 }
 
-// The reads of the chunk raw_dev[0, raw_len) with the record table recs_dev, trimmed by *t (nullptr: the filter alone) and
-// then judged by *f, on st, waited for.  Two waits: the judge's result words decide what is gathered and how much room it
+// The reads of the chunk raw_dev[0, raw_len) with the record table recs_dev, clipped at the adapter *a (nullptr: none; with
+// one, t is a trim), trimmed by *t (nullptr: the filter alone) and then judged by *f, on st, waited for.  Two waits: the judge's result words decide what is gathered and how much room it
 // needs; the gathered bytes come down in one copy.  FQGPU_E_ARG with *out_len = 0 and report, keep bits and windows zeroed: a
 // byte that cannot be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                    const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
-                    uint8_t *keep_out, uint32_t *win_out) {
+                    const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
+                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
   *out_len = 0;
   for (unsigned i = 0; i < FQGPU_TRIM_REPORT_WORDS; i++) report[i] = 0;
   if (n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  if (a && !t) return FQGPU_E_ARG;
   if (!n_recs) return FQGPU_OK;
   if (!t) win_out = nullptr;  // (a filter has no windows)
   SelectScratch &ss = ctx->select;
-  const char *const span = t ? "trim" : "filter";
+  const char *const span = a ? "clip" : t ? "trim" : "filter";
   const unsigned R = (unsigned)n_recs;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
   int rc;
   if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
+      (a && (rc = ss.clip.reserve(n_recs * 2))) ||
       (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
     return rc;
   if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
@@ -701,11 +917,19 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   uint32_t *const win = t ? ss.win.as<uint32_t>() : nullptr;
   FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
   fq_timer_span_begin(ctx, span, st);
-  const auto judge = t ? &k_select_judge<true> : &k_select_judge<false>;
+  const dim3 judge_grid((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64)));
+  if (a) {  // the adapter's bit planes: bit j of a plane is set iff A[j] is that base
+    unsigned long long plane[4] = {0, 0, 0, 0};
+    for (unsigned j = 0; j < a->len; j++) plane[a->seq[j] == 'A' ? 0 : a->seq[j] == 'C' ? 1 : a->seq[j] == 'G' ? 2 : 3] |= 1ull << j;
+    hipLaunchKernelGGL(k_adapter_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, plane[0],
+                       plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, ss.clip.as<uint16_t>(), ss.res.as<SelectResult>());
+    FQ_HIP(hipGetLastError());
+  }
+  const auto judge = a ? &k_select_judge<true, true> : t ? &k_select_judge<true> : &k_select_judge<false>;
   const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
-  hipLaunchKernelGGL(judge, dim3((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64))),
-                     dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
-                     ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>());
+  hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
+                     ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>(),
+                     a ? ss.clip.as<uint16_t>() : nullptr);
   FQ_HIP(hipGetLastError());
   if (out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
     fq_timer_span_end(ctx, st);

@@ -561,6 +561,47 @@ int fqgpu_chunk_trim(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f,
 int fqgpu_dblock_trim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
                       size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
 
+/* ---- Extension (nothing in the reference): a 3' ADAPTER clipped from the reads of a chunk, then trimmed, then filtered,
+ * where the chunk lies already -- in HBM.  What fastp, cutadapt and Trimmomatic do to a short-insert read whose 3' end runs
+ * into the sequencing adapter: find the adapter and cut the read there.  An adapter is a string A[0, m) over ACGT,
+ * 1 <= m <= FQGPU_ADAPTER_MAX, with a min_overlap in 1 .. m and a max_err_pct in 0 .. 50.  For a read with the sequence line
+ * s[0, L), integer arithmetic throughout:
+ *   0 the clip       at every place p in 0 .. L-1: ov = min(m, L - p), mism(p) = the number of j < ov with s[p + j] != A[j]
+ *                    (an N in the read is a mismatch; there are no indels).  p is a HIT iff ov >= min_overlap and
+ *                    100 * mism(p) <= max_err_pct * ov.  The clip place a is the SMALLEST hit -- the leftmost one wins even
+ *                    when a later place matches better (fastp's rule for a given adapter), which makes the result independent
+ *                    of how the work is split -- and a = L when there is none.  The search runs over the whole untrimmed line
+ *   1 .. 4           the steps of fqgpu_chunk_trim, on the read as if its length were a: f = min(cut_front, a),
+ *                    t = min(cut_tail, a - f), the two walks over [f, a - t), crop.  A NULL trim cuts nothing beyond the clip
+ *   5 the filter     on the window that is left, as fqgpu_chunk_trim.  a == 0 gives an emptied read: dropped, counted under
+ *                    dropped_short and reads_emptied, its window (0, 0)
+ * Output, keep bits and windows are those of fqgpu_chunk_trim.
+ *   report  FQGPU_TRIM_REPORT_WORDS uint64_t: 0 .. 13 as the trim's report -- word 12, bases_cut_tail, stays the sum of
+ *           L - start - n and so includes the clipped bases; bases_in = word 11 + word 12 + the sum of n over all records keeps
+ *           holding | 14 reads_with_adapter (a < L, kept or not) | 15 bases_cut_adapter (the sum of L - a over all records)
+ *   out == NULL, out_cap < *out_len, keep_out, win_out   as fqgpu_chunk_trim
+ * The sequence line is read iff max_n is on OR an adapter is given, and is then judged over all L bytes by the filter's rule
+ * (a byte outside ACGTN: FQGPU_E_ARG); the quality line is read by the trim's rule alone.  An adapter fqgpu_adapter_check
+ * refuses (len outside 1 .. 64, a byte of seq[0, len) outside upper-case ACGT, a byte behind len that is not zero,
+ * min_overlap outside 1 .. len, max_err_pct above 50, reserved not zero), a trim or filter their checks refuse:
+ * FQGPU_E_ARG, with *out_len = 0, a zeroed report and -- where the chunk itself is refused -- zeroed keep bits and windows.
+ *   fqgpu_adapter_check  host only: FQGPU_OK or FQGPU_E_ARG
+ *   fqgpu_chunk_clip     the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_trim is valid, on
+ *                        the same stream; it leaves the chunk as it is and is waited for before it returns.  a == NULL: exactly
+ *                        fqgpu_chunk_trim with the same t and f (a NULL t is then refused as it is there)
+ *   fqgpu_dblock_clip    waits for the block's last operation as fqgpu_dblock_trim does; a == NULL: exactly fqgpu_dblock_trim.
+ * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_adapter_check works. */
+#define FQGPU_ADAPTER_MAX 64
+typedef struct {
+  uint8_t seq[FQGPU_ADAPTER_MAX];                    /* A[0, len) in "ACGT" (upper case), zero behind */
+  uint32_t len, min_overlap, max_err_pct, reserved;  /* 1 .. 64 | 1 .. len | 0 .. 50 | zero */
+} fqgpu_adapter;
+int fqgpu_adapter_check(const fqgpu_adapter *a);
+int fqgpu_chunk_clip(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
+                     size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
+int fqgpu_dblock_clip(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f,
+                      uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -31,6 +31,15 @@
 //               nothing is left is dropped.  Trimmed and gathered on the device as the filter is, .fqx used and .fqs verified
 //               the same way.  A trim option with c, x, t or s, with --records, --fasta, --index or --index-stride, N above
 //               65535, Q above 64 and --crop 0 are usage errors.  A failed run leaves neither <out.fastq> nor <out.fastq>.part)
+//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT]
+//              (extension: restores the reads with the 3' adapter SEQ (1 .. 64 of ACGT) CLIPPED, with or without the trim and
+//               filter options, which then work on what is left in front of the adapter: the read is cut at the leftmost place
+//               where SEQ, or the part of it that fits in front of the read's end, at least N bases of it (default 5, at most
+//               SEQ's length), matches with at most PCT percent mismatches (default 10, at most 50; an N in the read is a
+//               mismatch, no indels).  A read that starts with the adapter is dropped.  Searched, trimmed and gathered on the
+//               device, .fqx used and .fqs verified as with a trim.  An adapter option with c, x, t or s, with --records,
+//               --fasta, --index or --index-stride, without --adapter, and an adapter fqgpu_adapter_check refuses are usage
+//               errors.  A failed run leaves neither <out.fastq> nor <out.fastq>.part)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -58,7 +67,8 @@
 // bytes read of the archive; with a report "stats": its path, "bases" and "mean_quality" (total Phred / bases, the one
 // number that is no integer and in no report); with a filter "filter": what was read, what was kept and what each
 // criterion dropped ("records" / "raw_bytes" of the line are then what was written); with a trim "trim": the same and the
-// reads trimmed, the bases cut from either end and the reads emptied.  Needs a GPU: no CPU fallback.
+// reads trimmed, the bases cut from either end and the reads emptied, and with an adapter -- then alone -- the reads in which it
+// was found and the bases it took.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -76,6 +86,7 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "usage: fqc_tool c|d <in> <out> [-t N] [-R MiB] [-S MiB] [-d 0,1,..] [--accumulate-n] [--index] [--index-stride KiSymbols] [--checksum] [--records A:B] [--stats report.tsv [--positions P]]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--min-len N] [--max-len N] [--max-n K] [--min-mean-q Q] [--max-low-q Q:PCT]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--cut-front N] [--cut-tail N] [--trim-q5 Q] [--trim-q3 Q] [--crop L] [filter options]\n"
+                         "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
@@ -92,6 +103,8 @@ int main(int argc, char **argv) {
   bool filtered = false;
   fqgpu_trim trim = {0, 0, 0, 0, FQGPU_FILTER_NONE, {0, 0, 0}};
   bool trimmed = false;
+  fqgpu_adapter adapter = {{0}, 0, 5, 10, 0};
+  bool clipped = false, adapter_opt = false;
   // a decimal number of at most nine digits (so that it fits a uint32_t)
   const auto u32 = [](const std::string &t, uint32_t &out) {
     if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
@@ -138,6 +151,20 @@ int main(int argc, char **argv) {
       }
       trimmed = true;
     }
+    else if (a == "--adapter") {
+      const std::string v = val();
+      adapter.len = static_cast<uint32_t>(v.size());  // (too long a one is refused by the check below)
+      std::memset(adapter.seq, 0, sizeof adapter.seq);
+      std::memcpy(adapter.seq, v.data(), std::min<std::size_t>(v.size(), FQGPU_ADAPTER_MAX));
+      clipped = true;
+    } else if (a == "--adapter-overlap" || a == "--adapter-err") {
+      const std::string v = val();
+      if (!u32(v, a == "--adapter-overlap" ? adapter.min_overlap : adapter.max_err_pct)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      adapter_opt = true;
+    }
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
       const std::string v = val();
@@ -182,6 +209,21 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "read trimming: expected --cut-front and --cut-tail 0 .. 65535, --trim-q5 and --trim-q3 0 .. 64, --crop 1 or more\n");
     return 2;
   }
+  if ((clipped || adapter_opt) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "adapter clipping goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (adapter_opt && !clipped) {
+    std::fprintf(stderr, "--adapter-overlap and --adapter-err need --adapter SEQ\n");
+    return 2;
+  }
+  if (clipped) {
+    if (adapter.min_overlap > adapter.len) adapter.min_overlap = adapter.len;  // (N is capped at the adapter's length)
+    if (fqgpu_adapter_check(&adapter) != FQGPU_OK) {
+      std::fprintf(stderr, "adapter clipping: expected --adapter of 1 .. 64 bases ACGT (upper case), --adapter-overlap 1 or more, --adapter-err 0 .. 50\n");
+      return 2;
+    }
+  }
   // (said before any device is touched)
   if (stats_opt && argv[1][0] != 'c') {
     std::fprintf(stderr, "--stats goes with c alone (s <in.fqc> <report.tsv> summarises an archive): not with d, x, t or s\n");
@@ -205,6 +247,7 @@ int main(int argc, char **argv) {
     const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
+                         : clipped ? processArchiveClipped(argv[2], argv[3], adapter, trimmed ? &trim : nullptr, filtered ? &filter : nullptr, set)
                          : trimmed ? processArchiveTrimmed(argv[2], argv[3], trim, filtered ? &filter : nullptr, set)
                          : filtered ? processArchiveFiltered(argv[2], argv[3], filter, set)
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
@@ -231,17 +274,19 @@ int main(int argc, char **argv) {
       std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
     }
     if (filtered) {
-      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
+      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
       std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
                   "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
                   w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
     }
-    if (trimmed) {
+    if (trimmed || clipped) {
       const auto w = [&](unsigned i) { return (unsigned long long)r.trim[i]; };
       std::printf(", \"trim\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
                   "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
-                  "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu}",
+                  "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu",
                   w(0), w(1), w(2), w(3), w(4), w(5), w(6), w(7), w(8), w(9), w(10), w(11), w(12), w(13));
+      if (clipped) std::printf(", \"reads_with_adapter\": %llu, \"bases_cut_adapter\": %llu", w(14), w(15));
+      std::printf("}");
     }
     if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
     std::printf("}\n");
