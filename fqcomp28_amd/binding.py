@@ -159,6 +159,11 @@ _PROTOS = {
                                    C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_clip": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                     C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_tail_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_tailtrim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                       C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_tailtrim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                        C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -320,12 +325,12 @@ def filter_check(flt):
     return lib().fqgpu_filter_check(_p(flt))
 
 
-def _select_call(fn, front, specs, n_recs, more=(), out_cap=None, want_keep=True, query=False):
+def _select_call(fn, front, specs, n_recs, more=(), out_cap=None, want_keep=True, query=False, report_words=None):
     """A device filter or trim call -> dict(rc, out, out_len, report, keep).  specs: the call's trim and filter words in the order
     of its arguments (None: NULL); more: the outputs it takes behind keep_out.  out_cap None: the size is asked for first
     (out=NULL), then the call is made with a buffer of that size -- query: the size is asked for and that is all; a number: ONE
-    call with a buffer of that many bytes."""
-    report = np.zeros(FILTER_REPORT_WORDS, dtype=np.uint64)
+    call with a buffer of that many bytes.  report_words: the words of the call's report when they are not the filter's."""
+    report = np.zeros(FILTER_REPORT_WORDS if report_words is None else report_words, dtype=np.uint64)
     keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
     n = C.c_size_t(0)
     words = [None if s is None else np.ascontiguousarray(s, dtype=np.uint32) for s in specs]
@@ -391,6 +396,36 @@ def _clip_call(fn, front, adapter, trim, flt, n_recs, want_win=True, **kw):
     """A device clip call -> dict(rc, out, out_len, report, keep, win) as _trim_call; adapter, trim, flt None: NULL"""
     win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
     return dict(_select_call(fn, front, (adapter, trim, flt), n_recs, more=(win,), **kw), win=win)
+
+
+TAIL_REPORT_WORDS = 24
+TAIL_REPORT_NAMES = CLIP_REPORT_NAMES + ("reads_with_poly_tail", "bases_cut_poly", "reads_window_cut", "bases_cut_window")
+POLY_BASES = {"A": 1, "C": 2, "G": 4, "T": 8}
+
+
+def read_tail(poly="", poly_min_len=None, poly_every=None, poly_max_mism=None, window_len=0, window_q=0, reserved=(0, 0)):
+    """an fqgpu_tail (include/fqgpu.h) as a uint32 array of eight words.  poly: the bases of the set as a string of ACGT, or
+    the bit mask itself; with a set, the defaults are a shortest tail of 10, one mismatch per 8 bases and at most 5 (the
+    tool's); without, zero.  The defaults cut nothing."""
+    bases = sum(POLY_BASES[c] for c in set(poly)) if isinstance(poly, str) else int(poly)
+    on = bases != 0
+    pick = lambda v, d: (d if on else 0) if v is None else v  # noqa: E731
+    return np.array([bases, pick(poly_min_len, 10), pick(poly_every, 8), pick(poly_max_mism, 5), window_len, window_q, reserved[0], reserved[1]],
+                    dtype=np.uint32)
+
+
+def tail_check(tail):
+    """fqgpu_tail_check -> rc (host only)"""
+    return lib().fqgpu_tail_check(_p(tail))
+
+
+def _tail_call(fn, front, adapter, tail, trim, flt, n_recs, want_win=True, want_places=True, **kw):
+    """A device tail call -> dict(rc, out, out_len, report, keep, win, places) as _clip_call, the report of TAIL_REPORT_WORDS;
+    places: uint16[n_recs, 4], a0, a1, e, e2 of every record; adapter, tail, trim, flt None: NULL"""
+    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
+    places = np.zeros((n_recs, 4), dtype=np.uint16) if want_places else None
+    return dict(_select_call(fn, front, (adapter, tail, trim, flt), n_recs, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
+                win=win, places=places)
 
 
 def pinned_empty(n_bytes):
@@ -515,6 +550,12 @@ class DBlock:
         _trim_call"""
         return _clip_call(lib().fqgpu_dblock_clip, (self.ctx.h, self.h), adapter, trim, flt, self.n_recs, **kw)
 
+    def tailtrim(self, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_dblock_tailtrim: the reads of the raw block clipped at `adapter` (None: no adapter), their poly-X tail and the
+        sliding-window cut of `tail` (read_tail; None: neither) taken, trimmed by `trim` and then judged by `flt` ->
+        dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
+        return _tail_call(lib().fqgpu_dblock_tailtrim, (self.ctx.h, self.h), adapter, tail, trim, flt, self.n_recs, **kw)
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -630,6 +671,12 @@ class Context:
         """fqgpu_chunk_clip: the reads of the chunk on the staging block (n_recs records) clipped at `adapter`, trimmed by
         `trim` and then judged by `flt`, where chunk_trim is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
         return _clip_call(lib().fqgpu_chunk_clip, (self.h,), adapter, trim, flt, n_recs, **kw)
+
+    def chunk_tailtrim(self, n_recs, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_chunk_tailtrim: the reads of the chunk on the staging block (n_recs records) clipped at `adapter`, their
+        poly-X tail and the sliding-window cut of `tail` taken, trimmed by `trim` and then judged by `flt`, where chunk_clip is
+        valid -> dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
+        return _tail_call(lib().fqgpu_chunk_tailtrim, (self.h,), adapter, tail, trim, flt, n_recs, **kw)
 
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""

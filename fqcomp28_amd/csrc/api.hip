@@ -1690,23 +1690,29 @@ extern "C" int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigne
 // The six calls (b, staged: as stats_call; trim: a trim call, which needs *t and takes a NULL filter for one that keeps
 // everything; a: a clip call's adapter -- with one, a NULL trim is one that cuts nothing; a clip call without one is the trim
 // call): no device is said before any argument is looked at; *out_len and the report are zeroed before anything else
-// can fail.
+// can fail.  tail: one of the two tail calls, whose report has FQGPU_TAIL_REPORT_WORDS words; x: its tail -- NULL, or one
+// with both rules off, makes it the clip call with the same a, t, f (words 16 .. 23 zero), unless the places are asked for:
+// then k_tail_find runs with nothing to do, and the results are the clip call's all the same.
 static int select_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, bool trim, const fqgpu_adapter *a, const fqgpu_trim *t,
                        const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
-                       uint32_t *win_out) {
+                       uint32_t *win_out, bool tail = false, const fqgpu_tail *x = nullptr, uint16_t *places_out = nullptr) {
   static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one zeroing for both reports");
   if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
   if (out_len) *out_len = 0;
-  if (report) memset(report, 0, FQGPU_FILTER_REPORT_WORDS * sizeof(uint64_t));
+  if (report) memset(report, 0, (tail ? FQGPU_TAIL_REPORT_WORDS : FQGPU_FILTER_REPORT_WORDS) * sizeof(uint64_t));
   const fqgpu_trim none = {0u, 0u, 0u, 0u, FQGPU_FILTER_NONE, {0u, 0u, 0u}};
-  if (a && !t) t = &none;
+  const fqgpu_tail off = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+  if (x && fqgpu_tail_check(x) != FQGPU_OK) return FQGPU_E_ARG;
+  const bool tail_on = x && (x->poly_bases || x->window_len);
+  if (tail && !tail_on) x = places_out && (a || t) ? &off : nullptr;
+  if ((a || x) && !t) t = &none;
   if (!ctx || !out_len || !report || (a && fqgpu_adapter_check(a) != FQGPU_OK) || (trim && fqgpu_trim_check(t) != FQGPU_OK) ||
       ((f || !trim) && fqgpu_filter_check(f) != FQGPU_OK))
     return FQGPU_E_ARG;
   const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
   if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
   return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, a, trim ? t : nullptr, f ? f : &all, out, out_cap, out_len,
-                         report, keep_out, win_out);
+                         report, keep_out, win_out, x, places_out);
 }
 
 extern "C" int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
@@ -1737,4 +1743,16 @@ extern "C" int fqgpu_chunk_clip(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fq
 extern "C" int fqgpu_dblock_clip(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f,
                                  uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
   return select_call(ctx, b, false, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out);
+}
+
+extern "C" int fqgpu_chunk_tailtrim(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                                    uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
+                                    uint16_t *places_out) {
+  return select_call(ctx, nullptr, true, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out, true, x, places_out);
+}
+
+extern "C" int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                                     const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
+                                     uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
+  return select_call(ctx, b, false, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out, true, x, places_out);
 }

@@ -107,6 +107,16 @@ extern "C" int fqgpu_adapter_check(const fqgpu_adapter *a) {
   return FQGPU_OK;
 }
 
+// Poly-X tails and the sliding-window cut (select.hip applies them): what a tail may say.
+extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
+  if (!x || x->poly_bases > 15u || x->poly_max_mism > 255u || x->window_len > 32u || x->reserved[0] || x->reserved[1]) return FQGPU_E_ARG;
+  if (x->poly_bases ? x->poly_min_len < 1u || x->poly_min_len > 65535u || x->poly_every < 2u || x->poly_every > 255u
+                    : x->poly_min_len || x->poly_every)
+    return FQGPU_E_ARG;
+  if (x->window_len ? x->window_q < 1u || x->window_q > 64u : x->window_q != 0u) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

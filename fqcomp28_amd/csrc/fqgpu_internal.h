@@ -237,11 +237,12 @@ struct StatsScratch {
 
 // Selection of the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip): per record the kept size, the
 // start of its header line and -- reserved by a trim call alone -- its window, beside it -- by a clip call alone -- its clip
-// place (a uint16_t: k_adapter_find writes it, the judge reads it), the keep bits, the offsets of the kept records
+// place (a uint16_t: k_adapter_find writes it, the judge reads it) and -- by a tail call alone -- its places a0, a1, e, e2
+// (four uint16_t: k_tail_find writes them, the judge reads them), the keep bits, the offsets of the kept records
 // in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
 // filter and trim calls: each is waited for before it returns.
 struct SelectScratch {
-  DevBuf ksize, hstart, win, clip, keep, koff, dst, res, scan_tmp;
+  DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   void *host = nullptr;
   void release();
 };
@@ -442,10 +443,12 @@ int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
 // *t (nullptr: the filter alone, win_out is not looked at) and then judged by *f
 // (select.hip; both have passed their checks), on st, waited for: report (FQGPU_TRIM_REPORT_WORDS, which are
 // FQGPU_FILTER_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
-// into out
+// into out.  x (nullptr: none; one needs a trim and has passed its check): the tail trims between the clip and the trim; the
+// report then has FQGPU_TAIL_REPORT_WORDS words and places_out (nullptr: not wanted) receives a0, a1, e, e2 of every record
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
-                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
+                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x = nullptr,
+                    uint16_t *places_out = nullptr);
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

@@ -683,8 +683,10 @@ inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &
 
 namespace detail {
 /** processArchiveFiltered (trim == nullptr; the filter is needed), processArchiveTrimmed and processArchiveClipped (with an
- *  adapter, trim and filter may both be nullptr; reported as a trim), `who` of the three: every block
- *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed / decodeChunkClipped), only the kept bytes come down and
+ *  adapter, trim and filter may both be nullptr; reported as a trim) and processArchiveTailTrimmed (with a tail, adapter, trim
+ *  and filter may all be nullptr; reported as a trim of FQGPU_TAIL_REPORT_WORDS words), `who` of the four: every block
+ *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed / decodeChunkClipped /
+ *  decodeChunkTailTrimmed), only the kept bytes come down and
  *  reach the file.  A usable `<archive>.fqx` is used, and with a usable `<archive>.fqs` every chunk is verified before any
  *  of it is written: the digest is of the WHOLE restored chunk, as the writer took it.  Never builds an index.  The kept
  *  sizes are known only after the decode, so the blocks go through OrderedPieceWriter as the FASTA pieces do: handed out in
@@ -692,13 +694,14 @@ namespace detail {
  *  was written; the chunks' reports, added word by word, go to rep.filter or rep.trim. */
 inline FarmReport processArchiveSelected(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim *trim,
                                          const fqgpu_filter *filter, const Settings &set, const char *who,
-                                         const fqgpu_adapter *adapter = nullptr) {
+                                         const fqgpu_adapter *adapter = nullptr, const fqgpu_tail *tail = nullptr) {
   static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one report size for both");
-  constexpr unsigned W = FQGPU_FILTER_REPORT_WORDS;
+  const unsigned W = tail ? FQGPU_TAIL_REPORT_WORDS : FQGPU_FILTER_REPORT_WORDS;  // (rep.trim has 24 words only with a tail)
   const std::string name(who);
+  if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
   if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
   if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-  if ((filter || !(trim || adapter)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+  if ((filter || !(trim || adapter || tail)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
   Archive archive(archive_path);
   const std::size_t n_blocks = archive.chunkOffsets().size() - 1;
   std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
@@ -721,7 +724,7 @@ inline FarmReport processArchiveSelected(const path_t &archive_path, const path_
   detail::runWorkers(T, [&](unsigned t) {
     CompressedBuffersSrc cbs;
     FastqChunk piece;
-    uint64_t report[W];
+    uint64_t report[FQGPU_TAIL_REPORT_WORDS];  // (the longest of the reports)
     for (;;) {
       const std::size_t k = next.fetch_add(1);  // (in order: whoever waits in the writer waits for blocks already taken)
       if (stopped.load() || k >= n_blocks) break;
@@ -732,7 +735,8 @@ inline FarmReport processArchiveSelected(const path_t &archive_path, const path_
         used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
       }
       clk.lap("read");
-      if (adapter) wksp[t]->decodeChunkClipped(piece, cbs, *adapter, trim, filter, report);
+      if (tail) wksp[t]->decodeChunkTailTrimmed(piece, cbs, adapter, *tail, trim, filter, report);
+      else if (adapter) wksp[t]->decodeChunkClipped(piece, cbs, *adapter, trim, filter, report);
       else if (trim) wksp[t]->decodeChunkTrimmed(piece, cbs, *trim, filter, report);
       else wksp[t]->decodeChunkFiltered(piece, cbs, *filter, report);
       clk.lap("decode");
@@ -752,7 +756,7 @@ inline FarmReport processArchiveSelected(const path_t &archive_path, const path_
   }, [&] { stopped.store(true); writer.abort(); });
   writer.flush();
   rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::vector<uint64_t> &sum = trim || adapter ? rep.trim : rep.filter;
+  std::vector<uint64_t> &sum = trim || adapter || tail ? rep.trim : rep.filter;
   sum.assign(W, 0);
   for (unsigned t = 0; t < T; ++t) {
     rep.in += istats[t];
@@ -790,6 +794,17 @@ inline FarmReport processArchiveTrimmed(const path_t &archive_path, const path_t
 inline FarmReport processArchiveClipped(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter &adapter,
                                         const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
   return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveClipped", &adapter);
+}
+
+/** Extension: `d [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q]`, with or without the adapter,
+ *  trim and filter options -- the reads clipped at the 3' adapter (nullptr: none), their poly-X tail and everything from a
+ *  sliding-window quality drop on taken (fqgpu_chunk_tailtrim's steps 0b and 1b), then trimmed by `trim` (nullptr: nothing
+ *  more is cut) and judged by `filter` (nullptr: every read that is not emptied is kept), in input order
+ *  (detail::processArchiveSelected).  rep.in counts what was written; rep.trim has FQGPU_TAIL_REPORT_WORDS words here: the
+ *  clip's sixteen, then the reads with a poly tail, the bases it took, the reads the window cut and the bases it took. */
+inline FarmReport processArchiveTailTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter *adapter,
+                                            const fqgpu_tail &tail, const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
+  return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveTailTrimmed", adapter, &tail);
 }
 
 /** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function

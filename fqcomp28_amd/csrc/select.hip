@@ -78,7 +78,7 @@ static_assert(SEL_WAVE_RECORDS == 64 && SEL_GROUP_LANES == 8 && SEL_ROUND_RECORD
 // the result words on the device: the report (include/fqgpu.h; word 0 is filled in by the host) and the two flags
 static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one result struct serves both reports");
 struct SelectResult {
-  unsigned long long w[FQGPU_TRIM_REPORT_WORDS];
+  unsigned long long w[FQGPU_TAIL_REPORT_WORDS];
   unsigned int bad;       // a byte that cannot be judged, a record outside the chunk or without symbols
   unsigned int not_bare;  // k_crc_check's verdict: text behind a '+', or the last '\n' outside the chunk
 };
@@ -86,6 +86,7 @@ constexpr unsigned R_KEPT = 1, R_BASES_IN = 2, R_BASES_KEPT = 3, R_BYTES_KEPT = 
                    R_CUT_TAIL = 12, R_EMPTIED = 13;
 template <bool TRIM> constexpr unsigned R_COUNTERS = TRIM ? 14 : 10;  // the words a judge counts
 constexpr unsigned R_WITH_ADAPTER = 14, R_CUT_ADAPTER = 15, R_COUNTERS_CLIP = 16;  // ... behind an adapter search
+constexpr unsigned R_WITH_POLY = 16, R_CUT_POLY = 17, R_WINDOW_CUT = 18, R_CUT_WINDOW = 19, R_COUNTERS_TAIL = 20;  // ... behind the tail trims
 
 constexpr unsigned SW_H = 0x80808080u, SW_L = 0x01010101u;
 // per byte of x (every byte < 128), 0 <= k <= 128: bit 7 set where the byte is >= k
@@ -476,16 +477,325 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
 }
 
-// TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at.  CLIP (with TRIM): clip[r]
-// stands for the read's length in the trim's steps 1 to 4 (k_adapter_find has written it, and has judged the sequence line)
-template <bool TRIM, bool CLIP = false>
+// ---- the tail trims (include/fqgpu.h, steps 0b and 1b): both are "the first place where a prefix property fails", a
+// min-reduction over places.
+constexpr unsigned TAIL_NONE = 0xFFFFFFFFu;
+struct TailSpec {
+  unsigned bases, min_len, every, max_mism;  // the poly rule; bases 0: off
+  unsigned W, level, thr;                    // the window rule in quality BYTES: level = Q + 33, thr = level * W; W 0: off
+};
+
+// a poly walk on its way down a line, per base X; the same in the eight lanes of a record
+struct PolyWalk {
+  unsigned ent[4];  // the mismatches the walk enters the next word with
+  unsigned v[4];    // the first violation, a tail place i = a0 - place; TAIL_NONE: none so far
+  unsigned t[4];    // the largest tail place in front of it at which X stands
+};
+__device__ __forceinline__ bool poly_done(const PolyWalk &pw, unsigned bases) {
+  bool done = true;
+#pragma unroll
+  for (unsigned X = 0; X < 4; X++) done = done && (!((bases >> X) & 1u) || pw.v[X] != TAIL_NONE);
+  return done;
+}
+
+// One word of the poly walk over s[0, a0): x the planes of lane sub's word, whose byte 0 stands at place pos0 of the line.
+// The walk comes from the line's end, so the word is entered with the mismatches of the lanes behind it.  Every lane of the
+// record's eight calls this together.  mism <= min(i / every, max_mism) is mism <= max_mism && mism * every <= i: no division.
+__device__ __forceinline__ void tail_poly_word(PolyWalk &pw, const ClipWord x, int pos0, unsigned sub, int a0, const TailSpec &sp) {
+  const unsigned in = sel_bits(-pos0, a0 - pos0);
+  const unsigned plane[4] = {x.ac & 0xFFFFu, x.ac >> 16, x.gt & 0xFFFFu, x.gt >> 16};
+  const int i0 = a0 - pos0;  // the tail place of byte j is i0 - j
+#pragma unroll
+  for (unsigned X = 0; X < 4; X++) {
+    if (!((sp.bases >> X) & 1u)) continue;  // (uniform)
+    const unsigned mm = in & ~plane[X];
+    unsigned inc = __popc(mm);
+#pragma unroll
+    for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+      const unsigned o = __shfl_up(inc, d, SEL_GROUP_LANES);
+      if (sub >= d) inc += o;
+    }
+    const unsigned sum = __shfl(inc, SEL_GROUP_LANES - 1, SEL_GROUP_LANES);
+    const unsigned e = pw.ent[X] + (sum - inc);
+    unsigned viol = 0;
+#pragma unroll
+    for (int j = 0; j < 16; j++) {
+      const unsigned c = e + __popc(mm >> j);  // mism(i0 - j): the mismatches from byte j to the line's end
+      const bool over = c > sp.max_mism || (int)(c * sp.every) > i0 - j;
+      viol |= over ? 1u << j : 0u;
+    }
+    viol &= in;
+    // the first violation is the one at the highest byte
+    unsigned first = viol ? (unsigned)(i0 - (31 - (int)__builtin_clz(viol))) : TAIL_NONE;
+#pragma unroll
+    for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) first = min(first, (unsigned)__shfl_xor(first, d, SEL_GROUP_LANES));
+    if (pw.v[X] == TAIL_NONE) pw.v[X] = first;
+    // the X in front of it: tail places i < v, bytes j > i0 - v
+    const int lo = pw.v[X] == TAIL_NONE ? 0 : i0 - (int)pw.v[X] + 1;
+    const unsigned hits = plane[X] & in & sel_bits(lo, 16);
+    unsigned far = hits ? (unsigned)(i0 - (int)__builtin_ctz(hits)) : 0u;
+#pragma unroll
+    for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) far = max(far, (unsigned)__shfl_xor(far, d, SEL_GROUP_LANES));
+    pw.t[X] = max(pw.t[X], far);
+    pw.ent[X] += sum;
+  }
+}
+
+// One request of the poly walk (word 8 k + sub in lane sub, k = 0, 1), the later word first.  A word is left out when no
+// record of the WAVE has anything for the walk in it: it lies behind a0, or every walk has met its violation.
+__device__ __forceinline__ void tail_poly_step(PolyWalk &pw, const ClipWord (&x)[SEL_UNROLL], unsigned p0, unsigned sub, int lead, int a0, const TailSpec &sp) {
+#pragma unroll
+  for (unsigned kk = 0; kk < SEL_UNROLL; kk++) {
+    const unsigned k = SEL_UNROLL - 1 - kk;
+    const int first = (int)(p0 + 16u * SEL_GROUP_LANES * k) - lead;
+    const bool idle = first >= a0 || poly_done(pw, sp.bases);  // (the same in a record's lanes)
+    if (__all(idle)) continue;                                 // (uniform)
+    tail_poly_word(pw, x[k], first + (int)(16u * sub), sub, a0, sp);
+  }
+}
+
+__device__ __forceinline__ uint4 tail_shfl4(const uint4 v, unsigned src) {
+  return make_uint4(__shfl(v.x, src, SEL_GROUP_LANES), __shfl(v.y, src, SEL_GROUP_LANES), __shfl(v.z, src, SEL_GROUP_LANES),
+                    __shfl(v.w, src, SEL_GROUP_LANES));
+}
+// w[i] for an i that is the same in every lane, without an indexed register file; an i of 12 or more gives 0.  (The
+// window asks for w[12] when W >= 29: that word only feeds the bytes behind W + 15 -- the upper half of an alignbyte by 0
+// for W = 32, the byte that would enter behind place 15 otherwise -- and no sum that is tested holds them.)
+__device__ __forceinline__ unsigned tail_pick(const unsigned (&w)[12], unsigned i) {
+  unsigned r = 0;
+#pragma unroll
+  for (unsigned k = 0; k < 12; k++) r = i == k ? w[k] : r;
+  return r;
+}
+
+// The sixteen windows that start in one word of a quality line: own, and the two words behind it, give the 47 bytes they can
+// look at; pos0: the place in the line of the word's byte 0.  The window at byte 0 is summed by v_sad_u8, every next one
+// takes a byte in and lets one out.  -> a bit for every place p in [f, e - W] whose W bytes sum to less than thr.
+__device__ __forceinline__ unsigned tail_window_word(const uint4 own, const uint4 n1, const uint4 n2, int pos0, int f, int e, const TailSpec &sp) {
+  const unsigned w[12] = {own.x, own.y, own.z, own.w, n1.x, n1.y, n1.z, n1.w, n2.x, n2.y, n2.z, n2.w};
+  unsigned s = 0;
+#pragma unroll
+  for (int i = 0; i < 8; i++) s = __builtin_amdgcn_sad_u8(w[i] & sw_mask(-4 * i, (int)sp.W - 4 * i), 0u, s);
+  // the bytes W .. W + 15
+  const unsigned wq = sp.W >> 2, wr = sp.W & 3u;
+  unsigned t[5], in4[4];
+#pragma unroll
+  for (unsigned i = 0; i < 5; i++) t[i] = tail_pick(w, wq + i);
+#pragma unroll
+  for (unsigned i = 0; i < 4; i++) in4[i] = __builtin_amdgcn_alignbyte(t[i + 1], t[i], wr);
+  unsigned fails = 0;
+#pragma unroll
+  for (int j = 0; j < 16; j++) {
+    fails |= s < sp.thr ? 1u << j : 0u;
+    s += ((in4[j >> 2] >> (8 * (j & 3))) & 0xFFu) - ((w[j >> 2] >> (8 * (j & 3))) & 0xFFu);
+  }
+  return fails & sel_bits(f - pos0, e - (int)sp.W + 1 - pos0);
+}
+
+// One request of a quality line (word 8 k + sub in lane sub, k = 0, 1) tested by the record's eight lanes together: y0 the
+// NEXT request's first word (zero when the line ends in this one; more: some record of the wave has a next request), done: the
+// record has its window already.  -> the smallest failing place among the lane's, or TAIL_NONE.
+__device__ __forceinline__ unsigned tail_window_request(const uint4 (&x)[SEL_UNROLL], const uint4 y0, bool more, bool done, unsigned p0, unsigned sub,
+                                                        int lead, int f, int e, const TailSpec &sp) {
+  uint4 n0[2], n1[2];
+#pragma unroll
+  for (unsigned d = 1; d <= 2; d++) {
+    const unsigned src = (sub + d) & (SEL_GROUP_LANES - 1);
+    const bool wrap = sub + d >= SEL_GROUP_LANES;
+    const uint4 b0 = tail_shfl4(x[0], src), b1 = tail_shfl4(x[1], src);
+    uint4 b2 = make_uint4(0, 0, 0, 0);
+    if (more) b2 = tail_shfl4(y0, src);  // (uniform)
+    n0[d - 1] = wrap ? b1 : b0;
+    n1[d - 1] = wrap ? b2 : b1;
+  }
+  unsigned best = TAIL_NONE;
+#pragma unroll
+  for (unsigned kk = 0; kk < SEL_UNROLL; kk++) {
+    const unsigned k = SEL_UNROLL - 1 - kk;  // (the later word first: the earlier one's place replaces its)
+    const int first = (int)(p0 + 16u * SEL_GROUP_LANES * k) - lead;
+    // (uniform) no record of the wave has a window that starts there
+    if (__all(done || first + (int)sp.W > e || first + (int)(16u * SEL_GROUP_LANES) <= f)) continue;
+    const int pos0 = first + (int)(16u * sub);
+    const unsigned fails = k ? tail_window_word(x[1], n1[0], n1[1], pos0, f, e, sp) : tail_window_word(x[0], n0[0], n0[1], pos0, f, e, sp);
+    if (fails) best = (unsigned)(pos0 + (int)__builtin_ctz(fails));
+  }
+  return done ? TAIL_NONE : best;
+}
+
+// the first place in [from, to) of a word at which the quality byte is below the level, or TAIL_NONE
+__device__ __forceinline__ unsigned tail_low_place(const uint4 v, int pos0, int from, int to, unsigned level) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  unsigned low = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) low |= ((~sw_ge(w[i] & ~SW_H, level) & SW_H) * CLIP_GATHER) >> 28 << (4 * i);
+  low &= sel_bits(from - pos0, to - pos0);
+  return low ? (unsigned)(pos0 + (int)__builtin_ctz(low)) : TAIL_NONE;
+}
+
+// places[r] = a0, a1, e, e2 of record r (include/fqgpu.h, steps 0 to 1b): the clip place (clip[r] behind k_adapter_find, else
+// the read's length), the place in front of the poly-X tail, the end the fixed cuts leave and the place of the window cut.
+// The judge's access pattern as in k_adapter_find.  Poly: a word's planes (clip_planes, which judges ACGTN on the way -- left
+// to k_adapter_find where that has run), per base X the mismatches counted in tail order, a prefix sum over the record's eight
+// lanes for the count a word is entered with, sixteen places tested per lane, the first violation a min-reduction and the
+// largest X place in front of it a max-reduction by shuffles.  Window: a lane takes the bytes behind its word from its
+// neighbours by shuffles, forms its sixteen window sums, the first failing window is a min-reduction and e2 the first low
+// byte from there.  A read longer than one request walks the requests backwards for the poly tail and forwards for the
+// window, every lane of the wave the same number of steps: a correctness path.  A line that is read here is judged over all
+// its bytes.
+__global__ void __launch_bounds__(SEL_THREADS)
+k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
+            const fqgpu_tail x, const fqgpu_trim t, const uint16_t *__restrict__ clip, uint2 *__restrict__ places,
+            SelectResult *__restrict__ res) {
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  const TailSpec sp = {x.poly_bases, x.poly_min_len, x.poly_every, x.poly_max_mism, x.window_len, x.window_q + 33u, (x.window_q + 33u) * x.window_len};
+  const bool poly = sp.bases != 0, window = sp.W != 0, judge_seq = clip == nullptr;
+  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+  const unsigned long long r = r0 + lane;
+  const bool have = r < n_recs;
+  fqgpu_rec mine = {0u, 0u, 0u};
+  if (have) mine = recs[r];
+  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len &&
+                  (unsigned long long)mine.qual_off + mine.len <= raw_len;
+  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read; the judge refuses it)
+  unsigned my_a0 = read_len;
+  if (clip != nullptr && ok) my_a0 = min((unsigned)clip[r], read_len);
+  const unsigned my_span = max(poly ? (mine.seq_off & 15u) + read_len : 0u, window ? (mine.qual_off & 15u) + read_len : 0u);
+  const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
+  const auto cut_lo = [&](unsigned len) { return min(t.cut_front, len); };
+  const auto cut_hi = [&](unsigned len) { return len - min(t.cut_tail, len - min(t.cut_front, len)); };
+
+  unsigned my_a1 = my_a0, my_e2 = cut_hi(my_a0);  // (what holds when no line is read)
+  bool my_bad = false;
+  if (poly || window) {  // (uniform)
+    const auto fetch = [&](SelStage &st, unsigned j) {
+      st.seq_off = __shfl(mine.seq_off, j);
+      st.qual_off = __shfl(mine.qual_off, j);
+      st.len = __shfl(read_len, j);
+      if (poly) sel_load_line(st.s, raw, st.seq_off, st.len, 0, sub);
+      if (window) sel_load_line(st.q, raw, st.qual_off, st.len, 0, sub);
+    };
+    // the planes of the lane's words of the request at p0 of the sequence line
+    const auto planes = [&](ClipWord (&y)[SEL_UNROLL], const uint4 (&v)[SEL_UNROLL], const SelStage &st, unsigned p0, bool &bad) {
+      const int lead = (int)(st.seq_off & 15u), span = st.len ? lead + (int)st.len : 0;
+      bool b = false;
+#pragma unroll
+      for (unsigned k = 0; k < SEL_UNROLL; k++) {
+        const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
+        y[k] = clip_planes(v[k], sel_bits(lead - rel, span - rel), b);
+      }
+      if (judge_seq) bad = bad || b;
+    };
+    // the lane's words of the request at p0 of the quality line, judged: 33 .. 96
+    const auto judge_qual = [&](const uint4 (&v)[SEL_UNROLL], const SelStage &st, unsigned p0, bool &bad) {
+      const int lead = (int)(st.qual_off & 15u), span = st.len ? lead + (int)st.len : 0;
+      SelCounts c = {0u, 0u, 0u, false};
+#pragma unroll
+      for (unsigned k = 0; k < SEL_UNROLL; k++) {
+        const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
+        if (rel >= span) continue;
+        sel_judge_qual<false>(c, v[k], max(lead - rel, 0), min(span - rel, 16), 0, 0, sp.level);
+      }
+      bad = bad || c.bad;
+    };
+    SelStage cur, nxt;
+    fetch(cur, group);
+#pragma unroll 1
+    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
+      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+      const unsigned a0 = __shfl(my_a0, SEL_ROUND_RECORDS * k + group);
+      unsigned steps = 1;
+      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
+        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+        steps = fq_uniform(steps);
+      }
+      bool bad = false;
+      unsigned a1 = a0;
+      if (poly) {  // (uniform) from the line's last request down
+        PolyWalk pw = {{0u, 0u, 0u, 0u}, {TAIL_NONE, TAIL_NONE, TAIL_NONE, TAIL_NONE}, {0u, 0u, 0u, 0u}};
+        const int lead = (int)(cur.seq_off & 15u);
+        ClipWord y[SEL_UNROLL];
+        for (unsigned s = steps - 1; s >= 1; s--) {  // a long read: not loaded ahead
+          uint4 v[SEL_UNROLL];
+          sel_load_line(v, raw, cur.seq_off, cur.len, s * SEL_STEP_BYTES, sub);
+          planes(y, v, cur, s * SEL_STEP_BYTES, bad);
+          tail_poly_step(pw, y, s * SEL_STEP_BYTES, sub, lead, (int)a0, sp);
+        }
+        planes(y, cur.s, cur, 0, bad);
+        tail_poly_step(pw, y, 0, sub, lead, (int)a0, sp);
+        unsigned tl = 0;
+#pragma unroll
+        for (unsigned X = 0; X < 4; X++)
+          if ((sp.bases >> X) & 1u) tl = max(tl, pw.t[X] >= sp.min_len ? pw.t[X] : 0u);
+        a1 = a0 - tl;
+      }
+      const unsigned f = cut_lo(a1), e = cut_hi(a1);
+      unsigned e2 = e;
+      if (window) {  // (uniform) from the line's first request up
+        const int lead = (int)(cur.qual_off & 15u);
+        uint4 q[SEL_UNROLL];
+#pragma unroll
+        for (unsigned i = 0; i < SEL_UNROLL; i++) q[i] = cur.q[i];
+        unsigned at = TAIL_NONE;  // the first failing window
+        for (unsigned s = 0; s < steps; s++) {
+          uint4 y[SEL_UNROLL] = {make_uint4(0, 0, 0, 0), make_uint4(0, 0, 0, 0)};
+          if (s + 1 < steps) sel_load_line(y, raw, cur.qual_off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);  // (uniform) a long read
+          judge_qual(q, cur, s * SEL_STEP_BYTES, bad);
+          unsigned got = tail_window_request(q, y[0], s + 1 < steps, at != TAIL_NONE, s * SEL_STEP_BYTES, sub, lead, (int)f, (int)e, sp);
+#pragma unroll
+          for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) got = min(got, (unsigned)__shfl_xor(got, d));
+          const bool fresh = at == TAIL_NONE && got != TAIL_NONE;  // (the same in a record's lanes)
+          if (__any(fresh)) {  // (uniform) the first low byte from there: in this request, or in the next one's first words
+            const int from = fresh ? (int)got : (int)e, rel0 = (int)(s * SEL_STEP_BYTES + 16u * sub) - lead;
+            unsigned low = tail_low_place(q[0], rel0, from, (int)e, sp.level);
+            low = min(low, tail_low_place(q[1], rel0 + (int)(16u * SEL_GROUP_LANES), from, (int)e, sp.level));
+            low = min(low, tail_low_place(y[0], rel0 + (int)SEL_STEP_BYTES, from, (int)e, sp.level));
+#pragma unroll
+            for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) low = min(low, (unsigned)__shfl_xor(low, d));
+            if (fresh) {
+              at = got;
+              e2 = min(low, e);
+            }
+          }
+#pragma unroll
+          for (unsigned i = 0; i < SEL_UNROLL; i++) q[i] = y[i];
+        }
+      }
+      // over the record's eight lanes: "a byte that cannot be judged"; then back to the record's own lane
+      unsigned got = a1 | e2 << 16, flag = bad;
+#pragma unroll
+      for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) flag |= __shfl_xor(flag, d);
+      const unsigned from = (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES;
+      const unsigned mine_got = __shfl(got, from), mine_flag = __shfl(flag, from);
+      if (lane / SEL_ROUND_RECORDS == k) {
+        my_a1 = mine_got & 0xFFFFu;
+        my_e2 = mine_got >> 16;
+        my_bad = mine_flag != 0u;
+      }
+      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
+    }
+  }
+  if (have) places[r] = make_uint2(my_a0 | my_a1 << 16, cut_hi(my_a1) | my_e2 << 16);
+  if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
+}
+
+// TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at.  STEP0 (with TRIM): what
+// stands in front of the trim's steps.  SEL_CLIP: clip[r] stands for the read's length in the trim's steps 1 to 4
+// (k_adapter_find has written it, and has judged the sequence line).  SEL_TAIL: k_tail_find has left a0, a1, e, e2 in
+// places[r]; the walks run over [min(cut_front, e2), e2) -- which is [f, e2), since f = min(cut_front, a1) and
+// f <= e2 <= a1 -- and cut_tail, which is in e already, is not applied again.
+constexpr unsigned SEL_PLAIN = 0, SEL_CLIP = 1, SEL_TAIL = 2;
+template <bool TRIM, unsigned STEP0 = SEL_PLAIN>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
                const fqgpu_trim t, const fqgpu_filter f, uint32_t *__restrict__ ksize, uint32_t *__restrict__ hstart,
                uint32_t *__restrict__ win, unsigned long long *__restrict__ keep, SelectResult *__restrict__ res,
-               const uint16_t *__restrict__ clip) {
-  static_assert(TRIM || !CLIP, "a clip is a trim's step 0");
-  constexpr unsigned NC = CLIP ? R_COUNTERS_CLIP : R_COUNTERS<TRIM>;
+               const uint16_t *__restrict__ clip, const uint2 *__restrict__ places) {
+  static_assert(TRIM || STEP0 == SEL_PLAIN, "a clip and a tail trim stand in front of a trim's steps");
+  static_assert(STEP0 <= SEL_TAIL, "plain, clip or tail");
+  constexpr bool CLIP = STEP0 != SEL_PLAIN;  // the trim's steps see another length than the read's
+  constexpr unsigned NC = STEP0 == SEL_TAIL ? R_COUNTERS_TAIL : CLIP ? R_COUNTERS_CLIP : R_COUNTERS<TRIM>;
   __shared__ unsigned wg[NC];
   if (threadIdx.x < NC) wg[threadIdx.x] = 0;
   __syncthreads();
@@ -508,7 +818,10 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
 
   // the window of a read of `len` symbols left by the fixed cuts, and by the two walks' results
   const auto cut_lo = [&](unsigned len) { return min(t.cut_front, len); };
-  const auto cut_hi = [&](unsigned len) { return len - min(t.cut_tail, len - min(t.cut_front, len)); };
+  const auto cut_hi = [&](unsigned len) {
+    if constexpr (STEP0 == SEL_TAIL) return len;  // (e2: cut_tail is in it)
+    else return len - min(t.cut_tail, len - min(t.cut_front, len));
+  };
   const auto window = [&](unsigned start, unsigned stop) {  // -> start | n << 16
     if (start >= stop) return 0u;
     return start | min(stop - start, t.crop) << 16;
@@ -517,7 +830,12 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   unsigned n_count = 0, q_bytes = 0, low_count = 0;
   unsigned my_win = 0;
   unsigned eff_len = read_len;  // the length the trim sees: the clip place behind an adapter search
-  if constexpr (CLIP) eff_len = ok ? min((unsigned)clip[r], read_len) : 0u;
+  uint2 my_places = make_uint2(0u, 0u);  // SEL_TAIL: a0 | a1 << 16, e | e2 << 16
+  if constexpr (STEP0 == SEL_CLIP) eff_len = ok ? min((unsigned)clip[r], read_len) : 0u;
+  if constexpr (STEP0 == SEL_TAIL) {
+    if (ok) my_places = places[r];
+    eff_len = min(my_places.y >> 16, read_len);
+  }
   if constexpr (TRIM) my_win = window(cut_lo(eff_len), cut_hi(eff_len));  // (what holds when no line is read)
   if (need_seq || need_qual) {  // (uniform)
     // record j of the wave's 64, for the lanes of the group that reads it
@@ -698,9 +1016,18 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
     cnt[R_CUT_TAIL] = ok ? mine.len - start - n : 0u;
     cnt[R_EMPTIED] = emptied;
   }
-  if constexpr (CLIP) {
+  if constexpr (STEP0 == SEL_CLIP) {
     cnt[R_WITH_ADAPTER] = ok && eff_len < mine.len;
     cnt[R_CUT_ADAPTER] = ok ? mine.len - eff_len : 0u;
+  }
+  if constexpr (STEP0 == SEL_TAIL) {  // (zero in a record that is not ok)
+    const unsigned a0 = min(my_places.x & 0xFFFFu, read_len), a1 = min(my_places.x >> 16, a0), e = min(my_places.y & 0xFFFFu, a1);
+    cnt[R_WITH_ADAPTER] = a0 < read_len;
+    cnt[R_CUT_ADAPTER] = read_len - a0;
+    cnt[R_WITH_POLY] = a1 < a0;
+    cnt[R_CUT_POLY] = a0 - a1;
+    cnt[R_WINDOW_CUT] = eff_len < e;
+    cnt[R_CUT_WINDOW] = e - min(eff_len, e);
   }
   unsigned long long bytes = size;  // (64 records of up to 2^32 - 1 bytes)
 #pragma unroll
@@ -885,7 +1212,7 @@ k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__rest
 }  // namespace
 
 void SelectScratch::release() {
-  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
+  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &places, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
   if (host) (void)hipHostFree(host);
   host = nullptr;
 }
@@ -894,22 +1221,26 @@ void SelectScratch::release() {
 // one, t is a trim), trimmed by *t (nullptr: the filter alone) and then judged by *f, on st, waited for.  Two waits: the judge's result words decide what is gathered and how much room it
 // needs; the gathered bytes come down in one copy.  FQGPU_E_ARG with *out_len = 0 and report, keep bits and windows zeroed: a
 // byte that cannot be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
+// x (nullptr: none; with one, t is a trim): the tail trims between the clip and the trim, k_tail_find in front of the judge;
+// the report then has FQGPU_TAIL_REPORT_WORDS words, and places_out (nullptr, or 4 uint16_t per record) receives a0, a1, e, e2.
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
-                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
+                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x, uint16_t *places_out) {
+  const unsigned words = x ? FQGPU_TAIL_REPORT_WORDS : FQGPU_TRIM_REPORT_WORDS;
   *out_len = 0;
-  for (unsigned i = 0; i < FQGPU_TRIM_REPORT_WORDS; i++) report[i] = 0;
+  for (unsigned i = 0; i < words; i++) report[i] = 0;
   if (n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  if (a && !t) return FQGPU_E_ARG;
+  if ((a || x) && !t) return FQGPU_E_ARG;
   if (!n_recs) return FQGPU_OK;
   if (!t) win_out = nullptr;  // (a filter has no windows)
+  if (!x) places_out = nullptr;
   SelectScratch &ss = ctx->select;
-  const char *const span = a ? "clip" : t ? "trim" : "filter";
+  const char *const span = x ? "tailtrim" : a ? "clip" : t ? "trim" : "filter";
   const unsigned R = (unsigned)n_recs;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
   int rc;
   if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
-      (a && (rc = ss.clip.reserve(n_recs * 2))) ||
+      (a && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) ||
       (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
     return rc;
   if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
@@ -925,11 +1256,16 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
                        plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, ss.clip.as<uint16_t>(), ss.res.as<SelectResult>());
     FQ_HIP(hipGetLastError());
   }
-  const auto judge = a ? &k_select_judge<true, true> : t ? &k_select_judge<true> : &k_select_judge<false>;
+  if (x) {
+    hipLaunchKernelGGL(k_tail_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, *x, *t,
+                       a ? ss.clip.as<uint16_t>() : nullptr, ss.places.as<uint2>(), ss.res.as<SelectResult>());
+    FQ_HIP(hipGetLastError());
+  }
+  const auto judge = x ? &k_select_judge<true, SEL_TAIL> : a ? &k_select_judge<true, SEL_CLIP> : t ? &k_select_judge<true> : &k_select_judge<false>;
   const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
   hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
                      ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>(),
-                     a ? ss.clip.as<uint16_t>() : nullptr);
+                     a ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr);
   FQ_HIP(hipGetLastError());
   if (out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
     fq_timer_span_end(ctx, st);
@@ -939,13 +1275,15 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   FQ_HIP(hipMemcpyAsync(ss.host, ss.res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
   if (keep_out) FQ_HIP(hipMemcpyAsync(keep_out, ss.keep.p, (n_recs + 7) / 8, hipMemcpyDeviceToHost, st));
   if (win_out) FQ_HIP(hipMemcpyAsync(win_out, win, n_recs * 4, hipMemcpyDeviceToHost, st));
+  if (places_out) FQ_HIP(hipMemcpyAsync(places_out, ss.places.p, n_recs * 8, hipMemcpyDeviceToHost, st));
   FQ_HIP(hipStreamSynchronize(st));
   if (res.bad) {
     if (keep_out) memset(keep_out, 0, (n_recs + 7) / 8);
     if (win_out) memset(win_out, 0, n_recs * 4);
+    if (places_out) memset(places_out, 0, n_recs * 8);
     return FQGPU_E_ARG;
   }
-  for (unsigned i = 1; i < FQGPU_TRIM_REPORT_WORDS; i++) report[i] = res.w[i];
+  for (unsigned i = 1; i < words; i++) report[i] = res.w[i];
   report[0] = n_recs;
   const size_t total = (size_t)res.w[R_BYTES_KEPT];
   *out_len = total;

@@ -664,6 +664,15 @@ public:
     decodeChunkSelected(piece, cbs, trim, filter, report, "decodeChunkClipped", &adapter);
   }
 
+  /** Extension: the reads of the chunk clipped at `adapter` (nullptr: none), their poly-X tail and the sliding-window cut of
+   *  `tail` taken, trimmed by `trim` (nullptr: nothing more is cut) and then judged by `filter` (nullptr: every read that is not
+   *  emptied is kept), as decodeChunkTrimmed lays them out (fqgpu_chunk_tailtrim); `report` receives the chunk's
+   *  FQGPU_TAIL_REPORT_WORDS counters.  Works as decodeChunkClipped does in every other respect. */
+  void decodeChunkTailTrimmed(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_adapter *adapter, const fqgpu_tail &tail,
+                              const fqgpu_trim *trim, const fqgpu_filter *filter, uint64_t *report) {
+    decodeChunkSelected(piece, cbs, trim, filter, report, "decodeChunkTailTrimmed", adapter, &tail);
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */
@@ -683,20 +692,22 @@ public:
 
 private:
   /** decodeChunkFiltered (trim == nullptr; the filter is needed), decodeChunkTrimmed and decodeChunkClipped (with an adapter,
-   *  trim and filter may both be nullptr), `who` of the three: the check-only decode, the digest, then ONE fqgpu_chunk_filter /
-   *  fqgpu_chunk_trim / fqgpu_chunk_clip into a buffer of the chunk's recorded size -- the kept bytes are never more than the
+   *  trim and filter may both be nullptr) and decodeChunkTailTrimmed (with a tail, all three may be), `who` of the four: the
+   *  check-only decode, the digest, then ONE fqgpu_chunk_filter / fqgpu_chunk_trim / fqgpu_chunk_clip / fqgpu_chunk_tailtrim
+   *  into a buffer of the chunk's recorded size -- the kept bytes are never more than the
    *  chunk, so there is no size query */
   void decodeChunkSelected(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim *trim, const fqgpu_filter *filter,
-                           uint64_t *report, const char *who, const fqgpu_adapter *adapter = nullptr) {
+                           uint64_t *report, const char *who, const fqgpu_adapter *adapter = nullptr, const fqgpu_tail *tail = nullptr) {
     StageClock clk;
     last_digest_ = {};
-    const std::string name(who), step(adapter ? "clip" : trim ? "trim" : "filter");
+    const std::string name(who), step(tail ? "tail trim" : adapter ? "clip" : trim ? "trim" : "filter");
     const auto refused = [&](const std::string &what) {
       return std::runtime_error(name + ": chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
     };
+    if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
     if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
     if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-    if ((filter || !(trim || adapter)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+    if ((filter || !(trim || adapter || tail)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
     ChunkArgs a;
     if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
     clk.lap("misc");
@@ -723,7 +734,8 @@ private:
     piece.raw_data.resize(cbs.original_size.total);
     uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
     std::size_t len = 0;
-    const int src = adapter ? fqgpu_chunk_clip(ctx_, adapter, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
+    const int src = tail    ? fqgpu_chunk_tailtrim(ctx_, adapter, tail, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr, nullptr)
+                    : adapter ? fqgpu_chunk_clip(ctx_, adapter, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
                     : trim  ? fqgpu_chunk_trim(ctx_, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
                          : fqgpu_chunk_filter(ctx_, filter, out, piece.raw_data.size(), &len, report, nullptr);
     if (src != FQGPU_OK) throw refused("the " + step + ": " + fqgpu_strerror(src));

@@ -602,6 +602,67 @@ int fqgpu_chunk_clip(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_trim *t
 int fqgpu_dblock_clip(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f,
                       uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out);
 
+/* ---- Extension (nothing in the reference): POLY-X TAILS and a SLIDING-WINDOW quality cut taken from the 3' end of the reads
+ * of a chunk, between the adapter clip and the trim's steps, where the chunk lies already -- in HBM.  A two-colour instrument
+ * reads "no signal" as G, so a read that runs off its fragment ends in a run of G with a few errors in it and often high
+ * qualities (fastp trims these by default on such data); Trimmomatic SLIDINGWINDOW:W:Q and fastp --cut_right are the window
+ * rule.  For a read with the sequence line s[0, L) and Phred values p[i] = quality byte - 33, integer arithmetic throughout:
+ *   0  the clip      fqgpu_chunk_clip's step 0, unchanged: a0.  A NULL adapter: a0 = L
+ *   0b the poly tail over s[0, a0) (poly_bases on).  For a base X of the set and i = 1 .. a0: b_i = s[a0 - i]; mism_X(i) is the
+ *                    number of j in 1 .. i with b_j != X (an N is a mismatch for every X); ok_X(i) holds iff
+ *                    mism_X(i) <= min(i / poly_every, poly_max_mism).  v_X is the smallest i with !ok_X(i), a0 + 1 when there
+ *                    is none: the walk stops at the FIRST violation, a place behind it never counts, however well it matches.
+ *                    t_X is the largest i < v_X with b_i == X (the tail that is cut begins with an X), 0 when there is none;
+ *                    t_X < poly_min_len gives t_X = 0.  t is the largest t_X over the set and a1 = a0 - t.  Off: a1 = a0
+ *   1  fixed cuts    on the read as if its length were a1: f = min(cut_front, a1), e = a1 - min(cut_tail, a1 - f).  A NULL trim
+ *                    cuts nothing
+ *   1b the window    over [f, e) (window_len = W on, window_q = Q).  For p = f, f+1, ... while p + W <= e:
+ *                    S(p) = p[p] + ... + p[p+W-1]; take the smallest p with S(p) < Q * W; e2 is the smallest i >= p with
+ *                    p[i] < Q -- it exists and lies inside that window: the good bases at the window's front are kept, as fastp
+ *                    does.  No such p, e - f < W, or off: e2 = e
+ *   2 .. 4           the two running-sum walks of fqgpu_chunk_trim over [f, e2), then the crop
+ *   5  the filter    on the window that is left, exactly as fqgpu_chunk_trim: an emptied read is dropped, counted under
+ *                    dropped_short and reads_emptied
+ * Output, keep bits and windows have the forms of fqgpu_chunk_trim.
+ *   report  FQGPU_TAIL_REPORT_WORDS uint64_t: 0 .. 15 as fqgpu_chunk_clip's report -- word 12 stays the sum of L - start - n,
+ *           and bases_in = word 11 + word 12 + the sum of n keeps holding | 16 reads_with_poly_tail (a1 < a0, kept or not) |
+ *           17 bases_cut_poly (the sum of a0 - a1) | 18 reads_window_cut (e2 < e) | 19 bases_cut_window (the sum of e - e2) |
+ *           20 .. 23 zero.  Reports of several chunks add word by word
+ *   places_out   NULL, or 4 uint16_t per record, kept or not: a0, a1, e, e2
+ *   out == NULL, out_cap < *out_len, keep_out, win_out   as fqgpu_chunk_clip
+ * The sequence line is read iff max_n is on, an adapter is given, or poly_bases != 0; the quality line iff the trim's rule
+ * says so or window_len != 0.  A line that is read is judged over all L bytes (ACGTN; 33 .. 96: FQGPU_E_ARG), a line that is
+ * not read is not looked at.  A tail fqgpu_tail_check refuses (poly_bases above 15; a poly_max_mism above 255; with poly_bases
+ * on a poly_min_len outside 1 .. 65535 or a poly_every outside 2 .. 255, with it off either of the two not zero; window_len
+ * above 32; with window_len on a window_q outside 1 .. 64, with it off a window_q not zero; reserved not zero), an adapter,
+ * trim or filter its own check refuses, a record outside the chunk or of length 0, a NULL where data is expected: FQGPU_E_ARG,
+ * with *out_len = 0, a zeroed report and -- where the chunk itself is refused -- zeroed keep bits, windows and places.
+ *   fqgpu_tail_check      host only: FQGPU_OK or FQGPU_E_ARG
+ *   fqgpu_chunk_tailtrim  the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_clip is valid, on
+ *                         the same stream; it leaves the chunk as it is and is waited for before it returns.  x == NULL, or a
+ *                         tail with both rules off: output, report words 0 .. 15, keep bits and windows are those of
+ *                         fqgpu_chunk_clip with the same a, t, f (a NULL a then follows that call's rules), words 16 .. 23
+ *                         zero, the places a0 = a1 and e = e2
+ *   fqgpu_dblock_tailtrim waits for the block's last operation as fqgpu_dblock_clip does; x == NULL: as above.
+ * Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_tail_check works. */
+typedef struct {
+  uint32_t poly_bases;     /* bit 0 A, 1 C, 2 G, 3 T; 0 = poly trim off; above 15 refused */
+  uint32_t poly_min_len;   /* shortest tail that is cut; 1 .. 65535 when poly_bases != 0, else 0 */
+  uint32_t poly_every;     /* one mismatch allowed per this many tail bases; 2 .. 255 when on, else 0 */
+  uint32_t poly_max_mism;  /* and never more than this many; 0 .. 255 */
+  uint32_t window_len;     /* W; 0 = window cut off; 1 .. 32 */
+  uint32_t window_q;       /* Q; 1 .. 64 when window_len != 0, else 0 */
+  uint32_t reserved[2];    /* zero */
+} fqgpu_tail;
+#define FQGPU_TAIL_REPORT_WORDS 24
+int fqgpu_tail_check(const fqgpu_tail *x);
+int fqgpu_chunk_tailtrim(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                         uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
+                         uint16_t *places_out);
+int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                          const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
+                          uint32_t *win_out, uint16_t *places_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -40,6 +40,20 @@
 //               device, .fqx used and .fqs verified as with a trim.  An adapter option with c, x, t or s, with --records,
 //               --fasta, --index or --index-stride, without --adapter, and an adapter fqgpu_adapter_check refuses are usage
 //               errors.  A failed run leaves neither <out.fastq> nor <out.fastq>.part)
+//   fqc_tool d <in.fqc> <out.fastq> [-t threads] [-d dev,dev,...] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M]
+//              [--window W:Q]
+//              (extension: restores the reads with their POLY-G TAIL (--poly-x: a tail of any one base) and everything from a
+//               SLIDING-WINDOW quality drop on cut, with or without --adapter, the trim and the filter options; both stand
+//               behind the adapter clip and in front of the trim.  The tail: the longest run at the 3' end, at least N bases
+//               (default 10, 1 .. 65535), that begins and ends with the base and has at most one other base per K (default 8,
+//               2 .. 255) and M in all (default 5, 0 .. 255); the walk from the end stops at the first place with more.  The
+//               window (Trimmomatic SLIDINGWINDOW:W:Q, fastp --cut_right): behind --cut-front / --cut-tail, the read is cut in
+//               the first window of W bases (1 .. 32) whose mean Phred is below Q (1 .. 64), at its first base below Q.
+//               Found, trimmed and gathered on the device, .fqx used and .fqs verified as with a trim.  One of these options
+//               with c, x, t or s, with --records, --fasta, --index or --index-stride, --poly-every or --poly-mism without
+//               --poly-g or --poly-x, and values fqgpu_tail_check refuses are usage errors.  A failed run leaves neither
+//               <out.fastq> nor <out.fastq>.part.  N is optional: the argument behind --poly-g / --poly-x is taken for it
+//               whenever it does not begin with '-', so a word that is no number there is a usage error, not a path)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -68,7 +82,8 @@
 // number that is no integer and in no report); with a filter "filter": what was read, what was kept and what each
 // criterion dropped ("records" / "raw_bytes" of the line are then what was written); with a trim "trim": the same and the
 // reads trimmed, the bases cut from either end and the reads emptied, and with an adapter -- then alone -- the reads in which it
-// was found and the bases it took.  Needs a GPU: no CPU fallback.
+// was found and the bases it took, and with a poly or window option -- then alone -- the reads with a poly tail, the bases it
+// took, the reads the window cut and the bases it took.  Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -87,6 +102,8 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--min-len N] [--max-len N] [--max-n K] [--min-mean-q Q] [--max-low-q Q:PCT]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--cut-front N] [--cut-tail N] [--trim-q5 Q] [--trim-q3 Q] [--crop L] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
+                         "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q] [adapter options] [trim options] [filter options]\n"
+                         "                  (the argument behind --poly-g / --poly-x is taken as N unless it begins with '-')\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
@@ -105,6 +122,9 @@ int main(int argc, char **argv) {
   bool trimmed = false;
   fqgpu_adapter adapter = {{0}, 0, 5, 10, 0};
   bool clipped = false, adapter_opt = false;
+  fqgpu_tail tail = {0, 0, 0, 0, 0, 0, {0, 0}};
+  uint32_t poly_every = 8, poly_mism = 5;
+  bool tailed = false, poly_opt = false;
   // a decimal number of at most nine digits (so that it fits a uint32_t)
   const auto u32 = [](const std::string &t, uint32_t &out) {
     if (t.empty() || t.size() > 9 || t.find_first_not_of("0123456789") != std::string::npos) return false;
@@ -165,6 +185,33 @@ int main(int argc, char **argv) {
       }
       adapter_opt = true;
     }
+    else if (a == "--poly-g" || a == "--poly-x") {
+      tail.poly_bases = a == "--poly-g" ? 4u : 15u;
+      tail.poly_min_len = 10;
+      if (i + 1 < argc && argv[i + 1][0] != '-') {  // [N]
+        const std::string v = argv[++i];
+        if (!u32(v, tail.poly_min_len)) {
+          std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+          return 2;
+        }
+      }
+      tailed = true;
+    } else if (a == "--poly-every" || a == "--poly-mism") {
+      const std::string v = val();
+      if (!u32(v, a == "--poly-every" ? poly_every : poly_mism)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      poly_opt = true;
+    } else if (a == "--window") {
+      const std::string v = val();
+      const std::size_t colon = v.find(':');
+      if (colon == std::string::npos || !u32(v.substr(0, colon), tail.window_len) || !u32(v.substr(colon + 1), tail.window_q) || !tail.window_len) {
+        std::fprintf(stderr, "--window %s: expected W:Q (cut in the first window of W bases, 1 .. 32, whose mean Phred is below Q, 1 .. 64)\n", v.c_str());
+        return 2;
+      }
+      tailed = true;
+    }
     else if (a == "--records" && argv[1][0] == 'd') {
       // A:B or A: (decimal record numbers)
       const std::string v = val();
@@ -224,6 +271,24 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
+  if ((tailed || poly_opt) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "poly tails and the window cut go with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (poly_opt && !tail.poly_bases) {
+    std::fprintf(stderr, "--poly-every and --poly-mism need --poly-g or --poly-x\n");
+    return 2;
+  }
+  if (tailed) {
+    if (tail.poly_bases) {
+      tail.poly_every = poly_every;
+      tail.poly_max_mism = poly_mism;
+    }
+    if (fqgpu_tail_check(&tail) != FQGPU_OK) {
+      std::fprintf(stderr, "tail trims: expected --poly-g / --poly-x 1 .. 65535, --poly-every 2 .. 255, --poly-mism 0 .. 255, --window W:Q with W 1 .. 32 and Q 1 .. 64\n");
+      return 2;
+    }
+  }
   // (said before any device is touched)
   if (stats_opt && argv[1][0] != 'c') {
     std::fprintf(stderr, "--stats goes with c alone (s <in.fqc> <report.tsv> summarises an archive): not with d, x, t or s\n");
@@ -247,6 +312,8 @@ int main(int argc, char **argv) {
     const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
+                         : tailed  ? processArchiveTailTrimmed(argv[2], argv[3], clipped ? &adapter : nullptr, tail, trimmed ? &trim : nullptr,
+                                                               filtered ? &filter : nullptr, set)
                          : clipped ? processArchiveClipped(argv[2], argv[3], adapter, trimmed ? &trim : nullptr, filtered ? &filter : nullptr, set)
                          : trimmed ? processArchiveTrimmed(argv[2], argv[3], trim, filtered ? &filter : nullptr, set)
                          : filtered ? processArchiveFiltered(argv[2], argv[3], filter, set)
@@ -274,18 +341,21 @@ int main(int argc, char **argv) {
       std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
     }
     if (filtered) {
-      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
+      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped || tailed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
       std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
                   "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
                   w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
     }
-    if (trimmed || clipped) {
+    if (trimmed || clipped || tailed) {
       const auto w = [&](unsigned i) { return (unsigned long long)r.trim[i]; };
       std::printf(", \"trim\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
                   "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
                   "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu",
                   w(0), w(1), w(2), w(3), w(4), w(5), w(6), w(7), w(8), w(9), w(10), w(11), w(12), w(13));
       if (clipped) std::printf(", \"reads_with_adapter\": %llu, \"bases_cut_adapter\": %llu", w(14), w(15));
+      if (tailed)
+        std::printf(", \"reads_with_poly_tail\": %llu, \"bases_cut_poly\": %llu, \"reads_window_cut\": %llu, \"bases_cut_window\": %llu", w(16), w(17),
+                    w(18), w(19));
       std::printf("}");
     }
     if (fasta) std::printf(", \"form\": \"fasta\", \"archive_bytes_read\": %llu", (unsigned long long)r.archive_bytes_read);
