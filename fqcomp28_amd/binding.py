@@ -164,6 +164,11 @@ _PROTOS = {
                                        C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_tailtrim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_probe_words": (C.c_size_t, [C.c_uint, C.c_uint]),
+    "fqgpu_probes_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fqgpu_dblock_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fqgpu_probe_merge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "fqgpu_host_alloc": (C.c_void_p, [C.c_size_t]),
     "fqgpu_host_free": (None, [C.c_void_p]),
     "fqgpu_host_trim": (C.c_size_t, []),
@@ -428,6 +433,65 @@ def _tail_call(fn, front, adapter, tail, trim, flt, n_recs, want_win=True, want_
                 win=win, places=places)
 
 
+PROBES_MAX = 16
+PROBE_HEAD_WORDS, PROBE_TABLE_HEAD_WORDS = 8, 8
+PROBE_WINDOW_ROWS = 320  # rows the device sums on chip (select.hip); a hit between this and `positions` is added one by one
+PROBE_TABLE_NAMES = ("reads_with", "bases_behind", "reads_whole", "reads_emptied")
+_ADAPTER_WORDS = ADAPTER_MAX // 4 + 4
+
+
+def read_probes(adapters, n=None, reserved=(0, 0, 0)):
+    """an fqgpu_probes (include/fqgpu.h) as a uint32 array of 4 + 16 * 20 words: n, three reserved words, then the probes --
+    `adapters` is a list of read_adapter arrays, at most PROBES_MAX of it is stored; n: what n says when it is not
+    len(adapters) (for the checks' tests)"""
+    p = np.zeros(4 + PROBES_MAX * _ADAPTER_WORDS, dtype=np.uint32)
+    p[0] = len(adapters) if n is None else n
+    p[1:4] = reserved
+    for k, a in enumerate(adapters[:PROBES_MAX]):
+        p[4 + k * _ADAPTER_WORDS:4 + (k + 1) * _ADAPTER_WORDS] = np.ascontiguousarray(a, dtype=np.uint32)
+    return p
+
+
+def probes_check(probes):
+    """fqgpu_probes_check -> rc (host only)"""
+    return lib().fqgpu_probes_check(_p(probes))
+
+
+def probe_words(n_probes, positions):
+    """fqgpu_probe_words: uint64 words of an adapter-content result (0: n_probes or positions out of range)"""
+    return lib().fqgpu_probe_words(n_probes, positions)
+
+
+def probe_merge(dst, src):
+    """fqgpu_probe_merge: dst += src in place (two uint64 arrays) -> rc"""
+    assert dst.dtype == np.uint64 and src.dtype == np.uint64 and dst.flags.c_contiguous and src.flags.c_contiguous
+    return lib().fqgpu_probe_merge(_p(dst), dst.size, _p(src), src.size)
+
+
+def probe_view(words):
+    """The parts of an adapter-content result (include/fqgpu.h) as numpy views of `words`, a uint64 array of
+    probe_words(n, P): the head's words by name, `tables` uint64[n + 1, 8] (PROBE_TABLE_NAMES in front) and `rows`
+    uint64[n + 1, P + 1]; table n is "any"."""
+    assert words.dtype == np.uint64 and words.ndim == 1 and words.size >= PROBE_HEAD_WORDS
+    n, P = int(words[2]), int(words[3])
+    stride = PROBE_TABLE_HEAD_WORDS + P + 1
+    assert words.size == PROBE_HEAD_WORDS + (n + 1) * stride, "not a result of the probes and positions it names"
+    body = words[PROBE_HEAD_WORDS:].reshape(n + 1, stride)
+    return dict(n_records=words[0:1], n_bases=words[1:2], n_probes=words[2:3], positions=words[3:4], fingerprint=words[4:5],
+                tables=body[:, :PROBE_TABLE_HEAD_WORDS], rows=body[:, PROBE_TABLE_HEAD_WORDS:])
+
+
+def _probe_call(fn, front, probes, positions, n_recs, want_places=True, cap_words=None):
+    """A device probe call -> dict(rc, out, places): out a fresh uint64 array of the size probes and positions ask for
+    (cap_words: of that many words instead), places uint16[n_recs, n] or None"""
+    probes = np.ascontiguousarray(probes, dtype=np.uint32)
+    n = int(probes[0])
+    out = np.zeros(max(probe_words(n, positions), 1) if cap_words is None else max(cap_words, 1), dtype=np.uint64)
+    places = np.zeros((n_recs, min(max(n, 1), PROBES_MAX)), dtype=np.uint16) if want_places else None
+    rc = fn(*front, _p(probes), positions, _p(out), out.size if cap_words is None else cap_words, _p(places))
+    return dict(rc=rc, out=out, places=places)
+
+
 def pinned_empty(n_bytes):
     """uint8 array in page-locked host memory (fqgpu_host_alloc); freed when the array dies"""
     p = lib().fqgpu_host_alloc(max(1, n_bytes))
@@ -532,6 +596,11 @@ class DBlock:
         rc, out = _stats_call(lib().fqgpu_dblock_stats, positions, self.ctx.h, self.h)
         _check(rc, "dblock_stats")
         return out
+
+    def probe(self, probes, positions, want_places=True, **kw):
+        """fqgpu_dblock_probe: the adapter content of the raw block as it lies on the device, for `probes` (read_probes) ->
+        dict(rc, out, places); see _probe_call, probe_view"""
+        return _probe_call(lib().fqgpu_dblock_probe, (self.ctx.h, self.h), probes, positions, self.n_recs, want_places, **kw)
 
     def filter(self, flt, **kw):
         """fqgpu_dblock_filter: the reads of the raw block, as it lies on the device, that pass `flt` (read_filter) ->
@@ -657,6 +726,11 @@ class Context:
         """fqgpu_chunk_stats -> (rc, words): the read summary of the chunk on the staging block, where chunk_crc32 is valid"""
         return _stats_call(lib().fqgpu_chunk_stats, positions, self.h)
 
+    def chunk_probe(self, probes, positions, n_recs, want_places=True, **kw):
+        """fqgpu_chunk_probe: the adapter content of the chunk on the staging block (n_recs records), where chunk_stats is
+        valid -> dict(rc, out, places); see _probe_call"""
+        return _probe_call(lib().fqgpu_chunk_probe, (self.h,), probes, positions, n_recs, want_places, **kw)
+
     def chunk_filter(self, flt, n_recs, **kw):
         """fqgpu_chunk_filter: the reads of the chunk on the staging block (n_recs records) that pass `flt`, where chunk_stats
         is valid -> dict(rc, out, out_len, report, keep); see _filter_call"""
@@ -742,14 +816,15 @@ class Context:
         return dict(rc=rc, seq=bufs["seq"][:sl].copy(), qual=bufs["qual"][:ql].copy(), readlens=bufs["readlens"],
                     n_count=bufs["n_count"], n_pos=bufs["n_pos"][:nn].copy(), raw_after=raw)
 
-    def encode_raw(self, raw, flags=0, recs=None, header_format=None, want_crc=False, want_stats=None):
+    def encode_raw(self, raw, flags=0, recs=None, header_format=None, want_crc=False, want_stats=None, want_probes=None):
         """The two-halves call on an UNPARSED chunk (fqgpu_encode_begin / _records / _wait / _end): the
         record table comes back from the GPU.  -> dict like encode_block's, plus recs and used_len.
         header_format = (types, separators, first_header) -- types[i] 0 = NUMERIC / 1 = STRING, separators as bytes,
         first_header with its '@' -- also codes the header fields on the device (fqgpu_encode_headers_*):
         `header_fields` = [(flags, content, lengths) per field] or, for a header that cannot be coded,
         `headers_rc` = FQGPU_E_HEADER and `bad_record`.  want_crc: fqgpu_chunk_crc32 between begin and end ->
-        `crc32`, `crc_len`; want_stats=P: fqgpu_chunk_stats there too -> `stats`."""
+        `crc32`, `crc_len`; want_stats=P: fqgpu_chunk_stats there too -> `stats`; want_probes=(probes, P): fqgpu_chunk_probe
+        there too -> `probe`, `probe_places`."""
         raw = np.array(raw, dtype=np.uint8, copy=True)
         n, nb, used = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
         if recs is not None:
@@ -771,6 +846,12 @@ class Context:
             if rc:
                 lib().fqgpu_encode_cancel(self.h)
                 return dict(rc=rc)
+        if want_probes is not None:
+            got = self.chunk_probe(want_probes[0], want_probes[1], n.value)
+            if got["rc"]:
+                lib().fqgpu_encode_cancel(self.h)
+                return dict(rc=got["rc"])
+            hdr["probe"], hdr["probe_places"] = got["out"], got["places"]
         if header_format is not None:
             types, seps, first = header_format
             types = np.ascontiguousarray(types, dtype=np.uint8)
@@ -822,7 +903,7 @@ class Context:
                     recs=table, used_len=used.value, n_bases=nb.value, **hdr)
 
     def decode_chunk(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, index=None,
-                     build_index=False, want_raw=True, want_stats=None):
+                     build_index=False, want_raw=True, want_stats=None, want_probes=None):
         """Both decode passes on the device (fqgpu_decode_chunk): headers decoded from their field streams, the chunk
         laid out, sequence and quality decoded.  header_format = (types, separators, first_header) and header_fields =
         [(flags, content, lengths) per field] as encode_raw takes and returns them; index as in decode_block.
@@ -831,7 +912,8 @@ class Context:
         on the way -> also "index": (seq, qual), two empty arrays after a failure; want_raw=False: raw is None and
         raw_out == NULL goes down -- index only with build_index, or a decode that only checks on a handle in checking
         mode (set_check_only); without either the call is refused (FQGPU_E_ARG).  want_stats=P: fqgpu_chunk_stats
-        behind the decode -> also "stats_rc", "stats"."""
+        behind the decode -> also "stats_rc", "stats"; want_probes=(probes, P): fqgpu_chunk_probe behind the decode -> also
+        "probe_rc", "probe", "probe_places"."""
         args, keep = _chunk_args(header_format, header_fields, readlens, seq, qual, n_count, n_pos, index)
         raw = np.zeros(raw_len, dtype=np.uint8) if want_raw else None  # (None: index only, or a handle that only checks)
         recs = np.zeros(len(readlens), dtype=REC_DTYPE)
@@ -848,15 +930,22 @@ class Context:
                     _check(lib().fqgpu_decode_index(self.h, s, _p(idx), idx.size, C.byref(n_idx)), "fqgpu_decode_index")
                 built.append(idx)
             return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), index=tuple(built),
-                        **self._want_stats(want_stats))
+                        **self._want_stats(want_stats), **self._want_probes(want_probes, len(readlens)))
         rc = lib().fqgpu_decode_chunk(self.h, *args, _p(raw), raw_len, _p(recs), C.byref(laid), C.byref(bad))
-        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), **self._want_stats(want_stats))
+        return dict(rc=rc, raw=raw, recs=recs, laid_out_len=laid.value, bad_record=_bad(bad), **self._want_stats(want_stats),
+                    **self._want_probes(want_probes, len(readlens)))
 
     def _want_stats(self, positions):
         if positions is None:
             return {}
         rc, words = self.chunk_stats(positions)
         return dict(stats_rc=rc, stats=words)
+
+    def _want_probes(self, want, n_recs):
+        if want is None:
+            return {}
+        got = self.chunk_probe(want[0], want[1], n_recs)
+        return dict(probe_rc=got["rc"], probe=got["out"], probe_places=got["places"])
 
     def decode_chunk_range(self, header_format, header_fields, readlens, seq, qual, n_count, n_pos, raw_len, first, end,
                            index=None, out_cap=None):

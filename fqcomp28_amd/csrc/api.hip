@@ -1686,6 +1686,31 @@ extern "C" int fqgpu_dblock_stats(fqgpu_ctx *ctx, const fqgpu_dblock *b, unsigne
   return stats_call(ctx, b, false, positions, out, cap_words);
 }
 
+// ------------------------------------------------------------------ adapter content of a chunk in HBM (select.hip)
+// The two calls (b, staged: as stats_call): no device is said before any argument is looked at; an `out` that is large
+// enough is zeroed before anything else can fail.
+static int probe_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const fqgpu_probes *p, unsigned positions, uint64_t *out,
+                      size_t cap_words, uint16_t *places_out) {
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  if (!ctx || !out || fqgpu_probes_check(p) != FQGPU_OK) return FQGPU_E_ARG;
+  const size_t words = fqgpu_probe_words(p->n, positions);
+  if (!words) return FQGPU_E_ARG;
+  if (cap_words < words) return FQGPU_E_OVERFLOW;
+  memset(out, 0, words * sizeof(uint64_t));
+  if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
+  return fq_probe_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, p, positions, out, places_out);
+}
+
+extern "C" int fqgpu_chunk_probe(fqgpu_ctx *ctx, const fqgpu_probes *p, unsigned positions, uint64_t *out, size_t cap_words,
+                                 uint16_t *places_out) {
+  return probe_call(ctx, nullptr, true, p, positions, out, cap_words, places_out);
+}
+
+extern "C" int fqgpu_dblock_probe(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_probes *p, unsigned positions, uint64_t *out,
+                                  size_t cap_words, uint16_t *places_out) {
+  return probe_call(ctx, b, false, p, positions, out, cap_words, places_out);
+}
+
 // ------------------------------------------------------------------ the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip)
 // The six calls (b, staged: as stats_call; trim: a trim call, which needs *t and takes a NULL filter for one that keeps
 // everything; a: a clip call's adapter -- with one, a NULL trim is one that cuts nothing; a clip call without one is the trim

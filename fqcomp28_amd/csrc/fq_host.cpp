@@ -107,6 +107,48 @@ extern "C" int fqgpu_adapter_check(const fqgpu_adapter *a) {
   return FQGPU_OK;
 }
 
+// Adapter content (select.hip counts it): the size of a result, what a probe set may say, its fingerprint, and dst += src.
+extern "C" size_t fqgpu_probe_words(unsigned n_probes, unsigned positions) {
+  if (n_probes < 1u || n_probes > FQGPU_PROBES_MAX || positions < 1u || positions > 65535u) return 0u;
+  return 8u + ((size_t)n_probes + 1u) * (8u + (size_t)positions + 1u);
+}
+extern "C" int fqgpu_probes_check(const fqgpu_probes *p) {
+  if (!p || p->n < 1u || p->n > FQGPU_PROBES_MAX || p->reserved[0] || p->reserved[1] || p->reserved[2]) return FQGPU_E_ARG;
+  for (unsigned k = 0; k < p->n; k++)
+    if (fqgpu_adapter_check(&p->probe[k]) != FQGPU_OK) return FQGPU_E_ARG;
+  const uint8_t *const rest = reinterpret_cast<const uint8_t *>(&p->probe[p->n]);
+  for (size_t i = 0; i < (FQGPU_PROBES_MAX - p->n) * sizeof(fqgpu_adapter); i++)
+    if (rest[i]) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+// zlib's CRC-32 of the bytes of probe[0 .. n) (bit by bit: at most 1280 bytes, once per call)
+uint32_t fq_probes_fingerprint(const fqgpu_probes *p) {
+  static_assert(sizeof(fqgpu_adapter) == 80, "the fingerprint is taken over 80 bytes a probe");
+  const uint8_t *const b = reinterpret_cast<const uint8_t *>(p->probe);
+  uint32_t c = 0xFFFFFFFFu;
+  for (size_t i = 0; i < p->n * sizeof(fqgpu_adapter); i++) {
+    c ^= b[i];
+    for (int j = 0; j < 8; j++) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+  }
+  return ~c;
+}
+extern "C" int fqgpu_probe_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words) {
+  if (!dst || !src || src_words < 8u || dst_words != src_words || src[2] > FQGPU_PROBES_MAX || src[3] > 65535u ||
+      src_words != fqgpu_probe_words((unsigned)src[2], (unsigned)src[3]))
+    return FQGPU_E_ARG;
+  const bool empty = dst[0] == 0;  // (a block of zeros is an empty result of any probe set)
+  const bool blank = empty && !dst[2] && !dst[3] && !dst[4];
+  if (!blank && (dst[2] != src[2] || dst[3] != src[3] || dst[4] != src[4])) return FQGPU_E_ARG;
+  if (empty) {
+    memcpy(dst, src, src_words * sizeof(uint64_t));
+    return FQGPU_OK;
+  }
+  if (!src[0]) return FQGPU_OK;
+  for (size_t i = 0; i < dst_words; i++)
+    if (i < 2u || i >= 8u) dst[i] += src[i];
+  return FQGPU_OK;
+}
+
 // Poly-X tails and the sliding-window cut (select.hip applies them): what a tail may say.
 extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   if (!x || x->poly_bases > 15u || x->poly_max_mism > 255u || x->window_len > 32u || x->reserved[0] || x->reserved[1]) return FQGPU_E_ARG;

@@ -240,9 +240,11 @@ struct StatsScratch {
 // place (a uint16_t: k_adapter_find writes it, the judge reads it) and -- by a tail call alone -- its places a0, a1, e, e2
 // (four uint16_t: k_tail_find writes them, the judge reads them), the keep bits, the offsets of the kept records
 // in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
-// filter and trim calls: each is waited for before it returns.
+// filter and trim calls: each is waited for before it returns.  A probe call (adapter content) has two buffers of its own
+// here: its u64 result tables and -- when asked for -- the records' places, n uint16_t each.
 struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
+  DevBuf probe_out, probe_places;
   void *host = nullptr;
   void release();
 };
@@ -449,6 +451,12 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                     uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x = nullptr,
                     uint16_t *places_out = nullptr);
+
+// Adapter content of a chunk in HBM (select.hip; the probe set has passed its check, positions is 1 .. 65535), on st, waited
+// for: out[0, fqgpu_probe_words(p->n, positions)) on the host and -- places_out != nullptr -- p->n places per record
+int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                   const fqgpu_probes *p, unsigned positions, uint64_t *out, uint16_t *places_out);
+uint32_t fq_probes_fingerprint(const fqgpu_probes *p);  // fq_host.cpp: zlib's CRC-32 of the bytes of probe[0 .. n)
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total
 int fq_scan_u32_to_u32(hipStream_t st, const uint32_t *in, size_t n, uint32_t *out, DevBuf &tmp);

@@ -20,6 +20,7 @@
 #include <exception>
 #include <functional>
 #include <mutex>
+#include <optional>
 #include <thread>
 #include <type_traits>
 
@@ -60,6 +61,9 @@ struct Settings {  // the part of src/settings.h:36-50 this path needs, plus the
   /** Extension: rows of the read summary every worker takes of its chunks where they lie on the device (Workspace::setStats;
    *  1 .. 65535); the report carries the merged result.  0: none.  compressFarm and processArchiveCheck look at it. */
   unsigned stats_positions = 0;
+  /** Extension: the adapters every worker also searches its chunks for, where the summary is taken and with its rows
+   *  (Workspace::setProbes; needs stats_positions); the report carries the merged adapter content.  Empty: none. */
+  std::optional<fqgpu_probes> probes;
 };
 
 struct InputStats {  // src/report.h
@@ -85,18 +89,27 @@ struct FarmReport {
   uint32_t file_crc32 = 0;
   uint64_t archive_bytes_read = 0;  // processArchiveFasta: what was read of the archive file (the quality streams are not)
   std::vector<uint64_t> stats;      // the read summary of every chunk, merged (fqgpu_stats_words(set.stats_positions) words; empty: none taken)
+  std::vector<uint64_t> probes;     // the adapter content of every chunk, merged (fqgpu_probe_words words; empty: set.probes was not given)
   std::vector<uint64_t> filter;     // processArchiveFiltered: the chunks' filter reports, added word by word (FQGPU_FILTER_REPORT_WORDS; empty: none)
   std::vector<uint64_t> trim;       // processArchiveTrimmed: the chunks' trim reports, added word by word (FQGPU_TRIM_REPORT_WORDS; empty: none)
 };
 
 namespace detail {
-/** the workers' summaries into the report */
+/** the workers' summaries, and their adapter content, into the report */
 template <class Workspaces> void mergeStats(FarmReport &rep, const Workspaces &wksp, unsigned positions) {
   if (!positions) return;
   rep.stats.assign(fqgpu_stats_words(positions), 0);
   rep.stats[5] = positions;
   for (const auto &w : wksp) fqgpuCheck(fqgpu_stats_merge(rep.stats.data(), rep.stats.size(), w->stats().data(), w->stats().size()), "stats");
+  for (const auto &w : wksp) {
+    const std::vector<uint64_t> &p = w->probes();
+    if (p.empty()) continue;
+    if (rep.probes.empty()) rep.probes.assign(p.size(), 0);
+    if (p[0]) fqgpuCheck(fqgpu_probe_merge(rep.probes.data(), rep.probes.size(), p.data(), p.size()), "probes");  // (a worker without a chunk has nothing)
+  }
 }
+/** the report's probe set: nullptr unless a summary is taken as well */
+inline const fqgpu_probes *probesOf(const Settings &set) { return set.stats_positions && set.probes ? &*set.probes : nullptr; }
 inline std::size_t miscBytes(const CompressedBuffersDst &cbs) {
   std::size_t n = cbs.compressed_readlens.size() + cbs.compressed_n_count.size() + cbs.compressed_n_pos.size();
   for (const auto &f : cbs.compressed_header_fields) n += f.isDifferentFlag.size() + f.content.size() + f.contentLength.size();
@@ -168,6 +181,7 @@ FarmReport compressFarm(const DatasetMeta &meta, Source &&next_chunk, Sink &&wri
     wksp[t]->setDecodeIndex(set.decode_index, set.index_stride);
     wksp[t]->setChecksum(set.checksum);
     wksp[t]->setStats(set.stats_positions);
+    wksp[t]->setProbes(detail::probesOf(set), set.stats_positions);
     chunks[t].raw_data.reserve(set.reading_chunk_size);
     buffers[t].seq.reserve(set.reading_chunk_size / 8 + (1u << 20));
     buffers[t].qual.reserve(set.reading_chunk_size / 3 + (1u << 20));
@@ -269,6 +283,7 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
     wksp[t]->setVerify(set.verify);
     if (set.check_only) wksp[t]->setCheckOnly(true);
     wksp[t]->setStats(set.stats_positions);
+    wksp[t]->setProbes(detail::probesOf(set), set.stats_positions);
   });
   std::vector<InputStats> istats(T);
   FarmReport rep;
@@ -807,9 +822,9 @@ inline FarmReport processArchiveTailTrimmed(const path_t &archive_path, const pa
   return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveTailTrimmed", adapter, &tail);
 }
 
-/** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function
- *  of the summary -- written as `<path>.part` and renamed when it is complete. */
-inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w) {
+namespace detail {
+/** the report of the summary `w`, `more` behind it */
+inline void writeStatsReportText(const path_t &path, const std::vector<uint64_t> &w, const std::string &more) {
   if (w.size() < 176 || w.size() != fqgpu_stats_words(static_cast<unsigned>(w[5]))) throw std::logic_error("writeStatsReport: not a read summary");
   const std::size_t rows = static_cast<std::size_t>(w[5]) + 1;
   const uint64_t *len = w.data() + 176, *base = len + rows, *qual = base + 5 * rows;
@@ -840,6 +855,7 @@ inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w)
   };
   table("base", base, 5);
   table("qual", qual, 64);
+  out += more;
   const path_t part = path.string() + ".part";
   std::FILE *f = std::fopen(part.string().c_str(), "wb");
   const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
@@ -849,6 +865,44 @@ inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w)
     throw std::runtime_error("cannot write " + part.string());
   }
   std::filesystem::rename(part, path);
+}
+}  // namespace detail
+/** Extension: the report file of a read summary (fqgpu_chunk_stats) -- text, tab-separated, integers only, a pure function
+ *  of the summary -- written as `<path>.part` and renamed when it is complete. */
+inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w) { detail::writeStatsReportText(path, w, std::string()); }
+/** Extension: the same report followed by the lines of an adapter content result `p` (fqgpu_chunk_probe) for the probe set
+ *  `set`, whose probes have the names `names`: per probe "probe", its number, name, sequence, min_overlap, max_err_pct and the
+ *  table's four counters, the same for "any" with "-" in the probe's places, then "probepos", the table and the row for every
+ *  non-zero cell.  An empty `p` (no chunk was taken) counts as a result of zeros. */
+inline void writeStatsReport(const path_t &path, const std::vector<uint64_t> &w, const std::vector<uint64_t> &p, const fqgpu_probes &set,
+                             const std::vector<std::string> &names) {
+  const unsigned n = set.n;
+  const std::size_t rows = static_cast<std::size_t>(w.size() > 5 ? w[5] : 0) + 1, stride = 8 + rows;
+  if (names.size() != n || (!p.empty() && (p.size() != fqgpu_probe_words(n, static_cast<unsigned>(rows - 1)) || (p[0] && (p[2] != n || p[3] != rows - 1)))))
+    throw std::logic_error("writeStatsReport: not an adapter content result of these probes");
+  const auto word = [&](std::size_t t, std::size_t i) -> uint64_t { return p.empty() ? 0 : p[8 + t * stride + i]; };
+  std::string out;
+  const auto num = [&](uint64_t v) { out += std::to_string(v); };
+  for (unsigned t = 0; t <= n; ++t) {
+    out += "probe\t";
+    if (t < n) {
+      const fqgpu_adapter &a = set.probe[t];
+      num(t); out += '\t'; out += names[t]; out += '\t'; out.append(reinterpret_cast<const char *>(a.seq), a.len); out += '\t';
+      num(a.min_overlap); out += '\t'; num(a.max_err_pct);
+    } else {
+      out += "any\t-\t-\t-\t-";
+    }
+    for (unsigned c = 0; c < 4; ++c) { out += '\t'; num(word(t, c)); }
+    out += '\n';
+  }
+  for (unsigned t = 0; t <= n; ++t)
+    for (std::size_t r = 0; r < rows; ++r)
+      if (const uint64_t v = word(t, 8 + r)) {
+        out += "probepos\t";
+        if (t < n) num(t); else out += "any";
+        out += '\t'; num(r); out += '\t'; num(v); out += '\n';
+      }
+  detail::writeStatsReportText(path, w, out);
 }
 /** total Phred of a read summary / its bases (0 without bases) */
 inline double statsMeanQuality(const std::vector<uint64_t> &w) {

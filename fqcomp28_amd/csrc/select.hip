@@ -39,6 +39,8 @@
 // sequence lines in the judge's access pattern, the search itself bit-parallel -- a word's bases as four bit planes, every
 // place a shift, four ANDs with the adapter's planes and a population count.  It leaves one uint16_t per record, the clip
 // place, which the judge (its flag CLIP) takes for the read's length in the trim's steps; the gather sees only windows.
+// Its template flag PROBE makes it the adapter-content pass (fqgpu_chunk_probe, fqgpu_dblock_probe): the same search with up
+// to sixteen adapters over the same planes, the hits counted by read position in LDS; no judge and no gather behind it.
 //
 // fq_scan_u32_to_u64 -- the kept sizes become the records' places in the output.
 //
@@ -351,12 +353,15 @@ __device__ __forceinline__ unsigned clip_word_hits(const ClipWord own, const Cli
 
 // One request of a line (word 8 k + sub in lane sub, k = 0, 1) searched by the record's eight lanes together: x its planes,
 // nx those of the NEXT request's first word (zero when the line ends in this one; more: some record of the wave has a next
-// request), p0 and lead as in sel_load_line.  -> the smallest hit among the lane's places, or CLIP_NONE.
+// request), p0 and lead as in sel_load_line.  -> the smallest hit among the lane's places, or CLIP_NONE.  In two halves, so
+// that the probe form does the first once for all its probes: what lies behind the lane's words, then the test.
 constexpr unsigned CLIP_NONE = 0xFFFFFFFFu;
-__device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL], const ClipWord nx, bool more, const ClipAdapter &ad, bool wide,
-                                                 unsigned p0, unsigned sub, int lead, int len) {
-  // the four words behind each of the lane's two: from the lanes behind it, and past lane 7 from the next word of lane 0 on
-  ClipWord n0[4], n1[4];
+struct ClipBehind {
+  ClipWord n0[4], n1[4];  // the four words behind each of the lane's two
+};
+__device__ __forceinline__ ClipBehind clip_behind(const ClipWord (&x)[SEL_UNROLL], const ClipWord nx, bool more, unsigned sub) {
+  // from the lanes behind it, and past lane 7 from the next word of lane 0 on
+  ClipBehind r;
 #pragma unroll
   for (unsigned d = 1; d <= 4; d++) {
     const unsigned src = (sub + d) & (SEL_GROUP_LANES - 1);
@@ -370,9 +375,13 @@ __device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL]
       b2.ac = __shfl(nx.ac, src, SEL_GROUP_LANES);
       b2.gt = __shfl(nx.gt, src, SEL_GROUP_LANES);
     }
-    n0[d - 1] = wrap ? b1 : b0;
-    n1[d - 1] = wrap ? b2 : b1;
+    r.n0[d - 1] = wrap ? b1 : b0;
+    r.n1[d - 1] = wrap ? b2 : b1;
   }
+  return r;
+}
+__device__ __forceinline__ unsigned clip_test(const ClipWord (&x)[SEL_UNROLL], const ClipBehind &bh, const ClipAdapter &ad, bool wide, unsigned p0,
+                                              unsigned sub, int lead, int len) {
   unsigned best = CLIP_NONE;
 #pragma unroll
   for (unsigned kk = 0; kk < SEL_UNROLL; kk++) {
@@ -380,11 +389,57 @@ __device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL]
     const int first = (int)(p0 + 16u * SEL_GROUP_LANES * k) - lead;  // the place of the eight words' first byte
     if (__all(first >= len)) continue;  // (uniform) no record of the wave has a base there
     const int place0 = first + (int)(16u * sub);
-    const unsigned hits = clip_word_hits(x[k], k ? n1 : n0, ad, wide, place0, len);
+    const unsigned hits = clip_word_hits(x[k], k ? bh.n1 : bh.n0, ad, wide, place0, len);
     if (hits) best = (unsigned)(place0 + (int)__builtin_ctz(hits));
   }
   return best;
 }
+__device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL], const ClipWord nx, bool more, const ClipAdapter &ad, bool wide,
+                                                 unsigned p0, unsigned sub, int lead, int len) {
+  const ClipBehind bh = clip_behind(x, nx, more, sub);
+  return clip_test(x, bh, ad, wide, p0, sub, lead, len);
+}
+
+// ---- adapter content (include/fqgpu.h, fqgpu_chunk_probe): the probe form's counts.  A workgroup sums in LDS, u32 -- it has
+// 256 records of at most 65535 bases, so no cell can overflow --: the chunk's bases, four counters for each of the n + 1
+// tables, and PROBE_WINDOW_ROWS rows of n + 1 cells with one more row that stands for row P when P lies beyond the window
+// (stats.hip's layout of the same problem).  A hit between the window and P goes to global memory directly: correct, slow,
+// rare.  At the end a non-zero word reaches the result as one 64-bit atomic.
+constexpr unsigned PROBE_WINDOW_ROWS = 320;
+constexpr unsigned PROBE_TABLE_HEAD = 8, PROBE_HEAD = 8;
+constexpr unsigned PROBE_LDS_WORDS = 1 + 4 * (FQGPU_PROBES_MAX + 1) + (PROBE_WINDOW_ROWS + 1) * (FQGPU_PROBES_MAX + 1);
+constexpr unsigned PW_WITH = 0, PW_BEHIND = 1, PW_WHOLE = 2, PW_EMPTIED = 3;
+// the result's word of table t: its counter c / its row
+__device__ __forceinline__ unsigned long long probe_word(unsigned P, unsigned t, unsigned c) {
+  return PROBE_HEAD + (unsigned long long)t * (PROBE_TABLE_HEAD + P + 1ull) + c;
+}
+// a read of length len that table t (probe t of m bases; t == n: "any", m 0) cuts at a < len
+__device__ __forceinline__ void probe_count(uint32_t *lds, unsigned long long *__restrict__ out, unsigned n, unsigned P, unsigned t, unsigned a,
+                                            unsigned len, unsigned m) {
+  const unsigned row = min(a, P);
+  if (row < PROBE_WINDOW_ROWS || row == P) atomicAdd(&lds[1 + 4 * (n + 1) + min(row, PROBE_WINDOW_ROWS) * (n + 1) + t], 1u);
+  else atomicAdd(&out[probe_word(P, t, PROBE_TABLE_HEAD + row)], 1ull);
+  atomicAdd(&lds[1 + 4 * t + PW_WITH], 1u);
+  atomicAdd(&lds[1 + 4 * t + PW_BEHIND], len - a);
+  if (m && a + m <= len) atomicAdd(&lds[1 + 4 * t + PW_WHOLE], 1u);
+  if (a == 0) atomicAdd(&lds[1 + 4 * t + PW_EMPTIED], 1u);
+}
+
+// what the two forms of k_adapter_find take: one adapter and the records' clip places / a probe set as the search takes it,
+// the rows, the result tables and the records' places (nullptr: not wanted)
+struct FindOne {
+  unsigned long long plane_a, plane_c, plane_g, plane_t;
+  unsigned m, min_overlap, max_err_pct;
+  uint16_t *clip;
+};
+struct FindMany {
+  ClipAdapter ad[FQGPU_PROBES_MAX];
+  unsigned n, P;
+  unsigned long long *out;
+  uint16_t *places;
+};
+template <bool PROBE> struct FindArgs { using type = FindOne; };
+template <> struct FindArgs<true> { using type = FindMany; };
 
 // clip[r] = the clip place of record r (include/fqgpu.h, step 0): the smallest place at which the adapter hits, or the
 // read's length.  The judge's access pattern -- a wave takes 64 records with one table load, eight lanes read a record's
@@ -393,13 +448,17 @@ __device__ __forceinline__ unsigned clip_request(const ClipWord (&x)[SEL_UNROLL]
 // behind its word from its neighbours' planes by shuffles.  The line is judged over all its bytes on the way (ACGTN), so the
 // judge behind this kernel does not read it again for that.  A read longer than one request walks the requests forwards with
 // the next request's planes in hand: a correctness path.
+// PROBE (fqgpu_chunk_probe) is the same search with many adapters: a request's planes and what lies behind the lane's words
+// are built once, and a uniform loop over the probes -- their planes and limits scalar loads from the kernel's arguments,
+// `wide` by the probe -- tests them.  A probe's first hit in a record is counted where it is found, by the first of the
+// record's eight lanes (probe_count), and its place stored when places are asked for; `found` keeps a bit per probe so that
+// a later request of a long read does not count it again.  There is no verdict to hand on, so a record outside the chunk
+// or without symbols is refused here.  Without PROBE nothing of this is compiled: no loop, no LDS.
+template <bool PROBE>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
-               unsigned long long plane_a, unsigned long long plane_c, unsigned long long plane_g, unsigned long long plane_t,
-               unsigned m, unsigned min_overlap, unsigned max_err_pct, uint16_t *__restrict__ clip, SelectResult *__restrict__ res) {
+               const typename FindArgs<PROBE>::type arg, SelectResult *__restrict__ res) {
   const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
-  const ClipAdapter ad = {plane_a, plane_c, plane_g, plane_t, m, min_overlap, 100u - max_err_pct};
-  const bool wide = m > 32u;
   const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
   const unsigned long long r = r0 + lane;
   const bool have = r < n_recs;
@@ -429,51 +488,127 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
     }
   };
   unsigned my_clip = read_len;
-  bool my_bad = false;
+  bool my_bad = PROBE && have && !ok;
   Stage cur, nxt;
   fetch(cur, group);
+  if constexpr (PROBE) {
+    __shared__ uint32_t lds[PROBE_LDS_WORDS];
+    const unsigned n = arg.n, P = arg.P, used = 1 + (4 + PROBE_WINDOW_ROWS + 1) * (n + 1);
+    for (unsigned i = threadIdx.x; i < used; i += SEL_THREADS) lds[i] = 0;
+    __syncthreads();
 #pragma unroll 1
-  for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
-    if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
-    unsigned steps = 1;
-    if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
-      steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
+    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
+      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+      unsigned steps = 1;
+      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
+        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
 #pragma unroll
-      for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-      steps = fq_uniform(steps);
-    }
-    const int lead = (int)(cur.off & 15u);
-    bool bad = false;
-    ClipWord x[SEL_UNROLL];
-    planes(x, cur.s, cur, 0, bad);
-    unsigned best = CLIP_NONE;
-    for (unsigned s = 0; s < steps; s++) {
-      ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
-      if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
-        uint4 v[SEL_UNROLL];
-        sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
-        planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
+        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+        steps = fq_uniform(steps);
       }
-      best = min(best, clip_request(x, y[0], s + 1 < steps, ad, wide, s * SEL_STEP_BYTES, sub, lead, (int)cur.len));
+      const int lead = (int)(cur.off & 15u);
+      const unsigned long long rec = r0 + SEL_ROUND_RECORDS * k + group;  // the record of this lane's group
+      bool bad = false;
+      ClipWord x[SEL_UNROLL];
+      planes(x, cur.s, cur, 0, bad);
+      unsigned found = 0, any = CLIP_NONE;  // (the same in a record's eight lanes)
+      for (unsigned s = 0; s < steps; s++) {
+        ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
+        if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
+          uint4 v[SEL_UNROLL];
+          sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
+          planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
+        }
+        const ClipBehind bh = clip_behind(x, y[0], s + 1 < steps, sub);
+#pragma unroll 1
+        for (unsigned p = 0; p < n; p++) {  // (uniform)
+          const ClipAdapter ad = arg.ad[p];
+          unsigned got = clip_test(x, bh, ad, ad.m > 32u, s * SEL_STEP_BYTES, sub, lead, (int)cur.len);
 #pragma unroll
-      for (unsigned i = 0; i < SEL_UNROLL; i++) x[i] = y[i];
-    }
-    // over the record's eight lanes: the smallest hit, and "a byte that cannot be judged" in the top bit
-    unsigned got = min(best, cur.len) | (bad ? 0x80000000u : 0u);
+          for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) got = min(got, (unsigned)__shfl_xor(got, d));
+          if (got != CLIP_NONE && !(found >> p & 1u)) {  // the probe's first hit in this record
+            found |= 1u << p;
+            any = min(any, got);
+            if (sub == 0) probe_count(lds, arg.out, n, P, p, got, cur.len, ad.m);
+            if (sub == 1 && arg.places) arg.places[rec * n + p] = (uint16_t)got;
+          }
+        }
 #pragma unroll
-    for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
-      const unsigned o = __shfl_xor(got, d);
-      got = min(got & 0x7FFFFFFFu, o & 0x7FFFFFFFu) | ((got | o) & 0x80000000u);
+        for (unsigned i = 0; i < SEL_UNROLL; i++) x[i] = y[i];
+      }
+      if (cur.len) {  // (a record of this chunk)
+        if (any != CLIP_NONE && sub == 0) probe_count(lds, arg.out, n, P, n, any, cur.len, 0u);
+        if (arg.places)  // the probes without a hit: lane j of the record takes the probes j, j + 8
+          for (unsigned p = sub; p < n; p += SEL_GROUP_LANES)
+            if (!(found >> p & 1u)) arg.places[rec * n + p] = (uint16_t)cur.len;
+      }
+      if (__any(bad)) my_bad = true;  // (one flag for the chunk: whose byte it was does not matter)
+      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
     }
-    // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
-    const unsigned mine_got = __shfl(got, (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES);
-    if (lane / SEL_ROUND_RECORDS == k) {
-      my_clip = mine_got & 0x7FFFFFFFu;
-      my_bad = mine_got >> 31;
+    unsigned bases = read_len;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) bases += __shfl_xor(bases, d);
+    if (lane == 0 && bases) atomicAdd(&lds[0], bases);
+    __syncthreads();
+    // a word of the workgroup's sums -> its word of the result
+    for (unsigned i = threadIdx.x; i < used; i += SEL_THREADS) {
+      const unsigned v = lds[i];
+      if (!v) continue;
+      unsigned long long at = 1;  // n_bases
+      if (i >= 1 + 4 * (n + 1)) {
+        const unsigned j = i - (1 + 4 * (n + 1)), place = j / (n + 1), t = j % (n + 1);
+        at = probe_word(P, t, PROBE_TABLE_HEAD + (place < PROBE_WINDOW_ROWS ? place : P));
+      } else if (i >= 1) {
+        at = probe_word(P, (i - 1) / 4, (i - 1) % 4);
+      }
+      atomicAdd(&arg.out[at], (unsigned long long)v);
     }
-    if (k + 1 < SEL_GROUP_LANES) cur = nxt;
+  } else {
+    const ClipAdapter ad = {arg.plane_a, arg.plane_c, arg.plane_g, arg.plane_t, arg.m, arg.min_overlap, 100u - arg.max_err_pct};
+    const bool wide = arg.m > 32u;
+#pragma unroll 1
+    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
+      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
+      unsigned steps = 1;
+      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
+        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+        steps = fq_uniform(steps);
+      }
+      const int lead = (int)(cur.off & 15u);
+      bool bad = false;
+      ClipWord x[SEL_UNROLL];
+      planes(x, cur.s, cur, 0, bad);
+      unsigned best = CLIP_NONE;
+      for (unsigned s = 0; s < steps; s++) {
+        ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
+        if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
+          uint4 v[SEL_UNROLL];
+          sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
+          planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
+        }
+        best = min(best, clip_request(x, y[0], s + 1 < steps, ad, wide, s * SEL_STEP_BYTES, sub, lead, (int)cur.len));
+#pragma unroll
+        for (unsigned i = 0; i < SEL_UNROLL; i++) x[i] = y[i];
+      }
+      // over the record's eight lanes: the smallest hit, and "a byte that cannot be judged" in the top bit
+      unsigned got = min(best, cur.len) | (bad ? 0x80000000u : 0u);
+#pragma unroll
+      for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+        const unsigned o = __shfl_xor(got, d);
+        got = min(got & 0x7FFFFFFFu, o & 0x7FFFFFFFu) | ((got | o) & 0x80000000u);
+      }
+      // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
+      const unsigned mine_got = __shfl(got, (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES);
+      if (lane / SEL_ROUND_RECORDS == k) {
+        my_clip = mine_got & 0x7FFFFFFFu;
+        my_bad = mine_got >> 31;
+      }
+      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
+    }
+    if (have) arg.clip[r] = (uint16_t)my_clip;
   }
-  if (have) clip[r] = (uint16_t)my_clip;
   if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
 }
 
@@ -1212,7 +1347,7 @@ k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__rest
 }  // namespace
 
 void SelectScratch::release() {
-  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &places, &keep, &koff, &dst, &res, &scan_tmp}) b->release();
+  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &places, &keep, &koff, &dst, &res, &scan_tmp, &probe_out, &probe_places}) b->release();
   if (host) (void)hipHostFree(host);
   host = nullptr;
 }
@@ -1252,8 +1387,9 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   if (a) {  // the adapter's bit planes: bit j of a plane is set iff A[j] is that base
     unsigned long long plane[4] = {0, 0, 0, 0};
     for (unsigned j = 0; j < a->len; j++) plane[a->seq[j] == 'A' ? 0 : a->seq[j] == 'C' ? 1 : a->seq[j] == 'G' ? 2 : 3] |= 1ull << j;
-    hipLaunchKernelGGL(k_adapter_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, plane[0],
-                       plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, ss.clip.as<uint16_t>(), ss.res.as<SelectResult>());
+    const FindOne one = {plane[0], plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, ss.clip.as<uint16_t>()};
+    hipLaunchKernelGGL(k_adapter_find<false>, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, one,
+                       ss.res.as<SelectResult>());
     FQ_HIP(hipGetLastError());
   }
   if (x) {
@@ -1302,5 +1438,61 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   FQ_HIP(hipGetLastError());
   FQ_HIP(hipMemcpyAsync(out, ss.dst.p, total, hipMemcpyDeviceToHost, st));
   FQ_HIP(hipStreamSynchronize(st));
+  return FQGPU_OK;
+}
+
+// Adapter content of the chunk raw_dev[0, raw_len) with the record table recs_dev, on st, waited for: out[0,
+// fqgpu_probe_words(p->n, P)) and -- places_out != nullptr -- p->n places per record.  One kernel, k_adapter_find's probe
+// form, and one wait.  FQGPU_E_ARG with out and places_out zeroed: a sequence byte outside ACGTN, a record that is not inside
+// the chunk, has no symbol or more than a readlen_t counts.
+int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
+                   const fqgpu_probes *p, unsigned P, uint64_t *out, uint16_t *places_out) {
+  const unsigned n = p->n;
+  const size_t words = fqgpu_probe_words(n, P);
+  if (!words || n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  for (size_t i = 0; i < words; i++) out[i] = 0;
+  SelectScratch &ss = ctx->select;
+  const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS, places_bytes = n_recs * n * sizeof(uint16_t);
+  int rc;
+  if ((rc = ss.probe_out.reserve(words * 8)) || (places_out && n_recs && (rc = ss.probe_places.reserve(places_bytes))) ||
+      (rc = ss.res.reserve(sizeof(SelectResult))))
+    return rc;
+  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
+  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
+  FindMany many = {};
+  for (unsigned k = 0; k < n; k++) {  // the probes' bit planes: bit j of a plane is set iff A[j] is that base
+    const fqgpu_adapter &a = p->probe[k];
+    ClipAdapter &ad = many.ad[k];
+    for (unsigned j = 0; j < a.len; j++) (a.seq[j] == 'A' ? ad.a : a.seq[j] == 'C' ? ad.c : a.seq[j] == 'G' ? ad.g : ad.t) |= 1ull << j;
+    ad.m = a.len;
+    ad.min_overlap = a.min_overlap;
+    ad.keep_pct = 100u - a.max_err_pct;
+  }
+  many.n = n;
+  many.P = P;
+  many.out = ss.probe_out.as<unsigned long long>();
+  many.places = places_out && n_recs ? ss.probe_places.as<uint16_t>() : nullptr;
+  FQ_HIP(hipMemsetAsync(ss.probe_out.p, 0, words * 8, st));
+  FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
+  if (n_recs) {
+    fq_timer_span_begin(ctx, "probe", st);
+    hipLaunchKernelGGL(k_adapter_find<true>, dim3((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64))), dim3(SEL_THREADS), 0, st,
+                       raw_dev, (unsigned long long)raw_len, recs_dev, (unsigned)n_recs, many, ss.res.as<SelectResult>());
+    fq_timer_span_end(ctx, st);
+    FQ_HIP(hipGetLastError());
+  }
+  FQ_HIP(hipMemcpyAsync(ss.host, ss.res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipMemcpyAsync(out, ss.probe_out.p, words * 8, hipMemcpyDeviceToHost, st));
+  if (many.places) FQ_HIP(hipMemcpyAsync(places_out, ss.probe_places.p, places_bytes, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  if (res.bad) {
+    for (size_t i = 0; i < words; i++) out[i] = 0;
+    if (many.places) memset(places_out, 0, places_bytes);
+    return FQGPU_E_ARG;
+  }
+  out[0] = n_recs;
+  out[2] = n;
+  out[3] = P;
+  out[4] = fq_probes_fingerprint(p);
   return FQGPU_OK;
 }

@@ -306,12 +306,35 @@ public:
   }
   [[nodiscard]] const std::vector<uint64_t> &stats() const { return stats_; }
 
+  /** Extension: every chunk is also searched for the probes' adapters where it lies on the device (fqgpu_chunk_probe,
+   *  `positions` rows; taken where the summary is taken) and the result added to probes(), the adapter content of all its
+   *  chunks so far (fqgpu_probe_merge).  nullptr: off, not one call more. */
+  void setProbes(const fqgpu_probes *probes, unsigned positions) {
+    probes_on_ = probes != nullptr;
+    probes_.clear();
+    probes_chunk_.clear();
+    if (!probes) return;
+    if (fqgpu_probes_check(probes) != FQGPU_OK) throw std::invalid_argument("setProbes: a probe set fqgpu_probes_check refuses");
+    probe_set_ = *probes;
+    probe_positions_ = positions;
+    probes_.assign(fqgpu_probe_words(probes->n, positions), 0);
+    probes_chunk_.assign(probes_.size(), 0);
+    if (probes_.empty()) throw std::invalid_argument("setProbes: positions must be 1 .. 65535");
+  }
+  /** all zeros while no chunk has been taken: fqgpu_probe_merge's empty result */
+  [[nodiscard]] const std::vector<uint64_t> &probes() const { return probes_; }
+
 protected:
-  /** the summary of the chunk on the handle, into stats() */
+  /** the summary of the chunk on the handle, into stats(), and its adapter content, into probes() */
   void takeStats(const char *what) {
-    if (!stats_positions_) return;
-    fqgpuCheck(fqgpu_chunk_stats(ctx_, stats_positions_, stats_chunk_.data(), stats_chunk_.size()), what);
-    fqgpuCheck(fqgpu_stats_merge(stats_.data(), stats_.size(), stats_chunk_.data(), stats_chunk_.size()), what);
+    if (stats_positions_) {
+      fqgpuCheck(fqgpu_chunk_stats(ctx_, stats_positions_, stats_chunk_.data(), stats_chunk_.size()), what);
+      fqgpuCheck(fqgpu_stats_merge(stats_.data(), stats_.size(), stats_chunk_.data(), stats_chunk_.size()), what);
+    }
+    if (probes_on_) {
+      fqgpuCheck(fqgpu_chunk_probe(ctx_, &probe_set_, probe_positions_, probes_chunk_.data(), probes_chunk_.size(), nullptr), what);
+      fqgpuCheck(fqgpu_probe_merge(probes_.data(), probes_.size(), probes_chunk_.data(), probes_chunk_.size()), what);
+    }
   }
   explicit Workspace(const DatasetMeta *meta, int device)
       : meta_(meta), fmt_(meta->header_fmt), first_header_fields_(headers::fromHeader(meta->first_header, fmt_)) {
@@ -335,6 +358,10 @@ protected:
 private:
   unsigned stats_positions_ = 0;
   std::vector<uint64_t> stats_, stats_chunk_;
+  bool probes_on_ = false;
+  fqgpu_probes probe_set_ = {};
+  unsigned probe_positions_ = 0;
+  std::vector<uint64_t> probes_, probes_chunk_;
 };
 
 class CompressionWorkspace : public Workspace {

@@ -663,6 +663,51 @@ int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_ada
                           const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
                           uint32_t *win_out, uint16_t *places_out);
 
+/* ---- Extension (nothing in the reference): ADAPTER CONTENT -- which 3' adapters the reads of a chunk hold, in how many reads
+ * and where, counted where the chunk lies already -- in HBM.  FastQC's "Adapter Content" module, and the question in front
+ * of fqgpu_chunk_clip: which sequence to clip, and what that would cut.  A probe set is n probes, 1 <= n <=
+ * FQGPU_PROBES_MAX, each an fqgpu_adapter with its own min_overlap and max_err_pct; P = `positions`, 1 .. 65535, is the
+ * number of rows.  For a read of length L, a_k is the clip place of step 0 of fqgpu_chunk_clip for probe k alone (L when
+ * there is no hit) and a = min over k of a_k: for every probe the pass reports exactly what a clip with that adapter would
+ * do.  Nothing else is applied -- no trim, no filter.  Integer arithmetic throughout; the result is a pure function of the
+ * chunk's records and adds over chunks.
+ *   out  fqgpu_probe_words(n, P) = 8 + (n + 1) (8 + P + 1) uint64_t:
+ *        head   0 n_records | 1 n_bases | 2 n_probes | 3 positions | 4 the probe set's fingerprint: zlib's CRC-32 of the
+ *               80 n bytes of probe[0 .. n) | 5 .. 7 zero
+ *        then n + 1 tables: table k for probe k, table n for "any", which uses a.  A table is 8 words and P + 1 rows:
+ *               0 reads_with (a_k < L) | 1 bases_behind (the sum of L - a_k) | 2 reads_whole (a_k + m_k <= L, m_k probe k's
+ *               length: the hit shows the whole probe; zero in the "any" table) | 3 reads_emptied (a_k == 0) | 4 .. 7 zero |
+ *               row i: the reads with a_k < L and min(a_k, P) == i -- the rows sum to word 0
+ *   places_out   NULL, or n uint16_t per record: places_out[r * n + k] = a_k of record r
+ * Only the sequence lines are read; they are judged over all their bytes (a byte outside ACGTN: FQGPU_E_ARG), the quality
+ * lines are not looked at.  A record outside the chunk, or of length 0: FQGPU_E_ARG.  Every FQGPU_E_ARG zeroes `out`, and
+ * where the chunk itself is refused places_out as well.  Counts of rows up to 319 (and of row P) are summed on the chip;
+ * rows between 320 and P are added in global memory one by one -- correct, slow, and rare with reads of some hundred bases.
+ *   fqgpu_probe_words    host only: the size of a result; 0 for n outside 1 .. 16 or positions outside 1 .. 65535
+ *   fqgpu_probes_check   host only: FQGPU_OK iff n is in 1 .. 16, reserved is zero, every probe[k < n] passes
+ *                        fqgpu_adapter_check and every byte of probe[k >= n] is zero.  Equal probes are allowed
+ *   fqgpu_chunk_probe    the chunk on the handle's staging block, in exactly the states in which fqgpu_chunk_stats is valid,
+ *                        on the same stream; it leaves the chunk as it is -- digest, summary and any selection give the same
+ *                        result before it and after it -- and is waited for before it returns
+ *   fqgpu_dblock_probe   waits for the block's last operation as fqgpu_dblock_stats does
+ *   fqgpu_probe_merge    host only: dst += src.  Head words 2, 3 and 4 must be equal and both lengths fqgpu_probe_words of
+ *                        them, else FQGPU_E_ARG; a dst whose n_records is 0 is empty (a dst of all zeros counts as empty)
+ *                        and becomes a copy of src: fqgpu_stats_merge's rule
+ * cap_words below the size needed: FQGPU_E_OVERFLOW, nothing is written.  A probe set its check refuses, bad positions or a
+ * NULL where data is expected: FQGPU_E_ARG.  Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any
+ * argument is looked at; the three host helpers work. */
+#define FQGPU_PROBES_MAX 16
+typedef struct {
+  uint32_t n, reserved[3];                /* 1 .. 16 | zero */
+  fqgpu_adapter probe[FQGPU_PROBES_MAX];  /* probe[k >= n]: all bytes zero */
+} fqgpu_probes;
+size_t fqgpu_probe_words(unsigned n_probes, unsigned positions);
+int fqgpu_probes_check(const fqgpu_probes *p);
+int fqgpu_chunk_probe(fqgpu_ctx *ctx, const fqgpu_probes *p, unsigned positions, uint64_t *out, size_t cap_words, uint16_t *places_out);
+int fqgpu_dblock_probe(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_probes *p, unsigned positions, uint64_t *out, size_t cap_words,
+                       uint16_t *places_out);
+int fqgpu_probe_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

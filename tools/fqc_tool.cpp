@@ -74,12 +74,26 @@
 //              (extension: the same report for the input, taken beside the encode; the archive is what it is without the
 //               option, and `s` on it gives the same bytes.  --stats with d, x or t, and --positions without a report to
 //               write, are usage errors)
+//   fqc_tool s <in.fqc> <report.tsv> ... --adapters LIST [--adapter-overlap N] [--adapter-err PCT]
+//   fqc_tool c <in.fastq> <out.fqc> ... --stats <report.tsv> --adapters LIST [--adapter-overlap N] [--adapter-err PCT]
+//              (extension: ADAPTER CONTENT -- the report also says, for each of up to 16 probe adapters, in how many reads
+//               `d --adapter` with that sequence would find it, how many bases it would cut, in how many reads the whole probe
+//               shows, how many it would empty, and the reads by the place of the cut (--positions rows, as the summary); the
+//               same for "any", the leftmost cut of all probes.  Searched on the device beside the summary, all probes in one
+//               pass.  LIST is comma-separated; an item is `all` (every built-in), a built-in name -- truseq, truseq-r1,
+//               truseq-r2, nextera, smallrna-3p, smallrna-5p, solid, poly-a, poly-g --, NAME=SEQ or a bare SEQ, which is its own
+//               name.  N (default 5, capped at a probe's length) and PCT (default 10) hold for every probe.  The lines follow
+//               the summary's: "probe", number, name, sequence, N, PCT, reads_with, bases_behind, reads_whole, reads_emptied;
+//               the same for "any"; "probepos", probe, row, count for every non-zero cell.  --adapters with d, x or t or
+//               without a report to write, an item that is neither a built-in name nor a valid adapter, more than 16 probes,
+//               and --adapter with s or c are usage errors.  Without --adapters every output is what it was)
 // (fqcomp28 c --i1 in.fastq -o out.fqc -t N / fqcomp28 d -i out.fqc --o1 out.fastq, src/app.cpp:29-76.)
 // Prints one JSON line with sizes, seconds and blocks per worker; d and x also say how many blocks were decoded from a decode
 // index ("index": "used") or were given one ("built"), and its bytes; "sums" / "verified" / "crc32": what became of the chunk
 // sums file, the blocks whose digest was compared and held, the whole file's CRC-32; with --fasta also "form": "fasta" and the
 // bytes read of the archive; with a report "stats": its path, "bases" and "mean_quality" (total Phred / bases, the one
-// number that is no integer and in no report); with a filter "filter": what was read, what was kept and what each
+// number that is no integer and in no report), with --adapters also "adapters", the number of probes, and "reads_with_any";
+// with a filter "filter": what was read, what was kept and what each
 // criterion dropped ("records" / "raw_bytes" of the line are then what was written); with a trim "trim": the same and the
 // reads trimmed, the bases cut from either end and the reads emptied, and with an adapter -- then alone -- the reads in which it
 // was found and the bases it took, and with a poly or window option -- then alone -- the reads with a poly tail, the bases it
@@ -107,7 +121,8 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
-                         "       fqc_tool s <in.fqc> <report.tsv> [-t N] [-d 0,1,..] [--positions P]\n");
+                         "       fqc_tool s <in.fqc> <report.tsv> [-t N] [-d 0,1,..] [--positions P]\n"
+                         "       fqc_tool s|c ... --adapters all|NAME|NAME=SEQ|SEQ,... [--adapter-overlap N] [--adapter-err PCT]   (c: with --stats)\n");
     return 2;
   }
   Settings set;
@@ -122,6 +137,8 @@ int main(int argc, char **argv) {
   bool trimmed = false;
   fqgpu_adapter adapter = {{0}, 0, 5, 10, 0};
   bool clipped = false, adapter_opt = false;
+  std::string adapters_list;
+  bool adapters_opt = false;
   fqgpu_tail tail = {0, 0, 0, 0, 0, 0, {0, 0}};
   uint32_t poly_every = 8, poly_mism = 5;
   bool tailed = false, poly_opt = false;
@@ -177,6 +194,9 @@ int main(int argc, char **argv) {
       std::memset(adapter.seq, 0, sizeof adapter.seq);
       std::memcpy(adapter.seq, v.data(), std::min<std::size_t>(v.size(), FQGPU_ADAPTER_MAX));
       clipped = true;
+    } else if (a == "--adapters") {
+      adapters_list = val();
+      adapters_opt = true;
     } else if (a == "--adapter-overlap" || a == "--adapter-err") {
       const std::string v = val();
       if (!u32(v, a == "--adapter-overlap" ? adapter.min_overlap : adapter.max_err_pct)) {
@@ -256,13 +276,62 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "read trimming: expected --cut-front and --cut-tail 0 .. 65535, --trim-q5 and --trim-q3 0 .. 64, --crop 1 or more\n");
     return 2;
   }
-  if ((clipped || adapter_opt) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+  if (adapters_opt && ((argv[1][0] != 'c' && !stats_cmd) || stats_path.empty())) {  // (said before any device is touched)
+    std::fprintf(stderr, "--adapters goes with s, and with c --stats <report.tsv>: not with d, x or t, and not without a report to write\n");
+    return 2;
+  }
+  if ((clipped || (adapter_opt && !adapters_opt)) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
     std::fprintf(stderr, "adapter clipping goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
     return 2;
   }
-  if (adapter_opt && !clipped) {
-    std::fprintf(stderr, "--adapter-overlap and --adapter-err need --adapter SEQ\n");
+  if (adapter_opt && !clipped && !adapters_opt) {
+    std::fprintf(stderr, "--adapter-overlap and --adapter-err need --adapter SEQ, or --adapters LIST\n");
     return 2;
+  }
+  fqgpu_probes probes = {};
+  std::vector<std::string> probe_names;
+  if (adapters_opt) {
+    static const char *const builtin[][2] = {{"truseq", "AGATCGGAAGAGC"}, {"truseq-r1", "AGATCGGAAGAGCACACGTCTGAACTCCAGTCA"},
+                                             {"truseq-r2", "AGATCGGAAGAGCGTCGTGTAGGGAAAGAGTGT"}, {"nextera", "CTGTCTCTTATACACATCT"},
+                                             {"smallrna-3p", "TGGAATTCTCGG"}, {"smallrna-5p", "GATCGTCGGACT"}, {"solid", "CGCCTTGGCCGT"},
+                                             {"poly-a", "AAAAAAAAAAAAAAAAAAAA"}, {"poly-g", "GGGGGGGGGGGGGGGGGGGG"}};
+    // one probe more; false: it is no adapter fqgpu_adapter_check takes, or the seventeenth
+    const auto add = [&](const std::string &name, const std::string &seq) {
+      if (probes.n >= FQGPU_PROBES_MAX) {
+        std::fprintf(stderr, "--adapters %s: more than %d probes\n", adapters_list.c_str(), FQGPU_PROBES_MAX);
+        return false;
+      }
+      fqgpu_adapter p = {{0}, static_cast<uint32_t>(seq.size()), adapter.min_overlap, adapter.max_err_pct, 0};
+      std::memcpy(p.seq, seq.data(), std::min<std::size_t>(seq.size(), FQGPU_ADAPTER_MAX));
+      if (p.min_overlap > p.len) p.min_overlap = p.len;  // (N is capped at the probe's length, as d --adapter caps it)
+      if (fqgpu_adapter_check(&p) != FQGPU_OK) {
+        std::fprintf(stderr, "--adapters: %s is neither all, a built-in name nor 1 .. 64 bases ACGT (upper case); --adapter-overlap 1 or more, --adapter-err 0 .. 50\n",
+                     name.c_str());
+        return false;
+      }
+      probes.probe[probes.n++] = p;
+      probe_names.push_back(name);
+      return true;
+    };
+    for (std::size_t at = 0; at <= adapters_list.size();) {
+      const std::size_t comma = std::min(adapters_list.find(',', at), adapters_list.size());
+      const std::string item = adapters_list.substr(at, comma - at);
+      at = comma + 1;
+      const std::size_t eq = item.find('=');
+      bool ok = true, known = false;
+      if (item == "all") {
+        for (const auto &b : builtin) ok = ok && add(b[0], b[1]);
+        known = true;
+      }
+      for (const auto &b : builtin)
+        if (item == b[0]) { ok = add(b[0], b[1]); known = true; }
+      if (!known) ok = eq == std::string::npos ? add(item, item) : eq != 0 && add(item.substr(0, eq), item.substr(eq + 1));
+      if (!ok) {
+        if (eq == 0) std::fprintf(stderr, "--adapters: %s has no name in front of its =\n", item.c_str());
+        return 2;
+      }
+    }
+    set.probes = probes;
   }
   if (clipped) {
     if (adapter.min_overlap > adapter.len) adapter.min_overlap = adapter.len;  // (N is capped at the adapter's length)
@@ -320,7 +389,8 @@ int main(int argc, char **argv) {
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
-    if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
+    if (!stats_path.empty() && adapters_opt) writeStatsReport(stats_path, r.stats, r.probes, probes, probe_names);
+    else if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
                 "\"seq_bytes\": %zu, \"qual_bytes\": %zu, \"misc_bytes\": %zu, \"seconds\": %.6f, \"blocks_per_worker\": [",
                 argv[1], set.n_threads, set.devices.size(), r.in.raw, r.in.n_records, comp ? r.out.n_blocks : (std::size_t)0,
@@ -339,6 +409,9 @@ int main(int argc, char **argv) {
       std::string quoted;
       for (const char ch : stats_path) { if (ch == '"' || ch == '\\') quoted += '\\'; quoted += ch; }
       std::printf(", \"stats\": \"%s\", \"bases\": %llu, \"mean_quality\": %.6f", quoted.c_str(), (unsigned long long)r.stats[1], statsMeanQuality(r.stats));
+      if (adapters_opt)
+        std::printf(", \"adapters\": %u, \"reads_with_any\": %llu", probes.n,
+                    (unsigned long long)(r.probes.empty() ? 0 : r.probes[8 + probes.n * (8 + (std::size_t)set.stats_positions + 1)]));
     }
     if (filtered) {
       const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped || tailed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
