@@ -6,7 +6,9 @@ it; the product -- fqcomp28_amd/csrc/archive.hpp -- never does).  It exists so t
     src/archive.h:10-17 and src/archive.cpp:45-55, 57-106, 108-163 -- field order, sizes, index --
     instead of against itself, and
   * BASELINE configs[4] ("decode a reference-produced archive") runs on a real `.fqc`-shaped file
-    whose seq/qual streams come from the CPU oracle (the reference binary cannot be built here).
+    whose seq/qual streams come from the CPU oracle.
+The reading is pinned to the reference's compiled Archive: tests/test_reference_pin.py::test_container parses what
+`oracle/_ref/ref_tool write-archive` writes, rewrites it byte for byte, and has the reference read what this module writes.
 
 Layout (little-endian):
   u32 n_blocks                          src/archive.cpp:45-50 (written last, at offset 0)

@@ -7,12 +7,12 @@
  * src/workspace.cpp:14-88).  It is the checker for the HIP path and the CPU
  * baseline of bench.py ("kind": "port"); nothing under fqcomp28_amd/ may call it.
  *
- * Parity status: PARITY UNPINNED against the reference itself -- the reference cannot be built here (its build fetches four
- * repositories over the network) and holds no golden byte
- * vectors for this path (every test is a round-trip).  The zstd
- * primitives are pinned against libzstd.so.1 1.4.8; the model layer is pinned
- * by the reference's own round-trip tests restated in tests/ and by the
- * surveyor's independent regression values.
+ * Parity status: pinned to the reference's compiled code.  The reference's own sources build into
+ * oracle/_ref/ref_tool against the shim of oracle/ref/ (zstd's names over fse_oracle.c), and
+ * tests/test_reference_pin.py compares tables, streams, N buffers and bounds with it byte for byte
+ * (the reference holds no golden byte vectors for this path: every test of its own is a
+ * round-trip).  Not pinned: the arithmetic of the zstd fork, for which fse_oracle.c
+ * stands, itself pinned against libzstd.so.1 1.4.8 only.
  */
 #ifndef FQC_ORACLE_H
 #define FQC_ORACLE_H

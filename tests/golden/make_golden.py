@@ -1,9 +1,10 @@
 """Regenerates tests/golden/expected.json and the first5 byte vectors from the CPU oracle.
 
-The reference cannot be built or run here; these vectors are the
-oracle's outputs on the reference's own test inputs (test/data/*.fastq, MIT, public
-SRA reads).  The seq/qual sizes and sha1[:12] were independently reproduced by the
-surveyor's scratch restatement (SURVEY.md 8(c) "Cross-session regression values").
+These vectors are the oracle's outputs on the reference's own test inputs (test/data/*.fastq,
+MIT, public SRA reads).  The reference's compiled coder (oracle/_ref/ref_tool, built from its own
+sources by `make -C oracle ref`) writes the same bytes: tests/test_reference_pin.py compares them.
+The seq/qual sizes and sha1[:12] were also reproduced by the surveyor's scratch restatement
+(SURVEY.md 8(c) "Cross-session regression values").
 Run:  python tests/golden/make_golden.py
 """
 import hashlib

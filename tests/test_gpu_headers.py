@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import ref_pin as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -102,36 +103,15 @@ def test_strings_that_change_numbers_that_wrap_fields_that_are_missing(ctx):
     2^31 (the difference wraps), a number followed by other characters (from_chars reads the digits in front),
     headers with fewer separators than the format (the rest of the fields is empty or everything), a separator as
     the first character of a field; 3 000 records: twelve workgroups, the last one ragged"""
-    rng = np.random.default_rng(11)
-    names = [b"EAS687", b"EAS688", b"EAS688", b"TIOBDUREN", b"B", b"", b"x" * 254, b"y" * 100, b"-lead"]
-    nums = [b"5", b"4", b"2147483647", b"-2147483648", b"0", b"33808546", b"-7", b"12ab", b"007", b"-0"]
-    hdrs = [b"@EAS687.1 5 length=50/1"]
-    for i in range(2999):
-        a = names[int(rng.integers(len(names)))] if rng.random() < 0.3 else hdrs[-1][1:].split(b".")[0]
-        b = nums[int(rng.integers(len(nums)))] if rng.random() < 0.5 else b"%d" % int(rng.integers(0, 2**31))
-        c = b"length" if rng.random() < 0.9 else b"len"
-        h = b"@%s.%d %s %s=%d/%d" % (a, i + 2, b, c, 50 + i % 251, 1 + i % 2)
-        if i % 97 == 0:
-            h = h[: int(rng.integers(2, len(h)))]   # cut: later fields are missing
-            if not h[-1:].isdigit():                   # (a missing numeric field would be an error: next test)
-                h = b"@q.1 2 z=3/4"
-        hdrs.append(h)
-    # cut headers whose numeric fields ended up empty cannot be coded: keep those the oracle codes
-    ok = []
-    for h in hdrs:
-        try:
-            HO.encode_headers([h], hdrs[0])
-            ok.append(h)
-        except ValueError:
-            ok.append(b"@q.1 2 z=3/4")
+    ok = R.headers_changing_wrapping_cut()   # (the list is shared with tests/test_reference_pin.py)
     raw = fastq_of(ok)
     assert_fields_equal(code_on_gpu(ctx, raw, ok[0]), ok, ok[0], lossless=False)
 
 
 def test_single_field_and_many_fields(ctx):
-    hdrs = [b"@%d" % (1000 - 3 * i) for i in range(700)]
+    hdrs = R.headers_single_field()
     assert_fields_equal(code_on_gpu(ctx, fastq_of(hdrs), hdrs[0]), hdrs, hdrs[0])
-    hdrs = [b"@" + b":".join(b"%s%d" % (b"f" if k % 3 else b"", (i * (k + 1)) % 1000) for k in range(64)) for i in range(300)]
+    hdrs = R.headers_64_fields()
     types, seps = HO.format_from_header(hdrs[0])
     assert len(types) == 64
     assert_fields_equal(code_on_gpu(ctx, fastq_of(hdrs), hdrs[0]), hdrs, hdrs[0])
@@ -140,13 +120,13 @@ def test_single_field_and_many_fields(ctx):
 def test_headers_that_cannot_be_coded_are_reported_with_their_record(ctx, F):
     """the host coder throws where the reference asserts (src/headers.cpp:20, 83, 117); the device reports the FIRST
     such record"""
-    good = [b"@r.%d x" % (i + 1) for i in range(1000)]
-    for at, bad in ((0, b"@r.x1 x"), (517, b"@r. x"), (999, b"@r.99999999999 x"), (300, b"@r.2147483648 x"), (301, b"@r.-2147483649 x"),
-                    (640, b"@r.7 " + b"z" * 255)):
+    good = R.UNCODABLE_GOOD
+    later_at, later = R.UNCODABLE_LATER
+    for at, bad in R.UNCODABLE:
         hdrs = list(good)
         hdrs[at] = bad
         if at < 900:
-            hdrs[950] = b"@r.+5 x"   # a later one must not win
+            hdrs[later_at] = later   # a later one must not win
         with pytest.raises(ValueError):
             HO.encode_headers(hdrs, good[0])
         g = code_on_gpu(ctx, fastq_of(hdrs), good[0])

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as O
+import ref_pin as R
 
 pytestmark = pytest.mark.gpu
 
@@ -265,24 +266,7 @@ def test_random_blocks_match_oracle(F, seed):
     ctx.close()
 
 
-def _rescale_tables(ft, new_log):
-    """FreqTable POD with every context renormalised to 2^new_log (largest-remainder on the old
-    normalised counts, -1 entries kept): tables a foreign writer could have produced."""
-    out = ft.copy()
-    norm = out["norm"][0]
-    logs = out["logs"][0]
-    for c in range(norm.shape[0]):
-        old = norm[c].astype(np.int64)
-        cnt = np.where(old == -1, 1, old)
-        tot = int(cnt.sum())
-        target = 1 << new_log
-        scaled = np.where(cnt > 0, np.maximum(1, cnt * target // tot), 0)
-        scaled[np.argmax(scaled)] += target - int(scaled.sum())
-        assert scaled.min() >= 0 and int(scaled.sum()) == target and scaled[np.argmax(scaled)] > 0
-        norm[c] = np.where((old == -1) & (scaled == 1), -1, scaled).astype(norm.dtype)
-        logs[c] = new_log
-    out["max_log"][0] = new_log
-    return out
+_rescale_tables = R.rescale_tables   # (shared with tests/test_reference_pin.py)
 
 
 @pytest.mark.parametrize("log", [12, 5])
