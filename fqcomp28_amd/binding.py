@@ -130,6 +130,8 @@ _PROTOS = {
     "fqgpu_ctx_reserve": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "fqgpu_ctx_set_seq_segment": (C.c_int, [C.c_void_p, C.c_uint]),
     "fqgpu_ctx_set_seq_group": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
+    "fqgpu_ctx_set_seq_handover": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
+    "fqgpu_dblock_seq_handover": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "fqgpu_dblock_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_load_streams": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -636,6 +638,12 @@ class DBlock:
         _check(lib().fqgpu_dblock_longest_chain(self.h, C.byref(a), C.byref(b)), "dblock_longest_chain")
         return a.value, b.value
 
+    def seq_handover(self):
+        """(handed over, kept): segment groups of the sequence chains of the last encode (Context.set_seq_handover)"""
+        a, b = C.c_uint(), C.c_uint()
+        _check(lib().fqgpu_dblock_seq_handover(self.h, C.byref(a), C.byref(b)), "dblock_seq_handover")
+        return a.value, b.value
+
     def qual_segment_classes(self):
         """segments of the quality chains of the last encode by class -> dict(transparent, anchored, uniform, opaque)"""
         c = (C.c_size_t * 4)()
@@ -705,6 +713,11 @@ class Context:
             q, g = seq_group if isinstance(seq_group, tuple) else (seq_group, 0)
             _check(lib().fqgpu_ctx_set_seq_group(self.h, q, g), "set_seq_group")
         _check(lib().fqgpu_ctx_set_chain_params(self.h, segment, flags), "set_chain_params")
+
+    def set_seq_handover(self, cap, prefix_segments=1):
+        """fqgpu_ctx_set_seq_handover: groups down to `cap` states behind `prefix_segments` segments leave the set walk
+        (cap 0: none does)"""
+        _check(lib().fqgpu_ctx_set_seq_handover(self.h, cap, prefix_segments), "set_seq_handover")
 
     def set_index_stride(self, symbols):
         _check(lib().fqgpu_ctx_set_index_stride(self.h, symbols), "set_index_stride")

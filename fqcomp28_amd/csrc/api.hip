@@ -325,7 +325,7 @@ static void free_lane(EncLane &l) {
   for (int s = 0; s < 2; s++) {
     EncScratch &e = l.enc[s];
     DevBuf *eb[] = {&e.slot_of, &e.keys, &e.sorted_sym, &e.out16, &e.tile_hist, &e.tile_base, &e.group_sum,
-                    &e.ctx_arrays, &e.seg_state, &e.seg_arrays, &e.seq_bdesc, &e.seq_plan, &e.seq_fbuf, &e.seq_cbuf, &e.tile_bits, &e.tile_bit_base, &e.scan_tmp, &e.tile_runs, &e.tile_sync, &e.dbg_enc16};
+                    &e.ctx_arrays, &e.seg_state, &e.seg_arrays, &e.seq_bdesc, &e.seq_plan, &e.seq_fbuf, &e.seq_cbuf, &e.seq_cand, &e.tile_bits, &e.tile_bit_base, &e.scan_tmp, &e.tile_runs, &e.tile_sync, &e.dbg_enc16};
     for (DevBuf *b : eb) b->release();
   }
   hipEvent_t evs[] = {l.ev_fork, l.ev_join};
@@ -507,6 +507,8 @@ extern "C" int fqgpu_ctx_create(int device, const void *seq_ft, const void *qual
   if (const char *e = getenv("FQGPU_SETFUNC_WGS")) ctx->setfunc_wgs = (unsigned)atoi(e);  // experiments: same bits
   if (const char *e = getenv("FQGPU_SEQ_GROUP")) ctx->seq_group = (unsigned)atoi(e);  // experiments
   if (const char *e = getenv("FQGPU_SEQ_GROUP_MIN")) ctx->seq_group_min = (unsigned)atoi(e);
+  if (const char *e = getenv("FQGPU_SEQ_CAND_CAP")) ctx->seq_cand_cap = std::min((unsigned)atoi(e), 64u);
+  if (const char *e = getenv("FQGPU_SEQ_CAND_PREFIX")) ctx->seq_cand_prefix = std::max((unsigned)atoi(e), 1u);
   if (!rc) rc = upload_tables(ctx, 0, seq_ft);
   if (!rc) rc = upload_tables(ctx, 1, qual_ft);
   if (rc) { fqgpu_ctx_destroy(ctx); return rc; }
@@ -565,6 +567,13 @@ extern "C" int fqgpu_ctx_set_seq_group(fqgpu_ctx *ctx, unsigned max_segments, un
   if (!ctx) return FQGPU_E_ARG;
   ctx->seq_group = max_segments ? max_segments : 8u;
   ctx->seq_group_min = min_groups ? min_groups : 16u;
+  return FQGPU_OK;
+}
+
+extern "C" int fqgpu_ctx_set_seq_handover(fqgpu_ctx *ctx, unsigned cap, unsigned prefix_segments) {
+  if (!ctx || cap > 64) return FQGPU_E_ARG;
+  ctx->seq_cand_cap = cap;
+  ctx->seq_cand_prefix = prefix_segments ? prefix_segments : 1u;
   return FQGPU_OK;
 }
 
@@ -850,6 +859,20 @@ extern "C" int fqgpu_dblock_longest_chain(const fqgpu_dblock *b, unsigned *seq_s
   FQ_HIP(hipMemcpy(&tmp, b->result, sizeof(tmp), hipMemcpyDeviceToHost));
   if (seq_segments) *seq_segments = tmp.s[0].refixed;
   if (qual_segments) *qual_segments = tmp.s[1].refixed;
+  return FQGPU_OK;
+}
+
+extern "C" int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed_over, unsigned *kept) {
+  if (!b) return FQGPU_E_ARG;
+  (void)hipSetDevice(b->device);
+  if (b->last_op && !b->result_pulled && b->owner) {
+    const int rc = fqgpu_sync(b->owner);
+    if (rc) return rc;
+  }
+  BlockResult tmp;
+  FQ_HIP(hipMemcpy(&tmp, b->result, sizeof(tmp), hipMemcpyDeviceToHost));
+  if (handed_over) *handed_over = tmp.seq_groups_handed;
+  if (kept) *kept = tmp.seq_groups_kept;
   return FQGPU_OK;
 }
 

@@ -63,6 +63,22 @@ constexpr unsigned SETS_MAX_CLASSES = 512;  // above this a segment keeps carryi
 constexpr unsigned SETS_MAX_GROUP = 16;     // segments a wave walks in one go, at most
 constexpr unsigned SETS_BLOCK = 1024;       // symbols per 16-byte-per-lane load; S is a multiple
 
+// Hand-over of collapsed groups (two-symbol path).  After a prefix of P segments the states a group still carries are
+// few (19-40 after 2048 symbols, fewer than 10 from 8192 on), and a 64-lane gather per step walks mostly spare lanes.  A
+// wave of k_seq_setfunc that stands at n <= cap classes behind the prefix writes them out as the group's CANDIDATES and
+// takes its next group; k_seq_candwalk walks the rest of the group with one lane per candidate (64 / W groups per wave)
+// and needs nothing but the context's table in LDS; k_seq_resolve finds a group entry's candidate through F_P.
+constexpr unsigned SEQ_CAND_MAX = 64;        // candidates of a handed-over group, at most (one wave-instruction)
+constexpr unsigned SEQ_CAND_KEPT = 0xFFFFu;  // cand0[group][0] of a group that kept its functions (no state: states are even)
+constexpr unsigned CANDW_WAVES = 8;          // waves of a k_seq_candwalk workgroup
+struct SeqHandover {
+  unsigned W;        // candidate slots per group: 16, 32 or 64 (0: nothing is handed over)
+  unsigned cap, P;   // a group is handed over with at most cap classes behind its first P segments
+  uint16_t *cand0;   // [first function of the group][W] the candidates behind the prefix, padded with the last one
+  uint16_t *cand;    // [function][W] candidate k's state behind that segment (segments P.. of a handed-over group)
+  unsigned *counts;  // groups handed over, groups kept (of the block)
+};
+
 template <unsigned MAXC_, unsigned BMW_>
 struct SetsWaveLdsT {
   static constexpr unsigned MAXC = MAXC_, BMW = BMW_;
@@ -265,9 +281,9 @@ template <bool XO>
 __device__ __forceinline__ unsigned sets_idx(unsigned v, unsigned size) { return XO ? v >> 1 : v - size; }
 
 // merge of equal states among the n classes of L.list; returns the new class count.  Skipped
-// (list untouched) when it would not lower the number of gathers per step.
+// (list untouched) when it would not lower the number of gathers per step (force: the number of classes).
 template <bool XO, class LT>
-__device__ __forceinline__ unsigned sets_merge(LT &L, unsigned n, unsigned n1, unsigned nw, unsigned size) {
+__device__ __forceinline__ unsigned sets_merge(LT &L, unsigned n, unsigned n1, unsigned nw, unsigned size, bool force = false) {
   const unsigned lane = fq_lane();
   sets_clear(L);
   for (unsigned i = lane; i < n; i += 64) {
@@ -276,7 +292,7 @@ __device__ __forceinline__ unsigned sets_merge(LT &L, unsigned n, unsigned n1, u
   }
   fq_lds_wave_sync();
   const unsigned nn = sets_count(L, nw);
-  if ((nn + 63) / 64 >= (n + 63) / 64) return n;
+  if (force ? nn >= n : (nn + 63) / 64 >= (n + 63) / 64) return n;
   unsigned st[LT::MAXC / 64];
 #pragma unroll
   for (unsigned j = 0; j < LT::MAXC / 64; j++) {
@@ -308,7 +324,8 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
               const uint32_t *__restrict__ plan, const uint32_t *__restrict__ logs,
               const uint16_t *__restrict__ next, unsigned next_stride, const uint16_t *__restrict__ pow, unsigned pow_stride,
               unsigned S, unsigned qmax, unsigned gmin,
-              unsigned rounds, unsigned fstride, uint16_t *__restrict__ fbuf, unsigned *__restrict__ work_counter, unsigned table_bytes) {
+              unsigned rounds, unsigned fstride, uint16_t *__restrict__ fbuf, unsigned *__restrict__ work_counter, unsigned table_bytes,
+              const SeqHandover H) {
   constexpr unsigned WAVES = TWO ? SETS_WAVES2 : SETS_WAVES;
   // ALL of the kernel's LDS is the dynamic block, the context's table first: next[4][size] (TWO: next2[16][size]) sits at LDS
   // address 0, so a gather's address is row + state with nothing added (with the per-wave buffers as static LDS in front of
@@ -370,6 +387,18 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
           if (jj < per && xi < size) f[xi] = level == 0 ? (uint16_t)x0[jj] : L.list[L.m[x0[jj]]];
         }
       };
+      // behind the prefix: a group down to <= cap classes leaves its candidates to k_seq_candwalk (its later functions are
+      // never written); every group's cand0[0] says which way it went
+      const bool may_hand = TWO && H.W != 0 && nblk > H.P * sub_blocks;
+      bool handed = false;
+      auto hand_over = [&]() {
+        if (level != 1) return false;
+        if (n > H.cap) n = sets_merge<true>(L, n, n1, nw, size, true);
+        if (n > H.cap) return false;
+        uint16_t *c0 = H.cand0 + (size_t)(fseg[c] + s0) * H.W;
+        if (lane < H.W) c0[lane] = L.list[min(lane, n - 1)];
+        return true;
+      };
       for (unsigned blk = 0; blk < nblk; blk++) {
         // A segment that is S times ONE symbol (a homopolymer context fed its own base) is a power of
         // that symbol's transition: T_s^S from the handle's table, one lookup per carried state instead
@@ -394,6 +423,7 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
             while (stop <= w) stop = stop == 1 ? 4 : stop == 4 ? 12 : stop == 12 ? 32 : stop * 4;  // merge points inside the segment are dropped
             if (blk + 1 < nblk) cur = gseg[(size_t)(blk + 1) * 64 + lane];
             write_function(blk / sub_blocks);
+            if (may_hand && blk + 1 == H.P * sub_blocks && (handed = hand_over())) break;
             continue;
           }
         }
@@ -453,10 +483,114 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
         }
         cur = nxt;
         if ((blk + 1) % sub_blocks == 0) write_function(blk / sub_blocks);
+        if (may_hand && blk + 1 == H.P * sub_blocks && (handed = hand_over())) break;
+      }
+      if (TWO && H.W != 0 && lane == 0) {
+        if (!handed) H.cand0[(size_t)(fseg[c] + s0) * H.W] = (uint16_t)SEQ_CAND_KEPT;
+        atomicAdd(&H.counts[handed ? 0 : 1], 1u);
       }
       unsigned nk = 0;
       if (lane == 0) nk = atomicAdd(&s_next, 1u);
       k = k0 + (unsigned)__builtin_amdgcn_readfirstlane(nk);
+    }
+  }
+}
+
+// sets_gather2 with the row pair in a vector register (every candidate slot of a wave has its own segment's rows)
+template <int HALF>
+__device__ __forceinline__ unsigned cand_gather2(unsigned rowpair, unsigned y) {
+  unsigned addr;
+  if (HALF == 0)
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD" : "=v"(addr) : "v"(rowpair), "v"(y));
+  else
+    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD" : "=v"(addr) : "v"(rowpair), "v"(y));
+  return *reinterpret_cast<fq_lds_u16 *>((uintptr_t)addr);
+}
+
+// Step A', two-symbol path: the handed-over groups of one k_seq_setfunc item.  A lane owns (group, candidate k): it starts
+// from cand0[group][k], walks segments P .. Q-1 of its group two symbols per gather and stores its state at every segment
+// boundary.  64 / W groups share a wave (fixed slots of W lanes; the slots behind a group's n candidates shadow the last
+// one, cand0 is padded that way).  Every walked segment is a full S: the chain's last segment belongs to no group.
+// LDS: the context's two-symbol table at address 0 and nothing else (64 KB at log 11), so a K3 or K6 workgroup of another
+// lane fits beside it.  W lanes of a slot hold 16 W symbols of THEIR segment; the rows of a step are read from the slot's
+// own lanes (v_readlane per slot, one v_cndmask per further slot) and are off the add -> ds_read_u16 -> wait chain.
+template <unsigned W>
+__global__ void __launch_bounds__(CANDW_WAVES * 64)
+k_seq_candwalk(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict__ arrays, const uint32_t *__restrict__ plan,
+               const uint32_t *__restrict__ logs, const uint16_t *__restrict__ next2, unsigned next_stride, unsigned S,
+               unsigned qmax, unsigned gmin, unsigned rounds, const SeqHandover H) {
+  static_assert(W == 16 || W == 32 || W == 64, "slots of a wave");
+  constexpr unsigned GPW = 64 / W;  // groups per wave
+  constexpr unsigned B = SeqModel::B;
+  extern __shared__ uint32_t lds[];
+  const uint32_t *fitem = plan, *fseg = plan + (B + 1);
+  const unsigned item = blockIdx.x;
+  if (item >= fitem[B]) return;  // the grid is an upper bound
+  const unsigned c = seq_item_ctx(fitem, item);
+  const unsigned log = logs[c], size = 1u << log;
+  const unsigned nf = fseg[c + 1] - fseg[c], Q = seq_group_of(nf, qmax, gmin), nl = (nf + Q - 1) / Q;
+  const unsigned k0 = (item - fitem[c]) * (SETS_WAVES2 * rounds), k_end = min(k0 + SETS_WAVES2 * rounds, nl);
+  auto is_handed = [&](unsigned g) { return min(Q, nf - g * Q) > H.P && H.cand0[(size_t)(fseg[c] + g * Q) * W] != SEQ_CAND_KEPT; };
+  // (no static LDS, no __syncthreads_or: the table must sit at LDS address 0; the vote goes through its first word)
+  if (threadIdx.x == 0) lds[0] = 0;
+  __syncthreads();
+  for (unsigned g = k0 + threadIdx.x; g < k_end; g += CANDW_WAVES * 64)
+    if (is_handed(g)) lds[0] = 1;
+  __syncthreads();
+  const bool any = lds[0] != 0;
+  __syncthreads();
+  if (!any) return;  // (uniform) the item kept all its groups: no table to load
+  {
+    const uint4 *src = reinterpret_cast<const uint4 *>(next2 + (size_t)c * next_stride);
+    uint4 *dst = reinterpret_cast<uint4 *>(lds);
+    for (unsigned e = threadIdx.x; e < 2 * size; e += CANDW_WAVES * 64) dst[e] = src[e];
+  }
+  __syncthreads();
+  const unsigned wave = threadIdx.x >> 6, lane = fq_lane(), slot = lane / W, kk = lane % W;
+  const unsigned chunks = S / (16 * W);  // 16-byte-per-lane loads of a slot per segment (S is a multiple of 1024)
+  const uint8_t *run = sorted_sym + arrays[B + c];
+  for (unsigned ws = wave; k0 + ws * GPW < k_end; ws += CANDW_WAVES) {
+    unsigned g = k0 + ws * GPW + slot;
+    const bool act = g < k_end && is_handed(g);
+    const unsigned long long mask = __ballot(act);
+    if (mask == 0ull) continue;  // (wave-uniform)
+    // a slot without a handed-over group walks along with the wave's first one and stores nothing
+    const unsigned g_first = (unsigned)__builtin_amdgcn_readlane(g, (unsigned)__builtin_amdgcn_readfirstlane((unsigned)__ffsll((long long)mask) - 1u));
+    if (!act) g = g_first;
+    const unsigned s0 = g * Q, nseg = min(Q, nf - s0);
+    unsigned seg_max = 0;  // (wave-uniform) the longest group of the wave; a shorter one repeats its last segment, unstored
+#pragma unroll
+    for (unsigned t = 0; t < GPW; t++) seg_max = max(seg_max, (unsigned)__builtin_amdgcn_readlane(nseg, t * W));
+    const size_t f0 = (size_t)fseg[c] + s0;
+    unsigned y = H.cand0[f0 * W + kk];
+    auto chunk_at = [&](unsigned j, unsigned ch) {
+      return reinterpret_cast<const uint4 *>(run + (size_t)(s0 + min(j, nseg - 1)) * S)[ch * W + kk];
+    };
+    uint4 cur = chunk_at(H.P, 0);
+    for (unsigned j = H.P; j < seg_max; j++) {
+      for (unsigned ch = 0; ch < chunks; ch++) {
+        const bool more = ch + 1 < chunks;
+        const uint4 nxt = more ? chunk_at(j, ch + 1) : j + 1 < seg_max ? chunk_at(j + 1, 0) : cur;  // lands while cur is walked
+        const uint4 rows = sets_pack_rows(cur, log);
+        for (unsigned gi = 0; gi < W; gi++) {
+          unsigned r[4] = {(unsigned)__builtin_amdgcn_readlane(rows.x, gi), (unsigned)__builtin_amdgcn_readlane(rows.y, gi),
+                           (unsigned)__builtin_amdgcn_readlane(rows.z, gi), (unsigned)__builtin_amdgcn_readlane(rows.w, gi)};
+#pragma unroll
+          for (unsigned t = 1; t < GPW; t++) {
+            const unsigned o[4] = {(unsigned)__builtin_amdgcn_readlane(rows.x, t * W + gi), (unsigned)__builtin_amdgcn_readlane(rows.y, t * W + gi),
+                                   (unsigned)__builtin_amdgcn_readlane(rows.z, t * W + gi), (unsigned)__builtin_amdgcn_readlane(rows.w, t * W + gi)};
+#pragma unroll
+            for (int i = 0; i < 4; i++) r[i] = slot == t ? o[i] : r[i];
+          }
+#pragma unroll
+          for (int i = 0; i < 4; i++) {
+            if constexpr (GPW == 1) { y = sets_gather2<0>(r[i], y); y = sets_gather2<1>(r[i], y); }
+            else { y = cand_gather2<0>(r[i], y); y = cand_gather2<1>(r[i], y); }
+          }
+        }
+        cur = nxt;
+      }
+      if (act && j < nseg) H.cand[(f0 + j) * W + kk] = (uint16_t)y;
     }
   }
 }
@@ -469,16 +603,57 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
 //  compose  one wave per item: the item's composed function for every possible entry state
 //  resolve  one thread per context: item by item
 //  expand   one thread per item: group by group inside the item
+// The state behind segment j of a group, for the group's entry state e, through ONE set of helpers: a group that kept
+// its functions reads F_j[e] from fbuf; a handed-over one has x = F_P[e] (the state behind the prefix) in fbuf, finds the
+// candidate k with cand0[group][k] == x (at most W u16 entries, 16 bytes per load; duplicates are harmless) and reads
+// cand[j][k].  fg: index of the group's first function.  The HEAD of the group's candidate row (its first 16 bytes) says
+// whether the group was handed over and holds the first eight candidates; it depends on nothing but fg, so it is asked for
+// together with the group's functions and a kept group still costs ONE round of loads.
+constexpr unsigned SEQ_SLOT_KEPT = 0xFFFFFFFFu;
+__device__ __forceinline__ uint4 seq_group_head(const SeqHandover &H, size_t fg) {
+  return H.W != 0 ? *reinterpret_cast<const uint4 *>(H.cand0 + fg * H.W) : make_uint4(SEQ_CAND_KEPT, 0u, 0u, 0u);
+}
+__device__ __forceinline__ bool seq_group_handed(const uint4 head) { return (head.x & 0xFFFFu) != SEQ_CAND_KEPT; }
+__device__ __forceinline__ unsigned seq_group_slot(const SeqHandover &H, size_t fg, const uint4 head, unsigned x) {
+  if (!seq_group_handed(head)) return SEQ_SLOT_KEPT;
+  const uint4 *c0 = reinterpret_cast<const uint4 *>(H.cand0 + fg * H.W);
+  uint4 v = head;
+  for (unsigned i = 0;;) {
+    const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (unsigned t = 0; t < 8; t++)
+      if (((w[t >> 1] >> (16 * (t & 1))) & 0xFFFFu) == x) return 8 * i + t;
+    if (++i >= H.W / 8) return 0;  // (not reached: F_P maps into the candidates)
+    v = c0[i];
+  }
+}
+__device__ __forceinline__ unsigned seq_state_behind(const SeqHandover &H, const uint16_t *__restrict__ fbuf, unsigned fstride,
+                                                     size_t fg, unsigned j, unsigned e, unsigned slot) {
+  return slot != SEQ_SLOT_KEPT && j >= H.P ? (unsigned)H.cand[(fg + j) * H.W + slot] : (unsigned)fbuf[(fg + j) * fstride + (e >> 1)];
+}
+
 __device__ __forceinline__ unsigned seq_resolve_groups(const uint32_t *__restrict__ fseg, const uint32_t *__restrict__ seg,
                                                        const uint16_t *__restrict__ fbuf, unsigned fstride, unsigned c, unsigned Q,
                                                        unsigned nf, unsigned ns, unsigned s_begin, unsigned s_end, unsigned xo,
-                                                       uint16_t *__restrict__ entry) {
+                                                       uint16_t *__restrict__ entry, const SeqHandover &H) {
   for (unsigned s0 = s_begin; s0 < s_end; s0 += Q) {
     entry[seg[c] + s0] = (uint16_t)xo;
+    const size_t fg = (size_t)fseg[c] + s0;
+    const uint4 head = seq_group_head(H, fg);
     unsigned v[SETS_MAX_GROUP];
+    // one round of loads from fbuf, the head beside them (behind the prefix of a handed-over group fbuf is stale) ...
 #pragma unroll
     for (unsigned j = 0; j < SETS_MAX_GROUP; j++)
-      v[j] = j < Q && s0 + j < nf ? (unsigned)fbuf[(size_t)(fseg[c] + s0 + j) * fstride + (xo >> 1)] : 0u;
+      v[j] = j < Q && s0 + j < nf ? seq_state_behind(H, fbuf, fstride, fg, j, xo, SEQ_SLOT_KEPT) : 0u;
+    if (seq_group_handed(head) && s0 + H.P < nf && H.P < Q) {  // ... and one from cand, for the candidate that F_P[xo] names
+      unsigned xp = 0;
+#pragma unroll
+      for (unsigned j = 0; j < SETS_MAX_GROUP; j++) xp = j + 1 == H.P ? v[j] : xp;
+      const unsigned slot = seq_group_slot(H, fg, head, xp);
+#pragma unroll
+      for (unsigned j = 0; j < SETS_MAX_GROUP; j++)
+        if (j >= H.P && j < Q && s0 + j < nf) v[j] = seq_state_behind(H, fbuf, fstride, fg, j, xo, slot);
+    }
     unsigned nx = xo;
 #pragma unroll
     for (unsigned j = 0; j < SETS_MAX_GROUP; j++)
@@ -497,7 +672,7 @@ constexpr unsigned SEQ_RESOLVE_THREADS = 1024;
 template <unsigned PER0>
 __device__ __forceinline__ void seq_compose_item(const uint32_t *__restrict__ plan, const uint32_t *__restrict__ logs,
                                                  const uint16_t *__restrict__ fbuf, unsigned fstride, unsigned qmax, unsigned gmin,
-                                                 unsigned item, uint16_t *__restrict__ cbuf) {
+                                                 unsigned item, uint16_t *__restrict__ cbuf, const SeqHandover &H) {
   constexpr unsigned B = SeqModel::B;
   const uint32_t *fseg = plan + (B + 1), *citem = plan + 4 * (B + 1);
   const unsigned lane = fq_lane();
@@ -508,12 +683,27 @@ __device__ __forceinline__ void seq_compose_item(const uint32_t *__restrict__ pl
   unsigned x[PER0];  // (state - size) * 2 behind the groups walked so far, for every entry state of the item
 #pragma unroll
   for (unsigned j = 0; j < PER0; j++) x[j] = ((lane + 64u * j) & (size - 1)) * 2u;
+  // which of the item's groups were handed over: lane l asks for group g0 + l, before the chain through the groups starts
+  const unsigned long long handed = __ballot(g0 + lane < g1 && seq_group_handed(seq_group_head(H, (size_t)fseg[c] + (g0 + lane) * Q)));
   for (unsigned g = g0; g < g1; g++) {
-    const unsigned last = min(g * Q + Q, nf) - 1;  // the group's last function: entry of the group -> entry of the next
-    const uint16_t *f = fbuf + (size_t)(fseg[c] + last) * fstride;
+    const unsigned last = min(Q, nf - g * Q) - 1;  // the group's last function: entry of the group -> entry of the next
+    const size_t fg = (size_t)fseg[c] + g * Q;
+    if (((handed >> (g - g0)) & 1ull) == 0ull) {  // (wave-uniform)
 #pragma unroll
-    for (unsigned j = 0; j < PER0; j++)
-      if (j < per) x[j] = f[x[j] >> 1];
+      for (unsigned j = 0; j < PER0; j++)
+        if (j < per) x[j] = seq_state_behind(H, fbuf, fstride, fg, last, x[j], SEQ_SLOT_KEPT);
+    } else {  // three rounds: the state behind the prefix, its candidate, the candidate's state behind the group
+      const uint4 head = seq_group_head(H, fg);
+#pragma unroll
+      for (unsigned j = 0; j < PER0; j++)
+        if (j < per) x[j] = seq_state_behind(H, fbuf, fstride, fg, H.P - 1, x[j], SEQ_SLOT_KEPT);
+#pragma unroll
+      for (unsigned j = 0; j < PER0; j++)
+        if (j < per) x[j] = seq_group_slot(H, fg, head, x[j]);
+#pragma unroll
+      for (unsigned j = 0; j < PER0; j++)
+        if (j < per) x[j] = seq_state_behind(H, fbuf, fstride, fg, last, 0u, x[j]);
+    }
   }
   uint16_t *o = cbuf + (size_t)item * fstride;
 #pragma unroll
@@ -530,7 +720,7 @@ template <unsigned PER0>
 __global__ void __launch_bounds__(SEQ_RESOLVE_THREADS)
 k_seq_resolve(const uint32_t *__restrict__ plan, const uint32_t *__restrict__ logs, const uint16_t *__restrict__ fbuf,
               unsigned fstride, unsigned qmax, unsigned gmin, uint16_t *__restrict__ cbuf, uint16_t *__restrict__ item_entry,
-              uint16_t *__restrict__ entry) {
+              uint16_t *__restrict__ entry, const SeqHandover H) {
   constexpr unsigned B = SeqModel::B;
   const uint32_t *fseg = plan + (B + 1), *seg = plan + 2 * (B + 1), *citem = plan + 4 * (B + 1);
   const unsigned c = threadIdx.x;
@@ -538,12 +728,12 @@ k_seq_resolve(const uint32_t *__restrict__ plan, const uint32_t *__restrict__ lo
   if (c < B) {
     ns = seg[c + 1] - seg[c]; nf = ns ? ns - 1 : 0; Q = seq_group_of(nf, qmax, gmin);
     ni = citem[c + 1] - citem[c];
-    if (ni == 0) (void)seq_resolve_groups(fseg, seg, fbuf, fstride, c, Q, nf, ns, 0, ns, 0u, entry);  // FSE_initCState: state = size
+    if (ni == 0) (void)seq_resolve_groups(fseg, seg, fbuf, fstride, c, Q, nf, ns, 0, ns, 0u, entry, H);  // FSE_initCState: state = size
   }
   const unsigned n_items = citem[B];
   if (n_items == 0) return;  // (uniform) no long chain in this block
   for (unsigned item = threadIdx.x >> 6; item < n_items; item += SEQ_RESOLVE_THREADS / 64)
-    seq_compose_item<PER0>(plan, logs, fbuf, fstride, qmax, gmin, item, cbuf);
+    seq_compose_item<PER0>(plan, logs, fbuf, fstride, qmax, gmin, item, cbuf, H);
   __threadfence();
   __syncthreads();
   if (c < B && ni) {
@@ -563,7 +753,7 @@ k_seq_resolve(const uint32_t *__restrict__ plan, const uint32_t *__restrict__ lo
     const unsigned s_begin = (item - citem[ic]) * SEQ_ITEM_GROUPS * iQ;
     const unsigned s_end = item + 1 == citem[ic + 1] ? ins : min(s_begin + SEQ_ITEM_GROUPS * iQ, ins);
     const unsigned xo = __hip_atomic_load(&item_entry[item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    (void)seq_resolve_groups(fseg, seg, fbuf, fstride, ic, iQ, inf, ins, s_begin, s_end, xo, entry);
+    (void)seq_resolve_groups(fseg, seg, fbuf, fstride, ic, iQ, inf, ins, s_begin, s_end, xo, entry, H);
   }
 }
 

@@ -193,9 +193,14 @@ int encode_stream(fqgpu_ctx *ctx, EncLane &lane, hipStream_t st, fqgpu_dblock *b
     if ((rc = sc.seg_arrays.reserve(seg_arrays_bytes))) return rc;
     if ((rc = sc.seq_fbuf.reserve(((size_t)gen_max_segs + B) * gen_fstride * 2 + 64))) return rc;
   }
+  // hand-over of collapsed groups (two-symbol tables only): candidate slots per group
+  const unsigned cand_cap = serial_seq && tab.next2 != nullptr ? min(ctx->seq_cand_cap, SEQ_CAND_MAX) : 0u;
+  const unsigned cand_W = cand_cap == 0 ? 0u : cand_cap <= 16 ? 16u : cand_cap <= 32 ? 32u : 64u;
+  const unsigned cand_P = min(max(ctx->seq_cand_prefix, 1u), SETS_MAX_GROUP);
   if (serial_seq) {
     if ((rc = sc.seq_plan.reserve((size_t)SEGPLAN_WORDS * 4 + (size_t)seq_max_segs * 2 + 64))) return rc;
     if ((rc = sc.seq_fbuf.reserve((size_t)seq_max_segs * seq_fstride * 2 + 64))) return rc;
+    if (cand_W && (rc = sc.seq_cand.reserve((size_t)seq_max_segs * cand_W * 4 + 64))) return rc;  // cand0 | cand
     if ((rc = sc.seq_cbuf.reserve((size_t)(seq_max_segs / SEQ_ITEM_GROUPS + B + 1) * (seq_fstride * 2 + 2) + 64))) return rc;
   }
   if (serial_seq && (rc = sc.seq_bdesc.reserve((size_t)(n_ptiles + 1) * SeqModel::B * 6 + 64))) return rc;
@@ -309,6 +314,14 @@ int encode_stream(fqgpu_ctx *ctx, EncLane &lane, hipStream_t st, fqgpu_dblock *b
     for (unsigned i = 0; i < FQ_SEQ_POW_SETS; i++)
       if (tab.seq_pow[i] && tab.seq_pow_S[i] == seq_S) pow = tab.seq_pow[i];
     const bool dbg_skip = fq_debug_flag("FQGPU_DEBUG_SKIP_SEQ_CHAIN");  // timing experiment only: wrong output
+    SeqHandover hand{};
+    hand.W = cand_W; hand.cap = cand_cap; hand.P = cand_P;
+    if (cand_W) {
+      hand.cand0 = sc.seq_cand.as<uint16_t>();
+      hand.cand = hand.cand0 + (size_t)seq_max_segs * cand_W;
+      hand.counts = &b->result->seq_groups_handed;
+    }
+    SeqHandover no_hand{};
     if (!dbg_off) hipLaunchKernelGGL(k_seq_segplan, dim3(1), dim3(256), 0, st, arrays, seq_S, Q, gmin, wpg * rounds, plan);
     FQ_SPAN_END();
     FQ_SPAN_BEGIN("seq.setfunc");
@@ -326,18 +339,35 @@ int encode_stream(fqgpu_ctx *ctx, EncLane &lane, hipStream_t st, fqgpu_dblock *b
       } else if (two)
         hipLaunchKernelGGL((k_seq_setfunc<32, true>), dim3(min(max_fitems, ctx->setfunc_wgs ? ctx->setfunc_wgs : ctx->n_cus)), dim3(SETS_WAVES2 * 64),
                            (32u << tab.max_log) + SETS_WAVES2 * sizeof(SetsWaveLds11) + 16, st, sc.sorted_sym.as<uint8_t>(), arrays, plan, tab.logs, tab.next2,
-                           4 * next_stride, pow, next_stride, seq_S, Q, gmin, rounds, seq_fstride, fbuf, plan + 5 * (B + 1), 32u << tab.max_log);
+                           4 * next_stride, pow, next_stride, seq_S, Q, gmin, rounds, seq_fstride, fbuf, plan + 5 * (B + 1), 32u << tab.max_log, hand);
       else
         hipLaunchKernelGGL((k_seq_setfunc<64, false>), dim3(min(max_fitems, 2 * ctx->n_cus)), dim3(SETS_WAVES * 64),
                            (8u << tab.max_log) + SETS_WAVES * sizeof(SetsWaveLds) + 16, st, sc.sorted_sym.as<uint8_t>(), arrays, plan, tab.logs, tab.next1,
-                           next_stride, pow, next_stride, seq_S, Q, gmin, rounds, seq_fstride, fbuf, plan + 5 * (B + 1), 8u << tab.max_log);
+                           next_stride, pow, next_stride, seq_S, Q, gmin, rounds, seq_fstride, fbuf, plan + 5 * (B + 1), 8u << tab.max_log, no_hand);
       FQ_SPAN_END();
+      if (cand_W) {  // the rest of the handed-over groups: one workgroup per k_seq_setfunc item, nothing but the table in LDS
+        FQ_SPAN_BEGIN("seq.candwalk");
+        if (!(dbg_off || fq_debug_skipk("candwalk"))) {
+          const dim3 cgrid(max_fitems), cblock(CANDW_WAVES * 64);
+          const unsigned clds = 32u << tab.max_log;
+          if (cand_W == 16)
+            hipLaunchKernelGGL(k_seq_candwalk<16>, cgrid, cblock, clds, st, sc.sorted_sym.as<uint8_t>(), arrays, plan, tab.logs, tab.next2, 4 * next_stride,
+                               seq_S, Q, gmin, rounds, hand);
+          else if (cand_W == 32)
+            hipLaunchKernelGGL(k_seq_candwalk<32>, cgrid, cblock, clds, st, sc.sorted_sym.as<uint8_t>(), arrays, plan, tab.logs, tab.next2, 4 * next_stride,
+                               seq_S, Q, gmin, rounds, hand);
+          else
+            hipLaunchKernelGGL(k_seq_candwalk<64>, cgrid, cblock, clds, st, sc.sorted_sym.as<uint8_t>(), arrays, plan, tab.logs, tab.next2, 4 * next_stride,
+                               seq_S, Q, gmin, rounds, hand);
+        }
+        FQ_SPAN_END();
+      }
       FQ_SPAN_BEGIN("seq.resolve");  dbg_off = (dbg_mask & 8u) != 0 || fq_debug_skipk("resolve");
       if (!dbg_off) {
         if (tab.max_log <= 11)
-          hipLaunchKernelGGL(k_seq_resolve<32>, dim3(1), dim3(SEQ_RESOLVE_THREADS), 0, st, plan, tab.logs, fbuf, seq_fstride, Q, gmin, cbuf, item_entry, entry);
+          hipLaunchKernelGGL(k_seq_resolve<32>, dim3(1), dim3(SEQ_RESOLVE_THREADS), 0, st, plan, tab.logs, fbuf, seq_fstride, Q, gmin, cbuf, item_entry, entry, hand);
         else
-          hipLaunchKernelGGL(k_seq_resolve<64>, dim3(1), dim3(SEQ_RESOLVE_THREADS), 0, st, plan, tab.logs, fbuf, seq_fstride, Q, gmin, cbuf, item_entry, entry);
+          hipLaunchKernelGGL(k_seq_resolve<64>, dim3(1), dim3(SEQ_RESOLVE_THREADS), 0, st, plan, tab.logs, fbuf, seq_fstride, Q, gmin, cbuf, item_entry, entry, no_hand);
       }
       FQ_SPAN_END();
       FQ_SPAN_BEGIN("seq.chains");  dbg_off = (dbg_mask & 8u) != 0 || fq_debug_skipk("emit");

@@ -54,6 +54,12 @@ struct DevTables {
   size_t ct_words = 0, dt_words = 0;
 };
 #define FQ_SEQ_POW_SETS 4
+#ifndef FQ_SEQ_CAND_CAP_DEFAULT  // (A/B variants: make variant DEFS=-DFQ_SEQ_CAND_CAP_DEFAULT=...)
+#define FQ_SEQ_CAND_CAP_DEFAULT 32u
+#endif
+#ifndef FQ_SEQ_CAND_PREFIX_DEFAULT
+#define FQ_SEQ_CAND_PREFIX_DEFAULT 1u
+#endif
 
 // Result block of one (block, stream) coding job, in device memory.
 struct StreamResult {
@@ -68,6 +74,8 @@ struct StreamResult {
 struct BlockResult {
   StreamResult s[2];
   unsigned long long n_pos_len;  // number of u16 entries in n_pos
+  unsigned int seq_groups_handed;  // sequence chains: segment groups k_seq_setfunc handed over to k_seq_candwalk ...
+  unsigned int seq_groups_kept;    // ... and groups it walked to their end (both 0 when nothing may be handed over)
 };
 
 // ---------------------------------------------------------------- helpers
@@ -152,6 +160,7 @@ struct EncScratch {
   DevBuf seq_plan;    // segment plan of the sequence chains (encode.hip: SEGPLAN_WORDS) + entry states
   DevBuf seq_fbuf;    // u16 [segments][1 << max_log] segment functions F: entry state -> exit state
   DevBuf seq_cbuf;    // sequence stream: composed functions and entry states of the items of long chains (k_seq_compose)
+  DevBuf seq_cand;    // sequence stream: u16 cand0[segments][W] | cand[segments][W], candidates of the handed-over groups (encode.hip: SeqHandover)
   DevBuf tile_bits;   // u32 [ptiles]
   DevBuf tile_bit_base;  // u64 [ptiles+1]
   DevBuf dbg_enc16;   // timing experiments only (FQGPU_DEBUG_NO_ALIAS): enc16 apart from the keys, so that stale keys stay valid
@@ -263,6 +272,8 @@ struct fqgpu_ctx {
   unsigned seq_segment = 0;      // segment length of the sequence chain kernels (0 = default)
   unsigned seq_group = 8;        // segments a k_seq_setfunc wave walks in one go, at most (<= SETS_MAX_GROUP)
   unsigned seq_group_min = 16;   // ... as long as a chain keeps this many groups (one per wave of a workgroup)
+  unsigned seq_cand_cap = FQ_SEQ_CAND_CAP_DEFAULT;  // a group down to this many states behind its prefix goes to k_seq_candwalk (0: none does)
+  unsigned seq_cand_prefix = FQ_SEQ_CAND_PREFIX_DEFAULT;  // ... segments of that prefix
   bool lds_atomics_ordered = false;  // probed at creation: k_scatter may rank with LDS atomics
   bool tile_sorted = true;           // tile-sorted partition + fused gather/pack (needs lds_atomics_ordered); false: slot-based path
   unsigned index_stride = 1u << 20;  // symbols between the snapshots of a decode index

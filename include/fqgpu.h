@@ -102,6 +102,10 @@ int fqgpu_ctx_set_seq_segment(fqgpu_ctx *ctx, unsigned symbols);
  * splits into min_groups such groups (0 = default 16, the waves of a workgroup).  Results never
  * depend on it. */
 int fqgpu_ctx_set_seq_group(fqgpu_ctx *ctx, unsigned max_segments, unsigned min_groups);
+/* Hand-over of collapsed groups (tables of log <= 11): a wave of the segment-function kernel that is down to at most `cap`
+ * distinct states behind the first `prefix_segments` segments of a group (0 = 1) leaves the rest of the group to a kernel
+ * that walks one lane per remaining state.  cap 1..64; 0 hands nothing over.  Results never depend on it. */
+int fqgpu_ctx_set_seq_handover(fqgpu_ctx *ctx, unsigned cap, unsigned prefix_segments);
 /* Allocates now what blocks of up to this shape will need (staging block of the host-pointer calls,
  * scratch of every encode lane): a worker calls it while it builds its workspace, so that its
  * first block does not pay for the allocations.  Optional; everything grows on demand. */
@@ -256,6 +260,9 @@ int fqgpu_dblock_status(const fqgpu_dblock *b, size_t *seq_len, size_t *qual_len
 /* diagnostics of the last encode (after fqgpu_sync): the longest run of symbols one lane
  * had to walk serially, per stream (the latency floor of the chain kernels) */
 int fqgpu_dblock_longest_chain(const fqgpu_dblock *b, unsigned *seq_steps, unsigned *qual_steps);
+/* diagnostics of the last encode (waits for it): segment groups of the sequence chains that were handed over
+ * (fqgpu_ctx_set_seq_handover) and groups that were not; both 0 where nothing may be handed over */
+int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed_over, unsigned *kept);
 /* diagnostics of the last encode of this block: how many segments of the quality chains
  * (src/fse_quality.cpp:19-52 cut into segments of S symbols) the chain kernels took as
  * counts[0] transparent (a symbol with one table cell inside: the state behind it is known),
