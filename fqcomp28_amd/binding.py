@@ -127,6 +127,7 @@ _PROTOS = {
     "fqgpu_dblock_fetch_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "fqgpu_dblock_load_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
     "fqgpu_ctx_set_lanes": (C.c_int, [C.c_void_p, C.c_uint]),
+    "fqgpu_ctx_fill_scratch": (C.c_int, [C.c_void_p, C.c_ubyte, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "fqgpu_ctx_reserve": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "fqgpu_ctx_set_seq_segment": (C.c_int, [C.c_void_p, C.c_uint]),
     "fqgpu_ctx_set_seq_group": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
@@ -727,6 +728,13 @@ class Context:
 
     def sync(self):
         _check(lib().fqgpu_sync(self.h), "sync")
+
+    def fill_scratch(self, byte):
+        """fqgpu_ctx_fill_scratch (a diagnostic for tests): every device scratch buffer of the handle, but the ones that
+        carry state on purpose, set to `byte` up to its capacity -> (buffers, bytes) filled"""
+        n, nb = C.c_size_t(0), C.c_size_t(0)
+        _check(lib().fqgpu_ctx_fill_scratch(self.h, byte, C.byref(n), C.byref(nb)), "fill_scratch")
+        return n.value, nb.value
 
     def chunk_crc32(self):
         """fqgpu_chunk_crc32 -> (rc, crc, len): the chunk on the staging block -- the one encode_raw has just coded, or

@@ -319,15 +319,40 @@ EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b) {
   return &l;
 }
 
-static void free_lane(EncLane &l) {
-  DevBuf *bufs[] = {&l.rec_start, &l.n_cnt32, &l.n_off, &l.scan_tmp, &l.first_sym, &l.tile_first, &l.rscan};
-  for (DevBuf *b : bufs) b->release();
-  for (int s = 0; s < 2; s++) {
-    EncScratch &e = l.enc[s];
-    DevBuf *eb[] = {&e.slot_of, &e.keys, &e.sorted_sym, &e.out16, &e.tile_hist, &e.tile_base, &e.group_sum,
-                    &e.ctx_arrays, &e.seg_state, &e.seg_arrays, &e.seq_bdesc, &e.seq_plan, &e.seq_fbuf, &e.seq_cbuf, &e.seq_cand, &e.tile_bits, &e.tile_bit_base, &e.scan_tmp, &e.tile_runs, &e.tile_sync, &e.dbg_enc16};
-    for (DevBuf *b : eb) b->release();
+// ------------------------------------------------------------------ the handle's scratch, one enumeration
+// Every device scratch buffer a handle owns, as f(owner, name, pointer, bytes allocated): the DevBuf lists of the scratch
+// structs (fqgpu_internal.h: FQ_SCRATCH_BUFS) and the staging block's buffers.  fqgpu_ctx_destroy frees what this visits and
+// fqgpu_ctx_fill_scratch fills it: one walk for both.
+template <class F> static void dblock_each_buf(fqgpu_dblock *b, const fqgpu_ctx *hp, F &&f);
+
+template <class F> static void ctx_each_devbuf(fqgpu_ctx *ctx, F &&f) {  // f(owner, name, DevBuf &)
+  for (int i = 0; i < FQ_MAX_LANES; i++) {
+    EncLane &l = ctx->lanes[i];
+    fq_each_buf(l, [&](const char *n, DevBuf &b) { f("lane", n, b); });
+    for (int s = 0; s < 2; s++) fq_each_buf(l.enc[s], [&](const char *n, DevBuf &b) { f("lane.enc", n, b); });
   }
+  fq_each_buf(*ctx, [&](const char *n, DevBuf &b) { f("ctx", n, b); });
+  fq_each_buf(ctx->hp_parse, [&](const char *n, DevBuf &b) { f("hp_parse", n, b); });
+  fq_each_buf(ctx->hp_hdr, [&](const char *n, DevBuf &b) { f("hp_hdr", n, b); });
+  fq_each_buf(ctx->hp_chunk, [&](const char *n, DevBuf &b) { f("hp_chunk", n, b); });
+  fq_each_buf(ctx->crc, [&](const char *n, DevBuf &b) { f("crc", n, b); });
+  fq_each_buf(ctx->stats, [&](const char *n, DevBuf &b) { f("stats", n, b); });
+  fq_each_buf(ctx->select, [&](const char *n, DevBuf &b) { f("select", n, b); });
+}
+
+// The scratch buffers whose content is state ON PURPOSE: fqgpu_ctx_fill_scratch leaves them alone.  Every other scratch word
+// is written before it is read within one call ("Scratch that carries state").
+static const struct { const char *owner, *name, *why; } kScratchState[] = {
+    {"lane", "rscan", "k_record_scan's tickets and epoch-stamped status words count on from launch to launch (zeroed when allocated and every 2^24 launches)"},
+    {"crc", "tab", "the CRC multiplier tables are built once per handle (CrcScratch::tab_built)"},
+};
+static bool scratch_is_state(const char *owner, const char *name) {
+  for (const auto &e : kScratchState)
+    if (!strcmp(e.owner, owner) && !strcmp(e.name, name)) return true;
+  return false;
+}
+
+static void free_lane(EncLane &l) {  // (its DevBufs: ctx_each_devbuf)
   hipEvent_t evs[] = {l.ev_fork, l.ev_join};
   for (hipEvent_t e : evs) if (e) (void)hipEventDestroy(e);
   hipStream_t sts[] = {l.st_seq, l.st_qual};
@@ -529,15 +554,12 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
 #endif
   free_tables(ctx->tab[0]);
   free_tables(ctx->tab[1]);
-  DevBuf *bufs[] = {&ctx->n_cnt32, &ctx->n_off, &ctx->scan_tmp, &ctx->dec_desc, &ctx->dec_chunks, &ctx->dec_recstart,
-                     &ctx->dec_idx, &ctx->dec_entries};
-  for (DevBuf *b : bufs) b->release();
-  ctx->hp_parse.release();  // the device parser's scratch (fqgpu_ctx_reserve / fqgpu_encode_begin without a record table)
-  ctx->hp_hdr.release();
-  ctx->hp_chunk.release();
-  ctx->crc.release();
-  ctx->stats.release();
-  ctx->select.release();
+  ctx_each_devbuf(ctx, [](const char *, const char *, DevBuf &b) { b.release(); });
+  ctx->hp_hdr.release_host();
+  ctx->hp_chunk.release_host();
+  ctx->crc.release_host();
+  ctx->stats.release_host();
+  ctx->select.release_host();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
   if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
@@ -681,8 +703,7 @@ extern "C" int fqgpu_ctx_dump_tables(fqgpu_ctx *ctx, int stream, unsigned model,
 extern "C" void fqgpu_dblock_destroy(fqgpu_dblock *b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  void *ps[] = {b->raw, b->recs, b->seq, b->qual, b->readlens, b->n_count, b->n_pos, b->result, b->index[0], b->index[1]};
-  for (void *p : ps) if (p) (void)hipFree(p);
+  dblock_each_buf(b, nullptr, [](const char *, void *p, size_t) { if (p) (void)hipFree(p); });
   if (b->ev_encoded) (void)hipEventDestroy(b->ev_encoded);
   delete b;
 }
@@ -1039,6 +1060,54 @@ static int hp_block_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size_
   b->result_pulled = true;
   memset(&b->host_result, 0, sizeof(b->host_result));
   *out = b;
+  return FQGPU_OK;
+}
+
+// The device buffers of a block as f(name, pointer, bytes allocated).  hp: the handle whose staging block b is -- the sizes are
+// the handle's (hp_grow counts elements) --, or nullptr: a caller's block, sizes not asked for (0).
+template <class F> static void dblock_each_buf(fqgpu_dblock *b, const fqgpu_ctx *hp, F &&f) {
+  f("raw", b->raw, hp ? hp->hp_raw : 0);
+  f("recs", b->recs, hp ? hp->hp_recs * sizeof(fqgpu_rec) : 0);
+  f("seq", b->seq, hp ? hp->hp_seq : 0);
+  f("qual", b->qual, hp ? hp->hp_qual : 0);
+  f("readlens", b->readlens, hp ? hp->hp_side * 2 : 0);
+  f("n_count", b->n_count, hp ? hp->hp_side * 2 : 0);  // (grown in step with readlens: hp_block_acquire)
+  f("n_pos", b->n_pos, hp ? hp->hp_npos * 2 : 0);
+  f("result", b->result, hp ? sizeof(BlockResult) : 0);
+  f("index[0]", b->index[0], hp && b->index[0] ? b->index_cap[0] + 64 : 0);  // (fq_index_reserve)
+  f("index[1]", b->index[1], hp && b->index[1] ? b->index_cap[1] + 64 : 0);
+}
+
+extern "C" int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t *n_buffers, size_t *n_bytes) {
+  if (!ctx || ctx->hp_pending || ctx->hp_hdr.pending) return FQGPU_E_ARG;
+  int rc = fqgpu_sync(ctx);  // (selects the device)
+  if (rc) return rc;
+  size_t bufs = 0, bytes = 0;
+  hipError_t he = hipSuccess;
+  auto fill = [&](void *p, size_t n) {
+    if (!p || !n || he != hipSuccess) return;
+    if ((he = hipMemsetAsync(p, byte, n, ctx->stream)) != hipSuccess) return;
+    bufs++;
+    bytes += n;
+  };
+  ctx_each_devbuf(ctx, [&](const char *owner, const char *name, DevBuf &b) {
+    if (!scratch_is_state(owner, name)) fill(b.p, b.cap);
+  });
+  if (fqgpu_dblock *b = ctx->hp_block) {
+    dblock_each_buf(b, ctx, [&](const char *, void *p, size_t n) { fill(p, n); });
+    // the staging block holds nothing any more: no chunk to digest, no index, no result
+    b->index_bytes[0] = b->index_bytes[1] = 0;
+    b->seq_len = b->qual_len = b->n_pos_len = 0;
+    b->last_op = 0;
+    b->result_pulled = true;
+    memset(&b->host_result, 0, sizeof(b->host_result));
+    ctx->hp_index_built = false;
+    ctx->hp_crc_what = 0;
+  }
+  FQ_HIP(he);
+  FQ_HIP(hipStreamSynchronize(ctx->stream));
+  if (n_buffers) *n_buffers = bufs;
+  if (n_bytes) *n_bytes = bytes;
   return FQGPU_OK;
 }
 

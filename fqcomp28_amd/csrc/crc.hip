@@ -244,8 +244,7 @@ int crc_launch(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *data_dev, size_t l
 
 }  // namespace
 
-void CrcScratch::release() {
-  for (DevBuf *b : {&tab, &rem, &res, &chk, &clen, &coff, &flat, &scan_tmp}) b->release();
+void CrcScratch::release_host() {
   if (host) (void)hipHostFree(host);
   host = nullptr;
   tab_built = false;

@@ -633,13 +633,11 @@ int fq_qual_counts_sorted(hipStream_t st, const uint8_t *raw_dev, const fqgpu_re
     }
   } while (0);
   (void)hipStreamSynchronize(st);
-  DevBuf *own[] = {&readlens, &result, &lane.rec_start, &lane.n_cnt32, &lane.n_off, &lane.scan_tmp, &lane.first_sym, &lane.tile_first};
-  for (DevBuf *b : own) b->release();
-  for (EncScratch *e : {&ss, &sq}) {
-    DevBuf *eb[] = {&e->slot_of, &e->keys, &e->sorted_sym, &e->out16, &e->tile_hist, &e->tile_base, &e->group_sum, &e->ctx_arrays,
-                    &e->tile_runs, &e->tile_sync, &e->scan_tmp};
-    for (DevBuf *b : eb) b->release();
-  }
+  readlens.release();
+  result.release();
+  fq_release_bufs(lane);  // (the lane is this call's own: the lists of fqgpu_internal.h)
+  fq_release_bufs(ss);
+  fq_release_bufs(sq);
   return rc;
 }
 

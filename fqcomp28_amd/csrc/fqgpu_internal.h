@@ -111,14 +111,27 @@ struct DevBuf {
   template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
 
+// The DevBufs of a scratch struct, ONE list per struct: what frees a handle and what fills its scratch with a byte
+// (fqgpu_ctx_fill_scratch) both walk it, so a buffer cannot be freed but never filled.  FQ_SCRATCH_BUFS(T, FQ_B(T, m), ...)
+// stands behind the struct; tests/test_build_invariants.py holds every list against the DevBuf members of its struct.
+template <class T> struct FqBufOf { const char *name; DevBuf T::*m; };
+#define FQ_B(T, m) {#m, &T::m}
+#define FQ_SCRATCH_BUFS(T, ...)                                                      \
+  inline constexpr FqBufOf<T> fq_bufs_##T[] = {__VA_ARGS__};                         \
+  template <class F> static inline void fq_each_buf(T &s, F &&f) {                   \
+    for (const FqBufOf<T> &e : fq_bufs_##T) f(e.name, s.*(e.m));                     \
+  }
+template <class T> static inline void fq_release_bufs(T &s) { fq_each_buf(s, [](const char *, DevBuf &b) { b.release(); }); }
+
 struct KernelTimer;  // api.cpp
 
 // grow-only scratch of the device record parser (parse.hip)
 struct ParseScratch {
   DevBuf cnt, base, sum, nl_pos, scan_tmp;
   size_t total_nl = 0;  // newlines counted by fq_parse_count
-  void release() { for (DevBuf *b : {&cnt, &base, &sum, &nl_pos, &scan_tmp}) b->release(); total_nl = 0; }
 };
+FQ_SCRATCH_BUFS(ParseScratch, FQ_B(ParseScratch, cnt), FQ_B(ParseScratch, base), FQ_B(ParseScratch, sum), FQ_B(ParseScratch, nl_pos),
+                FQ_B(ParseScratch, scan_tmp))
 
 // Result words of the device header coder (headers.hip), and its grow-only scratch
 struct HdrResult {
@@ -136,13 +149,14 @@ struct HdrScratch {
   size_t bound = 0;
   bool pending = false;           // kernels queued for the block in flight, results not collected yet
   bool collected = false;
-  void release() {
-    for (DevBuf *b : {&wg_sum, &wg_base, &out, &first, &res}) b->release();
+  void release_host() {  // (the device buffers: fq_release_bufs)
     if (host_res) (void)hipHostFree(host_res);
     if (host_first) (void)hipHostFree(host_first);
     host_res = nullptr; host_first = nullptr; pending = collected = false;
   }
 };
+FQ_SCRATCH_BUFS(HdrScratch, FQ_B(HdrScratch, wg_sum), FQ_B(HdrScratch, wg_base), FQ_B(HdrScratch, out), FQ_B(HdrScratch, first),
+                FQ_B(HdrScratch, res))
 
 // Scratch of the encode pipeline for one stream.
 struct EncScratch {
@@ -168,6 +182,12 @@ struct EncScratch {
   DevBuf tile_runs;   // tile-sorted path: uint2 [tiles][min(B, tile)] run list of every tile (encode.hip: enc_tile_sort.h)
   DevBuf tile_sync;   // tile-sorted path: u64 status[tiles] | u32 tile counter, pad | u32 run_count[tiles]
 };
+FQ_SCRATCH_BUFS(EncScratch, FQ_B(EncScratch, slot_of), FQ_B(EncScratch, keys), FQ_B(EncScratch, sorted_sym), FQ_B(EncScratch, out16),
+                FQ_B(EncScratch, tile_hist), FQ_B(EncScratch, tile_base), FQ_B(EncScratch, group_sum), FQ_B(EncScratch, ctx_arrays),
+                FQ_B(EncScratch, seg_state), FQ_B(EncScratch, seg_arrays), FQ_B(EncScratch, seq_bdesc), FQ_B(EncScratch, seq_plan),
+                FQ_B(EncScratch, seq_fbuf), FQ_B(EncScratch, seq_cbuf), FQ_B(EncScratch, seq_cand), FQ_B(EncScratch, tile_bits),
+                FQ_B(EncScratch, tile_bit_base), FQ_B(EncScratch, dbg_enc16), FQ_B(EncScratch, scan_tmp), FQ_B(EncScratch, tile_runs),
+                FQ_B(EncScratch, tile_sync))
 
 // One encode lane: everything a block needs while it is being coded, so that several
 // blocks can be in flight on one GPU (two HIP streams: sequence pipeline, quality pipeline).
@@ -184,6 +204,8 @@ struct EncLane {
   DevBuf scan_tmp;
   EncScratch enc[2];
 };
+FQ_SCRATCH_BUFS(EncLane, FQ_B(EncLane, rec_start), FQ_B(EncLane, n_cnt32), FQ_B(EncLane, n_off), FQ_B(EncLane, first_sym),
+                FQ_B(EncLane, tile_first), FQ_B(EncLane, rscan), FQ_B(EncLane, scan_tmp))
 
 // Header decode and chunk layout (decode_headers.hip, fqgpu_decode_chunk): the format, the dataset's first header and
 // the offsets of every stream in ONE staging buffer (this struct first, then readlens, the first header, per field
@@ -218,13 +240,15 @@ struct ChunkScratch {
     host_cap = host ? n + n / 8 : 0;
     return host != nullptr;
   }
-  void release() {
-    for (DevBuf *b : {&stage, &agg, &cls, &clp, &hlen, &tlen, &toff, &res, &scan_tmp, &pick}) b->release();
+  void release_host() {
     delete[] host;
     host = nullptr;
     host_cap = 0;
   }
 };
+FQ_SCRATCH_BUFS(ChunkScratch, FQ_B(ChunkScratch, stage), FQ_B(ChunkScratch, agg), FQ_B(ChunkScratch, cls), FQ_B(ChunkScratch, clp),
+                FQ_B(ChunkScratch, hlen), FQ_B(ChunkScratch, tlen), FQ_B(ChunkScratch, toff), FQ_B(ChunkScratch, res),
+                FQ_B(ChunkScratch, scan_tmp), FQ_B(ChunkScratch, pick))
 
 // CRC-32 of a chunk in HBM (crc.hip): multiplier tables (built once per handle), the slices' remainders, the result words
 // and, for a chunk with text behind its '+' lines, the canonical bytes gathered into `flat`
@@ -232,8 +256,10 @@ struct CrcScratch {
   DevBuf tab, rem, res, chk, clen, coff, flat, scan_tmp;
   uint32_t *host = nullptr;  // page-locked landing place of {crc32, len lo, len hi, 0} and, behind them, the record check's verdict
   bool tab_built = false;
-  void release();
+  void release_host();
 };
+FQ_SCRATCH_BUFS(CrcScratch, FQ_B(CrcScratch, tab), FQ_B(CrcScratch, rem), FQ_B(CrcScratch, res), FQ_B(CrcScratch, chk),
+                FQ_B(CrcScratch, clen), FQ_B(CrcScratch, coff), FQ_B(CrcScratch, flat), FQ_B(CrcScratch, scan_tmp))
 
 // Read summary of a chunk in HBM (stats.hip): the u64 result table, the workgroups' u32 slabs, the "a byte that cannot be
 // counted" flag and its page-locked landing place; all grown on demand
@@ -241,8 +267,9 @@ struct StatsScratch {
   DevBuf out, slabs, bad;
   unsigned *host_bad = nullptr;
   bool attr_set = false;  // the count kernel's LDS size has been asked for
-  void release();
+  void release_host();
 };
+FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs), FQ_B(StatsScratch, bad))
 
 // Selection of the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip): per record the kept size, the
 // start of its header line and -- reserved by a trim call alone -- its window, beside it -- by a clip call alone -- its clip
@@ -255,8 +282,11 @@ struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   DevBuf probe_out, probe_places;
   void *host = nullptr;
-  void release();
+  void release_host();
 };
+FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, hstart), FQ_B(SelectScratch, win), FQ_B(SelectScratch, clip),
+                FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
+                FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places))
 
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
@@ -311,6 +341,10 @@ struct fqgpu_ctx {
   StatsScratch stats;
   SelectScratch select;
 };
+
+// (the handle's own DevBufs: the decode scratch)
+FQ_SCRATCH_BUFS(fqgpu_ctx, FQ_B(fqgpu_ctx, n_cnt32), FQ_B(fqgpu_ctx, n_off), FQ_B(fqgpu_ctx, scan_tmp), FQ_B(fqgpu_ctx, dec_desc),
+                FQ_B(fqgpu_ctx, dec_chunks), FQ_B(fqgpu_ctx, dec_recstart), FQ_B(fqgpu_ctx, dec_idx), FQ_B(fqgpu_ctx, dec_entries))
 
 EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b = nullptr);  // api.hip: the next lane in turn or the block's own; creates streams on first use
 // Blocks a handle keeps in flight when the caller has not said (fqgpu_ctx_set_lanes(ctx, 0), the default): four -- two

@@ -177,8 +177,7 @@ int fq_parse_on_device(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, D
   if (!rc && !(recs = fq_dev_alloc<fqgpu_rec>(R))) rc = FQGPU_E_NOMEM;
   if (!rc) rc = fq_parse_records(st, raw_dev, raw_len, ps, recs, R, n_bases, n_n, nullptr);
   std::swap(ps.scan_tmp, scan_tmp);
-  DevBuf *bufs[] = {&ps.cnt, &ps.base, &ps.sum, &ps.nl_pos};
-  for (DevBuf *b : bufs) b->release();
+  fq_release_bufs(ps);  // (scan_tmp is the caller's again: ps holds an empty one)
   if (rc) { if (recs) (void)hipFree(recs); return rc; }
   *recs_dev = recs;
   *n_recs = R;

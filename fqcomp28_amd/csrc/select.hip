@@ -1346,8 +1346,7 @@ k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__rest
 
 }  // namespace
 
-void SelectScratch::release() {
-  for (DevBuf *b : {&ksize, &hstart, &win, &clip, &places, &keep, &koff, &dst, &res, &scan_tmp, &probe_out, &probe_places}) b->release();
+void SelectScratch::release_host() {
   if (host) (void)hipHostFree(host);
   host = nullptr;
 }

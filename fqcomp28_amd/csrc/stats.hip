@@ -214,8 +214,7 @@ k_stats_reduce(const uint32_t *__restrict__ slabs, unsigned n_slabs, unsigned P,
 
 }  // namespace
 
-void StatsScratch::release() {
-  for (DevBuf *b : {&out, &slabs, &bad}) b->release();
+void StatsScratch::release_host() {
   if (host_bad) (void)hipHostFree(host_bad);
   host_bad = nullptr;
   attr_set = false;

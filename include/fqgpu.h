@@ -270,6 +270,16 @@ int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed_over, unsi
  * a power of one transition), [3] opaque (the full entry-state -> exit-state function).  Reads the
  * scratch of the encode lane that coded the block: valid until that lane codes another block. */
 int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]);
+/* diagnostics, for tests of "no result depends on what the scratch held before": waits for the handle (fqgpu_sync) and sets
+ * every byte of every device scratch buffer the handle owns -- the encode lanes, the decode scratch, the device parser's,
+ * header coder's and chunk decoder's, the checksum, summary and selection scratch, and the staging block of the host-pointer
+ * calls, inputs and outputs alike -- to `byte`, up to each buffer's capacity.  Exempt are the buffers that carry state from
+ * call to call on purpose (the table beside the implementation names them).  *n_buffers / *n_bytes (either may be NULL): how
+ * many buffers and bytes were filled.  Afterwards the staging block holds no chunk and no index (fqgpu_chunk_* and
+ * fqgpu_encode_index / fqgpu_decode_index answer FQGPU_E_ARG until the next host-pointer call), and
+ * fqgpu_dblock_qual_segment_classes of a block coded before is meaningless.  FQGPU_E_ARG while a block of fqgpu_encode_begin
+ * or its header fields are still to be collected.  Nothing in the product calls it. */
+int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t *n_buffers, size_t *n_bytes);
 /* copies results to the host (synchronous); any pointer may be NULL */
 int fqgpu_dblock_fetch(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint8_t *seq_out, uint8_t *qual_out,
                        uint16_t *readlens_out, uint16_t *n_count_out, uint16_t *n_pos_out,

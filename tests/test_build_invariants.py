@@ -135,3 +135,47 @@ def test_seq_setfunc_table_sits_at_lds_address_zero(tmp_path):
     body = body[:body.index("s_endpgm")]
     n_sdwa = len(re.findall(r"v_add_u32_sdwa v\d+, s\d+, v\d+ .*src0_sel:WORD_[01]", body))
     assert n_sdwa >= 16, n_sdwa
+
+
+def test_every_scratch_buffer_is_in_the_list_that_frees_and_fills_it():
+    """fqgpu_ctx_destroy frees and fqgpu_ctx_fill_scratch fills what ONE enumeration visits: per scratch struct the list
+    behind it (FQ_SCRATCH_BUFS, fqgpu_internal.h), for the staging block dblock_each_buf (api.hip).  A DevBuf member that
+    is missing from its struct's list, or a block pointer missing from dblock_each_buf, would be neither freed nor filled.
+
+    The check reads the sources as text, so it also trips on a spelling it does not know.  When it does:
+      - a new DevBuf member: add FQ_B(Struct, member) to the FQ_SCRATCH_BUFS list behind its struct; declare it as the
+        others are (`DevBuf a, b;` -- plain members, no initialiser), or teach `members` below the new form;
+      - a new scratch struct: give it a FQ_SCRATCH_BUFS list, visit it in ctx_each_devbuf and add its expression to `visited`;
+      - a new device pointer in fqgpu_dblock: add it to dblock_each_buf with the bytes allocated for it, and to both lists
+        below (`owned` takes every non-const pointer member, of any type)."""
+    csrc = os.path.join(ROOT, "fqcomp28_amd", "csrc")
+    head = re.sub(r"//.*", "", open(os.path.join(csrc, "fqgpu_internal.h")).read())
+    lists = {m.group(1): re.findall(r"FQ_B\(\s*(\w+)\s*,\s*(\w+)\s*\)", m.group(2) + ")")
+             for m in re.finditer(r"^FQ_SCRATCH_BUFS\((\w+),(.*?)\)\)\n", head, re.S | re.M)}
+    structs = dict(re.findall(r"^struct (\w+) \{\n(.*?)^\};", head, re.S | re.M))
+    with_bufs = {name for name, body in structs.items() if name != "DevBuf" and re.search(r"^\s*DevBuf\s+\w", body, re.M)}
+    assert with_bufs == set(lists) and len(lists) >= 9, (sorted(with_bufs), sorted(lists))
+    for name, entries in lists.items():
+        members = [n.strip() for decl in re.findall(r"^\s*DevBuf\s+([^;()]+);", structs[name], re.M) for n in decl.split(",")]
+        assert all(owner == name for owner, _ in entries), name
+        listed = [m for _, m in entries]
+        assert sorted(listed) == sorted(members) and len(set(listed)) == len(listed), (name, sorted(set(members) ^ set(listed)))
+    api = re.sub(r"//.*", "", open(os.path.join(csrc, "api.hip")).read())
+    # every struct with a list is visited by the handle's enumeration (an EncScratch through its lane)
+    walk = re.search(r"static void ctx_each_devbuf\([^)]*\) \{.*?^\}", api, re.S | re.M).group(0)
+    visited = set(re.findall(r"fq_each_buf\(([^,]+),", walk))
+    assert visited == {"l", "l.enc[s]", "*ctx", "ctx->hp_parse", "ctx->hp_hdr", "ctx->hp_chunk", "ctx->crc", "ctx->stats", "ctx->select"}, visited
+    fields = dict(re.findall(r"^\s*(\w+Scratch)\s+(\w+)(?:\[\d\])?;", structs["fqgpu_ctx"] + structs["EncLane"], re.M))
+    assert set(fields) == set(lists) - {"EncLane", "fqgpu_ctx"}, sorted(fields)
+    # the staging block: every device pointer of a block
+    each = re.search(r"static void dblock_each_buf\([^)]*\) \{.*?^\}", api, re.S | re.M).group(0)
+    assert re.findall(r'f\("[^"]+", b->([\w\[\]]+),', each) == ["raw", "recs", "seq", "qual", "readlens", "n_count", "n_pos", "result", "index[0]", "index[1]"]
+    # (every pointer member the block may write through, whatever its type; `owner` is the handle, not a buffer)
+    owned = re.findall(r"^\s*(?!const\b)\w+ \*(.*?);", structs["fqgpu_dblock"], re.M)
+    names = sorted(re.sub(r"\s*=.*", "", n).strip(" *") for decl in owned for n in re.split(r",(?![^{]*\})", re.sub(r";.*", "", decl)))
+    assert names == sorted(["owner", "raw", "recs", "seq", "qual", "readlens", "n_count", "n_pos", "result", "index[2]"]), \
+        ("a device pointer of fqgpu_dblock that dblock_each_buf does not visit, or a member this test cannot read", names)
+    # the exemptions name buffers that exist
+    for owner, name in re.findall(r'\{"(\w+)", "(\w+)", "', re.search(r"kScratchState\[\] = \{(.*?)^\};", api, re.S | re.M).group(1)):
+        struct = {"lane": "EncLane", "crc": "CrcScratch"}[owner]
+        assert (struct, name) in lists[struct]

@@ -2,12 +2,10 @@
 the set walk that is down to <= cap states behind a prefix of a group leaves the rest of the group to a kernel that walks
 one lane per remaining state, and the resolve step finds a group entry's lane through the function behind the prefix.
 Whatever (cap, prefix), group size and table shape: the five streams are the CPU oracle's, byte for byte."""
-import functools
-
 import numpy as np
 import pytest
 
-import oracle_lib as O
+from seq_blocks import block as _block
 
 BASES = ["uniform", "skewed", "markov", "all_A", "mostly_A"]
 GROUPS = [(2, 1), (3, 1), (8, 1), (16, 4)]
@@ -20,59 +18,6 @@ def F():
     import fqcomp28_amd as F
     assert F.device_count() >= 1, "no GPU visible: the product path has no CPU fallback"
     return F
-
-
-def _rewrite_bases(raw, recs, make):
-    """the block with its bases replaced by make(n) -> codes 0..3 (A, C, G, T)"""
-    raw = raw.copy()
-    lens = recs["len"].astype(np.int64)
-    letters = np.frombuffer(b"ACGT", dtype=np.uint8)[make(int(lens.sum()))]
-    at = 0
-    for off, ln in zip(recs["seq_off"].astype(np.int64), lens):
-        raw[off: off + ln] = letters[at: at + ln]
-        at += ln
-    return raw
-
-
-def _markov(rng, n):  # 70 %: repeat the previous base, else a fresh uniform one
-    fresh = rng.integers(0, 4, size=n)
-    keep = rng.random(n) < 0.7
-    keep[0] = False
-    return fresh[np.maximum.accumulate(np.where(keep, 0, np.arange(n)))]
-
-
-def _half_all_a(rng, recs, n):  # first half of the reads all A, the rest uniform
-    out = rng.integers(0, 4, size=n)
-    out[: int(recs["len"][: len(recs) // 2].sum())] = 0
-    return out
-
-
-MAKERS = {
-    "skewed": lambda rng, recs, n: rng.choice(4, size=n, p=[0.55, 0.05, 0.1, 0.3]),
-    "markov": lambda rng, recs, n: _markov(rng, n),
-    "all_A": lambda rng, recs, n: np.zeros(n, dtype=np.int64),
-    "mostly_A": lambda rng, recs, n: rng.choice(4, size=n, p=[0.997, 0.001, 0.001, 0.001]),
-    "mixed": _half_all_a,
-    "two_letters": lambda rng, recs, n: rng.choice(4, size=n, p=[0.6, 0.4, 0.0, 0.0]),
-}
-
-
-@functools.lru_cache(maxsize=None)
-def _block(bases, size=6 << 20):
-    """(raw, recs, sft, qft, the oracle's encoding): computed once per shape of the bases, shared by every case"""
-    import fqcomp28_amd as F
-    raw, n = F.synth_fastq(size, 2, seed=28)
-    recs = F.parse_fastq(raw)
-    assert len(recs) == n
-    if bases != "uniform":
-        rng = np.random.default_rng(5)
-        raw = _rewrite_bases(raw, recs, lambda m: MAKERS[bases](rng, recs, m))
-    _, _, sft, qft = O.freq_tables(raw, recs)
-    want = O.OracleCtx(sft, qft).encode(raw, recs)
-    assert want["rc"] == 0
-    for a in (raw, recs):
-        a.setflags(write=False)
-    return raw, recs, sft, qft, want
 
 
 def _encode(F, blk, segment, group, handover):

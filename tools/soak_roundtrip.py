@@ -5,7 +5,10 @@ block itself or from another block (foreign tables: escapes and rare symbols), e
 the oracle's -> decode of the ORACLE's streams -> raw block byte-equal.  A third of the cases move the chain stage's
 segment lengths and group sizes off their defaults, a third code a decode index and decode through it; the block goes
 through the device-resident calls, the host-pointer call or, unparsed, through the GPU's record finder; behind the
-host-pointer calls the oracle's streams are damaged (bit flips, truncation, random bytes) and decoded by both.
+host-pointer calls the oracle's streams are damaged (bit flips, truncation, random bytes) and decoded by both.  Before a
+random half of the cases -- drawn from a generator of its own, so that a seed names the same cases as ever -- the handle
+codes the block once, by the path and on the lane of the case, and its scratch is then filled with 0x00, 0xFF or 0xA5
+(Context.fill_scratch), and again between the encode and the decode: no result may depend on what the scratch held.
     python tools/soak_roundtrip.py [cases, default 60] [first seed] [largest block in MiB, default 3] [smallest block in MiB, default: 3000 bytes]"""
 import os
 import sys
@@ -41,7 +44,10 @@ def rewrite_qualities(raw, recs, rng, how):
     return raw
 
 
-def several_blocks_in_flight(case, seed):
+FILL_BYTES = [0, 255, 165]
+
+
+def several_blocks_in_flight(case, seed, fill_rng):
     """2 .. 6 blocks of different sizes and kinds on ONE handle, encoded without waiting in between (each takes the
     next encode lane), then decoded in one batch: every block against the oracle."""
     rng = np.random.default_rng(seed)
@@ -69,6 +75,8 @@ def several_blocks_in_flight(case, seed):
                 assert np.array_equal(g[k], e[k]), (case, "several", k)
             b.wipe()
             good.append((b, raw))
+    if fill_rng.random() < 0.5:
+        ctx.fill_scratch(int(fill_rng.choice(FILL_BYTES)))
     if good:
         ctx.decode_dblocks([b for b, _ in good])
         ctx.sync()
@@ -89,6 +97,7 @@ def main():
     t0 = time.time()
     done = damaged = 0
     verbose = bool(os.environ.get("SOAK_VERBOSE"))
+    fill_rng = np.random.default_rng([seed0, 0xF111])  # apart from the cases' generators
     if verbose:  # a case that does not come back: where it stands, after a minute
         import faulthandler
         faulthandler.enable()
@@ -100,7 +109,7 @@ def main():
         if case % 10 == 0 and case:
             print("case %d of %d, %d round trips, %.0f s" % (case, cases, done, time.time() - t0), flush=True)
         if case % 5 == 4:
-            done += several_blocks_in_flight(case, seed0 + case) > 0
+            done += several_blocks_in_flight(case, seed0 + case, fill_rng) > 0
             continue
         rng = np.random.default_rng(seed0 + case)
         mode = int(rng.choice([2, 2, 3, 4, 4, 5, 6]))
@@ -129,23 +138,32 @@ def main():
             ctx.set_index_stride(int(rng.choice([1, 2, 4])) << 16)
         octx = O.OracleCtx(sft, qft)
         e = octx.encode(raw, recs)
+        fill = fill_rng.random() < 0.5
         path = int(rng.integers(0, 3))  # 0: device-resident block, 1: host-pointer call, 2: unparsed chunk (GPU parser)
-        if path == 0:
-            b = ctx.dblock(raw, recs)
-            b.encode(flags=F.F_DECODE_INDEX if with_index else 0)
-            ctx.sync()
-            rc = b.status()[0]
-            g = b.fetch() if rc == 0 else None
-        else:
+        flags = F.F_DECODE_INDEX if with_index else 0
+        b = ctx.dblock(raw, recs) if path == 0 else None
+
+        def encode():
+            if b is not None:  # (coded again, a block goes back to the lane of its last encode: the same scratch)
+                b.encode(flags=flags)
+                ctx.sync()
+                rc = b.status()[0]
+                return rc, (b.fetch() if rc == 0 else None)
             g = ctx.encode_block(raw, recs) if path == 1 else ctx.encode_raw(raw)
-            rc = g["rc"]
-            b = None
+            return g["rc"], g
+
+        if fill and raw.size <= (8 << 20):  # the scratch sized and used by this very block on this very path, then filled
+            encode()
+            ctx.fill_scratch(int(fill_rng.choice(FILL_BYTES)))
+        rc, g = encode()
         assert rc == e["rc"], (case, path, rc, e["rc"])
         if rc == 0:
             for k in ("seq", "qual", "readlens", "n_count", "n_pos"):
                 assert np.array_equal(g[k], e[k]), (case, mode, how, path, k)
             if path == 2:
                 assert np.array_equal(g["recs"], recs), (case, "record table of the GPU parser")
+            if fill:
+                ctx.fill_scratch(int(fill_rng.choice(FILL_BYTES)))
             if b is not None:
                 # decode of the ORACLE's streams (with this block's own index when it has one: the index belongs to
                 # the streams, which are the oracle's byte for byte)
