@@ -527,6 +527,7 @@ extern "C" int fqgpu_ctx_create(int device, const void *seq_ft, const void *qual
     return FQGPU_E_HIP;
   }
   rc = fq_probe_lds_atomic_order(ctx->stream, &ctx->lds_atomics_ordered);
+  if (!rc) rc = fq_encode_init_device();
   if (getenv("FQGPU_NO_LDS_ATOMIC_RANK")) ctx->lds_atomics_ordered = false;  // force the ballot kernel
   if (getenv("FQGPU_SLOT_PARTITION")) ctx->tile_sorted = false;  // the slot-based partition/gather (same bits, for comparisons)
   if (const char *e = getenv("FQGPU_SETFUNC_WGS")) ctx->setfunc_wgs = (unsigned)atoi(e);  // experiments: same bits
@@ -671,6 +672,7 @@ extern "C" int fqgpu_ctx_set_lanes(fqgpu_ctx *ctx, unsigned lanes) {
   if (rc) return rc;
   ctx->n_lanes = lanes;
   ctx->next_lane = 0;
+  for (EncLane &l : ctx->lanes) l.forget_diag();  // blocks land on other lanes from here on: no lane answers for an earlier encode
   return FQGPU_OK;
 }
 
@@ -902,13 +904,17 @@ extern "C" int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dbl
   counts[0] = counts[1] = counts[2] = counts[3] = 0;
   int rc = fqgpu_sync(ctx);
   if (rc) return rc;
-  if (!b->diag_cls || !b->diag_n_segs) return FQGPU_E_ARG;  // no encode of this block yet
+  // the classes lie in the scratch of the lane that coded the block: the handle's own lane, and only while no later encode has
+  // gone through it and it has not been reset (free_lane, fqgpu_ctx_set_lanes)
+  if (b->owner != ctx || !b->diag_stamp || b->home_lane < 0 || b->home_lane >= FQ_MAX_LANES) return FQGPU_E_ARG;
+  const EncLane &lane = ctx->lanes[b->home_lane];
+  if (lane.diag_stamp != b->diag_stamp || !lane.diag_cls || !lane.diag_n_segs) return FQGPU_E_ARG;
   uint32_t n = 0;
-  FQ_HIP(hipMemcpy(&n, b->diag_n_segs, 4, hipMemcpyDeviceToHost));
+  FQ_HIP(hipMemcpy(&n, lane.diag_n_segs, 4, hipMemcpyDeviceToHost));
   if (!n) return FQGPU_OK;
   uint8_t *cls = static_cast<uint8_t *>(malloc(n));
   if (!cls) return FQGPU_E_NOMEM;
-  const hipError_t he = hipMemcpy(cls, b->diag_cls, n, hipMemcpyDeviceToHost);
+  const hipError_t he = hipMemcpy(cls, lane.diag_cls, n, hipMemcpyDeviceToHost);
   if (he == hipSuccess)
     for (uint32_t i = 0; i < n; i++) counts[cls[i] == 1 ? 0 : cls[i] == 0xFF ? 2 : cls[i] == 0 ? 3 : 1]++;
   free(cls);
@@ -1084,6 +1090,7 @@ extern "C" int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t
   if (rc) return rc;
   size_t bufs = 0, bytes = 0;
   hipError_t he = hipSuccess;
+  for (EncLane &l : ctx->lanes) l.forget_diag();  // the segment classes of earlier encodes are about to be overwritten
   auto fill = [&](void *p, size_t n) {
     if (!p || !n || he != hipSuccess) return;
     if ((he = hipMemsetAsync(p, byte, n, ctx->stream)) != hipSuccess) return;
@@ -1126,7 +1133,7 @@ extern "C" int fqgpu_ctx_reserve(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, 
       (rc = ctx->hp_parse.nl_pos.reserve((n_recs * 4 + 8) * 4)))
     return rc;
   const unsigned first = ctx->next_lane;
-  for (unsigned l = 0; l < fq_lanes_for(ctx, n_bases) && !rc; l++) rc = fq_encode_launch(ctx, b, 0, nullptr, nullptr, true);
+  for (unsigned l = 0; l < fq_lanes_for(ctx, n_bases) && !rc; l++) rc = fq_encode_reserve(ctx, b);
   ctx->next_lane = first;
   return rc;
 }

@@ -21,8 +21,7 @@ constexpr unsigned SEG_NONE = 0xFFFFFFFFu;
 // class of a segment (SegArrays::cls): 0 = opaque, 1 .. 64 = anchored (the state behind its anchor
 // symbol is one of that many candidates; 1 = reset symbol: transparent), 0xFF = uniform (S times
 // one symbol whose count is too large to be an anchor)
-constexpr unsigned SEG_CLS_OPAQUE = 0, SEG_CLS_UNIFORM = 0xFF, SEG_MAX_CAND = 64;
-constexpr unsigned SEG_SLOT = 16;  // lanes of one candidate walk: four walks share a wave
+constexpr unsigned SEG_CLS_OPAQUE = 0, SEG_CLS_UNIFORM = 0xFF;  // (SEG_MAX_CAND = 64, SEG_SLOT: enc_plan.h)
 
 // segment table of one stream (all arrays indexed by the global segment number)
 struct SegArrays {

@@ -56,19 +56,14 @@ __device__ __forceinline__ unsigned reset_state(const LdsCTable &t, unsigned sym
 //      packed (nb, bits) of every symbol; 64 segments of a context per wave.
 // All three read the context's one-symbol transition table next[s][x] from LDS (tables.hip
 // builds it once per handle).  Exact by construction: no speculation, nothing to verify.
-constexpr unsigned SETS_WAVES = 8;          // segments (waves) per workgroup in step A, one-symbol table
-constexpr unsigned SETS_WAVES2 = 16;        // ... with the 64 KB two-symbol table (one workgroup per CU)
-constexpr unsigned SETS_ROUNDS = 4;         // a workgroup owns WAVES * max(SETS_ROUNDS / group, 1) groups, handed out to its waves one by one
+// (SETS_WAVES, SETS_WAVES2, SETS_ROUNDS, SETS_MAX_GROUP, SETS_BLOCK, SEQ_CAND_MAX: enc_plan.h, the host sizes scratch by them)
 constexpr unsigned SETS_MAX_CLASSES = 512;  // above this a segment keeps carrying every state
-constexpr unsigned SETS_MAX_GROUP = 16;     // segments a wave walks in one go, at most
-constexpr unsigned SETS_BLOCK = 1024;       // symbols per 16-byte-per-lane load; S is a multiple
 
 // Hand-over of collapsed groups (two-symbol path).  After a prefix of P segments the states a group still carries are
 // few (19-40 after 2048 symbols, fewer than 10 from 8192 on), and a 64-lane gather per step walks mostly spare lanes.  A
 // wave of k_seq_setfunc that stands at n <= cap classes behind the prefix writes them out as the group's CANDIDATES and
 // takes its next group; k_seq_candwalk walks the rest of the group with one lane per candidate (64 / W groups per wave)
 // and needs nothing but the context's table in LDS; k_seq_resolve finds a group entry's candidate through F_P.
-constexpr unsigned SEQ_CAND_MAX = 64;        // candidates of a handed-over group, at most (one wave-instruction)
 constexpr unsigned SEQ_CAND_KEPT = 0xFFFFu;  // cand0[group][0] of a group that kept its functions (no state: states are even)
 constexpr unsigned CANDW_WAVES = 8;          // waves of a k_seq_candwalk workgroup
 struct SeqHandover {
@@ -100,11 +95,7 @@ __device__ __forceinline__ unsigned seq_group_of(unsigned nf, unsigned qmax, uns
   return min(max((nf + gmin - 1) / gmin, 1u), qmax);
 }
 
-// plan[]: fitem_base[B+1] (step A workgroups before every context) | fseg_base[B+1] (functions
-// before every context) | seg_base[B+1] (segments) | eitem_base[B+1] (step C waves) |
-// citem_base[B+1] (step B items: 64 groups each, for chains of more than SEQ_ITEM_GROUPS groups)
-constexpr unsigned SEGPLAN_WORDS = 5 * (SeqModel::B + 1) + 4;  // + the work counter of step A
-constexpr unsigned SEQ_ITEM_GROUPS = 64;
+// plan[]: its layout, SEGPLAN_WORDS and SEQ_ITEM_GROUPS stand in enc_plan.h
 // items of a chain with nl groups (0: the chain is short, k_seq_resolve walks its groups itself)
 __device__ __forceinline__ unsigned seq_items_of(unsigned nl) { return nl > SEQ_ITEM_GROUPS ? (nl + SEQ_ITEM_GROUPS - 1) / SEQ_ITEM_GROUPS : 0u; }
 

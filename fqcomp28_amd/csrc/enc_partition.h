@@ -13,7 +13,7 @@
 // (Staging the tile's partition in LDS to write whole runs was measured SLOWER: the 32 KB buffer
 // costs two thirds of the occupancy and the loop is VALU-bound on the ballot match, not on stores.)
 constexpr unsigned SC_BATCH = 4096;      // quality: 36 KB of LDS per wave
-constexpr unsigned SC_BATCH_SEQ = 8192;  // sequence: 32 bytes per context and batch
+// (SC_BATCH_SEQ = 8192, sequence: 32 bytes per context and batch -- enc_plan.h)
 
 
 // ORDERED: the rank comes from one LDS atomic per lane instead of the ballot match.  Same-address

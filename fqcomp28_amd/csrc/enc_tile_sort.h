@@ -17,7 +17,7 @@
 // Stable = every context's run keeps encode order = its tANS state chain; the streams are
 // bit-identical to the slot-based path (kept as the fallback when the probe of
 // fq_probe_lds_atomic_order fails).
-constexpr unsigned TS_TILE = 32768;    // symbols per tile (lpos16 and the 16-bit cursors hold 0 .. 32768)
+// (TS_TILE = 32768 symbols per tile: enc_plan.h)
 constexpr unsigned TS_BATCH = 4096;    // symbols ranked between two workgroup barriers (K3: 72 KB of LDS, two workgroups per CU)
 constexpr unsigned TS_THREADS = 512;   // K3
 constexpr unsigned TS_WAVES = TS_THREADS / 64;

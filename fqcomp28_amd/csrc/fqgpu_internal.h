@@ -158,36 +158,18 @@ struct HdrScratch {
 FQ_SCRATCH_BUFS(HdrScratch, FQ_B(HdrScratch, wg_sum), FQ_B(HdrScratch, wg_base), FQ_B(HdrScratch, out), FQ_B(HdrScratch, first),
                 FQ_B(HdrScratch, res))
 
-// Scratch of the encode pipeline for one stream.
+// Scratch of the encode pipeline for one stream.  What each buffer holds, its size and the sub-arrays inside it: EncPlan
+// (enc_plan.h), which both fqgpu_ctx_reserve and a launch reserve from.
 struct EncScratch {
-  DevBuf slot_of;     // u32 [M]   sorted position of every symbol (encode order)
-  DevBuf keys;        // u32 [M]   ctx | sym << 16 of every symbol (encode order)
-  DevBuf sorted_sym;  // u8  [M+pad]
-  DevBuf out16;       // u16 [M+pad] (nb<<12 | bits) at sorted position
-  DevBuf tile_hist;   // u32 [tiles][B]
-  DevBuf tile_base;   // u32 [tiles][B]
-  DevBuf group_sum;   // u32 [groups][B]
-  DevBuf ctx_arrays;  // ctx_count[B], ctx_start[B+1], seg_base[B+1], item_base[B+1]
-  DevBuf seg_state;   // u16 final_state[B]
-  DevBuf seg_arrays;  // generic chain kernels: per-segment tables (encode.hip: SegArrays)
-  DevBuf seq_bdesc;   // sequence stream: batch descriptors of the batch-sorted partition (encode.hip: SeqBatchDesc)
-  DevBuf seq_plan;    // segment plan of the sequence chains (encode.hip: SEGPLAN_WORDS) + entry states
-  DevBuf seq_fbuf;    // u16 [segments][1 << max_log] segment functions F: entry state -> exit state
-  DevBuf seq_cbuf;    // sequence stream: composed functions and entry states of the items of long chains (k_seq_compose)
-  DevBuf seq_cand;    // sequence stream: u16 cand0[segments][W] | cand[segments][W], candidates of the handed-over groups (encode.hip: SeqHandover)
-  DevBuf tile_bits;   // u32 [ptiles]
-  DevBuf tile_bit_base;  // u64 [ptiles+1]
+  DevBuf slot_of, keys, sorted_sym, out16, tile_hist, tile_base, group_sum, ctx_arrays, seg_state, seg_arrays;
+  DevBuf seq_bdesc, seq_plan, seq_fbuf, seq_cbuf, seq_cand, tile_bits, tile_bit_base, tile_runs, tile_sync;
   DevBuf dbg_enc16;   // timing experiments only (FQGPU_DEBUG_NO_ALIAS): enc16 apart from the keys, so that stale keys stay valid
-  DevBuf scan_tmp;    // u64 chunk sums for the scans
-  DevBuf tile_runs;   // tile-sorted path: uint2 [tiles][min(B, tile)] run list of every tile (encode.hip: enc_tile_sort.h)
-  DevBuf tile_sync;   // tile-sorted path: u64 status[tiles] | u32 tile counter, pad | u32 run_count[tiles]
 };
 FQ_SCRATCH_BUFS(EncScratch, FQ_B(EncScratch, slot_of), FQ_B(EncScratch, keys), FQ_B(EncScratch, sorted_sym), FQ_B(EncScratch, out16),
                 FQ_B(EncScratch, tile_hist), FQ_B(EncScratch, tile_base), FQ_B(EncScratch, group_sum), FQ_B(EncScratch, ctx_arrays),
                 FQ_B(EncScratch, seg_state), FQ_B(EncScratch, seg_arrays), FQ_B(EncScratch, seq_bdesc), FQ_B(EncScratch, seq_plan),
                 FQ_B(EncScratch, seq_fbuf), FQ_B(EncScratch, seq_cbuf), FQ_B(EncScratch, seq_cand), FQ_B(EncScratch, tile_bits),
-                FQ_B(EncScratch, tile_bit_base), FQ_B(EncScratch, dbg_enc16), FQ_B(EncScratch, scan_tmp), FQ_B(EncScratch, tile_runs),
-                FQ_B(EncScratch, tile_sync))
+                FQ_B(EncScratch, tile_bit_base), FQ_B(EncScratch, dbg_enc16), FQ_B(EncScratch, tile_runs), FQ_B(EncScratch, tile_sync))
 
 // One encode lane: everything a block needs while it is being coded, so that several
 // blocks can be in flight on one GPU (two HIP streams: sequence pipeline, quality pipeline).
@@ -203,6 +185,13 @@ struct EncLane {
   unsigned rscan_epoch = 0, rscan_tickets = 0;  // launches so far (24 bits used) / tickets handed out so far
   DevBuf scan_tmp;
   EncScratch enc[2];
+  // diagnostics (fqgpu_dblock_qual_segment_classes): where the lane's last encode left the classes of its quality segments
+  // and their number (in enc[1], set after its buffers are reserved), and that encode's stamp (fqgpu_ctx::encodes; 0: none)
+  const uint8_t *diag_cls = nullptr;
+  const uint32_t *diag_n_segs = nullptr;
+  unsigned long long diag_stamp = 0;
+  // whatever may move or overwrite enc[1] without being an encode (reserving ahead, set_lanes, fill_scratch) calls this first
+  void forget_diag() { diag_cls = nullptr; diag_n_segs = nullptr; diag_stamp = 0; }
 };
 FQ_SCRATCH_BUFS(EncLane, FQ_B(EncLane, rec_start), FQ_B(EncLane, n_cnt32), FQ_B(EncLane, n_off), FQ_B(EncLane, first_sym),
                 FQ_B(EncLane, tile_first), FQ_B(EncLane, rscan), FQ_B(EncLane, scan_tmp))
@@ -310,6 +299,7 @@ struct fqgpu_ctx {
   unsigned n_cus = 256;          // compute units of the device
   unsigned setfunc_wgs = 0;      // persistent workgroups of k_seq_setfunc (0 = default, see fqgpu_ctx_create)
   unsigned n_lanes = 0, next_lane = 0;  // n_lanes 0 = by block size: fq_lanes_for()
+  unsigned long long encodes = 0;       // encode launches so far: the stamp a lane and a block keep of their last one
   const void *recent[FQ_RECENT_BLOCKS] = {};  // the blocks coded last (compared, never followed: api.hip fq_next_lane)
   unsigned recent_at = 0;
   EncLane lanes[FQ_MAX_LANES];
@@ -381,10 +371,9 @@ struct fqgpu_dblock {
   // decode index (extension): device copy per stream, valid bytes, allocated bytes
   uint8_t *index[2] = {nullptr, nullptr};
   size_t index_bytes[2] = {0, 0}, index_cap[2] = {0, 0};
-  // diagnostics (fqgpu_dblock_qual_segment_classes): where the lane that coded this block last left the classes of its
-  // quality segments -- lane scratch, valid until that lane codes another block
-  const uint8_t *diag_cls = nullptr;
-  const uint32_t *diag_n_segs = nullptr;
+  // diagnostics (fqgpu_dblock_qual_segment_classes): the stamp of the block's last encode; lane home_lane of the owner holds
+  // its segment classes as long as that lane's stamp is the same
+  unsigned long long diag_stamp = 0;
 };
 
 // Decode index of one stream: header, then one snapshot per multiple of `stride` symbols.
@@ -443,8 +432,9 @@ int fq_seq_pow_ensure(hipStream_t st, DevTables &t, unsigned n_models, unsigned 
 // wait: event the lane's first kernel waits for (inputs arriving on another stream), or nullptr;
 // done: receives the stream on which the block's last kernel was launched (copies of the results
 // ordered behind the encode go there), may be nullptr
-int fq_encode_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned flags, hipEvent_t wait = nullptr,
-                     hipStream_t *done = nullptr, bool reserve_only = false);
+int fq_encode_launch(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned flags, hipEvent_t wait = nullptr, hipStream_t *done = nullptr);
+int fq_encode_reserve(fqgpu_ctx *ctx, const fqgpu_dblock *b);  // the scratch of a block of b's shape on the next lane in turn, nothing launched
+int fq_encode_init_device();  // once per handle, on its device: the dynamic-LDS limit of k_seq_setfunc
 int fq_probe_lds_atomic_order(hipStream_t st, bool *ordered);
 // Part of one block that holds both decode indexes (fqgpu_decode_chunk_range): stream s (0 = sequence) walks its strides
 // k_lo[s] .. k_hi[s] alone, with the kernels and the placement rule of a whole decode, and the N pass patches the records

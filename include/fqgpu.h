@@ -268,7 +268,10 @@ int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed_over, unsi
  * counts[0] transparent (a symbol with one table cell inside: the state behind it is known),
  * [1] anchored (a symbol with <= 64 cells: one walk per candidate), [2] uniform (S times one symbol:
  * a power of one transition), [3] opaque (the full entry-state -> exit-state function).  Reads the
- * scratch of the encode lane that coded the block: valid until that lane codes another block. */
+ * scratch of the encode lane that coded the block, so it answers only while that scratch still holds
+ * this block's last encode: FQGPU_E_ARG when b is not a block of ctx or was never encoded, when the
+ * lane has coded another block since, and after fqgpu_ctx_set_lanes, fqgpu_ctx_reserve or
+ * fqgpu_ctx_fill_scratch until b is encoded again. */
 int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]);
 /* diagnostics, for tests of "no result depends on what the scratch held before": waits for the handle (fqgpu_sync) and sets
  * every byte of every device scratch buffer the handle owns -- the encode lanes, the decode scratch, the device parser's,
