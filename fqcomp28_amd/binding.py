@@ -167,6 +167,14 @@ _PROTOS = {
                                        C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_tailtrim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                         C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_chunk_select_marked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_select_marked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                             C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "fqgpu_chunk_pair_names": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fqgpu_dblock_pair_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "fqgpu_read_id_len": (C.c_size_t, [C.c_void_p, C.c_size_t]),
     "fqgpu_probe_words": (C.c_size_t, [C.c_uint, C.c_uint]),
     "fqgpu_probes_check": (C.c_int, [C.c_void_p]),
     "fqgpu_chunk_probe": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -436,6 +444,30 @@ def _tail_call(fn, front, adapter, tail, trim, flt, n_recs, want_win=True, want_
                 win=win, places=places)
 
 
+MARKED_REPORT_NAMES = TAIL_REPORT_NAMES + ("dropped_unmarked",)
+DROPPED_UNMARKED = 20
+NO_MISMATCH = (1 << 64) - 1
+
+
+def _marked_call(fn, front, adapter, tail, trim, flt, first, end, mark=None, want_win=True, want_places=True, **kw):
+    """A device marked call (fqgpu_*_select_marked) over the records [first, end) -> dict(rc, out, out_len, report, keep, win,
+    places) as _tail_call, everything relative to `first`; mark: None (NULL), or uint8 of (end - first + 7) // 8 bytes in the
+    keep bits' layout; adapter, tail, trim, flt None: NULL"""
+    n = max(end - first, 0)
+    win = np.zeros(n, dtype=np.uint32) if want_win else None
+    places = np.zeros((n, 4), dtype=np.uint16) if want_places else None
+    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.uint8)
+    call = lambda *a: fn(*a[:len(front) + 4], first, end, _p(mark), *a[len(front) + 4:])  # noqa: E731
+    return dict(_select_call(call, front, (adapter, tail, trim, flt), n, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
+                win=win, places=places)
+
+
+def read_id_len(header_line):
+    """fqgpu_read_id_len (host only): the length of the read id of a header line (bytes, with its '@')"""
+    line = np.frombuffer(bytes(header_line), dtype=np.uint8)
+    return lib().fqgpu_read_id_len(_p(line) if line.size else None, line.size)
+
+
 PROBES_MAX = 16
 PROBE_HEAD_WORDS, PROBE_TABLE_HEAD_WORDS = 8, 8
 PROBE_WINDOW_ROWS = 320  # rows the device sums on chip (select.hip); a hit between this and `positions` is added one by one
@@ -628,6 +660,19 @@ class DBlock:
         dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
         return _tail_call(lib().fqgpu_dblock_tailtrim, (self.ctx.h, self.h), adapter, tail, trim, flt, self.n_recs, **kw)
 
+    def select_marked(self, first, end, mark=None, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_dblock_select_marked: the records [first, end) of the raw block judged as tailtrim judges them, a record whose
+        bit in `mark` is 0 dropped whatever its verdict -> dict(rc, out, out_len, report, keep, win, places), all relative to
+        `first`; see _marked_call"""
+        return _marked_call(lib().fqgpu_dblock_select_marked, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, **kw)
+
+    def pair_names(self, first, other, other_first, count):
+        """fqgpu_dblock_pair_names: the read ids of this block's records first + i against `other`'s other_first + i, i < count
+        -> (rc, mismatch): the first i whose ids differ, None when there is none"""
+        m = C.c_size_t(7)
+        rc = lib().fqgpu_dblock_pair_names(self.ctx.h, self.h, first, other.h if other is not None else None, other_first, count, C.byref(m))
+        return rc, None if m.value == NO_MISMATCH else m.value
+
     def status(self):
         a, b, c, d = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         rc = lib().fqgpu_dblock_status(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d))
@@ -772,6 +817,18 @@ class Context:
         poly-X tail and the sliding-window cut of `tail` taken, trimmed by `trim` and then judged by `flt`, where chunk_clip is
         valid -> dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
         return _tail_call(lib().fqgpu_chunk_tailtrim, (self.h,), adapter, tail, trim, flt, n_recs, **kw)
+
+    def chunk_select_marked(self, first, end, mark=None, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_chunk_select_marked: the records [first, end) of the chunk on the staging block, where chunk_tailtrim is
+        valid, against `mark` -> dict(rc, out, out_len, report, keep, win, places); see _marked_call"""
+        return _marked_call(lib().fqgpu_chunk_select_marked, (self.h,), adapter, tail, trim, flt, first, end, mark, **kw)
+
+    def chunk_pair_names(self, first, other, other_first, count):
+        """fqgpu_chunk_pair_names: the read ids of the chunk staged here against those of the chunk staged on the Context
+        `other` -> (rc, mismatch) as DBlock.pair_names"""
+        m = C.c_size_t(7)
+        rc = lib().fqgpu_chunk_pair_names(self.h, first, other.h if other is not None else None, other_first, count, C.byref(m))
+        return rc, None if m.value == NO_MISMATCH else m.value
 
     def set_check_only(self, on=True):
         """fqgpu_ctx_set_check_only: decode_chunk(want_raw=False) decodes and judges, nothing of the chunk comes back"""

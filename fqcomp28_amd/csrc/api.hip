@@ -1880,3 +1880,71 @@ extern "C" int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, cons
                                      uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
   return select_call(ctx, b, false, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out, true, x, places_out);
 }
+
+// ------------------------------------------------------------------ a record range of a chunk in HBM against a mark, and the read ids of two chunks (select.hip)
+// The two marked calls (b, staged: as stats_call): the tail calls' front -- no device is said before any argument is looked
+// at, *out_len and the report are zeroed before anything else can fail -- with every one of a, x, t, f allowed to be NULL, and
+// the range [first, end) of the block's record table handed to fq_select_chunk as a table of its own.
+static int marked_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                       const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
+                       uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  if (out_len) *out_len = 0;
+  if (report) memset(report, 0, FQGPU_TAIL_REPORT_WORDS * sizeof(uint64_t));
+  const fqgpu_trim none = {0u, 0u, 0u, 0u, FQGPU_FILTER_NONE, {0u, 0u, 0u}};
+  const fqgpu_tail off = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
+  if (x && fqgpu_tail_check(x) != FQGPU_OK) return FQGPU_E_ARG;
+  if (!x || !(x->poly_bases || x->window_len)) x = places_out ? &off : nullptr;  // (as the tail calls: the clip's kernels, unless the places are asked for)
+  if (!t) t = &none;
+  if (!ctx || !out_len || !report || (a && fqgpu_adapter_check(a) != FQGPU_OK) || fqgpu_trim_check(t) != FQGPU_OK ||
+      (f && fqgpu_filter_check(f) != FQGPU_OK))
+    return FQGPU_E_ARG;
+  if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
+  if (first >= end || end > b->n_recs) return FQGPU_E_ARG;
+  const FqSelectMark m = {first != 0, mark_in};
+  return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs + first, end - first, a, t, f ? f : &all, out, out_cap, out_len, report,
+                         keep_out, win_out, x, places_out, &m);
+}
+
+extern "C" int fqgpu_chunk_select_marked(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                                         size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
+                                         uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
+  return marked_call(ctx, nullptr, true, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out);
+}
+
+extern "C" int fqgpu_dblock_select_marked(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                                          const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap,
+                                          size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
+  return marked_call(ctx, b, false, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out);
+}
+
+// The two id calls: both chunks at rest -- every stream of both handles, and of a block's owner, is waited for --, then one
+// kernel on ctx's stream.
+static int names_call(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
+                      size_t *mismatch) {
+  if (count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs || count > bb->n_recs - first_b)
+    return FQGPU_E_ARG;
+  return fq_pair_names(ctx, ctx->stream, ba->raw, ba->raw_len, ba->recs + first_a, first_a != 0, bb->raw, bb->raw_len, bb->recs + first_b,
+                       first_b != 0, count, mismatch);
+}
+
+extern "C" int fqgpu_chunk_pair_names(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, size_t *mismatch) {
+  if (mismatch) *mismatch = (size_t)-1;
+  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
+  if (!ctx_a || !ctx_b || !mismatch || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
+  const fqgpu_dblock *ba = nullptr, *bb = nullptr;
+  int rc;
+  if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
+  return names_call(ctx_a, ba, first_a, bb, first_b, count, mismatch);
+}
+
+extern "C" int fqgpu_dblock_pair_names(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
+                                       size_t count, size_t *mismatch) {
+  if (mismatch) *mismatch = (size_t)-1;
+  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
+  if (!ctx || !mismatch) return FQGPU_E_ARG;
+  int rc;
+  if ((rc = settled_block(ctx, ba)) || (rc = settled_block(ctx, bb))) return rc;
+  return names_call(ctx, ba, first_a, bb, first_b, count, mismatch);
+}

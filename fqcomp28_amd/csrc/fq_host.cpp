@@ -159,6 +159,16 @@ extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   return FQGPU_OK;
 }
 
+// The read id of a header line (select.hip compares them, k_pair_names): the bytes behind the line's first byte, the '@', up
+// to the first ' ', '\t' or '\n' or the end of what is given, without a "/1" or "/2" at their end.
+extern "C" size_t fqgpu_read_id_len(const uint8_t *header_line, size_t len) {
+  if (!header_line || len < 2) return 0;
+  size_t n = 0;
+  while (1 + n < len && header_line[1 + n] != ' ' && header_line[1 + n] != '\t' && header_line[1 + n] != '\n') n++;
+  if (n >= 2 && header_line[n - 1] == '/' && (header_line[n] == '1' || header_line[n] == '2')) n -= 2;
+  return n;
+}
+
 namespace {
 struct SplitMix {
   uint64_t s;

@@ -266,16 +266,19 @@ FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs)
 // (four uint16_t: k_tail_find writes them, the judge reads them), the keep bits, the offsets of the kept records
 // in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
 // filter and trim calls: each is waited for before it returns.  A probe call (adapter content) has two buffers of its own
-// here: its u64 result tables and -- when asked for -- the records' places, n uint16_t each.
+// here: its u64 result tables and -- when asked for -- the records' places, n uint16_t each.  A marked call
+// (fqgpu_chunk_select_marked) has one: the caller's mark, a u64 word per 64 records.
 struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   DevBuf probe_out, probe_places;
+  DevBuf mark;
   void *host = nullptr;
   void release_host();
 };
 FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, hstart), FQ_B(SelectScratch, win), FQ_B(SelectScratch, clip),
                 FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
-                FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places))
+                FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places),
+                FQ_B(SelectScratch, mark))
 
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
@@ -481,11 +484,23 @@ int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
 // (select.hip; both have passed their checks), on st, waited for: report (FQGPU_TRIM_REPORT_WORDS, which are
 // FQGPU_FILTER_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
 // into out.  x (nullptr: none; one needs a trim and has passed its check): the tail trims between the clip and the trim; the
-// report then has FQGPU_TAIL_REPORT_WORDS words and places_out (nullptr: not wanted) receives a0, a1, e, e2 of every record
+// report then has FQGPU_TAIL_REPORT_WORDS words and places_out (nullptr: not wanted) receives a0, a1, e, e2 of every record.
+// m (nullptr: none; one needs a trim): recs_dev points at the first record of a RANGE of the chunk's table and n_recs is the
+// range's count -- every output is relative to it -- and the range is judged against a mark; the report is a tail's with word 20
+struct FqSelectMark {
+  bool prev;            // the range's first record is not the table's first: recs_dev[-1] is the record in front of it
+  const uint8_t *mark;  // host: (n_recs + 7) / 8 bytes in keep_out's layout; nullptr: every record is marked
+};
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                     uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x = nullptr,
-                    uint16_t *places_out = nullptr);
+                    uint16_t *places_out = nullptr, const FqSelectMark *m = nullptr);
+
+// The read ids (include/fqgpu.h) of the records recs_a[i] and recs_b[i], i < count, of two chunks in HBM on ctx's device, both
+// at rest (select.hip), on st, waited for; prev_*: the table has a record in front of recs_*[0].  *mismatch: the smallest i
+// whose ids differ, (size_t)-1 when there is none.  FQGPU_E_ARG: count 0, or a header line outside its chunk
+int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, bool prev_a,
+                  const uint8_t *raw_b, size_t raw_len_b, const fqgpu_rec *recs_b, bool prev_b, size_t count, size_t *mismatch);
 
 // Adapter content of a chunk in HBM (select.hip; the probe set has passed its check, positions is 1 .. 65535), on st, waited
 // for: out[0, fqgpu_probe_words(p->n, positions)) on the host and -- places_out != nullptr -- p->n places per record

@@ -17,6 +17,7 @@
 #include <chrono>
 #include <condition_variable>
 #include <cstdlib>
+#include <cstring>
 #include <exception>
 #include <functional>
 #include <mutex>
@@ -820,6 +821,212 @@ inline FarmReport processArchiveClipped(const path_t &archive_path, const path_t
 inline FarmReport processArchiveTailTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter *adapter,
                                             const fqgpu_tail &tail, const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
   return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveTailTrimmed", adapter, &tail);
+}
+
+namespace detail {
+/** Bits [from, from + count) of src -- bit i & 7 of byte i >> 3, the keep bits' layout -- as `count` bits from bit 0 of dst,
+ *  which has (count + 7) / 8 bytes; the bits of its last byte behind them are zero. */
+inline void sliceBits(const uint8_t *src, std::size_t from, std::size_t count, uint8_t *dst) {
+  std::memset(dst, 0, (count + 7) / 8);
+  for (std::size_t i = 0; i < count; ++i)
+    if ((src[(from + i) >> 3] >> ((from + i) & 7)) & 1u) dst[i >> 3] |= static_cast<uint8_t>(1u << (i & 7));
+}
+/** The other way: `count` bits from bit 0 of src become the bits [at, at + count) of dst; its other bits stay. */
+inline void placeBits(const uint8_t *src, std::size_t count, uint8_t *dst, std::size_t at) {
+  for (std::size_t i = 0; i < count; ++i) {
+    const uint8_t bit = static_cast<uint8_t>(1u << ((at + i) & 7));
+    if ((src[i >> 3] >> (i & 7)) & 1u) dst[(at + i) >> 3] |= bit;
+    else dst[(at + i) >> 3] &= static_cast<uint8_t>(~bit);
+  }
+}
+}  // namespace detail
+
+/** Extension: a part of a paired restore's work unit -- the mates of the records [at, at + end - first) of the unit are the
+ *  records [first, end) of block `block` of archive 2 */
+struct MatePiece {
+  std::size_t block = 0, first = 0, end = 0, at = 0;
+};
+/** The mates of a unit that holds the records [a, b) of archive 1, as pieces of the blocks of archive 2 (counts2: its
+ *  records per block) in order: planRecordRange with every piece's place in the unit.  Throws as planRecordRange does. */
+inline std::vector<MatePiece> planMateUnit(const std::vector<uint32_t> &counts2, std::size_t a, std::size_t b) {
+  std::vector<std::size_t> start2(counts2.size() + 1, 0);
+  for (std::size_t k = 0; k < counts2.size(); ++k) start2[k + 1] = start2[k] + counts2[k];
+  std::vector<MatePiece> pieces;
+  for (const RangePiece &pc : planRecordRange(counts2, a, b)) pieces.push_back(MatePiece{pc.block, pc.first, pc.end, start2[pc.block] + pc.first - a});
+  return pieces;
+}
+
+/** Extension: what a paired restore did -- a FarmReport per mate (in: what was written; trim: the chunks' marked reports,
+ *  FQGPU_TAIL_REPORT_WORDS words added word by word; index, sums and verified as in a single restore, mate 2's counted per
+ *  DECODE) and the pairs: both mates kept, dropped because mate 1 alone failed, mate 2 alone, both.  decodes2: chunk decodes
+ *  of archive 2 (its number of chunks when the two archives are cut at the same records). */
+struct PairedReport {
+  FarmReport mate1, mate2;
+  uint64_t pairs = 0, kept = 0, dropped_mate1_only = 0, dropped_mate2_only = 0, dropped_both = 0;
+  std::size_t blocks1 = 0, blocks2 = 0, decodes2 = 0;
+};
+
+/** Extension: `d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq>` -- two archives whose records are mates restored in
+ *  step: record i of both outputs are mates, and a pair is written only if BOTH mates pass.  Every selection step of
+ *  processArchiveTailTrimmed applies to both mates (adapter1 to mate 1, adapter2 to mate 2; each of the five may be nullptr:
+ *  with all of them nullptr both files are restored whole and only the read ids are checked).
+ *  The two archives need the same number of records and nothing else: their chunks are cut by bytes, so a chunk of archive 1
+ *  -- the work unit, handed out in order -- holds the records [A, B) and planMateUnit(counts2, A, B) names the one to
+ *  three chunks of archive 2 that hold their mates.  A worker owns one workspace per archive, both on its device, and needs
+ *  no other worker: (1) chunk k of archive 1 decoded check-only, its digest taken; (2) a size query over it for its keep
+ *  bits K1; (3) for every piece (j, lo, hi): chunk j of archive 2 decoded check-only, its digest taken, the read ids of the
+ *  piece compared with their mates' (fqgpu_chunk_pair_names: a mismatch ends the run), the piece selected against the
+ *  matching slice of K1 -- its output is appended to the unit's piece of file 2, its keep bits to K; (4) chunk k selected
+ *  against K; (5) both pieces go to their OrderedPieceWriter as piece k.  A chunk of archive 2 that straddles a boundary of
+ *  archive 1 is decoded by two workers (rep.decodes2 counts); with archives cut at the same records every chunk is decoded
+ *  once.  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
+ *  nor a `.part` file.  Throws before any output is opened when the archives' record totals differ. */
+inline PairedReport processArchivePaired(const path_t &archive1_path, const path_t &out1, const path_t &archive2_path, const path_t &out2,
+                                         const fqgpu_adapter *adapter1, const fqgpu_adapter *adapter2, const fqgpu_tail *tail,
+                                         const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
+  const std::string name("processArchivePaired");
+  if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
+  for (const fqgpu_adapter *a : {adapter1, adapter2})
+    if (a && fqgpu_adapter_check(a) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
+  if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
+  if (filter && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+  if (set.devices.empty()) throw std::invalid_argument(name + ": no device");
+  Archive archive1(archive1_path), archive2(archive2_path);
+  const std::vector<uint32_t> counts1 = archive1.recordCounts(), counts2 = archive2.recordCounts();
+  const std::size_t n1 = counts1.size(), n2 = counts2.size();
+  std::vector<std::size_t> start1(n1 + 1, 0);  // the first record of every chunk, numbered across the archive
+  for (std::size_t k = 0; k < n1; ++k) start1[k + 1] = start1[k] + counts1[k];
+  std::size_t total2 = 0;
+  for (const uint32_t c : counts2) total2 += c;
+  if (start1[n1] != total2)
+    throw std::runtime_error(name + ": " + archive1_path.string() + " holds " + std::to_string(start1[n1]) + " records, " +
+                             archive2_path.string() + " " + std::to_string(total2) + ": not the two files of one paired run");
+  std::unique_ptr<DecodeIndexFile> sidecar1 = detail::openDecodeIndex(archive1_path), sidecar2 = detail::openDecodeIndex(archive2_path);
+  detail::ChunkVerifier verifier1(archive1_path, n1, false), verifier2(archive2_path, n2, false);
+  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n1, 1))));
+  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp1(T), wksp2(T);
+  detail::runWorkers(T, [&](unsigned t) {
+    const int device = set.devices[t % set.devices.size()];
+    wksp1[t] = std::make_unique<DecompressionWorkspace>(&archive1.meta(), device);
+    wksp2[t] = std::make_unique<DecompressionWorkspace>(&archive2.meta(), device);
+    wksp1[t]->setVerify(verifier1.on());
+    wksp2[t]->setVerify(verifier2.on());
+  });
+  const auto t0 = std::chrono::steady_clock::now();
+  OrderedPieceWriter writer1(out1, n1), writer2(out2, n1);
+  constexpr unsigned W = FQGPU_TAIL_REPORT_WORDS;
+  std::vector<InputStats> istats1(T), istats2(T);
+  std::vector<std::vector<uint64_t>> reports1(T, std::vector<uint64_t>(W, 0)), reports2(T, std::vector<uint64_t>(W, 0));
+  PairedReport rep;
+  rep.mate1.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
+  rep.mate2.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
+  std::atomic<std::size_t> next{0}, used1{0}, used_bytes1{0}, used2{0}, used_bytes2{0}, decodes2{0};
+  std::atomic<bool> stopped{false};
+  detail::runWorkers(T, [&](unsigned t) {
+    CompressedBuffersSrc cbs1, cbs2;
+    FastqChunk piece1, piece2;
+    std::vector<uint8_t> k1, k, mark, keep;
+    uint64_t report[W];
+    DecompressionWorkspace &w1 = *wksp1[t], &w2 = *wksp2[t];
+    for (;;) {
+      const std::size_t unit = next.fetch_add(1);  // (in order: whoever waits in a writer waits for units already taken)
+      if (stopped.load() || unit >= n1) break;
+      StageClock clk;
+      const std::size_t A = start1[unit], n = counts1[unit];
+      piece1.clear();
+      piece2.clear();
+      piece1.idx = piece2.idx = static_cast<unsigned>(unit);
+      std::size_t len1 = 0, len2 = 0;
+      if (n) {
+        archive1.readBlockAt(unit, cbs1);
+        if (sidecar1 && sidecar1->get(cbs1)) {
+          used1.fetch_add(1);
+          used_bytes1.fetch_add(cbs1.decode_index[0].size() + cbs1.decode_index[1].size());
+        }
+        clk.lap("read");
+        w1.stagePairedChunk(cbs1);
+        verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
+        k1.assign((n + 7) / 8, 0);
+        (void)w1.selectMarked(adapter1, tail, trim, filter, 0, n, nullptr, nullptr, 0, report, k1.data());
+        clk.lap("mate 1");
+        k.assign((n + 7) / 8, 0);
+        for (const MatePiece &pc : planMateUnit(counts2, A, A + n)) {
+          archive2.readBlockAt(pc.block, cbs2);
+          if (sidecar2 && sidecar2->get(cbs2)) {
+            used2.fetch_add(1);
+            used_bytes2.fetch_add(cbs2.decode_index[0].size() + cbs2.decode_index[1].size());
+          }
+          w2.stagePairedChunk(cbs2);
+          verifier2.check(cbs2, w2.lastDigest());
+          decodes2.fetch_add(1);
+          rep.mate2.blocks_per_worker[t]++;
+          const std::size_t count = pc.end - pc.first, at = pc.at;
+          const std::size_t differs = w1.pairNames(at, w2, pc.first, count);
+          if (differs != static_cast<std::size_t>(-1))
+            throw std::runtime_error(name + ": record " + std::to_string(A + at + differs) + ": the read ids of the two mates differ (chunk " +
+                                     std::to_string(unit) + " of " + archive1_path.string() + ", chunk " + std::to_string(pc.block) + " of " +
+                                     archive2_path.string() + ")");
+          mark.resize((count + 7) / 8);
+          keep.assign((count + 7) / 8, 0);
+          detail::sliceBits(k1.data(), at, count, mark.data());
+          piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
+          len2 += w2.selectMarked(adapter2, tail, trim, filter, pc.first, pc.end, mark.data(),
+                                  reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2, cbs2.original_size.total, report, keep.data());
+          for (unsigned i = 0; i < W; ++i) reports2[t][i] += report[i];
+          detail::placeBits(keep.data(), count, k.data(), at);
+        }
+        clk.lap("mate 2");
+        piece1.raw_data.resize(cbs1.original_size.total);
+        len1 = w1.selectMarked(adapter1, tail, trim, filter, 0, n, k.data(), reinterpret_cast<uint8_t *>(piece1.raw_data.data()),
+                               piece1.raw_data.size(), report, nullptr);
+        for (unsigned i = 0; i < W; ++i) reports1[t][i] += report[i];
+        istats1[t].n_records += static_cast<std::size_t>(report[1]);
+        istats2[t].n_records += static_cast<std::size_t>(report[1]);
+        clk.lap("gather 1");
+      }
+      piece1.raw_data.resize(len1);
+      piece2.raw_data.resize(len2);
+      istats1[t].raw += len1;
+      istats2[t].raw += len2;
+      rep.mate1.blocks_per_worker[t]++;
+      try {
+        writer1.writePiece(unit, piece1.raw_data.data(), len1);
+        writer2.writePiece(unit, piece2.raw_data.data(), len2);
+      } catch (const OrderedPieceWriter::Aborted &) {
+        break;  // (another worker has failed and says why)
+      }
+      clk.lap("write");
+      clk.done(static_cast<unsigned>(unit));
+    }
+  }, [&] { stopped.store(true); writer1.abort(); writer2.abort(); });
+  writer1.flush();
+  writer2.flush();
+  rep.mate1.seconds = rep.mate2.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  rep.mate1.trim.assign(W, 0);
+  rep.mate2.trim.assign(W, 0);
+  for (unsigned t = 0; t < T; ++t) {
+    rep.mate1.in += istats1[t];
+    rep.mate2.in += istats2[t];
+    for (unsigned i = 0; i < W; ++i) {
+      rep.mate1.trim[i] += reports1[t][i];
+      rep.mate2.trim[i] += reports2[t][i];
+    }
+  }
+  rep.mate1.indexed_blocks = used1.load();
+  rep.mate1.index_bytes = used_bytes1.load();
+  rep.mate2.indexed_blocks = used2.load();
+  rep.mate2.index_bytes = used_bytes2.load();
+  verifier1.report(rep.mate1);
+  verifier2.report(rep.mate2);
+  rep.blocks1 = n1;
+  rep.blocks2 = n2;
+  rep.decodes2 = decodes2.load();
+  rep.pairs = start1[n1];
+  rep.kept = rep.mate1.trim[1];
+  rep.dropped_mate1_only = rep.mate2.trim[20];  // mate 2 passes, its mark -- mate 1's verdict -- says no
+  rep.dropped_mate2_only = rep.mate1.trim[20];
+  rep.dropped_both = rep.pairs - rep.kept - rep.dropped_mate1_only - rep.dropped_mate2_only;
+  return rep;
 }
 
 namespace detail {

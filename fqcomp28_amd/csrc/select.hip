@@ -59,6 +59,13 @@
 // wave per kept record, as k_crc_canon_write): a correctness path, kept because the five-piece form takes twice its time
 // there.
 //
+// A record RANGE and a MARK (fqgpu_chunk_select_marked, fqgpu_dblock_select_marked: a paired restore's selection).  The range
+// is these kernels over recs + first and end - first -- the judge's argument `prev` gives the range's first record its header
+// line --, every scratch array and every output then the range's.  k_select_mark, between the judge and the scan, ANDs the
+// caller's mark into the keep words, takes a record that flips out of the kept sizes and the kept counters and counts it
+// in report word 20.  k_pair_names compares the read ids of two chunks' records (fqgpu_chunk_pair_names): eight lanes to a
+// pair, both ids loaded from wherever they start, one atomicMin for the first pair that differs.
+//
 // All global stores are ordinary vector stores from plain C++.
 #include "fqgpu_internal.h"
 
@@ -917,7 +924,8 @@ k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const f
 
 // TRIM: the reads are trimmed by t, the windows go to win; without, t and win are not looked at.  STEP0 (with TRIM): what
 // stands in front of the trim's steps.  SEL_CLIP: clip[r] stands for the read's length in the trim's steps 1 to 4
-// (k_adapter_find has written it, and has judged the sequence line).  SEL_TAIL: k_tail_find has left a0, a1, e, e2 in
+// (k_adapter_find has written it, and has judged the sequence line).  prev != 0: recs is not the front of the chunk's table
+// (fqgpu_chunk_select_marked's range) and recs[-1] is the record in front of its first.  SEL_TAIL: k_tail_find has left a0, a1, e, e2 in
 // places[r]; the walks run over [min(cut_front, e2), e2) -- which is [f, e2), since f = min(cut_front, a1) and
 // f <= e2 <= a1 -- and cut_tail, which is in e already, is not applied again.
 constexpr unsigned SEL_PLAIN = 0, SEL_CLIP = 1, SEL_TAIL = 2;
@@ -926,7 +934,7 @@ __global__ void __launch_bounds__(SEL_THREADS)
 k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
                const fqgpu_trim t, const fqgpu_filter f, uint32_t *__restrict__ ksize, uint32_t *__restrict__ hstart,
                uint32_t *__restrict__ win, unsigned long long *__restrict__ keep, SelectResult *__restrict__ res,
-               const uint16_t *__restrict__ clip, const uint2 *__restrict__ places) {
+               const uint16_t *__restrict__ clip, const uint2 *__restrict__ places, const unsigned prev) {
   static_assert(TRIM || STEP0 == SEL_PLAIN, "a clip and a tail trim stand in front of a trim's steps");
   static_assert(STEP0 <= SEL_TAIL, "plain, clip or tail");
   constexpr bool CLIP = STEP0 != SEL_PLAIN;  // the trim's steps see another length than the read's
@@ -943,9 +951,10 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   const bool have = r < n_recs;
   fqgpu_rec mine = {0u, 0u, 0u};
   if (have) mine = recs[r];
-  // the start of the record's header line: behind the record in front (its entry sits in the lane in front)
+  // the start of the record's header line: behind the record in front (its entry sits in the lane in front; prev: the table
+  // is a range of a chunk's and its first record has one in front of it as well)
   unsigned h0 = __shfl_up(mine.qual_off + mine.len + 1u, 1);
-  if (lane == 0) h0 = have && r ? recs[r - 1].qual_off + recs[r - 1].len + 1u : 0u;
+  if (lane == 0) h0 = have && (r || prev) ? recs[(long long)r - 1].qual_off + recs[(long long)r - 1].len + 1u : 0u;
   const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len &&
                   (unsigned long long)mine.qual_off + mine.len <= raw_len;
   bool bad = have && !ok;
@@ -1344,6 +1353,170 @@ k_select_gather_records(const uint8_t *__restrict__ raw, const fqgpu_rec *__rest
   }
 }
 
+// ---- a record range and a mark (include/fqgpu.h, fqgpu_chunk_select_marked).  The range needs no kernel of its own: every
+// kernel above indexes by a record table and a count, and takes recs + first and end - first; the judge's `prev` gives the
+// range's first record its header line.  The mark is this kernel, between the judge and the scan: a wave per 64 records --
+// the judge's keep word --, keep &= mark, and for every record that flips ksize[r] = 0, so that the scan and the gather
+// never see it.  What the flipped records had added to n_kept, bases_kept and bytes_kept is summed over the wave by
+// shuffles, over the workgroup in LDS, and taken back with one atomic per counter and workgroup; the same count goes to
+// word 20.  The judge leaves the keep bits behind the table's end zero, so mark bits there change nothing.
+constexpr unsigned R_UNMARKED = 20;
+__global__ void __launch_bounds__(SEL_THREADS)
+k_select_mark(const unsigned long long *__restrict__ mark, unsigned n_recs, uint32_t *__restrict__ ksize, const uint32_t *__restrict__ win,
+              unsigned long long *__restrict__ keep, SelectResult *__restrict__ res) {
+  __shared__ unsigned wg_n, wg_bases;
+  __shared__ unsigned long long wg_bytes;
+  if (threadIdx.x == 0) {
+    wg_n = 0;
+    wg_bases = 0;
+    wg_bytes = 0;
+  }
+  __syncthreads();
+  const unsigned lane = fq_lane();
+  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+  if (r0 < n_recs) {  // (uniform)
+    const unsigned long long kw = keep[r0 / 64], gone = kw & ~mark[r0 / 64];
+    if (gone) {  // (uniform)
+      unsigned bases = 0;  // (64 records of at most 65535 bases)
+      unsigned long long bytes = 0;
+      if ((gone >> lane) & 1ull) {
+        bytes = ksize[r0 + lane];
+        bases = win[r0 + lane] >> 16;
+        ksize[r0 + lane] = 0;
+      }
+#pragma unroll
+      for (int d = 32; d > 0; d >>= 1) {
+        bases += __shfl_xor(bases, d);
+        bytes += __shfl_xor(bytes, d);
+      }
+      if (lane == 0) {
+        keep[r0 / 64] = kw & ~gone;
+        atomicAdd(&wg_n, (unsigned)__popcll(gone));
+        atomicAdd(&wg_bases, bases);
+        atomicAdd(&wg_bytes, bytes);
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 4 && wg_n) {  // (a subtraction is the addition of the two's complement)
+    const unsigned long long n = wg_n;
+    if (threadIdx.x == 0) atomicAdd(&res->w[R_KEPT], 0ull - n);
+    if (threadIdx.x == 1) atomicAdd(&res->w[R_BASES_KEPT], 0ull - wg_bases);
+    if (threadIdx.x == 2) atomicAdd(&res->w[R_BYTES_KEPT], 0ull - wg_bytes);
+    if (threadIdx.x == 3) atomicAdd(&res->w[R_UNMARKED], n);
+  }
+}
+
+// ---- the read ids of two chunks compared (include/fqgpu.h, fqgpu_chunk_pair_names)
+constexpr unsigned PAIR_THREADS = 256;
+constexpr unsigned PAIR_STEP_BYTES = SEL_GROUP_LANES * 16;  // bytes of an id a pair's eight lanes hold at a time
+struct PairSide {
+  const uint8_t *raw;
+  unsigned long long raw_len;
+  const fqgpu_rec *recs;  // the first record of the range
+  unsigned prev;          // it has a record in front of it in its table
+};
+// a record's header line: the first byte of its id (behind the '@'), the bytes from there to the line's '\n'
+struct PairLine {
+  long long id0;
+  unsigned cap;
+  bool ok;  // the line has its '@' and its '\n' and lies inside the chunk
+};
+__device__ __forceinline__ PairLine pair_line(const PairSide &s, unsigned long long i, bool have) {
+  PairLine l = {0, 0u, true};
+  if (!have) return l;
+  const fqgpu_rec rec = s.recs[i];
+  unsigned long long h0 = 0;
+  if (i || s.prev) {
+    const fqgpu_rec before = s.recs[(long long)i - 1];
+    h0 = (unsigned long long)before.qual_off + before.len + 1ull;
+  }
+  l.ok = h0 + 2ull <= rec.seq_off && rec.seq_off <= s.raw_len;
+  l.id0 = (long long)h0 + 1;
+  l.cap = l.ok ? (unsigned)(rec.seq_off - h0 - 2ull) : 0u;
+  return l;
+}
+// the sixteen bytes of an id from place c on; nothing is read from the line's '\n' on (a word reaches at most fifteen bytes
+// behind the '\n', where the sequence line stands, or the spare bytes every raw block has behind its chunk)
+__device__ __forceinline__ uint4 pair_word(const PairSide &s, const PairLine &l, unsigned c) {
+  if (c >= l.cap) return make_uint4(0, 0, 0, 0);
+  const SelU128 v = *reinterpret_cast<const SelU128 *>(s.raw + l.id0 + c);
+  return make_uint4(v.a, v.b, v.c, v.d);
+}
+// a bit for each byte of a word that ends an id: ' ', '\t' or '\n' (a byte >= 128 ends none: the compares see seven bits)
+__device__ __forceinline__ unsigned pair_ends(const uint4 v) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+  unsigned ends = 0;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const unsigned y = w[i] & ~SW_H;
+    ends |= (((sw_eq(y, ' ') | sw_eq(y, '\t') | sw_eq(y, '\n')) & ~w[i]) * CLIP_GATHER) >> 28 << (4 * i);
+  }
+  return ends;
+}
+// the id's length without a "/1" or "/2" at its end
+__device__ __forceinline__ unsigned pair_strip(const PairSide &s, const PairLine &l, unsigned e) {
+  if (e < 2u) return e;
+  const unsigned slash = s.raw[l.id0 + e - 2], mate = s.raw[l.id0 + e - 1];
+  return slash == '/' && (mate == '1' || mate == '2') ? e - 2u : e;
+}
+
+// *first_diff = min(*first_diff, i) for every i < count at which the read ids of A's record i and B's record i differ in
+// length or in a byte.  EIGHT LANES TO A PAIR, the judge's grouping: lane j of the eight holds the bytes [16 j, 16 j + 16)
+// of both ids, loaded from wherever the ids start, so that the two words of a lane stand for the same places and are
+// compared as they are; a header line of 30 to 80 bytes is then one load instruction per side whose eight addresses fall
+// into the one or two cache lines that hold the line, where a lane per pair would walk its line word by word, every load
+// instruction of the wave over 64 different lines and as many turns as the longest line of the 64 takes.  An id's end is
+// the first ' ', '\t' or '\n' (SWAR byte tests, a min-reduction over the eight lanes by shuffles), the line's own '\n' at
+// the latest; the two bytes in front of it decide on "/1" and "/2".  A line longer than 128 bytes takes more turns, every
+// lane of the wave the same number: a correctness path.  One atomicMin per wave that has a differing pair.
+__global__ void __launch_bounds__(PAIR_THREADS)
+k_pair_names(const PairSide A, const PairSide B, unsigned count, unsigned long long *__restrict__ first_diff, unsigned *__restrict__ bad) {
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1);
+  const unsigned long long i = ((unsigned long long)blockIdx.x * PAIR_THREADS + threadIdx.x) / SEL_GROUP_LANES;
+  const bool have = i < count;
+  const PairLine la = pair_line(A, i, have), lb = pair_line(B, i, have);
+  const bool fine = have && la.ok && lb.ok;
+  unsigned steps = max((max(la.cap, lb.cap) + PAIR_STEP_BYTES - 1) / PAIR_STEP_BYTES, 1u);
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+  steps = fq_uniform(steps);
+  const uint4 xa = pair_word(A, la, 16u * sub), xb = pair_word(B, lb, 16u * sub);
+  // the ids' ends
+  unsigned ea = la.cap, eb = lb.cap;
+  for (unsigned s = 0; s < steps; s++) {
+    const unsigned c = s * PAIR_STEP_BYTES + 16u * sub;
+    const unsigned fa = pair_ends(s ? pair_word(A, la, c) : xa) & sel_bits(0, (int)la.cap - (int)c);
+    const unsigned fb = pair_ends(s ? pair_word(B, lb, c) : xb) & sel_bits(0, (int)lb.cap - (int)c);
+    if (fa) ea = min(ea, c + (unsigned)__builtin_ctz(fa));
+    if (fb) eb = min(eb, c + (unsigned)__builtin_ctz(fb));
+  }
+#pragma unroll
+  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
+    ea = min(ea, (unsigned)__shfl_xor(ea, d));
+    eb = min(eb, (unsigned)__shfl_xor(eb, d));
+  }
+  if (fine) {
+    ea = pair_strip(A, la, ea);
+    eb = pair_strip(B, lb, eb);
+  }
+  // the bytes in front of them
+  unsigned differ = ea != eb;
+  for (unsigned s = 0; s < steps; s++) {
+    const unsigned c = s * PAIR_STEP_BYTES + 16u * sub;
+    const uint4 va = s ? pair_word(A, la, c) : xa, vb = s ? pair_word(B, lb, c) : xb;
+    const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
+    const int left = (int)min(ea, eb) - (int)c;  // the id's bytes from this word's first on
+#pragma unroll
+    for (int k = 0; k < 4; k++) differ |= ((wa[k] ^ wb[k]) & sw_mask(-4 * k, left - 4 * k)) != 0u;
+  }
+#pragma unroll
+  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) differ |= __shfl_xor(differ, d);
+  const unsigned long long found = __ballot(fine && differ);
+  if (found && lane == (unsigned)__builtin_ctzll(found)) atomicMin(first_diff, i);  // (the wave's pairs rise with its lanes)
+  if (__any(have && !fine) && lane == 0) *bad = 1u;  // (every writer stores the same value)
+}
+
 }  // namespace
 
 void SelectScratch::release_host() {
@@ -1357,30 +1530,37 @@ void SelectScratch::release_host() {
 // byte that cannot be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
 // x (nullptr: none; with one, t is a trim): the tail trims between the clip and the trim, k_tail_find in front of the judge;
 // the report then has FQGPU_TAIL_REPORT_WORDS words, and places_out (nullptr, or 4 uint16_t per record) receives a0, a1, e, e2.
+// m (nullptr: none; with one, t is a trim and the report a tail's): recs_dev is a range of the chunk's table -- m->prev: not
+// its front -- and m->mark (nullptr: none) the range's mark, k_select_mark behind the judge; word 20 is counted.
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
-                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x, uint16_t *places_out) {
-  const unsigned words = x ? FQGPU_TAIL_REPORT_WORDS : FQGPU_TRIM_REPORT_WORDS;
+                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x, uint16_t *places_out, const FqSelectMark *m) {
+  const unsigned words = x || m ? FQGPU_TAIL_REPORT_WORDS : FQGPU_TRIM_REPORT_WORDS;
   *out_len = 0;
   for (unsigned i = 0; i < words; i++) report[i] = 0;
   if (n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  if ((a || x) && !t) return FQGPU_E_ARG;
+  if ((a || x || m) && !t) return FQGPU_E_ARG;
   if (!n_recs) return FQGPU_OK;
   if (!t) win_out = nullptr;  // (a filter has no windows)
   if (!x) places_out = nullptr;
   SelectScratch &ss = ctx->select;
-  const char *const span = x ? "tailtrim" : a ? "clip" : t ? "trim" : "filter";
+  const char *const span = m ? "select_marked" : x ? "tailtrim" : a ? "clip" : t ? "trim" : "filter";
+  const uint8_t *const mark = m ? m->mark : nullptr;
   const unsigned R = (unsigned)n_recs;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
   int rc;
   if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
-      (a && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) ||
+      (a && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) || (mark && (rc = ss.mark.reserve(n_waves * 8))) ||
       (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
     return rc;
   if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
   const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
   uint32_t *const win = t ? ss.win.as<uint32_t>() : nullptr;
   FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
+  if (mark) {  // (its last word padded with zeros)
+    FQ_HIP(hipMemsetAsync(ss.mark.p, 0, n_waves * 8, st));
+    FQ_HIP(hipMemcpyAsync(ss.mark.p, mark, (n_recs + 7) / 8, hipMemcpyHostToDevice, st));
+  }
   fq_timer_span_begin(ctx, span, st);
   const dim3 judge_grid((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64)));
   if (a) {  // the adapter's bit planes: bit j of a plane is set iff A[j] is that base
@@ -1400,8 +1580,13 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
   hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
                      ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>(),
-                     a ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr);
+                     a ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr, m && m->prev ? 1u : 0u);
   FQ_HIP(hipGetLastError());
+  if (mark) {
+    hipLaunchKernelGGL(k_select_mark, judge_grid, dim3(SEL_THREADS), 0, st, ss.mark.as<unsigned long long>(), R, ss.ksize.as<uint32_t>(), win,
+                       ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>());
+    FQ_HIP(hipGetLastError());
+  }
   if (out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
     fq_timer_span_end(ctx, st);
     return rc;
@@ -1493,5 +1678,33 @@ int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
   out[2] = n;
   out[3] = P;
   out[4] = fq_probes_fingerprint(p);
+  return FQGPU_OK;
+}
+
+// The read ids of `count` records of two chunks on one device compared, on st (both chunks are at rest), waited for:
+// *mismatch = the first pair that differs, or (size_t)-1.  One kernel, one wait; the result word and its landing place are
+// ctx's selection result.  FQGPU_E_ARG: a record whose header line does not lie inside its chunk.
+int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, bool prev_a,
+                  const uint8_t *raw_b, size_t raw_len_b, const fqgpu_rec *recs_b, bool prev_b, size_t count, size_t *mismatch) {
+  *mismatch = (size_t)-1;
+  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  SelectScratch &ss = ctx->select;
+  if (const int rc = ss.res.reserve(sizeof(SelectResult))) return rc;
+  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
+  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
+  SelectResult *const dev = ss.res.as<SelectResult>();
+  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
+  FQ_HIP(hipMemsetAsync(dev, 0xFF, sizeof(unsigned long long), st));  // word 0: no pair so far
+  const PairSide A = {raw_a, (unsigned long long)raw_len_a, recs_a, prev_a ? 1u : 0u}, B = {raw_b, (unsigned long long)raw_len_b, recs_b, prev_b ? 1u : 0u};
+  const size_t per_wg = PAIR_THREADS / SEL_GROUP_LANES;
+  fq_timer_span_begin(ctx, "pair_names", st);
+  hipLaunchKernelGGL(k_pair_names, dim3((unsigned)((count + per_wg - 1) / per_wg)), dim3(PAIR_THREADS), 0, st, A, B, (unsigned)count, &dev->w[0],
+                     &dev->bad);
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipGetLastError());
+  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  if (res.bad) return FQGPU_E_ARG;
+  *mismatch = res.w[0] == ~0ull ? (size_t)-1 : (size_t)res.w[0];
   return FQGPU_OK;
 }

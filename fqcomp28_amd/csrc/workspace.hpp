@@ -700,6 +700,40 @@ public:
     decodeChunkSelected(piece, cbs, trim, filter, report, "decodeChunkTailTrimmed", adapter, &tail);
   }
 
+  /** Extension (paired restores, process.hpp: processArchivePaired): the three steps a worker makes a pair of chunks of.
+   *  stagePairedChunk decodes the chunk check-only, takes its digest for lastDigest() when setVerify is on and leaves it on
+   *  the handle's staging block (as decodeChunkFiltered does in front of its filter call); there is no host fallback.
+   *  selectMarked is fqgpu_chunk_select_marked on the chunk staged last: records [first, end) against `mark` (nullptr: none;
+   *  (end - first + 7) / 8 bytes), each of adapter, tail, trim and filter nullptr for "off"; out == nullptr asks for the
+   *  counters and the keep bits alone; -> the bytes written to out (at most out_cap: the chunk's recorded size is always
+   *  enough).  pairNames is fqgpu_chunk_pair_names: the read ids of this handle's staged records first + i against those of
+   *  `mate`'s mate_first + i, i < count -> the first i that differs, (size_t)-1 when none does.  A call the device refuses
+   *  throws std::runtime_error naming the chunk. */
+  void stagePairedChunk(CompressedBuffersSrc &cbs) {
+    StageClock clk;
+    stageChunk(cbs, "stagePairedChunk", &clk);
+    staged_idx_ = cbs.chunk_idx;
+    clk.done(cbs.chunk_idx);
+  }
+  std::size_t selectMarked(const fqgpu_adapter *adapter, const fqgpu_tail *tail, const fqgpu_trim *trim, const fqgpu_filter *filter,
+                           std::size_t first, std::size_t end, const uint8_t *mark, uint8_t *out, std::size_t out_cap, uint64_t *report,
+                           uint8_t *keep_out) {
+    std::size_t len = 0;
+    const int rc = fqgpu_chunk_select_marked(ctx_, adapter, tail, trim, filter, first, end, mark, out, out_cap, &len, report, keep_out, nullptr, nullptr);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("selectMarked: chunk " + std::to_string(staged_idx_) + ", records " + std::to_string(first) + ":" +
+                               std::to_string(end) + ": " + fqgpu_strerror(rc));
+    return len;
+  }
+  std::size_t pairNames(std::size_t first, DecompressionWorkspace &mate, std::size_t mate_first, std::size_t count) {
+    std::size_t mismatch = static_cast<std::size_t>(-1);
+    const int rc = fqgpu_chunk_pair_names(ctx_, first, mate.ctx_, mate_first, count, &mismatch);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("pairNames: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
+                               fqgpu_strerror(rc));
+    return mismatch;
+  }
+
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every
    *  misc stream is restored from its compressed twin to the size the container recorded; index.n_count /
    *  index.n_pos are set to the ends of the buffers (the decoder pops from there) */
@@ -735,11 +769,33 @@ private:
     if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
     if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
     if ((filter || !(trim || adapter || tail)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
-    ChunkArgs a;
-    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
-    clk.lap("misc");
     piece.clear();
     piece.idx = cbs.chunk_idx;
+    stageChunk(cbs, who, &clk);
+    piece.raw_data.resize(cbs.original_size.total);
+    uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
+    std::size_t len = 0;
+    const int src = tail    ? fqgpu_chunk_tailtrim(ctx_, adapter, tail, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr, nullptr)
+                    : adapter ? fqgpu_chunk_clip(ctx_, adapter, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
+                    : trim  ? fqgpu_chunk_trim(ctx_, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
+                         : fqgpu_chunk_filter(ctx_, filter, out, piece.raw_data.size(), &len, report, nullptr);
+    if (src != FQGPU_OK) throw refused("the " + step + ": " + fqgpu_strerror(src));
+    piece.raw_data.resize(len);
+    clk.lap(step.c_str());
+    clk.done(cbs.chunk_idx);
+  }
+
+  /** The chunk decoded check-only -- nothing of it comes back -- with the block's decode indexes when present, and its
+   *  digest taken (setVerify): it is left on the handle's staging block, where the fqgpu_chunk_* calls find it.  No host
+   *  fallback: a chunk the device refuses throws std::runtime_error naming the chunk and the record. */
+  void stageChunk(CompressedBuffersSrc &cbs, const char *who, StageClock *clk = nullptr) {
+    last_digest_ = {};
+    const auto refused = [&](const std::string &what) {
+      return std::runtime_error(std::string(who) + ": chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
+    };
+    ChunkArgs a;
+    if (!chunkArgs(cbs, a)) throw refused("header field streams do not match the format");
+    if (clk) clk->lap("misc");
     // the check-only mode is this call's alone: a workspace that restores whole chunks elsewhere keeps doing so
     struct CheckOnly {
       fqgpu_ctx *ctx;
@@ -756,19 +812,8 @@ private:
     if (rc != FQGPU_OK)
       throw refused(bad == static_cast<std::size_t>(-1) ? std::string("no record named: ") + fqgpu_strerror(rc)
                                                          : "record " + std::to_string(bad) + ": " + fqgpu_strerror(rc));
-    clk.lap("gpu");
+    if (clk) clk->lap("gpu");
     takeDigest();
-    piece.raw_data.resize(cbs.original_size.total);
-    uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
-    std::size_t len = 0;
-    const int src = tail    ? fqgpu_chunk_tailtrim(ctx_, adapter, tail, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr, nullptr)
-                    : adapter ? fqgpu_chunk_clip(ctx_, adapter, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
-                    : trim  ? fqgpu_chunk_trim(ctx_, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
-                         : fqgpu_chunk_filter(ctx_, filter, out, piece.raw_data.size(), &len, report, nullptr);
-    if (src != FQGPU_OK) throw refused("the " + step + ": " + fqgpu_strerror(src));
-    piece.raw_data.resize(len);
-    clk.lap(step.c_str());
-    clk.done(cbs.chunk_idx);
   }
 
   /** decodeChunk through fqgpu_decode_chunk; false: the device refused the chunk (the host path decides) */
@@ -830,6 +875,7 @@ private:
 
   bool build_index_ = false, index_only_ = false, verify_ = false, check_only_ = false;
   ChunkDigest last_digest_;
+  unsigned staged_idx_ = 0;  // the chunk stagePairedChunk staged last (for messages)
   /** the digest of the chunk the handle has just restored */
   void takeDigest() {
     if (!verify_) return;

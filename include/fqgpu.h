@@ -647,7 +647,7 @@ int fqgpu_dblock_clip(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter
  *   report  FQGPU_TAIL_REPORT_WORDS uint64_t: 0 .. 15 as fqgpu_chunk_clip's report -- word 12 stays the sum of L - start - n,
  *           and bases_in = word 11 + word 12 + the sum of n keeps holding | 16 reads_with_poly_tail (a1 < a0, kept or not) |
  *           17 bases_cut_poly (the sum of a0 - a1) | 18 reads_window_cut (e2 < e) | 19 bases_cut_window (the sum of e - e2) |
- *           20 .. 23 zero.  Reports of several chunks add word by word
+ *           20 .. 23 zero (word 20 is fqgpu_chunk_select_marked's).  Reports of several chunks add word by word
  *   places_out   NULL, or 4 uint16_t per record, kept or not: a0, a1, e, e2
  *   out == NULL, out_cap < *out_len, keep_out, win_out   as fqgpu_chunk_clip
  * The sequence line is read iff max_n is on, an adapter is given, or poly_bases != 0; the quality line iff the trim's rule
@@ -682,6 +682,55 @@ int fqgpu_chunk_tailtrim(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tai
 int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
                           const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
                           uint32_t *win_out, uint16_t *places_out);
+
+/* ---- Extension (nothing in the reference): PAIRED chunks -- a selection restricted to a RECORD RANGE of a chunk and to a MARK,
+ * and the READ IDS of two chunks compared, where the chunks lie already -- in HBM.  Paired-end reads come as two files whose
+ * record i are mates; a restore that drops reads must drop a pair when either mate fails, and the chunks of two archives are
+ * cut by bytes, so that the mates of one chunk's records lie in a range of one to three chunks of the other archive.  The two
+ * calls are what a paired restore is made of: judge mate 1 (a size query: its keep bits), judge the matching range of mate 2
+ * with those bits as the mark (its keep bits are the pair's), gather mate 1 with the pair's bits as the mark.
+ *   fqgpu_chunk_select_marked   records [first, end) of the chunk alone are judged, counted and written; first < end <= n_recs,
+ *                  else FQGPU_E_ARG.  Steps 0 to 5 are exactly those of fqgpu_chunk_tailtrim; each of a, x, t, f may be NULL,
+ *                  which means "off", and all four NULL keeps every read.  report[0], keep_out, win_out, places_out, the
+ *                  offsets inside out and the bits of mark_in are all relative to `first`: record first + i is bit i & 7 of
+ *                  byte i >> 3, word i of win_out, row i of places_out.
+ *   mark_in        NULL (every record is marked), or (end - first + 7) / 8 bytes in keep_out's layout.  A record whose bit is 0
+ *                  is dropped whatever its own verdict.  The bits of the last byte behind `end` are not looked at.
+ *   report  FQGPU_TAIL_REPORT_WORDS uint64_t, the tail calls' report of the range: words 5 .. 19 are the records' own -- what
+ *           each criterion dropped and what was cut; the mark does not change them -- | 1 n_kept, 3 bases_kept, 4 bytes_kept count
+ *           the records that are kept AND marked | 20 dropped_unmarked: the records that pass every criterion and whose mark bit
+ *           is 0 | 21 .. 23 zero.  n_records = n_kept + words 5 .. 9 + word 20 always.  Reports add word by word.
+ *   keep_out       the final bit: the record's own verdict AND its mark
+ *   out == NULL, out_cap < *out_len, win_out, places_out, the lines that are read and judged, what is refused and what a
+ *   refusal zeroes: as fqgpu_chunk_tailtrim, over the range.  Valid in exactly the states in which fqgpu_chunk_tailtrim is
+ *   valid, on the same stream; it leaves the chunk as it is and is waited for before it returns, so several calls on one
+ *   staged chunk are allowed.  With first = 0, end = n_recs, mark_in = NULL and arguments fqgpu_chunk_tailtrim accepts, every
+ *   output is that call's, byte for byte (word 20 is zero).
+ *   fqgpu_dblock_select_marked  waits for the block's last operation as fqgpu_dblock_tailtrim does.
+ * The READ ID of a record is the bytes of its header line behind the '@', up to the first ' ', '\t' or '\n'; if they end in
+ * "/1" or "/2", those two bytes are not part of it -- judged for each mate on its own, so "x/1" and "x" have one id.
+ *   fqgpu_chunk_pair_names   compares the ids of record first_a + i of the chunk staged on ctx_a and record first_b + i of the
+ *                  chunk staged on ctx_b (each where fqgpu_chunk_stats is valid) for i < count.  *mismatch = the smallest i whose
+ *                  ids differ in length or in any byte, (size_t)-1 when there is none: a mismatch still returns FQGPU_OK, the
+ *                  caller decides what to make of it.  Both handles must be of one device, else FQGPU_E_ARG; every stream of
+ *                  both is waited for first, then ONE kernel runs on ctx_a's stream and is waited for.  ctx_a == ctx_b is allowed
+ *                  (a chunk against itself).  count == 0, a range outside either chunk, a header line that does not lie
+ *                  inside its chunk (a table that is not the chunk's), a NULL: FQGPU_E_ARG with *mismatch = (size_t)-1.
+ *   fqgpu_dblock_pair_names  two blocks of ctx's device; waits for each block's last operation as fqgpu_dblock_stats does, the
+ *                  owners of blocks of other handles included.  A block of another device: FQGPU_E_ARG.
+ *   fqgpu_read_id_len        host only, the rule's statement: the id's length for a header line of `len` bytes that starts
+ *                  with its '@' (the line's end counts as an end when no ' ', '\t' or '\n' stands in front of it); 0 for NULL.
+ * Without a GPU the four device calls return FQGPU_E_NO_DEVICE before any argument is looked at; fqgpu_read_id_len works. */
+int fqgpu_chunk_select_marked(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                              size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
+                              uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out);
+int fqgpu_dblock_select_marked(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                               const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap,
+                               size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out);
+int fqgpu_chunk_pair_names(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, size_t *mismatch);
+int fqgpu_dblock_pair_names(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
+                            size_t *mismatch);
+size_t fqgpu_read_id_len(const uint8_t *header_line, size_t len);
 
 /* ---- Extension (nothing in the reference): ADAPTER CONTENT -- which 3' adapters the reads of a chunk hold, in how many reads
  * and where, counted where the chunk lies already -- in HBM.  FastQC's "Adapter Content" module, and the question in front

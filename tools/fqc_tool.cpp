@@ -54,6 +54,19 @@
 //               --poly-g or --poly-x, and values fqgpu_tail_check refuses are usage errors.  A failed run leaves neither
 //               <out.fastq> nor <out.fastq>.part.  N is optional: the argument behind --poly-g / --poly-x is taken for it
 //               whenever it does not begin with '-', so a word that is no number there is a usage error, not a path)
+//   fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [-t threads] [-d dev,dev,...]
+//              [every filter, trim, adapter, poly and window option]
+//              (extension: PAIRED restore -- two archives whose records are mates, restored in step: record i of both outputs
+//               are mates, and a pair is written only if BOTH mates pass, so the outputs stay in step whatever is dropped.
+//               Every selection option applies to both mates; --adapter2 is mate 2's 3' adapter (default: --adapter's).  The
+//               read ids of every pair -- the header line up to its first blank, without a "/1" or "/2" at the end -- are
+//               compared on the device: the first pair whose ids differ ends the command, exit 1, naming the record.  Without
+//               a selection option both files are restored whole and only the ids are checked.  The archives need the same
+//               number of records and nothing else: different block sizes, read lengths and header formats are fine, a chunk
+//               of <in2.fqc> that straddles a chunk boundary of <in1.fqc> is decoded twice.  Each archive's .fqx is used and
+//               its .fqs verified as in a single restore.  --mate with c, x, t or s, with --records, --fasta, --index or
+//               --index-stride, and --adapter2 without --mate or without --adapter's rules met are usage errors.  A failed run
+//               leaves neither output nor a .part file)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -97,7 +110,12 @@
 // criterion dropped ("records" / "raw_bytes" of the line are then what was written); with a trim "trim": the same and the
 // reads trimmed, the bases cut from either end and the reads emptied, and with an adapter -- then alone -- the reads in which it
 // was found and the bases it took, and with a poly or window option -- then alone -- the reads with a poly tail, the bases it
-// took, the reads the window cut and the bases it took.  Needs a GPU: no CPU fallback.
+// took, the reads the window cut and the bases it took.  With --mate the line's "records" / "raw_bytes" are mate 1's output,
+// "raw_bytes2" mate 2's, "pairs": {"pairs", "kept", "dropped_mate1_only", "dropped_mate2_only", "dropped_both"} what became of
+// the pairs, "blocks1" / "blocks2" the archives' chunks and "decodes2" the chunk decodes of archive 2, "sums2" / "verified2"
+// (per decode) its chunk sums; with a selection option "mate1" and "mate2" replace "filter" and "trim": the keys of "trim", the
+// adapter, poly and window keys always there, and "dropped_unmarked", the reads that passed and whose mate did not.
+// Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
 #include <cstdio>
@@ -118,6 +136,8 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q] [adapter options] [trim options] [filter options]\n"
                          "                  (the argument behind --poly-g / --poly-x is taken as N unless it begins with '-')\n"
+                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
+                         "                  (paired: a pair is kept only if both mates pass; the read ids of every pair are compared)\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
                          "       fqc_tool t <in.fqc> [-t N] [-d 0,1,..]\n"
@@ -137,6 +157,9 @@ int main(int argc, char **argv) {
   bool trimmed = false;
   fqgpu_adapter adapter = {{0}, 0, 5, 10, 0};
   bool clipped = false, adapter_opt = false;
+  fqgpu_adapter adapter2 = {{0}, 0, 5, 10, 0};
+  bool clipped2 = false, mate = false;
+  std::string mate_in, mate_out;
   std::string adapters_list;
   bool adapters_opt = false;
   fqgpu_tail tail = {0, 0, 0, 0, 0, 0, {0, 0}};
@@ -194,6 +217,16 @@ int main(int argc, char **argv) {
       std::memset(adapter.seq, 0, sizeof adapter.seq);
       std::memcpy(adapter.seq, v.data(), std::min<std::size_t>(v.size(), FQGPU_ADAPTER_MAX));
       clipped = true;
+    } else if (a == "--adapter2") {
+      const std::string v = val();
+      adapter2.len = static_cast<uint32_t>(v.size());  // (too long a one is refused by the check below)
+      std::memset(adapter2.seq, 0, sizeof adapter2.seq);
+      std::memcpy(adapter2.seq, v.data(), std::min<std::size_t>(v.size(), FQGPU_ADAPTER_MAX));
+      clipped2 = true;
+    } else if (a == "--mate") {
+      mate_in = val();
+      mate_out = val();
+      mate = true;
     } else if (a == "--adapters") {
       adapters_list = val();
       adapters_opt = true;
@@ -256,6 +289,14 @@ int main(int argc, char **argv) {
       for (const char *p = val(); *p;) { set.devices.push_back(std::atoi(p)); while (*p && *p != ',') ++p; if (*p) ++p; }
     } else { std::fprintf(stderr, "unknown option %s\nusage: fqc_tool c|d <in> <out> [options] | fqc_tool x|t <in.fqc> [options]\n", a.c_str()); return 2; }
   }
+  if (mate && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
+    std::fprintf(stderr, "--mate goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (clipped2 && !mate) {
+    std::fprintf(stderr, "--adapter2 is mate 2's adapter: it needs --mate <in2.fqc> <out2.fastq>\n");
+    return 2;
+  }
   if (fasta && (argv[1][0] != 'd' || set.decode_index)) {  // (said before any device is touched)
     std::fprintf(stderr, "--fasta goes with d alone, and builds no index: not with c, x, t, --index or --index-stride\n");
     return 2;
@@ -280,11 +321,20 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--adapters goes with s, and with c --stats <report.tsv>: not with d, x or t, and not without a report to write\n");
     return 2;
   }
+  if (mate && !clipped2 && clipped) {  // (mate 2's adapter is mate 1's unless it has its own)
+    std::memcpy(adapter2.seq, adapter.seq, sizeof adapter2.seq);
+    adapter2.len = adapter.len;
+  }
+  if (mate) {  // (--adapter-overlap and --adapter-err hold for both)
+    adapter2.min_overlap = adapter.min_overlap;
+    adapter2.max_err_pct = adapter.max_err_pct;
+    clipped2 = clipped2 || clipped;
+  }
   if ((clipped || (adapter_opt && !adapters_opt)) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
     std::fprintf(stderr, "adapter clipping goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
     return 2;
   }
-  if (adapter_opt && !clipped && !adapters_opt) {
+  if (adapter_opt && !clipped && !clipped2 && !adapters_opt) {
     std::fprintf(stderr, "--adapter-overlap and --adapter-err need --adapter SEQ, or --adapters LIST\n");
     return 2;
   }
@@ -340,6 +390,13 @@ int main(int argc, char **argv) {
       return 2;
     }
   }
+  if (clipped2) {
+    if (adapter2.min_overlap > adapter2.len) adapter2.min_overlap = adapter2.len;  // (N is capped at the adapter's length)
+    if (fqgpu_adapter_check(&adapter2) != FQGPU_OK) {
+      std::fprintf(stderr, "adapter clipping: expected --adapter2 of 1 .. 64 bases ACGT (upper case), --adapter-overlap 1 or more, --adapter-err 0 .. 50\n");
+      return 2;
+    }
+  }
   if ((tailed || poly_opt) && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
     std::fprintf(stderr, "poly tails and the window cut go with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
     return 2;
@@ -378,7 +435,12 @@ int main(int argc, char **argv) {
       set.build_index = set.decode_index && !range;
       set.decode_index = false;
     }
-    const FarmReport r = check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
+    PairedReport paired;
+    if (mate)
+      paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped ? &adapter : nullptr, clipped2 ? &adapter2 : nullptr,
+                                    tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr, set);
+    const FarmReport r = mate ? paired.mate1
+                         : check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
                          : tailed  ? processArchiveTailTrimmed(argv[2], argv[3], clipped ? &adapter : nullptr, tail, trimmed ? &trim : nullptr,
@@ -413,13 +475,31 @@ int main(int argc, char **argv) {
         std::printf(", \"adapters\": %u, \"reads_with_any\": %llu", probes.n,
                     (unsigned long long)(r.probes.empty() ? 0 : r.probes[8 + probes.n * (8 + (std::size_t)set.stats_positions + 1)]));
     }
-    if (filtered) {
+    if (mate) {
+      std::printf(", \"raw_bytes2\": %zu, \"pairs\": {\"pairs\": %llu, \"kept\": %llu, \"dropped_mate1_only\": %llu, \"dropped_mate2_only\": %llu, "
+                  "\"dropped_both\": %llu}, \"blocks1\": %zu, \"blocks2\": %zu, \"decodes2\": %zu, \"index2\": \"%s\", \"sums2\": \"%s\", \"verified2\": %zu",
+                  paired.mate2.in.raw, (unsigned long long)paired.pairs, (unsigned long long)paired.kept, (unsigned long long)paired.dropped_mate1_only,
+                  (unsigned long long)paired.dropped_mate2_only, (unsigned long long)paired.dropped_both, paired.blocks1, paired.blocks2, paired.decodes2,
+                  paired.mate2.indexed_blocks ? "used" : "none", paired.mate2.sums, paired.mate2.verified_blocks);
+      for (int m = 0; m < 2 && (filtered || trimmed || clipped || clipped2 || tailed); ++m) {
+        const std::vector<uint64_t> &t = m ? paired.mate2.trim : paired.mate1.trim;
+        const auto w = [&](unsigned i) { return (unsigned long long)t[i]; };
+        std::printf(", \"mate%d\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
+                    "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
+                    "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu, "
+                    "\"reads_with_adapter\": %llu, \"bases_cut_adapter\": %llu, \"reads_with_poly_tail\": %llu, \"bases_cut_poly\": %llu, "
+                    "\"reads_window_cut\": %llu, \"bases_cut_window\": %llu, \"dropped_unmarked\": %llu}",
+                    m + 1, w(0), w(1), w(2), w(3), w(4), w(5), w(6), w(7), w(8), w(9), w(10), w(11), w(12), w(13), w(14), w(15), w(16), w(17), w(18),
+                    w(19), w(20));
+      }
+    }
+    if (filtered && !mate) {
       const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped || tailed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
       std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
                   "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
                   w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
     }
-    if (trimmed || clipped || tailed) {
+    if ((trimmed || clipped || tailed) && !mate) {
       const auto w = [&](unsigned i) { return (unsigned long long)r.trim[i]; };
       std::printf(", \"trim\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
                   "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
