@@ -91,8 +91,8 @@ struct FarmReport {
   uint64_t archive_bytes_read = 0;  // processArchiveFasta: what was read of the archive file (the quality streams are not)
   std::vector<uint64_t> stats;      // the read summary of every chunk, merged (fqgpu_stats_words(set.stats_positions) words; empty: none taken)
   std::vector<uint64_t> probes;     // the adapter content of every chunk, merged (fqgpu_probe_words words; empty: set.probes was not given)
-  std::vector<uint64_t> filter;     // processArchiveFiltered: the chunks' filter reports, added word by word (FQGPU_FILTER_REPORT_WORDS; empty: none)
-  std::vector<uint64_t> trim;       // processArchiveTrimmed: the chunks' trim reports, added word by word (FQGPU_TRIM_REPORT_WORDS; empty: none)
+  std::vector<uint64_t> filter;     // processArchiveSelected with a filter alone: the chunks' filter reports, added word by word (FQGPU_FILTER_REPORT_WORDS; empty: none)
+  std::vector<uint64_t> trim;       // processArchiveSelected with anything that cuts: the chunks' trim reports, added word by word (Selection::reportWords; empty: none)
 };
 
 namespace detail {
@@ -324,18 +324,40 @@ FarmReport decompressFarm(const DatasetMeta &meta, Source &&next_block, Sink &&w
 }
 
 namespace detail {
-/** the archive's decode index file, if one lies beside it and was written for it */
-inline std::unique_ptr<DecodeIndexFile> openDecodeIndex(const path_t &archive_path) {
-  std::unique_ptr<DecodeIndexFile> sidecar;
-  if (std::filesystem::exists(DecodeIndexFile::pathFor(archive_path))) {
-    sidecar = std::make_unique<DecodeIndexFile>(DecodeIndexFile::pathFor(archive_path), PosFile::Mode::Read);
-    if (!sidecar->belongsTo(DecodeIndexFile::identityOf(archive_path))) {
-      std::fprintf(stderr, "%s was written for another archive: not used\n", DecodeIndexFile::pathFor(archive_path).string().c_str());
-      sidecar.reset();
+/** The archive's decode index file and what was used of it, the `.fqx` counterpart of ChunkVerifier: opened if one lies
+ *  beside the archive and was written for it (another archive's is reported on stderr and not used), asked by the workers
+ *  block by block, and at the end it says what it gave. */
+class IndexSidecar {
+public:
+  explicit IndexSidecar(const path_t &archive_path) {
+    const path_t p = DecodeIndexFile::pathFor(archive_path);
+    if (!std::filesystem::exists(p)) return;
+    file_ = std::make_unique<DecodeIndexFile>(p, PosFile::Mode::Read);
+    if (!file_->belongsTo(DecodeIndexFile::identityOf(archive_path))) {
+      std::fprintf(stderr, "%s was written for another archive: not used\n", p.string().c_str());
+      file_.reset();
     }
   }
-  return sidecar;
-}
+  [[nodiscard]] bool on() const { return file_ != nullptr; }
+  /** thread-safe: the block's indexes into cbs.decode_index, counted; false: there is no usable file, or it has no entry for
+   *  the chunk, which is then decoded without.  seq_only (the FASTA farm): the entry is checked as a whole, but the quality
+   *  index has no use there, is dropped and not counted. */
+  bool get(CompressedBuffersSrc &cbs, bool seq_only = false) {
+    if (!file_ || !file_->get(cbs)) return false;
+    if (seq_only) cbs.decode_index[1].clear();
+    blocks_.fetch_add(1);
+    bytes_.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
+    return true;
+  }
+  void report(FarmReport &rep) const {
+    rep.indexed_blocks = blocks_.load();
+    rep.index_bytes = bytes_.load();
+  }
+
+private:
+  std::unique_ptr<DecodeIndexFile> file_;
+  std::atomic<std::size_t> blocks_{0}, bytes_{0};
+};
 }  // namespace detail
 
 namespace detail {
@@ -440,6 +462,90 @@ private:
   std::atomic<std::size_t> blocks_{0}, bytes_{0};
   bool done_ = false;
 };
+
+/** The ordered hand-out loop of the restores whose unit of work is a numbered item -- a piece, a block, a pair of chunks:
+ *  processArchiveRange, processArchiveFasta, processArchiveSelected, processArchivePaired.  It comes in two steps because the
+ *  output is opened between them: detail::pieceFarm(name, n_items, set, make) readies the workers, run(body, abort, block_of)
+ *  is the loop.  What every such restore relies on:
+ *   - Worker count: T = max(1, min(set.n_threads, max(n_items, 1))).  The report's blocks_per_worker has max(1, set.n_threads)
+ *     entries, of which only the first T are ever counted.
+ *   - Device check: an empty set.devices throws std::invalid_argument("<name>: no device") from pieceFarm, that is before the
+ *     caller has created any output file.  Worker t uses set.devices[t % set.devices.size()].
+ *   - Start-up: make(t, device) builds worker t's state -- its workspace or workspaces, buffers and accumulators, of any type,
+ *     movable or not; the helper knows nothing of it -- and the T of them are built concurrently.  The clock starts only when
+ *     all exist (workers()[0] may then serve the caller before the loop: processArchiveRange sizes its edge pieces with it).
+ *   - Hand-out: the items 0 .. n_items - 1 are handed out by ONE atomic counter, in increasing order, and a worker takes a new
+ *     one only while nobody has failed.  OrderedPieceWriter's freedom from deadlock rests on this and on the next but one
+ *     point: whoever waits in a writer waits for items that are already taken.
+ *   - body(state, item, clk, in) does one item, adds what it wrote to `in` and says whether to go on.  When it returns false,
+ *     or an OrderedPieceWriter::Aborted escapes it, the worker leaves quietly: somebody else has failed and says why.
+ *   - When anything else escapes it, the stop flag is set and abort() is called, which must release everybody who waits in a
+ *     writer (a FastqWriter has no waiters: nothing to do).  The others finish their item or are released, and leave.  After
+ *     all have joined, the first exception by worker index is rethrown (runWorkers' rule); the caller's writers die without a
+ *     flush(), so neither `<out>` nor `<out>.part` remains.
+ *   - Per-item clock: every item gets a fresh StageClock, closed with block_of(item), the number of the block the item came
+ *     from (FQGPU_SHIM_TRACE=1 prints the body's laps under it).
+ *   - report(), called after the writers' flush(), gives blocks_per_worker, the workers' `in` added up and seconds, which so
+ *     runs from "all workers ready" to "writers flushed". */
+template <class State> class PieceFarm {
+public:
+  template <class Make> PieceFarm(const std::string &name, std::size_t n_items, const Settings &set, Make &&make)
+      : n_items_(n_items), blocks_(std::max(1u, set.n_threads), 0) {
+    if (set.devices.empty()) throw std::invalid_argument(name + ": no device");
+    const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n_items, 1))));
+    workers_.resize(T);
+    in_.resize(T);
+    runWorkers(T, [&](unsigned t) { workers_[t].reset(new State(make(t, set.devices[t % set.devices.size()]))); });
+    t0_ = std::chrono::steady_clock::now();
+  }
+  [[nodiscard]] const std::vector<std::unique_ptr<State>> &workers() const { return workers_; }
+  template <class Body, class Abort, class BlockOf> void run(Body &&body, Abort &&abort, BlockOf &&block_of) {
+    std::atomic<std::size_t> next{0};
+    std::atomic<bool> stopped{false};
+    runWorkers(static_cast<unsigned>(workers_.size()), [&](unsigned t) {
+      for (;;) {
+        const std::size_t item = next.fetch_add(1);
+        if (stopped.load() || item >= n_items_) break;
+        StageClock clk;
+        try {
+          if (!body(*workers_[t], item, clk, in_[t])) break;
+        } catch (const OrderedPieceWriter::Aborted &) {
+          break;
+        }
+        blocks_[t]++;
+        clk.done(static_cast<unsigned>(block_of(item)));
+      }
+    }, [&] { stopped.store(true); abort(); });
+  }
+  /** items that are blocks, or units numbered as their blocks are */
+  template <class Body, class Abort> void run(Body &&body, Abort &&abort) { run(body, abort, [](std::size_t item) { return item; }); }
+  [[nodiscard]] FarmReport report() const {
+    FarmReport rep;
+    rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0_).count();
+    rep.blocks_per_worker = blocks_;
+    for (const InputStats &in : in_) rep.in += in;
+    return rep;
+  }
+
+private:
+  std::size_t n_items_;
+  std::vector<unsigned> blocks_;
+  std::vector<std::unique_ptr<State>> workers_;
+  std::vector<InputStats> in_;
+  std::chrono::steady_clock::time_point t0_;
+};
+/** the farm whose worker state is what make(t, device) returns */
+template <class Make> auto pieceFarm(const std::string &name, std::size_t n_items, const Settings &set, Make &&make) {
+  return PieceFarm<std::invoke_result_t<Make &, unsigned, int>>(name, n_items, set, make);
+}
+
+/** A restoring worker's state: its workspace, the block it has read and the piece it makes of it. */
+struct RestoreWorker {
+  DecompressionWorkspace wksp;
+  CompressedBuffersSrc cbs;
+  FastqChunk piece;
+  RestoreWorker(const DatasetMeta &meta, int device, bool verify = false) : wksp(&meta, device) { wksp.setVerify(verify); }
+};
 }  // namespace detail
 
 /** processArchiveParts (src/process.cpp:84-105): archive in, file out (chunks in original order).  set.build_index: an
@@ -449,25 +555,21 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
   Archive archive(archive_path);
   const std::vector<uint64_t> chunk_at = archive.chunkOffsets();
   FastqWriter writer(mates1_out, chunk_at);
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  detail::IndexSidecar sidecar(archive_path);
   std::unique_ptr<detail::DecodeIndexBuilder> builder;
   detail::ChunkVerifier verifier(archive_path, chunk_at.size() - 1, false);
   Settings farm = set;
-  farm.build_index = set.build_index && !sidecar;
+  farm.build_index = set.build_index && !sidecar.on();
   farm.index_only = false;
   farm.verify = verifier.on();
   farm.check_only = false;
   farm.stats_positions = 0;
   if (farm.build_index) builder = std::make_unique<detail::DecodeIndexBuilder>(archive_path);
-  std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
   FarmReport rep = decompressFarm(
       archive.meta(),
       [&](CompressedBuffersSrc &cbs) {
         if (!archive.readBlock(cbs)) return false;
-        if (sidecar && sidecar->get(cbs)) {  // (a chunk the file has no entry for is decoded without)
-          used_blocks.fetch_add(1);
-          used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
-        }
+        sidecar.get(cbs);
         return true;
       },
       [&](const FastqChunk &chunk, const CompressedBuffersSrc &cbs, const ChunkDigest &digest) {
@@ -477,8 +579,7 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
       },
       [&] { archive.abort(); }, farm);
   writer.flush();
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
+  sidecar.report(rep);
   verifier.report(rep);
   if (builder) builder->finish(rep);
   return rep;
@@ -491,27 +592,22 @@ inline FarmReport processArchiveParts(const path_t &archive_path, const path_t &
  *  command fails: checking is all it does. */
 inline FarmReport processArchiveCheck(const path_t &archive_path, const Settings &set) {
   Archive archive(archive_path);
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  detail::IndexSidecar sidecar(archive_path);
   detail::ChunkVerifier verifier(archive_path, archive.chunkOffsets().size() - 1, true);
   Settings farm = set;
   farm.build_index = farm.index_only = false;
   farm.verify = verifier.on();
   farm.check_only = true;
-  std::atomic<std::size_t> used_blocks{0}, used_bytes{0};
   FarmReport rep = decompressFarm(
       archive.meta(),
       [&](CompressedBuffersSrc &cbs) {
         if (!archive.readBlock(cbs)) return false;
-        if (sidecar && sidecar->get(cbs)) {
-          used_blocks.fetch_add(1);
-          used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
-        }
+        sidecar.get(cbs);
         return true;
       },
       [&](const FastqChunk &, const CompressedBuffersSrc &cbs, const ChunkDigest &digest) { verifier.check(cbs, digest); },
       [&] { archive.abort(); }, farm);
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
+  sidecar.report(rep);
   verifier.report(rep, true);
   return rep;
 }
@@ -573,12 +669,9 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
   }
   const std::vector<RangePiece> pieces = planRecordRange(counts, a, b);
   const std::vector<uint64_t> chunk_at = archive.chunkOffsets();
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
-  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(pieces.size())));
-  if (set.devices.empty()) throw std::invalid_argument("processArchiveRange: no device");
-  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
-  detail::runWorkers(T, [&](unsigned t) { wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]); });
-  const auto t0 = std::chrono::steady_clock::now();
+  detail::IndexSidecar sidecar(archive_path);
+  auto farm = detail::pieceFarm("processArchiveRange", pieces.size(), set,
+                                [&](unsigned, int device) { return detail::RestoreWorker(archive.meta(), device); });
   std::vector<uint64_t> out_at(pieces.size() + 1, 0);
   for (std::size_t p = 0; p < pieces.size(); ++p) {
     const RangePiece &pc = pieces[p];
@@ -586,47 +679,29 @@ inline FarmReport processArchiveRange(const path_t &archive_path, const path_t &
     if (!pc.whole) {
       CompressedBuffersSrc cbs;
       archive.readBlockAt(pc.block, cbs);
-      size = wksp[0]->rangeSize(cbs, pc.first, pc.end);
+      size = farm.workers()[0]->wksp.rangeSize(cbs, pc.first, pc.end);
     }
     out_at[p + 1] = out_at[p] + size;
   }
   FastqWriter writer(mates1_out, out_at);
-  std::vector<InputStats> istats(T);
-  FarmReport rep;
-  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
-  std::atomic<bool> stopped{false};
-  detail::runWorkers(T, [&](unsigned t) {
-    CompressedBuffersSrc cbs;
-    FastqChunk chunk;
-    for (;;) {
-      const std::size_t p = next.fetch_add(1);
-      if (stopped.load() || p >= pieces.size()) break;
-      const RangePiece &pc = pieces[p];
-      StageClock clk;
-      archive.readBlockAt(pc.block, cbs);
-      if (sidecar && sidecar->get(cbs)) {
-        used_blocks.fetch_add(1);
-        used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
-      }
-      clk.lap("read");
-      if (pc.whole) wksp[t]->decodeChunk(chunk, cbs);
-      else wksp[t]->decodeChunkRange(chunk, cbs, pc.first, pc.end);
-      clk.lap("decode");
-      chunk.idx = static_cast<unsigned>(p);  // (the writer places pieces, not chunks)
-      istats[t].raw += chunk.raw_data.size();
-      istats[t].n_records += chunk.records.size();
-      rep.blocks_per_worker[t]++;
-      writer.writeChunk(chunk);
-      clk.lap("write");
-      clk.done(static_cast<unsigned>(pc.block));
-    }
-  }, [&] { stopped.store(true); });
+  farm.run([&](detail::RestoreWorker &w, std::size_t p, StageClock &clk, InputStats &in) {
+    const RangePiece &pc = pieces[p];
+    archive.readBlockAt(pc.block, w.cbs);
+    sidecar.get(w.cbs);
+    clk.lap("read");
+    if (pc.whole) w.wksp.decodeChunk(w.piece, w.cbs);
+    else w.wksp.decodeChunkRange(w.piece, w.cbs, pc.first, pc.end);
+    clk.lap("decode");
+    w.piece.idx = static_cast<unsigned>(p);  // (the writer places pieces, not chunks)
+    in.raw += w.piece.raw_data.size();
+    in.n_records += w.piece.records.size();
+    writer.writeChunk(w.piece);
+    clk.lap("write");
+    return true;
+  }, [] {}, [&](std::size_t p) { return pieces[p].block; });  // (the sizes are known: nobody waits in this writer)
   writer.flush();
-  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
+  FarmReport rep = farm.report();
+  sidecar.report(rep);
   return rep;
 }
 
@@ -646,181 +721,80 @@ inline FarmReport processArchiveFasta(const path_t &archive_path, const path_t &
     for (const uint32_t n : counts) b += n;
   }
   const std::vector<RangePiece> pieces = planRecordRange(counts, a, b);
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
-  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(pieces.size())));
-  if (set.devices.empty()) throw std::invalid_argument("processArchiveFasta: no device");
-  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
-  detail::runWorkers(T, [&](unsigned t) { wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]); });
+  detail::IndexSidecar sidecar(archive_path);
+  auto farm = detail::pieceFarm("processArchiveFasta", pieces.size(), set,
+                                [&](unsigned, int device) { return detail::RestoreWorker(archive.meta(), device); });
   const uint64_t read_before = archive.bytesRead();
-  const auto t0 = std::chrono::steady_clock::now();
   OrderedPieceWriter writer(fasta_out, pieces.size());
-  std::vector<InputStats> istats(T);
-  FarmReport rep;
-  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
-  std::atomic<bool> stopped{false};
-  detail::runWorkers(T, [&](unsigned t) {
-    CompressedBuffersSrc cbs;
-    FastqChunk piece;
-    for (;;) {
-      const std::size_t p = next.fetch_add(1);  // (in order: whoever waits in the writer waits for pieces already taken)
-      if (stopped.load() || p >= pieces.size()) break;
-      const RangePiece &pc = pieces[p];
-      StageClock clk;
-      archive.readBlockAt(pc.block, cbs, false);
-      if (sidecar && sidecar->get(cbs)) {
-        cbs.decode_index[1].clear();  // (the entry is checked as a whole; the quality index has no use here)
-        used_blocks.fetch_add(1);
-        used_bytes.fetch_add(cbs.decode_index[0].size());
-      }
-      clk.lap("read");
-      wksp[t]->decodeChunkFasta(piece, cbs, pc.first, pc.end);
-      clk.lap("decode");
-      istats[t].raw += piece.raw_data.size();
-      istats[t].n_records += pc.end - pc.first;
-      rep.blocks_per_worker[t]++;
-      try {
-        writer.writePiece(p, piece.raw_data.data(), piece.raw_data.size());
-      } catch (const OrderedPieceWriter::Aborted &) {
-        break;  // (another worker has failed and says why)
-      }
-      clk.lap("write");
-      clk.done(static_cast<unsigned>(pc.block));
-    }
-  }, [&] { stopped.store(true); writer.abort(); });
+  farm.run([&](detail::RestoreWorker &w, std::size_t p, StageClock &clk, InputStats &in) {
+    const RangePiece &pc = pieces[p];
+    archive.readBlockAt(pc.block, w.cbs, false);
+    sidecar.get(w.cbs, true);
+    clk.lap("read");
+    w.wksp.decodeChunkFasta(w.piece, w.cbs, pc.first, pc.end);
+    clk.lap("decode");
+    in.raw += w.piece.raw_data.size();
+    in.n_records += pc.end - pc.first;
+    writer.writePiece(p, w.piece.raw_data.data(), w.piece.raw_data.size());
+    clk.lap("write");
+    return true;
+  }, [&] { writer.abort(); }, [&](std::size_t p) { return pieces[p].block; });
   writer.flush();
-  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  for (unsigned t = 0; t < T; ++t) rep.in += istats[t];
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
+  FarmReport rep = farm.report();
+  sidecar.report(rep);
   rep.archive_bytes_read = archive.bytesRead() - read_before;
   return rep;
 }
 
-namespace detail {
-/** processArchiveFiltered (trim == nullptr; the filter is needed), processArchiveTrimmed and processArchiveClipped (with an
- *  adapter, trim and filter may both be nullptr; reported as a trim) and processArchiveTailTrimmed (with a tail, adapter, trim
- *  and filter may all be nullptr; reported as a trim of FQGPU_TAIL_REPORT_WORDS words), `who` of the four: every block
- *  decoded on the device and selected there (decodeChunkFiltered / decodeChunkTrimmed / decodeChunkClipped /
- *  decodeChunkTailTrimmed), only the kept bytes come down and
- *  reach the file.  A usable `<archive>.fqx` is used, and with a usable `<archive>.fqs` every chunk is verified before any
- *  of it is written: the digest is of the WHOLE restored chunk, as the writer took it.  Never builds an index.  The kept
- *  sizes are known only after the decode, so the blocks go through OrderedPieceWriter as the FASTA pieces do: handed out in
- *  order, placed by the sizes published so far; a failed run leaves neither `<out>` nor `<out>.part`.  rep.in counts what
- *  was written; the chunks' reports, added word by word, go to rep.filter or rep.trim. */
-inline FarmReport processArchiveSelected(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim *trim,
-                                         const fqgpu_filter *filter, const Settings &set, const char *who,
-                                         const fqgpu_adapter *adapter = nullptr, const fqgpu_tail *tail = nullptr) {
-  static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one report size for both");
-  const unsigned W = tail ? FQGPU_TAIL_REPORT_WORDS : FQGPU_FILTER_REPORT_WORDS;  // (rep.trim has 24 words only with a tail)
-  const std::string name(who);
-  if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
-  if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
-  if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-  if ((filter || !(trim || adapter || tail)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+/** Extension: `d` with any of the filter, trim, adapter, poly and window options -- the reads as `sel` leaves them, in input
+ *  order: clipped at the 3' adapter, their poly-X tail and everything from a sliding-window quality drop on taken, trimmed,
+ *  then judged by the filter (each step nullptr: off; no filter: every read that is not emptied is kept; a selection that
+ *  cuts nothing needs its filter and writes the passing reads as the bytes a plain restore writes for them).  Every block is
+ *  decoded on the device and selected there (decodeChunkSelected); only the kept bytes come down and reach the file.  A
+ *  usable `<archive>.fqx` is used, and with a usable `<archive>.fqs` every chunk is verified before any of it is written: the
+ *  digest is of the WHOLE restored chunk, as the writer took it.  Never builds an index.  The kept sizes are known only after
+ *  the decode, so the blocks go through OrderedPieceWriter as the FASTA pieces do: handed out in order, placed by the sizes
+ *  published so far; a failed run leaves neither `<out>` nor `<out>.part`.  rep.in counts what was written.  The chunks'
+ *  reports, added word by word, go to rep.filter (what was read and why it was dropped) when nothing is cut, else to rep.trim:
+ *  the same and what was cut, with an adapter words 14 and 15 (the reads in which it was found, the bases it took), with a
+ *  tail FQGPU_TAIL_REPORT_WORDS words (then the reads with a poly tail, its bases, the reads the window cut, its bases). */
+inline FarmReport processArchiveSelected(const path_t &archive_path, const path_t &mates1_out, const Selection &sel, const Settings &set) {
+  sel.check("processArchiveSelected");
   Archive archive(archive_path);
   const std::size_t n_blocks = archive.chunkOffsets().size() - 1;
-  std::unique_ptr<DecodeIndexFile> sidecar = detail::openDecodeIndex(archive_path);
+  detail::IndexSidecar sidecar(archive_path);
   detail::ChunkVerifier verifier(archive_path, n_blocks, false);
-  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n_blocks, 1))));
-  if (set.devices.empty()) throw std::invalid_argument(name + ": no device");
-  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp(T);
-  detail::runWorkers(T, [&](unsigned t) {
-    wksp[t] = std::make_unique<DecompressionWorkspace>(&archive.meta(), set.devices[t % set.devices.size()]);
-    wksp[t]->setVerify(verifier.on());
-  });
-  const auto t0 = std::chrono::steady_clock::now();
+  struct Worker : detail::RestoreWorker {
+    using RestoreWorker::RestoreWorker;
+    uint64_t report[FQGPU_TAIL_REPORT_WORDS], sum[FQGPU_TAIL_REPORT_WORDS] = {};  // (the longest of the reports)
+  };
+  const unsigned W = sel.reportWords();
+  auto farm = detail::pieceFarm("processArchiveSelected", n_blocks, set,
+                                [&](unsigned, int device) { return Worker(archive.meta(), device, verifier.on()); });
   OrderedPieceWriter writer(mates1_out, n_blocks);
-  std::vector<InputStats> istats(T);
-  std::vector<std::vector<uint64_t>> reports(T, std::vector<uint64_t>(W, 0));
-  FarmReport rep;
-  rep.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0}, used_blocks{0}, used_bytes{0};
-  std::atomic<bool> stopped{false};
-  detail::runWorkers(T, [&](unsigned t) {
-    CompressedBuffersSrc cbs;
-    FastqChunk piece;
-    uint64_t report[FQGPU_TAIL_REPORT_WORDS];  // (the longest of the reports)
-    for (;;) {
-      const std::size_t k = next.fetch_add(1);  // (in order: whoever waits in the writer waits for blocks already taken)
-      if (stopped.load() || k >= n_blocks) break;
-      StageClock clk;
-      archive.readBlockAt(k, cbs);
-      if (sidecar && sidecar->get(cbs)) {
-        used_blocks.fetch_add(1);
-        used_bytes.fetch_add(cbs.decode_index[0].size() + cbs.decode_index[1].size());
-      }
-      clk.lap("read");
-      if (tail) wksp[t]->decodeChunkTailTrimmed(piece, cbs, adapter, *tail, trim, filter, report);
-      else if (adapter) wksp[t]->decodeChunkClipped(piece, cbs, *adapter, trim, filter, report);
-      else if (trim) wksp[t]->decodeChunkTrimmed(piece, cbs, *trim, filter, report);
-      else wksp[t]->decodeChunkFiltered(piece, cbs, *filter, report);
-      clk.lap("decode");
-      verifier.check(cbs, wksp[t]->lastDigest());  // (before anything of the chunk reaches the file)
-      for (unsigned i = 0; i < W; ++i) reports[t][i] += report[i];
-      istats[t].raw += piece.raw_data.size();
-      istats[t].n_records += static_cast<std::size_t>(report[1]);
-      rep.blocks_per_worker[t]++;
-      try {
-        writer.writePiece(k, piece.raw_data.data(), piece.raw_data.size());
-      } catch (const OrderedPieceWriter::Aborted &) {
-        break;  // (another worker has failed and says why)
-      }
-      clk.lap("write");
-      clk.done(static_cast<unsigned>(k));
-    }
-  }, [&] { stopped.store(true); writer.abort(); });
+  farm.run([&](Worker &w, std::size_t k, StageClock &clk, InputStats &in) {
+    archive.readBlockAt(k, w.cbs);
+    sidecar.get(w.cbs);
+    clk.lap("read");
+    w.wksp.decodeChunkSelected(w.piece, w.cbs, sel, w.report);
+    clk.lap("decode");
+    verifier.check(w.cbs, w.wksp.lastDigest());  // (before anything of the chunk reaches the file)
+    for (unsigned i = 0; i < W; ++i) w.sum[i] += w.report[i];
+    in.raw += w.piece.raw_data.size();
+    in.n_records += static_cast<std::size_t>(w.report[1]);
+    writer.writePiece(k, w.piece.raw_data.data(), w.piece.raw_data.size());
+    clk.lap("write");
+    return true;
+  }, [&] { writer.abort(); });
   writer.flush();
-  rep.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  std::vector<uint64_t> &sum = trim || adapter || tail ? rep.trim : rep.filter;
+  FarmReport rep = farm.report();
+  std::vector<uint64_t> &sum = sel.trims() ? rep.trim : rep.filter;
   sum.assign(W, 0);
-  for (unsigned t = 0; t < T; ++t) {
-    rep.in += istats[t];
-    for (unsigned i = 0; i < W; ++i) sum[i] += reports[t][i];
-  }
-  rep.indexed_blocks = used_blocks.load();
-  rep.index_bytes = used_bytes.load();
+  for (const auto &w : farm.workers())
+    for (unsigned i = 0; i < W; ++i) sum[i] += w->sum[i];
+  sidecar.report(rep);
   verifier.report(rep);
   return rep;
-}
-}  // namespace detail
-
-/** Extension: `d --min-len / --max-len / --max-n / --min-mean-q / --max-low-q` -- the reads that pass `filter`, in input
- *  order, as the FASTQ bytes a plain restore writes for them (detail::processArchiveSelected).  rep.in counts what was
- *  written, rep.filter what was read and why it was dropped. */
-inline FarmReport processArchiveFiltered(const path_t &archive_path, const path_t &mates1_out, const fqgpu_filter &filter,
-                                         const Settings &set) {
-  return detail::processArchiveSelected(archive_path, mates1_out, nullptr, &filter, set, "processArchiveFiltered");
-}
-
-/** Extension: `d --cut-front / --cut-tail / --trim-q5 / --trim-q3 / --crop`, with or without the filter options -- the reads
- *  trimmed by `trim` and then judged by `filter` (nullptr: every read that is not emptied is kept), in input order, as
- *  trimmed FASTQ (detail::processArchiveSelected).  rep.in counts what was written, rep.trim what was read, what was cut and
- *  why reads were dropped. */
-inline FarmReport processArchiveTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_trim &trim,
-                                        const fqgpu_filter *filter, const Settings &set) {
-  return detail::processArchiveSelected(archive_path, mates1_out, &trim, filter, set, "processArchiveTrimmed");
-}
-
-/** Extension: `d --adapter SEQ [--adapter-overlap N] [--adapter-err PCT]`, with or without the trim and filter options -- the
- *  reads clipped at the 3' adapter (fqgpu_chunk_clip's step 0), then trimmed by `trim` (nullptr: nothing more is cut) and
- *  judged by `filter` (nullptr: every read that is not emptied is kept), in input order (detail::processArchiveSelected).
- *  rep.in counts what was written; rep.trim is the trim's report with words 14 and 15, the reads in which the adapter was
- *  found and the bases it took. */
-inline FarmReport processArchiveClipped(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter &adapter,
-                                        const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
-  return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveClipped", &adapter);
-}
-
-/** Extension: `d [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q]`, with or without the adapter,
- *  trim and filter options -- the reads clipped at the 3' adapter (nullptr: none), their poly-X tail and everything from a
- *  sliding-window quality drop on taken (fqgpu_chunk_tailtrim's steps 0b and 1b), then trimmed by `trim` (nullptr: nothing
- *  more is cut) and judged by `filter` (nullptr: every read that is not emptied is kept), in input order
- *  (detail::processArchiveSelected).  rep.in counts what was written; rep.trim has FQGPU_TAIL_REPORT_WORDS words here: the
- *  clip's sixteen, then the reads with a poly tail, the bases it took, the reads the window cut and the bases it took. */
-inline FarmReport processArchiveTailTrimmed(const path_t &archive_path, const path_t &mates1_out, const fqgpu_adapter *adapter,
-                                            const fqgpu_tail &tail, const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
-  return detail::processArchiveSelected(archive_path, mates1_out, trim, filter, set, "processArchiveTailTrimmed", adapter, &tail);
 }
 
 namespace detail {
@@ -867,9 +841,9 @@ struct PairedReport {
 };
 
 /** Extension: `d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq>` -- two archives whose records are mates restored in
- *  step: record i of both outputs are mates, and a pair is written only if BOTH mates pass.  Every selection step of
- *  processArchiveTailTrimmed applies to both mates (adapter1 to mate 1, adapter2 to mate 2; each of the five may be nullptr:
- *  with all of them nullptr both files are restored whole and only the read ids are checked).
+ *  step: record i of both outputs are mates, and a pair is written only if BOTH mates pass.  Every step of `sel`
+ *  (processArchiveSelected) applies to both mates, but that mate 2 is clipped at adapter2 instead of sel.adapter; each of the
+ *  five may be nullptr: with all of them nullptr both files are restored whole and only the read ids are checked.
  *  The two archives need the same number of records and nothing else: their chunks are cut by bytes, so a chunk of archive 1
  *  -- the work unit, handed out in order -- holds the records [A, B) and planMateUnit(counts2, A, B) names the one to
  *  three chunks of archive 2 that hold their mates.  A worker owns one workspace per archive, both on its device, and needs
@@ -882,15 +856,12 @@ struct PairedReport {
  *  once.  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
  *  nor a `.part` file.  Throws before any output is opened when the archives' record totals differ. */
 inline PairedReport processArchivePaired(const path_t &archive1_path, const path_t &out1, const path_t &archive2_path, const path_t &out2,
-                                         const fqgpu_adapter *adapter1, const fqgpu_adapter *adapter2, const fqgpu_tail *tail,
-                                         const fqgpu_trim *trim, const fqgpu_filter *filter, const Settings &set) {
+                                         const fqgpu_adapter *adapter2, const Selection &sel, const Settings &set) {
   const std::string name("processArchivePaired");
-  if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
-  for (const fqgpu_adapter *a : {adapter1, adapter2})
-    if (a && fqgpu_adapter_check(a) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
-  if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-  if (filter && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
-  if (set.devices.empty()) throw std::invalid_argument(name + ": no device");
+  Selection sel2 = sel;
+  sel2.adapter = adapter2;
+  sel.check(name, true);
+  sel2.check(name, true);
   Archive archive1(archive1_path), archive2(archive2_path);
   const std::vector<uint32_t> counts1 = archive1.recordCounts(), counts2 = archive2.recordCounts();
   const std::size_t n1 = counts1.size(), n2 = counts2.size();
@@ -901,126 +872,101 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   if (start1[n1] != total2)
     throw std::runtime_error(name + ": " + archive1_path.string() + " holds " + std::to_string(start1[n1]) + " records, " +
                              archive2_path.string() + " " + std::to_string(total2) + ": not the two files of one paired run");
-  std::unique_ptr<DecodeIndexFile> sidecar1 = detail::openDecodeIndex(archive1_path), sidecar2 = detail::openDecodeIndex(archive2_path);
+  detail::IndexSidecar sidecar1(archive1_path), sidecar2(archive2_path);
   detail::ChunkVerifier verifier1(archive1_path, n1, false), verifier2(archive2_path, n2, false);
-  const unsigned T = std::max(1u, std::min<unsigned>(set.n_threads, static_cast<unsigned>(std::max<std::size_t>(n1, 1))));
-  std::vector<std::unique_ptr<DecompressionWorkspace>> wksp1(T), wksp2(T);
-  detail::runWorkers(T, [&](unsigned t) {
-    const int device = set.devices[t % set.devices.size()];
-    wksp1[t] = std::make_unique<DecompressionWorkspace>(&archive1.meta(), device);
-    wksp2[t] = std::make_unique<DecompressionWorkspace>(&archive2.meta(), device);
-    wksp1[t]->setVerify(verifier1.on());
-    wksp2[t]->setVerify(verifier2.on());
-  });
-  const auto t0 = std::chrono::steady_clock::now();
-  OrderedPieceWriter writer1(out1, n1), writer2(out2, n1);
   constexpr unsigned W = FQGPU_TAIL_REPORT_WORDS;
-  std::vector<InputStats> istats1(T), istats2(T);
-  std::vector<std::vector<uint64_t>> reports1(T, std::vector<uint64_t>(W, 0)), reports2(T, std::vector<uint64_t>(W, 0));
-  PairedReport rep;
-  rep.mate1.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  rep.mate2.blocks_per_worker.assign(std::max(1u, set.n_threads), 0);
-  std::atomic<std::size_t> next{0}, used1{0}, used_bytes1{0}, used2{0}, used_bytes2{0}, decodes2{0};
-  std::atomic<bool> stopped{false};
-  detail::runWorkers(T, [&](unsigned t) {
-    CompressedBuffersSrc cbs1, cbs2;
-    FastqChunk piece1, piece2;
+  struct Worker {  // one workspace per archive, both on the worker's device; `in`, blocks and sums of mate 2 (mate 1's `in` and blocks are the farm's)
+    detail::RestoreWorker m1, m2;
     std::vector<uint8_t> k1, k, mark, keep;
-    uint64_t report[W];
-    DecompressionWorkspace &w1 = *wksp1[t], &w2 = *wksp2[t];
-    for (;;) {
-      const std::size_t unit = next.fetch_add(1);  // (in order: whoever waits in a writer waits for units already taken)
-      if (stopped.load() || unit >= n1) break;
-      StageClock clk;
-      const std::size_t A = start1[unit], n = counts1[unit];
-      piece1.clear();
-      piece2.clear();
-      piece1.idx = piece2.idx = static_cast<unsigned>(unit);
-      std::size_t len1 = 0, len2 = 0;
-      if (n) {
-        archive1.readBlockAt(unit, cbs1);
-        if (sidecar1 && sidecar1->get(cbs1)) {
-          used1.fetch_add(1);
-          used_bytes1.fetch_add(cbs1.decode_index[0].size() + cbs1.decode_index[1].size());
-        }
-        clk.lap("read");
-        w1.stagePairedChunk(cbs1);
-        verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
-        k1.assign((n + 7) / 8, 0);
-        (void)w1.selectMarked(adapter1, tail, trim, filter, 0, n, nullptr, nullptr, 0, report, k1.data());
-        clk.lap("mate 1");
-        k.assign((n + 7) / 8, 0);
-        for (const MatePiece &pc : planMateUnit(counts2, A, A + n)) {
-          archive2.readBlockAt(pc.block, cbs2);
-          if (sidecar2 && sidecar2->get(cbs2)) {
-            used2.fetch_add(1);
-            used_bytes2.fetch_add(cbs2.decode_index[0].size() + cbs2.decode_index[1].size());
-          }
-          w2.stagePairedChunk(cbs2);
-          verifier2.check(cbs2, w2.lastDigest());
-          decodes2.fetch_add(1);
-          rep.mate2.blocks_per_worker[t]++;
-          const std::size_t count = pc.end - pc.first, at = pc.at;
-          const std::size_t differs = w1.pairNames(at, w2, pc.first, count);
-          if (differs != static_cast<std::size_t>(-1))
-            throw std::runtime_error(name + ": record " + std::to_string(A + at + differs) + ": the read ids of the two mates differ (chunk " +
-                                     std::to_string(unit) + " of " + archive1_path.string() + ", chunk " + std::to_string(pc.block) + " of " +
-                                     archive2_path.string() + ")");
-          mark.resize((count + 7) / 8);
-          keep.assign((count + 7) / 8, 0);
-          detail::sliceBits(k1.data(), at, count, mark.data());
-          piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
-          len2 += w2.selectMarked(adapter2, tail, trim, filter, pc.first, pc.end, mark.data(),
-                                  reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2, cbs2.original_size.total, report, keep.data());
-          for (unsigned i = 0; i < W; ++i) reports2[t][i] += report[i];
-          detail::placeBits(keep.data(), count, k.data(), at);
-        }
-        clk.lap("mate 2");
-        piece1.raw_data.resize(cbs1.original_size.total);
-        len1 = w1.selectMarked(adapter1, tail, trim, filter, 0, n, k.data(), reinterpret_cast<uint8_t *>(piece1.raw_data.data()),
-                               piece1.raw_data.size(), report, nullptr);
-        for (unsigned i = 0; i < W; ++i) reports1[t][i] += report[i];
-        istats1[t].n_records += static_cast<std::size_t>(report[1]);
-        istats2[t].n_records += static_cast<std::size_t>(report[1]);
-        clk.lap("gather 1");
+    uint64_t report[W], sum1[W] = {}, sum2[W] = {};
+    InputStats in2;
+    unsigned decodes2 = 0;
+  };
+  auto farm = detail::pieceFarm(name, n1, set, [&](unsigned, int device) {
+    return Worker{{archive1.meta(), device, verifier1.on()}, {archive2.meta(), device, verifier2.on()}};
+  });
+  OrderedPieceWriter writer1(out1, n1), writer2(out2, n1);
+  farm.run([&](Worker &w, std::size_t unit, StageClock &clk, InputStats &in1) {
+    DecompressionWorkspace &w1 = w.m1.wksp, &w2 = w.m2.wksp;
+    CompressedBuffersSrc &cbs1 = w.m1.cbs, &cbs2 = w.m2.cbs;
+    FastqChunk &piece1 = w.m1.piece, &piece2 = w.m2.piece;
+    const std::size_t A = start1[unit], n = counts1[unit];
+    piece1.clear();
+    piece2.clear();
+    piece1.idx = piece2.idx = static_cast<unsigned>(unit);
+    std::size_t len1 = 0, len2 = 0;
+    if (n) {
+      archive1.readBlockAt(unit, cbs1);
+      sidecar1.get(cbs1);
+      clk.lap("read");
+      w1.stagePairedChunk(cbs1);
+      verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
+      w.k1.assign((n + 7) / 8, 0);
+      (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
+      clk.lap("mate 1");
+      w.k.assign((n + 7) / 8, 0);
+      for (const MatePiece &pc : planMateUnit(counts2, A, A + n)) {
+        archive2.readBlockAt(pc.block, cbs2);
+        sidecar2.get(cbs2);
+        w2.stagePairedChunk(cbs2);
+        verifier2.check(cbs2, w2.lastDigest());
+        w.decodes2++;
+        const std::size_t count = pc.end - pc.first, at = pc.at;
+        const std::size_t differs = w1.pairNames(at, w2, pc.first, count);
+        if (differs != static_cast<std::size_t>(-1))
+          throw std::runtime_error(name + ": record " + std::to_string(A + at + differs) + ": the read ids of the two mates differ (chunk " +
+                                   std::to_string(unit) + " of " + archive1_path.string() + ", chunk " + std::to_string(pc.block) + " of " +
+                                   archive2_path.string() + ")");
+        w.mark.resize((count + 7) / 8);
+        w.keep.assign((count + 7) / 8, 0);
+        detail::sliceBits(w.k1.data(), at, count, w.mark.data());
+        piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
+        len2 += w2.selectMarked(sel2, pc.first, pc.end, w.mark.data(), reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2,
+                                cbs2.original_size.total, w.report, w.keep.data());
+        for (unsigned i = 0; i < W; ++i) w.sum2[i] += w.report[i];
+        detail::placeBits(w.keep.data(), count, w.k.data(), at);
       }
-      piece1.raw_data.resize(len1);
-      piece2.raw_data.resize(len2);
-      istats1[t].raw += len1;
-      istats2[t].raw += len2;
-      rep.mate1.blocks_per_worker[t]++;
-      try {
-        writer1.writePiece(unit, piece1.raw_data.data(), len1);
-        writer2.writePiece(unit, piece2.raw_data.data(), len2);
-      } catch (const OrderedPieceWriter::Aborted &) {
-        break;  // (another worker has failed and says why)
-      }
-      clk.lap("write");
-      clk.done(static_cast<unsigned>(unit));
+      clk.lap("mate 2");
+      piece1.raw_data.resize(cbs1.original_size.total);
+      len1 = w1.selectMarked(sel, 0, n, w.k.data(), reinterpret_cast<uint8_t *>(piece1.raw_data.data()), piece1.raw_data.size(), w.report, nullptr);
+      for (unsigned i = 0; i < W; ++i) w.sum1[i] += w.report[i];
+      in1.n_records += static_cast<std::size_t>(w.report[1]);
+      w.in2.n_records += static_cast<std::size_t>(w.report[1]);
+      clk.lap("gather 1");
     }
-  }, [&] { stopped.store(true); writer1.abort(); writer2.abort(); });
+    piece1.raw_data.resize(len1);
+    piece2.raw_data.resize(len2);
+    in1.raw += len1;
+    w.in2.raw += len2;
+    writer1.writePiece(unit, piece1.raw_data.data(), len1);
+    writer2.writePiece(unit, piece2.raw_data.data(), len2);
+    clk.lap("write");
+    return true;
+  }, [&] { writer1.abort(); writer2.abort(); });
   writer1.flush();
   writer2.flush();
-  rep.mate1.seconds = rep.mate2.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  PairedReport rep;
+  rep.mate1 = farm.report();
+  rep.mate2.seconds = rep.mate1.seconds;
+  rep.mate2.blocks_per_worker.assign(rep.mate1.blocks_per_worker.size(), 0);
   rep.mate1.trim.assign(W, 0);
   rep.mate2.trim.assign(W, 0);
-  for (unsigned t = 0; t < T; ++t) {
-    rep.mate1.in += istats1[t];
-    rep.mate2.in += istats2[t];
+  for (std::size_t t = 0; t < farm.workers().size(); ++t) {
+    const Worker &w = *farm.workers()[t];
+    rep.mate2.in += w.in2;
+    rep.mate2.blocks_per_worker[t] = w.decodes2;
+    rep.decodes2 += w.decodes2;
     for (unsigned i = 0; i < W; ++i) {
-      rep.mate1.trim[i] += reports1[t][i];
-      rep.mate2.trim[i] += reports2[t][i];
+      rep.mate1.trim[i] += w.sum1[i];
+      rep.mate2.trim[i] += w.sum2[i];
     }
   }
-  rep.mate1.indexed_blocks = used1.load();
-  rep.mate1.index_bytes = used_bytes1.load();
-  rep.mate2.indexed_blocks = used2.load();
-  rep.mate2.index_bytes = used_bytes2.load();
+  sidecar1.report(rep.mate1);
+  sidecar2.report(rep.mate2);
   verifier1.report(rep.mate1);
   verifier2.report(rep.mate2);
   rep.blocks1 = n1;
   rep.blocks2 = n2;
-  rep.decodes2 = decodes2.load();
   rep.pairs = start1[n1];
   rep.kept = rep.mate1.trim[1];
   rep.dropped_mate1_only = rep.mate2.trim[20];  // mate 2 passes, its mark -- mate 1's verdict -- says no

@@ -534,6 +534,33 @@ public:
 
 };
 
+/** Extension: what a selecting restore does to every read, as one value -- the steps in the order they run: the clip at the
+ *  3' adapter, the poly-X tail and the sliding-window cut, the trim, then the filter that judges what is left.  nullptr: the
+ *  step is off (no filter: every read that is not emptied is kept).  The pointers are not owned. */
+struct Selection {
+  const fqgpu_adapter *adapter = nullptr;
+  const fqgpu_tail *tail = nullptr;
+  const fqgpu_trim *trim = nullptr;
+  const fqgpu_filter *filter = nullptr;
+  /** something is cut: the counters are a trim report (FarmReport::trim), not a filter report (FarmReport::filter) */
+  [[nodiscard]] bool trims() const { return adapter || tail || trim; }
+  /** the fqgpu_chunk_* call that serves it, by the name of its first step */
+  [[nodiscard]] const char *step() const { return tail ? "tail trim" : adapter ? "clip" : trim ? "trim" : "filter"; }
+  /** the words of that call's report (only a tail has more than the filter's and the trim's) */
+  [[nodiscard]] unsigned reportWords() const {
+    static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one report size for both");
+    return tail ? FQGPU_TAIL_REPORT_WORDS : FQGPU_FILTER_REPORT_WORDS;
+  }
+  /** throws std::invalid_argument("<name>: ...") for a step its fqgpu_*_check refuses.  A selection that cuts nothing needs
+   *  its filter; may_be_empty (the paired restore, which then restores both files whole): not even that. */
+  void check(const std::string &name, bool may_be_empty = false) const {
+    if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
+    if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
+    if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
+    if ((filter || !(trims() || may_be_empty)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+  }
+};
+
 class DecompressionWorkspace : public Workspace {
 public:
   explicit DecompressionWorkspace(const DatasetMeta *meta, int device = 0) : Workspace(meta, device) {}
@@ -661,50 +688,44 @@ public:
     return fastaOnDevice(cbs, first, end, nullptr);
   }
 
-  /** Extension: the reads of the chunk that pass `filter`, as the canonical FASTQ bytes decodeChunk lays out for them, into
-   *  piece.raw_data (fqgpu_chunk_filter); `report` receives the chunk's FQGPU_FILTER_REPORT_WORDS counters.  The chunk is
-   *  decoded check-only -- nothing of it comes back -- with the block's decode indexes when present, its digest is taken
-   *  and kept for lastDigest() when setVerify is on (the digest of the WHOLE restored chunk, so the caller compares it with
-   *  the writer's as always), and only the kept bytes cross the link: one copy.  piece.idx = cbs.chunk_idx, piece.records
+  /** Extension: the reads of the chunk as `sel` leaves them -- clipped, tail-trimmed, trimmed, then judged by its filter; with
+   *  a filter alone the reads that pass, as the canonical FASTQ bytes decodeChunk lays out for them -- into piece.raw_data.
+   *  ONE call serves a selection, named by its first step: fqgpu_chunk_tailtrim, fqgpu_chunk_clip, fqgpu_chunk_trim or
+   *  fqgpu_chunk_filter; `report` receives the chunk's sel.reportWords() counters (with an adapter words 14 and 15 among
+   *  them).  The chunk is decoded check-only -- nothing of it comes back -- with the block's decode indexes when present, its
+   *  digest is taken first and kept for lastDigest() when setVerify is on (the digest of the WHOLE restored chunk, so the
+   *  caller compares it with the writer's as always), and only the kept bytes cross the link, into a buffer of the chunk's
+   *  recorded size: they are never more than the chunk, so there is no size query.  piece.idx = cbs.chunk_idx, piece.records
    *  stays empty.  There is no host fallback and FQGPU_SHIM_HOST_HEADERS does not apply: a chunk the device refuses throws
    *  std::runtime_error naming the chunk and the record. */
-  void decodeChunkFiltered(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_filter &filter, uint64_t *report) {
-    decodeChunkSelected(piece, cbs, nullptr, &filter, report, "decodeChunkFiltered");
-  }
-
-  /** Extension: the reads of the chunk trimmed by `trim` and then judged by `filter` (nullptr: every read that is not emptied
-   *  is kept), as trimmed canonical FASTQ bytes, into piece.raw_data (fqgpu_chunk_trim); `report` receives the chunk's
-   *  FQGPU_TRIM_REPORT_WORDS counters.  Works as decodeChunkFiltered does: the chunk is decoded check-only with the block's
-   *  decode indexes when present, the digest of the WHOLE restored chunk is taken first and kept for lastDigest() when
-   *  setVerify is on, and one call fills a buffer of the chunk's recorded size, which is always enough.  No host fallback: a
-   *  chunk the device refuses throws std::runtime_error naming the chunk and the record. */
-  void decodeChunkTrimmed(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim &trim, const fqgpu_filter *filter, uint64_t *report) {
-    decodeChunkSelected(piece, cbs, &trim, filter, report, "decodeChunkTrimmed");
-  }
-
-  /** Extension: the reads of the chunk clipped at the 3' adapter `adapter`, trimmed by `trim` (nullptr: nothing is cut beyond
-   *  the clip) and then judged by `filter` (nullptr: every read that is not emptied is kept), as decodeChunkTrimmed lays them
-   *  out (fqgpu_chunk_clip); `report` receives the chunk's FQGPU_TRIM_REPORT_WORDS counters, words 14 and 15 among them.
-   *  Works as decodeChunkTrimmed does in every other respect. */
-  void decodeChunkClipped(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_adapter &adapter, const fqgpu_trim *trim,
-                          const fqgpu_filter *filter, uint64_t *report) {
-    decodeChunkSelected(piece, cbs, trim, filter, report, "decodeChunkClipped", &adapter);
-  }
-
-  /** Extension: the reads of the chunk clipped at `adapter` (nullptr: none), their poly-X tail and the sliding-window cut of
-   *  `tail` taken, trimmed by `trim` (nullptr: nothing more is cut) and then judged by `filter` (nullptr: every read that is not
-   *  emptied is kept), as decodeChunkTrimmed lays them out (fqgpu_chunk_tailtrim); `report` receives the chunk's
-   *  FQGPU_TAIL_REPORT_WORDS counters.  Works as decodeChunkClipped does in every other respect. */
-  void decodeChunkTailTrimmed(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_adapter *adapter, const fqgpu_tail &tail,
-                              const fqgpu_trim *trim, const fqgpu_filter *filter, uint64_t *report) {
-    decodeChunkSelected(piece, cbs, trim, filter, report, "decodeChunkTailTrimmed", adapter, &tail);
+  void decodeChunkSelected(FastqChunk &piece, CompressedBuffersSrc &cbs, const Selection &sel, uint64_t *report) {
+    StageClock clk;
+    last_digest_ = {};
+    sel.check("decodeChunkSelected");
+    piece.clear();
+    piece.idx = cbs.chunk_idx;
+    stageChunk(cbs, "decodeChunkSelected", &clk);
+    piece.raw_data.resize(cbs.original_size.total);
+    uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
+    const std::size_t cap = piece.raw_data.size();
+    std::size_t len = 0;
+    // (four calls, not fqgpu_chunk_select_marked: each runs its own kernel instantiation and fills its own report)
+    const int rc = sel.tail      ? fqgpu_chunk_tailtrim(ctx_, sel.adapter, sel.tail, sel.trim, sel.filter, out, cap, &len, report, nullptr, nullptr, nullptr)
+                   : sel.adapter ? fqgpu_chunk_clip(ctx_, sel.adapter, sel.trim, sel.filter, out, cap, &len, report, nullptr, nullptr)
+                   : sel.trim    ? fqgpu_chunk_trim(ctx_, sel.trim, sel.filter, out, cap, &len, report, nullptr, nullptr)
+                                 : fqgpu_chunk_filter(ctx_, sel.filter, out, cap, &len, report, nullptr);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("decodeChunkSelected: chunk " + std::to_string(cbs.chunk_idx) + ": the " + sel.step() + ": " + fqgpu_strerror(rc));
+    piece.raw_data.resize(len);
+    clk.lap(sel.step());
+    clk.done(cbs.chunk_idx);
   }
 
   /** Extension (paired restores, process.hpp: processArchivePaired): the three steps a worker makes a pair of chunks of.
    *  stagePairedChunk decodes the chunk check-only, takes its digest for lastDigest() when setVerify is on and leaves it on
-   *  the handle's staging block (as decodeChunkFiltered does in front of its filter call); there is no host fallback.
+   *  the handle's staging block (as decodeChunkSelected does in front of its selecting call); there is no host fallback.
    *  selectMarked is fqgpu_chunk_select_marked on the chunk staged last: records [first, end) against `mark` (nullptr: none;
-   *  (end - first + 7) / 8 bytes), each of adapter, tail, trim and filter nullptr for "off"; out == nullptr asks for the
+   *  (end - first + 7) / 8 bytes), any of sel's steps, or all, off; out == nullptr asks for the
    *  counters and the keep bits alone; -> the bytes written to out (at most out_cap: the chunk's recorded size is always
    *  enough).  pairNames is fqgpu_chunk_pair_names: the read ids of this handle's staged records first + i against those of
    *  `mate`'s mate_first + i, i < count -> the first i that differs, (size_t)-1 when none does.  A call the device refuses
@@ -715,11 +736,11 @@ public:
     staged_idx_ = cbs.chunk_idx;
     clk.done(cbs.chunk_idx);
   }
-  std::size_t selectMarked(const fqgpu_adapter *adapter, const fqgpu_tail *tail, const fqgpu_trim *trim, const fqgpu_filter *filter,
-                           std::size_t first, std::size_t end, const uint8_t *mark, uint8_t *out, std::size_t out_cap, uint64_t *report,
-                           uint8_t *keep_out) {
+  std::size_t selectMarked(const Selection &sel, std::size_t first, std::size_t end, const uint8_t *mark, uint8_t *out, std::size_t out_cap,
+                           uint64_t *report, uint8_t *keep_out) {
     std::size_t len = 0;
-    const int rc = fqgpu_chunk_select_marked(ctx_, adapter, tail, trim, filter, first, end, mark, out, out_cap, &len, report, keep_out, nullptr, nullptr);
+    const int rc = fqgpu_chunk_select_marked(ctx_, sel.adapter, sel.tail, sel.trim, sel.filter, first, end, mark, out, out_cap, &len, report, keep_out,
+                                             nullptr, nullptr);
     if (rc != FQGPU_OK)
       throw std::runtime_error("selectMarked: chunk " + std::to_string(staged_idx_) + ", records " + std::to_string(first) + ":" +
                                std::to_string(end) + ": " + fqgpu_strerror(rc));
@@ -752,39 +773,6 @@ public:
   }
 
 private:
-  /** decodeChunkFiltered (trim == nullptr; the filter is needed), decodeChunkTrimmed and decodeChunkClipped (with an adapter,
-   *  trim and filter may both be nullptr) and decodeChunkTailTrimmed (with a tail, all three may be), `who` of the four: the
-   *  check-only decode, the digest, then ONE fqgpu_chunk_filter / fqgpu_chunk_trim / fqgpu_chunk_clip / fqgpu_chunk_tailtrim
-   *  into a buffer of the chunk's recorded size -- the kept bytes are never more than the
-   *  chunk, so there is no size query */
-  void decodeChunkSelected(FastqChunk &piece, CompressedBuffersSrc &cbs, const fqgpu_trim *trim, const fqgpu_filter *filter,
-                           uint64_t *report, const char *who, const fqgpu_adapter *adapter = nullptr, const fqgpu_tail *tail = nullptr) {
-    StageClock clk;
-    last_digest_ = {};
-    const std::string name(who), step(tail ? "tail trim" : adapter ? "clip" : trim ? "trim" : "filter");
-    const auto refused = [&](const std::string &what) {
-      return std::runtime_error(name + ": chunk " + std::to_string(cbs.chunk_idx) + ": " + what);
-    };
-    if (tail && fqgpu_tail_check(tail) != FQGPU_OK) throw std::invalid_argument(name + ": a tail fqgpu_tail_check refuses");
-    if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
-    if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
-    if ((filter || !(trim || adapter || tail)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
-    piece.clear();
-    piece.idx = cbs.chunk_idx;
-    stageChunk(cbs, who, &clk);
-    piece.raw_data.resize(cbs.original_size.total);
-    uint8_t *const out = reinterpret_cast<uint8_t *>(piece.raw_data.data());
-    std::size_t len = 0;
-    const int src = tail    ? fqgpu_chunk_tailtrim(ctx_, adapter, tail, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr, nullptr)
-                    : adapter ? fqgpu_chunk_clip(ctx_, adapter, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
-                    : trim  ? fqgpu_chunk_trim(ctx_, trim, filter, out, piece.raw_data.size(), &len, report, nullptr, nullptr)
-                         : fqgpu_chunk_filter(ctx_, filter, out, piece.raw_data.size(), &len, report, nullptr);
-    if (src != FQGPU_OK) throw refused("the " + step + ": " + fqgpu_strerror(src));
-    piece.raw_data.resize(len);
-    clk.lap(step.c_str());
-    clk.done(cbs.chunk_idx);
-  }
-
   /** The chunk decoded check-only -- nothing of it comes back -- with the block's decode indexes when present, and its
    *  digest taken (setVerify): it is left on the handle's staging block, where the fqgpu_chunk_* calls find it.  No host
    *  fallback: a chunk the device refuses throws std::runtime_error naming the chunk and the record. */

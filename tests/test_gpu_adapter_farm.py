@@ -1,5 +1,5 @@
 """`fqc_tool d ... --adapter SEQ [--adapter-overlap N] [--adapter-err PCT]`: the clipped restore of a whole archive through the
-farm (process.hpp: processArchiveClipped), against the numpy restatement (adapter_ref.py) of the input file, byte for byte."""
+farm (process.hpp: processArchiveSelected), against the numpy restatement (adapter_ref.py) of the input file, byte for byte."""
 import json
 import os
 import shutil

@@ -1,5 +1,5 @@
 """`fqc_tool d ... --max-n / --min-mean-q / ...`: the filtered restore of a whole archive through the farm (process.hpp:
-processArchiveFiltered), against the numpy restatement (filter_ref.py) of the input file, byte for byte."""
+processArchiveSelected), against the numpy restatement (filter_ref.py) of the input file, byte for byte."""
 import json
 import os
 import shutil

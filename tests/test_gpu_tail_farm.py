@@ -1,5 +1,5 @@
 """`fqc_tool d ... [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q]`: the restore of a whole archive
-with the tail trims through the farm (process.hpp: processArchiveTailTrimmed), against the numpy restatement (tail_ref.py) of
+with the tail trims through the farm (process.hpp: processArchiveSelected), against the numpy restatement (tail_ref.py) of
 the input file, byte for byte."""
 import json
 import os

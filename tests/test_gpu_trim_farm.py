@@ -1,5 +1,5 @@
 """`fqc_tool d ... --cut-front / --cut-tail / --trim-q5 / --trim-q3 / --crop`: the trimmed restore of a whole archive through
-the farm (process.hpp: processArchiveTrimmed), against the numpy restatement (trim_ref.py) of the input file, byte for byte."""
+the farm (process.hpp: processArchiveSelected), against the numpy restatement (trim_ref.py) of the input file, byte for byte."""
 import json
 import os
 import shutil

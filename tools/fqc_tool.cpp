@@ -435,19 +435,14 @@ int main(int argc, char **argv) {
       set.build_index = set.decode_index && !range;
       set.decode_index = false;
     }
+    const Selection sel{clipped ? &adapter : nullptr, tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr};
     PairedReport paired;
-    if (mate)
-      paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped ? &adapter : nullptr, clipped2 ? &adapter2 : nullptr,
-                                    tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr, set);
+    if (mate) paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped2 ? &adapter2 : nullptr, sel, set);
     const FarmReport r = mate ? paired.mate1
                          : check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
                          : comp    ? processReads(argv[2], argv[3], set)
-                         : tailed  ? processArchiveTailTrimmed(argv[2], argv[3], clipped ? &adapter : nullptr, tail, trimmed ? &trim : nullptr,
-                                                               filtered ? &filter : nullptr, set)
-                         : clipped ? processArchiveClipped(argv[2], argv[3], adapter, trimmed ? &trim : nullptr, filtered ? &filter : nullptr, set)
-                         : trimmed ? processArchiveTrimmed(argv[2], argv[3], trim, filtered ? &filter : nullptr, set)
-                         : filtered ? processArchiveFiltered(argv[2], argv[3], filter, set)
+                         : sel.trims() || filtered ? processArchiveSelected(argv[2], argv[3], sel, set)
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
@@ -494,12 +489,12 @@ int main(int argc, char **argv) {
       }
     }
     if (filtered && !mate) {
-      const auto w = [&](unsigned i) { return (unsigned long long)(trimmed || clipped || tailed ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
+      const auto w = [&](unsigned i) { return (unsigned long long)(sel.trims() ? r.trim[i] : r.filter[i]); };  // (words 0 .. 9 are the same)
       std::printf(", \"filter\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"dropped_short\": %llu, "
                   "\"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu}",
                   w(0), w(1), w(2), w(3), w(5), w(6), w(7), w(8), w(9));
     }
-    if ((trimmed || clipped || tailed) && !mate) {
+    if (sel.trims() && !mate) {
       const auto w = [&](unsigned i) { return (unsigned long long)r.trim[i]; };
       std::printf(", \"trim\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
                   "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
