@@ -172,6 +172,17 @@ _PROTOS = {
     "fqgpu_dblock_select_marked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
                                              C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),
+    "fqgpu_chunk_select_limited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_select_limited": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "fqgpu_overlap_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_overlap_merge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
+    "fqgpu_chunk_pair_overlap": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_pair_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_chunk_pair_names": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_pair_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_read_id_len": (C.c_size_t, [C.c_void_p, C.c_size_t]),
@@ -462,6 +473,56 @@ def _marked_call(fn, front, adapter, tail, trim, flt, first, end, mark=None, wan
                 win=win, places=places)
 
 
+LIMITED_REPORT_NAMES = MARKED_REPORT_NAMES + ("reads_cut_limit", "bases_cut_limit")
+READS_CUT_LIMIT, BASES_CUT_LIMIT = 21, 22
+
+
+def _limited_call(fn, front, adapter, tail, trim, flt, first, end, mark=None, limit=None, want_win=True, want_places=True, **kw):
+    """A device limited call (fqgpu_*_select_limited) -> as _marked_call; limit: None (NULL), or uint16 of end - first limits"""
+    n = max(end - first, 0)
+    win = np.zeros(n, dtype=np.uint32) if want_win else None
+    places = np.zeros((n, 4), dtype=np.uint16) if want_places else None
+    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.uint8)
+    limit = None if limit is None else np.ascontiguousarray(limit, dtype=np.uint16)
+    call = lambda *a: fn(*a[:len(front) + 4], first, end, _p(mark), _p(limit), *a[len(front) + 4:])  # noqa: E731
+    return dict(_select_call(call, front, (adapter, tail, trim, flt), n, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
+                win=win, places=places)
+
+
+OVERLAP_MAX_LEN, OVERLAP_ROWS, OVERLAP_HEAD_WORDS = 512, 1024, 16
+OVERLAP_WORDS = OVERLAP_HEAD_WORDS + OVERLAP_ROWS
+OVERLAP_NAMES = ("n_pairs", "pairs_overlapped", "pairs_read_through", "bases_behind_a", "bases_behind_b", "pairs_not_analysed", "mismatches",
+                 "overlap_bases", "fingerprint")
+
+
+def read_overlap(min_overlap=30, max_mism=5, max_err_pct=20, reserved=(0, 0, 0, 0, 0)):
+    """an fqgpu_overlap (include/fqgpu.h) as a uint32 array of eight words; the defaults are the tool's"""
+    return np.array([min_overlap, max_mism, max_err_pct, *reserved], dtype=np.uint32)
+
+
+def overlap_check(spec):
+    """fqgpu_overlap_check -> rc (host only)"""
+    return lib().fqgpu_overlap_check(_p(None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)))
+
+
+def overlap_merge(dst, src):
+    """fqgpu_overlap_merge: dst += src in place (two uint64 arrays) -> rc"""
+    assert dst.dtype == np.uint64 and src.dtype == np.uint64 and dst.flags.c_contiguous and src.flags.c_contiguous
+    return lib().fqgpu_overlap_merge(_p(dst), dst.size, _p(src), src.size)
+
+
+def _overlap_call(fn, front, count, spec, want_arrays=True, cap_words=None):
+    """A device overlap call -> dict(rc, out, limit_a, limit_b, insert): out a fresh uint64 array of OVERLAP_WORDS (cap_words: of
+    that many words instead), the three arrays uint16[count] or None"""
+    spec = None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)
+    cap = OVERLAP_WORDS if cap_words is None else cap_words
+    out = np.zeros(max(cap, 1), dtype=np.uint64)
+    arrays = [np.zeros(max(count, 1), dtype=np.uint16) if want_arrays else None for _ in range(3)]
+    rc = fn(*front, count, _p(spec), _p(out), cap, *[_p(a) for a in arrays])
+    la, lb, ins = [None if a is None else a[:count] for a in arrays]
+    return dict(rc=rc, out=out, limit_a=la, limit_b=lb, insert=ins)
+
+
 def read_id_len(header_line):
     """fqgpu_read_id_len (host only): the length of the read id of a header line (bytes, with its '@')"""
     line = np.frombuffer(bytes(header_line), dtype=np.uint8)
@@ -666,6 +727,17 @@ class DBlock:
         `first`; see _marked_call"""
         return _marked_call(lib().fqgpu_dblock_select_marked, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, **kw)
 
+    def select_limited(self, first, end, mark=None, limit=None, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_dblock_select_limited: select_marked with a per-record limit (uint16 of end - first entries; None: NULL) in
+        front of its steps -> as select_marked, report words 21 / 22 counted"""
+        return _limited_call(lib().fqgpu_dblock_select_limited, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, limit, **kw)
+
+    def pair_overlap(self, first, other, other_first, count, spec, **kw):
+        """fqgpu_dblock_pair_overlap: the mate overlap of this block's records first + i (mate 1) and `other`'s other_first + i
+        (mate 2), i < count, for `spec` (read_overlap) -> dict(rc, out, limit_a, limit_b, insert); see _overlap_call"""
+        return _overlap_call(lib().fqgpu_dblock_pair_overlap, (self.ctx.h, self.h, first, other.h if other is not None else None, other_first),
+                             count, spec, **kw)
+
     def pair_names(self, first, other, other_first, count):
         """fqgpu_dblock_pair_names: the read ids of this block's records first + i against `other`'s other_first + i, i < count
         -> (rc, mismatch): the first i whose ids differ, None when there is none"""
@@ -822,6 +894,15 @@ class Context:
         """fqgpu_chunk_select_marked: the records [first, end) of the chunk on the staging block, where chunk_tailtrim is
         valid, against `mark` -> dict(rc, out, out_len, report, keep, win, places); see _marked_call"""
         return _marked_call(lib().fqgpu_chunk_select_marked, (self.h,), adapter, tail, trim, flt, first, end, mark, **kw)
+
+    def chunk_select_limited(self, first, end, mark=None, limit=None, adapter=None, tail=None, trim=None, flt=None, **kw):
+        """fqgpu_chunk_select_limited: chunk_select_marked with a per-record limit -> as DBlock.select_limited"""
+        return _limited_call(lib().fqgpu_chunk_select_limited, (self.h,), adapter, tail, trim, flt, first, end, mark, limit, **kw)
+
+    def chunk_pair_overlap(self, first, other, other_first, count, spec, **kw):
+        """fqgpu_chunk_pair_overlap: the mate overlap of the chunk staged here (mate 1) and the chunk staged on the Context
+        `other` (mate 2) -> as DBlock.pair_overlap"""
+        return _overlap_call(lib().fqgpu_chunk_pair_overlap, (self.h, first, other.h if other is not None else None, other_first), count, spec, **kw)
 
     def chunk_pair_names(self, first, other, other_first, count):
         """fqgpu_chunk_pair_names: the read ids of the chunk staged here against those of the chunk staged on the Context

@@ -1884,10 +1884,11 @@ extern "C" int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, cons
 // ------------------------------------------------------------------ a record range of a chunk in HBM against a mark, and the read ids of two chunks (select.hip)
 // The two marked calls (b, staged: as stats_call): the tail calls' front -- no device is said before any argument is looked
 // at, *out_len and the report are zeroed before anything else can fail -- with every one of a, x, t, f allowed to be NULL, and
-// the range [first, end) of the block's record table handed to fq_select_chunk as a table of its own.
+// the range [first, end) of the block's record table handed to fq_select_chunk as a table of its own.  limit_in (the
+// limited calls'; nullptr: none): the range's per-record limits, which travel with the mark.
 static int marked_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
                        const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
-                       uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
+                       uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out, const uint16_t *limit_in = nullptr) {
   if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
   if (out_len) *out_len = 0;
   if (report) memset(report, 0, FQGPU_TAIL_REPORT_WORDS * sizeof(uint64_t));
@@ -1902,7 +1903,7 @@ static int marked_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const
     return FQGPU_E_ARG;
   if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
   if (first >= end || end > b->n_recs) return FQGPU_E_ARG;
-  const FqSelectMark m = {first != 0, mark_in};
+  const FqSelectMark m = {first != 0, mark_in, limit_in};
   return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs + first, end - first, a, t, f ? f : &all, out, out_cap, out_len, report,
                          keep_out, win_out, x, places_out, &m);
 }
@@ -1917,6 +1918,21 @@ extern "C" int fqgpu_dblock_select_marked(fqgpu_ctx *ctx, const fqgpu_dblock *b,
                                           const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap,
                                           size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
   return marked_call(ctx, b, false, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out);
+}
+
+// The two limited calls: the marked calls with the range's limits (select.hip, k_select_limit)
+extern "C" int fqgpu_chunk_select_limited(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                                          size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in, uint8_t *out,
+                                          size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
+                                          uint16_t *places_out) {
+  return marked_call(ctx, nullptr, true, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out, limit_in);
+}
+
+extern "C" int fqgpu_dblock_select_limited(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                                           const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in,
+                                           uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
+                                           uint32_t *win_out, uint16_t *places_out) {
+  return marked_call(ctx, b, false, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out, limit_in);
 }
 
 // The two id calls: both chunks at rest -- every stream of both handles, and of a block's owner, is waited for --, then one
@@ -1947,4 +1963,48 @@ extern "C" int fqgpu_dblock_pair_names(fqgpu_ctx *ctx, const fqgpu_dblock *ba, s
   int rc;
   if ((rc = settled_block(ctx, ba)) || (rc = settled_block(ctx, bb))) return rc;
   return names_call(ctx, ba, first_a, bb, first_b, count, mismatch);
+}
+
+// The two overlap calls (staged: the chunks staged on the two handles; else two blocks of ctx_a's device): the id
+// calls' checks and waits, then one kernel on ctx_a's stream.  No device is said before any argument is looked at, too little
+// room before anything is written; every FQGPU_E_ARG leaves `out` and the three arrays zeroed.
+static int overlap_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
+                        size_t count, const fqgpu_overlap *o, uint64_t *out, size_t cap_words, uint16_t *limit_a_out, uint16_t *limit_b_out,
+                        uint16_t *insert_out) {
+  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
+  if (out && cap_words < FQGPU_OVERLAP_WORDS) return FQGPU_E_OVERFLOW;
+  const auto run = [&]() -> int {
+    if (!out) return FQGPU_E_ARG;
+    memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
+    if (!ctx_a || fqgpu_overlap_check(o) != FQGPU_OK) return FQGPU_E_ARG;
+    int rc;
+    if (staged) {
+      if (!ctx_b || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
+      if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
+    } else if ((rc = settled_block(ctx_a, ba)) || (rc = settled_block(ctx_a, bb))) {
+      return rc;
+    }
+    if (count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs || count > bb->n_recs - first_b)
+      return FQGPU_E_ARG;
+    return fq_pair_overlap(ctx_a, ctx_a->stream, ba->raw, ba->raw_len, ba->recs + first_a, bb->raw, bb->raw_len, bb->recs + first_b, count, o,
+                           out, limit_a_out, limit_b_out, insert_out);
+  };
+  const int rc = run();
+  if (rc == FQGPU_E_ARG) {
+    uint16_t *const arr[3] = {limit_a_out, limit_b_out, insert_out};
+    for (uint16_t *p : arr)
+      if (p && count) memset(p, 0, count * sizeof(uint16_t));
+  }
+  return rc;
+}
+
+extern "C" int fqgpu_chunk_pair_overlap(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const fqgpu_overlap *o,
+                                        uint64_t *out, size_t cap_words, uint16_t *limit_a_out, uint16_t *limit_b_out, uint16_t *insert_out) {
+  return overlap_call(true, ctx_a, ctx_b, nullptr, first_a, nullptr, first_b, count, o, out, cap_words, limit_a_out, limit_b_out, insert_out);
+}
+
+extern "C" int fqgpu_dblock_pair_overlap(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
+                                         size_t count, const fqgpu_overlap *o, uint64_t *out, size_t cap_words, uint16_t *limit_a_out,
+                                         uint16_t *limit_b_out, uint16_t *insert_out) {
+  return overlap_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, o, out, cap_words, limit_a_out, limit_b_out, insert_out);
 }

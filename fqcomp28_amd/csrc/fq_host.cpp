@@ -149,6 +149,38 @@ extern "C" int fqgpu_probe_merge(uint64_t *dst, size_t dst_words, const uint64_t
   return FQGPU_OK;
 }
 
+// Mate overlap (select.hip finds it): what a spec may say, its fingerprint, and dst += src.
+extern "C" int fqgpu_overlap_check(const fqgpu_overlap *o) {
+  if (!o || o->min_overlap < 1u || o->min_overlap > FQGPU_OVERLAP_MAX_LEN || o->max_mism > 65535u || o->max_err_pct > 50u) return FQGPU_E_ARG;
+  for (uint32_t r : o->reserved)
+    if (r) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+// zlib's CRC-32 of the spec's 32 bytes (bit by bit, once per call)
+uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o) {
+  static_assert(sizeof(fqgpu_overlap) == 32, "the fingerprint is taken over 32 bytes");
+  const uint8_t *const b = reinterpret_cast<const uint8_t *>(o);
+  uint32_t c = 0xFFFFFFFFu;
+  for (size_t i = 0; i < sizeof(fqgpu_overlap); i++) {
+    c ^= b[i];
+    for (int j = 0; j < 8; j++) c = (c >> 1) ^ ((c & 1u) ? 0xEDB88320u : 0u);
+  }
+  return ~c;
+}
+extern "C" int fqgpu_overlap_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words) {
+  if (!dst || !src || dst_words != FQGPU_OVERLAP_WORDS || src_words != FQGPU_OVERLAP_WORDS) return FQGPU_E_ARG;
+  const bool empty = dst[0] == 0;  // (a block of zeros is an empty result of any spec)
+  if (!(empty && !dst[8]) && dst[8] != src[8]) return FQGPU_E_ARG;
+  if (empty) {
+    memcpy(dst, src, src_words * sizeof(uint64_t));
+    return FQGPU_OK;
+  }
+  if (!src[0]) return FQGPU_OK;
+  for (size_t i = 0; i < dst_words; i++)
+    if (i != 8u) dst[i] += src[i];
+  return FQGPU_OK;
+}
+
 // Poly-X tails and the sliding-window cut (select.hip applies them): what a tail may say.
 extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   if (!x || x->poly_bases > 15u || x->poly_max_mism > 255u || x->window_len > 32u || x->reserved[0] || x->reserved[1]) return FQGPU_E_ARG;

@@ -267,18 +267,21 @@ FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs)
 // in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
 // filter and trim calls: each is waited for before it returns.  A probe call (adapter content) has two buffers of its own
 // here: its u64 result tables and -- when asked for -- the records' places, n uint16_t each.  A marked call
-// (fqgpu_chunk_select_marked) has one: the caller's mark, a u64 word per 64 records.
+// (fqgpu_chunk_select_marked) has one: the caller's mark, a u64 word per 64 records; a limited call
+// (fqgpu_chunk_select_limited) another: the caller's limits, a uint16_t per record.  An overlap call
+// (fqgpu_chunk_pair_overlap) has two: its u64 result words and the pairs' limit1, limit2 and I, three arrays of uint16_t.
 struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   DevBuf probe_out, probe_places;
-  DevBuf mark;
+  DevBuf mark, limit;
+  DevBuf overlap_out, overlap_pairs;
   void *host = nullptr;
   void release_host();
 };
 FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, hstart), FQ_B(SelectScratch, win), FQ_B(SelectScratch, clip),
                 FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
                 FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places),
-                FQ_B(SelectScratch, mark))
+                FQ_B(SelectScratch, mark), FQ_B(SelectScratch, limit), FQ_B(SelectScratch, overlap_out), FQ_B(SelectScratch, overlap_pairs))
 
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
@@ -490,6 +493,7 @@ int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
 struct FqSelectMark {
   bool prev;            // the range's first record is not the table's first: recs_dev[-1] is the record in front of it
   const uint8_t *mark;  // host: (n_recs + 7) / 8 bytes in keep_out's layout; nullptr: every record is marked
+  const uint16_t *limit = nullptr;  // host: n_recs limits (fqgpu_chunk_select_limited); nullptr: none.  With one, words 21 / 22 are counted
 };
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
@@ -501,6 +505,15 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
 // whose ids differ, (size_t)-1 when there is none.  FQGPU_E_ARG: count 0, or a header line outside its chunk
 int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, bool prev_a,
                   const uint8_t *raw_b, size_t raw_len_b, const fqgpu_rec *recs_b, bool prev_b, size_t count, size_t *mismatch);
+
+// The mate overlap (include/fqgpu.h) of the records recs_a[i] (mate 1) and recs_b[i] (mate 2), i < count, of two chunks in HBM
+// on ctx's device, both at rest (select.hip; the spec has passed its check), on st, waited for: out[0, FQGPU_OVERLAP_WORDS) on
+// the host and -- each where not nullptr -- count uint16_t of limit1, limit2 and I.  FQGPU_E_ARG with all of them zeroed:
+// count 0, a record outside its chunk or of length 0, a byte outside ACGTN in an analysed line
+int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, const uint8_t *raw_b,
+                    size_t raw_len_b, const fqgpu_rec *recs_b, size_t count, const fqgpu_overlap *o, uint64_t *out, uint16_t *limit_a_out,
+                    uint16_t *limit_b_out, uint16_t *insert_out);
+uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o);  // fq_host.cpp: zlib's CRC-32 of the spec's 32 bytes
 
 // Adapter content of a chunk in HBM (select.hip; the probe set has passed its check, positions is 1 .. 65535), on st, waited
 // for: out[0, fqgpu_probe_words(p->n, positions)) on the host and -- places_out != nullptr -- p->n places per record

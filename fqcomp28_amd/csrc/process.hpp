@@ -838,6 +838,7 @@ struct PairedReport {
   FarmReport mate1, mate2;
   uint64_t pairs = 0, kept = 0, dropped_mate1_only = 0, dropped_mate2_only = 0, dropped_both = 0;
   std::size_t blocks1 = 0, blocks2 = 0, decodes2 = 0;
+  std::vector<uint64_t> overlap;  // with Selection::overlap: the units' summaries merged (FQGPU_OVERLAP_WORDS; an archive without records: zeros)
 };
 
 /** Extension: `d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq>` -- two archives whose records are mates restored in
@@ -853,7 +854,13 @@ struct PairedReport {
  *  matching slice of K1 -- its output is appended to the unit's piece of file 2, its keep bits to K; (4) chunk k selected
  *  against K; (5) both pieces go to their OrderedPieceWriter as piece k.  A chunk of archive 2 that straddles a boundary of
  *  archive 1 is decoded by two workers (rep.decodes2 counts); with archives cut at the same records every chunk is decoded
- *  once.  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
+ *  once.  With sel.overlap the mate overlap of every piece is analysed behind the id check (fqgpu_chunk_pair_overlap) and its
+ *  summary merged into rep.overlap; with sel.overlap_trim as well the limits stand in front of each mate's steps, and the
+ *  order inside a unit changes, because mate 1 cannot be judged before its mates are staged: step (2) is left out and per
+ *  piece, behind the overlap, mate 1's records [at, at + count) are judged as a size query with their limits -- those keep
+ *  bits are the piece's mark --, then the piece of mate 2 is judged and gathered with its limits; step (4) takes mate 1's
+ *  limits too.  No chunk is decoded more often than without.
+ *  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
  *  nor a `.part` file.  Throws before any output is opened when the archives' record totals differ. */
 inline PairedReport processArchivePaired(const path_t &archive1_path, const path_t &out1, const path_t &archive2_path, const path_t &out2,
                                          const fqgpu_adapter *adapter2, const Selection &sel, const Settings &set) {
@@ -878,6 +885,8 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   struct Worker {  // one workspace per archive, both on the worker's device; `in`, blocks and sums of mate 2 (mate 1's `in` and blocks are the farm's)
     detail::RestoreWorker m1, m2;
     std::vector<uint8_t> k1, k, mark, keep;
+    std::vector<uint16_t> limit1, limit2;         // with an overlap spec: the unit's limits of mate 1, the piece's of mate 2
+    std::vector<uint64_t> overlap, overlap_sum;   // ... the piece's summary, the worker's
     uint64_t report[W], sum1[W] = {}, sum2[W] = {};
     InputStats in2;
     unsigned decodes2 = 0;
@@ -901,10 +910,16 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
       clk.lap("read");
       w1.stagePairedChunk(cbs1);
       verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
+      const bool limited = sel.overlap && sel.overlap_trim;  // mate 1 is then judged piece by piece, behind the piece's overlap
       w.k1.assign((n + 7) / 8, 0);
-      (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
+      if (!limited) (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
       clk.lap("mate 1");
       w.k.assign((n + 7) / 8, 0);
+      if (sel.overlap) {
+        w.limit1.assign(n, 0);
+        w.overlap.assign(FQGPU_OVERLAP_WORDS, 0);
+        if (w.overlap_sum.empty()) w.overlap_sum.assign(FQGPU_OVERLAP_WORDS, 0);
+      }
       for (const MatePiece &pc : planMateUnit(counts2, A, A + n)) {
         archive2.readBlockAt(pc.block, cbs2);
         sidecar2.get(cbs2);
@@ -919,16 +934,24 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
                                    archive2_path.string() + ")");
         w.mark.resize((count + 7) / 8);
         w.keep.assign((count + 7) / 8, 0);
-        detail::sliceBits(w.k1.data(), at, count, w.mark.data());
+        if (sel.overlap) {
+          w.limit2.assign(count, 0);
+          w1.pairOverlap(at, w2, pc.first, count, *sel.overlap, w.overlap.data(), w.limit1.data() + at, w.limit2.data());
+          if (fqgpu_overlap_merge(w.overlap_sum.data(), w.overlap_sum.size(), w.overlap.data(), w.overlap.size()) != FQGPU_OK)
+            throw std::logic_error(name + ": overlap summaries of different specs");
+        }
+        if (limited) (void)w1.selectMarked(sel, at, at + count, nullptr, nullptr, 0, w.report, w.mark.data(), w.limit1.data() + at);
+        else detail::sliceBits(w.k1.data(), at, count, w.mark.data());
         piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
         len2 += w2.selectMarked(sel2, pc.first, pc.end, w.mark.data(), reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2,
-                                cbs2.original_size.total, w.report, w.keep.data());
+                                cbs2.original_size.total, w.report, w.keep.data(), limited ? w.limit2.data() : nullptr);
         for (unsigned i = 0; i < W; ++i) w.sum2[i] += w.report[i];
         detail::placeBits(w.keep.data(), count, w.k.data(), at);
       }
       clk.lap("mate 2");
       piece1.raw_data.resize(cbs1.original_size.total);
-      len1 = w1.selectMarked(sel, 0, n, w.k.data(), reinterpret_cast<uint8_t *>(piece1.raw_data.data()), piece1.raw_data.size(), w.report, nullptr);
+      len1 = w1.selectMarked(sel, 0, n, w.k.data(), reinterpret_cast<uint8_t *>(piece1.raw_data.data()), piece1.raw_data.size(), w.report, nullptr,
+                             limited ? w.limit1.data() : nullptr);
       for (unsigned i = 0; i < W; ++i) w.sum1[i] += w.report[i];
       in1.n_records += static_cast<std::size_t>(w.report[1]);
       w.in2.n_records += static_cast<std::size_t>(w.report[1]);
@@ -951,8 +974,11 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   rep.mate2.blocks_per_worker.assign(rep.mate1.blocks_per_worker.size(), 0);
   rep.mate1.trim.assign(W, 0);
   rep.mate2.trim.assign(W, 0);
+  if (sel.overlap) rep.overlap.assign(FQGPU_OVERLAP_WORDS, 0);
   for (std::size_t t = 0; t < farm.workers().size(); ++t) {
     const Worker &w = *farm.workers()[t];
+    if (!w.overlap_sum.empty() && fqgpu_overlap_merge(rep.overlap.data(), rep.overlap.size(), w.overlap_sum.data(), w.overlap_sum.size()) != FQGPU_OK)
+      throw std::logic_error(name + ": overlap summaries of different specs");
     rep.mate2.in += w.in2;
     rep.mate2.blocks_per_worker[t] = w.decodes2;
     rep.decodes2 += w.decodes2;
@@ -973,6 +999,36 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   rep.dropped_mate2_only = rep.mate1.trim[20];
   rep.dropped_both = rep.pairs - rep.kept - rep.dropped_mate1_only - rep.dropped_mate2_only;
   return rep;
+}
+
+/** Extension: the report file of a mate overlap summary (fqgpu_chunk_pair_overlap, merged) -- text, tab-separated, integers
+ *  only, a pure function of the summary and the spec: the spec's three numbers, the eight summary words by name, then
+ *  "insert", I and the pairs for every non-empty row.  Written as `<path>.part` and renamed when it is complete. */
+inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu_overlap &spec) {
+  if (w.size() != FQGPU_OVERLAP_WORDS) throw std::logic_error("writeOverlapReport: not an overlap summary");
+  std::string out = "#fqgpu-overlap 1\n";
+  const auto line = [&](const char *name, uint64_t v) { out += name; out += '\t'; out += std::to_string(v); out += '\n'; };
+  line("min_overlap", spec.min_overlap);
+  line("max_mism", spec.max_mism);
+  line("max_err_pct", spec.max_err_pct);
+  const char *names[8] = {"pairs", "pairs_overlapped", "pairs_read_through", "bases_behind_1", "bases_behind_2", "pairs_not_analysed", "mismatches",
+                          "overlap_bases"};
+  for (int i = 0; i < 8; ++i) line(names[i], w[i]);
+  for (std::size_t r = 0; r < FQGPU_OVERLAP_ROWS; ++r)
+    if (w[16 + r]) { out += "insert\t"; out += std::to_string(r); out += '\t'; out += std::to_string(w[16 + r]); out += '\n'; }
+  return out;
+}
+inline void writeOverlapReport(const path_t &path, const std::vector<uint64_t> &w, const fqgpu_overlap &spec) {
+  const std::string out = overlapReportText(w, spec);
+  const path_t part = path.string() + ".part";
+  std::FILE *f = std::fopen(part.string().c_str(), "wb");
+  const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
+  if ((f && std::fclose(f) != 0) || !ok) {
+    std::error_code ec;
+    std::filesystem::remove(part, ec);
+    throw std::runtime_error("cannot write " + part.string());
+  }
+  std::filesystem::rename(part, path);
 }
 
 namespace detail {

@@ -66,6 +66,12 @@
 // in report word 20.  k_pair_names compares the read ids of two chunks' records (fqgpu_chunk_pair_names): eight lanes to a
 // pair, both ids loaded from wherever they start, one atomicMin for the first pair that differs.
 //
+// The MATE OVERLAP (fqgpu_chunk_pair_overlap, fqgpu_chunk_select_limited).  k_pair_overlap compares the sequence lines of two
+// chunks' records: a wave per 64 pairs, each pair's lines as 2-bit codes and an N plane in LDS, mate 2's reversed and
+// complemented, a lane per candidate shift, the first hit in the rule's order by a ballot; it leaves a summary with the
+// insert-size histogram and per pair the two limits and the insert size.  k_select_limit, behind k_adapter_find, takes the
+// minimum of a caller's per-record limit into the clip places, so that the judge's clip forms serve a limit unchanged.
+//
 // All global stores are ordinary vector stores from plain C++.
 #include "fqgpu_internal.h"
 
@@ -1517,6 +1523,220 @@ k_pair_names(const PairSide A, const PairSide B, unsigned count, unsigned long l
   if (__any(have && !fine) && lane == 0) *bad = 1u;  // (every writer stores the same value)
 }
 
+// ---- a per-record limit in front of the trim's steps (include/fqgpu.h, fqgpu_chunk_select_limited): behind k_adapter_find,
+// clip[r] = min(clip[r], limit[r]); without an adapter clip[r] is filled from the record's length first.  The judge and
+// k_tail_find then see the clip forms and nothing else changes.  Words 21 / 22 -- the records whose limit lies in front of
+// the adapter's place, and the bases between the two -- are summed over the wave by shuffles, over the workgroup in LDS, and
+// go out as one atomic per word and workgroup.  No line is read.
+constexpr unsigned R_CUT_LIMIT_READS = 21, R_CUT_LIMIT_BASES = 22;
+__global__ void __launch_bounds__(SEL_THREADS)
+k_select_limit(const fqgpu_rec *__restrict__ recs, unsigned n_recs, const uint16_t *__restrict__ limit, uint16_t *__restrict__ clip,
+               const unsigned have_clip, SelectResult *__restrict__ res) {
+  __shared__ unsigned wg_reads, wg_bases;
+  if (threadIdx.x == 0) {
+    wg_reads = 0;
+    wg_bases = 0;
+  }
+  __syncthreads();
+  const unsigned long long r = (unsigned long long)blockIdx.x * SEL_THREADS + threadIdx.x;
+  unsigned reads = 0, bases = 0;  // (256 records of at most 65535 bases)
+  if (r < n_recs) {
+    const unsigned len = min(recs[r].len, 65535u);  // (a longer one is refused by the judge)
+    const unsigned a = have_clip ? min((unsigned)clip[r], len) : len, a0 = min(a, (unsigned)limit[r]);
+    clip[r] = (uint16_t)a0;
+    reads = a0 < a;
+    bases = a - a0;
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    reads += __shfl_xor(reads, d);
+    bases += __shfl_xor(bases, d);
+  }
+  if (fq_lane() == 0 && reads) {
+    atomicAdd(&wg_reads, reads);
+    atomicAdd(&wg_bases, bases);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0 && wg_reads) {
+    atomicAdd(&res->w[R_CUT_LIMIT_READS], (unsigned long long)wg_reads);
+    atomicAdd(&res->w[R_CUT_LIMIT_BASES], (unsigned long long)wg_bases);
+  }
+}
+
+// ---- the mate overlap of two chunks' records (include/fqgpu.h, fqgpu_chunk_pair_overlap).  A workgroup is ONE wave and takes
+// 64 consecutive pairs: their table entries with one load, lane = pair, and their results back to the pair's lane at the
+// end, so that the three arrays go out as three coalesced stores.  The pairs are then taken one after the other by all 64
+// lanes.  Loading: a line has at most 512 bases, lane j reads the eight bytes [8 j, 8 j + 8) of each line from wherever the
+// line starts (the 64 spare bytes behind every chunk let the last word be read whole) and turns them into eight bits of
+// three planes -- the base's code A 00, C 01, G 10, T 11 as a low and a high plane, and an N plane -- by the packed compares
+// clip_planes uses; a byte that is none of ACGTN refuses the chunk.  The planes lie in LDS as bytes, read back as words: bit i
+// of word w is base 32 w + i.  The complement of a code is its inverse, so r = revcomp(s2) is s2's planes bit-reversed over
+// all 512 places (byte 63 - j takes the reversed byte j), the two code planes inverted; r[0] then stands at bit 512 - L2,
+// an offset that folds into the candidate's shift.  Searching: a lane takes one candidate d, 64 candidates in the order of
+// the rule at a time -- d = 0 .. L1 - min_overlap, then -1 .. -(L2 - min_overlap): exactly the shifts with ov >= min_overlap --
+// and walks the words of s1: the s1 words are the same for every lane (a broadcast), the bits of r beside them a funnel
+// shift of two neighbouring words, of which one is carried over; two XORs, the N planes, the mask of [lo, hi) and a
+// population count per word.  The first hit wins, so the round in which a lane hits is the last one (the lowest lane of the
+// ballot), and a round's walk ends as soon as no lane can hit any more -- mism only grows --, which for unrelated mates is
+// after the first word.  r's planes have 512 bits of slack on either side, so no index is tested.  Counters are kept by
+// the wave, the histogram in LDS; both go out as one atomic per touched word and workgroup.
+constexpr unsigned OV_THREADS = 64, OV_WG_PAIRS = 64;
+constexpr unsigned OV_WORDS = FQGPU_OVERLAP_MAX_LEN / 32;  // words of a plane
+constexpr unsigned OV_R_WORDS = 3 * OV_WORDS;              // ... of a plane of r: slack, the plane, slack
+constexpr unsigned OV_HEAD = 16;                           // words in front of the rows
+static_assert(OV_THREADS == 64 && OV_WG_PAIRS == 64 && FQGPU_OVERLAP_MAX_LEN == 8 * OV_THREADS, "lane = pair, and eight bases of a line to a lane");
+static_assert(FQGPU_OVERLAP_ROWS >= 2 * FQGPU_OVERLAP_MAX_LEN && FQGPU_OVERLAP_WORDS == OV_HEAD + FQGPU_OVERLAP_ROWS, "I <= 1023 has a row");
+struct OvSide {
+  const uint8_t *raw;
+  unsigned long long raw_len;
+  const fqgpu_rec *recs;  // the first record of the range
+};
+struct OvSpec {
+  unsigned min_overlap, max_mism, max_err_pct;
+};
+struct __attribute__((packed)) OvU64 { uint32_t a, b; };  // eight bytes at any address
+struct OvBits {
+  unsigned lo, hi, n;  // eight bits each
+  bool bad;
+};
+// the planes of the bases [8 lane, 8 lane + 8) of a line of len <= 512 bases that lies inside its chunk
+__device__ __forceinline__ OvBits ov_bits(const uint8_t *__restrict__ raw, unsigned off, unsigned len, unsigned lane) {
+  OvBits b = {0u, 0u, 0u, false};
+  const unsigned p = 8u * lane;
+  if (p >= len) return b;
+  const OvU64 v = *reinterpret_cast<const OvU64 *>(raw + off + p);
+  const unsigned w[2] = {v.a, v.b}, in = sel_bits(0, (int)(len - p)) & 0xFFu;
+  unsigned fine = 0;
+#pragma unroll
+  for (int i = 0; i < 2; i++) {
+    const unsigned y = w[i] & ~SW_H;
+    const unsigned ea = sw_eq(y, 'A'), ec = sw_eq(y, 'C'), eg = sw_eq(y, 'G'), et = sw_eq(y, 'T'), en = sw_eq(y, 'N');
+    b.lo |= ((ec | et) * CLIP_GATHER) >> 28 << (4 * i);
+    b.hi |= ((eg | et) * CLIP_GATHER) >> 28 << (4 * i);
+    b.n |= (en * CLIP_GATHER) >> 28 << (4 * i);
+    fine |= (((ea | ec | eg | et | en) & ~w[i]) * CLIP_GATHER) >> 28 << (4 * i);  // one of ACGTN, and below 128
+  }
+  b.bad = (~fine & in) != 0u;
+  b.lo &= in;
+  b.hi &= in;
+  b.n &= in;
+  return b;
+}
+// the bits [lo, hi) of a word, any lo and hi
+__device__ __forceinline__ unsigned ov_mask(int lo, int hi) {
+  const unsigned below_hi = hi <= 0 ? 0u : hi >= 32 ? 0xFFFFFFFFu : (1u << hi) - 1u;
+  const unsigned below_lo = lo <= 0 ? 0u : lo >= 32 ? 0xFFFFFFFFu : (1u << lo) - 1u;
+  return below_hi & ~below_lo;
+}
+
+__global__ void __launch_bounds__(OV_THREADS)
+k_pair_overlap(const OvSide A, const OvSide B, unsigned count, const OvSpec sp, unsigned long long *__restrict__ out,
+               uint16_t *__restrict__ pairs, unsigned *__restrict__ bad_out) {
+  __shared__ unsigned s1[3][OV_WORDS];    // mate 1: the code's low bit, its high bit, N
+  __shared__ unsigned rr[3][OV_R_WORDS];  // r, the code planes inverted already; the plane is the words [OV_WORDS, 2 OV_WORDS)
+  __shared__ unsigned hist[FQGPU_OVERLAP_ROWS];
+  const unsigned lane = threadIdx.x;
+  for (unsigned i = lane; i < FQGPU_OVERLAP_ROWS; i += OV_THREADS) hist[i] = 0;
+  for (unsigned i = lane; i < 3 * OV_R_WORDS; i += OV_THREADS) (&rr[0][0])[i] = 0;
+  const unsigned long long p0 = (unsigned long long)blockIdx.x * OV_WG_PAIRS;
+  const bool have = p0 + lane < count;
+  fqgpu_rec ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
+  if (have) {
+    ra = A.recs[p0 + lane];
+    rb = B.recs[p0 + lane];
+  }
+  const bool ok = have && ra.len != 0 && ra.len <= 65535u && (unsigned long long)ra.seq_off + ra.len <= A.raw_len && rb.len != 0 &&
+                  rb.len <= 65535u && (unsigned long long)rb.seq_off + rb.len <= B.raw_len;
+  const bool analysed = ok && ra.len <= FQGPU_OVERLAP_MAX_LEN && rb.len <= FQGPU_OVERLAP_MAX_LEN;
+  bool bad = have && !ok;
+  unsigned my_limit_a = ra.len, my_limit_b = rb.len, my_insert = 0;  // the lane's pair: no hit so far
+  unsigned n_over = 0, n_through = 0, behind_a = 0, behind_b = 0, n_mism = 0, n_ov = 0;  // (the same in every lane; 64 pairs of <= 512 bases)
+  uint8_t *const s1_bytes = reinterpret_cast<uint8_t *>(&s1[0][0]);
+  uint8_t *const rr_bytes = reinterpret_cast<uint8_t *>(&rr[0][0]);
+  unsigned long long todo = __ballot(analysed);
+  while (todo) {  // (uniform)
+    const unsigned p = (unsigned)__builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const unsigned L1 = fq_uniform(__shfl(ra.len, p)), L2 = fq_uniform(__shfl(rb.len, p));
+    const unsigned off_a = fq_uniform(__shfl(ra.seq_off, p)), off_b = fq_uniform(__shfl(rb.seq_off, p));
+    const OvBits x = ov_bits(A.raw, off_a, L1, lane), y = ov_bits(B.raw, off_b, L2, lane);
+    bad = bad || x.bad || y.bad;
+    __syncthreads();  // the pair in front has been searched
+    s1_bytes[lane] = (uint8_t)x.lo;
+    s1_bytes[4 * OV_WORDS + lane] = (uint8_t)x.hi;
+    s1_bytes[8 * OV_WORDS + lane] = (uint8_t)x.n;
+    rr_bytes[4 * OV_WORDS + 63 - lane] = (uint8_t)(~__brev(y.lo) >> 24);
+    rr_bytes[4 * (OV_R_WORDS + OV_WORDS) + 63 - lane] = (uint8_t)(~__brev(y.hi) >> 24);
+    rr_bytes[4 * (2 * OV_R_WORDS + OV_WORDS) + 63 - lane] = (uint8_t)(__brev(y.n) >> 24);
+    __syncthreads();
+    const bool can = L1 >= sp.min_overlap && L2 >= sp.min_overlap;
+    const unsigned n_pos = can ? L1 - sp.min_overlap + 1u : 0u, n_cand = can ? n_pos + L2 - sp.min_overlap : 0u;
+    const unsigned words = (L1 + 31u) / 32u;
+    bool hit = false;
+    int hit_d = 0;
+    unsigned hit_mism = 0, hit_ov = 0;
+    for (unsigned c0 = 0; c0 < n_cand && !hit; c0 += OV_THREADS) {  // (uniform)
+      const unsigned c = c0 + lane;
+      const bool live = c < n_cand;
+      const int d = !live ? 0 : c < n_pos ? (int)c : -(int)(c - n_pos + 1u);
+      const int lo = max(d, 0), hi = min((int)L1, d + (int)L2);
+      const unsigned ov = (unsigned)(hi - lo), bound = min(sp.max_mism, sp.max_err_pct * ov / 100u);
+      // r[i - d] is bit i + q0 of r's planes with their slack: q0 = 512 + (512 - L2) - d, in 1 .. 1023
+      const unsigned q0 = (unsigned)(2 * (int)FQGPU_OVERLAP_MAX_LEN - (int)L2 - d), sh = q0 & 31u, qw = q0 >> 5;
+      unsigned mism = live ? 0u : 0xFFFF0000u;  // (a lane without a candidate never hits)
+      unsigned c_lo = rr[0][qw], c_hi = rr[1][qw], c_n = rr[2][qw];
+      for (unsigned w = 0; w < words; w++) {  // (uniform)
+        const unsigned n_lo = rr[0][qw + w + 1u], n_hi = rr[1][qw + w + 1u], n_n = rr[2][qw + w + 1u];
+        const unsigned r_lo = __builtin_amdgcn_alignbit(n_lo, c_lo, sh), r_hi = __builtin_amdgcn_alignbit(n_hi, c_hi, sh),
+                       r_n = __builtin_amdgcn_alignbit(n_n, c_n, sh);
+        const unsigned differ = ((s1[0][w] ^ r_lo) | (s1[1][w] ^ r_hi) | s1[2][w] | r_n) & ov_mask(lo - 32 * (int)w, hi - 32 * (int)w);
+        mism += (unsigned)__popc(differ);
+        c_lo = n_lo;
+        c_hi = n_hi;
+        c_n = n_n;
+        if (!__any(mism <= bound)) break;  // (mism only grows)
+      }
+      const unsigned long long hits = __ballot(live && mism <= bound);
+      if (hits) {  // (uniform) the round's candidates rise with its lanes
+        const int first = __builtin_ctzll(hits);
+        hit = true;
+        hit_d = __shfl(d, first);
+        hit_mism = __shfl(mism, first);
+        hit_ov = __shfl(ov, first);
+      }
+    }
+    if (hit) {
+      const unsigned I = (unsigned)(hit_d + (int)L2), limit_a = min(L1, I), limit_b = min(L2, I);
+      n_over++;
+      n_through += limit_a < L1 || limit_b < L2;
+      behind_a += L1 - limit_a;
+      behind_b += L2 - limit_b;
+      n_mism += hit_mism;
+      n_ov += hit_ov;
+      if (lane == p) {
+        my_limit_a = limit_a;
+        my_limit_b = limit_b;
+        my_insert = I;
+      }
+      if (lane == 0) atomicAdd(&hist[I], 1u);  // (I <= L1 - min_overlap + L2 <= 1023)
+    }
+  }
+  __syncthreads();
+  for (unsigned i = lane; i < FQGPU_OVERLAP_ROWS; i += OV_THREADS)
+    if (const unsigned v = hist[i]) atomicAdd(&out[OV_HEAD + i], (unsigned long long)v);
+  const unsigned skipped = (unsigned)__popcll(__ballot(ok && !analysed));
+  const unsigned cnt[8] = {0u, n_over, n_through, behind_a, behind_b, skipped, n_mism, n_ov};
+#pragma unroll
+  for (unsigned i = 1; i < 8; i++)
+    if (lane == i && cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+  if (have) {
+    pairs[p0 + lane] = (uint16_t)my_limit_a;
+    pairs[(unsigned long long)count + p0 + lane] = (uint16_t)my_limit_b;
+    pairs[2ull * count + p0 + lane] = (uint16_t)my_insert;
+  }
+  if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
+}
+
 }  // namespace
 
 void SelectScratch::release_host() {
@@ -1531,7 +1751,8 @@ void SelectScratch::release_host() {
 // x (nullptr: none; with one, t is a trim): the tail trims between the clip and the trim, k_tail_find in front of the judge;
 // the report then has FQGPU_TAIL_REPORT_WORDS words, and places_out (nullptr, or 4 uint16_t per record) receives a0, a1, e, e2.
 // m (nullptr: none; with one, t is a trim and the report a tail's): recs_dev is a range of the chunk's table -- m->prev: not
-// its front -- and m->mark (nullptr: none) the range's mark, k_select_mark behind the judge; word 20 is counted.
+// its front -- and m->mark (nullptr: none) the range's mark, k_select_mark behind the judge; word 20 is counted.  m->limit
+// (nullptr: none): the range's limits, k_select_limit behind the adapter search; words 21 / 22 are counted.
 int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
                     const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                     uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x, uint16_t *places_out, const FqSelectMark *m) {
@@ -1546,11 +1767,14 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
   SelectScratch &ss = ctx->select;
   const char *const span = m ? "select_marked" : x ? "tailtrim" : a ? "clip" : t ? "trim" : "filter";
   const uint8_t *const mark = m ? m->mark : nullptr;
+  const uint16_t *const limit = m ? m->limit : nullptr;
+  const bool clipped = a || limit;  // clip[r] stands in front of the trim's steps
   const unsigned R = (unsigned)n_recs;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
   int rc;
   if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
-      (a && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) || (mark && (rc = ss.mark.reserve(n_waves * 8))) ||
+      (clipped && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) || (mark && (rc = ss.mark.reserve(n_waves * 8))) ||
+      (limit && (rc = ss.limit.reserve(n_recs * 2))) ||
       (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
     return rc;
   if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
@@ -1561,6 +1785,7 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
     FQ_HIP(hipMemsetAsync(ss.mark.p, 0, n_waves * 8, st));
     FQ_HIP(hipMemcpyAsync(ss.mark.p, mark, (n_recs + 7) / 8, hipMemcpyHostToDevice, st));
   }
+  if (limit) FQ_HIP(hipMemcpyAsync(ss.limit.p, limit, n_recs * 2, hipMemcpyHostToDevice, st));
   fq_timer_span_begin(ctx, span, st);
   const dim3 judge_grid((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64)));
   if (a) {  // the adapter's bit planes: bit j of a plane is set iff A[j] is that base
@@ -1571,16 +1796,21 @@ int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size
                        ss.res.as<SelectResult>());
     FQ_HIP(hipGetLastError());
   }
-  if (x) {
-    hipLaunchKernelGGL(k_tail_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, *x, *t,
-                       a ? ss.clip.as<uint16_t>() : nullptr, ss.places.as<uint2>(), ss.res.as<SelectResult>());
+  if (limit) {
+    hipLaunchKernelGGL(k_select_limit, dim3((unsigned)((n_recs + SEL_THREADS - 1) / SEL_THREADS)), dim3(SEL_THREADS), 0, st, recs_dev, R,
+                       ss.limit.as<uint16_t>(), ss.clip.as<uint16_t>(), a ? 1u : 0u, ss.res.as<SelectResult>());
     FQ_HIP(hipGetLastError());
   }
-  const auto judge = x ? &k_select_judge<true, SEL_TAIL> : a ? &k_select_judge<true, SEL_CLIP> : t ? &k_select_judge<true> : &k_select_judge<false>;
+  if (x) {
+    hipLaunchKernelGGL(k_tail_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, *x, *t,
+                       clipped ? ss.clip.as<uint16_t>() : nullptr, ss.places.as<uint2>(), ss.res.as<SelectResult>());
+    FQ_HIP(hipGetLastError());
+  }
+  const auto judge = x ? &k_select_judge<true, SEL_TAIL> : clipped ? &k_select_judge<true, SEL_CLIP> : t ? &k_select_judge<true> : &k_select_judge<false>;
   const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
   hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
                      ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>(),
-                     a ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr, m && m->prev ? 1u : 0u);
+                     clipped ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr, m && m->prev ? 1u : 0u);
   FQ_HIP(hipGetLastError());
   if (mark) {
     hipLaunchKernelGGL(k_select_mark, judge_grid, dim3(SEL_THREADS), 0, st, ss.mark.as<unsigned long long>(), R, ss.ksize.as<uint32_t>(), win,
@@ -1706,5 +1936,45 @@ int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t r
   FQ_HIP(hipStreamSynchronize(st));
   if (res.bad) return FQGPU_E_ARG;
   *mismatch = res.w[0] == ~0ull ? (size_t)-1 : (size_t)res.w[0];
+  return FQGPU_OK;
+}
+
+// The mate overlap of `count` records of two chunks on one device, on st (both chunks are at rest), waited for.  One kernel,
+// one wait: the result words, the three arrays and the verdict come down behind it.  FQGPU_E_ARG zeroes out; the three arrays
+// are then the caller's to zero.
+int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, const uint8_t *raw_b,
+                    size_t raw_len_b, const fqgpu_rec *recs_b, size_t count, const fqgpu_overlap *o, uint64_t *out, uint16_t *limit_a_out,
+                    uint16_t *limit_b_out, uint16_t *insert_out) {
+  memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
+  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  SelectScratch &ss = ctx->select;
+  int rc;
+  if ((rc = ss.overlap_out.reserve(FQGPU_OVERLAP_WORDS * 8)) || (rc = ss.overlap_pairs.reserve(count * 6)) || (rc = ss.res.reserve(sizeof(SelectResult))))
+    return rc;
+  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
+  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
+  SelectResult *const dev = ss.res.as<SelectResult>();
+  uint16_t *const pairs = ss.overlap_pairs.as<uint16_t>();
+  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
+  FQ_HIP(hipMemsetAsync(ss.overlap_out.p, 0, FQGPU_OVERLAP_WORDS * 8, st));
+  const OvSide A = {raw_a, (unsigned long long)raw_len_a, recs_a}, B = {raw_b, (unsigned long long)raw_len_b, recs_b};
+  const OvSpec sp = {o->min_overlap, o->max_mism, o->max_err_pct};
+  fq_timer_span_begin(ctx, "pair_overlap", st);
+  hipLaunchKernelGGL(k_pair_overlap, dim3((unsigned)((count + OV_WG_PAIRS - 1) / OV_WG_PAIRS)), dim3(OV_THREADS), 0, st, A, B, (unsigned)count, sp,
+                     ss.overlap_out.as<unsigned long long>(), pairs, &dev->bad);
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipGetLastError());
+  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipMemcpyAsync(out, ss.overlap_out.p, FQGPU_OVERLAP_WORDS * 8, hipMemcpyDeviceToHost, st));
+  if (limit_a_out) FQ_HIP(hipMemcpyAsync(limit_a_out, pairs, count * 2, hipMemcpyDeviceToHost, st));
+  if (limit_b_out) FQ_HIP(hipMemcpyAsync(limit_b_out, pairs + count, count * 2, hipMemcpyDeviceToHost, st));
+  if (insert_out) FQ_HIP(hipMemcpyAsync(insert_out, pairs + 2 * count, count * 2, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  if (res.bad) {  // (the caller zeroes the three arrays)
+    memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
+    return FQGPU_E_ARG;
+  }
+  out[0] = count;
+  out[8] = fq_overlap_fingerprint(o);
   return FQGPU_OK;
 }

@@ -542,6 +542,10 @@ struct Selection {
   const fqgpu_tail *tail = nullptr;
   const fqgpu_trim *trim = nullptr;
   const fqgpu_filter *filter = nullptr;
+  /** paired restores alone (processArchivePaired): the mate overlap is analysed with this spec and summarised in
+   *  PairedReport::overlap; overlap_trim: its limits stand in front of each mate's steps */
+  const fqgpu_overlap *overlap = nullptr;
+  bool overlap_trim = false;
   /** something is cut: the counters are a trim report (FarmReport::trim), not a filter report (FarmReport::filter) */
   [[nodiscard]] bool trims() const { return adapter || tail || trim; }
   /** the fqgpu_chunk_* call that serves it, by the name of its first step */
@@ -558,6 +562,8 @@ struct Selection {
     if (adapter && fqgpu_adapter_check(adapter) != FQGPU_OK) throw std::invalid_argument(name + ": an adapter fqgpu_adapter_check refuses");
     if (trim && fqgpu_trim_check(trim) != FQGPU_OK) throw std::invalid_argument(name + ": a trim fqgpu_trim_check refuses");
     if ((filter || !(trims() || may_be_empty)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
+    if (overlap && fqgpu_overlap_check(overlap) != FQGPU_OK) throw std::invalid_argument(name + ": an overlap spec fqgpu_overlap_check refuses");
+    if (overlap_trim && !overlap) throw std::invalid_argument(name + ": overlap_trim without an overlap spec");
   }
 };
 
@@ -724,8 +730,9 @@ public:
   /** Extension (paired restores, process.hpp: processArchivePaired): the three steps a worker makes a pair of chunks of.
    *  stagePairedChunk decodes the chunk check-only, takes its digest for lastDigest() when setVerify is on and leaves it on
    *  the handle's staging block (as decodeChunkSelected does in front of its selecting call); there is no host fallback.
-   *  selectMarked is fqgpu_chunk_select_marked on the chunk staged last: records [first, end) against `mark` (nullptr: none;
-   *  (end - first + 7) / 8 bytes), any of sel's steps, or all, off; out == nullptr asks for the
+   *  selectMarked is fqgpu_chunk_select_limited on the chunk staged last: records [first, end) against `mark` (nullptr: none;
+   *  (end - first + 7) / 8 bytes) with `limit` (nullptr: none -- then it is fqgpu_chunk_select_marked byte for byte; end - first
+   *  entries) in front of the steps, any of sel's steps, or all, off; out == nullptr asks for the
    *  counters and the keep bits alone; -> the bytes written to out (at most out_cap: the chunk's recorded size is always
    *  enough).  pairNames is fqgpu_chunk_pair_names: the read ids of this handle's staged records first + i against those of
    *  `mate`'s mate_first + i, i < count -> the first i that differs, (size_t)-1 when none does.  A call the device refuses
@@ -737,10 +744,10 @@ public:
     clk.done(cbs.chunk_idx);
   }
   std::size_t selectMarked(const Selection &sel, std::size_t first, std::size_t end, const uint8_t *mark, uint8_t *out, std::size_t out_cap,
-                           uint64_t *report, uint8_t *keep_out) {
+                           uint64_t *report, uint8_t *keep_out, const uint16_t *limit = nullptr) {
     std::size_t len = 0;
-    const int rc = fqgpu_chunk_select_marked(ctx_, sel.adapter, sel.tail, sel.trim, sel.filter, first, end, mark, out, out_cap, &len, report, keep_out,
-                                             nullptr, nullptr);
+    const int rc = fqgpu_chunk_select_limited(ctx_, sel.adapter, sel.tail, sel.trim, sel.filter, first, end, mark, limit, out, out_cap, &len, report,
+                                              keep_out, nullptr, nullptr);
     if (rc != FQGPU_OK)
       throw std::runtime_error("selectMarked: chunk " + std::to_string(staged_idx_) + ", records " + std::to_string(first) + ":" +
                                std::to_string(end) + ": " + fqgpu_strerror(rc));
@@ -753,6 +760,15 @@ public:
       throw std::runtime_error("pairNames: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
                                fqgpu_strerror(rc));
     return mismatch;
+  }
+  /** fqgpu_chunk_pair_overlap: this handle's staged records first + i (mate 1) against `mate`'s mate_first + i (mate 2),
+   *  i < count -> out[0, FQGPU_OVERLAP_WORDS) and, each where not nullptr, count limits of either mate */
+  void pairOverlap(std::size_t first, DecompressionWorkspace &mate, std::size_t mate_first, std::size_t count, const fqgpu_overlap &spec,
+                   uint64_t *out, uint16_t *limit_out, uint16_t *mate_limit_out) {
+    const int rc = fqgpu_chunk_pair_overlap(ctx_, first, mate.ctx_, mate_first, count, &spec, out, FQGPU_OVERLAP_WORDS, limit_out, mate_limit_out, nullptr);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("pairOverlap: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
+                               fqgpu_strerror(rc));
   }
 
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every

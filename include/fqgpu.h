@@ -777,6 +777,74 @@ int fqgpu_dblock_probe(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_probes
                        uint16_t *places_out);
 int fqgpu_probe_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words);
 
+/* ---- Extension (nothing in the reference): MATE OVERLAP -- where the two mates of a pair stop agreeing, found where both
+ * chunks lie already -- in HBM -- and a per-record LIMIT that a selection takes in front of its other steps.  When a fragment is
+ * shorter than the reads, each mate runs through the fragment's far end into the adapter; over the fragment the mates are
+ * reverse complements of each other, so the fragment's end is found without knowing the adapter (fastp's PE mode does this by
+ * default), and the same comparison gives the insert size of every overlapping pair.  For a pair with the sequence lines
+ * s1[0, L1) (mate 1) and s2[0, L2) (mate 2), let r[j] = comp(s2[L2 - 1 - j]), comp mapping A<->T, C<->G and N to N.  Integer
+ * arithmetic throughout:
+ *   candidates   an integer shift d puts r[0] beside s1[d]: the overlap covers s1[lo, hi), lo = max(0, d), hi = min(L1, d + L2),
+ *                ov = hi - lo.  mism(d) = the number of i in [lo, hi) with s1[i] != r[i - d]; an N in either read is a
+ *                mismatch, there are no indels.  d is a HIT iff ov >= min_overlap, mism(d) <= max_mism and
+ *                100 * mism(d) <= max_err_pct * ov
+ *   the choice   the candidates are tried in the order d = 0, 1, 2, ..., then d = -1, -2, ..., and the FIRST hit wins (fastp's
+ *                order): the chosen d minimises d >= 0 ? d : 512 + |d|.  A later shift that matches better does not count,
+ *                which -- like the adapter clip's leftmost hit -- makes the result independent of how the work is split
+ *   a hit        the insert size is I = d + L2 (>= ov >= 1); limit1 = min(L1, I) and limit2 = min(L2, I) are the bases of each
+ *                mate that lie inside the fragment.  No hit: I = 0, limit1 = L1, limit2 = L2
+ *   the cap      a pair with L1 or L2 above FQGPU_OVERLAP_MAX_LEN is NOT ANALYSED: a pair without a hit, counted in word 5, its
+ *                lines not looked at
+ * The sequence lines of an analysed pair are judged over all their bytes (a byte outside ACGTN: FQGPU_E_ARG); a record outside
+ * its chunk or of length 0: FQGPU_E_ARG.  Every FQGPU_E_ARG zeroes `out` and the three arrays.
+ *   out  FQGPU_OVERLAP_WORDS uint64_t: 0 n_pairs | 1 pairs_overlapped | 2 pairs_read_through (limit1 < L1 or limit2 < L2) |
+ *        3 bases_behind_a (the sum of L1 - limit1) | 4 bases_behind_b | 5 pairs_not_analysed | 6 mismatches (the sum of mism at
+ *        the chosen d) | 7 overlap_bases (the sum of ov) | 8 zlib's CRC-32 of the 32 bytes of the fqgpu_overlap | 9 .. 15 zero |
+ *        then 1024 rows: the overlapped pairs by I (I <= 1023 always: the rows sum to word 1)
+ *   limit_a_out, limit_b_out, insert_out   each NULL, or `count` uint16_t: limit1, limit2 and I of pair i
+ *   fqgpu_overlap_check       host only: min_overlap in 1 .. 512, max_mism in 0 .. 65535, max_err_pct in 0 .. 50, reserved zero:
+ *                             FQGPU_OK, else FQGPU_E_ARG
+ *   fqgpu_chunk_pair_overlap  record first_a + i of the chunk staged on ctx_a (mate 1) against record first_b + i of the chunk
+ *                             staged on ctx_b (mate 2), i < count: shaped and validated exactly like fqgpu_chunk_pair_names --
+ *                             valid in the same states, both handles of one device, every stream of both waited for, then ONE
+ *                             kernel on ctx_a's stream, waited for; ctx_a == ctx_b is allowed
+ *   fqgpu_dblock_pair_overlap as fqgpu_dblock_pair_names
+ *   fqgpu_overlap_merge       host only: dst += src.  Both lengths FQGPU_OVERLAP_WORDS and word 8 equal, else FQGPU_E_ARG; a dst
+ *                             whose n_pairs is 0 is empty (a dst of all zeros counts as empty) and becomes a copy of src:
+ *                             fqgpu_stats_merge's rule
+ * cap_words below FQGPU_OVERLAP_WORDS: FQGPU_E_OVERFLOW, nothing is written.  A spec its check refuses, count == 0, a range
+ * outside either chunk, a NULL where data is expected: FQGPU_E_ARG.  Without a GPU the two device calls return
+ * FQGPU_E_NO_DEVICE before any argument is looked at; the two host helpers work.
+ *
+ * THE LIMIT.  fqgpu_chunk_select_limited / fqgpu_dblock_select_limited are the marked calls with one more input:
+ *   limit_in   NULL, or end - first uint16_t relative to `first`.  Step 0 becomes a0 = min(a_adapter, limit[i]), a_adapter the
+ *              adapter's clip place, or L without an adapter; everything behind step 0 is unchanged.  A limit causes no line
+ *              to be read
+ *   report     words 14 / 15 keep counting a0 < L / L - a0 | 21 reads_cut_limit (limit < a_adapter) | 22 bases_cut_limit (the
+ *              sum of a_adapter - a0) | 23 zero
+ * With limit_in == NULL every output is the marked call's, byte for byte. */
+#define FQGPU_OVERLAP_MAX_LEN 512
+#define FQGPU_OVERLAP_ROWS 1024
+#define FQGPU_OVERLAP_WORDS (16 + FQGPU_OVERLAP_ROWS)
+typedef struct {
+  uint32_t min_overlap, max_mism, max_err_pct;  /* 1 .. 512 | 0 .. 65535 | 0 .. 50 */
+  uint32_t reserved[5];                         /* zero */
+} fqgpu_overlap;
+int fqgpu_overlap_check(const fqgpu_overlap *o);
+int fqgpu_chunk_pair_overlap(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const fqgpu_overlap *o,
+                             uint64_t *out, size_t cap_words, uint16_t *limit_a_out, uint16_t *limit_b_out, uint16_t *insert_out);
+int fqgpu_dblock_pair_overlap(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
+                              const fqgpu_overlap *o, uint64_t *out, size_t cap_words, uint16_t *limit_a_out, uint16_t *limit_b_out,
+                              uint16_t *insert_out);
+int fqgpu_overlap_merge(uint64_t *dst, size_t dst_words, const uint64_t *src, size_t src_words);
+int fqgpu_chunk_select_limited(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
+                               size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in, uint8_t *out, size_t out_cap,
+                               size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out);
+int fqgpu_dblock_select_limited(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
+                                const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in,
+                                uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
+                                uint16_t *places_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -65,7 +65,14 @@
 //               number of records and nothing else: different block sizes, read lengths and header formats are fine, a chunk
 //               of <in2.fqc> that straddles a chunk boundary of <in1.fqc> is decoded twice.  Each archive's .fqx is used and
 //               its .fqs verified as in a single restore.  --mate with c, x, t or s, with --records, --fasta, --index or
-//               --index-stride, and --adapter2 without --mate or without --adapter's rules met are usage errors.  A failed run
+//               --index-stride, and --adapter2 without --mate or without --adapter's rules met are usage errors.
+//               [--overlap-trim] [--overlap-report <file.tsv>] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT]: the mate
+//               overlap (include/fqgpu.h: where the two mates stop being reverse complements of each other is the fragment's
+//               end, no adapter sequence needed).  --overlap-trim cuts both mates there, in front of every other step;
+//               --overlap-report writes the summary and the insert-size histogram of the overlapping pairs as text, the same
+//               bytes whatever -t, -R and .fqx; either turns the analysis on, the other three (defaults 30, 5, 20) set its spec.
+//               With the report alone both output files are what they are without it.  Any of the five without --mate, the
+//               last three without one of the first two, and a spec fqgpu_overlap_check refuses are usage errors.  A failed run
 //               leaves neither output nor a .part file)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
@@ -114,7 +121,9 @@
 // "raw_bytes2" mate 2's, "pairs": {"pairs", "kept", "dropped_mate1_only", "dropped_mate2_only", "dropped_both"} what became of
 // the pairs, "blocks1" / "blocks2" the archives' chunks and "decodes2" the chunk decodes of archive 2, "sums2" / "verified2"
 // (per decode) its chunk sums; with a selection option "mate1" and "mate2" replace "filter" and "trim": the keys of "trim", the
-// adapter, poly and window keys always there, and "dropped_unmarked", the reads that passed and whose mate did not.
+// adapter, poly and window keys always there, and "dropped_unmarked", the reads that passed and whose mate did not.  With
+// an overlap option "overlap": {"pairs_overlapped", "pairs_read_through", "bases_behind_1", "bases_behind_2",
+// "pairs_not_analysed"}; with --overlap-trim "mate1" / "mate2" are there and end in "reads_cut_limit", "bases_cut_limit".
 // Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
@@ -136,7 +145,7 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q] [adapter options] [trim options] [filter options]\n"
                          "                  (the argument behind --poly-g / --poly-x is taken as N unless it begins with '-')\n"
-                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
+                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [--overlap-trim] [--overlap-report file.tsv] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
                          "                  (paired: a pair is kept only if both mates pass; the read ids of every pair are compared)\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
@@ -159,6 +168,9 @@ int main(int argc, char **argv) {
   bool clipped = false, adapter_opt = false;
   fqgpu_adapter adapter2 = {{0}, 0, 5, 10, 0};
   bool clipped2 = false, mate = false;
+  fqgpu_overlap overlap = {30, 5, 20, {0, 0, 0, 0, 0}};  // --overlap-min, --overlap-mism, --overlap-err
+  bool overlap_opt = false, overlap_trim = false;       // one of the five options; --overlap-trim
+  std::string overlap_path;                             // --overlap-report
   std::string mate_in, mate_out;
   std::string adapters_list;
   bool adapters_opt = false;
@@ -227,6 +239,18 @@ int main(int argc, char **argv) {
       mate_in = val();
       mate_out = val();
       mate = true;
+    } else if (a == "--overlap-trim") {
+      overlap_trim = overlap_opt = true;
+    } else if (a == "--overlap-report") {
+      overlap_path = val();
+      overlap_opt = true;
+    } else if (a == "--overlap-min" || a == "--overlap-mism" || a == "--overlap-err") {
+      const std::string v = val();
+      if (!u32(v, a == "--overlap-min" ? overlap.min_overlap : a == "--overlap-mism" ? overlap.max_mism : overlap.max_err_pct)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      overlap_opt = true;
     } else if (a == "--adapters") {
       adapters_list = val();
       adapters_opt = true;
@@ -291,6 +315,18 @@ int main(int argc, char **argv) {
   }
   if (mate && (argv[1][0] != 'd' || range || fasta || set.decode_index)) {  // (said before any device is touched)
     std::fprintf(stderr, "--mate goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
+    return 2;
+  }
+  if (overlap_opt && !mate) {
+    std::fprintf(stderr, "--overlap-trim, --overlap-report, --overlap-min, --overlap-mism and --overlap-err analyse the two mates of a pair: they need --mate <in2.fqc> <out2.fastq>\n");
+    return 2;
+  }
+  if (overlap_opt && !overlap_trim && overlap_path.empty()) {
+    std::fprintf(stderr, "--overlap-min, --overlap-mism and --overlap-err need --overlap-trim or --overlap-report <file.tsv>\n");
+    return 2;
+  }
+  if (overlap_opt && fqgpu_overlap_check(&overlap) != FQGPU_OK) {
+    std::fprintf(stderr, "mate overlap: expected --overlap-min 1 .. 512, --overlap-mism 0 .. 65535, --overlap-err 0 .. 50\n");
     return 2;
   }
   if (clipped2 && !mate) {
@@ -435,7 +471,8 @@ int main(int argc, char **argv) {
       set.build_index = set.decode_index && !range;
       set.decode_index = false;
     }
-    const Selection sel{clipped ? &adapter : nullptr, tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr};
+    const Selection sel{clipped ? &adapter : nullptr, tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr,
+                        overlap_opt ? &overlap : nullptr, overlap_trim};
     PairedReport paired;
     if (mate) paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped2 ? &adapter2 : nullptr, sel, set);
     const FarmReport r = mate ? paired.mate1
@@ -446,6 +483,7 @@ int main(int argc, char **argv) {
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
+    if (!overlap_path.empty()) writeOverlapReport(overlap_path, paired.overlap, overlap);
     if (!stats_path.empty() && adapters_opt) writeStatsReport(stats_path, r.stats, r.probes, probes, probe_names);
     else if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
@@ -476,16 +514,23 @@ int main(int argc, char **argv) {
                   paired.mate2.in.raw, (unsigned long long)paired.pairs, (unsigned long long)paired.kept, (unsigned long long)paired.dropped_mate1_only,
                   (unsigned long long)paired.dropped_mate2_only, (unsigned long long)paired.dropped_both, paired.blocks1, paired.blocks2, paired.decodes2,
                   paired.mate2.indexed_blocks ? "used" : "none", paired.mate2.sums, paired.mate2.verified_blocks);
-      for (int m = 0; m < 2 && (filtered || trimmed || clipped || clipped2 || tailed); ++m) {
+      if (overlap_opt) {
+        const auto w = [&](unsigned i) { return (unsigned long long)paired.overlap[i]; };
+        std::printf(", \"overlap\": {\"pairs_overlapped\": %llu, \"pairs_read_through\": %llu, \"bases_behind_1\": %llu, \"bases_behind_2\": %llu, "
+                    "\"pairs_not_analysed\": %llu}", w(1), w(2), w(3), w(4), w(5));
+      }
+      for (int m = 0; m < 2 && (filtered || trimmed || clipped || clipped2 || tailed || overlap_trim); ++m) {
         const std::vector<uint64_t> &t = m ? paired.mate2.trim : paired.mate1.trim;
         const auto w = [&](unsigned i) { return (unsigned long long)t[i]; };
         std::printf(", \"mate%d\": {\"records\": %llu, \"kept\": %llu, \"bases_in\": %llu, \"bases_kept\": %llu, \"bytes_kept\": %llu, "
                     "\"dropped_short\": %llu, \"dropped_long\": %llu, \"dropped_n\": %llu, \"dropped_mean_q\": %llu, \"dropped_low_q\": %llu, "
                     "\"reads_trimmed\": %llu, \"bases_cut_front\": %llu, \"bases_cut_tail\": %llu, \"reads_emptied\": %llu, "
                     "\"reads_with_adapter\": %llu, \"bases_cut_adapter\": %llu, \"reads_with_poly_tail\": %llu, \"bases_cut_poly\": %llu, "
-                    "\"reads_window_cut\": %llu, \"bases_cut_window\": %llu, \"dropped_unmarked\": %llu}",
+                    "\"reads_window_cut\": %llu, \"bases_cut_window\": %llu, \"dropped_unmarked\": %llu",
                     m + 1, w(0), w(1), w(2), w(3), w(4), w(5), w(6), w(7), w(8), w(9), w(10), w(11), w(12), w(13), w(14), w(15), w(16), w(17), w(18),
                     w(19), w(20));
+        if (overlap_trim) std::printf(", \"reads_cut_limit\": %llu, \"bases_cut_limit\": %llu", w(21), w(22));
+        std::printf("}");
       }
     }
     if (filtered && !mate) {
