@@ -53,7 +53,7 @@ __device__ __forceinline__ unsigned reset_state(const LdsCTable &t, unsigned sym
 //  (B) k_seq_resolve: entry state of every segment; a group's functions all start at the group's
 //      entry state (one round of independent loads), x <- F_last[x] from group to group.
 //  (C) k_seq_emit: every lane walks ONE segment from its now-known entry state and writes the
-//      packed (nb, bits) of every symbol; 64 segments of a context per wave.
+//      packed (nb, bits) of every symbol, 64 symbols and one cache line of output per round; 64 segments of a context per wave.
 // All three read the context's one-symbol transition table next[s][x] from LDS (tables.hip
 // builds it once per handle).  Exact by construction: no speculation, nothing to verify.
 // (SETS_WAVES, SETS_WAVES2, SETS_ROUNDS, SETS_MAX_GROUP, SETS_BLOCK, SEQ_CAND_MAX: enc_plan.h, the host sizes scratch by them)
@@ -748,7 +748,24 @@ k_seq_resolve(const uint32_t *__restrict__ plan, const uint32_t *__restrict__ lo
   }
 }
 
-// Step C: one lane per segment, 64 segments of one context per wave
+// Step C: one lane per segment, 64 segments of one context per wave.  The chain of a lane is short (state -> one
+// ds_read_u16 of next1[s][x] -> state), but a lone wave issues one instruction per four cycles, so every instruction of
+// the step is on the clock.  The loop therefore works in ROUNDS of 64 symbols:
+//  - the 64 symbols of the next round (four 16-byte loads) are asked for in front of the walk and waited for behind it;
+//  - a symbol's deltaNbBits is picked with two bit tests (three selects, no branch);
+//  - the round's 128 bytes of out16 are one cache line and leave with eight stores in a row, which this loop never waits
+//    for: gfx9 counts loads and stores in one counter, the next symbols were asked for in front of the stores, so the
+//    wait for them (vmcnt(8)) leaves the stores in flight -- provided nothing else is pending when the loop is entered.
+// What a whole round does not cover, the end of a chain's last segment, goes in groups of 16 with the state frozen
+// behind the chain's last symbol (one group asked for ahead, and a wait for everything per group, as before).
+// (Splitting the walk -- one wave walks the states alone and notes them every 512 symbols, eight waves emit the pieces --
+// makes the kernel shorter alone and the step slower: DESIGN.md section 8.)
+
+// one step of the state chain: state (as (state - size) * 2) behind symbol s
+__device__ __forceinline__ unsigned emit_next(const char *tbase, unsigned log1, unsigned s, unsigned xo) {
+  return *reinterpret_cast<const uint16_t *>(tbase + ((s << log1) + xo));
+}
+
 __global__ void __launch_bounds__(64)
 k_seq_emit(const uint8_t *__restrict__ sorted_sym, uint16_t *__restrict__ out16,
            const uint32_t *__restrict__ arrays, const uint32_t *__restrict__ plan,
@@ -761,7 +778,7 @@ k_seq_emit(const uint8_t *__restrict__ sorted_sym, uint16_t *__restrict__ out16,
   if (blockIdx.x >= eitem[B]) return;  // the grid is an upper bound
   const unsigned c = seq_item_ctx(eitem, blockIdx.x);
   const uint32_t *tbl = ct + ct_off[c];
-  const unsigned log = tbl[0] & 0xFFFFu, size = 1u << log;
+  const unsigned log = tbl[0] & 0xFFFFu, size = 1u << log, log1 = log + 1;
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(next1 + (size_t)c * next_stride);
     uint4 *dst = reinterpret_cast<uint4 *>(lds);
@@ -781,26 +798,66 @@ k_seq_emit(const uint8_t *__restrict__ sorted_sym, uint16_t *__restrict__ out16,
   const uint4 *gsym = reinterpret_cast<const uint4 *>(sorted_sym + run0);
   uint4 *gout = reinterpret_cast<uint4 *>(out16 + run0);
   unsigned xo = entry[seg[c] + k];
-  const unsigned groups = (len + 15) >> 4;  // the run is padded to 16: the pad is walked and never read back
-  uint4 sv = gsym[0];
-  for (unsigned g = 0; g < groups; g++) {
-    const uint4 sv_next = gsym[g + 1 < groups ? g + 1 : g];
-    const unsigned wds[4] = {sv.x, sv.y, sv.z, sv.w};
-    unsigned o[8];
-    const unsigned live = min(16u, len - g * 16);
+  auto packed = [&](unsigned s) {  // (nb << 12 | bits) of symbol s in state xo
+    const unsigned x = size + (xo >> 1);
+    const unsigned d01 = (s & 1u) ? dnb[1] : dnb[0], d23 = (s & 1u) ? dnb[3] : dnb[2];
+    const unsigned nb = (x + ((s & 2u) ? d23 : d01)) >> 16;
+    return (nb << 12) | (x & ((1u << nb) - 1u));
+  };
+  const unsigned full = len >> 6, last = full ? full - 1 : 0u;  // whole rounds
+  uint4 sv[4], nv[4];
 #pragma unroll
-    for (int j = 0; j < 16; j++) {
-      const unsigned s = (wds[j >> 2] >> (8 * (j & 3))) & 3u;
-      const unsigned x = size + (xo >> 1);
-      const unsigned nb = (x + (s == 0 ? dnb[0] : s == 1 ? dnb[1] : s == 2 ? dnb[2] : dnb[3])) >> 16;
-      const unsigned v = (nb << 12) | (x & ((1u << nb) - 1u));
-      if (j & 1) o[j >> 1] |= v << 16; else o[j >> 1] = v;
-      const unsigned nx = *reinterpret_cast<const uint16_t *>(tbase + ((s << (log + 1)) + xo));
-      if ((unsigned)j < live) xo = nx;  // the state stops at the end of the chain
+  for (int q = 0; q < 4; q++) sv[q] = gsym[q];  // (a run of fewer than 64 symbols: still inside the buffer, EncShape::padded)
+  // The first symbols and the entry state are USED here (empty statements that take them as operands), so they have arrived and nothing is
+  // in flight when the loop is entered: inside it the only wait for memory is then the one behind the stores, for the
+  // next round's symbols, which were asked for in front of the stores and leaves them in flight.
+#pragma unroll
+  for (int q = 0; q < 4; q++) asm volatile("" : "+v"(sv[q].x), "+v"(sv[q].y), "+v"(sv[q].z), "+v"(sv[q].w));
+  asm volatile("" : "+v"(xo));  // (the entry state as well: it was asked for behind them)
+  for (unsigned ch = 0; ch < full; ch++) {
+    const uint4 *nx = gsym + 4 * min(ch + 1, last);
+#pragma unroll
+    for (int q = 0; q < 4; q++) nv[q] = nx[q];
+    __builtin_amdgcn_sched_barrier(0);  // (the loads stay in front of the walk that hides them ...)
+    unsigned o[32];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+      const unsigned wds[4] = {sv[q].x, sv[q].y, sv[q].z, sv[q].w};
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const unsigned s = (wds[j >> 2] >> (8 * (j & 3))) & 3u, v = packed(s);
+        if (j & 1) o[8 * q + (j >> 1)] |= v << 16; else o[8 * q + (j >> 1)] = v;
+        xo = emit_next(tbase, log1, s, xo);
+      }
     }
-    gout[2 * g] = make_uint4(o[0], o[1], o[2], o[3]);
-    gout[2 * g + 1] = make_uint4(o[4], o[5], o[6], o[7]);
-    sv = sv_next;
+    __builtin_amdgcn_sched_barrier(0);  // (... the stores stay together ...)
+#pragma unroll
+    for (int q = 0; q < 8; q++) gout[8 * ch + q] = make_uint4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+    __builtin_amdgcn_sched_barrier(0);  // (... and the loads are waited for behind them)
+#pragma unroll
+    for (int q = 0; q < 4; q++) sv[q] = nv[q];
+  }
+  // the end of a chain's last segment, in groups of 16, the next group's symbols asked for a group ahead: the run is
+  // padded to 16, the pad is walked and never read back
+  const unsigned groups = (len + 15) >> 4;
+  if (full * 4 < groups) {
+    uint4 tv = gsym[full * 4];
+    for (unsigned g = full * 4; g < groups; g++) {
+      const uint4 tv_next = gsym[g + 1 < groups ? g + 1 : g];
+      const unsigned wds[4] = {tv.x, tv.y, tv.z, tv.w};
+      const unsigned live = min(16u, len - g * 16);
+      unsigned o[8];
+#pragma unroll
+      for (int j = 0; j < 16; j++) {
+        const unsigned s = (wds[j >> 2] >> (8 * (j & 3))) & 3u, v = packed(s);
+        if (j & 1) o[j >> 1] |= v << 16; else o[j >> 1] = v;
+        const unsigned nxs = emit_next(tbase, log1, s, xo);
+        if ((unsigned)j < live) xo = nxs;  // the state stops at the end of the chain
+      }
+      gout[2 * g] = make_uint4(o[0], o[1], o[2], o[3]);
+      gout[2 * g + 1] = make_uint4(o[4], o[5], o[6], o[7]);
+      tv = tv_next;
+    }
   }
   if (k == ns - 1) final_state[c] = (uint16_t)(size + (xo >> 1));
   if (fq_lane() == 0) atomicMax(&res->refixed, len);

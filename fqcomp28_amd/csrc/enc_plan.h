@@ -146,8 +146,10 @@ struct EncPlan : EncShape {
     // Generic chains: 4096 symbols by default; shorter for small blocks, which are chains of short, latency-bound kernels (a
     // lane of the walk/emit kernels walks one segment): 16 MiB blocks +8 %, 4 MiB blocks +25 % with 1024-2048 (measured)
     S = whole_blocks(in.seg_len ? in.seg_len : n_sym >= (24u << 20) ? 4096u : n_sym >= (4u << 20) ? 2048u : 1024u);
-    // Sequence chains: a lane of k_seq_emit walks one segment, a pure latency chain -- blocks of 64 MiB and less gain 4 %
-    // from 2048-symbol segments, 256 MiB blocks nothing.  The result never depends on either length.
+    // Sequence chains: a lane of k_seq_emit walks one whole segment, so the kernel's length grows with the segment -- blocks
+    // of 64 MiB and less gained 4 % from 2048-symbol segments, 256 MiB blocks nothing (measured with the kernel that emitted
+    // 16 symbols per round; not measured again with the 64-symbol rounds, which left the walk one lane per segment).
+    // The result never depends on either length.
     seq_S = whole_blocks(in.seq_segment ? in.seq_segment : n_sym >= (48u << 20) ? 4096u : n_sym >= (4u << 20) ? 2048u : 1024u);
     max_items = (unsigned)((size_t)n_sym / ((size_t)S * 64) + B + 1);
     gen_max_segs = n_sym / S + B + 1;
