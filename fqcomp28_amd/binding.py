@@ -183,6 +183,11 @@ _PROTOS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_pair_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_correct_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_pair_correct": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_pair_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_chunk_pair_names": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_pair_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_read_id_len": (C.c_size_t, [C.c_void_p, C.c_size_t]),
@@ -523,6 +528,36 @@ def _overlap_call(fn, front, count, spec, want_arrays=True, cap_words=None):
     return dict(rc=rc, out=out, limit_a=la, limit_b=lb, insert=ins)
 
 
+CORRECT_REPORT_WORDS = 8
+CORRECT_REPORT_NAMES = ("n_pairs", "pairs_with_insert", "pairs_corrected", "bases_corrected_a", "bases_corrected_b", "n_resolved",
+                        "mismatches_seen", "overlap_bases")
+
+
+def read_correct(good_q=30, bad_q=14, reserved=(0, 0, 0, 0, 0, 0)):
+    """an fqgpu_correct (include/fqgpu.h) as a uint32 array of eight words; the defaults are the tool's"""
+    return np.array([good_q, bad_q, *reserved], dtype=np.uint32)
+
+
+def correct_check(spec):
+    """fqgpu_correct_check -> rc (host only)"""
+    return lib().fqgpu_correct_check(_p(None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)))
+
+
+def _correct_call(fn, front, count, insert, spec, want_arrays=True, want_report=True):
+    """A device correcting call -> dict(rc, report, fixed_a, fixed_b): report a fresh uint64 array of CORRECT_REPORT_WORDS, the
+    two arrays uint16[count] or None; insert: None (NULL), or uint16 -- fewer than count (a count the call is to refuse) are
+    padded with zeros, so that the library never reads behind them.  THE CALL CHANGES BOTH CHUNKS"""
+    spec = None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)
+    insert = None if insert is None else np.ascontiguousarray(insert, dtype=np.uint16)
+    if insert is not None and insert.size < count:
+        insert = np.concatenate((insert, np.zeros(count - insert.size, dtype=np.uint16)))
+    report = np.zeros(CORRECT_REPORT_WORDS, dtype=np.uint64)
+    arrays = [np.zeros(max(count, 1), dtype=np.uint16) if want_arrays else None for _ in range(2)]
+    rc = fn(*front, count, _p(insert), _p(spec), _p(report) if want_report else None, *[_p(a) for a in arrays])
+    fa, fb = [None if a is None else a[:count] for a in arrays]
+    return dict(rc=rc, report=report, fixed_a=fa, fixed_b=fb)
+
+
 def read_id_len(header_line):
     """fqgpu_read_id_len (host only): the length of the read id of a header line (bytes, with its '@')"""
     line = np.frombuffer(bytes(header_line), dtype=np.uint8)
@@ -732,6 +767,13 @@ class DBlock:
         front of its steps -> as select_marked, report words 21 / 22 counted"""
         return _limited_call(lib().fqgpu_dblock_select_limited, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, limit, **kw)
 
+    def pair_correct(self, first, other, other_first, count, insert, spec, **kw):
+        """fqgpu_dblock_pair_correct: with the insert sizes `insert` (pair_overlap's) the mismatched bases inside the overlap of
+        this block's records first + i (mate 1) and `other`'s other_first + i (mate 2), i < count, corrected for `spec`
+        (read_correct); it CHANGES both blocks' raw bytes -> dict(rc, report, fixed_a, fixed_b); see _correct_call"""
+        return _correct_call(lib().fqgpu_dblock_pair_correct, (self.ctx.h, self.h, first, other.h if other is not None else None, other_first),
+                             count, insert, spec, **kw)
+
     def pair_overlap(self, first, other, other_first, count, spec, **kw):
         """fqgpu_dblock_pair_overlap: the mate overlap of this block's records first + i (mate 1) and `other`'s other_first + i
         (mate 2), i < count, for `spec` (read_overlap) -> dict(rc, out, limit_a, limit_b, insert); see _overlap_call"""
@@ -898,6 +940,12 @@ class Context:
     def chunk_select_limited(self, first, end, mark=None, limit=None, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_chunk_select_limited: chunk_select_marked with a per-record limit -> as DBlock.select_limited"""
         return _limited_call(lib().fqgpu_chunk_select_limited, (self.h,), adapter, tail, trim, flt, first, end, mark, limit, **kw)
+
+    def chunk_pair_correct(self, first, other, other_first, count, insert, spec, **kw):
+        """fqgpu_chunk_pair_correct: the correction inside the mate overlap of the chunk staged here (mate 1) and the chunk staged
+        on the Context `other` (mate 2); it CHANGES both staged chunks -> as DBlock.pair_correct"""
+        return _correct_call(lib().fqgpu_chunk_pair_correct, (self.h, first, other.h if other is not None else None, other_first), count, insert,
+                             spec, **kw)
 
     def chunk_pair_overlap(self, first, other, other_first, count, spec, **kw):
         """fqgpu_chunk_pair_overlap: the mate overlap of the chunk staged here (mate 1) and the chunk staged on the Context

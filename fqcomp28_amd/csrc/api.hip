@@ -2008,3 +2008,48 @@ extern "C" int fqgpu_dblock_pair_overlap(fqgpu_ctx *ctx, const fqgpu_dblock *ba,
                                          uint16_t *limit_b_out, uint16_t *insert_out) {
   return overlap_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, o, out, cap_words, limit_a_out, limit_b_out, insert_out);
 }
+
+// The two correcting calls (staged: the chunks staged on the two handles; else two blocks of ctx_a's device): the overlap
+// calls' checks and waits -- no device is said before any argument is looked at, then the arguments, then the states --, but
+// the two sides must be two chunks, for these calls CHANGE them (select.hip, k_pair_correct).  Every FQGPU_E_ARG leaves both
+// chunks as they were and the report and the two arrays zeroed.
+static int correct_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
+                        size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out,
+                        uint16_t *fixed_b_out) {
+  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
+  const auto run = [&]() -> int {
+    if (!report) return FQGPU_E_ARG;
+    memset(report, 0, FQGPU_CORRECT_REPORT_WORDS * sizeof(uint64_t));
+    if (!ctx_a || !insert_in || fqgpu_correct_check(c) != FQGPU_OK) return FQGPU_E_ARG;
+    int rc;
+    if (staged) {
+      if (!ctx_b || ctx_a == ctx_b || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
+      if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
+    } else {
+      if (ba == bb) return FQGPU_E_ARG;
+      if ((rc = settled_block(ctx_a, ba)) || (rc = settled_block(ctx_a, bb))) return rc;
+    }
+    if (ba == bb || count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs ||
+        count > bb->n_recs - first_b)
+      return FQGPU_E_ARG;
+    return fq_pair_correct(ctx_a, ctx_a->stream, ba->raw, ba->raw_len, ba->recs + first_a, bb->raw, bb->raw_len, bb->recs + first_b, count, insert_in,
+                           c, report, fixed_a_out, fixed_b_out);
+  };
+  const int rc = run();
+  if (rc == FQGPU_E_ARG) {
+    for (uint16_t *p : {fixed_a_out, fixed_b_out})
+      if (p && count) memset(p, 0, count * sizeof(uint16_t));
+  }
+  return rc;
+}
+
+extern "C" int fqgpu_chunk_pair_correct(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const uint16_t *insert_in,
+                                        const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out, uint16_t *fixed_b_out) {
+  return correct_call(true, ctx_a, ctx_b, nullptr, first_a, nullptr, first_b, count, insert_in, c, report, fixed_a_out, fixed_b_out);
+}
+
+extern "C" int fqgpu_dblock_pair_correct(fqgpu_ctx *ctx, fqgpu_dblock *ba, size_t first_a, fqgpu_dblock *bb, size_t first_b, size_t count,
+                                         const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out,
+                                         uint16_t *fixed_b_out) {
+  return correct_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, insert_in, c, report, fixed_a_out, fixed_b_out);
+}

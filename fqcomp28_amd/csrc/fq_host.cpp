@@ -181,6 +181,14 @@ extern "C" int fqgpu_overlap_merge(uint64_t *dst, size_t dst_words, const uint64
   return FQGPU_OK;
 }
 
+// The correction inside the mate overlap (select.hip applies it): what a spec may say.
+extern "C" int fqgpu_correct_check(const fqgpu_correct *c) {
+  if (!c || c->good_q < 1u || c->good_q > 63u || c->bad_q >= c->good_q) return FQGPU_E_ARG;
+  for (uint32_t r : c->reserved)
+    if (r) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
 // Poly-X tails and the sliding-window cut (select.hip applies them): what a tail may say.
 extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   if (!x || x->poly_bases > 15u || x->poly_max_mism > 255u || x->window_len > 32u || x->reserved[0] || x->reserved[1]) return FQGPU_E_ARG;

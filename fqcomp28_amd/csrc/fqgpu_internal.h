@@ -270,18 +270,22 @@ FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs)
 // (fqgpu_chunk_select_marked) has one: the caller's mark, a u64 word per 64 records; a limited call
 // (fqgpu_chunk_select_limited) another: the caller's limits, a uint16_t per record.  An overlap call
 // (fqgpu_chunk_pair_overlap) has two: its u64 result words and the pairs' limit1, limit2 and I, three arrays of uint16_t.
+// A correcting call (fqgpu_chunk_pair_correct) has two: the caller's inserts and the pairs' changed places, two arrays of
+// uint16_t; its counters are the result words.
 struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   DevBuf probe_out, probe_places;
   DevBuf mark, limit;
   DevBuf overlap_out, overlap_pairs;
+  DevBuf correct_in, correct_fixed;
   void *host = nullptr;
   void release_host();
 };
 FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, hstart), FQ_B(SelectScratch, win), FQ_B(SelectScratch, clip),
                 FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
                 FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places),
-                FQ_B(SelectScratch, mark), FQ_B(SelectScratch, limit), FQ_B(SelectScratch, overlap_out), FQ_B(SelectScratch, overlap_pairs))
+                FQ_B(SelectScratch, mark), FQ_B(SelectScratch, limit), FQ_B(SelectScratch, overlap_out), FQ_B(SelectScratch, overlap_pairs),
+                FQ_B(SelectScratch, correct_in), FQ_B(SelectScratch, correct_fixed))
 
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
@@ -514,6 +518,16 @@ int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t
                     size_t raw_len_b, const fqgpu_rec *recs_b, size_t count, const fqgpu_overlap *o, uint64_t *out, uint16_t *limit_a_out,
                     uint16_t *limit_b_out, uint16_t *insert_out);
 uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o);  // fq_host.cpp: zlib's CRC-32 of the spec's 32 bytes
+
+// The correction inside the mate overlap (include/fqgpu.h) of the records recs_a[i] (mate 1) and recs_b[i] (mate 2), i < count,
+// of two DIFFERENT chunks in HBM on ctx's device, both at rest (select.hip; the spec has passed its check), with the host's
+// insert_in[i], on st, waited for: it CHANGES both chunks.  report[0, FQGPU_CORRECT_REPORT_WORDS) on the host and -- each where
+// not nullptr -- count uint16_t of the places changed in either mate.  FQGPU_E_ARG with the report zeroed and both chunks as
+// they were: count 0, an insert the lengths do not allow, a record with an insert outside its chunk, of length 0 or above
+// 512, a byte inside an overlap that cannot be judged
+int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, uint8_t *raw_b, size_t raw_len_b,
+                    const fqgpu_rec *recs_b, size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report,
+                    uint16_t *fixed_a_out, uint16_t *fixed_b_out);
 
 // Adapter content of a chunk in HBM (select.hip; the probe set has passed its check, positions is 1 .. 65535), on st, waited
 // for: out[0, fqgpu_probe_words(p->n, positions)) on the host and -- places_out != nullptr -- p->n places per record

@@ -815,6 +815,15 @@ inline void placeBits(const uint8_t *src, std::size_t count, uint8_t *dst, std::
 }
 }  // namespace detail
 
+/** Extension: reports of fqgpu_chunk_pair_correct add word by word -- a piece's into its worker's, a worker's into the run's.
+ *  dst: empty (it becomes src's size, zeros) or FQGPU_CORRECT_REPORT_WORDS words; src: that many, else std::logic_error. */
+inline void addCorrectReport(std::vector<uint64_t> &dst, const uint64_t *src, std::size_t src_words) {
+  if (dst.empty()) dst.assign(FQGPU_CORRECT_REPORT_WORDS, 0);
+  if (!src || src_words != FQGPU_CORRECT_REPORT_WORDS || dst.size() != FQGPU_CORRECT_REPORT_WORDS)
+    throw std::logic_error("addCorrectReport: not a correction's report");
+  for (std::size_t i = 0; i < src_words; ++i) dst[i] += src[i];
+}
+
 /** Extension: a part of a paired restore's work unit -- the mates of the records [at, at + end - first) of the unit are the
  *  records [first, end) of block `block` of archive 2 */
 struct MatePiece {
@@ -839,6 +848,7 @@ struct PairedReport {
   uint64_t pairs = 0, kept = 0, dropped_mate1_only = 0, dropped_mate2_only = 0, dropped_both = 0;
   std::size_t blocks1 = 0, blocks2 = 0, decodes2 = 0;
   std::vector<uint64_t> overlap;  // with Selection::overlap: the units' summaries merged (FQGPU_OVERLAP_WORDS; an archive without records: zeros)
+  std::vector<uint64_t> correct;  // with Selection::correct: the pieces' reports added word by word (FQGPU_CORRECT_REPORT_WORDS)
 };
 
 /** Extension: `d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq>` -- two archives whose records are mates restored in
@@ -859,7 +869,12 @@ struct PairedReport {
  *  order inside a unit changes, because mate 1 cannot be judged before its mates are staged: step (2) is left out and per
  *  piece, behind the overlap, mate 1's records [at, at + count) are judged as a size query with their limits -- those keep
  *  bits are the piece's mark --, then the piece of mate 2 is judged and gathered with its limits; step (4) takes mate 1's
- *  limits too.  No chunk is decoded more often than without.
+ *  limits too.  No chunk is decoded more often than without.  With sel.correct every piece is corrected directly behind its
+ *  overlap (fqgpu_chunk_pair_correct with the piece's insert sizes), in front of everything that judges either mate, for it
+ *  changes qualities and N counts: the unit takes the order just described -- its condition is "limits or correction", the
+ *  limit pointers stay nullptr unless overlap_trim is on --, mate 1's chunk stays staged for the unit and collects every
+ *  piece's corrections before its final gather, and a chunk of archive 2 that two workers decode is patched by each in its
+ *  own range only.  The digests are taken at staging, before any correction; rep.correct sums the pieces' reports.
  *  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
  *  nor a `.part` file.  Throws before any output is opened when the archives' record totals differ. */
 inline PairedReport processArchivePaired(const path_t &archive1_path, const path_t &out1, const path_t &archive2_path, const path_t &out2,
@@ -887,6 +902,9 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
     std::vector<uint8_t> k1, k, mark, keep;
     std::vector<uint16_t> limit1, limit2;         // with an overlap spec: the unit's limits of mate 1, the piece's of mate 2
     std::vector<uint64_t> overlap, overlap_sum;   // ... the piece's summary, the worker's
+    std::vector<uint16_t> insert;                 // with a correction: the piece's insert sizes
+    uint64_t correct[FQGPU_CORRECT_REPORT_WORDS];  // ... the piece's report
+    std::vector<uint64_t> correct_sum;             // ... the worker's (empty until its first piece)
     uint64_t report[W], sum1[W] = {}, sum2[W] = {};
     InputStats in2;
     unsigned decodes2 = 0;
@@ -910,9 +928,10 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
       clk.lap("read");
       w1.stagePairedChunk(cbs1);
       verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
-      const bool limited = sel.overlap && sel.overlap_trim;  // mate 1 is then judged piece by piece, behind the piece's overlap
+      const bool limited = sel.overlap && sel.overlap_trim;  // the limits stand in front of each mate's steps
+      const bool by_piece = limited || sel.correct;          // mate 1 is then judged piece by piece, behind the piece's overlap
       w.k1.assign((n + 7) / 8, 0);
-      if (!limited) (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
+      if (!by_piece) (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
       clk.lap("mate 1");
       w.k.assign((n + 7) / 8, 0);
       if (sel.overlap) {
@@ -936,11 +955,17 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
         w.keep.assign((count + 7) / 8, 0);
         if (sel.overlap) {
           w.limit2.assign(count, 0);
-          w1.pairOverlap(at, w2, pc.first, count, *sel.overlap, w.overlap.data(), w.limit1.data() + at, w.limit2.data());
+          if (sel.correct) w.insert.assign(count, 0);
+          w1.pairOverlap(at, w2, pc.first, count, *sel.overlap, w.overlap.data(), w.limit1.data() + at, w.limit2.data(),
+                         sel.correct ? w.insert.data() : nullptr);
           if (fqgpu_overlap_merge(w.overlap_sum.data(), w.overlap_sum.size(), w.overlap.data(), w.overlap.size()) != FQGPU_OK)
             throw std::logic_error(name + ": overlap summaries of different specs");
+          if (sel.correct) {  // (in front of everything that judges either mate)
+            w1.pairCorrect(at, w2, pc.first, count, w.insert.data(), *sel.correct, w.correct);
+            addCorrectReport(w.correct_sum, w.correct, FQGPU_CORRECT_REPORT_WORDS);
+          }
         }
-        if (limited) (void)w1.selectMarked(sel, at, at + count, nullptr, nullptr, 0, w.report, w.mark.data(), w.limit1.data() + at);
+        if (by_piece) (void)w1.selectMarked(sel, at, at + count, nullptr, nullptr, 0, w.report, w.mark.data(), limited ? w.limit1.data() + at : nullptr);
         else detail::sliceBits(w.k1.data(), at, count, w.mark.data());
         piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
         len2 += w2.selectMarked(sel2, pc.first, pc.end, w.mark.data(), reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2,
@@ -975,10 +1000,12 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   rep.mate1.trim.assign(W, 0);
   rep.mate2.trim.assign(W, 0);
   if (sel.overlap) rep.overlap.assign(FQGPU_OVERLAP_WORDS, 0);
+  if (sel.correct) rep.correct.assign(FQGPU_CORRECT_REPORT_WORDS, 0);
   for (std::size_t t = 0; t < farm.workers().size(); ++t) {
     const Worker &w = *farm.workers()[t];
     if (!w.overlap_sum.empty() && fqgpu_overlap_merge(rep.overlap.data(), rep.overlap.size(), w.overlap_sum.data(), w.overlap_sum.size()) != FQGPU_OK)
       throw std::logic_error(name + ": overlap summaries of different specs");
+    if (!w.correct_sum.empty()) addCorrectReport(rep.correct, w.correct_sum.data(), w.correct_sum.size());
     rep.mate2.in += w.in2;
     rep.mate2.blocks_per_worker[t] = w.decodes2;
     rep.decodes2 += w.decodes2;
@@ -1003,9 +1030,13 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
 
 /** Extension: the report file of a mate overlap summary (fqgpu_chunk_pair_overlap, merged) -- text, tab-separated, integers
  *  only, a pure function of the summary and the spec: the spec's three numbers, the eight summary words by name, then
- *  "insert", I and the pairs for every non-empty row.  Written as `<path>.part` and renamed when it is complete. */
-inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu_overlap &spec) {
+ *  "insert", I and the pairs for every non-empty row; with a correction (`correct` and its summed report `cw`), and only then,
+ *  six more lines behind the last row: good_q, bad_q, pairs_corrected, bases_corrected_1, bases_corrected_2, n_resolved.
+ *  Written as `<path>.part` and renamed when it is complete. */
+inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu_overlap &spec, const fqgpu_correct *correct = nullptr,
+                                     const std::vector<uint64_t> &cw = {}) {
   if (w.size() != FQGPU_OVERLAP_WORDS) throw std::logic_error("writeOverlapReport: not an overlap summary");
+  if (correct && cw.size() != FQGPU_CORRECT_REPORT_WORDS) throw std::logic_error("writeOverlapReport: not a correction's report");
   std::string out = "#fqgpu-overlap 1\n";
   const auto line = [&](const char *name, uint64_t v) { out += name; out += '\t'; out += std::to_string(v); out += '\n'; };
   line("min_overlap", spec.min_overlap);
@@ -1016,10 +1047,19 @@ inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu
   for (int i = 0; i < 8; ++i) line(names[i], w[i]);
   for (std::size_t r = 0; r < FQGPU_OVERLAP_ROWS; ++r)
     if (w[16 + r]) { out += "insert\t"; out += std::to_string(r); out += '\t'; out += std::to_string(w[16 + r]); out += '\n'; }
+  if (correct) {  // behind the last row: the correction's two numbers and what it did
+    line("good_q", correct->good_q);
+    line("bad_q", correct->bad_q);
+    line("pairs_corrected", cw[2]);
+    line("bases_corrected_1", cw[3]);
+    line("bases_corrected_2", cw[4]);
+    line("n_resolved", cw[5]);
+  }
   return out;
 }
-inline void writeOverlapReport(const path_t &path, const std::vector<uint64_t> &w, const fqgpu_overlap &spec) {
-  const std::string out = overlapReportText(w, spec);
+inline void writeOverlapReport(const path_t &path, const std::vector<uint64_t> &w, const fqgpu_overlap &spec, const fqgpu_correct *correct = nullptr,
+                               const std::vector<uint64_t> &cw = {}) {
+  const std::string out = overlapReportText(w, spec, correct, cw);
   const path_t part = path.string() + ".part";
   std::FILE *f = std::fopen(part.string().c_str(), "wb");
   const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();

@@ -71,6 +71,9 @@
 // complemented, a lane per candidate shift, the first hit in the rule's order by a ballot; it leaves a summary with the
 // insert-size histogram and per pair the two limits and the insert size.  k_select_limit, behind k_adapter_find, takes the
 // minimum of a caller's per-record limit into the clip places, so that the judge's clip forms serve a limit unchanged.
+// k_pair_correct (fqgpu_chunk_pair_correct) is the one kernel here that CHANGES a chunk: with the pairs' insert sizes it
+// walks each overlap once, eight places to a lane, and where the mates disagree and one base is confident and the other
+// poor it replaces the poor one -- launched twice, first to judge and count, then, if nothing was refused, to store.
 //
 // All global stores are ordinary vector stores from plain C++.
 #include "fqgpu_internal.h"
@@ -1737,6 +1740,131 @@ k_pair_overlap(const OvSide A, const OvSide B, unsigned count, const OvSpec sp, 
   if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
 }
 
+// ---- the correction inside the mate overlap (include/fqgpu.h, fqgpu_chunk_pair_correct): THE kernel that changes a chunk.
+// k_pair_overlap's shape -- a wave takes 64 consecutive pairs, table entries and inserts with one load, lane = pair, the
+// per-pair results back in the pair's lane -- but no LDS: the wave walks the pairs that have an insert one after the other,
+// and a lane takes the eight places [lo + 8 lane, lo + 8 lane + 8) of the overlap.  The bytes of s1 and q1 are one eight-byte
+// load from wherever the place lies; those of s2 and q2 are the eight bytes that END at j = I - 1 - i, taken in reverse.
+// That window starts up to seven bytes in front of j's line -- bytes of a place behind hi, which is not judged -- and for a
+// chunk's first record in front of the chunk: its start is clamped to the chunk's first byte and the word shifted up by what
+// was clamped.  Reads behind a line's end fall into the chunk or its 64 spare bytes.  A place is decided from its own four
+// bytes, and no byte belongs to two places, so the launch with APPLY = false (it judges, counts and stores nothing into the
+// chunks) and the launch with APPLY = true (it stores, and counts nothing) decide alike, and the second one runs only when
+// the first refused nothing.  A store goes to s1[i], q1[i], i in [lo, hi), or s2[j], q2[j], j in [0, L2): inside lines that
+// the lane = pair check found inside their chunks.  Corrections are rare: plain byte stores under the lane's predicate.
+struct CorSide {
+  uint8_t *raw;
+  unsigned long long raw_len;
+  const fqgpu_rec *recs;  // the first record of the range
+};
+__device__ __forceinline__ unsigned long long cor_load8(const uint8_t *p) {
+  const OvU64 v = *reinterpret_cast<const OvU64 *>(p);
+  return (unsigned long long)v.b << 32 | v.a;
+}
+// the eight bytes of a chunk at off + rel (rel >= -7, off + rel + 8 > 0); the bytes in front of the chunk read as zero
+__device__ __forceinline__ unsigned long long cor_load8_back(const uint8_t *raw, unsigned off, int rel) {
+  const long long at = (long long)off + rel;
+  const unsigned clamped = at < 0 ? (unsigned)-at : 0u;
+  return cor_load8(raw + (at + clamped)) << (8u * clamped);
+}
+__device__ __forceinline__ unsigned cor_comp(unsigned b) { return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b; }
+__device__ __forceinline__ bool cor_is_base(unsigned b) { return b == 'A' || b == 'C' || b == 'G' || b == 'T' || b == 'N'; }
+__device__ __forceinline__ unsigned cor_wave_sum(unsigned v) {
+#pragma unroll
+  for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+template <bool APPLY>
+__global__ void __launch_bounds__(OV_THREADS)
+k_pair_correct(const CorSide A, const CorSide B, unsigned count, const uint16_t *__restrict__ inserts, unsigned good_q, unsigned bad_q,
+               unsigned long long *__restrict__ out, uint16_t *__restrict__ fixed, unsigned *__restrict__ bad_out) {
+  const unsigned lane = threadIdx.x;
+  const unsigned long long p0 = (unsigned long long)blockIdx.x * OV_WG_PAIRS;
+  const bool have = p0 + lane < count;
+  fqgpu_rec ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
+  unsigned ins = 0;
+  if (have) ins = inserts[p0 + lane];
+  if (ins) {  // (a pair without an insert: none of its lines, and not its table entries either)
+    ra = A.recs[p0 + lane];
+    rb = B.recs[p0 + lane];
+  }
+  const auto inside = [](const fqgpu_rec &r, unsigned long long raw_len) {
+    return r.len != 0 && r.len <= FQGPU_OVERLAP_MAX_LEN && (unsigned long long)r.seq_off + r.len <= raw_len &&
+           (unsigned long long)r.qual_off + r.len <= raw_len;
+  };
+  const bool ok = ins && inside(ra, A.raw_len) && inside(rb, B.raw_len) && ins <= ra.len + rb.len - 1u;
+  bool bad = ins && !ok;
+  unsigned my_fixed_a = 0, my_fixed_b = 0;                            // the lane's pair
+  unsigned n_fa = 0, n_fb = 0, n_res = 0, n_mism = 0;                 // the lane's places, over all pairs
+  unsigned n_pairs_fixed = 0, n_ov = 0;                               // (the same in every lane)
+  unsigned long long todo = __ballot(ok);
+  while (todo) {  // (uniform)
+    const unsigned p = (unsigned)__builtin_ctzll(todo);
+    todo &= todo - 1ull;
+    const unsigned L1 = fq_uniform(__shfl(ra.len, p)), L2 = fq_uniform(__shfl(rb.len, p)), I = fq_uniform(__shfl(ins, p));
+    const unsigned s1_off = fq_uniform(__shfl(ra.seq_off, p)), q1_off = fq_uniform(__shfl(ra.qual_off, p));
+    const unsigned s2_off = fq_uniform(__shfl(rb.seq_off, p)), q2_off = fq_uniform(__shfl(rb.qual_off, p));
+    const unsigned lo = I > L2 ? I - L2 : 0u, hi = min(L1, I);  // hi - lo >= 1, and <= 512
+    n_ov += hi - lo;
+    const unsigned i0 = lo + 8u * lane;
+    unsigned fa = 0, fb = 0;
+    if (i0 < hi) {
+      const unsigned n = min(8u, hi - i0);
+      const int j0 = (int)I - 1 - (int)i0 - 7;  // the window [j0, j0 + 8) of mate 2: place i0 + t stands beside j0 + 7 - t
+      const unsigned long long s1 = cor_load8(A.raw + s1_off + i0), q1 = cor_load8(A.raw + q1_off + i0);
+      const unsigned long long s2 = cor_load8_back(B.raw, s2_off, j0), q2 = cor_load8_back(B.raw, q2_off, j0);
+#pragma unroll
+      for (unsigned t = 0; t < 8; t++) {
+        const unsigned b1 = (unsigned)(s1 >> (8u * t)) & 0xFFu, c1 = (unsigned)(q1 >> (8u * t)) & 0xFFu;
+        const unsigned b2 = (unsigned)(s2 >> (8u * (7u - t))) & 0xFFu, c2 = (unsigned)(q2 >> (8u * (7u - t))) & 0xFFu;
+        const bool in = t < n;
+        bad = bad || (in && !(cor_is_base(b1) && cor_is_base(b2) && c1 >= 33u && c1 <= 96u && c2 >= 33u && c2 <= 96u));
+        const unsigned p1 = c1 - 33u, p2 = c2 - 33u;
+        const bool differ = in && (b1 == 'N' || b2 == 'N' || b1 != cor_comp(b2));
+        const bool win1 = differ && b1 != 'N' && p1 >= good_q && p2 <= bad_q;
+        const bool win2 = differ && b2 != 'N' && p2 >= good_q && p1 <= bad_q;
+        n_mism += differ;
+        fb += win1;
+        fa += win2;
+        n_res += (win1 && b2 == 'N') || (win2 && b1 == 'N');
+        if (APPLY) {
+          const unsigned j = (unsigned)(j0 + 7 - (int)t);  // (in [0, L2) for a place of the overlap)
+          if (win1) {
+            B.raw[s2_off + j] = (uint8_t)cor_comp(b1);
+            B.raw[q2_off + j] = (uint8_t)c1;
+          }
+          if (win2) {
+            A.raw[s1_off + i0 + t] = (uint8_t)cor_comp(b2);
+            A.raw[q1_off + i0 + t] = (uint8_t)c2;
+          }
+        }
+      }
+    }
+    if (!APPLY && __any(fa | fb)) {  // (uniform, and rare)
+      const unsigned pa = cor_wave_sum(fa), pb = cor_wave_sum(fb);
+      n_pairs_fixed++;
+      if (lane == p) {
+        my_fixed_a = pa;
+        my_fixed_b = pb;
+      }
+    }
+    n_fa += fa;
+    n_fb += fb;
+  }
+  if (APPLY) return;
+  const unsigned cnt[8] = {0u, (unsigned)__popcll(__ballot(ins != 0u)), n_pairs_fixed, cor_wave_sum(n_fa), cor_wave_sum(n_fb),
+                           cor_wave_sum(n_res), cor_wave_sum(n_mism), n_ov};
+#pragma unroll
+  for (unsigned i = 1; i < 8; i++)
+    if (lane == i && cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
+  if (have) {
+    fixed[p0 + lane] = (uint16_t)my_fixed_a;
+    fixed[(unsigned long long)count + p0 + lane] = (uint16_t)my_fixed_b;
+  }
+  if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
+}
+
 }  // namespace
 
 void SelectScratch::release_host() {
@@ -1976,5 +2104,50 @@ int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t
   }
   out[0] = count;
   out[8] = fq_overlap_fingerprint(o);
+  return FQGPU_OK;
+}
+
+// The correction inside the mate overlap of `count` records of two DIFFERENT chunks on one device, on st (both chunks are at
+// rest), waited for.  The same kernel twice: the first launch judges and counts and leaves the chunks alone; its result words,
+// the two arrays and the verdict come down behind it, and only when nothing was refused and a base is to change does the
+// second launch store -- so FQGPU_E_ARG leaves both chunks as they were.  The inserts go up as a limited call's limits do.
+// FQGPU_E_ARG zeroes report; the two arrays are then the caller's to zero.
+int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, uint8_t *raw_b, size_t raw_len_b,
+                    const fqgpu_rec *recs_b, size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report,
+                    uint16_t *fixed_a_out, uint16_t *fixed_b_out) {
+  memset(report, 0, FQGPU_CORRECT_REPORT_WORDS * sizeof(uint64_t));
+  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  SelectScratch &ss = ctx->select;
+  int rc;
+  if ((rc = ss.correct_in.reserve(count * 2)) || (rc = ss.correct_fixed.reserve(count * 4)) || (rc = ss.res.reserve(sizeof(SelectResult)))) return rc;
+  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
+  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
+  SelectResult *const dev = ss.res.as<SelectResult>();
+  uint16_t *const fixed = ss.correct_fixed.as<uint16_t>();
+  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
+  FQ_HIP(hipMemcpyAsync(ss.correct_in.p, insert_in, count * 2, hipMemcpyHostToDevice, st));
+  const CorSide A = {raw_a, (unsigned long long)raw_len_a, recs_a}, B = {raw_b, (unsigned long long)raw_len_b, recs_b};
+  const dim3 grid((unsigned)((count + OV_WG_PAIRS - 1) / OV_WG_PAIRS));
+  static_assert(FQGPU_CORRECT_REPORT_WORDS <= FQGPU_TAIL_REPORT_WORDS, "the counters are the selection result's words");
+  fq_timer_span_begin(ctx, "pair_correct", st);
+  hipLaunchKernelGGL(k_pair_correct<false>, grid, dim3(OV_THREADS), 0, st, A, B, (unsigned)count, ss.correct_in.as<uint16_t>(), c->good_q, c->bad_q,
+                     &dev->w[0], fixed, &dev->bad);
+  fq_timer_span_end(ctx, st);
+  FQ_HIP(hipGetLastError());
+  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  if (fixed_a_out) FQ_HIP(hipMemcpyAsync(fixed_a_out, fixed, count * 2, hipMemcpyDeviceToHost, st));
+  if (fixed_b_out) FQ_HIP(hipMemcpyAsync(fixed_b_out, fixed + count, count * 2, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  if (res.bad) return FQGPU_E_ARG;  // (the caller zeroes the two arrays)
+  for (unsigned i = 1; i < FQGPU_CORRECT_REPORT_WORDS; i++) report[i] = res.w[i];
+  report[0] = count;
+  if (report[3] + report[4]) {
+    fq_timer_span_begin(ctx, "pair_correct", st);
+    hipLaunchKernelGGL(k_pair_correct<true>, grid, dim3(OV_THREADS), 0, st, A, B, (unsigned)count, ss.correct_in.as<uint16_t>(), c->good_q, c->bad_q,
+                       &dev->w[0], fixed, &dev->bad);
+    fq_timer_span_end(ctx, st);
+    FQ_HIP(hipGetLastError());
+    FQ_HIP(hipStreamSynchronize(st));
+  }
   return FQGPU_OK;
 }

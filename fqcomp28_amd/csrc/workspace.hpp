@@ -546,6 +546,9 @@ struct Selection {
    *  PairedReport::overlap; overlap_trim: its limits stand in front of each mate's steps */
   const fqgpu_overlap *overlap = nullptr;
   bool overlap_trim = false;
+  /** ... and, with `correct`, the mismatched bases inside every overlap are corrected (fqgpu_chunk_pair_correct) behind the
+   *  analysis and in front of everything that judges either mate; PairedReport::correct sums its reports */
+  const fqgpu_correct *correct = nullptr;
   /** something is cut: the counters are a trim report (FarmReport::trim), not a filter report (FarmReport::filter) */
   [[nodiscard]] bool trims() const { return adapter || tail || trim; }
   /** the fqgpu_chunk_* call that serves it, by the name of its first step */
@@ -564,6 +567,8 @@ struct Selection {
     if ((filter || !(trims() || may_be_empty)) && fqgpu_filter_check(filter) != FQGPU_OK) throw std::invalid_argument(name + ": a filter fqgpu_filter_check refuses");
     if (overlap && fqgpu_overlap_check(overlap) != FQGPU_OK) throw std::invalid_argument(name + ": an overlap spec fqgpu_overlap_check refuses");
     if (overlap_trim && !overlap) throw std::invalid_argument(name + ": overlap_trim without an overlap spec");
+    if (correct && !overlap) throw std::invalid_argument(name + ": a correction without an overlap spec");
+    if (correct && fqgpu_correct_check(correct) != FQGPU_OK) throw std::invalid_argument(name + ": a correction fqgpu_correct_check refuses");
   }
 };
 
@@ -762,12 +767,22 @@ public:
     return mismatch;
   }
   /** fqgpu_chunk_pair_overlap: this handle's staged records first + i (mate 1) against `mate`'s mate_first + i (mate 2),
-   *  i < count -> out[0, FQGPU_OVERLAP_WORDS) and, each where not nullptr, count limits of either mate */
+   *  i < count -> out[0, FQGPU_OVERLAP_WORDS) and, each where not nullptr, count limits of either mate and count insert sizes */
   void pairOverlap(std::size_t first, DecompressionWorkspace &mate, std::size_t mate_first, std::size_t count, const fqgpu_overlap &spec,
-                   uint64_t *out, uint16_t *limit_out, uint16_t *mate_limit_out) {
-    const int rc = fqgpu_chunk_pair_overlap(ctx_, first, mate.ctx_, mate_first, count, &spec, out, FQGPU_OVERLAP_WORDS, limit_out, mate_limit_out, nullptr);
+                   uint64_t *out, uint16_t *limit_out, uint16_t *mate_limit_out, uint16_t *insert_out = nullptr) {
+    const int rc = fqgpu_chunk_pair_overlap(ctx_, first, mate.ctx_, mate_first, count, &spec, out, FQGPU_OVERLAP_WORDS, limit_out, mate_limit_out, insert_out);
     if (rc != FQGPU_OK)
       throw std::runtime_error("pairOverlap: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
+                               fqgpu_strerror(rc));
+  }
+  /** fqgpu_chunk_pair_correct: with pairOverlap's insert sizes of the same records, the mismatched bases inside every overlap
+   *  corrected IN BOTH STAGED CHUNKS -> report[0, FQGPU_CORRECT_REPORT_WORDS).  Every selection, digest or summary taken
+   *  afterwards sees the corrected bytes */
+  void pairCorrect(std::size_t first, DecompressionWorkspace &mate, std::size_t mate_first, std::size_t count, const uint16_t *insert,
+                   const fqgpu_correct &spec, uint64_t *report) {
+    const int rc = fqgpu_chunk_pair_correct(ctx_, first, mate.ctx_, mate_first, count, insert, &spec, report, nullptr, nullptr);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("pairCorrect: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
                                fqgpu_strerror(rc));
   }
 

@@ -845,6 +845,57 @@ int fqgpu_dblock_select_limited(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqg
                                 uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
                                 uint16_t *places_out);
 
+/* ---- Extension (nothing in the reference): OVERLAP CORRECTION -- where the mates of a pair disagree inside their overlap and
+ * one base is confident while the other is poor, the poor one is replaced (fastp's --correction).  THESE ARE THE CALLS THAT
+ * CHANGE A CHUNK: every other call on a staged chunk or a block leaves the chunk as it is; these two patch sequence and quality
+ * bytes of both chunks in HBM.  Digest, summary, probe and every selection taken afterwards see the corrected bytes.  A chunk
+ * staged by fqgpu_encode_begin has finished its encode by then: the streams fqgpu_encode_end delivers describe the UNCORRECTED
+ * chunk, and a block's streams and status likewise describe what its last encode saw.
+ * For a pair with the sequence lines s1[0, L1), s2[0, L2), the quality lines q1, q2 and an insert size I -- insert_out's
+ * meaning: I = d + L2, or 0 for "no hit" --, comp mapping A<->T, C<->G and N to N.  Integer arithmetic throughout:
+ *   I == 0       the pair is untouched and none of its four lines is looked at
+ *   I != 0       L1 <= 512, L2 <= 512 and 1 <= I <= L1 + L2 - 1 are required, else FQGPU_E_ARG: the inserts are the caller's
+ *                data and not trusted.  d = I - L2, lo = max(0, d), hi = min(L1, I): the overlap, hi - lo >= 1.  Place i in
+ *                [lo, hi) of mate 1 stands beside place j = I - 1 - i of mate 2, which lies in [0, L2)
+ *   a place      b1 = s1[i], b2 = s2[j], p1 = q1[i] - 33, p2 = q2[j] - 33.  It DISAGREES iff b1 == 'N' or b2 == 'N' or
+ *                b1 != comp(b2): the overlap rule's mismatch.  Mate 1 wins iff it disagrees, b1 != 'N', p1 >= good_q and
+ *                p2 <= bad_q: s2[j] := comp(b1), q2[j] := q1[i].  Mate 2 wins iff it disagrees, b2 != 'N', p2 >= good_q and
+ *                p1 <= bad_q: s1[i] := comp(b2), q1[i] := q2[j].  Otherwise nothing changes.  bad_q < good_q, so the two
+ *                exclude each other.  A winner is never N; a loser may be: an N beside a confident base becomes that base
+ *   independence every place is decided from the uncorrected bytes of its own four bytes alone, and no byte belongs to two
+ *                places: the result does not depend on how the work is split, and a second call with the same inserts
+ *                corrects nothing
+ * Only the overlap's bytes of the four lines are read and judged: a sequence byte outside ACGTN or a quality byte outside
+ * 33 .. 96 there is FQGPU_E_ARG, and so is a record with I != 0 that has length 0 or lies outside its chunk.
+ *   report  FQGPU_CORRECT_REPORT_WORDS uint64_t: 0 n_pairs | 1 pairs_with_insert (I != 0) | 2 pairs_corrected (at least one
+ *           base changed) | 3 bases_corrected_a (mate 2 won, mate 1 changed) | 4 bases_corrected_b (mate 1 won, mate 2 changed) |
+ *           5 n_resolved (corrected places whose old base was N, either mate) | 6 mismatches_seen (disagreeing places before
+ *           the correction) | 7 overlap_bases (the sum of hi - lo).  Reports add word by word.  With the inserts of
+ *           fqgpu_*_pair_overlap over the same records, words 1, 6 and 7 equal that summary's words 1, 6 and 7
+ *   insert_in    count uint16_t, as insert_out
+ *   fixed_a_out, fixed_b_out   each NULL, or `count` uint16_t: the places changed in mate 1 and in mate 2 of pair i
+ *   fqgpu_correct_check       host only: good_q in 1 .. 63, bad_q in 0 .. 62 and below good_q, reserved zero: FQGPU_OK, else
+ *                             FQGPU_E_ARG
+ *   fqgpu_chunk_pair_correct  shaped and validated like fqgpu_chunk_pair_overlap -- valid in the same states, both handles of
+ *                             one device, every stream of both waited for, then the kernels on ctx_a's stream, waited for --
+ *                             but ctx_a == ctx_b is refused: a record would be patched as both mate 1 and mate 2
+ *   fqgpu_dblock_pair_correct as fqgpu_dblock_pair_overlap, its waits for the blocks' owners included; ba == bb is refused
+ * A spec its check refuses, count == 0, a range outside either chunk, a NULL where data is expected: FQGPU_E_ARG.  EVERY
+ * FQGPU_E_ARG LEAVES BOTH CHUNKS EXACTLY AS THEY WERE and zeroes the report and the two arrays: the call judges and counts
+ * first and stores only when nothing was refused.  Without a GPU the two device calls return FQGPU_E_NO_DEVICE before any
+ * argument is looked at; the check works. */
+#define FQGPU_CORRECT_REPORT_WORDS 8
+typedef struct {
+  uint32_t good_q, bad_q;  /* 1 .. 63 | 0 .. 62, bad_q < good_q */
+  uint32_t reserved[6];    /* zero */
+} fqgpu_correct;
+int fqgpu_correct_check(const fqgpu_correct *c);
+int fqgpu_chunk_pair_correct(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const uint16_t *insert_in,
+                             const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out, uint16_t *fixed_b_out);
+int fqgpu_dblock_pair_correct(fqgpu_ctx *ctx, fqgpu_dblock *ba, size_t first_a, fqgpu_dblock *bb, size_t first_b, size_t count,
+                              const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out,
+                              uint16_t *fixed_b_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -73,7 +73,14 @@
 //               bytes whatever -t, -R and .fqx; either turns the analysis on, the other three (defaults 30, 5, 20) set its spec.
 //               With the report alone both output files are what they are without it.  Any of the five without --mate, the
 //               last three without one of the first two, and a spec fqgpu_overlap_check refuses are usage errors.  A failed run
-//               leaves neither output nor a .part file)
+//               leaves neither output nor a .part file.
+//               [--overlap-correct] [--correct-q GOOD:BAD]: OVERLAP CORRECTION (include/fqgpu.h, fastp's --correction) -- where
+//               the mates disagree inside their overlap and one base has a Phred of GOOD or more while the other has BAD or
+//               less (default 30:14), the poor base and its quality are replaced by the confident one's, on the device, behind
+//               the overlap's search and in front of every step that judges either mate.  An overlap option in its own
+//               right: it turns the analysis on, alone or beside any other option of d --mate, and the three spec options
+//               may be given with it alone.  --overlap-correct without --mate, --correct-q without --overlap-correct and a
+//               pair fqgpu_correct_check refuses (GOOD 1 .. 63, BAD below GOOD) are usage errors)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -123,7 +130,8 @@
 // (per decode) its chunk sums; with a selection option "mate1" and "mate2" replace "filter" and "trim": the keys of "trim", the
 // adapter, poly and window keys always there, and "dropped_unmarked", the reads that passed and whose mate did not.  With
 // an overlap option "overlap": {"pairs_overlapped", "pairs_read_through", "bases_behind_1", "bases_behind_2",
-// "pairs_not_analysed"}; with --overlap-trim "mate1" / "mate2" are there and end in "reads_cut_limit", "bases_cut_limit".
+// "pairs_not_analysed"}; with --overlap-trim "mate1" / "mate2" are there and end in "reads_cut_limit", "bases_cut_limit"; with
+// --overlap-correct, and only then, "overlap" ends in "pairs_corrected", "bases_corrected_1", "bases_corrected_2", "n_resolved".
 // Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
@@ -145,7 +153,7 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q] [adapter options] [trim options] [filter options]\n"
                          "                  (the argument behind --poly-g / --poly-x is taken as N unless it begins with '-')\n"
-                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [--overlap-trim] [--overlap-report file.tsv] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
+                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [--overlap-trim] [--overlap-report file.tsv] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT] [--overlap-correct] [--correct-q GOOD:BAD] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
                          "                  (paired: a pair is kept only if both mates pass; the read ids of every pair are compared)\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
@@ -171,6 +179,8 @@ int main(int argc, char **argv) {
   fqgpu_overlap overlap = {30, 5, 20, {0, 0, 0, 0, 0}};  // --overlap-min, --overlap-mism, --overlap-err
   bool overlap_opt = false, overlap_trim = false;       // one of the five options; --overlap-trim
   std::string overlap_path;                             // --overlap-report
+  fqgpu_correct correct = {30, 14, {0, 0, 0, 0, 0, 0}};  // --correct-q
+  bool overlap_correct = false, correct_opt = false;    // --overlap-correct; --correct-q
   std::string mate_in, mate_out;
   std::string adapters_list;
   bool adapters_opt = false;
@@ -241,6 +251,16 @@ int main(int argc, char **argv) {
       mate = true;
     } else if (a == "--overlap-trim") {
       overlap_trim = overlap_opt = true;
+    } else if (a == "--overlap-correct") {
+      overlap_correct = overlap_opt = true;
+    } else if (a == "--correct-q") {
+      const std::string v = val();
+      const std::size_t colon = v.find(':');
+      if (colon == std::string::npos || !u32(v.substr(0, colon), correct.good_q) || !u32(v.substr(colon + 1), correct.bad_q)) {
+        std::fprintf(stderr, "--correct-q %s: expected GOOD:BAD (two Phred values)\n", v.c_str());
+        return 2;
+      }
+      correct_opt = true;
     } else if (a == "--overlap-report") {
       overlap_path = val();
       overlap_opt = true;
@@ -317,16 +337,24 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--mate goes with a plain d alone: not with c, x, t, s, --records, --fasta, --index or --index-stride\n");
     return 2;
   }
-  if (overlap_opt && !mate) {
-    std::fprintf(stderr, "--overlap-trim, --overlap-report, --overlap-min, --overlap-mism and --overlap-err analyse the two mates of a pair: they need --mate <in2.fqc> <out2.fastq>\n");
+  if (correct_opt && !overlap_correct) {
+    std::fprintf(stderr, "--correct-q sets the two Phred values of --overlap-correct: it needs that option\n");
     return 2;
   }
-  if (overlap_opt && !overlap_trim && overlap_path.empty()) {
-    std::fprintf(stderr, "--overlap-min, --overlap-mism and --overlap-err need --overlap-trim or --overlap-report <file.tsv>\n");
+  if (overlap_opt && !mate) {
+    std::fprintf(stderr, "--overlap-trim, --overlap-report, --overlap-correct, --overlap-min, --overlap-mism and --overlap-err analyse the two mates of a pair: they need --mate <in2.fqc> <out2.fastq>\n");
+    return 2;
+  }
+  if (overlap_opt && !overlap_trim && !overlap_correct && overlap_path.empty()) {
+    std::fprintf(stderr, "--overlap-min, --overlap-mism and --overlap-err need --overlap-trim, --overlap-correct or --overlap-report <file.tsv>\n");
     return 2;
   }
   if (overlap_opt && fqgpu_overlap_check(&overlap) != FQGPU_OK) {
     std::fprintf(stderr, "mate overlap: expected --overlap-min 1 .. 512, --overlap-mism 0 .. 65535, --overlap-err 0 .. 50\n");
+    return 2;
+  }
+  if (overlap_correct && fqgpu_correct_check(&correct) != FQGPU_OK) {
+    std::fprintf(stderr, "overlap correction: expected --correct-q GOOD:BAD with GOOD 1 .. 63 and BAD below GOOD\n");
     return 2;
   }
   if (clipped2 && !mate) {
@@ -472,7 +500,7 @@ int main(int argc, char **argv) {
       set.decode_index = false;
     }
     const Selection sel{clipped ? &adapter : nullptr, tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr,
-                        overlap_opt ? &overlap : nullptr, overlap_trim};
+                        overlap_opt ? &overlap : nullptr, overlap_trim, overlap_correct ? &correct : nullptr};
     PairedReport paired;
     if (mate) paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped2 ? &adapter2 : nullptr, sel, set);
     const FarmReport r = mate ? paired.mate1
@@ -483,7 +511,7 @@ int main(int argc, char **argv) {
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
-    if (!overlap_path.empty()) writeOverlapReport(overlap_path, paired.overlap, overlap);
+    if (!overlap_path.empty()) writeOverlapReport(overlap_path, paired.overlap, overlap, sel.correct, paired.correct);
     if (!stats_path.empty() && adapters_opt) writeStatsReport(stats_path, r.stats, r.probes, probes, probe_names);
     else if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
@@ -517,7 +545,12 @@ int main(int argc, char **argv) {
       if (overlap_opt) {
         const auto w = [&](unsigned i) { return (unsigned long long)paired.overlap[i]; };
         std::printf(", \"overlap\": {\"pairs_overlapped\": %llu, \"pairs_read_through\": %llu, \"bases_behind_1\": %llu, \"bases_behind_2\": %llu, "
-                    "\"pairs_not_analysed\": %llu}", w(1), w(2), w(3), w(4), w(5));
+                    "\"pairs_not_analysed\": %llu", w(1), w(2), w(3), w(4), w(5));
+        if (overlap_correct) {
+          const auto c = [&](unsigned i) { return (unsigned long long)paired.correct[i]; };
+          std::printf(", \"pairs_corrected\": %llu, \"bases_corrected_1\": %llu, \"bases_corrected_2\": %llu, \"n_resolved\": %llu", c(2), c(3), c(4), c(5));
+        }
+        std::printf("}");
       }
       for (int m = 0; m < 2 && (filtered || trimmed || clipped || clipped2 || tailed || overlap_trim); ++m) {
         const std::vector<uint64_t> &t = m ? paired.mate2.trim : paired.mate1.trim;
