@@ -398,14 +398,26 @@ k_tile_hist(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs,
 //             bases in front of it, nearest in bits 7:6: src/fse_sequence.h:22-24) | symbol << 8 in ONE bit-field
 //             extract.  Bases in front of the read: the same string with 0xD7 (virtual T,C,C,T) shifted in.
 //             A byte that is no base at all is found by mapping the codes back to letters (v_perm) and comparing.
-//   quality   33 comes off all eight bytes at once; calcContext (src/fse_quality.h:40-44) per symbol from byte fields.
+//   quality   33 comes off all eight bytes at once; calcContext (src/fse_quality.h:40-44) for two symbols per instruction
+//             on 16-bit fields; the alphabet test is one byte-parallel test of the four symbol bytes.
 // The last quad of a read may be short (L mod 4), and a quad at the edge of the wave's range belongs to two waves:
-// every symbol is masked by its encode index.  Full quads leave their keys with one 8-byte (+ one 4-byte) store.
+// every symbol is masked by its encode index (the 4-bit mask `valid`).  There is ONE path for full and short quads: the
+// histogram adds carry the symbol's valid bit as their increment, the n valid symbols go out as 4, 2 + 1, 2 or 1 keys per
+// stream, the N's of a quad are one atomic add.  Only a quad cut by the START of the wave's range (at most one per wave)
+// stores symbol by symbol, behind a branch nobody else takes.  A lane finds its record without walking over the records:
+// a bit per quad in LDS marks the last quad of every record, and the record is a count of bits below the lane (v_mbcnt).
+// The kernel is held by latency and instruction issue together, not by HBM bytes (0.70 GB per 256 MiB block in about
+// 190 us): DESIGN.md section 8 has the counters.
 struct RecCache4 {
   uint32_t start[65];   // rec_start of records r0 .. r0 + 64
   uint32_t qpre[65];    // quads of this wave's range in the cached records before record k
   uint32_t jlo[64];     // first quad of record k inside the wave's range
-  fqgpu_rec rec[64];
+  uint32_t seq_off[64], qual_off[64], len[64];  // the records, field by field: every access is lane-indexed word k
+  // bit g: quad g of the window is the last one of its record and another quad follows it (every read has three bases or more, so every record that
+  // meets the wave's range has a quad).  The range has at most TS_TILE / 4 symbols: TS_TILE / 16 quads, one more per
+  // record of the window and one for a first record cut by the range; a chunk of 64 quads reads two whole words.
+  static constexpr unsigned QEND_WORDS = (TS_TILE / 16 + 64 + 2 + 63) / 64 * 2;
+  uint32_t qend[QEND_WORDS];
 };
 struct __attribute__((packed)) FqU64x1 { unsigned long long a; };  // eight bytes at any address
 
@@ -433,7 +445,7 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
   const unsigned wave = threadIdx.x >> 6, lane = fq_lane();
   const unsigned per = (((e1 - e0) + blockDim.x - 1u) / blockDim.x) * 64u;
   const unsigned wb = min(e0 + wave * per, e1), we = min(wb + per, e1);
-  bool bad_s = false, bad_q = false;
+  unsigned bad_s = 0, bad_q = 0;  // (accumulated in vector registers: a flag in a lane mask costs four scalar instructions per quad)
   if (wb < we) {
     RecCache4 &rc = rcache[wave];
     unsigned r0 = fq_locate(rec_start, 0, R - 1, wb);
@@ -443,7 +455,10 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
       fq_lds_wave_sync();  // nobody still reads the old window
       rc.start[lane] = r0 + lane <= R ? rec_start[r0 + lane] : 0xFFFFFFFFu;
       if (lane == 0) rc.start[64] = r0 + 64 <= R ? rec_start[r0 + 64] : 0xFFFFFFFFu;
-      if (r0 + lane < R) rc.rec[lane] = recs[r0 + lane];
+      if (r0 + lane < R) {
+        const fqgpu_rec x = recs[r0 + lane];
+        rc.seq_off[lane] = x.seq_off; rc.qual_off[lane] = x.qual_off; rc.len[lane] = x.len;
+      }
       fq_lds_wave_sync();
       unsigned nq = 0, jl = 0;
       {
@@ -457,48 +472,45 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
       rc.qpre[lane] = qincl - nq;
       rc.jlo[lane] = jl;
       if (lane == 63) rc.qpre[64] = qincl;
+      for (unsigned i = lane; i < RecCache4::QEND_WORDS; i += 64u) rc.qend[i] = 0u;
       fq_lds_wave_sync();
       const unsigned Q = fq_uniform(rc.qpre[64]);
+      if (nq && qincl != Q) atomicOr(&rc.qend[(qincl - 1u) >> 5], 1u << ((qincl - 1u) & 31u));
+      fq_lds_wave_sync();
       const unsigned covered = fq_uniform(rc.start[64]);
       const unsigned nch = (Q + 63u) >> 6;
 
       // ---- software pipeline over the chunks of 64 quads
       unsigned long long ws[K1Q_DEPTH], wq[K1Q_DEPTH];  // windows, already shifted: byte k = position p_hi - 7 + k
       unsigned ef[K1Q_DEPTH], vm[K1Q_DEPTH], mm[K1Q_DEPTH], rr[K1Q_DEPTH];  // first encode index, valid mask (4 bits; bit 4: the quad opens its record), missing bytes, record
-      unsigned kc = 0;  // (uniform) cached record holding the first quad of the next chunk to be fetched
+      unsigned kc = 0;  // (the same in every lane) cached record holding the first quad of the next chunk to be fetched
       auto fetch = [&](int slot, unsigned c) {
-        const unsigned g0 = c << 6, g = g0 + lane;
-        const bool on = g < Q;
-        unsigned k = 0, kk = kc, qn;
-        for (;;) {
-          const unsigned qs = fq_uniform(rc.qpre[kk]);
-          qn = fq_uniform(rc.qpre[kk + 1]);
-          if (on && g >= qs && g < qn) k = kk;
-          if (qn >= g0 + 64u || kk == 63u) break;
-          kk++;
-        }
-        kc = qn > g0 + 64u ? kk : min(kk + 1u, 63u);
-        const fqgpu_rec rec = rc.rec[k];
-        const unsigned rs = rc.start[k], j = rc.jlo[k] + (g - rc.qpre[k]);
-        const unsigned L = on ? rec.len : 4u, j4 = on ? 4u * j : 0u;
-        const unsigned p_hi = L - 1u - j4;            // the quad's first symbol in encode order
+        // lanes behind the window's last quad take that quad again, with no valid symbol: nothing else depends on `on`
+        const bool on = (c << 6) + lane < Q;
+        const unsigned g = min((c << 6) + lane, Q - 1u);
+        // the lane's record: kc + the records that end in this chunk in front of its quad (no walk over the records)
+        const unsigned ends_lo = rc.qend[2u * c], ends_hi = rc.qend[2u * c + 1u];
+        const unsigned k = kc + __builtin_amdgcn_mbcnt_hi(ends_hi, __builtin_amdgcn_mbcnt_lo(ends_lo, 0u));
+        kc += (unsigned)__popc(ends_lo) + (unsigned)__popc(ends_hi);
+        const unsigned rs = rc.start[k], j4 = 4u * (rc.jlo[k] + (g - rc.qpre[k]));
+        const unsigned p_hi = rc.len[k] - 1u - j4;      // the quad's first symbol in encode order
         const unsigned m = p_hi < 7u ? 7u - p_hi : 0u;  // window bytes in front of the read
         const unsigned first = p_hi < 7u ? 0u : p_hi - 7u;
-        const unsigned long long a = reinterpret_cast<const FqU64x1 *>(raw + (on ? rec.seq_off : 0u) + first)->a;
-        const unsigned long long b = reinterpret_cast<const FqU64x1 *>(raw + (on ? rec.qual_off : 0u) + first)->a;
+        const unsigned long long a = reinterpret_cast<const FqU64x1 *>(raw + rc.seq_off[k] + first)->a;
+        const unsigned long long b = reinterpret_cast<const FqU64x1 *>(raw + rc.qual_off[k] + first)->a;
         const unsigned e_first = rs + j4;
-        unsigned valid = 0;
-#pragma unroll
-        for (unsigned i = 0; i < 4; i++) {
-          const unsigned e = e_first + i;
-          valid |= (on && i <= p_hi && e >= wb && e < we) ? 1u << i : 0u;
-        }
+        // valid symbols: i <= p_hi (the read's last quad may be short) and wb <= e_first + i < we.  A quad handed out here
+        // has at least one, so both differences below are what they look like.
+        const unsigned v_lo = wb > e_first ? wb - e_first : 0u, v_hi = min(min(p_hi + 1u, 4u), we - e_first);
+        unsigned valid = on ? ((1u << v_hi) - 1u) & ~((1u << v_lo) - 1u) : 0u;
         valid |= (j4 == 0u && (valid & 1u)) ? 16u : 0u;  // the record's first symbol in encode order is this quad's first
         ws[slot] = a; wq[slot] = b; ef[slot] = e_first; vm[slot] = valid; mm[slot] = m; rr[slot] = r0 + k;
       };
       auto consume = [&](int slot) {
         const unsigned opens = vm[slot] >> 4, valid = vm[slot] & 15u, sh = 8u * mm[slot], e_first = ef[slot];
-        if (!valid) return;
+        if (!valid) return;  // (lanes behind the window's last quad: one region for the whole quad, none per symbol)
+        // valid bit i (symbol i = window byte 7 - i) as bit 7 of byte 3 - i: masks the byte-parallel tests below
+        const unsigned vb = (__umul24(valid, 0x402010u) | (valid << 31)) & 0x80808080u;  // (a 24-bit multiply runs at full rate)
         // -------- sequence
         const unsigned long long w = ws[slot] << sh;   // byte k = position p_hi - 7 + k (0 in front of the read)
         const unsigned lo = (unsigned)w, hi = (unsigned)(w >> 32);
@@ -506,61 +518,81 @@ k_tile_hist2(const uint8_t *__restrict__ raw, const fqgpu_rec *__restrict__ recs
         auto pack4 = [](unsigned c) { c |= c >> 6; c |= c >> 12; return c & 0xFFu; };  // four byte codes -> 8 bits
         unsigned H = pack4(clo) | (pack4(chi) << 8);
         H |= 0xD700u >> (16u - 2u * mm[slot]);          // virtual T,C,C,T in front of the read (mm = 0: nothing)
-        // bytes that are not A C G T: N (counted, coded as A) or no base at all
-        const unsigned diff = (__builtin_amdgcn_perm(0u, 0x54474341u, chi) ^ hi);
         unsigned k16[4];
 #pragma unroll
         for (unsigned i = 0; i < 4; i++) k16[i] = (H >> (2u * (3u - i))) & 0x3FFu;
-        if (diff) {
-#pragma unroll
-          for (unsigned i = 0; i < 4; i++) {
-            const unsigned d = (diff >> (8u * (3u - i))) & 0xFFu;
-            if (d && ((valid >> i) & 1u)) {
-              if (((hi >> (8u * (3u - i))) & 0xFFu) == 'N') atomicAdd(&n_cnt32[rr[slot]], 1u);  // (rare) replaceAndEncodeNs's n_count, src/fse_sequence.cpp:35-51
-              else bad_s = true;
-            }
-          }
+        // bytes that are not A C G T: N (counted, coded as A) or no base at all.  Bit 7 of a byte of nz80(x) says that
+        // the byte of x is not zero; no carry leaves a byte.
+        auto nz80 = [](unsigned x) { return (((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u; };
+        const unsigned diff = (__builtin_amdgcn_perm(0u, 0x54474341u, chi) ^ hi);
+        if (diff) {  // (rare)
+          const unsigned not_n = nz80(hi ^ 0x4E4E4E4Eu);
+          const unsigned n_ns = (unsigned)__popc(vb & ~not_n);
+          bad_s |= nz80(diff) & not_n & vb;
+          if (n_ns) atomicAdd(&n_cnt32[rr[slot]], n_ns);  // replaceAndEncodeNs's n_count, src/fse_sequence.cpp:35-51: one add per quad
         }
-        // -------- quality
+        // -------- quality: calcContext (src/fse_quality.h:40-44) of two symbols per instruction, a 16-bit field each.
+        // Every field holds a byte, so (max << 6) + q[-1] stays below 2^16 and plain 32-bit arithmetic serves both halves.
         const unsigned long long q33 = (wq[slot] - 0x2121212121212121ull) << sh;  // (a byte below 33 borrows from its UPPER neighbour only: a later position, and then the block is refused anyway)
         const unsigned ql = (unsigned)q33, qh = (unsigned)(q33 >> 32);
-        // byte fields 1 .. 7: b[t] = quality at position p_hi - 7 + t
-        const unsigned b1 = (ql >> 8) & 0xFFu, b2 = (ql >> 16) & 0xFFu, b3 = ql >> 24, b4 = qh & 0xFFu, b5 = (qh >> 8) & 0xFFu,
-                       b6 = (qh >> 16) & 0xFFu, b7 = qh >> 24;
-        const unsigned qs_[4] = {b7, b6, b5, b4};   // symbol of quad entry i
-        const unsigned qa[4] = {b6, b5, b4, b3};    // position - 1
-        const unsigned qb[4] = {b5, b4, b3, b2};    // position - 2
-        const unsigned qc[4] = {b4, b3, b2, b1};    // position - 3
-        unsigned cq[4];
-#pragma unroll
-        for (unsigned i = 0; i < 4; i++) {
-          cq[i] = ((((qb[i] > qc[i] ? qb[i] : qc[i]) << 6) + qa[i]) & 0xFFFu) | ((qb[i] == qc[i]) ? 0x1000u : 0u);
-          bad_q |= ((valid >> i) & 1u) && qs_[i] >= (unsigned)QualModel::A;
-        }
+        // byte t of q33 = quality at position p_hi - 7 + t; symbol i is byte 7 - i.  f(x, y): byte x | byte y << 16
+        const unsigned f65 = __builtin_amdgcn_perm(qh, ql, 0x0C050C06u), f54 = __builtin_amdgcn_perm(qh, ql, 0x0C040C05u),
+                       f43 = __builtin_amdgcn_perm(qh, ql, 0x0C030C04u), f32 = __builtin_amdgcn_perm(qh, ql, 0x0C020C03u),
+                       f21 = __builtin_amdgcn_perm(qh, ql, 0x0C010C02u);
+        typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+        auto ctx2 = [](unsigned a, unsigned b, unsigned c) {  // a, b, c: q[-1], q[-2], q[-3] of two symbols
+          const us2 m = __builtin_elementwise_max(__builtin_bit_cast(us2, b), __builtin_bit_cast(us2, c));
+          const unsigned v = (__builtin_bit_cast(unsigned, m) << 6) + a;
+          const unsigned eq = 0x10001000u - (b ^ c);   // a field of b ^ c is below 256: bit 12 stays set only where it is 0
+          return (v & 0x0FFF0FFFu) | (eq & ~0x0FFF0FFFu);  // (one bit-field insert; bits 15:13 of a field of eq are 0)
+        };
+        const unsigned cq01 = ctx2(f65, f54, f43), cq23 = ctx2(f43, f32, f21);  // cq[0] | cq[1] << 16, cq[2] | cq[3] << 16
+        // a valid symbol at or above the alphabet: bit 7 of (byte & 0x7F) + (128 - A) is set from A up, and bytes from 128 carry it themselves
+        static_assert(QualModel::A <= 128, "the byte-parallel range test");
+        bad_q |= (((qh & 0x7F7F7F7Fu) + (128u - (unsigned)QualModel::A) * 0x01010101u) | qh) & vb;
         // -------- keys out, histograms.  The keys are the CONTEXTS alone (one byte / two bytes per symbol): the symbol at
         // encode index e is part of the context at e - 1 -- the base in bits 7:6, the quality in bits 5:0 (the position in front
         // of p + 1 is p) -- and K3 takes it from there; only a record's first symbol in encode order has no such neighbour
         // and is left in first_seq / first_qual [record].  240 MB of symbols and key bytes less written here and read by K3.
-        if (opens) { first_seq[rr[slot]] = (uint8_t)(k16[0] >> 8); first_qual[rr[slot]] = (uint8_t)(qs_[0] & 63u); }
-        if (valid == 0xFu) {
-          struct __attribute__((packed)) P8 { uint32_t a, b; };
-          struct __attribute__((packed)) P4 { uint32_t a; };
-          *reinterpret_cast<P4 *>(ckey_seq + e_first) = P4{(k16[0] & 0xFFu) | ((k16[1] & 0xFFu) << 8) | ((k16[2] & 0xFFu) << 16) | (k16[3] << 24)};
-          *reinterpret_cast<P8 *>(ckey_qual + e_first) = P8{cq[0] | (cq[1] << 16), cq[2] | (cq[3] << 16)};
-#pragma unroll
-          for (unsigned i = 0; i < 4; i++) {
-            atomicAdd(&hist_s[k16[i] & 0xFFu], 1u);
-            atomicAdd(&hist_q[cq[i] >> 1], 1u << (16u * (cq[i] & 1u)));
-          }
-        } else {
+        if (opens) { first_seq[rr[slot]] = (uint8_t)(k16[0] >> 8); first_qual[rr[slot]] = (uint8_t)((qh >> 24) & 63u); }
+        // the four key bytes: byte i = (H >> (6 - 2 i)) & 0xFF
+        const unsigned kb = (((H >> 6) | (H << 14)) & 0x00FF00FFu) | (((H << 4) | (H << 24)) & ~0x00FF00FFu);
+        const unsigned cq[4] = {cq01 & 0xFFFFu, cq01 >> 16, cq23 & 0xFFFFu, cq23 >> 16};
+        // One path for full quads and for a read's short last quad (valid = 1, 3, 7: one quad in 38 of 150-base reads, so
+        // four chunks in five hold one): the n valid symbols go out as 4, 2 + 1, 2 or 1 keys, never a byte past the last
+        // valid one (those are the next record's first keys), and the histogram adds carry the valid bit as increment.
+        // Only a quad cut by the START of the wave's range (valid is no low run of bits) stores symbol by symbol.
+        struct __attribute__((packed)) P8 { uint32_t a, b; };
+        struct __attribute__((packed)) P4 { uint32_t a; };
+        struct __attribute__((packed)) P2 { uint16_t a; };
+        const bool cut = (valid & (valid + 1u)) != 0u;
+        const unsigned n = cut ? 0u : (unsigned)__popc(valid);
+        if (n & 4u) {
+          *reinterpret_cast<P4 *>(ckey_seq + e_first) = P4{kb};
+          *reinterpret_cast<P8 *>(ckey_qual + e_first) = P8{cq01, cq23};
+        }
+        if (n & 2u) {
+          *reinterpret_cast<P2 *>(ckey_seq + e_first) = P2{(uint16_t)kb};
+          *reinterpret_cast<P4 *>(ckey_qual + e_first) = P4{cq01};
+        }
+        if (n & 1u) {  // symbol 0 or symbol 2
+          const unsigned o = n & 2u;
+          ckey_seq[e_first + o] = (uint8_t)(o ? kb >> 16 : kb);
+          ckey_qual[e_first + o] = (uint16_t)(o ? cq23 : cq01);
+        }
+        if (cut) {  // (at most one quad per wave)
 #pragma unroll
           for (unsigned i = 0; i < 4; i++)
             if ((valid >> i) & 1u) {
               ckey_seq[e_first + i] = (uint8_t)k16[i];
               ckey_qual[e_first + i] = (uint16_t)cq[i];
-              atomicAdd(&hist_s[k16[i] & 0xFFu], 1u);
-              atomicAdd(&hist_q[cq[i] >> 1], 1u << (16u * (cq[i] & 1u)));
             }
+        }
+#pragma unroll
+        for (unsigned i = 0; i < 4; i++) {
+          const unsigned one = (valid >> i) & 1u;
+          atomicAdd(&hist_s[k16[i] & 0xFFu], one);
+          atomicAdd(&hist_q[cq[i] >> 1], one << (16u * (cq[i] & 1u)));
         }
       };
 #pragma unroll
