@@ -357,30 +357,32 @@ def filter_check(flt):
     return lib().fqgpu_filter_check(_p(flt))
 
 
-def _select_call(fn, front, specs, n_recs, more=(), out_cap=None, want_keep=True, query=False, report_words=None):
-    """A device filter or trim call -> dict(rc, out, out_len, report, keep).  specs: the call's trim and filter words in the order
-    of its arguments (None: NULL); more: the outputs it takes behind keep_out.  out_cap None: the size is asked for first
-    (out=NULL), then the call is made with a buffer of that size -- query: the size is asked for and that is all; a number: ONE
-    call with a buffer of that many bytes.  report_words: the words of the call's report when they are not the filter's."""
-    report = np.zeros(FILTER_REPORT_WORDS if report_words is None else report_words, dtype=np.uint64)
+def _select_call(fn, front, specs, n_recs, extra=(), more=(), want_win=True, want_places=True, out_cap=None, want_keep=True, query=False,
+                 report_words=FILTER_REPORT_WORDS):
+    """A device selection call (filter, trim, clip, tailtrim, select_marked, select_limited) -> dict(rc, out, out_len, report,
+    keep) plus the arrays named in `more`.  specs: the call's adapter, tail, trim and filter words in the order of its arguments
+    (None: NULL); extra: the C arguments it takes between the specs and `out` (a range's first, end, mark, limits); more: the
+    outputs it takes behind keep_out, of "win" -- the records' windows, uint32[n_recs], start | n << 16 -- and "places" --
+    uint16[n_recs, 4], a0, a1, e, e2 of every record --, each allocated unless want_win / want_places is false (then NULL, and
+    None in the dict).  out_cap None: the size is asked for first (out=NULL), then the call is made with a buffer of that size --
+    query: the size is asked for and that is all; a number: ONE call with a buffer of that many bytes.  report_words: the words
+    of the call's report."""
+    report = np.zeros(report_words, dtype=np.uint64)
     keep = np.zeros((n_recs + 7) // 8, dtype=np.uint8) if want_keep else None
+    arrays = dict(win=np.zeros(n_recs, dtype=np.uint32) if want_win else None, places=np.zeros((n_recs, 4), dtype=np.uint16) if want_places else None)
+    arrays = {name: arrays[name] for name in more}
     n = C.c_size_t(0)
     words = [None if s is None else np.ascontiguousarray(s, dtype=np.uint32) for s in specs]
-    specs = [_p(w) for w in words]
-    tail = (C.byref(n), _p(report), _p(keep)) + tuple(_p(m) for m in more)
+    head = (*front, *[_p(w) for w in words], *extra)
+    tail = (C.byref(n), _p(report), _p(keep), *[_p(a) for a in arrays.values()])
     if out_cap is None:
-        rc = fn(*front, *specs, None, 0, *tail)
+        rc = fn(*head, None, 0, *tail)
         if rc != 0 or query:
-            return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep)
+            return dict(rc=rc, out=None, out_len=n.value, report=report, keep=keep, **arrays)
         out_cap = n.value
     out = np.zeros(max(out_cap, 1), dtype=np.uint8)
-    rc = fn(*front, *specs, _p(out), out_cap, *tail)
-    return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep)
-
-
-def _filter_call(fn, front, flt, n_recs, **kw):
-    """A device filter call -> dict(rc, out, out_len, report, keep); out_cap, want_keep, query: see _select_call"""
-    return _select_call(fn, front, (flt,), n_recs, **kw)
+    rc = fn(*head, _p(out), out_cap, *tail)
+    return dict(rc=rc, out=out[:n.value] if rc == 0 else out, out_len=n.value, report=report, keep=keep, **arrays)
 
 
 TRIM_REPORT_WORDS = 16
@@ -395,13 +397,6 @@ def read_trim(cut_front=0, cut_tail=0, q_front=0, q_tail=0, crop=FILTER_NONE, re
 def trim_check(trim):
     """fqgpu_trim_check -> rc (host only)"""
     return lib().fqgpu_trim_check(_p(trim))
-
-
-def _trim_call(fn, front, trim, flt, n_recs, want_win=True, **kw):
-    """A device trim call -> dict(rc, out, out_len, report, keep, win): _filter_call's dict plus the records' windows
-    (start | n << 16).  flt None: a NULL filter.  out_cap, want_keep, query: see _select_call"""
-    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
-    return dict(_select_call(fn, front, (trim, flt), n_recs, more=(win,), **kw), win=win)
 
 
 ADAPTER_MAX = 64
@@ -422,12 +417,6 @@ def read_adapter(seq, min_overlap=5, max_err_pct=10, reserved=0, length=None):
 def adapter_check(adapter):
     """fqgpu_adapter_check -> rc (host only)"""
     return lib().fqgpu_adapter_check(_p(adapter))
-
-
-def _clip_call(fn, front, adapter, trim, flt, n_recs, want_win=True, **kw):
-    """A device clip call -> dict(rc, out, out_len, report, keep, win) as _trim_call; adapter, trim, flt None: NULL"""
-    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
-    return dict(_select_call(fn, front, (adapter, trim, flt), n_recs, more=(win,), **kw), win=win)
 
 
 TAIL_REPORT_WORDS = 24
@@ -451,47 +440,21 @@ def tail_check(tail):
     return lib().fqgpu_tail_check(_p(tail))
 
 
-def _tail_call(fn, front, adapter, tail, trim, flt, n_recs, want_win=True, want_places=True, **kw):
-    """A device tail call -> dict(rc, out, out_len, report, keep, win, places) as _clip_call, the report of TAIL_REPORT_WORDS;
-    places: uint16[n_recs, 4], a0, a1, e, e2 of every record; adapter, tail, trim, flt None: NULL"""
-    win = np.zeros(n_recs, dtype=np.uint32) if want_win else None
-    places = np.zeros((n_recs, 4), dtype=np.uint16) if want_places else None
-    return dict(_select_call(fn, front, (adapter, tail, trim, flt), n_recs, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
-                win=win, places=places)
-
-
 MARKED_REPORT_NAMES = TAIL_REPORT_NAMES + ("dropped_unmarked",)
 DROPPED_UNMARKED = 20
 NO_MISMATCH = (1 << 64) - 1
-
-
-def _marked_call(fn, front, adapter, tail, trim, flt, first, end, mark=None, want_win=True, want_places=True, **kw):
-    """A device marked call (fqgpu_*_select_marked) over the records [first, end) -> dict(rc, out, out_len, report, keep, win,
-    places) as _tail_call, everything relative to `first`; mark: None (NULL), or uint8 of (end - first + 7) // 8 bytes in the
-    keep bits' layout; adapter, tail, trim, flt None: NULL"""
-    n = max(end - first, 0)
-    win = np.zeros(n, dtype=np.uint32) if want_win else None
-    places = np.zeros((n, 4), dtype=np.uint16) if want_places else None
-    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.uint8)
-    call = lambda *a: fn(*a[:len(front) + 4], first, end, _p(mark), *a[len(front) + 4:])  # noqa: E731
-    return dict(_select_call(call, front, (adapter, tail, trim, flt), n, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
-                win=win, places=places)
-
-
 LIMITED_REPORT_NAMES = MARKED_REPORT_NAMES + ("reads_cut_limit", "bases_cut_limit")
 READS_CUT_LIMIT, BASES_CUT_LIMIT = 21, 22
 
 
-def _limited_call(fn, front, adapter, tail, trim, flt, first, end, mark=None, limit=None, want_win=True, want_places=True, **kw):
-    """A device limited call (fqgpu_*_select_limited) -> as _marked_call; limit: None (NULL), or uint16 of end - first limits"""
-    n = max(end - first, 0)
-    win = np.zeros(n, dtype=np.uint32) if want_win else None
-    places = np.zeros((n, 4), dtype=np.uint16) if want_places else None
+def _range_call(fn, front, specs, first, end, mark, *limit, **kw):
+    """A device marked or limited call over the records [first, end) -> _select_call's dict with win and places, everything
+    relative to `first`.  mark: None (NULL), or uint8 of (end - first + 7) // 8 bytes in the keep bits' layout; limit: the
+    limited calls' one more argument -- None (NULL), or uint16 of end - first limits"""
     mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.uint8)
-    limit = None if limit is None else np.ascontiguousarray(limit, dtype=np.uint16)
-    call = lambda *a: fn(*a[:len(front) + 4], first, end, _p(mark), _p(limit), *a[len(front) + 4:])  # noqa: E731
-    return dict(_select_call(call, front, (adapter, tail, trim, flt), n, more=(win, places), report_words=TAIL_REPORT_WORDS, **kw),
-                win=win, places=places)
+    limit = [None if v is None else np.ascontiguousarray(v, dtype=np.uint16) for v in limit]
+    return _select_call(fn, front, specs, max(end - first, 0), extra=(first, end, _p(mark), *[_p(v) for v in limit]), more=("win", "places"),
+                        report_words=TAIL_REPORT_WORDS, **kw)
 
 
 OVERLAP_MAX_LEN, OVERLAP_ROWS, OVERLAP_HEAD_WORDS = 512, 1024, 16
@@ -735,37 +698,38 @@ class DBlock:
 
     def filter(self, flt, **kw):
         """fqgpu_dblock_filter: the reads of the raw block, as it lies on the device, that pass `flt` (read_filter) ->
-        dict(rc, out, out_len, report, keep); see _filter_call"""
-        return _filter_call(lib().fqgpu_dblock_filter, (self.ctx.h, self.h), flt, self.n_recs, **kw)
+        dict(rc, out, out_len, report, keep); see _select_call"""
+        return _select_call(lib().fqgpu_dblock_filter, (self.ctx.h, self.h), (flt,), self.n_recs, **kw)
 
     def trim(self, trim, flt=None, **kw):
         """fqgpu_dblock_trim: the reads of the raw block, as it lies on the device, trimmed by `trim` (read_trim) and then
         judged by `flt` (read_filter; None: every read that is not emptied is kept) -> dict(rc, out, out_len, report, keep,
-        win); see _trim_call"""
-        return _trim_call(lib().fqgpu_dblock_trim, (self.ctx.h, self.h), trim, flt, self.n_recs, **kw)
+        win); see _select_call"""
+        return _select_call(lib().fqgpu_dblock_trim, (self.ctx.h, self.h), (trim, flt), self.n_recs, more=("win",), **kw)
 
     def clip(self, adapter, trim=None, flt=None, **kw):
         """fqgpu_dblock_clip: the reads of the raw block clipped at `adapter` (read_adapter; None: no adapter), trimmed by
         `trim` (None: nothing beyond the clip) and then judged by `flt` -> dict(rc, out, out_len, report, keep, win); see
-        _trim_call"""
-        return _clip_call(lib().fqgpu_dblock_clip, (self.ctx.h, self.h), adapter, trim, flt, self.n_recs, **kw)
+        _select_call"""
+        return _select_call(lib().fqgpu_dblock_clip, (self.ctx.h, self.h), (adapter, trim, flt), self.n_recs, more=("win",), **kw)
 
     def tailtrim(self, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_dblock_tailtrim: the reads of the raw block clipped at `adapter` (None: no adapter), their poly-X tail and the
         sliding-window cut of `tail` (read_tail; None: neither) taken, trimmed by `trim` and then judged by `flt` ->
-        dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
-        return _tail_call(lib().fqgpu_dblock_tailtrim, (self.ctx.h, self.h), adapter, tail, trim, flt, self.n_recs, **kw)
+        dict(rc, out, out_len, report, keep, win, places); see _select_call"""
+        return _select_call(lib().fqgpu_dblock_tailtrim, (self.ctx.h, self.h), (adapter, tail, trim, flt), self.n_recs, more=("win", "places"),
+                            report_words=TAIL_REPORT_WORDS, **kw)
 
     def select_marked(self, first, end, mark=None, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_dblock_select_marked: the records [first, end) of the raw block judged as tailtrim judges them, a record whose
         bit in `mark` is 0 dropped whatever its verdict -> dict(rc, out, out_len, report, keep, win, places), all relative to
-        `first`; see _marked_call"""
-        return _marked_call(lib().fqgpu_dblock_select_marked, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, **kw)
+        `first`; see _range_call"""
+        return _range_call(lib().fqgpu_dblock_select_marked, (self.ctx.h, self.h), (adapter, tail, trim, flt), first, end, mark, **kw)
 
     def select_limited(self, first, end, mark=None, limit=None, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_dblock_select_limited: select_marked with a per-record limit (uint16 of end - first entries; None: NULL) in
         front of its steps -> as select_marked, report words 21 / 22 counted"""
-        return _limited_call(lib().fqgpu_dblock_select_limited, (self.ctx.h, self.h), adapter, tail, trim, flt, first, end, mark, limit, **kw)
+        return _range_call(lib().fqgpu_dblock_select_limited, (self.ctx.h, self.h), (adapter, tail, trim, flt), first, end, mark, limit, **kw)
 
     def pair_correct(self, first, other, other_first, count, insert, spec, **kw):
         """fqgpu_dblock_pair_correct: with the insert sizes `insert` (pair_overlap's) the mismatched bases inside the overlap of
@@ -913,33 +877,34 @@ class Context:
 
     def chunk_filter(self, flt, n_recs, **kw):
         """fqgpu_chunk_filter: the reads of the chunk on the staging block (n_recs records) that pass `flt`, where chunk_stats
-        is valid -> dict(rc, out, out_len, report, keep); see _filter_call"""
-        return _filter_call(lib().fqgpu_chunk_filter, (self.h,), flt, n_recs, **kw)
+        is valid -> dict(rc, out, out_len, report, keep); see _select_call"""
+        return _select_call(lib().fqgpu_chunk_filter, (self.h,), (flt,), n_recs, **kw)
 
     def chunk_trim(self, trim, n_recs, flt=None, **kw):
         """fqgpu_chunk_trim: the reads of the chunk on the staging block (n_recs records) trimmed by `trim` and then judged by
-        `flt`, where chunk_filter is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
-        return _trim_call(lib().fqgpu_chunk_trim, (self.h,), trim, flt, n_recs, **kw)
+        `flt`, where chunk_filter is valid -> dict(rc, out, out_len, report, keep, win); see _select_call"""
+        return _select_call(lib().fqgpu_chunk_trim, (self.h,), (trim, flt), n_recs, more=("win",), **kw)
 
     def chunk_clip(self, adapter, n_recs, trim=None, flt=None, **kw):
         """fqgpu_chunk_clip: the reads of the chunk on the staging block (n_recs records) clipped at `adapter`, trimmed by
-        `trim` and then judged by `flt`, where chunk_trim is valid -> dict(rc, out, out_len, report, keep, win); see _trim_call"""
-        return _clip_call(lib().fqgpu_chunk_clip, (self.h,), adapter, trim, flt, n_recs, **kw)
+        `trim` and then judged by `flt`, where chunk_trim is valid -> dict(rc, out, out_len, report, keep, win); see _select_call"""
+        return _select_call(lib().fqgpu_chunk_clip, (self.h,), (adapter, trim, flt), n_recs, more=("win",), **kw)
 
     def chunk_tailtrim(self, n_recs, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_chunk_tailtrim: the reads of the chunk on the staging block (n_recs records) clipped at `adapter`, their
         poly-X tail and the sliding-window cut of `tail` taken, trimmed by `trim` and then judged by `flt`, where chunk_clip is
-        valid -> dict(rc, out, out_len, report, keep, win, places); see _tail_call"""
-        return _tail_call(lib().fqgpu_chunk_tailtrim, (self.h,), adapter, tail, trim, flt, n_recs, **kw)
+        valid -> dict(rc, out, out_len, report, keep, win, places); see _select_call"""
+        return _select_call(lib().fqgpu_chunk_tailtrim, (self.h,), (adapter, tail, trim, flt), n_recs, more=("win", "places"),
+                            report_words=TAIL_REPORT_WORDS, **kw)
 
     def chunk_select_marked(self, first, end, mark=None, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_chunk_select_marked: the records [first, end) of the chunk on the staging block, where chunk_tailtrim is
-        valid, against `mark` -> dict(rc, out, out_len, report, keep, win, places); see _marked_call"""
-        return _marked_call(lib().fqgpu_chunk_select_marked, (self.h,), adapter, tail, trim, flt, first, end, mark, **kw)
+        valid, against `mark` -> dict(rc, out, out_len, report, keep, win, places); see _range_call"""
+        return _range_call(lib().fqgpu_chunk_select_marked, (self.h,), (adapter, tail, trim, flt), first, end, mark, **kw)
 
     def chunk_select_limited(self, first, end, mark=None, limit=None, adapter=None, tail=None, trim=None, flt=None, **kw):
         """fqgpu_chunk_select_limited: chunk_select_marked with a per-record limit -> as DBlock.select_limited"""
-        return _limited_call(lib().fqgpu_chunk_select_limited, (self.h,), adapter, tail, trim, flt, first, end, mark, limit, **kw)
+        return _range_call(lib().fqgpu_chunk_select_limited, (self.h,), (adapter, tail, trim, flt), first, end, mark, limit, **kw)
 
     def chunk_pair_correct(self, first, other, other_first, count, insert, spec, **kw):
         """fqgpu_chunk_pair_correct: the correction inside the mate overlap of the chunk staged here (mate 1) and the chunk staged

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <string>
 #include <map>
@@ -1731,6 +1732,15 @@ static int settled_block(fqgpu_ctx *ctx, const fqgpu_dblock *b) {
   return FQGPU_OK;
 }
 
+// What the drivers take (FqChunkView): a block's whole chunk, or `count` of its records from `first` on.  FQGPU_E_ARG: no
+// record, or a range that does not lie inside the table.
+static FqChunkView chunk_view(const fqgpu_dblock *b) { return {b->raw, b->raw_len, b->recs, b->n_recs, false}; }
+static int range_view(const fqgpu_dblock *b, size_t first, size_t count, FqChunkView *v) {
+  if (count == 0 || first >= b->n_recs || count > b->n_recs - first) return FQGPU_E_ARG;  // (no sum that could overflow)
+  *v = {b->raw, b->raw_len, b->recs + first, count, first != 0};
+  return FQGPU_OK;
+}
+
 extern "C" int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len) {
   if (crc) *crc = 0;
   if (len) *len = 0;
@@ -1741,7 +1751,7 @@ extern "C" int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len) {
   if ((rc = staged_block(ctx, &b))) return rc;
   uint32_t c = 0;
   size_t n = ctx->hp_crc_len;
-  rc = ctx->hp_crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n)
+  rc = ctx->hp_crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, chunk_view(b), &c, &n)
                              : fq_crc_bytes(ctx, ctx->stream, b->raw, n, &c);
   if (rc) return rc;
   *crc = c;
@@ -1758,7 +1768,7 @@ extern "C" int fqgpu_dblock_crc32(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint32_
   if ((rc = settled_block(ctx, b))) return rc;
   uint32_t c = 0;
   size_t n = 0;
-  if ((rc = fq_crc_canonical(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, &c, &n))) return rc;
+  if ((rc = fq_crc_canonical(ctx, ctx->stream, chunk_view(b), &c, &n))) return rc;
   *crc = c;
   *len = n;
   return FQGPU_OK;
@@ -1774,7 +1784,7 @@ static int stats_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, unsign
   if (cap_words < words) return FQGPU_E_OVERFLOW;
   memset(out, 0, words * sizeof(uint64_t));
   if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
-  return fq_stats_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, positions, out);
+  return fq_stats_chunk(ctx, ctx->stream, chunk_view(b), positions, out);
 }
 
 extern "C" int fqgpu_chunk_stats(fqgpu_ctx *ctx, unsigned positions, uint64_t *out, size_t cap_words) {
@@ -1797,7 +1807,7 @@ static int probe_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const 
   if (cap_words < words) return FQGPU_E_OVERFLOW;
   memset(out, 0, words * sizeof(uint64_t));
   if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
-  return fq_probe_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, p, positions, out, places_out);
+  return fq_probe_chunk(ctx, ctx->stream, chunk_view(b), p, positions, out, places_out);
 }
 
 extern "C" int fqgpu_chunk_probe(fqgpu_ctx *ctx, const fqgpu_probes *p, unsigned positions, uint64_t *out, size_t cap_words,
@@ -1810,164 +1820,180 @@ extern "C" int fqgpu_dblock_probe(fqgpu_ctx *ctx, const fqgpu_dblock *b, const f
   return probe_call(ctx, b, false, p, positions, out, cap_words, places_out);
 }
 
-// ------------------------------------------------------------------ the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip)
-// The six calls (b, staged: as stats_call; trim: a trim call, which needs *t and takes a NULL filter for one that keeps
-// everything; a: a clip call's adapter -- with one, a NULL trim is one that cuts nothing; a clip call without one is the trim
-// call): no device is said before any argument is looked at; *out_len and the report are zeroed before anything else
-// can fail.  tail: one of the two tail calls, whose report has FQGPU_TAIL_REPORT_WORDS words; x: its tail -- NULL, or one
-// with both rules off, makes it the clip call with the same a, t, f (words 16 .. 23 zero), unless the places are asked for:
-// then k_tail_find runs with nothing to do, and the results are the clip call's all the same.
-static int select_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, bool trim, const fqgpu_adapter *a, const fqgpu_trim *t,
-                       const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
-                       uint32_t *win_out, bool tail = false, const fqgpu_tail *x = nullptr, uint16_t *places_out = nullptr) {
-  static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one zeroing for both reports");
+// ------------------------------------------------------------------ the selection: the reads of a chunk in HBM clipped, trimmed, judged, marked, limited (select.hip)
+// THE front of the twelve selection calls (b, staged: as stats_call), and the order of what a caller can observe:
+//   1. no device is said before any argument is looked at;
+//   2. *out_len and the report are zeroed before anything else can fail;
+//   3. the specs are checked, FQGPU_E_ARG;
+//   4. the chunk is found, staged or settled;
+//   5. a family with a range checks [first, end) against the table.
+// Between 3 and 4 the job is NORMALISED, so that fq_select_chunk looks at none of this again: a NULL trim beside an adapter, a
+// tail or a range is one that cuts nothing, a NULL filter one that keeps everything; a tail that is NULL or has both rules
+// off is no tail -- the clip's kernels, words 16 .. 19 zero -- unless the places are asked for: then k_tail_find runs with
+// nothing to do, and the results are the clip's all the same; the windows go with the trim and the places with the tail.
+struct SelectFamily {
+  bool need_trim, need_filter;  // a NULL one is refused (a filter call has no trim at all, and takes none)
+  bool range;                   // the records [first, end) of the table, handed to the driver as a table of their own
+};
+constexpr SelectFamily kFilterCall = {false, true, false}, kTrimCall = {true, false, false}, kRangeCall = {false, false, true};
+
+static int select_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const SelectFamily &fam, FqSelectJob job, size_t first, size_t end,
+                       FqSelectOut o) {
   if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
-  if (out_len) *out_len = 0;
-  if (report) memset(report, 0, (tail ? FQGPU_TAIL_REPORT_WORDS : FQGPU_FILTER_REPORT_WORDS) * sizeof(uint64_t));
-  const fqgpu_trim none = {0u, 0u, 0u, 0u, FQGPU_FILTER_NONE, {0u, 0u, 0u}};
-  const fqgpu_tail off = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
-  if (x && fqgpu_tail_check(x) != FQGPU_OK) return FQGPU_E_ARG;
-  const bool tail_on = x && (x->poly_bases || x->window_len);
-  if (tail && !tail_on) x = places_out && (a || t) ? &off : nullptr;
-  if ((a || x) && !t) t = &none;
-  if (!ctx || !out_len || !report || (a && fqgpu_adapter_check(a) != FQGPU_OK) || (trim && fqgpu_trim_check(t) != FQGPU_OK) ||
-      ((f || !trim) && fqgpu_filter_check(f) != FQGPU_OK))
+  if (o.out_len) *o.out_len = 0;
+  if (o.report) memset(o.report, 0, o.report_words * sizeof(uint64_t));
+  static const fqgpu_trim none = {0u, 0u, 0u, 0u, FQGPU_FILTER_NONE, {0u, 0u, 0u}};
+  static const fqgpu_tail off = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+  static const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
+  if (job.tail && fqgpu_tail_check(job.tail) != FQGPU_OK) return FQGPU_E_ARG;
+  if (!job.tail || !(job.tail->poly_bases || job.tail->window_len)) job.tail = o.places && (job.adapter || job.trim || fam.range) ? &off : nullptr;
+  if ((job.adapter || job.tail || fam.range) && !job.trim) job.trim = &none;
+  if (!ctx || !o.out_len || !o.report || (job.adapter && fqgpu_adapter_check(job.adapter) != FQGPU_OK) ||
+      ((job.trim || fam.need_trim) && fqgpu_trim_check(job.trim) != FQGPU_OK) ||
+      ((job.filter || fam.need_filter) && fqgpu_filter_check(job.filter) != FQGPU_OK))
     return FQGPU_E_ARG;
-  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
+  if (!job.filter) job.filter = &all;
+  if (!job.trim) o.win = nullptr;
+  if (!job.tail) o.places = nullptr;
+  job.span = fam.range ? "select_marked" : job.tail ? "tailtrim" : job.adapter ? "clip" : job.trim ? "trim" : "filter";
   if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
-  return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs, b->n_recs, a, trim ? t : nullptr, f ? f : &all, out, out_cap, out_len,
-                         report, keep_out, win_out, x, places_out);
+  FqChunkView v = chunk_view(b);
+  if (fam.range && (first >= end || range_view(b, first, end - first, &v) != FQGPU_OK)) return FQGPU_E_ARG;
+  return fq_select_chunk(ctx, ctx->stream, v, job, o);
 }
 
 extern "C" int fqgpu_chunk_filter(fqgpu_ctx *ctx, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                                   uint64_t *report, uint8_t *keep_out) {
-  return select_call(ctx, nullptr, true, false, nullptr, nullptr, f, out, out_cap, out_len, report, keep_out, nullptr);
+  return select_call(ctx, nullptr, true, kFilterCall, {nullptr, nullptr, nullptr, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_FILTER_REPORT_WORDS, keep_out});
 }
 
 extern "C" int fqgpu_dblock_filter(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_filter *f, uint8_t *out, size_t out_cap,
                                    size_t *out_len, uint64_t *report, uint8_t *keep_out) {
-  return select_call(ctx, b, false, false, nullptr, nullptr, f, out, out_cap, out_len, report, keep_out, nullptr);
+  return select_call(ctx, b, false, kFilterCall, {nullptr, nullptr, nullptr, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_FILTER_REPORT_WORDS, keep_out});
 }
 
 extern "C" int fqgpu_chunk_trim(fqgpu_ctx *ctx, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
                                 uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  return select_call(ctx, nullptr, true, true, nullptr, t, f, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, nullptr, true, kTrimCall, {nullptr, nullptr, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TRIM_REPORT_WORDS, keep_out, win_out});
 }
 
 extern "C" int fqgpu_dblock_trim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out,
                                  size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  return select_call(ctx, b, false, true, nullptr, t, f, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, b, false, kTrimCall, {nullptr, nullptr, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TRIM_REPORT_WORDS, keep_out, win_out});
 }
 
+// (a clip call without an adapter is the trim call)
 extern "C" int fqgpu_chunk_clip(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out,
                                 size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  return select_call(ctx, nullptr, true, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, nullptr, true, kTrimCall, {a, nullptr, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TRIM_REPORT_WORDS, keep_out, win_out});
 }
 
 extern "C" int fqgpu_dblock_clip(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f,
                                  uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out) {
-  return select_call(ctx, b, false, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out);
+  return select_call(ctx, b, false, kTrimCall, {a, nullptr, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TRIM_REPORT_WORDS, keep_out, win_out});
 }
 
 extern "C" int fqgpu_chunk_tailtrim(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
                                     uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
                                     uint16_t *places_out) {
-  return select_call(ctx, nullptr, true, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out, true, x, places_out);
+  return select_call(ctx, nullptr, true, kTrimCall, {a, x, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
 extern "C" int fqgpu_dblock_tailtrim(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
                                      const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
                                      uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
-  return select_call(ctx, b, false, true, a, t, f, out, out_cap, out_len, report, keep_out, win_out, true, x, places_out);
+  return select_call(ctx, b, false, kTrimCall, {a, x, t, f}, 0, 0,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
-// ------------------------------------------------------------------ a record range of a chunk in HBM against a mark, and the read ids of two chunks (select.hip)
-// The two marked calls (b, staged: as stats_call): the tail calls' front -- no device is said before any argument is looked
-// at, *out_len and the report are zeroed before anything else can fail -- with every one of a, x, t, f allowed to be NULL, and
-// the range [first, end) of the block's record table handed to fq_select_chunk as a table of its own.  limit_in (the
-// limited calls'; nullptr: none): the range's per-record limits, which travel with the mark.
-static int marked_call(fqgpu_ctx *ctx, const fqgpu_dblock *b, bool staged, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
-                       const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
-                       uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out, const uint16_t *limit_in = nullptr) {
-  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
-  if (out_len) *out_len = 0;
-  if (report) memset(report, 0, FQGPU_TAIL_REPORT_WORDS * sizeof(uint64_t));
-  const fqgpu_trim none = {0u, 0u, 0u, 0u, FQGPU_FILTER_NONE, {0u, 0u, 0u}};
-  const fqgpu_tail off = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
-  const fqgpu_filter all = {0u, FQGPU_FILTER_NONE, FQGPU_FILTER_NONE, 0u, 0u, 0u, {0u, 0u}};
-  if (x && fqgpu_tail_check(x) != FQGPU_OK) return FQGPU_E_ARG;
-  if (!x || !(x->poly_bases || x->window_len)) x = places_out ? &off : nullptr;  // (as the tail calls: the clip's kernels, unless the places are asked for)
-  if (!t) t = &none;
-  if (!ctx || !out_len || !report || (a && fqgpu_adapter_check(a) != FQGPU_OK) || fqgpu_trim_check(t) != FQGPU_OK ||
-      (f && fqgpu_filter_check(f) != FQGPU_OK))
-    return FQGPU_E_ARG;
-  if (const int rc = staged ? staged_block(ctx, &b) : settled_block(ctx, b)) return rc;
-  if (first >= end || end > b->n_recs) return FQGPU_E_ARG;
-  const FqSelectMark m = {first != 0, mark_in, limit_in};
-  return fq_select_chunk(ctx, ctx->stream, b->raw, b->raw_len, b->recs + first, end - first, a, t, f ? f : &all, out, out_cap, out_len, report,
-                         keep_out, win_out, x, places_out, &m);
-}
-
+// The marked and the limited calls (a paired restore's selection): every one of a, x, t, f may be NULL; the range's mark and
+// its per-record limits (the limited calls'; k_select_limit) travel in the job.
 extern "C" int fqgpu_chunk_select_marked(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
                                          size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap, size_t *out_len,
                                          uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
-  return marked_call(ctx, nullptr, true, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out);
+  return select_call(ctx, nullptr, true, kRangeCall, {a, x, t, f, mark_in}, first, end,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
 extern "C" int fqgpu_dblock_select_marked(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
                                           const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, uint8_t *out, size_t out_cap,
                                           size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out, uint16_t *places_out) {
-  return marked_call(ctx, b, false, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out);
+  return select_call(ctx, b, false, kRangeCall, {a, x, t, f, mark_in}, first, end,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
-// The two limited calls: the marked calls with the range's limits (select.hip, k_select_limit)
 extern "C" int fqgpu_chunk_select_limited(fqgpu_ctx *ctx, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t, const fqgpu_filter *f,
                                           size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in, uint8_t *out,
                                           size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out, uint32_t *win_out,
                                           uint16_t *places_out) {
-  return marked_call(ctx, nullptr, true, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out, limit_in);
+  return select_call(ctx, nullptr, true, kRangeCall, {a, x, t, f, mark_in, limit_in}, first, end,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
 extern "C" int fqgpu_dblock_select_limited(fqgpu_ctx *ctx, const fqgpu_dblock *b, const fqgpu_adapter *a, const fqgpu_tail *x, const fqgpu_trim *t,
                                            const fqgpu_filter *f, size_t first, size_t end, const uint8_t *mark_in, const uint16_t *limit_in,
                                            uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *keep_out,
                                            uint32_t *win_out, uint16_t *places_out) {
-  return marked_call(ctx, b, false, a, x, t, f, first, end, mark_in, out, out_cap, out_len, report, keep_out, win_out, places_out, limit_in);
+  return select_call(ctx, b, false, kRangeCall, {a, x, t, f, mark_in, limit_in}, first, end,
+                     {out, out_cap, out_len, report, FQGPU_TAIL_REPORT_WORDS, keep_out, win_out, places_out});
 }
 
-// The two id calls: both chunks at rest -- every stream of both handles, and of a block's owner, is waited for --, then one
-// kernel on ctx's stream.
-static int names_call(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
-                      size_t *mismatch) {
-  if (count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs || count > bb->n_recs - first_b)
-    return FQGPU_E_ARG;
-  return fq_pair_names(ctx, ctx->stream, ba->raw, ba->raw_len, ba->recs + first_a, first_a != 0, bb->raw, bb->raw_len, bb->recs + first_b,
-                       first_b != 0, count, mismatch);
+// ------------------------------------------------------------------ the calls on two chunks in HBM (pair.hip)
+// The two sides of a pair call at rest, as views of `count` records from first_a and first_b on; every call below goes through
+// here, behind its own argument checks (no device is said before any argument is looked at, then what the call zeroes, then
+// its specs, FQGPU_E_ARG).  staged: the chunks staged on the two handles -- both non-NULL, on one device, each with a chunk
+// --, every stream of both waited for; else two blocks of ctx_a's device, each settled: ctx_a's streams and its owner's waited
+// for.  Then the ranges against the tables.  distinct: the sides must be two chunks -- the calls that CHANGE them.  One
+// kernel on ctx_a's stream follows.  Every FQGPU_E_ARG of a call, from here or from its driver, leaves the call's report as
+// it was zeroed and its per-pair arrays zeroed, and the correcting calls' chunks untouched.
+static int pair_sides(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb,
+                      size_t first_b, size_t count, bool distinct, FqChunkView *a, FqChunkView *b) {
+  int rc;
+  if (staged) {
+    if (!ctx_b || (distinct && ctx_a == ctx_b) || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
+    if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
+  } else {
+    if (distinct && ba == bb) return FQGPU_E_ARG;
+    if ((rc = settled_block(ctx_a, ba)) || (rc = settled_block(ctx_a, bb))) return rc;
+  }
+  if ((rc = range_view(ba, first_a, count, a)) || (rc = range_view(bb, first_b, count, b))) return rc;
+  return FQGPU_OK;
+}
+// the tail of a pair call: its per-pair arrays zeroed on FQGPU_E_ARG
+static int pair_result(int rc, size_t count, std::initializer_list<uint16_t *> arrays) {
+  if (rc == FQGPU_E_ARG && count)
+    for (uint16_t *p : arrays)
+      if (p) memset(p, 0, count * sizeof(uint16_t));
+  return rc;
+}
+
+static int names_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb,
+                      size_t first_b, size_t count, size_t *mismatch) {
+  if (mismatch) *mismatch = (size_t)-1;
+  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
+  if (!ctx_a || !mismatch) return FQGPU_E_ARG;
+  FqChunkView a, b;
+  if (const int rc = pair_sides(staged, ctx_a, ctx_b, ba, first_a, bb, first_b, count, false, &a, &b)) return rc;
+  return fq_pair_names(ctx_a, ctx_a->stream, a, b, mismatch);
 }
 
 extern "C" int fqgpu_chunk_pair_names(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, size_t *mismatch) {
-  if (mismatch) *mismatch = (size_t)-1;
-  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
-  if (!ctx_a || !ctx_b || !mismatch || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
-  const fqgpu_dblock *ba = nullptr, *bb = nullptr;
-  int rc;
-  if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
-  return names_call(ctx_a, ba, first_a, bb, first_b, count, mismatch);
+  return names_call(true, ctx_a, ctx_b, nullptr, first_a, nullptr, first_b, count, mismatch);
 }
 
 extern "C" int fqgpu_dblock_pair_names(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
                                        size_t count, size_t *mismatch) {
-  if (mismatch) *mismatch = (size_t)-1;
-  if (const int rc = use_device(ctx ? ctx->device : 0)) return rc;
-  if (!ctx || !mismatch) return FQGPU_E_ARG;
-  int rc;
-  if ((rc = settled_block(ctx, ba)) || (rc = settled_block(ctx, bb))) return rc;
-  return names_call(ctx, ba, first_a, bb, first_b, count, mismatch);
+  return names_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, mismatch);
 }
 
-// The two overlap calls (staged: the chunks staged on the two handles; else two blocks of ctx_a's device): the id
-// calls' checks and waits, then one kernel on ctx_a's stream.  No device is said before any argument is looked at, too little
-// room before anything is written; every FQGPU_E_ARG leaves `out` and the three arrays zeroed.
+// The overlap calls: too little room is said before anything is written.
 static int overlap_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
                         size_t count, const fqgpu_overlap *o, uint64_t *out, size_t cap_words, uint16_t *limit_a_out, uint16_t *limit_b_out,
                         uint16_t *insert_out) {
@@ -1977,25 +2003,11 @@ static int overlap_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const f
     if (!out) return FQGPU_E_ARG;
     memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
     if (!ctx_a || fqgpu_overlap_check(o) != FQGPU_OK) return FQGPU_E_ARG;
-    int rc;
-    if (staged) {
-      if (!ctx_b || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
-      if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
-    } else if ((rc = settled_block(ctx_a, ba)) || (rc = settled_block(ctx_a, bb))) {
-      return rc;
-    }
-    if (count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs || count > bb->n_recs - first_b)
-      return FQGPU_E_ARG;
-    return fq_pair_overlap(ctx_a, ctx_a->stream, ba->raw, ba->raw_len, ba->recs + first_a, bb->raw, bb->raw_len, bb->recs + first_b, count, o,
-                           out, limit_a_out, limit_b_out, insert_out);
+    FqChunkView a, b;
+    if (const int rc = pair_sides(staged, ctx_a, ctx_b, ba, first_a, bb, first_b, count, false, &a, &b)) return rc;
+    return fq_pair_overlap(ctx_a, ctx_a->stream, a, b, o, out, limit_a_out, limit_b_out, insert_out);
   };
-  const int rc = run();
-  if (rc == FQGPU_E_ARG) {
-    uint16_t *const arr[3] = {limit_a_out, limit_b_out, insert_out};
-    for (uint16_t *p : arr)
-      if (p && count) memset(p, 0, count * sizeof(uint16_t));
-  }
-  return rc;
+  return pair_result(run(), count, {limit_a_out, limit_b_out, insert_out});
 }
 
 extern "C" int fqgpu_chunk_pair_overlap(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const fqgpu_overlap *o,
@@ -2009,10 +2021,7 @@ extern "C" int fqgpu_dblock_pair_overlap(fqgpu_ctx *ctx, const fqgpu_dblock *ba,
   return overlap_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, o, out, cap_words, limit_a_out, limit_b_out, insert_out);
 }
 
-// The two correcting calls (staged: the chunks staged on the two handles; else two blocks of ctx_a's device): the overlap
-// calls' checks and waits -- no device is said before any argument is looked at, then the arguments, then the states --, but
-// the two sides must be two chunks, for these calls CHANGE them (select.hip, k_pair_correct).  Every FQGPU_E_ARG leaves both
-// chunks as they were and the report and the two arrays zeroed.
+// The correcting calls: the two sides must be two chunks, for these calls CHANGE them (pair.hip, k_pair_correct).
 static int correct_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
                         size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out,
                         uint16_t *fixed_b_out) {
@@ -2021,26 +2030,11 @@ static int correct_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const f
     if (!report) return FQGPU_E_ARG;
     memset(report, 0, FQGPU_CORRECT_REPORT_WORDS * sizeof(uint64_t));
     if (!ctx_a || !insert_in || fqgpu_correct_check(c) != FQGPU_OK) return FQGPU_E_ARG;
-    int rc;
-    if (staged) {
-      if (!ctx_b || ctx_a == ctx_b || ctx_a->device != ctx_b->device) return FQGPU_E_ARG;
-      if ((rc = staged_block(ctx_a, &ba)) || (rc = staged_block(ctx_b, &bb)) || (rc = fqgpu_sync(ctx_a)) || (rc = fqgpu_sync(ctx_b))) return rc;
-    } else {
-      if (ba == bb) return FQGPU_E_ARG;
-      if ((rc = settled_block(ctx_a, ba)) || (rc = settled_block(ctx_a, bb))) return rc;
-    }
-    if (ba == bb || count == 0 || first_a >= ba->n_recs || count > ba->n_recs - first_a || first_b >= bb->n_recs ||
-        count > bb->n_recs - first_b)
-      return FQGPU_E_ARG;
-    return fq_pair_correct(ctx_a, ctx_a->stream, ba->raw, ba->raw_len, ba->recs + first_a, bb->raw, bb->raw_len, bb->recs + first_b, count, insert_in,
-                           c, report, fixed_a_out, fixed_b_out);
+    FqChunkView a, b;
+    if (const int rc = pair_sides(staged, ctx_a, ctx_b, ba, first_a, bb, first_b, count, true, &a, &b)) return rc;
+    return fq_pair_correct(ctx_a, ctx_a->stream, a, b, insert_in, c, report, fixed_a_out, fixed_b_out);
   };
-  const int rc = run();
-  if (rc == FQGPU_E_ARG) {
-    for (uint16_t *p : {fixed_a_out, fixed_b_out})
-      if (p && count) memset(p, 0, count * sizeof(uint16_t));
-  }
-  return rc;
+  return pair_result(run(), count, {fixed_a_out, fixed_b_out});
 }
 
 extern "C" int fqgpu_chunk_pair_correct(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const uint16_t *insert_in,

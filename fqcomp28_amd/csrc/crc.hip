@@ -259,13 +259,15 @@ int fq_crc_bytes(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *data_dev, size_t
   return FQGPU_OK;
 }
 
-// The digest of the canonical bytes of the chunk raw_dev[0, raw_len) with the record table recs_dev, on st, waited for;
+// The digest of the canonical bytes of the chunk v (raw_dev[0, raw_len) with the record table recs_dev), on st, waited for;
 // *len = their number.  Bare '+' lines: the chunk itself up to the end of its last record -- which is raw_len for every
 // chunk the parsers cut, so the check of the record table and the digest of raw_dev[0, raw_len) are queued together and
 // waited for ONCE (32 bytes come back); a chunk that ends elsewhere is digested again up to there.  Otherwise the
 // canonical bytes are gathered into scratch first (one more pass over the chunk: correctness only).
-int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                     uint32_t *crc, size_t *len) {
+int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, uint32_t *crc, size_t *len) {
+  const uint8_t *const raw_dev = v.raw;
+  const fqgpu_rec *const recs_dev = v.recs;
+  const size_t raw_len = v.raw_len, n_recs = v.n_recs;
   if (!n_recs || n_recs >= ((size_t)1 << 32)) return FQGPU_E_ARG;
   CrcScratch &cs = ctx->crc;
   int rc;

@@ -149,7 +149,7 @@ extern "C" int fqgpu_probe_merge(uint64_t *dst, size_t dst_words, const uint64_t
   return FQGPU_OK;
 }
 
-// Mate overlap (select.hip finds it): what a spec may say, its fingerprint, and dst += src.
+// Mate overlap (pair.hip finds it): what a spec may say, its fingerprint, and dst += src.
 extern "C" int fqgpu_overlap_check(const fqgpu_overlap *o) {
   if (!o || o->min_overlap < 1u || o->min_overlap > FQGPU_OVERLAP_MAX_LEN || o->max_mism > 65535u || o->max_err_pct > 50u) return FQGPU_E_ARG;
   for (uint32_t r : o->reserved)
@@ -181,7 +181,7 @@ extern "C" int fqgpu_overlap_merge(uint64_t *dst, size_t dst_words, const uint64
   return FQGPU_OK;
 }
 
-// The correction inside the mate overlap (select.hip applies it): what a spec may say.
+// The correction inside the mate overlap (pair.hip applies it): what a spec may say.
 extern "C" int fqgpu_correct_check(const fqgpu_correct *c) {
   if (!c || c->good_q < 1u || c->good_q > 63u || c->bad_q >= c->good_q) return FQGPU_E_ARG;
   for (uint32_t r : c->reserved)
@@ -199,7 +199,7 @@ extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   return FQGPU_OK;
 }
 
-// The read id of a header line (select.hip compares them, k_pair_names): the bytes behind the line's first byte, the '@', up
+// The read id of a header line (pair.hip compares them, k_pair_names): the bytes behind the line's first byte, the '@', up
 // to the first ' ', '\t' or '\n' or the end of what is given, without a "/1" or "/2" at their end.
 extern "C" size_t fqgpu_read_id_len(const uint8_t *header_line, size_t len) {
   if (!header_line || len < 2) return 0;

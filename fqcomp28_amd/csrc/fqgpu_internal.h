@@ -260,18 +260,18 @@ struct StatsScratch {
 };
 FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs), FQ_B(StatsScratch, bad))
 
-// Selection of the reads of a chunk in HBM that pass a filter, trimmed first or not (select.hip): per record the kept size, the
-// start of its header line and -- reserved by a trim call alone -- its window, beside it -- by a clip call alone -- its clip
-// place (a uint16_t: k_adapter_find writes it, the judge reads it) and -- by a tail call alone -- its places a0, a1, e, e2
-// (four uint16_t: k_tail_find writes them, the judge reads them), the keep bits, the offsets of the kept records
-// in the output, the gathered output, the result words and their page-locked landing place; all grown on demand.  One for
-// filter and trim calls: each is waited for before it returns.  A probe call (adapter content) has two buffers of its own
-// here: its u64 result tables and -- when asked for -- the records' places, n uint16_t each.  A marked call
-// (fqgpu_chunk_select_marked) has one: the caller's mark, a u64 word per 64 records; a limited call
-// (fqgpu_chunk_select_limited) another: the caller's limits, a uint16_t per record.  An overlap call
-// (fqgpu_chunk_pair_overlap) has two: its u64 result words and the pairs' limit1, limit2 and I, three arrays of uint16_t.
-// A correcting call (fqgpu_chunk_pair_correct) has two: the caller's inserts and the pairs' changed places, two arrays of
-// uint16_t; its counters are the result words.
+// The scratch of the calls on chunks at rest in HBM (select.hip, pair.hip); all grown on demand, and one for all of them: each
+// call is waited for before it returns.
+//   the selection  per record the kept size, the start of its header line and -- a trim's -- its window, its clip place (a
+//                  uint16_t: k_adapter_find or k_select_limit writes it, the judge reads it) and -- a tail's -- its places a0,
+//                  a1, e, e2; the keep bits, the offsets of the kept records in the output, the gathered output; the caller's
+//                  mark (a u64 word per 64 records) and limits (a uint16_t per record)
+//   the probe      its u64 result tables and -- when asked for -- the records' places, n uint16_t each
+//   the overlap    its u64 result words and the pairs' limit1, limit2 and I, three arrays of uint16_t
+//   the correction the caller's inserts and the pairs' changed places, two arrays of uint16_t; its counters are the result words
+//   every call     `res`, the result words (SelectResult, sel_words.h), and `host`, their page-locked landing place, between
+//                  begin and finish
+struct SelectResult;
 struct SelectScratch {
   DevBuf ksize, hstart, win, clip, places, keep, koff, dst, res, scan_tmp;
   DevBuf probe_out, probe_places;
@@ -280,6 +280,11 @@ struct SelectScratch {
   DevBuf correct_in, correct_fixed;
   void *host = nullptr;
   void release_host();
+  // The frame of a call: begin reserves `res`, allocates `host` once and queues the zeroing of the result words on st; finish
+  // queues their copy to `host` behind whatever the driver queued, waits for st -- the call's one wait, or its first of two --
+  // and hands the words back.
+  int begin(hipStream_t st);
+  int finish(hipStream_t st, const SelectResult *&result);
 };
 FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, hstart), FQ_B(SelectScratch, win), FQ_B(SelectScratch, clip),
                 FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
@@ -477,62 +482,75 @@ int fq_chunk_layout(hipStream_t st, ChunkScratch &cs, uint8_t *raw_dev, fqgpu_re
 int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, ParseScratch &ps, fqgpu_rec *recs_dev,
                      size_t n_recs, size_t *n_bases, size_t *n_n, size_t *used_len);
 
+// ---------------------------------------------------------------- calls on a chunk at rest in HBM
+// A chunk, or a record range of one, as every driver below takes it; the bytes and the table lie on the device.  Everything a
+// driver hands back per record is relative to recs[0].
+struct FqChunkView {
+  const uint8_t *raw;     // the WHOLE chunk, whatever the range (a record's offsets count from here)
+  size_t raw_len;
+  const fqgpu_rec *recs;  // the range's first record
+  size_t n_recs;          // the range's count
+  bool prev;              // recs[-1] exists: the range's first record is not the table's first
+};
+
 // CRC-32 of device bytes (crc.hip), on st, waited for: of data_dev[0, len) as it lies / of the canonical bytes of a chunk
 int fq_crc_bytes(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *data_dev, size_t len, uint32_t *crc);
-int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                     uint32_t *crc, size_t *len);
+int fq_crc_canonical(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, uint32_t *crc, size_t *len);
 
 // Read summary of a chunk in HBM (stats.hip), on st, waited for: out[0, fqgpu_stats_words(positions)) on the host
-int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                   unsigned positions, uint64_t *out);
+int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, unsigned positions, uint64_t *out);
 
-// The reads of a chunk in HBM clipped at the adapter *a (nullptr: none; one needs a trim, which may cut nothing), trimmed by
-// *t (nullptr: the filter alone, win_out is not looked at) and then judged by *f
-// (select.hip; both have passed their checks), on st, waited for: report (FQGPU_TRIM_REPORT_WORDS, which are
-// FQGPU_FILTER_REPORT_WORDS), *out_len, keep_out, win_out and -- out != nullptr, out_cap enough -- ONE copy of *out_len bytes
-// into out.  x (nullptr: none; one needs a trim and has passed its check): the tail trims between the clip and the trim; the
-// report then has FQGPU_TAIL_REPORT_WORDS words and places_out (nullptr: not wanted) receives a0, a1, e, e2 of every record.
-// m (nullptr: none; one needs a trim): recs_dev points at the first record of a RANGE of the chunk's table and n_recs is the
-// range's count -- every output is relative to it -- and the range is judged against a mark; the report is a tail's with word 20
-struct FqSelectMark {
-  bool prev;            // the range's first record is not the table's first: recs_dev[-1] is the record in front of it
-  const uint8_t *mark;  // host: (n_recs + 7) / 8 bytes in keep_out's layout; nullptr: every record is marked
-  const uint16_t *limit = nullptr;  // host: n_recs limits (fqgpu_chunk_select_limited); nullptr: none.  With one, words 21 / 22 are counted
+// The selection (select.hip): the reads of v clipped, trimmed and judged as the job says, on st, waited for.  The job is
+// NORMALISED by its one front (api.hip, select_call), and the driver does not look again: every spec has passed its check; an
+// adapter, a tail, a mark or a limit stands beside a trim (one that cuts nothing, if the caller gave none); the filter is
+// never nullptr; out.win is nullptr without a trim, out.places without a tail.
+struct FqSelectJob {
+  const fqgpu_adapter *adapter;  // nullptr: none.  k_adapter_find in front of the judge
+  const fqgpu_tail *tail;        // nullptr: none.  k_tail_find between the clip and the trim
+  const fqgpu_trim *trim;        // nullptr: the filter alone
+  const fqgpu_filter *filter;
+  const uint8_t *mark;           // host: (n_recs + 7) / 8 bytes in keep's layout; nullptr: every record is marked.  Word 20 is counted
+  const uint16_t *limit;         // host: n_recs limits in front of the trim's steps; nullptr: none.  Words 21 / 22 are counted
+  const char *span;              // the name its launches are timed under
 };
-int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                    const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
-                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x = nullptr,
-                    uint16_t *places_out = nullptr, const FqSelectMark *m = nullptr);
-
-// The read ids (include/fqgpu.h) of the records recs_a[i] and recs_b[i], i < count, of two chunks in HBM on ctx's device, both
-// at rest (select.hip), on st, waited for; prev_*: the table has a record in front of recs_*[0].  *mismatch: the smallest i
-// whose ids differ, (size_t)-1 when there is none.  FQGPU_E_ARG: count 0, or a header line outside its chunk
-int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, bool prev_a,
-                  const uint8_t *raw_b, size_t raw_len_b, const fqgpu_rec *recs_b, bool prev_b, size_t count, size_t *mismatch);
-
-// The mate overlap (include/fqgpu.h) of the records recs_a[i] (mate 1) and recs_b[i] (mate 2), i < count, of two chunks in HBM
-// on ctx's device, both at rest (select.hip; the spec has passed its check), on st, waited for: out[0, FQGPU_OVERLAP_WORDS) on
-// the host and -- each where not nullptr -- count uint16_t of limit1, limit2 and I.  FQGPU_E_ARG with all of them zeroed:
-// count 0, a record outside its chunk or of length 0, a byte outside ACGTN in an analysed line
-int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, const uint8_t *raw_b,
-                    size_t raw_len_b, const fqgpu_rec *recs_b, size_t count, const fqgpu_overlap *o, uint64_t *out, uint16_t *limit_a_out,
-                    uint16_t *limit_b_out, uint16_t *insert_out);
-uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o);  // fq_host.cpp: zlib's CRC-32 of the spec's 32 bytes
-
-// The correction inside the mate overlap (include/fqgpu.h) of the records recs_a[i] (mate 1) and recs_b[i] (mate 2), i < count,
-// of two DIFFERENT chunks in HBM on ctx's device, both at rest (select.hip; the spec has passed its check), with the host's
-// insert_in[i], on st, waited for: it CHANGES both chunks.  report[0, FQGPU_CORRECT_REPORT_WORDS) on the host and -- each where
-// not nullptr -- count uint16_t of the places changed in either mate.  FQGPU_E_ARG with the report zeroed and both chunks as
-// they were: count 0, an insert the lengths do not allow, a record with an insert outside its chunk, of length 0 or above
-// 512, a byte inside an overlap that cannot be judged
-int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, uint8_t *raw_b, size_t raw_len_b,
-                    const fqgpu_rec *recs_b, size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report,
-                    uint16_t *fixed_a_out, uint16_t *fixed_b_out);
+// report[0, report_words), *out_len, keep, win (a window per record), places (a0, a1, e, e2 per record) -- each of the three
+// where not nullptr -- and, out != nullptr and out_cap enough, ONE copy of *out_len bytes into out.  The front has zeroed
+// *out_len and the report.
+struct FqSelectOut {
+  uint8_t *out;
+  size_t out_cap;
+  size_t *out_len;
+  uint64_t *report;
+  unsigned report_words;
+  uint8_t *keep;
+  uint32_t *win;
+  uint16_t *places;
+};
+int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, const FqSelectJob &job, const FqSelectOut &o);
 
 // Adapter content of a chunk in HBM (select.hip; the probe set has passed its check, positions is 1 .. 65535), on st, waited
 // for: out[0, fqgpu_probe_words(p->n, positions)) on the host and -- places_out != nullptr -- p->n places per record
-int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                   const fqgpu_probes *p, unsigned positions, uint64_t *out, uint16_t *places_out);
+int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, const fqgpu_probes *p, unsigned positions, uint64_t *out,
+                   uint16_t *places_out);
+
+// The calls on two chunks (pair.hip): the records a.recs[i] (mate 1) and b.recs[i] (mate 2), i < a.n_recs == b.n_recs, of two
+// chunks on ctx's device, both at rest, on st, waited for.  FQGPU_E_ARG: no record, or two counts.
+// The read ids (include/fqgpu.h) compared.  *mismatch: the smallest i whose ids differ, (size_t)-1 when there is none.
+// FQGPU_E_ARG: a header line outside its chunk
+int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, size_t *mismatch);
+// The mate overlap (the spec has passed its check): out[0, FQGPU_OVERLAP_WORDS) on the host and -- each where not nullptr --
+// a uint16_t per pair of limit1, limit2 and I.  FQGPU_E_ARG with `out` zeroed, the three arrays then the caller's to zero: a
+// record outside its chunk or of length 0, a byte outside ACGTN in an analysed line
+int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, const fqgpu_overlap *o, uint64_t *out,
+                    uint16_t *limit_a_out, uint16_t *limit_b_out, uint16_t *insert_out);
+uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o);  // fq_host.cpp: zlib's CRC-32 of the spec's 32 bytes
+// The correction inside the mate overlap (the spec has passed its check) of two DIFFERENT chunks, with the host's insert_in[i]:
+// it CHANGES both chunks, writing through the views' raw.  report[0, FQGPU_CORRECT_REPORT_WORDS) on the host and -- each where
+// not nullptr -- a uint16_t per pair of the places changed in either mate.  FQGPU_E_ARG with the report zeroed, both chunks as
+// they were and the two arrays the caller's to zero: an insert the lengths do not allow, a record with an insert outside its
+// chunk, of length 0 or above 512, a byte inside an overlap that cannot be judged
+int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, const uint16_t *insert_in,
+                    const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out, uint16_t *fixed_b_out);
 uint32_t fq_probes_fingerprint(const fqgpu_probes *p);  // fq_host.cpp: zlib's CRC-32 of the bytes of probe[0 .. n)
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total

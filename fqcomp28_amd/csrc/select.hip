@@ -59,24 +59,17 @@
 // wave per kept record, as k_crc_canon_write): a correctness path, kept because the five-piece form takes twice its time
 // there.
 //
-// A record RANGE and a MARK (fqgpu_chunk_select_marked, fqgpu_dblock_select_marked: a paired restore's selection).  The range
-// is these kernels over recs + first and end - first -- the judge's argument `prev` gives the range's first record its header
-// line --, every scratch array and every output then the range's.  k_select_mark, between the judge and the scan, ANDs the
-// caller's mark into the keep words, takes a record that flips out of the kept sizes and the kept counters and counts it
-// in report word 20.  k_pair_names compares the read ids of two chunks' records (fqgpu_chunk_pair_names): eight lanes to a
-// pair, both ids loaded from wherever they start, one atomicMin for the first pair that differs.
-//
-// The MATE OVERLAP (fqgpu_chunk_pair_overlap, fqgpu_chunk_select_limited).  k_pair_overlap compares the sequence lines of two
-// chunks' records: a wave per 64 pairs, each pair's lines as 2-bit codes and an N plane in LDS, mate 2's reversed and
-// complemented, a lane per candidate shift, the first hit in the rule's order by a ballot; it leaves a summary with the
-// insert-size histogram and per pair the two limits and the insert size.  k_select_limit, behind k_adapter_find, takes the
-// minimum of a caller's per-record limit into the clip places, so that the judge's clip forms serve a limit unchanged.
-// k_pair_correct (fqgpu_chunk_pair_correct) is the one kernel here that CHANGES a chunk: with the pairs' insert sizes it
-// walks each overlap once, eight places to a lane, and where the mates disagree and one base is confident and the other
-// poor it replaces the poor one -- launched twice, first to judge and count, then, if nothing was refused, to store.
+// A record RANGE, a MARK and a LIMIT (fqgpu_chunk_select_marked, fqgpu_chunk_select_limited: a paired restore's selection).
+// The range is these kernels over a view's recs and n_recs (FqChunkView, fqgpu_internal.h) -- its `prev` gives the range's
+// first record its header line --, every scratch array and every output then the range's.  k_select_mark, between the judge
+// and the scan, ANDs the caller's mark into the keep words, takes a record that flips out of the kept sizes and the kept
+// counters and counts it in report word 20.  k_select_limit, behind k_adapter_find, takes the minimum of a caller's
+// per-record limit into the clip places, so that the judge's clip forms serve a limit unchanged.  The calls on two chunks,
+// which find such marks and limits, are pair.hip.
 //
 // All global stores are ordinary vector stores from plain C++.
 #include "fqgpu_internal.h"
+#include "sel_words.h"
 
 #include <string.h>
 
@@ -92,38 +85,13 @@ constexpr unsigned SEL_ROUND_RECORDS = SEL_WAVE_RECORDS / SEL_GROUP_LANES;  // r
 constexpr unsigned SEL_STEP_BYTES = SEL_GROUP_LANES * 16 * SEL_UNROLL;      // bytes of a line a record's lanes ask for in one go
 constexpr unsigned SEL_TILE_BYTES = SEL_GATHER_THREADS * 16 * SEL_GATHER_WORDS;  // output bytes of a gather workgroup
 static_assert(SEL_WAVE_RECORDS == 64 && SEL_GROUP_LANES == 8 && SEL_ROUND_RECORDS == 8 && SEL_UNROLL == 2, "a wave's records sit in its lanes");
+static_assert(SEL_GROUP_LANES == SW_GROUP_LANES, "pair.hip groups a record's lanes as the judge does");
 
-// the result words on the device: the report (include/fqgpu.h; word 0 is filled in by the host) and the two flags
-static_assert(FQGPU_FILTER_REPORT_WORDS == FQGPU_TRIM_REPORT_WORDS, "one result struct serves both reports");
-struct SelectResult {
-  unsigned long long w[FQGPU_TAIL_REPORT_WORDS];
-  unsigned int bad;       // a byte that cannot be judged, a record outside the chunk or without symbols
-  unsigned int not_bare;  // k_crc_check's verdict: text behind a '+', or the last '\n' outside the chunk
-};
 constexpr unsigned R_KEPT = 1, R_BASES_IN = 2, R_BASES_KEPT = 3, R_BYTES_KEPT = 4, R_DROPPED = 5, R_TRIMMED = 10, R_CUT_FRONT = 11,
                    R_CUT_TAIL = 12, R_EMPTIED = 13;
 template <bool TRIM> constexpr unsigned R_COUNTERS = TRIM ? 14 : 10;  // the words a judge counts
 constexpr unsigned R_WITH_ADAPTER = 14, R_CUT_ADAPTER = 15, R_COUNTERS_CLIP = 16;  // ... behind an adapter search
 constexpr unsigned R_WITH_POLY = 16, R_CUT_POLY = 17, R_WINDOW_CUT = 18, R_CUT_WINDOW = 19, R_COUNTERS_TAIL = 20;  // ... behind the tail trims
-
-constexpr unsigned SW_H = 0x80808080u, SW_L = 0x01010101u;
-// per byte of x (every byte < 128), 0 <= k <= 128: bit 7 set where the byte is >= k
-__device__ __forceinline__ unsigned sw_ge(unsigned x, unsigned k) { return ((x | SW_H) - k * SW_L) & SW_H; }
-// ... set where the byte equals c
-__device__ __forceinline__ unsigned sw_eq(unsigned x, unsigned c) { return ~sw_ge(x ^ (c * SW_L), 1u) & SW_H; }
-// 0xFF in the bytes [lo, hi) of a word, 0 <= lo, hi <= 4
-__device__ __forceinline__ unsigned sw_mask(int lo, int hi) {
-  lo = max(lo, 0);
-  hi = min(hi, 4);
-  if (lo >= hi) return 0u;
-  return (0xFFFFFFFFu >> (8 * (4 - hi))) & (0xFFFFFFFFu << (8 * lo));
-}
-// bit j set for the bytes lo <= j < hi of a 16-byte word (any lo, hi)
-__device__ __forceinline__ unsigned sel_bits(int lo, int hi) {
-  lo = min(max(lo, 0), 16);
-  hi = min(max(hi, 0), 16);
-  return hi > lo ? ((1u << hi) - 1u) & ~((1u << lo) - 1u) : 0u;
-}
 
 // what a lane keeps of the record its group reads: the lines' places and the first words of both
 struct SelStage {
@@ -304,7 +272,6 @@ __device__ __forceinline__ void sel_walk_step(SelWalk &wk, const uint4 (&v)[SEL_
 struct ClipWord {
   unsigned ac, gt;
 };
-constexpr unsigned CLIP_GATHER = 0x00204081u;  // x * this: the bits 7, 15, 23, 31 of x side by side in the bits 28 .. 31
 
 // The planes of one word; `in`: a bit for each byte inside the line, the others come out as "no base".  bad: a byte inside
 // the line that is none of ACGTN.
@@ -1216,8 +1183,6 @@ __device__ __forceinline__ unsigned sel_find(const unsigned long long *__restric
   return lo;
 }
 
-struct __attribute__((packed)) SelU128 { uint32_t a, b, c, d; };  // sixteen bytes at any address
-
 // a kept record as the gather sees it: where its pieces come from
 struct SelRec {
   long long h0, seq, qual;  // the header line, the first kept byte of the sequence and of the quality line, in the chunk
@@ -1416,116 +1381,6 @@ k_select_mark(const unsigned long long *__restrict__ mark, unsigned n_recs, uint
   }
 }
 
-// ---- the read ids of two chunks compared (include/fqgpu.h, fqgpu_chunk_pair_names)
-constexpr unsigned PAIR_THREADS = 256;
-constexpr unsigned PAIR_STEP_BYTES = SEL_GROUP_LANES * 16;  // bytes of an id a pair's eight lanes hold at a time
-struct PairSide {
-  const uint8_t *raw;
-  unsigned long long raw_len;
-  const fqgpu_rec *recs;  // the first record of the range
-  unsigned prev;          // it has a record in front of it in its table
-};
-// a record's header line: the first byte of its id (behind the '@'), the bytes from there to the line's '\n'
-struct PairLine {
-  long long id0;
-  unsigned cap;
-  bool ok;  // the line has its '@' and its '\n' and lies inside the chunk
-};
-__device__ __forceinline__ PairLine pair_line(const PairSide &s, unsigned long long i, bool have) {
-  PairLine l = {0, 0u, true};
-  if (!have) return l;
-  const fqgpu_rec rec = s.recs[i];
-  unsigned long long h0 = 0;
-  if (i || s.prev) {
-    const fqgpu_rec before = s.recs[(long long)i - 1];
-    h0 = (unsigned long long)before.qual_off + before.len + 1ull;
-  }
-  l.ok = h0 + 2ull <= rec.seq_off && rec.seq_off <= s.raw_len;
-  l.id0 = (long long)h0 + 1;
-  l.cap = l.ok ? (unsigned)(rec.seq_off - h0 - 2ull) : 0u;
-  return l;
-}
-// the sixteen bytes of an id from place c on; nothing is read from the line's '\n' on (a word reaches at most fifteen bytes
-// behind the '\n', where the sequence line stands, or the spare bytes every raw block has behind its chunk)
-__device__ __forceinline__ uint4 pair_word(const PairSide &s, const PairLine &l, unsigned c) {
-  if (c >= l.cap) return make_uint4(0, 0, 0, 0);
-  const SelU128 v = *reinterpret_cast<const SelU128 *>(s.raw + l.id0 + c);
-  return make_uint4(v.a, v.b, v.c, v.d);
-}
-// a bit for each byte of a word that ends an id: ' ', '\t' or '\n' (a byte >= 128 ends none: the compares see seven bits)
-__device__ __forceinline__ unsigned pair_ends(const uint4 v) {
-  const unsigned w[4] = {v.x, v.y, v.z, v.w};
-  unsigned ends = 0;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const unsigned y = w[i] & ~SW_H;
-    ends |= (((sw_eq(y, ' ') | sw_eq(y, '\t') | sw_eq(y, '\n')) & ~w[i]) * CLIP_GATHER) >> 28 << (4 * i);
-  }
-  return ends;
-}
-// the id's length without a "/1" or "/2" at its end
-__device__ __forceinline__ unsigned pair_strip(const PairSide &s, const PairLine &l, unsigned e) {
-  if (e < 2u) return e;
-  const unsigned slash = s.raw[l.id0 + e - 2], mate = s.raw[l.id0 + e - 1];
-  return slash == '/' && (mate == '1' || mate == '2') ? e - 2u : e;
-}
-
-// *first_diff = min(*first_diff, i) for every i < count at which the read ids of A's record i and B's record i differ in
-// length or in a byte.  EIGHT LANES TO A PAIR, the judge's grouping: lane j of the eight holds the bytes [16 j, 16 j + 16)
-// of both ids, loaded from wherever the ids start, so that the two words of a lane stand for the same places and are
-// compared as they are; a header line of 30 to 80 bytes is then one load instruction per side whose eight addresses fall
-// into the one or two cache lines that hold the line, where a lane per pair would walk its line word by word, every load
-// instruction of the wave over 64 different lines and as many turns as the longest line of the 64 takes.  An id's end is
-// the first ' ', '\t' or '\n' (SWAR byte tests, a min-reduction over the eight lanes by shuffles), the line's own '\n' at
-// the latest; the two bytes in front of it decide on "/1" and "/2".  A line longer than 128 bytes takes more turns, every
-// lane of the wave the same number: a correctness path.  One atomicMin per wave that has a differing pair.
-__global__ void __launch_bounds__(PAIR_THREADS)
-k_pair_names(const PairSide A, const PairSide B, unsigned count, unsigned long long *__restrict__ first_diff, unsigned *__restrict__ bad) {
-  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1);
-  const unsigned long long i = ((unsigned long long)blockIdx.x * PAIR_THREADS + threadIdx.x) / SEL_GROUP_LANES;
-  const bool have = i < count;
-  const PairLine la = pair_line(A, i, have), lb = pair_line(B, i, have);
-  const bool fine = have && la.ok && lb.ok;
-  unsigned steps = max((max(la.cap, lb.cap) + PAIR_STEP_BYTES - 1) / PAIR_STEP_BYTES, 1u);
-#pragma unroll
-  for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-  steps = fq_uniform(steps);
-  const uint4 xa = pair_word(A, la, 16u * sub), xb = pair_word(B, lb, 16u * sub);
-  // the ids' ends
-  unsigned ea = la.cap, eb = lb.cap;
-  for (unsigned s = 0; s < steps; s++) {
-    const unsigned c = s * PAIR_STEP_BYTES + 16u * sub;
-    const unsigned fa = pair_ends(s ? pair_word(A, la, c) : xa) & sel_bits(0, (int)la.cap - (int)c);
-    const unsigned fb = pair_ends(s ? pair_word(B, lb, c) : xb) & sel_bits(0, (int)lb.cap - (int)c);
-    if (fa) ea = min(ea, c + (unsigned)__builtin_ctz(fa));
-    if (fb) eb = min(eb, c + (unsigned)__builtin_ctz(fb));
-  }
-#pragma unroll
-  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) {
-    ea = min(ea, (unsigned)__shfl_xor(ea, d));
-    eb = min(eb, (unsigned)__shfl_xor(eb, d));
-  }
-  if (fine) {
-    ea = pair_strip(A, la, ea);
-    eb = pair_strip(B, lb, eb);
-  }
-  // the bytes in front of them
-  unsigned differ = ea != eb;
-  for (unsigned s = 0; s < steps; s++) {
-    const unsigned c = s * PAIR_STEP_BYTES + 16u * sub;
-    const uint4 va = s ? pair_word(A, la, c) : xa, vb = s ? pair_word(B, lb, c) : xb;
-    const unsigned wa[4] = {va.x, va.y, va.z, va.w}, wb[4] = {vb.x, vb.y, vb.z, vb.w};
-    const int left = (int)min(ea, eb) - (int)c;  // the id's bytes from this word's first on
-#pragma unroll
-    for (int k = 0; k < 4; k++) differ |= ((wa[k] ^ wb[k]) & sw_mask(-4 * k, left - 4 * k)) != 0u;
-  }
-#pragma unroll
-  for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) differ |= __shfl_xor(differ, d);
-  const unsigned long long found = __ballot(fine && differ);
-  if (found && lane == (unsigned)__builtin_ctzll(found)) atomicMin(first_diff, i);  // (the wave's pairs rise with its lanes)
-  if (__any(have && !fine) && lane == 0) *bad = 1u;  // (every writer stores the same value)
-}
-
 // ---- a per-record limit in front of the trim's steps (include/fqgpu.h, fqgpu_chunk_select_limited): behind k_adapter_find,
 // clip[r] = min(clip[r], limit[r]); without an adapter clip[r] is filled from the record's length first.  The judge and
 // k_tail_find then see the clip forms and nothing else changes.  Words 21 / 22 -- the records whose limit lies in front of
@@ -1566,305 +1421,6 @@ k_select_limit(const fqgpu_rec *__restrict__ recs, unsigned n_recs, const uint16
   }
 }
 
-// ---- the mate overlap of two chunks' records (include/fqgpu.h, fqgpu_chunk_pair_overlap).  A workgroup is ONE wave and takes
-// 64 consecutive pairs: their table entries with one load, lane = pair, and their results back to the pair's lane at the
-// end, so that the three arrays go out as three coalesced stores.  The pairs are then taken one after the other by all 64
-// lanes.  Loading: a line has at most 512 bases, lane j reads the eight bytes [8 j, 8 j + 8) of each line from wherever the
-// line starts (the 64 spare bytes behind every chunk let the last word be read whole) and turns them into eight bits of
-// three planes -- the base's code A 00, C 01, G 10, T 11 as a low and a high plane, and an N plane -- by the packed compares
-// clip_planes uses; a byte that is none of ACGTN refuses the chunk.  The planes lie in LDS as bytes, read back as words: bit i
-// of word w is base 32 w + i.  The complement of a code is its inverse, so r = revcomp(s2) is s2's planes bit-reversed over
-// all 512 places (byte 63 - j takes the reversed byte j), the two code planes inverted; r[0] then stands at bit 512 - L2,
-// an offset that folds into the candidate's shift.  Searching: a lane takes one candidate d, 64 candidates in the order of
-// the rule at a time -- d = 0 .. L1 - min_overlap, then -1 .. -(L2 - min_overlap): exactly the shifts with ov >= min_overlap --
-// and walks the words of s1: the s1 words are the same for every lane (a broadcast), the bits of r beside them a funnel
-// shift of two neighbouring words, of which one is carried over; two XORs, the N planes, the mask of [lo, hi) and a
-// population count per word.  The first hit wins, so the round in which a lane hits is the last one (the lowest lane of the
-// ballot), and a round's walk ends as soon as no lane can hit any more -- mism only grows --, which for unrelated mates is
-// after the first word.  r's planes have 512 bits of slack on either side, so no index is tested.  Counters are kept by
-// the wave, the histogram in LDS; both go out as one atomic per touched word and workgroup.
-constexpr unsigned OV_THREADS = 64, OV_WG_PAIRS = 64;
-constexpr unsigned OV_WORDS = FQGPU_OVERLAP_MAX_LEN / 32;  // words of a plane
-constexpr unsigned OV_R_WORDS = 3 * OV_WORDS;              // ... of a plane of r: slack, the plane, slack
-constexpr unsigned OV_HEAD = 16;                           // words in front of the rows
-static_assert(OV_THREADS == 64 && OV_WG_PAIRS == 64 && FQGPU_OVERLAP_MAX_LEN == 8 * OV_THREADS, "lane = pair, and eight bases of a line to a lane");
-static_assert(FQGPU_OVERLAP_ROWS >= 2 * FQGPU_OVERLAP_MAX_LEN && FQGPU_OVERLAP_WORDS == OV_HEAD + FQGPU_OVERLAP_ROWS, "I <= 1023 has a row");
-struct OvSide {
-  const uint8_t *raw;
-  unsigned long long raw_len;
-  const fqgpu_rec *recs;  // the first record of the range
-};
-struct OvSpec {
-  unsigned min_overlap, max_mism, max_err_pct;
-};
-struct __attribute__((packed)) OvU64 { uint32_t a, b; };  // eight bytes at any address
-struct OvBits {
-  unsigned lo, hi, n;  // eight bits each
-  bool bad;
-};
-// the planes of the bases [8 lane, 8 lane + 8) of a line of len <= 512 bases that lies inside its chunk
-__device__ __forceinline__ OvBits ov_bits(const uint8_t *__restrict__ raw, unsigned off, unsigned len, unsigned lane) {
-  OvBits b = {0u, 0u, 0u, false};
-  const unsigned p = 8u * lane;
-  if (p >= len) return b;
-  const OvU64 v = *reinterpret_cast<const OvU64 *>(raw + off + p);
-  const unsigned w[2] = {v.a, v.b}, in = sel_bits(0, (int)(len - p)) & 0xFFu;
-  unsigned fine = 0;
-#pragma unroll
-  for (int i = 0; i < 2; i++) {
-    const unsigned y = w[i] & ~SW_H;
-    const unsigned ea = sw_eq(y, 'A'), ec = sw_eq(y, 'C'), eg = sw_eq(y, 'G'), et = sw_eq(y, 'T'), en = sw_eq(y, 'N');
-    b.lo |= ((ec | et) * CLIP_GATHER) >> 28 << (4 * i);
-    b.hi |= ((eg | et) * CLIP_GATHER) >> 28 << (4 * i);
-    b.n |= (en * CLIP_GATHER) >> 28 << (4 * i);
-    fine |= (((ea | ec | eg | et | en) & ~w[i]) * CLIP_GATHER) >> 28 << (4 * i);  // one of ACGTN, and below 128
-  }
-  b.bad = (~fine & in) != 0u;
-  b.lo &= in;
-  b.hi &= in;
-  b.n &= in;
-  return b;
-}
-// the bits [lo, hi) of a word, any lo and hi
-__device__ __forceinline__ unsigned ov_mask(int lo, int hi) {
-  const unsigned below_hi = hi <= 0 ? 0u : hi >= 32 ? 0xFFFFFFFFu : (1u << hi) - 1u;
-  const unsigned below_lo = lo <= 0 ? 0u : lo >= 32 ? 0xFFFFFFFFu : (1u << lo) - 1u;
-  return below_hi & ~below_lo;
-}
-
-__global__ void __launch_bounds__(OV_THREADS)
-k_pair_overlap(const OvSide A, const OvSide B, unsigned count, const OvSpec sp, unsigned long long *__restrict__ out,
-               uint16_t *__restrict__ pairs, unsigned *__restrict__ bad_out) {
-  __shared__ unsigned s1[3][OV_WORDS];    // mate 1: the code's low bit, its high bit, N
-  __shared__ unsigned rr[3][OV_R_WORDS];  // r, the code planes inverted already; the plane is the words [OV_WORDS, 2 OV_WORDS)
-  __shared__ unsigned hist[FQGPU_OVERLAP_ROWS];
-  const unsigned lane = threadIdx.x;
-  for (unsigned i = lane; i < FQGPU_OVERLAP_ROWS; i += OV_THREADS) hist[i] = 0;
-  for (unsigned i = lane; i < 3 * OV_R_WORDS; i += OV_THREADS) (&rr[0][0])[i] = 0;
-  const unsigned long long p0 = (unsigned long long)blockIdx.x * OV_WG_PAIRS;
-  const bool have = p0 + lane < count;
-  fqgpu_rec ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
-  if (have) {
-    ra = A.recs[p0 + lane];
-    rb = B.recs[p0 + lane];
-  }
-  const bool ok = have && ra.len != 0 && ra.len <= 65535u && (unsigned long long)ra.seq_off + ra.len <= A.raw_len && rb.len != 0 &&
-                  rb.len <= 65535u && (unsigned long long)rb.seq_off + rb.len <= B.raw_len;
-  const bool analysed = ok && ra.len <= FQGPU_OVERLAP_MAX_LEN && rb.len <= FQGPU_OVERLAP_MAX_LEN;
-  bool bad = have && !ok;
-  unsigned my_limit_a = ra.len, my_limit_b = rb.len, my_insert = 0;  // the lane's pair: no hit so far
-  unsigned n_over = 0, n_through = 0, behind_a = 0, behind_b = 0, n_mism = 0, n_ov = 0;  // (the same in every lane; 64 pairs of <= 512 bases)
-  uint8_t *const s1_bytes = reinterpret_cast<uint8_t *>(&s1[0][0]);
-  uint8_t *const rr_bytes = reinterpret_cast<uint8_t *>(&rr[0][0]);
-  unsigned long long todo = __ballot(analysed);
-  while (todo) {  // (uniform)
-    const unsigned p = (unsigned)__builtin_ctzll(todo);
-    todo &= todo - 1ull;
-    const unsigned L1 = fq_uniform(__shfl(ra.len, p)), L2 = fq_uniform(__shfl(rb.len, p));
-    const unsigned off_a = fq_uniform(__shfl(ra.seq_off, p)), off_b = fq_uniform(__shfl(rb.seq_off, p));
-    const OvBits x = ov_bits(A.raw, off_a, L1, lane), y = ov_bits(B.raw, off_b, L2, lane);
-    bad = bad || x.bad || y.bad;
-    __syncthreads();  // the pair in front has been searched
-    s1_bytes[lane] = (uint8_t)x.lo;
-    s1_bytes[4 * OV_WORDS + lane] = (uint8_t)x.hi;
-    s1_bytes[8 * OV_WORDS + lane] = (uint8_t)x.n;
-    rr_bytes[4 * OV_WORDS + 63 - lane] = (uint8_t)(~__brev(y.lo) >> 24);
-    rr_bytes[4 * (OV_R_WORDS + OV_WORDS) + 63 - lane] = (uint8_t)(~__brev(y.hi) >> 24);
-    rr_bytes[4 * (2 * OV_R_WORDS + OV_WORDS) + 63 - lane] = (uint8_t)(__brev(y.n) >> 24);
-    __syncthreads();
-    const bool can = L1 >= sp.min_overlap && L2 >= sp.min_overlap;
-    const unsigned n_pos = can ? L1 - sp.min_overlap + 1u : 0u, n_cand = can ? n_pos + L2 - sp.min_overlap : 0u;
-    const unsigned words = (L1 + 31u) / 32u;
-    bool hit = false;
-    int hit_d = 0;
-    unsigned hit_mism = 0, hit_ov = 0;
-    for (unsigned c0 = 0; c0 < n_cand && !hit; c0 += OV_THREADS) {  // (uniform)
-      const unsigned c = c0 + lane;
-      const bool live = c < n_cand;
-      const int d = !live ? 0 : c < n_pos ? (int)c : -(int)(c - n_pos + 1u);
-      const int lo = max(d, 0), hi = min((int)L1, d + (int)L2);
-      const unsigned ov = (unsigned)(hi - lo), bound = min(sp.max_mism, sp.max_err_pct * ov / 100u);
-      // r[i - d] is bit i + q0 of r's planes with their slack: q0 = 512 + (512 - L2) - d, in 1 .. 1023
-      const unsigned q0 = (unsigned)(2 * (int)FQGPU_OVERLAP_MAX_LEN - (int)L2 - d), sh = q0 & 31u, qw = q0 >> 5;
-      unsigned mism = live ? 0u : 0xFFFF0000u;  // (a lane without a candidate never hits)
-      unsigned c_lo = rr[0][qw], c_hi = rr[1][qw], c_n = rr[2][qw];
-      for (unsigned w = 0; w < words; w++) {  // (uniform)
-        const unsigned n_lo = rr[0][qw + w + 1u], n_hi = rr[1][qw + w + 1u], n_n = rr[2][qw + w + 1u];
-        const unsigned r_lo = __builtin_amdgcn_alignbit(n_lo, c_lo, sh), r_hi = __builtin_amdgcn_alignbit(n_hi, c_hi, sh),
-                       r_n = __builtin_amdgcn_alignbit(n_n, c_n, sh);
-        const unsigned differ = ((s1[0][w] ^ r_lo) | (s1[1][w] ^ r_hi) | s1[2][w] | r_n) & ov_mask(lo - 32 * (int)w, hi - 32 * (int)w);
-        mism += (unsigned)__popc(differ);
-        c_lo = n_lo;
-        c_hi = n_hi;
-        c_n = n_n;
-        if (!__any(mism <= bound)) break;  // (mism only grows)
-      }
-      const unsigned long long hits = __ballot(live && mism <= bound);
-      if (hits) {  // (uniform) the round's candidates rise with its lanes
-        const int first = __builtin_ctzll(hits);
-        hit = true;
-        hit_d = __shfl(d, first);
-        hit_mism = __shfl(mism, first);
-        hit_ov = __shfl(ov, first);
-      }
-    }
-    if (hit) {
-      const unsigned I = (unsigned)(hit_d + (int)L2), limit_a = min(L1, I), limit_b = min(L2, I);
-      n_over++;
-      n_through += limit_a < L1 || limit_b < L2;
-      behind_a += L1 - limit_a;
-      behind_b += L2 - limit_b;
-      n_mism += hit_mism;
-      n_ov += hit_ov;
-      if (lane == p) {
-        my_limit_a = limit_a;
-        my_limit_b = limit_b;
-        my_insert = I;
-      }
-      if (lane == 0) atomicAdd(&hist[I], 1u);  // (I <= L1 - min_overlap + L2 <= 1023)
-    }
-  }
-  __syncthreads();
-  for (unsigned i = lane; i < FQGPU_OVERLAP_ROWS; i += OV_THREADS)
-    if (const unsigned v = hist[i]) atomicAdd(&out[OV_HEAD + i], (unsigned long long)v);
-  const unsigned skipped = (unsigned)__popcll(__ballot(ok && !analysed));
-  const unsigned cnt[8] = {0u, n_over, n_through, behind_a, behind_b, skipped, n_mism, n_ov};
-#pragma unroll
-  for (unsigned i = 1; i < 8; i++)
-    if (lane == i && cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
-  if (have) {
-    pairs[p0 + lane] = (uint16_t)my_limit_a;
-    pairs[(unsigned long long)count + p0 + lane] = (uint16_t)my_limit_b;
-    pairs[2ull * count + p0 + lane] = (uint16_t)my_insert;
-  }
-  if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
-}
-
-// ---- the correction inside the mate overlap (include/fqgpu.h, fqgpu_chunk_pair_correct): THE kernel that changes a chunk.
-// k_pair_overlap's shape -- a wave takes 64 consecutive pairs, table entries and inserts with one load, lane = pair, the
-// per-pair results back in the pair's lane -- but no LDS: the wave walks the pairs that have an insert one after the other,
-// and a lane takes the eight places [lo + 8 lane, lo + 8 lane + 8) of the overlap.  The bytes of s1 and q1 are one eight-byte
-// load from wherever the place lies; those of s2 and q2 are the eight bytes that END at j = I - 1 - i, taken in reverse.
-// That window starts up to seven bytes in front of j's line -- bytes of a place behind hi, which is not judged -- and for a
-// chunk's first record in front of the chunk: its start is clamped to the chunk's first byte and the word shifted up by what
-// was clamped.  Reads behind a line's end fall into the chunk or its 64 spare bytes.  A place is decided from its own four
-// bytes, and no byte belongs to two places, so the launch with APPLY = false (it judges, counts and stores nothing into the
-// chunks) and the launch with APPLY = true (it stores, and counts nothing) decide alike, and the second one runs only when
-// the first refused nothing.  A store goes to s1[i], q1[i], i in [lo, hi), or s2[j], q2[j], j in [0, L2): inside lines that
-// the lane = pair check found inside their chunks.  Corrections are rare: plain byte stores under the lane's predicate.
-struct CorSide {
-  uint8_t *raw;
-  unsigned long long raw_len;
-  const fqgpu_rec *recs;  // the first record of the range
-};
-__device__ __forceinline__ unsigned long long cor_load8(const uint8_t *p) {
-  const OvU64 v = *reinterpret_cast<const OvU64 *>(p);
-  return (unsigned long long)v.b << 32 | v.a;
-}
-// the eight bytes of a chunk at off + rel (rel >= -7, off + rel + 8 > 0); the bytes in front of the chunk read as zero
-__device__ __forceinline__ unsigned long long cor_load8_back(const uint8_t *raw, unsigned off, int rel) {
-  const long long at = (long long)off + rel;
-  const unsigned clamped = at < 0 ? (unsigned)-at : 0u;
-  return cor_load8(raw + (at + clamped)) << (8u * clamped);
-}
-__device__ __forceinline__ unsigned cor_comp(unsigned b) { return b == 'A' ? 'T' : b == 'T' ? 'A' : b == 'C' ? 'G' : b == 'G' ? 'C' : b; }
-__device__ __forceinline__ bool cor_is_base(unsigned b) { return b == 'A' || b == 'C' || b == 'G' || b == 'T' || b == 'N'; }
-__device__ __forceinline__ unsigned cor_wave_sum(unsigned v) {
-#pragma unroll
-  for (int m = 32; m; m >>= 1) v += __shfl_xor(v, m);
-  return v;
-}
-
-template <bool APPLY>
-__global__ void __launch_bounds__(OV_THREADS)
-k_pair_correct(const CorSide A, const CorSide B, unsigned count, const uint16_t *__restrict__ inserts, unsigned good_q, unsigned bad_q,
-               unsigned long long *__restrict__ out, uint16_t *__restrict__ fixed, unsigned *__restrict__ bad_out) {
-  const unsigned lane = threadIdx.x;
-  const unsigned long long p0 = (unsigned long long)blockIdx.x * OV_WG_PAIRS;
-  const bool have = p0 + lane < count;
-  fqgpu_rec ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
-  unsigned ins = 0;
-  if (have) ins = inserts[p0 + lane];
-  if (ins) {  // (a pair without an insert: none of its lines, and not its table entries either)
-    ra = A.recs[p0 + lane];
-    rb = B.recs[p0 + lane];
-  }
-  const auto inside = [](const fqgpu_rec &r, unsigned long long raw_len) {
-    return r.len != 0 && r.len <= FQGPU_OVERLAP_MAX_LEN && (unsigned long long)r.seq_off + r.len <= raw_len &&
-           (unsigned long long)r.qual_off + r.len <= raw_len;
-  };
-  const bool ok = ins && inside(ra, A.raw_len) && inside(rb, B.raw_len) && ins <= ra.len + rb.len - 1u;
-  bool bad = ins && !ok;
-  unsigned my_fixed_a = 0, my_fixed_b = 0;                            // the lane's pair
-  unsigned n_fa = 0, n_fb = 0, n_res = 0, n_mism = 0;                 // the lane's places, over all pairs
-  unsigned n_pairs_fixed = 0, n_ov = 0;                               // (the same in every lane)
-  unsigned long long todo = __ballot(ok);
-  while (todo) {  // (uniform)
-    const unsigned p = (unsigned)__builtin_ctzll(todo);
-    todo &= todo - 1ull;
-    const unsigned L1 = fq_uniform(__shfl(ra.len, p)), L2 = fq_uniform(__shfl(rb.len, p)), I = fq_uniform(__shfl(ins, p));
-    const unsigned s1_off = fq_uniform(__shfl(ra.seq_off, p)), q1_off = fq_uniform(__shfl(ra.qual_off, p));
-    const unsigned s2_off = fq_uniform(__shfl(rb.seq_off, p)), q2_off = fq_uniform(__shfl(rb.qual_off, p));
-    const unsigned lo = I > L2 ? I - L2 : 0u, hi = min(L1, I);  // hi - lo >= 1, and <= 512
-    n_ov += hi - lo;
-    const unsigned i0 = lo + 8u * lane;
-    unsigned fa = 0, fb = 0;
-    if (i0 < hi) {
-      const unsigned n = min(8u, hi - i0);
-      const int j0 = (int)I - 1 - (int)i0 - 7;  // the window [j0, j0 + 8) of mate 2: place i0 + t stands beside j0 + 7 - t
-      const unsigned long long s1 = cor_load8(A.raw + s1_off + i0), q1 = cor_load8(A.raw + q1_off + i0);
-      const unsigned long long s2 = cor_load8_back(B.raw, s2_off, j0), q2 = cor_load8_back(B.raw, q2_off, j0);
-#pragma unroll
-      for (unsigned t = 0; t < 8; t++) {
-        const unsigned b1 = (unsigned)(s1 >> (8u * t)) & 0xFFu, c1 = (unsigned)(q1 >> (8u * t)) & 0xFFu;
-        const unsigned b2 = (unsigned)(s2 >> (8u * (7u - t))) & 0xFFu, c2 = (unsigned)(q2 >> (8u * (7u - t))) & 0xFFu;
-        const bool in = t < n;
-        bad = bad || (in && !(cor_is_base(b1) && cor_is_base(b2) && c1 >= 33u && c1 <= 96u && c2 >= 33u && c2 <= 96u));
-        const unsigned p1 = c1 - 33u, p2 = c2 - 33u;
-        const bool differ = in && (b1 == 'N' || b2 == 'N' || b1 != cor_comp(b2));
-        const bool win1 = differ && b1 != 'N' && p1 >= good_q && p2 <= bad_q;
-        const bool win2 = differ && b2 != 'N' && p2 >= good_q && p1 <= bad_q;
-        n_mism += differ;
-        fb += win1;
-        fa += win2;
-        n_res += (win1 && b2 == 'N') || (win2 && b1 == 'N');
-        if (APPLY) {
-          const unsigned j = (unsigned)(j0 + 7 - (int)t);  // (in [0, L2) for a place of the overlap)
-          if (win1) {
-            B.raw[s2_off + j] = (uint8_t)cor_comp(b1);
-            B.raw[q2_off + j] = (uint8_t)c1;
-          }
-          if (win2) {
-            A.raw[s1_off + i0 + t] = (uint8_t)cor_comp(b2);
-            A.raw[q1_off + i0 + t] = (uint8_t)c2;
-          }
-        }
-      }
-    }
-    if (!APPLY && __any(fa | fb)) {  // (uniform, and rare)
-      const unsigned pa = cor_wave_sum(fa), pb = cor_wave_sum(fb);
-      n_pairs_fixed++;
-      if (lane == p) {
-        my_fixed_a = pa;
-        my_fixed_b = pb;
-      }
-    }
-    n_fa += fa;
-    n_fb += fb;
-  }
-  if (APPLY) return;
-  const unsigned cnt[8] = {0u, (unsigned)__popcll(__ballot(ins != 0u)), n_pairs_fixed, cor_wave_sum(n_fa), cor_wave_sum(n_fb),
-                           cor_wave_sum(n_res), cor_wave_sum(n_mism), n_ov};
-#pragma unroll
-  for (unsigned i = 1; i < 8; i++)
-    if (lane == i && cnt[i]) atomicAdd(&out[i], (unsigned long long)cnt[i]);
-  if (have) {
-    fixed[p0 + lane] = (uint16_t)my_fixed_a;
-    fixed[(unsigned long long)count + p0 + lane] = (uint16_t)my_fixed_b;
-  }
-  if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
-}
-
 }  // namespace
 
 void SelectScratch::release_host() {
@@ -1872,135 +1428,133 @@ void SelectScratch::release_host() {
   host = nullptr;
 }
 
-// The reads of the chunk raw_dev[0, raw_len) with the record table recs_dev, clipped at the adapter *a (nullptr: none; with
-// one, t is a trim), trimmed by *t (nullptr: the filter alone) and then judged by *f, on st, waited for.  Two waits: the judge's result words decide what is gathered and how much room it
-// needs; the gathered bytes come down in one copy.  FQGPU_E_ARG with *out_len = 0 and report, keep bits and windows zeroed: a
-// byte that cannot be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
-// x (nullptr: none; with one, t is a trim): the tail trims between the clip and the trim, k_tail_find in front of the judge;
-// the report then has FQGPU_TAIL_REPORT_WORDS words, and places_out (nullptr, or 4 uint16_t per record) receives a0, a1, e, e2.
-// m (nullptr: none; with one, t is a trim and the report a tail's): recs_dev is a range of the chunk's table -- m->prev: not
-// its front -- and m->mark (nullptr: none) the range's mark, k_select_mark behind the judge; word 20 is counted.  m->limit
-// (nullptr: none): the range's limits, k_select_limit behind the adapter search; words 21 / 22 are counted.
-int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                    const fqgpu_adapter *a, const fqgpu_trim *t, const fqgpu_filter *f, uint8_t *out, size_t out_cap, size_t *out_len,
-                    uint64_t *report, uint8_t *keep_out, uint32_t *win_out, const fqgpu_tail *x, uint16_t *places_out, const FqSelectMark *m) {
-  const unsigned words = x || m ? FQGPU_TAIL_REPORT_WORDS : FQGPU_TRIM_REPORT_WORDS;
-  *out_len = 0;
-  for (unsigned i = 0; i < words; i++) report[i] = 0;
-  if (n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  if ((a || x || m) && !t) return FQGPU_E_ARG;
+int SelectScratch::begin(hipStream_t st) {
+  if (const int rc = res.reserve(sizeof(SelectResult))) return rc;
+  if (!host) FQ_HIP(hipHostMalloc(&host, sizeof(SelectResult), hipHostMallocPortable));
+  FQ_HIP(hipMemsetAsync(res.p, 0, sizeof(SelectResult), st));
+  return FQGPU_OK;
+}
+
+int SelectScratch::finish(hipStream_t st, const SelectResult *&result) {
+  FQ_HIP(hipMemcpyAsync(host, res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
+  result = static_cast<const SelectResult *>(host);
+  return FQGPU_OK;
+}
+
+// The selection of a normalised job (fqgpu_internal.h) over the records of v, on st, waited for.  Two waits: the judge's
+// result words decide what is gathered and how much room it needs; the gathered bytes come down in one copy.  FQGPU_E_ARG
+// with *out_len and the report as the front left them -- zero -- and keep bits, windows and places zeroed: a byte that cannot
+// be judged, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
+int fq_select_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, const FqSelectJob &job, const FqSelectOut &o) {
+  const size_t n_recs = v.n_recs;
+  if (n_recs >= ((size_t)1 << 32) || v.raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
   if (!n_recs) return FQGPU_OK;
-  if (!t) win_out = nullptr;  // (a filter has no windows)
-  if (!x) places_out = nullptr;
   SelectScratch &ss = ctx->select;
-  const char *const span = m ? "select_marked" : x ? "tailtrim" : a ? "clip" : t ? "trim" : "filter";
-  const uint8_t *const mark = m ? m->mark : nullptr;
-  const uint16_t *const limit = m ? m->limit : nullptr;
-  const bool clipped = a || limit;  // clip[r] stands in front of the trim's steps
+  const fqgpu_adapter *const a = job.adapter;
+  const fqgpu_tail *const x = job.tail;
+  const fqgpu_trim *const t = job.trim;
+  const bool clipped = a || job.limit;  // clip[r] stands in front of the trim's steps
   const unsigned R = (unsigned)n_recs;
+  const unsigned long long raw_len = v.raw_len;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS;
   int rc;
   if ((rc = ss.ksize.reserve(n_recs * 4)) || (rc = ss.hstart.reserve(n_recs * 4)) || (t && (rc = ss.win.reserve(n_recs * 4))) ||
-      (clipped && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) || (mark && (rc = ss.mark.reserve(n_waves * 8))) ||
-      (limit && (rc = ss.limit.reserve(n_recs * 2))) ||
-      (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.res.reserve(sizeof(SelectResult))))
+      (clipped && (rc = ss.clip.reserve(n_recs * 2))) || (x && (rc = ss.places.reserve(n_recs * 8))) ||
+      (job.mark && (rc = ss.mark.reserve(n_waves * 8))) || (job.limit && (rc = ss.limit.reserve(n_recs * 2))) ||
+      (rc = ss.keep.reserve(n_waves * 8)) || (rc = ss.koff.reserve((n_recs + 1) * 8)) || (rc = ss.begin(st)))
     return rc;
-  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
-  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
   uint32_t *const win = t ? ss.win.as<uint32_t>() : nullptr;
-  FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
-  if (mark) {  // (its last word padded with zeros)
+  uint16_t *const clip = clipped ? ss.clip.as<uint16_t>() : nullptr;
+  uint2 *const places = x ? ss.places.as<uint2>() : nullptr;
+  SelectResult *const dev = ss.res.as<SelectResult>();
+  if (job.mark) {  // (its last word padded with zeros)
     FQ_HIP(hipMemsetAsync(ss.mark.p, 0, n_waves * 8, st));
-    FQ_HIP(hipMemcpyAsync(ss.mark.p, mark, (n_recs + 7) / 8, hipMemcpyHostToDevice, st));
+    FQ_HIP(hipMemcpyAsync(ss.mark.p, job.mark, (n_recs + 7) / 8, hipMemcpyHostToDevice, st));
   }
-  if (limit) FQ_HIP(hipMemcpyAsync(ss.limit.p, limit, n_recs * 2, hipMemcpyHostToDevice, st));
-  fq_timer_span_begin(ctx, span, st);
+  if (job.limit) FQ_HIP(hipMemcpyAsync(ss.limit.p, job.limit, n_recs * 2, hipMemcpyHostToDevice, st));
+  fq_timer_span_begin(ctx, job.span, st);
   const dim3 judge_grid((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64)));
   if (a) {  // the adapter's bit planes: bit j of a plane is set iff A[j] is that base
     unsigned long long plane[4] = {0, 0, 0, 0};
     for (unsigned j = 0; j < a->len; j++) plane[a->seq[j] == 'A' ? 0 : a->seq[j] == 'C' ? 1 : a->seq[j] == 'G' ? 2 : 3] |= 1ull << j;
-    const FindOne one = {plane[0], plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, ss.clip.as<uint16_t>()};
-    hipLaunchKernelGGL(k_adapter_find<false>, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, one,
-                       ss.res.as<SelectResult>());
+    const FindOne one = {plane[0], plane[1], plane[2], plane[3], a->len, a->min_overlap, a->max_err_pct, clip};
+    hipLaunchKernelGGL(k_adapter_find<false>, judge_grid, dim3(SEL_THREADS), 0, st, v.raw, raw_len, v.recs, R, one, dev);
     FQ_HIP(hipGetLastError());
   }
-  if (limit) {
-    hipLaunchKernelGGL(k_select_limit, dim3((unsigned)((n_recs + SEL_THREADS - 1) / SEL_THREADS)), dim3(SEL_THREADS), 0, st, recs_dev, R,
-                       ss.limit.as<uint16_t>(), ss.clip.as<uint16_t>(), a ? 1u : 0u, ss.res.as<SelectResult>());
+  if (job.limit) {
+    hipLaunchKernelGGL(k_select_limit, dim3((unsigned)((n_recs + SEL_THREADS - 1) / SEL_THREADS)), dim3(SEL_THREADS), 0, st, v.recs, R,
+                       ss.limit.as<uint16_t>(), clip, a ? 1u : 0u, dev);
     FQ_HIP(hipGetLastError());
   }
   if (x) {
-    hipLaunchKernelGGL(k_tail_find, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, *x, *t,
-                       clipped ? ss.clip.as<uint16_t>() : nullptr, ss.places.as<uint2>(), ss.res.as<SelectResult>());
+    hipLaunchKernelGGL(k_tail_find, judge_grid, dim3(SEL_THREADS), 0, st, v.raw, raw_len, v.recs, R, *x, *t, clip, places, dev);
     FQ_HIP(hipGetLastError());
   }
   const auto judge = x ? &k_select_judge<true, SEL_TAIL> : clipped ? &k_select_judge<true, SEL_CLIP> : t ? &k_select_judge<true> : &k_select_judge<false>;
   const auto gather = t ? &k_select_gather<true> : &k_select_gather<false>;
-  hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, raw_dev, (unsigned long long)raw_len, recs_dev, R, t ? *t : fqgpu_trim{}, *f,
-                     ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>(),
-                     clipped ? ss.clip.as<uint16_t>() : nullptr, x ? ss.places.as<uint2>() : nullptr, m && m->prev ? 1u : 0u);
+  hipLaunchKernelGGL(judge, judge_grid, dim3(SEL_THREADS), 0, st, v.raw, raw_len, v.recs, R, t ? *t : fqgpu_trim{}, *job.filter,
+                     ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), win, ss.keep.as<unsigned long long>(), dev, clip, places,
+                     v.prev ? 1u : 0u);
   FQ_HIP(hipGetLastError());
-  if (mark) {
+  if (job.mark) {
     hipLaunchKernelGGL(k_select_mark, judge_grid, dim3(SEL_THREADS), 0, st, ss.mark.as<unsigned long long>(), R, ss.ksize.as<uint32_t>(), win,
-                       ss.keep.as<unsigned long long>(), ss.res.as<SelectResult>());
+                       ss.keep.as<unsigned long long>(), dev);
     FQ_HIP(hipGetLastError());
   }
-  if (out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
+  if (o.out && (rc = fq_scan_u32_to_u64(st, ss.ksize.as<uint32_t>(), n_recs, ss.koff.as<unsigned long long>(), ss.scan_tmp))) {
     fq_timer_span_end(ctx, st);
     return rc;
   }
   fq_timer_span_end(ctx, st);
-  FQ_HIP(hipMemcpyAsync(ss.host, ss.res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
-  if (keep_out) FQ_HIP(hipMemcpyAsync(keep_out, ss.keep.p, (n_recs + 7) / 8, hipMemcpyDeviceToHost, st));
-  if (win_out) FQ_HIP(hipMemcpyAsync(win_out, win, n_recs * 4, hipMemcpyDeviceToHost, st));
-  if (places_out) FQ_HIP(hipMemcpyAsync(places_out, ss.places.p, n_recs * 8, hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  if (res.bad) {
-    if (keep_out) memset(keep_out, 0, (n_recs + 7) / 8);
-    if (win_out) memset(win_out, 0, n_recs * 4);
-    if (places_out) memset(places_out, 0, n_recs * 8);
+  if (o.keep) FQ_HIP(hipMemcpyAsync(o.keep, ss.keep.p, (n_recs + 7) / 8, hipMemcpyDeviceToHost, st));
+  if (o.win) FQ_HIP(hipMemcpyAsync(o.win, win, n_recs * 4, hipMemcpyDeviceToHost, st));
+  if (o.places) FQ_HIP(hipMemcpyAsync(o.places, places, n_recs * 8, hipMemcpyDeviceToHost, st));
+  const SelectResult *res;
+  if ((rc = ss.finish(st, res))) return rc;
+  if (res->bad) {
+    if (o.keep) memset(o.keep, 0, (n_recs + 7) / 8);
+    if (o.win) memset(o.win, 0, n_recs * 4);
+    if (o.places) memset(o.places, 0, n_recs * 8);
     return FQGPU_E_ARG;
   }
-  for (unsigned i = 1; i < words; i++) report[i] = res.w[i];
-  report[0] = n_recs;
-  const size_t total = (size_t)res.w[R_BYTES_KEPT];
-  *out_len = total;
-  if (!out || !total) return FQGPU_OK;
-  if (out_cap < total) return FQGPU_E_OVERFLOW;
+  for (unsigned i = 1; i < o.report_words; i++) o.report[i] = res->w[i];
+  o.report[0] = n_recs;
+  const size_t total = (size_t)res->w[R_BYTES_KEPT];
+  *o.out_len = total;
+  if (!o.out || !total) return FQGPU_OK;
+  if (o.out_cap < total) return FQGPU_E_OVERFLOW;
   if ((rc = ss.dst.reserve(total + 64))) return rc;
-  fq_timer_span_begin(ctx, span, st);
-  if (t || !res.not_bare)
-    hipLaunchKernelGGL(gather, dim3((unsigned)((total + SEL_TILE_BYTES - 1) / SEL_TILE_BYTES)), dim3(SEL_GATHER_THREADS), 0, st, raw_dev,
-                       recs_dev, ss.hstart.as<uint32_t>(), win, ss.koff.as<unsigned long long>(), R, (unsigned long long)total,
-                       res.not_bare == 0u, ss.dst.as<uint8_t>());
+  // the second phase: the gather, then one copy down
+  fq_timer_span_begin(ctx, job.span, st);
+  if (t || !res->not_bare)
+    hipLaunchKernelGGL(gather, dim3((unsigned)((total + SEL_TILE_BYTES - 1) / SEL_TILE_BYTES)), dim3(SEL_GATHER_THREADS), 0, st, v.raw, v.recs,
+                       ss.hstart.as<uint32_t>(), win, ss.koff.as<unsigned long long>(), R, (unsigned long long)total, res->not_bare == 0u,
+                       ss.dst.as<uint8_t>());
   else
-    hipLaunchKernelGGL(k_select_gather_records, dim3((unsigned)min((n_recs + 3) / 4, (size_t)8192)), dim3(256), 0, st, raw_dev, recs_dev, R,
+    hipLaunchKernelGGL(k_select_gather_records, dim3((unsigned)min((n_recs + 3) / 4, (size_t)8192)), dim3(256), 0, st, v.raw, v.recs, R,
                        ss.ksize.as<uint32_t>(), ss.hstart.as<uint32_t>(), ss.koff.as<unsigned long long>(), ss.dst.as<uint8_t>());
   fq_timer_span_end(ctx, st);
   FQ_HIP(hipGetLastError());
-  FQ_HIP(hipMemcpyAsync(out, ss.dst.p, total, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipMemcpyAsync(o.out, ss.dst.p, total, hipMemcpyDeviceToHost, st));
   FQ_HIP(hipStreamSynchronize(st));
   return FQGPU_OK;
 }
 
-// Adapter content of the chunk raw_dev[0, raw_len) with the record table recs_dev, on st, waited for: out[0,
-// fqgpu_probe_words(p->n, P)) and -- places_out != nullptr -- p->n places per record.  One kernel, k_adapter_find's probe
-// form, and one wait.  FQGPU_E_ARG with out and places_out zeroed: a sequence byte outside ACGTN, a record that is not inside
-// the chunk, has no symbol or more than a readlen_t counts.
-int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                   const fqgpu_probes *p, unsigned P, uint64_t *out, uint16_t *places_out) {
+// Adapter content of the records of v, on st, waited for: out[0, fqgpu_probe_words(p->n, P)) and -- places_out != nullptr --
+// p->n places per record.  One kernel, k_adapter_find's probe form, and one wait.  FQGPU_E_ARG with out and places_out zeroed:
+// a sequence byte outside ACGTN, a record that is not inside the chunk, has no symbol or more than a readlen_t counts.
+int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, const fqgpu_probes *p, unsigned P, uint64_t *out,
+                   uint16_t *places_out) {
   const unsigned n = p->n;
-  const size_t words = fqgpu_probe_words(n, P);
-  if (!words || n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
+  const size_t words = fqgpu_probe_words(n, P), n_recs = v.n_recs;
+  if (!words || n_recs >= ((size_t)1 << 32) || v.raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
   for (size_t i = 0; i < words; i++) out[i] = 0;
   SelectScratch &ss = ctx->select;
   const size_t n_waves = (n_recs + SEL_WAVE_RECORDS - 1) / SEL_WAVE_RECORDS, places_bytes = n_recs * n * sizeof(uint16_t);
   int rc;
-  if ((rc = ss.probe_out.reserve(words * 8)) || (places_out && n_recs && (rc = ss.probe_places.reserve(places_bytes))) ||
-      (rc = ss.res.reserve(sizeof(SelectResult))))
+  if ((rc = ss.probe_out.reserve(words * 8)) || (places_out && n_recs && (rc = ss.probe_places.reserve(places_bytes))) || (rc = ss.begin(st)))
     return rc;
-  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
-  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
   FindMany many = {};
   for (unsigned k = 0; k < n; k++) {  // the probes' bit planes: bit j of a plane is set iff A[j] is that base
     const fqgpu_adapter &a = p->probe[k];
@@ -2015,19 +1569,18 @@ int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
   many.out = ss.probe_out.as<unsigned long long>();
   many.places = places_out && n_recs ? ss.probe_places.as<uint16_t>() : nullptr;
   FQ_HIP(hipMemsetAsync(ss.probe_out.p, 0, words * 8, st));
-  FQ_HIP(hipMemsetAsync(ss.res.p, 0, sizeof(SelectResult), st));
   if (n_recs) {
     fq_timer_span_begin(ctx, "probe", st);
     hipLaunchKernelGGL(k_adapter_find<true>, dim3((unsigned)((n_waves + SEL_THREADS / 64 - 1) / (SEL_THREADS / 64))), dim3(SEL_THREADS), 0, st,
-                       raw_dev, (unsigned long long)raw_len, recs_dev, (unsigned)n_recs, many, ss.res.as<SelectResult>());
+                       v.raw, (unsigned long long)v.raw_len, v.recs, (unsigned)n_recs, many, ss.res.as<SelectResult>());
     fq_timer_span_end(ctx, st);
     FQ_HIP(hipGetLastError());
   }
-  FQ_HIP(hipMemcpyAsync(ss.host, ss.res.p, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
   FQ_HIP(hipMemcpyAsync(out, ss.probe_out.p, words * 8, hipMemcpyDeviceToHost, st));
   if (many.places) FQ_HIP(hipMemcpyAsync(places_out, ss.probe_places.p, places_bytes, hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  if (res.bad) {
+  const SelectResult *res;
+  if ((rc = ss.finish(st, res))) return rc;
+  if (res->bad) {
     for (size_t i = 0; i < words; i++) out[i] = 0;
     if (many.places) memset(places_out, 0, places_bytes);
     return FQGPU_E_ARG;
@@ -2036,118 +1589,5 @@ int fq_probe_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_
   out[2] = n;
   out[3] = P;
   out[4] = fq_probes_fingerprint(p);
-  return FQGPU_OK;
-}
-
-// The read ids of `count` records of two chunks on one device compared, on st (both chunks are at rest), waited for:
-// *mismatch = the first pair that differs, or (size_t)-1.  One kernel, one wait; the result word and its landing place are
-// ctx's selection result.  FQGPU_E_ARG: a record whose header line does not lie inside its chunk.
-int fq_pair_names(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, bool prev_a,
-                  const uint8_t *raw_b, size_t raw_len_b, const fqgpu_rec *recs_b, bool prev_b, size_t count, size_t *mismatch) {
-  *mismatch = (size_t)-1;
-  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  SelectScratch &ss = ctx->select;
-  if (const int rc = ss.res.reserve(sizeof(SelectResult))) return rc;
-  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
-  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
-  SelectResult *const dev = ss.res.as<SelectResult>();
-  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
-  FQ_HIP(hipMemsetAsync(dev, 0xFF, sizeof(unsigned long long), st));  // word 0: no pair so far
-  const PairSide A = {raw_a, (unsigned long long)raw_len_a, recs_a, prev_a ? 1u : 0u}, B = {raw_b, (unsigned long long)raw_len_b, recs_b, prev_b ? 1u : 0u};
-  const size_t per_wg = PAIR_THREADS / SEL_GROUP_LANES;
-  fq_timer_span_begin(ctx, "pair_names", st);
-  hipLaunchKernelGGL(k_pair_names, dim3((unsigned)((count + per_wg - 1) / per_wg)), dim3(PAIR_THREADS), 0, st, A, B, (unsigned)count, &dev->w[0],
-                     &dev->bad);
-  fq_timer_span_end(ctx, st);
-  FQ_HIP(hipGetLastError());
-  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  if (res.bad) return FQGPU_E_ARG;
-  *mismatch = res.w[0] == ~0ull ? (size_t)-1 : (size_t)res.w[0];
-  return FQGPU_OK;
-}
-
-// The mate overlap of `count` records of two chunks on one device, on st (both chunks are at rest), waited for.  One kernel,
-// one wait: the result words, the three arrays and the verdict come down behind it.  FQGPU_E_ARG zeroes out; the three arrays
-// are then the caller's to zero.
-int fq_pair_overlap(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, const uint8_t *raw_b,
-                    size_t raw_len_b, const fqgpu_rec *recs_b, size_t count, const fqgpu_overlap *o, uint64_t *out, uint16_t *limit_a_out,
-                    uint16_t *limit_b_out, uint16_t *insert_out) {
-  memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
-  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  SelectScratch &ss = ctx->select;
-  int rc;
-  if ((rc = ss.overlap_out.reserve(FQGPU_OVERLAP_WORDS * 8)) || (rc = ss.overlap_pairs.reserve(count * 6)) || (rc = ss.res.reserve(sizeof(SelectResult))))
-    return rc;
-  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
-  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
-  SelectResult *const dev = ss.res.as<SelectResult>();
-  uint16_t *const pairs = ss.overlap_pairs.as<uint16_t>();
-  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
-  FQ_HIP(hipMemsetAsync(ss.overlap_out.p, 0, FQGPU_OVERLAP_WORDS * 8, st));
-  const OvSide A = {raw_a, (unsigned long long)raw_len_a, recs_a}, B = {raw_b, (unsigned long long)raw_len_b, recs_b};
-  const OvSpec sp = {o->min_overlap, o->max_mism, o->max_err_pct};
-  fq_timer_span_begin(ctx, "pair_overlap", st);
-  hipLaunchKernelGGL(k_pair_overlap, dim3((unsigned)((count + OV_WG_PAIRS - 1) / OV_WG_PAIRS)), dim3(OV_THREADS), 0, st, A, B, (unsigned)count, sp,
-                     ss.overlap_out.as<unsigned long long>(), pairs, &dev->bad);
-  fq_timer_span_end(ctx, st);
-  FQ_HIP(hipGetLastError());
-  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipMemcpyAsync(out, ss.overlap_out.p, FQGPU_OVERLAP_WORDS * 8, hipMemcpyDeviceToHost, st));
-  if (limit_a_out) FQ_HIP(hipMemcpyAsync(limit_a_out, pairs, count * 2, hipMemcpyDeviceToHost, st));
-  if (limit_b_out) FQ_HIP(hipMemcpyAsync(limit_b_out, pairs + count, count * 2, hipMemcpyDeviceToHost, st));
-  if (insert_out) FQ_HIP(hipMemcpyAsync(insert_out, pairs + 2 * count, count * 2, hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  if (res.bad) {  // (the caller zeroes the three arrays)
-    memset(out, 0, FQGPU_OVERLAP_WORDS * sizeof(uint64_t));
-    return FQGPU_E_ARG;
-  }
-  out[0] = count;
-  out[8] = fq_overlap_fingerprint(o);
-  return FQGPU_OK;
-}
-
-// The correction inside the mate overlap of `count` records of two DIFFERENT chunks on one device, on st (both chunks are at
-// rest), waited for.  The same kernel twice: the first launch judges and counts and leaves the chunks alone; its result words,
-// the two arrays and the verdict come down behind it, and only when nothing was refused and a base is to change does the
-// second launch store -- so FQGPU_E_ARG leaves both chunks as they were.  The inserts go up as a limited call's limits do.
-// FQGPU_E_ARG zeroes report; the two arrays are then the caller's to zero.
-int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, uint8_t *raw_a, size_t raw_len_a, const fqgpu_rec *recs_a, uint8_t *raw_b, size_t raw_len_b,
-                    const fqgpu_rec *recs_b, size_t count, const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report,
-                    uint16_t *fixed_a_out, uint16_t *fixed_b_out) {
-  memset(report, 0, FQGPU_CORRECT_REPORT_WORDS * sizeof(uint64_t));
-  if (!count || count >= ((size_t)1 << 32) || raw_len_a >= ((size_t)1 << 32) || raw_len_b >= ((size_t)1 << 32)) return FQGPU_E_ARG;
-  SelectScratch &ss = ctx->select;
-  int rc;
-  if ((rc = ss.correct_in.reserve(count * 2)) || (rc = ss.correct_fixed.reserve(count * 4)) || (rc = ss.res.reserve(sizeof(SelectResult)))) return rc;
-  if (!ss.host) FQ_HIP(hipHostMalloc(&ss.host, sizeof(SelectResult), hipHostMallocPortable));
-  const SelectResult &res = *static_cast<const SelectResult *>(ss.host);
-  SelectResult *const dev = ss.res.as<SelectResult>();
-  uint16_t *const fixed = ss.correct_fixed.as<uint16_t>();
-  FQ_HIP(hipMemsetAsync(dev, 0, sizeof(SelectResult), st));
-  FQ_HIP(hipMemcpyAsync(ss.correct_in.p, insert_in, count * 2, hipMemcpyHostToDevice, st));
-  const CorSide A = {raw_a, (unsigned long long)raw_len_a, recs_a}, B = {raw_b, (unsigned long long)raw_len_b, recs_b};
-  const dim3 grid((unsigned)((count + OV_WG_PAIRS - 1) / OV_WG_PAIRS));
-  static_assert(FQGPU_CORRECT_REPORT_WORDS <= FQGPU_TAIL_REPORT_WORDS, "the counters are the selection result's words");
-  fq_timer_span_begin(ctx, "pair_correct", st);
-  hipLaunchKernelGGL(k_pair_correct<false>, grid, dim3(OV_THREADS), 0, st, A, B, (unsigned)count, ss.correct_in.as<uint16_t>(), c->good_q, c->bad_q,
-                     &dev->w[0], fixed, &dev->bad);
-  fq_timer_span_end(ctx, st);
-  FQ_HIP(hipGetLastError());
-  FQ_HIP(hipMemcpyAsync(ss.host, dev, sizeof(SelectResult), hipMemcpyDeviceToHost, st));
-  if (fixed_a_out) FQ_HIP(hipMemcpyAsync(fixed_a_out, fixed, count * 2, hipMemcpyDeviceToHost, st));
-  if (fixed_b_out) FQ_HIP(hipMemcpyAsync(fixed_b_out, fixed + count, count * 2, hipMemcpyDeviceToHost, st));
-  FQ_HIP(hipStreamSynchronize(st));
-  if (res.bad) return FQGPU_E_ARG;  // (the caller zeroes the two arrays)
-  for (unsigned i = 1; i < FQGPU_CORRECT_REPORT_WORDS; i++) report[i] = res.w[i];
-  report[0] = count;
-  if (report[3] + report[4]) {
-    fq_timer_span_begin(ctx, "pair_correct", st);
-    hipLaunchKernelGGL(k_pair_correct<true>, grid, dim3(OV_THREADS), 0, st, A, B, (unsigned)count, ss.correct_in.as<uint16_t>(), c->good_q, c->bad_q,
-                       &dev->w[0], fixed, &dev->bad);
-    fq_timer_span_end(ctx, st);
-    FQ_HIP(hipGetLastError());
-    FQ_HIP(hipStreamSynchronize(st));
-  }
   return FQGPU_OK;
 }

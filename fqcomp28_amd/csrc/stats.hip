@@ -220,11 +220,13 @@ void StatsScratch::release_host() {
   attr_set = false;
 }
 
-// The summary of the chunk raw_dev[0, raw_len) with the record table recs_dev, on st, waited for: out[0, fqgpu_stats_words(P)).
+// The summary of the chunk v (raw_dev[0, raw_len) with the record table recs_dev), on st, waited for: out[0, fqgpu_stats_words(P)).
 // FQGPU_E_ARG with out zeroed: a byte that cannot be counted, or a record that is not inside the chunk or has no symbol
 // (len 0: no parser of this project makes one, and a read without symbols has no mean quality and no GC content).
-int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const uint8_t *raw_dev, size_t raw_len, const fqgpu_rec *recs_dev, size_t n_recs,
-                   unsigned P, uint64_t *out) {
+int fq_stats_chunk(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &v, unsigned P, uint64_t *out) {
+  const uint8_t *const raw_dev = v.raw;
+  const fqgpu_rec *const recs_dev = v.recs;
+  const size_t raw_len = v.raw_len, n_recs = v.n_recs;
   const size_t words = fqgpu_stats_words(P);
   if (!words || n_recs >= ((size_t)1 << 32) || raw_len >= ((size_t)1 << 32)) return FQGPU_E_ARG;
   StatsScratch &ss = ctx->stats;

@@ -1,4 +1,4 @@
-"""The overlap correction on the device (k_pair_correct in fqcomp28_amd/csrc/select.hip, behind fqgpu_*_pair_correct) against
+"""The overlap correction on the device (k_pair_correct in fqcomp28_amd/csrc/pair.hip, behind fqgpu_*_pair_correct) against
 the restatement in correct_ref.py: the eight report words, the two per-pair arrays and BOTH chunks' whole raw bytes fetched
 back -- header lines, '+' lines and every untouched read included -- for equality; what is refused leaves both chunks as they
 were.  Integer arithmetic: there is no tolerance."""

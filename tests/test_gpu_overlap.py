@@ -1,4 +1,4 @@
-"""The mate overlap on the device (k_pair_overlap and k_select_limit in fqcomp28_amd/csrc/select.hip, behind
+"""The mate overlap on the device (k_pair_overlap in fqcomp28_amd/csrc/pair.hip and k_select_limit in select.hip, behind
 fqgpu_*_pair_overlap and fqgpu_*_select_limited) against the restatement in overlap_ref.py: all 1040 summary words, the three
 per-pair arrays, and -- for a selection with limits -- the kept bytes, all 24 report words, the keep bits, the windows and
 the places, for equality.  Integer arithmetic: there is no tolerance."""

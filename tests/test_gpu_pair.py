@@ -1,4 +1,4 @@
-"""The paired calls on the device (k_select_mark, k_pair_names and the judge's range in fqcomp28_amd/csrc/select.hip, behind
+"""The paired calls on the device (k_select_mark and the judge's range in fqcomp28_amd/csrc/select.hip, k_pair_names in pair.hip, behind
 fqgpu_*_select_marked and fqgpu_*_pair_names) against the numpy restatement in pair_ref.py: the kept bytes, all 24 report
 words, the final keep bits, the windows and the places of a record range under a mark, and the first pair whose read ids
 differ, for equality.  Integer arithmetic: there is no tolerance."""
@@ -346,6 +346,60 @@ def test_two_handles_with_their_own_tables_on_staged_chunks(F, golden):
              "a tail call behind the marked calls: the chunk is as it was")
     c1.close()
     c2.close()
+
+
+@pytest.mark.parametrize("cut", [None, (574, 572)], ids=["the fixture as it is", "the fixture from pairs 574 and 572 on"])
+def test_a_record_range_of_the_staged_chunk_in_every_pair_call(F, ctx, golden, cut):
+    """first_a = 3, first_b = 5, count = 64 + 1 of the chunks staged on two handles: a partial last wave, a record in front of
+    either range, two different firsts.  Every pair call gives what its block form gives for the same ranges and what its
+    reference gives; the correcting calls run on fresh copies.  In the fixture as it is, record 3 of mate 1 and record 5 of
+    mate 2 are strangers -- their ids differ at once and nothing overlaps.  Cut in front of pair 574 and of pair 572 the
+    chunks' records 3 and 5 are pair 577, whose 65 pairs are the 65 of the fixture with the most overlaps (overlap_ref: 19),
+    so that the overlap's own inserts make the correction change both chunks."""
+    import correct_ref as CR
+    import overlap_ref as OR
+    (raw1, recs1), (raw2, recs2) = golden
+    if cut:
+        raw1, raw2 = raw1[int(PR.header_starts(recs1)[cut[0]]):].copy(), raw2[int(PR.header_starts(recs2)[cut[1]]):].copy()
+        recs1, recs2 = F.parse_fastq(raw1), F.parse_fastq(raw2)
+    first_a, first_b, count = 3, 5, 64 + 1
+    where = (raw1, recs1, first_a, raw2, recs2, first_b, count)
+
+    def fresh():
+        c1, c2 = TS.context_for(F, raw1, recs1), TS.context_for(F, raw2, recs2)
+        assert c1.encode_raw(raw1)["rc"] == 0 == c2.encode_raw(raw2)["rc"]
+        return c1, c2, ctx.dblock(raw1, recs1), ctx.dblock(raw2, recs2)
+
+    c1, c2, b1, b2 = fresh()
+    # names
+    want = (0, PR.first_mismatch(*where))
+    assert want == ((0, None) if cut else (0, 0))
+    assert c1.chunk_pair_names(first_a, c2, first_b, count) == want == b1.pair_names(first_a, b2, first_b, count)
+    # overlap
+    want = OR.overlap_records(*where, OR.spec())
+    assert int(want[0][OR.OVERLAPPED]) == (19 if cut else 0)
+    for what, g in (("staged", c1.chunk_pair_overlap(first_a, c2, first_b, count, OR.spec())), ("blocks", b1.pair_overlap(first_a, b2, first_b, count, OR.spec()))):
+        assert g["rc"] == 0 and g["out"].tolist() == want[0].tolist(), what
+        assert [g[k].tolist() for k in ("limit_a", "limit_b", "insert")] == [w.tolist() for w in want[1:]], what
+    # correct: with the overlap's inserts, and with an insert of a whole read for every pair, which lays strangers over each other
+    changed = False
+    for ins in (want[3], np.full(count, 100, dtype=np.uint16)):
+        if changed:
+            for h in (c1, c2, b1, b2):
+                h.close()
+            c1, c2, b1, b2 = fresh()
+        want_a, want_b, report, fa, fb = CR.correct_records(*where, ins, CR.spec())
+        changed = want_a.tobytes() != raw1.tobytes() and want_b.tobytes() != raw2.tobytes()
+        assert changed == bool(ins.any()), "a correction that corrects"
+        for what, g in (("staged", c1.chunk_pair_correct(first_a, c2, first_b, count, ins, CR.spec())), ("blocks", b1.pair_correct(first_a, b2, first_b, count, ins, CR.spec()))):
+            assert g["rc"] == 0 and g["report"].tolist() == report.tolist(), what
+            assert g["fixed_a"].tolist() == fa.tolist() and g["fixed_b"].tolist() == fb.tolist(), what
+        for c, b, got, recs in ((c1, b1, want_a, recs1), (c2, b2, want_b, recs2)):
+            assert b.fetch(raw=True)["raw"].tobytes() == got.tobytes()
+            s = c.chunk_select_marked(0, len(recs))
+            assert s["rc"] == 0 and s["out"].tobytes() == PR.marked_records(got, recs, 0, len(recs))[0].tobytes()
+    for h in (c1, c2, b1, b2):
+        h.close()
 
 
 # ---------------------------------------------------------------- 6. scratch history
