@@ -10,6 +10,7 @@
 #include <new>
 #include <string>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -322,10 +323,8 @@ EncLane *fq_next_lane(fqgpu_ctx *ctx, size_t n_bases, fqgpu_dblock *b) {
 
 // ------------------------------------------------------------------ the handle's scratch, one enumeration
 // Every device scratch buffer a handle owns, as f(owner, name, pointer, bytes allocated): the DevBuf lists of the scratch
-// structs (fqgpu_internal.h: FQ_SCRATCH_BUFS) and the staging block's buffers.  fqgpu_ctx_destroy frees what this visits and
-// fqgpu_ctx_fill_scratch fills it: one walk for both.
-template <class F> static void dblock_each_buf(fqgpu_dblock *b, const fqgpu_ctx *hp, F &&f);
-
+// structs (fqgpu_internal.h: FQ_SCRATCH_BUFS) and the staging block's arrays (FQ_DBLOCK_BUFS).  fqgpu_ctx_destroy frees what
+// these visit and fqgpu_ctx_fill_scratch fills it: one walk for both.
 template <class F> static void ctx_each_devbuf(fqgpu_ctx *ctx, F &&f) {  // f(owner, name, DevBuf &)
   for (int i = 0; i < FQ_MAX_LANES; i++) {
     EncLane &l = ctx->lanes[i];
@@ -563,7 +562,7 @@ extern "C" void fqgpu_ctx_destroy(fqgpu_ctx *ctx) {
   ctx->stats.release_host();
   ctx->select.release_host();
   for (int i = 0; i < FQ_MAX_LANES; i++) free_lane(ctx->lanes[i]);
-  if (ctx->hp_block) fqgpu_dblock_destroy(ctx->hp_block);
+  fqgpu_dblock_destroy(ctx->hp.block);
   if (ctx->hp_ev_h2d) (void)hipEventDestroy(ctx->hp_ev_h2d);
   if (ctx->hp_result) (void)hipHostFree(ctx->hp_result);
   if (ctx->timer) {
@@ -653,7 +652,7 @@ static int index_header(int stream, size_t n_bases, const void *data, size_t len
 
 static int index_accept(fqgpu_dblock *b, int stream, const void *data, size_t len) {
   const int rc = index_header(stream, b->n_bases, data, len, nullptr);
-  return rc ? rc : fq_index_reserve(b, stream, len, false);
+  return rc ? rc : b->index[stream].grow(len + 64);
 }
 
 extern "C" int fqgpu_dblock_load_index(fqgpu_ctx *ctx, fqgpu_dblock *b, int stream, const void *data, size_t len) {
@@ -706,25 +705,31 @@ extern "C" int fqgpu_ctx_dump_tables(fqgpu_ctx *ctx, int stream, unsigned model,
 extern "C" void fqgpu_dblock_destroy(fqgpu_dblock *b) {
   if (!b) return;
   (void)hipSetDevice(b->device);
-  dblock_each_buf(b, nullptr, [](const char *, void *p, size_t) { if (p) (void)hipFree(p); });
+  fq_dblock_each_buf(*b, [](const char *, auto &a) { (void)a.release(); });
   if (b->ev_encoded) (void)hipEventDestroy(b->ev_encoded);
   delete b;
 }
 
-// stream / side-stream buffers of a block whose raw_len, n_recs, n_bases and n_pos_cap are set
+// A block of the handle's device that holds nothing but its result words; every error path of its maker is a plain return.
+// nullptr: no memory.
+struct DblockDestroy { void operator()(fqgpu_dblock *b) const { fqgpu_dblock_destroy(b); } };
+typedef std::unique_ptr<fqgpu_dblock, DblockDestroy> DblockPtr;
+static DblockPtr dblock_new(fqgpu_ctx *ctx) {
+  DblockPtr b(new (std::nothrow) fqgpu_dblock());
+  if (!b) return b;
+  b->device = ctx->device;
+  b->owner = ctx;
+  if (b->result.grow(1)) b.reset();
+  return b;
+}
+
+// stream / side-stream arrays of a caller's block whose n_recs, n_bases and n_pos_cap are set: exactly what they must hold
 static int alloc_block_outputs(fqgpu_dblock *b) {
   b->seq_cap = fqgpu_bound_seq(b->n_bases);
   b->qual_cap = fqgpu_bound_qual(b->n_bases);
-  b->seq_alloc = b->seq_cap + 64;
-  b->qual_alloc = b->qual_cap + 64;
-  b->seq = fq_dev_alloc<uint8_t>(b->seq_alloc);
-  b->qual = fq_dev_alloc<uint8_t>(b->qual_alloc);
-  b->readlens = fq_dev_alloc<uint16_t>(b->n_recs);
-  b->n_count = fq_dev_alloc<uint16_t>(b->n_recs);
-  b->n_pos = fq_dev_alloc<uint16_t>(b->n_pos_cap + 16);
-  b->result = fq_dev_alloc<BlockResult>(1);
-  if (!b->seq || !b->qual || !b->readlens || !b->n_count || !b->n_pos || !b->result) return FQGPU_E_NOMEM;
-  memset(&b->host_result, 0, sizeof(b->host_result));
+  if (b->seq.grow(b->seq_cap + 64) || b->qual.grow(b->qual_cap + 64) || b->readlens.grow(b->n_recs) || b->n_count.grow(b->n_recs) ||
+      b->n_pos.grow(b->n_pos_cap + 16))
+    return FQGPU_E_NOMEM;
   return FQGPU_OK;
 }
 
@@ -742,29 +747,21 @@ extern "C" int fqgpu_dblock_create(fqgpu_ctx *ctx, const uint8_t *raw, size_t ra
     const uint8_t *s = raw + recs[i].seq_off, *e = s + recs[i].len;
     while ((s = static_cast<const uint8_t *>(memchr(s, 'N', (size_t)(e - s)))) != nullptr) { n_n++; s++; }
   }
-  fqgpu_dblock *b = new (std::nothrow) fqgpu_dblock();
+  DblockPtr b = dblock_new(ctx);
   if (!b) return FQGPU_E_NOMEM;
-  b->device = ctx->device;
-  b->owner = ctx;
   b->raw_len = raw_len; b->n_recs = n_recs; b->n_bases = n_bases;
   b->n_pos_cap = n_n;
-  b->raw = fq_dev_alloc<uint8_t>(raw_len + 64);
-  b->recs = fq_dev_alloc<fqgpu_rec>(n_recs);
-  if (!b->raw || !b->recs || alloc_block_outputs(b) != FQGPU_OK) {
-    fqgpu_dblock_destroy(b);
-    return FQGPU_E_NOMEM;
-  }
-  hipError_t he = hipMemcpyAsync(b->raw, raw, raw_len, hipMemcpyHostToDevice, ctx->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, ctx->stream);
-  if (he == hipSuccess) he = hipMemsetAsync(b->result, 0, sizeof(BlockResult), ctx->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-  if (he != hipSuccess) { fqgpu_dblock_destroy(b); return fq_hip_error(he, __FILE__, __LINE__); }
-  *out = b;
+  if (b->raw.grow(raw_len + 64) || b->recs.grow(n_recs) || alloc_block_outputs(b.get())) return FQGPU_E_NOMEM;
+  FQ_HIP(hipMemcpyAsync(b->raw, raw, raw_len, hipMemcpyHostToDevice, ctx->stream));
+  FQ_HIP(hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, ctx->stream));
+  FQ_HIP(hipMemsetAsync(b->result, 0, sizeof(BlockResult), ctx->stream));
+  FQ_HIP(hipStreamSynchronize(ctx->stream));
+  *out = b.release();
   return FQGPU_OK;
 }
 
 int fq_parse_on_device(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, DevBuf &scan_tmp,
-                       fqgpu_rec **recs_dev, size_t *n_recs, size_t *n_bases, size_t *n_n);
+                       DevArray<fqgpu_rec> &recs, size_t *n_recs, size_t *n_bases, size_t *n_n);
 
 // Raw block in, record table built on the GPU (parse.hip): replaces FastqReader::parseRecords
 // (reference src/fastq_io.cpp:67-125) for callers that hand over unparsed chunks.
@@ -773,29 +770,19 @@ extern "C" int fqgpu_dblock_create_from_raw(fqgpu_ctx *ctx, const uint8_t *raw, 
   *out = nullptr;
   int rc = use_device(ctx->device);
   if (rc) return rc;
-  fqgpu_dblock *b = new (std::nothrow) fqgpu_dblock();
-  if (!b) return FQGPU_E_NOMEM;
-  b->device = ctx->device;
-  b->owner = ctx;
-  b->raw = fq_dev_alloc<uint8_t>(raw_len + 64);
-  if (!b->raw) { fqgpu_dblock_destroy(b); return FQGPU_E_NOMEM; }
-  hipError_t he = hipMemsetAsync(b->raw + raw_len, 0, 64, ctx->stream);
-  if (he == hipSuccess) he = hipMemcpyAsync(b->raw, raw, raw_len, hipMemcpyHostToDevice, ctx->stream);
-  if (he != hipSuccess) { fqgpu_dblock_destroy(b); return fq_hip_error(he, __FILE__, __LINE__); }
-  size_t n_n = 0;
-  rc = fq_parse_on_device(ctx->stream, b->raw, raw_len, ctx->scan_tmp, &b->recs, &b->n_recs, &b->n_bases, &n_n);
-  if (rc) { fqgpu_dblock_destroy(b); return rc; }
+  DblockPtr b = dblock_new(ctx);
+  if (!b || b->raw.grow(raw_len + 64)) return FQGPU_E_NOMEM;
+  FQ_HIP(hipMemsetAsync(b->raw + raw_len, 0, 64, ctx->stream));
+  FQ_HIP(hipMemcpyAsync(b->raw, raw, raw_len, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = fq_parse_on_device(ctx->stream, b->raw, raw_len, ctx->scan_tmp, b->recs, &b->n_recs, &b->n_bases, &b->n_pos_cap))) return rc;
   // the block ends with the last complete record (partial tail ignored like the reference)
   fqgpu_rec last;
-  he = hipMemcpy(&last, b->recs + (b->n_recs - 1), sizeof(last), hipMemcpyDeviceToHost);
-  if (he != hipSuccess) { fqgpu_dblock_destroy(b); return fq_hip_error(he, __FILE__, __LINE__); }
+  FQ_HIP(hipMemcpy(&last, b->recs + (b->n_recs - 1), sizeof(last), hipMemcpyDeviceToHost));
   b->raw_len = (size_t)last.qual_off + last.len + 1;
-  b->n_pos_cap = n_n;
-  if ((rc = alloc_block_outputs(b))) { fqgpu_dblock_destroy(b); return rc; }
-  he = hipMemsetAsync(b->result, 0, sizeof(BlockResult), ctx->stream);
-  if (he == hipSuccess) he = hipStreamSynchronize(ctx->stream);
-  if (he != hipSuccess) { fqgpu_dblock_destroy(b); return fq_hip_error(he, __FILE__, __LINE__); }
-  *out = b;
+  if ((rc = alloc_block_outputs(b.get()))) return rc;
+  FQ_HIP(hipMemsetAsync(b->result, 0, sizeof(BlockResult), ctx->stream));
+  FQ_HIP(hipStreamSynchronize(ctx->stream));
+  *out = b.release();
   return FQGPU_OK;
 }
 
@@ -817,8 +804,7 @@ extern "C" int fqgpu_dblock_encode(fqgpu_ctx *ctx, fqgpu_dblock *b, unsigned fla
   if (!ctx || !b || b->device != ctx->device) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
-  b->last_op = 1;
-  b->result_pulled = false;
+  b->launched(1);
   return fq_encode_launch(ctx, b, flags);
 }
 
@@ -947,22 +933,8 @@ extern "C" int fqgpu_dblock_load_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const 
   if (rc) return rc;
   // foreign streams may be larger than what this block's own encode would need
   // (seq_cap / qual_cap stay the capacities a later re-encode of this block is judged against)
-  if (seq_len + 64 > b->seq_alloc) {
-    (void)hipFree(b->seq);
-    b->seq = fq_dev_alloc<uint8_t>(seq_len + 64);
-    b->seq_alloc = b->seq ? seq_len + 64 : 0;
-  }
-  if (qual_len + 64 > b->qual_alloc) {
-    (void)hipFree(b->qual);
-    b->qual = fq_dev_alloc<uint8_t>(qual_len + 64);
-    b->qual_alloc = b->qual ? qual_len + 64 : 0;
-  }
-  if (n_pos_len > b->n_pos_cap) {
-    (void)hipFree(b->n_pos);
-    b->n_pos = fq_dev_alloc<uint16_t>(n_pos_len + 16);
-    b->n_pos_cap = n_pos_len;
-  }
-  if (!b->seq || !b->qual || !b->n_pos) return FQGPU_E_NOMEM;
+  if (b->seq.grow(seq_len + 64) || b->qual.grow(qual_len + 64) || b->n_pos.grow(n_pos_len + 16)) return FQGPU_E_NOMEM;
+  if (n_pos_len > b->n_pos_cap) b->n_pos_cap = n_pos_len;
   FQ_HIP(hipMemset(b->seq + seq_len, 0, 16));  // the bit reader loads whole dwords
   FQ_HIP(hipMemset(b->qual + qual_len, 0, 16));
   FQ_HIP(hipMemcpy(b->seq, seq, seq_len, hipMemcpyHostToDevice));
@@ -970,9 +942,7 @@ extern "C" int fqgpu_dblock_load_streams(fqgpu_ctx *ctx, fqgpu_dblock *b, const 
   FQ_HIP(hipMemcpy(b->n_count, n_count, b->n_recs * 2, hipMemcpyHostToDevice));
   if (n_pos_len) FQ_HIP(hipMemcpy(b->n_pos, n_pos, n_pos_len * 2, hipMemcpyHostToDevice));
   b->seq_len = seq_len; b->qual_len = qual_len; b->n_pos_len = n_pos_len;
-  b->last_op = 0;  // the result block no longer describes these streams
-  b->result_pulled = true;
-  b->index_bytes[0] = b->index_bytes[1] = 0;  // an index belongs to the streams it was made for
+  b->drop_results();  // the result block no longer describes these streams, and an index belongs to the streams it was made for
   return FQGPU_OK;
 }
 
@@ -993,7 +963,7 @@ static int dblocks_decode(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks, size_t n_
     }
     if (!b->seq_len || !b->qual_len) return FQGPU_E_ARG;
   }
-  for (size_t i = 0; i < n_blocks; i++) { blocks[i]->last_op = 2; blocks[i]->result_pulled = false; }
+  for (size_t i = 0; i < n_blocks; i++) blocks[i]->launched(2);
   return fq_decode_launch(ctx, blocks, n_blocks, nullptr, build_index);
 }
 
@@ -1023,70 +993,31 @@ extern "C" int fqgpu_dblocks_decode_indexing(fqgpu_ctx *ctx, fqgpu_dblock *const
 // The two calls below stage through one device block the handle keeps between calls: a worker
 // that codes chunk after chunk (reference src/process.cpp:49-54) pays hipMalloc only while its
 // chunks are still growing.
-template <class T>
-static bool hp_grow(T *&p, size_t &have, size_t need) {
-  if (p && need <= have) return true;
-  if (p) (void)hipFree(p);
-  have = need + need / 8;
-  p = fq_dev_alloc<T>(have);
-  if (!p) have = 0;
-  return p != nullptr;
-}
+// One rule of growth for the staging block: an eighth more than is needed.
+template <class A> static bool hp_room(A &a, size_t need) { return a.grow(need, need / 8) == FQGPU_OK; }
 
 static int hp_block_acquire(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, size_t n_bases, size_t seq_cap,
                             size_t qual_cap, size_t n_pos_cap, fqgpu_dblock **out) {
-  fqgpu_dblock *b = ctx->hp_block;
-  if (!b) {
-    b = new (std::nothrow) fqgpu_dblock();
-    if (!b) return FQGPU_E_NOMEM;
-    b->device = ctx->device;
-    b->owner = ctx;
-    b->result = fq_dev_alloc<BlockResult>(1);
-    if (!b->result) { delete b; return FQGPU_E_NOMEM; }  // published only when complete
-    ctx->hp_block = b;
-  }
-  size_t side2 = ctx->hp_side;
-  const bool ok = hp_grow(b->raw, ctx->hp_raw, raw_len + 64) && hp_grow(b->recs, ctx->hp_recs, n_recs) &&
-                  hp_grow(b->seq, ctx->hp_seq, seq_cap + 64) && hp_grow(b->qual, ctx->hp_qual, qual_cap + 64) &&
-                  hp_grow(b->readlens, ctx->hp_side, n_recs) && hp_grow(b->n_count, side2, n_recs) &&
-                  hp_grow(b->n_pos, ctx->hp_npos, n_pos_cap + 16);
+  if (!ctx->hp.block && !(ctx->hp.block = dblock_new(ctx).release())) return FQGPU_E_NOMEM;
+  fqgpu_dblock *b = ctx->hp.block;
+  const bool ok = hp_room(b->raw, raw_len + 64) && hp_room(b->recs, n_recs) && hp_room(b->seq, seq_cap + 64) &&
+                  hp_room(b->qual, qual_cap + 64) && hp_room(b->readlens, n_recs) && hp_room(b->n_count, n_recs) &&
+                  hp_room(b->n_pos, n_pos_cap + 16);
   if (!ok) {  // leave nothing half-sized behind
     fqgpu_dblock_destroy(b);
-    ctx->hp_block = nullptr;
-    ctx->hp_raw = ctx->hp_recs = ctx->hp_seq = ctx->hp_qual = ctx->hp_side = ctx->hp_npos = 0;
+    ctx->hp.block = nullptr;
+    ctx->hp.clear();
     return FQGPU_E_NOMEM;
   }
   b->raw_len = raw_len; b->n_recs = n_recs; b->n_bases = n_bases;
   b->seq_cap = seq_cap; b->qual_cap = qual_cap; b->n_pos_cap = n_pos_cap;
-  b->seq_alloc = ctx->hp_seq; b->qual_alloc = ctx->hp_qual;
-  b->seq_len = b->qual_len = b->n_pos_len = 0;
-  b->index_bytes[0] = b->index_bytes[1] = 0;
-  ctx->hp_index_built = false;
-  ctx->hp_crc_what = 0;
-  b->last_op = 0;
-  b->result_pulled = true;
-  memset(&b->host_result, 0, sizeof(b->host_result));
+  ctx->hp.clear();
   *out = b;
   return FQGPU_OK;
 }
 
-// The device buffers of a block as f(name, pointer, bytes allocated).  hp: the handle whose staging block b is -- the sizes are
-// the handle's (hp_grow counts elements) --, or nullptr: a caller's block, sizes not asked for (0).
-template <class F> static void dblock_each_buf(fqgpu_dblock *b, const fqgpu_ctx *hp, F &&f) {
-  f("raw", b->raw, hp ? hp->hp_raw : 0);
-  f("recs", b->recs, hp ? hp->hp_recs * sizeof(fqgpu_rec) : 0);
-  f("seq", b->seq, hp ? hp->hp_seq : 0);
-  f("qual", b->qual, hp ? hp->hp_qual : 0);
-  f("readlens", b->readlens, hp ? hp->hp_side * 2 : 0);
-  f("n_count", b->n_count, hp ? hp->hp_side * 2 : 0);  // (grown in step with readlens: hp_block_acquire)
-  f("n_pos", b->n_pos, hp ? hp->hp_npos * 2 : 0);
-  f("result", b->result, hp ? sizeof(BlockResult) : 0);
-  f("index[0]", b->index[0], hp && b->index[0] ? b->index_cap[0] + 64 : 0);  // (fq_index_reserve)
-  f("index[1]", b->index[1], hp && b->index[1] ? b->index_cap[1] + 64 : 0);
-}
-
 extern "C" int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t *n_buffers, size_t *n_bytes) {
-  if (!ctx || ctx->hp_pending || ctx->hp_hdr.pending) return FQGPU_E_ARG;
+  if (!ctx || ctx->hp.pending || ctx->hp_hdr.pending) return FQGPU_E_ARG;
   int rc = fqgpu_sync(ctx);  // (selects the device)
   if (rc) return rc;
   size_t bufs = 0, bytes = 0;
@@ -1101,17 +1032,8 @@ extern "C" int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t
   ctx_each_devbuf(ctx, [&](const char *owner, const char *name, DevBuf &b) {
     if (!scratch_is_state(owner, name)) fill(b.p, b.cap);
   });
-  if (fqgpu_dblock *b = ctx->hp_block) {
-    dblock_each_buf(b, ctx, [&](const char *, void *p, size_t n) { fill(p, n); });
-    // the staging block holds nothing any more: no chunk to digest, no index, no result
-    b->index_bytes[0] = b->index_bytes[1] = 0;
-    b->seq_len = b->qual_len = b->n_pos_len = 0;
-    b->last_op = 0;
-    b->result_pulled = true;
-    memset(&b->host_result, 0, sizeof(b->host_result));
-    ctx->hp_index_built = false;
-    ctx->hp_crc_what = 0;
-  }
+  if (ctx->hp.block) fq_dblock_each_buf(*ctx->hp.block, [&](const char *, auto &a) { fill(a.p, a.bytes()); });
+  ctx->hp.clear();  // no chunk to digest, no index, no result
   FQ_HIP(he);
   FQ_HIP(hipStreamSynchronize(ctx->stream));
   if (n_buffers) *n_buffers = bufs;
@@ -1127,7 +1049,6 @@ extern "C" int fqgpu_ctx_reserve(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, 
   int rc = use_device(ctx->device);
   if (rc) return rc;
   if ((rc = fqgpu_sync(ctx))) return rc;
-  ctx->hp_pending = false;
   fqgpu_dblock *b = nullptr;
   if ((rc = hp_block_acquire(ctx, raw_len, n_recs, n_bases, fqgpu_bound_seq(n_bases), fqgpu_bound_qual(n_bases), n_bases / 64 + 1024, &b))) return rc;
   if ((rc = ctx->hp_parse.cnt.reserve((raw_len / 4096 + 2) * 4)) || (rc = ctx->hp_parse.base.reserve((raw_len / 4096 + 3) * 4)) ||
@@ -1143,8 +1064,7 @@ extern "C" int fqgpu_ctx_reserve(fqgpu_ctx *ctx, size_t raw_len, size_t n_recs, 
 // vectors that go back to the pin cache, where another thread may pick them up) must not be read or
 // written by a copy that is still in flight.
 static int hp_fail(fqgpu_ctx *ctx, int rc) {
-  ctx->hp_pending = false;
-  ctx->hp_crc_what = 0;
+  ctx->hp.clear();
   (void)fqgpu_sync(ctx);
   return rc;
 }
@@ -1161,7 +1081,7 @@ static int hp_encode_begin(fqgpu_ctx *ctx, const uint8_t *raw, size_t raw_len, c
   if (!ctx || !raw || !raw_len || (recs && !n_recs)) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
-  ctx->hp_pending = false;  // (a block begun and never collected is dropped: fqgpu_sync below waits for it)
+  ctx->hp.pending = false;  // (a block begun and never collected is dropped: fqgpu_sync below waits for it)
   ctx->hp_hdr.pending = ctx->hp_hdr.collected = false;
   size_t n_bases = 0, n_n = 0, used = raw_len;
   if (recs && (rc = check_recs(recs, n_recs, raw_len, &n_bases))) return rc;
@@ -1175,7 +1095,7 @@ static int hp_encode_begin(fqgpu_ctx *ctx, const uint8_t *raw, size_t raw_len, c
   FQ_HIP_HP(hipMemcpyAsync(b->raw, raw, raw_len, hipMemcpyHostToDevice, ctx->stream));
   if (!recs) {
     if ((rc = fq_parse_count(ctx->stream, b->raw, raw_len, ctx->hp_parse, &n_recs))) return hp_fail(ctx, rc);
-    if (!hp_grow(b->recs, ctx->hp_recs, n_recs)) return hp_fail(ctx, FQGPU_E_NOMEM);
+    if (!hp_room(b->recs, n_recs)) return hp_fail(ctx, FQGPU_E_NOMEM);
     if ((rc = fq_parse_records(ctx->stream, b->raw, raw_len, ctx->hp_parse, b->recs, n_recs, &n_bases, &n_n, &used))) return hp_fail(ctx, rc);
   }
   // The reference's capacities are the ones the overflow rule is judged against.  n_pos: the device
@@ -1185,17 +1105,16 @@ static int hp_encode_begin(fqgpu_ctx *ctx, const uint8_t *raw, size_t raw_len, c
     return hp_fail(ctx, rc);
   if (recs) FQ_HIP_HP(hipMemcpyAsync(b->recs, recs, n_recs * sizeof(fqgpu_rec), hipMemcpyHostToDevice, ctx->stream));
   FQ_HIP_HP(hipEventRecord(ctx->hp_ev_h2d, ctx->stream));
-  b->last_op = 1;
-  b->result_pulled = false;
+  b->launched(1);
   hipStream_t st = nullptr;
   // (the device copy of raw is scratch here: its N's are patched on the host by fqgpu_encode_end)
   if ((rc = fq_encode_launch(ctx, b, flags & ~FQGPU_F_WRITE_BACK_N, ctx->hp_ev_h2d, &st))) return hp_fail(ctx, rc);
   FQ_HIP_HP(hipMemcpyAsync(ctx->hp_result, b->result, sizeof(BlockResult), hipMemcpyDeviceToHost, st));
-  ctx->hp_pending = true;
-  ctx->hp_flags = flags;
-  ctx->hp_done = st;
-  ctx->hp_used = used;
-  ctx->hp_crc_what = 1;
+  ctx->hp.pending = true;
+  ctx->hp.flags = flags;
+  ctx->hp.done = st;
+  ctx->hp.used = used;
+  ctx->hp.crc_what = 1;
   if (n_recs_out) *n_recs_out = n_recs;
   if (n_bases_out) *n_bases_out = n_bases;
   if (used_len) *used_len = used;
@@ -1208,20 +1127,20 @@ extern "C" int fqgpu_encode_begin(fqgpu_ctx *ctx, const uint8_t *raw, size_t raw
 }
 
 extern "C" int fqgpu_encode_records(fqgpu_ctx *ctx, fqgpu_rec *recs_out, size_t cap) {
-  if (!ctx || !recs_out || !ctx->hp_pending || !ctx->hp_block || cap < ctx->hp_block->n_recs) return FQGPU_E_ARG;
+  if (!ctx || !recs_out || !ctx->hp.pending || !ctx->hp.block || cap < ctx->hp.block->n_recs) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
   // on the handle's copy stream: the table was built (or uploaded) there; the lanes' kernels are not waited for
-  FQ_HIP(hipMemcpyAsync(recs_out, ctx->hp_block->recs, ctx->hp_block->n_recs * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, ctx->stream));
+  FQ_HIP(hipMemcpyAsync(recs_out, ctx->hp.block->recs, ctx->hp.block->n_recs * sizeof(fqgpu_rec), hipMemcpyDeviceToHost, ctx->stream));
   FQ_HIP(hipStreamSynchronize(ctx->stream));
   return FQGPU_OK;
 }
 
 // waits for the block in flight and reads its result block; the block stays pending
 static int hp_collect(fqgpu_ctx *ctx) {
-  fqgpu_dblock *b = ctx->hp_block;
+  fqgpu_dblock *b = ctx->hp.block;
   if (b->result_pulled) return FQGPU_OK;
-  FQ_HIP_HP(hipStreamSynchronize(ctx->hp_done));
+  FQ_HIP_HP(hipStreamSynchronize(ctx->hp.done));
   b->host_result = *ctx->hp_result;
   b->result_pulled = true;
   const BlockResult &r = b->host_result;
@@ -1232,13 +1151,13 @@ static int hp_collect(fqgpu_ctx *ctx) {
 }
 
 extern "C" int fqgpu_encode_wait(fqgpu_ctx *ctx, size_t *seq_len, size_t *qual_len, size_t *n_pos_len) {
-  if (!ctx || !ctx->hp_pending || !ctx->hp_block) return FQGPU_E_ARG;
+  if (!ctx || !ctx->hp.pending || !ctx->hp.block) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
   if ((rc = hp_collect(ctx))) return rc;
-  if (seq_len) *seq_len = ctx->hp_block->seq_len;
-  if (qual_len) *qual_len = ctx->hp_block->qual_len;
-  if (n_pos_len) *n_pos_len = ctx->hp_block->n_pos_len;
+  if (seq_len) *seq_len = ctx->hp.block->seq_len;
+  if (qual_len) *qual_len = ctx->hp.block->qual_len;
+  if (n_pos_len) *n_pos_len = ctx->hp.block->n_pos_len;
   return FQGPU_OK;
 }
 
@@ -1246,8 +1165,7 @@ extern "C" int fqgpu_encode_cancel(fqgpu_ctx *ctx) {
   if (!ctx) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
-  ctx->hp_pending = false;
-  ctx->hp_crc_what = 0;
+  ctx->hp.clear();
   ctx->hp_hdr.pending = ctx->hp_hdr.collected = false;
   return fqgpu_sync(ctx);
 }
@@ -1256,12 +1174,12 @@ extern "C" int fqgpu_encode_cancel(fqgpu_ctx *ctx) {
 // its record table was uploaded or built -- beside the lane's encode kernels.
 extern "C" int fqgpu_encode_headers_begin(fqgpu_ctx *ctx, const uint8_t *field_types, const char *separators, unsigned n_fields,
                                           const uint8_t *first_header, size_t first_header_len) {
-  if (!ctx || !ctx->hp_pending || !ctx->hp_block || ctx->hp_hdr.pending || !field_types || !first_header || (n_fields > 1 && !separators))
+  if (!ctx || !ctx->hp.pending || !ctx->hp.block || ctx->hp_hdr.pending || !field_types || !first_header || (n_fields > 1 && !separators))
     return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
-  const fqgpu_dblock *b = ctx->hp_block;
-  if ((rc = fq_headers_launch(ctx->stream, b->raw, ctx->hp_used, b->recs, b->n_recs, b->n_bases, field_types, separators, n_fields,
+  const fqgpu_dblock *b = ctx->hp.block;
+  if ((rc = fq_headers_launch(ctx->stream, b->raw, ctx->hp.used, b->recs, b->n_recs, b->n_bases, field_types, separators, n_fields,
                               first_header, first_header_len, ctx->hp_hdr)))
     return rc == FQGPU_E_ARG ? rc : hp_fail(ctx, rc);
   ctx->hp_hdr.pending = true;
@@ -1305,20 +1223,20 @@ extern "C" int fqgpu_encode_headers_end(fqgpu_ctx *ctx, uint8_t *out, size_t out
 extern "C" int fqgpu_encode_end(fqgpu_ctx *ctx, uint8_t *raw, uint8_t *seq_out, size_t seq_cap, size_t *seq_len,
                                 uint8_t *qual_out, size_t qual_cap, size_t *qual_len, uint16_t *readlens_out,
                                 uint16_t *n_count_out, uint16_t *n_pos_out, size_t n_pos_cap, size_t *n_pos_len) {
-  if (!ctx || !ctx->hp_pending || !ctx->hp_block) return FQGPU_E_ARG;
+  if (!ctx || !ctx->hp.pending || !ctx->hp.block) return FQGPU_E_ARG;
   int rc = use_device(ctx->device);
   if (rc) return rc;
   if (!seq_out || !qual_out || !seq_len || !qual_len) return hp_fail(ctx, FQGPU_E_ARG);
-  fqgpu_dblock *b = ctx->hp_block;
-  hipStream_t st = ctx->hp_done;
+  fqgpu_dblock *b = ctx->hp.block;
+  hipStream_t st = ctx->hp.done;
   const size_t n_recs = b->n_recs;
   if ((rc = hp_collect(ctx))) return rc;
-  ctx->hp_pending = false;
+  ctx->hp.pending = false;
   if (b->seq_len > seq_cap || b->qual_len > qual_cap) return FQGPU_E_OVERFLOW;
   if (n_pos_out && b->n_pos_len > n_pos_cap) return FQGPU_E_ARG;
   // N -> A on the host needs the N tables even if the caller does not want them
   std::vector<uint16_t> tmp_cnt, tmp_pos;
-  const bool patch = raw && (ctx->hp_flags & FQGPU_F_WRITE_BACK_N) && b->n_pos_len;
+  const bool patch = raw && (ctx->hp.flags & FQGPU_F_WRITE_BACK_N) && b->n_pos_len;
   uint16_t *cnt_h = n_count_out, *pos_h = n_pos_out;
   if (patch && !cnt_h) { tmp_cnt.resize(n_recs); cnt_h = tmp_cnt.data(); }
   if (patch && !pos_h) { tmp_pos.resize(b->n_pos_len); pos_h = tmp_pos.data(); }
@@ -1351,7 +1269,7 @@ extern "C" int fqgpu_encode_end(fqgpu_ctx *ctx, uint8_t *raw, uint8_t *seq_out, 
 // The staging block's decode index of stream s: its size to *len and, if there is an `out` and anything to bring, its bytes
 // (cap < *len: FQGPU_E_ARG) -- behind the stream `st`, or with a synchronous copy (st = nullptr).  *he: what the copy said.
 static int hp_index_fetch(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len, hipStream_t st, hipError_t *he) {
-  const fqgpu_dblock *b = ctx->hp_block;
+  const fqgpu_dblock *b = ctx->hp.block;
   *he = hipSuccess;
   *len = b->index_bytes[stream];
   if (!out || !*len) return FQGPU_OK;
@@ -1366,10 +1284,10 @@ static int hp_index_fetch(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, 
 // The decode index of the block fqgpu_encode_begin coded with FQGPU_F_DECODE_INDEX: after fqgpu_encode_wait or _end,
 // until the handle's next host-pointer call.
 extern "C" int fqgpu_encode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len) {
-  if (!ctx || !ctx->hp_block || stream < 0 || stream > 1 || !len) return FQGPU_E_ARG;
-  if (ctx->hp_block->last_op != 1 || !ctx->hp_block->result_pulled) return FQGPU_E_ARG;
+  if (!ctx || !ctx->hp.block || stream < 0 || stream > 1 || !len) return FQGPU_E_ARG;
+  if (ctx->hp.block->last_op != 1 || !ctx->hp.block->result_pulled) return FQGPU_E_ARG;
   hipError_t he;
-  const int rc = hp_index_fetch(ctx, stream, out, cap, len, ctx->hp_done, &he);
+  const int rc = hp_index_fetch(ctx, stream, out, cap, len, ctx->hp.done, &he);
   if (rc) return rc;
   FQ_HIP(he);
   return FQGPU_OK;
@@ -1449,8 +1367,7 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
       b->index_bytes[k] = s.index_len[k];
     }
   b->seq_len = s.seq_len; b->qual_len = s.seq_only ? 0 : s.qual_len; b->n_pos_len = s.n_pos_len;
-  b->last_op = 2;
-  b->result_pulled = false;
+  b->launched(2);
   fqgpu_dblock *one[1] = {b};
   if ((rc = fq_decode_launch(ctx, one, 1, plan, s.build_index, s.seq_only ? FQ_DEC_SEQ : FQ_DEC_BOTH))) return hp_fail(ctx, rc);
   if (!ctx->hp_result) FQ_HIP_HP(hipHostMalloc(reinterpret_cast<void **>(&ctx->hp_result), sizeof(BlockResult), hipHostMallocPortable));
@@ -1474,17 +1391,17 @@ static int hp_decode_staged(fqgpu_ctx *ctx, fqgpu_dblock *b, const DecStreams &s
                                                                                          : FQGPU_OK;
   if (s.build_index) {
     if (verdict) b->index_bytes[0] = b->index_bytes[1] = 0;
-    ctx->hp_index_built = !verdict;
+    ctx->hp.index_built = !verdict;
   }
   if (!verdict && !plan && !s.seq_only) {  // a whole block, restored: fqgpu_chunk_crc32 may digest it
-    ctx->hp_crc_what = 2;
-    ctx->hp_crc_len = b->raw_len;
+    ctx->hp.crc_what = 2;
+    ctx->hp.crc_len = b->raw_len;
   }
   return verdict;
 }
 
 static int hp_decode(fqgpu_ctx *ctx, const DecStreams &s, const fqgpu_rec *recs, size_t n_recs, uint8_t *raw_out, size_t raw_len) {
-  if (ctx) ctx->hp_crc_what = 0;  // (whatever becomes of this decode, the chunk before it is no longer what the handle answers for)
+  if (ctx) ctx->hp.end_digest();  // (whatever becomes of this decode, the chunk before it is no longer what the handle answers for)
   if (!ctx || !s.ok() || !recs || !raw_out) return FQGPU_E_ARG;
   if (s.n_count_len < n_recs) return FQGPU_E_CORRUPT;
   int rc = use_device(ctx->device);
@@ -1556,8 +1473,7 @@ static int layout_verdict(unsigned long long bad, unsigned long long total, size
 static int decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const uint16_t *readlens, size_t n_recs, const DecStreams &s,
                         uint8_t *raw_out, size_t raw_len, fqgpu_rec *recs_out, size_t *laid_out_len, size_t *bad_record) {
   const size_t n_count_len = s.n_count_len;
-  if (ctx && s.build_index) ctx->hp_index_built = false;
-  if (ctx) ctx->hp_crc_what = 0;  // (as hp_decode: also a call that is refused for its arguments ends the last chunk's digest)
+  if (ctx) ctx->hp.end_digest(s.build_index);  // (as hp_decode: also a call that is refused for its arguments ends the last chunk's digest)
   if (bad_record) *bad_record = (size_t)-1;
   if (laid_out_len) *laid_out_len = 0;
   if ((!raw_out && !s.build_index && !(ctx && ctx->check_only)) || !laid_out_len || !bad_record) return FQGPU_E_ARG;
@@ -1572,7 +1488,7 @@ static int decode_chunk(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, const u
   *laid_out_len = (size_t)total;
   if (total < raw_len) FQ_HIP_HP(hipMemsetAsync(b->raw + total, 0, raw_len - total, ctx->stream));
   rc = hp_decode_staged(ctx, b, s, nullptr, raw_out, 0, raw_len, recs_out, 0, n_recs);
-  if (!rc) ctx->hp_crc_len = (size_t)total;  // (zeros behind the last record are no part of the chunk)
+  if (!rc) ctx->hp.crc_len = (size_t)total;  // (zeros behind the last record are no part of the chunk)
   return rc;
 }
 
@@ -1601,7 +1517,7 @@ extern "C" int fqgpu_decode_chunk_indexing(fqgpu_ctx *ctx, const fqgpu_header_st
 // The decode index fqgpu_decode_chunk_indexing built, until the handle's next host-pointer call.
 extern "C" int fqgpu_decode_index(fqgpu_ctx *ctx, int stream, uint8_t *out, size_t cap, size_t *len) {
   if (len) *len = 0;
-  if (!ctx || !ctx->hp_block || stream < 0 || stream > 1 || !len || !ctx->hp_index_built) return FQGPU_E_ARG;
+  if (!ctx || !ctx->hp.block || stream < 0 || stream > 1 || !len || !ctx->hp.index_built) return FQGPU_E_ARG;
   hipError_t he;
   int rc = hp_index_fetch(ctx, stream, out, cap, len, nullptr, &he);
   if (!rc && he != hipSuccess) rc = FQGPU_E_HIP;
@@ -1645,7 +1561,7 @@ static int decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, c
   const size_t n_count_len = s.n_count_len;
   if (bad_record) *bad_record = (size_t)-1;
   if (out_len) *out_len = 0;
-  if (ctx) ctx->hp_crc_what = 0;  // (a range is never digested)
+  if (ctx) ctx->hp.end_digest();  // (a range is never digested)
   if (!out_len || !bad_record || first >= end || end > n_recs) return FQGPU_E_ARG;
   std::vector<uint32_t> rs;
   size_t n_bases = 0;
@@ -1676,7 +1592,7 @@ static int decode_chunk_range(fqgpu_ctx *ctx, const fqgpu_header_streams *hdr, c
   if (!out) return FQGPU_OK;
   if (out_cap < len) return FQGPU_E_OVERFLOW;
   rc = hp_decode_staged(ctx, b, s, indexed ? &plan : nullptr, out, skip, len, recs_out, first, end - first);
-  ctx->hp_crc_what = 0;  // (without indexes the whole chunk was decoded; it still is a range that was asked for)
+  ctx->hp.end_digest();  // (without indexes the whole chunk was decoded; it still is a range that was asked for)
   return rc;
 }
 
@@ -1718,8 +1634,8 @@ extern "C" int fqgpu_ctx_set_check_only(fqgpu_ctx *ctx, int on) {
 // uploaded or built there, so the call runs beside the lane's encode kernels and waits for none of them; after a decode
 // the stream is idle.  FQGPU_E_ARG: no chunk there.
 static int staged_block(const fqgpu_ctx *ctx, const fqgpu_dblock **b) {
-  if (!ctx->hp_block || !ctx->hp_crc_what) return FQGPU_E_ARG;
-  *b = ctx->hp_block;
+  if (!ctx->hp.block || !ctx->hp.crc_what) return FQGPU_E_ARG;
+  *b = ctx->hp.block;
   return FQGPU_OK;
 }
 
@@ -1750,8 +1666,8 @@ extern "C" int fqgpu_chunk_crc32(fqgpu_ctx *ctx, uint32_t *crc, size_t *len) {
   if (!ctx || !crc || !len) return FQGPU_E_ARG;
   if ((rc = staged_block(ctx, &b))) return rc;
   uint32_t c = 0;
-  size_t n = ctx->hp_crc_len;
-  rc = ctx->hp_crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, chunk_view(b), &c, &n)
+  size_t n = ctx->hp.crc_len;
+  rc = ctx->hp.crc_what == 1 ? fq_crc_canonical(ctx, ctx->stream, chunk_view(b), &c, &n)
                              : fq_crc_bytes(ctx, ctx->stream, b->raw, n, &c);
   if (rc) return rc;
   *crc = c;

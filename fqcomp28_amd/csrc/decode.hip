@@ -881,7 +881,7 @@ int idx_jobs_prepare(fqgpu_ctx *ctx, const std::vector<fqgpu_dblock *> &blocks, 
     x.n_sym = (unsigned)b->n_bases; x.stride = ctx->index_stride; x.n_snap = fq_index_n_snap(x.n_sym, x.stride);
     *snap_max = x.n_snap > *snap_max ? x.n_snap : *snap_max;
     for (int s = 0; s < 2; s++) {
-      if ((rc = fq_index_reserve(b, s, fq_index_bytes(x.n_snap, s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS), true))) return rc;
+      if ((rc = b->index[s].grow(fq_index_bytes(x.n_snap, s ? FQGPU_QUAL_MODELS : FQGPU_SEQ_MODELS) + 64, 0, true))) return rc;
       x.index[s] = b->index[s];
     }
     snaps += x.n_snap;

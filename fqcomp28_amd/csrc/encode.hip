@@ -434,7 +434,7 @@ int launch_index(fqgpu_ctx *ctx, EncScratch &sc, const EncPlan &p, const EncView
   const unsigned stride = ctx->index_stride;
   const unsigned n_snap = fq_index_n_snap(p.n_sym, stride);
   const size_t bytes = fq_index_bytes(n_snap, M::B);
-  if (int rc = fq_index_reserve(b, M::STREAM, bytes, true)) return rc;
+  if (int rc = b->index[M::STREAM].grow(bytes + 64, 0, true)) return rc;
   {
     EncStage s{ctx, st, FQ_SPAN("index")};
     hipLaunchKernelGGL(k_index_meta<M>, dim3(n_snap / 256 + 1), dim3(256), 0, st, b->raw, b->recs, v.rec_start, p.R, p.n_sym, stride,

@@ -93,6 +93,31 @@ template <class T> static inline T *fq_dev_alloc(size_t n) {
   return reinterpret_cast<T *>(p);
 }
 
+// A typed device array: pointer and ELEMENTS allocated, the one record of what stands behind a block's buffer.  Reads as its
+// pointer.  grow: room for `need` elements, allocated with `slack` more; never shrinks; the outgrown buffer is freed first
+// (check_free: a failing hipFree is an error); on failure the array is empty.
+template <class T> struct DevArray {
+  T *p = nullptr;
+  size_t n = 0;
+  operator T *() const { return p; }
+  T *operator->() const { return p; }
+  size_t bytes() const { return n * sizeof(T); }
+  int grow(size_t need, size_t slack = 0, bool check_free = false) {
+    if (p && need <= n) return FQGPU_OK;
+    const hipError_t e = release();
+    if (check_free) FQ_HIP(e);
+    if (!(p = fq_dev_alloc<T>(need + slack))) return FQGPU_E_NOMEM;
+    n = need + slack;
+    return FQGPU_OK;
+  }
+  hipError_t release() {
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr;
+    n = 0;
+    return e;
+  }
+};
+
 // Growable device buffer (never shrinks): the per-handle scratch.
 struct DevBuf {
   void *p = nullptr;
@@ -295,6 +320,30 @@ FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, h
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
 
+// The staging block of the host-pointer calls, kept between calls (grow-only device arrays), and what it holds:
+//   - `pending` spans fqgpu_encode_begin .. fqgpu_encode_end; flags, done and used describe the block begun last (done also
+//     serves fqgpu_encode_index behind its end) and mean nothing before one;
+//   - crc_what says what fqgpu_chunk_crc32 and the other chunk calls may read: 0 nothing, 1 the chunk fqgpu_encode_begin
+//     uploaded (its canonical bytes, by its record table), 2 the crc_len bytes a whole-chunk decode has just restored;
+//   - index_built: the block holds the indexes fqgpu_decode_chunk_indexing built (fqgpu_decode_index).  A refused decode call
+//     ends the digest and keeps the indexes, so the two are apart;
+//   - clear() is the ONLY writer of "holds nothing", the handle's part and the block's: whoever acquires the block, fills the
+//     scratch, cancels or fails calls it.
+struct HpStage {
+  fqgpu_dblock *block = nullptr;
+  bool pending = false;
+  unsigned flags = 0;
+  hipStream_t done = nullptr;  // the stream the pending block's last kernel runs on
+  size_t used = 0;             // bytes of the pending chunk up to its last complete record
+  bool index_built = false;
+  int crc_what = 0;
+  size_t crc_len = 0;
+  inline void clear();
+  // the named part of clear() a decode call starts with, before its arguments are looked at: also a refused call ends the
+  // last chunk's digest (and_index: and an indexing decode drops the indexes built before it)
+  void end_digest(bool and_index = false) { crc_what = 0; if (and_index) index_built = false; }
+};
+
 struct fqgpu_ctx {
   int device = 0;
   hipStream_t stream = nullptr;  // uploads, decode
@@ -324,23 +373,12 @@ struct fqgpu_ctx {
   DevBuf dec_chunks, dec_recstart;  // chunk list and per-block rec_start of the indexed decode
   DevBuf dec_idx, dec_entries;      // indexing decode: its job descriptors, the contexts' entries at every snapshot
   KernelTimer *timer = nullptr;
-  // staging block of the host-pointer calls, kept between calls (grow-only device buffers)
-  fqgpu_dblock *hp_block = nullptr;
-  size_t hp_raw = 0, hp_recs = 0, hp_seq = 0, hp_qual = 0, hp_side = 0, hp_npos = 0;  // allocated elements
+  HpStage hp;                         // the staging block of the host-pointer calls and what it holds
   hipEvent_t hp_ev_h2d = nullptr;     // "the block's inputs have arrived": the lane's streams wait for it
   BlockResult *hp_result = nullptr;   // page-locked landing place of the result block
   ParseScratch hp_parse;              // fqgpu_encode_begin without a record table: the table is built on the device
-  bool hp_pending = false;            // a block of fqgpu_encode_begin is in flight (fqgpu_encode_end collects it)
-  unsigned hp_flags = 0;
-  hipStream_t hp_done = nullptr;      // the stream its last kernel runs on
-  size_t hp_used = 0;                 // bytes of the chunk up to its last complete record
   HdrScratch hp_hdr;                  // fqgpu_encode_headers_*: the header fields of the block in flight
   ChunkScratch hp_chunk;              // fqgpu_decode_chunk: header decode and layout
-  bool hp_index_built = false;        // the staging block holds the indexes fqgpu_decode_chunk_indexing built (fqgpu_decode_index)
-  // fqgpu_chunk_crc32: what of the staging block may be digested -- 0 nothing, 1 the chunk fqgpu_encode_begin uploaded (its
-  // canonical bytes, by its record table), 2 the hp_crc_len bytes a whole-chunk decode has just restored
-  int hp_crc_what = 0;
-  size_t hp_crc_len = 0;
   bool check_only = false;            // fqgpu_ctx_set_check_only: fqgpu_decode_chunk takes raw_out == NULL
   CrcScratch crc;
   StatsScratch stats;
@@ -362,17 +400,18 @@ static inline unsigned fq_lanes_for(const fqgpu_ctx *ctx, size_t n_bases) {
 struct fqgpu_dblock {
   int device = 0;
   fqgpu_ctx *owner = nullptr;  // the handle whose lanes code this block (status / fetch synchronise it)
-  uint8_t *raw = nullptr;
+  DevArray<uint8_t> raw;   // raw_len + 64: the kernels' loads run past a line's end
   size_t raw_len = 0;
-  fqgpu_rec *recs = nullptr;
+  DevArray<fqgpu_rec> recs;
   size_t n_recs = 0;
   size_t n_bases = 0;
-  uint8_t *seq = nullptr;  size_t seq_cap = 0;   // capacities the overflow rule is judged against (reference rule or the caller's)
-  uint8_t *qual = nullptr; size_t qual_cap = 0;
-  size_t seq_alloc = 0, qual_alloc = 0;          // bytes allocated behind seq / qual (>= cap + 64)
-  uint16_t *readlens = nullptr, *n_count = nullptr, *n_pos = nullptr;
+  // seq_cap, qual_cap: the capacities the overflow rule is judged against (reference rule or the caller's); the arrays hold
+  // 64 bytes more at least.  n_pos_cap: entries of n_pos provided for; the array holds 16 more at least
+  DevArray<uint8_t> seq, qual;
+  size_t seq_cap = 0, qual_cap = 0;
+  DevArray<uint16_t> readlens, n_count, n_pos;
   size_t n_pos_cap = 0;
-  BlockResult *result = nullptr;  // device
+  DevArray<BlockResult> result;
   BlockResult host_result;        // filled by fqgpu_sync-ing calls
   size_t seq_len = 0, qual_len = 0, n_pos_len = 0;  // stream sizes used by decode
   // "the block's last encode is through", recorded behind its last kernel: the next encode of the SAME block -- on whichever lane it
@@ -383,13 +422,34 @@ struct fqgpu_dblock {
   int home_lane = -1;  // the lane of the block's last encode (api.hip: fq_next_lane)
   int last_op = 0;  // 1 = encode, 2 = decode: which fields of the result block are meaningful
   bool result_pulled = true;  // host_result / stream sizes reflect the last launched operation
-  // decode index (extension): device copy per stream, valid bytes, allocated bytes
-  uint8_t *index[2] = {nullptr, nullptr};
-  size_t index_bytes[2] = {0, 0}, index_cap[2] = {0, 0};
+  void launched(int op) { last_op = op; result_pulled = false; }
+  // the result block and the indexes describe no streams any more
+  void drop_results() { last_op = 0; result_pulled = true; index_bytes[0] = index_bytes[1] = 0; }
+  // decode index (extension): device copy per stream (64 spare bytes behind it), valid bytes
+  DevArray<uint8_t> index[2];
+  size_t index_bytes[2] = {0, 0};
   // diagnostics (fqgpu_dblock_qual_segment_classes): the stamp of the block's last encode; lane home_lane of the owner holds
   // its segment classes as long as that lane's stamp is the same
   unsigned long long diag_stamp = 0;
 };
+
+// The device arrays of a block, ONE list: fqgpu_dblock_destroy frees and fqgpu_ctx_fill_scratch fills what it visits, as
+// f(name, array).  tests/test_build_invariants.py holds it against the DevArray members of the struct.
+#define FQ_DBLOCK_BUFS(X) X(raw) X(recs) X(seq) X(qual) X(readlens) X(n_count) X(n_pos) X(result) X(index[0]) X(index[1])
+template <class F> static inline void fq_dblock_each_buf(fqgpu_dblock &b, F &&f) {
+#define FQ_X(m) f(#m, b.m);
+  FQ_DBLOCK_BUFS(FQ_X)
+#undef FQ_X
+}
+
+inline void HpStage::clear() {
+  pending = index_built = false;
+  crc_what = 0;
+  if (!block) return;
+  block->drop_results();
+  block->seq_len = block->qual_len = block->n_pos_len = 0;
+  block->host_result = BlockResult();
+}
 
 // Decode index of one stream: header, then one snapshot per multiple of `stride` symbols.
 struct FqIndexHeader {
@@ -423,19 +483,6 @@ FQ_HD static inline uint16_t *fq_index_states(uint8_t *index, unsigned B, unsign
   return reinterpret_cast<uint16_t *>(fq_index_snap(index, B, k) + FQ_INDEX_SNAP_HEAD);
 }
 FQ_HD static inline const uint16_t *fq_index_states(const uint8_t *index, unsigned B, unsigned k) { return fq_index_states(const_cast<uint8_t *>(index), B, k); }
-// room on the device for `bytes` of the block's decode index of stream s (never shrinks); check_free: a failing hipFree of
-// the outgrown buffer is an error
-static inline int fq_index_reserve(fqgpu_dblock *b, int s, size_t bytes, bool check_free) {
-  if (bytes <= b->index_cap[s]) return FQGPU_OK;
-  if (b->index[s]) {
-    const hipError_t e = hipFree(b->index[s]);
-    if (check_free) FQ_HIP(e);
-  }
-  b->index[s] = fq_dev_alloc<uint8_t>(bytes + 64);
-  b->index_cap[s] = b->index[s] ? bytes : 0;
-  return b->index[s] ? FQGPU_OK : FQGPU_E_NOMEM;
-}
-
 // ---------------------------------------------------------------- launches (encode.hip / decode.hip / tables.hip)
 int fq_build_freq_tables(int device, hipStream_t st, const uint8_t *raw_dev, const fqgpu_rec *recs_dev,
                          size_t n_recs, uint32_t *seq_counts_dev, uint32_t *qual_counts_dev, size_t n_bases, unsigned min_len);

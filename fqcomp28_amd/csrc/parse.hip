@@ -164,22 +164,19 @@ int fq_parse_records(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, Par
   return FQGPU_OK;
 }
 
-// the two steps with a record table allocated here; on success *recs_dev is hipMalloc'ed and the caller's
+// the two steps with the record table in the caller's array, grown here to the record count
 int fq_parse_on_device(hipStream_t st, const uint8_t *raw_dev, size_t raw_len, DevBuf &scan_tmp,
-                       fqgpu_rec **recs_dev, size_t *n_recs, size_t *n_bases, size_t *n_n) {
-  *recs_dev = nullptr;
+                       DevArray<fqgpu_rec> &recs, size_t *n_recs, size_t *n_bases, size_t *n_n) {
   *n_recs = *n_bases = *n_n = 0;
   ParseScratch ps;
   std::swap(ps.scan_tmp, scan_tmp);
   size_t R = 0;
   int rc = fq_parse_count(st, raw_dev, raw_len, ps, &R);
-  fqgpu_rec *recs = nullptr;
-  if (!rc && !(recs = fq_dev_alloc<fqgpu_rec>(R))) rc = FQGPU_E_NOMEM;
+  if (!rc) rc = recs.grow(R);
   if (!rc) rc = fq_parse_records(st, raw_dev, raw_len, ps, recs, R, n_bases, n_n, nullptr);
   std::swap(ps.scan_tmp, scan_tmp);
   fq_release_bufs(ps);  // (scan_tmp is the caller's again: ps holds an empty one)
-  if (rc) { if (recs) (void)hipFree(recs); return rc; }
-  *recs_dev = recs;
+  if (rc) return rc;
   *n_recs = R;
   return FQGPU_OK;
 }

@@ -139,15 +139,16 @@ def test_seq_setfunc_table_sits_at_lds_address_zero(tmp_path):
 
 def test_every_scratch_buffer_is_in_the_list_that_frees_and_fills_it():
     """fqgpu_ctx_destroy frees and fqgpu_ctx_fill_scratch fills what ONE enumeration visits: per scratch struct the list
-    behind it (FQ_SCRATCH_BUFS, fqgpu_internal.h), for the staging block dblock_each_buf (api.hip).  A DevBuf member that
-    is missing from its struct's list, or a block pointer missing from dblock_each_buf, would be neither freed nor filled.
+    behind it (FQ_SCRATCH_BUFS, fqgpu_internal.h), for a block the list behind fqgpu_dblock (FQ_DBLOCK_BUFS).  A DevBuf
+    member that is missing from its struct's list, or a device array of a block missing from FQ_DBLOCK_BUFS, would be neither
+    freed nor filled.
 
     The check reads the sources as text, so it also trips on a spelling it does not know.  When it does:
       - a new DevBuf member: add FQ_B(Struct, member) to the FQ_SCRATCH_BUFS list behind its struct; declare it as the
         others are (`DevBuf a, b;` -- plain members, no initialiser), or teach `members` below the new form;
       - a new scratch struct: give it a FQ_SCRATCH_BUFS list, visit it in ctx_each_devbuf and add its expression to `visited`;
-      - a new device pointer in fqgpu_dblock: add it to dblock_each_buf with the bytes allocated for it, and to both lists
-        below (`owned` takes every non-const pointer member, of any type)."""
+      - a new device buffer in fqgpu_dblock: declare it as a DevArray<T> and add X(member) to FQ_DBLOCK_BUFS.  A bare
+        non-const pointer member is taken for a buffer the list cannot visit: only `owner`, the handle, is one."""
     csrc = os.path.join(ROOT, "fqcomp28_amd", "csrc")
     head = re.sub(r"//.*", "", open(os.path.join(csrc, "fqgpu_internal.h")).read())
     lists = {m.group(1): re.findall(r"FQ_B\(\s*(\w+)\s*,\s*(\w+)\s*\)", m.group(2) + ")")
@@ -167,14 +168,23 @@ def test_every_scratch_buffer_is_in_the_list_that_frees_and_fills_it():
     assert visited == {"l", "l.enc[s]", "*ctx", "ctx->hp_parse", "ctx->hp_hdr", "ctx->hp_chunk", "ctx->crc", "ctx->stats", "ctx->select"}, visited
     fields = dict(re.findall(r"^\s*(\w+Scratch)\s+(\w+)(?:\[\d\])?;", structs["fqgpu_ctx"] + structs["EncLane"], re.M))
     assert set(fields) == set(lists) - {"EncLane", "fqgpu_ctx"}, sorted(fields)
-    # the staging block: every device pointer of a block
-    each = re.search(r"static void dblock_each_buf\([^)]*\) \{.*?^\}", api, re.S | re.M).group(0)
-    assert re.findall(r'f\("[^"]+", b->([\w\[\]]+),', each) == ["raw", "recs", "seq", "qual", "readlens", "n_count", "n_pos", "result", "index[0]", "index[1]"]
-    # (every pointer member the block may write through, whatever its type; `owner` is the handle, not a buffer)
+    # a block: every device array of fqgpu_dblock is in the list, every entry of the list names one, and both walks use it
+    listed = re.findall(r"X\(([\w\[\]]+)\)", re.search(r"^#define FQ_DBLOCK_BUFS\(X\)(.*)$", head, re.M).group(1))
+    arrays = []
+    for decl in re.findall(r"^\s*DevArray<\w+>\s+([^;()]+);", structs["fqgpu_dblock"], re.M):
+        for name in (n.strip() for n in decl.split(",")):
+            m = re.fullmatch(r"(\w+)\[(\d+)\]", name)
+            arrays += ["%s[%d]" % (m.group(1), i) for i in range(int(m.group(2)))] if m else [name]
+    assert len(arrays) >= 10 and len(set(listed)) == len(listed), (arrays, listed)
+    assert sorted(listed) == sorted(arrays), \
+        ("a device array of fqgpu_dblock that FQ_DBLOCK_BUFS does not visit, or an entry that names no member", sorted(set(arrays) ^ set(listed)))
+    # (no bare pointer the block may write through: a buffer declared that way would escape the list; `owner` is the handle)
     owned = re.findall(r"^\s*(?!const\b)\w+ \*(.*?);", structs["fqgpu_dblock"], re.M)
     names = sorted(re.sub(r"\s*=.*", "", n).strip(" *") for decl in owned for n in re.split(r",(?![^{]*\})", re.sub(r";.*", "", decl)))
-    assert names == sorted(["owner", "raw", "recs", "seq", "qual", "readlens", "n_count", "n_pos", "result", "index[2]"]), \
-        ("a device pointer of fqgpu_dblock that dblock_each_buf does not visit, or a member this test cannot read", names)
+    assert names == ["owner"], ("a device pointer of fqgpu_dblock that is no DevArray, or a member this test cannot read", names)
+    for fn in ("fqgpu_dblock_destroy", "fqgpu_ctx_fill_scratch"):
+        body = re.search(r"^extern \"C\" \w+ %s\(.*?^\}" % fn, api, re.S | re.M).group(0)
+        assert "fq_dblock_each_buf(" in body, fn
     # the exemptions name buffers that exist
     for owner, name in re.findall(r'\{"(\w+)", "(\w+)", "', re.search(r"kScratchState\[\] = \{(.*?)^\};", api, re.S | re.M).group(1)):
         struct = {"lane": "EncLane", "crc": "CrcScratch"}[owner]

@@ -474,3 +474,71 @@ def test_chunk_services_small_chunk_after_large_chunk(F, byte):
                 TP.holds(ctx.chunk_probe(probes, P, len(recs)), PR.probe_of(raw, table, probes, P), "probe alone")
     finally:
         ctx.close()
+
+
+# ================================================================ the staging block's sizes
+# (buffers, bytes) that fill_scratch(0xA5) returns after each step of test_staging_block_sizes_over_a_host_pointer_history,
+# measured with FQGPU_LIB pointing at the library of the parent commit (fbea9db, before the block's buffers became typed
+# arrays): the staging block allocates what it allocated, and the fill covers what it covered.
+PARENT_PAIRS = [(56, 125979823), (58, 128121608), (74, 128131764), (75, 128137420), (75, 128137420)]
+
+
+@functools.lru_cache(maxsize=None)
+def hp_chunks():
+    """-> (tables, small, large): the fixture's tables; a chunk of 4 of its reads; one of 400 records of 200 bases (two reads
+    each: 80 000 symbols, a snapshot in either index at the smallest stride)"""
+    raw, recs = O.load_fastq(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "SRR065390_sub_1.fastq"))
+    _, _, sft, qft = O.freq_tables(raw, recs)
+    b = raw.tobytes()
+    line = lambda r, off: b[int(r[off]): int(r[off]) + int(r["len"])]
+    small = TH.fastq_of([b"@run1.%d lane:%d length=100" % (i + 1, i % 8) for i in range(4)])
+    large = b"".join(b"@run2.%d lane:%d length=200\n" % (i + 1, i % 8) + line(recs[2 * i], "seq_off") + line(recs[2 * i + 1], "seq_off") +
+                     b"\n+\n" + line(recs[2 * i], "qual_off") + line(recs[2 * i + 1], "qual_off") + b"\n" for i in range(400))
+    small.setflags(write=False)
+    return (sft, qft), small, np.frombuffer(large, dtype=np.uint8)
+
+
+def test_staging_block_sizes_over_a_host_pointer_history(F):
+    """small encode, large encode with decode indexes, indexing decode of the small chunk, indexed decode of the large one, the
+    small encode again, all through ONE staging block, a fill behind each: every output is the oracle's (the restored chunks
+    their inputs, the built index a fresh handle's encoder's), and every fill visits the buffers and bytes the parent's visits"""
+    tables, small, large = hp_chunks()
+    first_small, first_large = b"@run1.1 lane:0 length=100", b"@run2.1 lane:0 length=200"
+    octx = O.OracleCtx(*tables)
+    want_small, want_large = (octx.encode(c, O.parse_fastq(c)) for c in (small, large))
+    octx.close()
+    fresh = F.Context(*tables)
+    fresh.set_index_stride(STRIDE)
+    small_index = TD.encode(F, fresh, small, first_small, True)["index"]
+    fresh.close()
+    ctx = F.Context(*tables)
+    ctx.set_index_stride(STRIDE)
+    pairs = []
+
+    def encoded(chunk, first, want, index):
+        g = TD.encode(F, ctx, chunk, first, index)
+        assert want["rc"] == 0
+        same_streams(g, want, ("encode", chunk.size))
+        assert np.array_equal(g["recs"], O.parse_fastq(chunk)) and g["used_len"] == chunk.size
+        pairs.append(ctx.fill_scratch(0xA5))
+        return g
+
+    try:
+        g_small = encoded(small, first_small, want_small, False)
+        g_large = encoded(large, first_large, want_large, True)
+        assert all(TB.index_fields(ix, s)[1] == 1 for s, ix in enumerate(g_large["index"]))
+        d = ctx.decode_chunk(TD.fmt_of(first_small), g_small["header_fields"], g_small["readlens"], g_small["seq"], g_small["qual"],
+                             g_small["n_count"], g_small["n_pos"], small.size, build_index=True)
+        assert d["rc"] == 0 and d["bad_record"] is None and np.array_equal(d["raw"], small)
+        TB.same_index(d["index"], small_index, "built by the decode")
+        pairs.append(ctx.fill_scratch(0xA5))
+        recs = O.parse_fastq(large)
+        w = want_large
+        rc, out = ctx.decode_block(w["seq"], w["qual"], w["n_count"], w["n_pos"], recs, O.blank_skeleton(large, recs), index=g_large["index"])
+        assert rc == 0 and np.array_equal(out, large)
+        pairs.append(ctx.fill_scratch(0xA5))
+        encoded(small, first_small, want_small, False)
+    finally:
+        ctx.close()
+    print("fill_scratch pairs:", pairs)
+    assert pairs == PARENT_PAIRS, pairs
