@@ -1095,10 +1095,11 @@ def test_gpu_parser_matches_cpu_parser(F, golden_dir):
         assert np.array_equal(g[k], e[k]), k
     b.close()
     # malformed input is refused
-    for bad in (b"@r\nACGT\n-\nIIII\n", b"@r\nACGT\n+\nIII\n", b"r\nACGT\n+\nIIII\n", b"@r\nAC\n+\nII\n", b"no newline"):
+    for bad, code in ((b"@r\nACGT\n-\nIIII\n", -4), (b"@r\nACGT\n+\nIII\n", -4), (b"r\nACGT\n+\nIIII\n", -4), (b"@r\nAC\n+\nII\n", -2),
+                      (b"no newline", -4)):
         with pytest.raises(F.FqgpuError) as ei:
             ctx.dblock(np.frombuffer(bad, dtype=np.uint8))
-        assert ei.value.code in (-4, -2)
+        assert ei.value.code == code, bad
     ctx.close()
 
 
