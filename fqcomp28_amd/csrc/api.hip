@@ -485,10 +485,21 @@ static int upload_tables(fqgpu_ctx *ctx, int stream, const void *ft) {
   DevTables &t = ctx->tab[stream];
   const uint8_t *p = static_cast<const uint8_t *>(ft);
   const uint32_t *logs = reinterpret_cast<const uint32_t *>(p + l.logs_off);
+  const int16_t *norm = reinterpret_cast<const int16_t *>(p);
   uint32_t max_log = 0;
   for (int i = 0; i < l.n_models; i++) {
     if (logs[i] < 5 || logs[i] > 12) return FQGPU_E_ARG;  // FSE_MIN_TABLELOG .. FSE_MAX_TABLELOG
     if (logs[i] > max_log) max_log = logs[i];
+    // every entry -1 or more, and the entries sum to 2^log with -1 counted as 1: refused here, before a kernel runs.
+    // (k_build_tables counts an entry below -1 as 0 and would pass [-2, 2^log, 0, 0]; and behind its own refusal of a
+    // sum the transition-table kernels would still walk that context's unbuilt tables.)
+    uint32_t sum = 0;
+    for (int s = 0; s < l.alpha; s++) {
+      const int n = norm[(size_t)i * l.alpha + s];
+      if (n < -1) return FQGPU_E_ARG;
+      sum += n == -1 ? 1u : (uint32_t)n;
+    }
+    if (sum != (1u << logs[i])) return FQGPU_E_ARG;
   }
   t.max_log = max_log;
   t.norm = fq_dev_alloc<int16_t>((size_t)l.n_models * l.alpha);

@@ -98,7 +98,13 @@ def test_device_tables_match_oracle_word_for_word(F, golden_dir):
 
 
 def test_tables_from_counts_normalisation_corner_cases(F):
-    """Count vectors that hit the low-probability (-1), the rounding and the normalizeM2 paths."""
+    """One seeded draw, every count 1 or more.  By the classifier of tests/tables_ref.py it takes, in the 8192 quality
+    contexts: the low-probability arm (2788 contexts), both sides of every rounding threshold rtb[1..7], a tie for the
+    largest probability, still == 0 and still < 0 on the simple path, logs 7 to 11, and FSE_normalizeM2 in 142 contexts --
+    all 142 through its proportional spread, 29 of them through its second low-one pass.  It holds no count of 0, no log
+    5 or 6, no refusal and none of M2's other branches; the 256 sequence contexts take logs 8 to 11 and the wrap ([1, 1, 1,
+    1]).  The table words are compared in every eleventh quality context (11 of the M2 ones) and in no sequence context.
+    The families that aim at each branch are in tests/test_gpu_tables.py."""
     rng = np.random.default_rng(5)
     sc = 1 + rng.integers(0, 3000, (256, 4)).astype(np.uint32)
     sc[3] = [1, 1, 1, 1]
@@ -118,7 +124,7 @@ def test_tables_from_counts_normalisation_corner_cases(F):
     gs, gq = F.tables_from_counts(sc, qc)
     assert gs.tobytes() == osft.tobytes()
     assert gq.tobytes() == oqft.tobytes()
-    # and the tables built from them (covers logs 5..11 and many -1 symbols)
+    # and the tables built from them (logs 7..11 and many -1 symbols)
     ctx = F.Context(gs, gq)
     for m in range(0, 8192, 11):
         ct, dt = ctx.dump_tables(1, m)
