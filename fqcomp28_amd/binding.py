@@ -188,6 +188,11 @@ _PROTOS = {
                                            C.c_void_p, C.c_void_p]),
     "fqgpu_dblock_pair_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_merge_check": (C.c_int, [C.c_void_p]),
+    "fqgpu_chunk_pair_merge": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "fqgpu_dblock_pair_merge": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fqgpu_chunk_pair_names": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_pair_names": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_size_t)]),
     "fqgpu_read_id_len": (C.c_size_t, [C.c_void_p, C.c_size_t]),
@@ -521,6 +526,60 @@ def _correct_call(fn, front, count, insert, spec, want_arrays=True, want_report=
     return dict(rc=rc, report=report, fixed_a=fa, fixed_b=fb)
 
 
+MERGE_REPORT_WORDS = 16
+MERGE_REPORT_NAMES = ("n_pairs", "pairs_with_insert", "pairs_merged", "bases_merged", "bytes_out", "overlap_bases", "places_disagree",
+                      "places_n", "bases_dropped_a", "bases_dropped_b", "pairs_unmarked", "pairs_too_short")
+
+
+def read_merge(floor_q=2, min_len=1, reserved=(0, 0, 0, 0, 0, 0)):
+    """an fqgpu_merge (include/fqgpu.h) as a uint32 array of eight words; the defaults are the tool's"""
+    return np.array([floor_q, min_len, *reserved], dtype=np.uint32)
+
+
+def merge_check(spec):
+    """fqgpu_merge_check -> rc (host only)"""
+    return lib().fqgpu_merge_check(_p(None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)))
+
+
+def _merge_call(fn, front, count, insert, mark, spec, cap=None, out=None, want_out=True, want_merged=True, want_report=True,
+                want_len=True):
+    """A device merging call -> dict(rc, out, out_len, report, merged): report a fresh uint64 array of MERGE_REPORT_WORDS, merged
+    the uint8 bits of the merged pairs or None, out_len the call's *out_len, out the merged bytes (uint8[out_len]) when the call
+    wrote them, else the buffer as the call left it.  insert: None (NULL), or uint16 -- fewer than count are padded with zeros,
+    so that the library never reads behind them; mark: None, or the uint8 bits.  out: the caller's own uint8 buffer (its size is
+    the capacity said, or `cap` if given); else cap bytes are provided -- cap None: as many as a size query (out == NULL) asks
+    for; want_out False: out == NULL"""
+    spec = None if spec is None else np.ascontiguousarray(spec, dtype=np.uint32)
+    insert = None if insert is None else np.ascontiguousarray(insert, dtype=np.uint16)
+    if insert is not None and insert.size < count:
+        insert = np.concatenate((insert, np.zeros(count - insert.size, dtype=np.uint16)))
+    mark = None if mark is None else np.ascontiguousarray(mark, dtype=np.uint8)
+    n_bits = max((count + 7) // 8, 1)
+
+    def call(buf, cap_said):
+        report = np.zeros(MERGE_REPORT_WORDS, dtype=np.uint64)
+        merged = np.zeros(n_bits, dtype=np.uint8) if want_merged else None
+        n = C.c_size_t(0)
+        rc = fn(*front, count, _p(insert), _p(mark), _p(spec), _p(buf), cap_said, C.byref(n) if want_len else None,
+                _p(report) if want_report else None, _p(merged))
+        return rc, int(n.value), report, None if merged is None else merged[:(count + 7) // 8]
+
+    if not want_out:
+        rc, n, report, merged = call(None, 0)
+        return dict(rc=rc, out=None, out_len=n, report=report, merged=merged)
+    if out is None:
+        if cap is None:
+            rc, n, report, merged = call(None, 0)
+            if rc != 0:
+                return dict(rc=rc, out=None, out_len=n, report=report, merged=merged)
+            cap = n
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+    elif cap is None:
+        cap = out.size
+    rc, n, report, merged = call(out, cap)
+    return dict(rc=rc, out=out[:n] if rc == 0 else out, out_len=n, report=report, merged=merged)
+
+
 def read_id_len(header_line):
     """fqgpu_read_id_len (host only): the length of the read id of a header line (bytes, with its '@')"""
     line = np.frombuffer(bytes(header_line), dtype=np.uint8)
@@ -738,6 +797,13 @@ class DBlock:
         return _correct_call(lib().fqgpu_dblock_pair_correct, (self.ctx.h, self.h, first, other.h if other is not None else None, other_first),
                              count, insert, spec, **kw)
 
+    def pair_merge(self, first, other, other_first, count, insert, mark, spec, **kw):
+        """fqgpu_dblock_pair_merge: with the insert sizes `insert` (pair_overlap's) and the mark bits `mark` (None: every pair)
+        this block's records first + i (mate 1) and `other`'s other_first + i (mate 2), i < count, merged into one read each for
+        `spec` (read_merge); both blocks stay as they are -> dict(rc, out, out_len, report, merged); see _merge_call"""
+        return _merge_call(lib().fqgpu_dblock_pair_merge, (self.ctx.h, self.h, first, other.h if other is not None else None, other_first),
+                           count, insert, mark, spec, **kw)
+
     def pair_overlap(self, first, other, other_first, count, spec, **kw):
         """fqgpu_dblock_pair_overlap: the mate overlap of this block's records first + i (mate 1) and `other`'s other_first + i
         (mate 2), i < count, for `spec` (read_overlap) -> dict(rc, out, limit_a, limit_b, insert); see _overlap_call"""
@@ -911,6 +977,12 @@ class Context:
         on the Context `other` (mate 2); it CHANGES both staged chunks -> as DBlock.pair_correct"""
         return _correct_call(lib().fqgpu_chunk_pair_correct, (self.h, first, other.h if other is not None else None, other_first), count, insert,
                              spec, **kw)
+
+    def chunk_pair_merge(self, first, other, other_first, count, insert, mark, spec, **kw):
+        """fqgpu_chunk_pair_merge: the mates of the chunk staged here (mate 1) and of the chunk staged on the Context `other`
+        (mate 2) merged; both staged chunks stay as they are -> as DBlock.pair_merge"""
+        return _merge_call(lib().fqgpu_chunk_pair_merge, (self.h, first, other.h if other is not None else None, other_first), count, insert,
+                           mark, spec, **kw)
 
     def chunk_pair_overlap(self, first, other, other_first, count, spec, **kw):
         """fqgpu_chunk_pair_overlap: the mate overlap of the chunk staged here (mate 1) and the chunk staged on the Context

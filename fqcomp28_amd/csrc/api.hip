@@ -1974,3 +1974,36 @@ extern "C" int fqgpu_dblock_pair_correct(fqgpu_ctx *ctx, fqgpu_dblock *ba, size_
                                          uint16_t *fixed_b_out) {
   return correct_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, insert_in, c, report, fixed_a_out, fixed_b_out);
 }
+
+// The merging calls: nothing is patched, so the two sides may be one chunk.  `out` is written behind the verdict alone.
+static int merge_call(bool staged, fqgpu_ctx *ctx_a, fqgpu_ctx *ctx_b, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b,
+                      size_t count, const uint16_t *insert_in, const uint8_t *mark_in, const fqgpu_merge *m, uint8_t *out, size_t out_cap,
+                      size_t *out_len, uint64_t *report, uint8_t *merged_out) {
+  if (const int rc = use_device(ctx_a ? ctx_a->device : 0)) return rc;
+  const auto run = [&]() -> int {
+    if (!report || !out_len) return FQGPU_E_ARG;
+    if (!ctx_a || !insert_in || fqgpu_merge_check(m) != FQGPU_OK) return FQGPU_E_ARG;
+    FqChunkView a, b;
+    if (const int rc = pair_sides(staged, ctx_a, ctx_b, ba, first_a, bb, first_b, count, false, &a, &b)) return rc;
+    return fq_pair_merge(ctx_a, ctx_a->stream, a, b, insert_in, mark_in, m, out, out_cap, out_len, report, merged_out);
+  };
+  const int rc = run();
+  if (rc == FQGPU_E_ARG) {
+    if (out_len) *out_len = 0;
+    if (report) memset(report, 0, FQGPU_MERGE_REPORT_WORDS * sizeof(uint64_t));
+    if (merged_out && count) memset(merged_out, 0, (count + 7) / 8);
+  }
+  return rc;
+}
+
+extern "C" int fqgpu_chunk_pair_merge(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const uint16_t *insert_in,
+                                      const uint8_t *mark_in, const fqgpu_merge *m, uint8_t *out, size_t out_cap, size_t *out_len,
+                                      uint64_t *report, uint8_t *merged_out) {
+  return merge_call(true, ctx_a, ctx_b, nullptr, first_a, nullptr, first_b, count, insert_in, mark_in, m, out, out_cap, out_len, report, merged_out);
+}
+
+extern "C" int fqgpu_dblock_pair_merge(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
+                                       const uint16_t *insert_in, const uint8_t *mark_in, const fqgpu_merge *m, uint8_t *out, size_t out_cap,
+                                       size_t *out_len, uint64_t *report, uint8_t *merged_out) {
+  return merge_call(false, ctx, nullptr, ba, first_a, bb, first_b, count, insert_in, mark_in, m, out, out_cap, out_len, report, merged_out);
+}

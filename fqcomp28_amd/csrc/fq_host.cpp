@@ -189,6 +189,14 @@ extern "C" int fqgpu_correct_check(const fqgpu_correct *c) {
   return FQGPU_OK;
 }
 
+// The merge of two mates into one read (pair.hip builds it): what a spec may say.
+extern "C" int fqgpu_merge_check(const fqgpu_merge *m) {
+  if (!m || m->floor_q > 63u || m->min_len < 1u || m->min_len > 1023u) return FQGPU_E_ARG;
+  for (uint32_t r : m->reserved)
+    if (r) return FQGPU_E_ARG;
+  return FQGPU_OK;
+}
+
 // Poly-X tails and the sliding-window cut (select.hip applies them): what a tail may say.
 extern "C" int fqgpu_tail_check(const fqgpu_tail *x) {
   if (!x || x->poly_bases > 15u || x->poly_max_mism > 255u || x->window_len > 32u || x->reserved[0] || x->reserved[1]) return FQGPU_E_ARG;

@@ -294,6 +294,9 @@ FQ_SCRATCH_BUFS(StatsScratch, FQ_B(StatsScratch, out), FQ_B(StatsScratch, slabs)
 //   the probe      its u64 result tables and -- when asked for -- the records' places, n uint16_t each
 //   the overlap    its u64 result words and the pairs' limit1, limit2 and I, three arrays of uint16_t
 //   the correction the caller's inserts and the pairs' changed places, two arrays of uint16_t; its counters are the result words
+//   the merge      the caller's inserts, per pair the merged record's size (a uint32_t), the merged bits (a u64 word per 64
+//                  pairs) and the merged records themselves, to the next multiple of 16 bytes; the records' places are `koff`,
+//                  the caller's mark `mark`; its counters are the result words
 //   every call     `res`, the result words (SelectResult, sel_words.h), and `host`, their page-locked landing place, between
 //                  begin and finish
 struct SelectResult;
@@ -303,6 +306,7 @@ struct SelectScratch {
   DevBuf mark, limit;
   DevBuf overlap_out, overlap_pairs;
   DevBuf correct_in, correct_fixed;
+  DevBuf merge_in, merge_size, merge_bits, merge_out;
   void *host = nullptr;
   void release_host();
   // The frame of a call: begin reserves `res`, allocates `host` once and queues the zeroing of the result words on st; finish
@@ -315,7 +319,8 @@ FQ_SCRATCH_BUFS(SelectScratch, FQ_B(SelectScratch, ksize), FQ_B(SelectScratch, h
                 FQ_B(SelectScratch, places), FQ_B(SelectScratch, keep), FQ_B(SelectScratch, koff), FQ_B(SelectScratch, dst),
                 FQ_B(SelectScratch, res), FQ_B(SelectScratch, scan_tmp), FQ_B(SelectScratch, probe_out), FQ_B(SelectScratch, probe_places),
                 FQ_B(SelectScratch, mark), FQ_B(SelectScratch, limit), FQ_B(SelectScratch, overlap_out), FQ_B(SelectScratch, overlap_pairs),
-                FQ_B(SelectScratch, correct_in), FQ_B(SelectScratch, correct_fixed))
+                FQ_B(SelectScratch, correct_in), FQ_B(SelectScratch, correct_fixed), FQ_B(SelectScratch, merge_in),
+                FQ_B(SelectScratch, merge_size), FQ_B(SelectScratch, merge_bits), FQ_B(SelectScratch, merge_out))
 
 #define FQ_MAX_LANES 8
 #define FQ_RECENT_BLOCKS 8
@@ -598,6 +603,13 @@ uint32_t fq_overlap_fingerprint(const fqgpu_overlap *o);  // fq_host.cpp: zlib's
 // chunk, of length 0 or above 512, a byte inside an overlap that cannot be judged
 int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, const uint16_t *insert_in,
                     const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out, uint16_t *fixed_b_out);
+// The merge of the mates into one read (the spec has passed its check), with the host's insert_in[i] and mark_in (nullptr: every
+// pair is marked); both chunks stay as they are.  *out_len, report[0, FQGPU_MERGE_REPORT_WORDS) and -- where not nullptr --
+// merged_out on the host, and, out != nullptr and out_cap enough, one copy of *out_len bytes into out (else FQGPU_E_OVERFLOW).
+// FQGPU_E_ARG with `out` untouched, *out_len and the report zeroed and merged_out the caller's to zero: an insert the lengths
+// do not allow, a merged pair's record outside its chunk or of length 0, a byte of a merged pair that cannot be judged
+int fq_pair_merge(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, const uint16_t *insert_in, const uint8_t *mark_in,
+                  const fqgpu_merge *m, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *merged_out);
 uint32_t fq_probes_fingerprint(const fqgpu_probes *p);  // fq_host.cpp: zlib's CRC-32 of the bytes of probe[0 .. n)
 
 // generic exclusive scans (scan.hip): out has n+1 entries, out[n] = total

@@ -1,5 +1,5 @@
 // The calls on the records of TWO chunks that lie in HBM, mate 1's and mate 2's (include/fqgpu.h: fqgpu_chunk_pair_names,
-// fqgpu_chunk_pair_overlap, fqgpu_chunk_pair_correct and their fqgpu_dblock_* forms).  Extension: nothing in the reference.
+// fqgpu_chunk_pair_overlap, fqgpu_chunk_pair_correct, fqgpu_chunk_pair_merge and their fqgpu_dblock_* forms).  Extension: nothing in the reference.
 // Each takes two views (FqChunkView, fqgpu_internal.h) of one count, is one kernel over the pairs, and lands its verdict in
 // the selection's result words (sel_words.h), whose packed byte compares it shares with select.hip.
 //
@@ -14,6 +14,9 @@
 // k_pair_correct is the one kernel of the library that CHANGES a chunk: with the pairs' insert sizes it walks each overlap
 // once, eight places to a lane, and where the mates disagree and one base is confident and the other poor it replaces the
 // poor one -- launched twice, first to judge and count, then, if nothing was refused, to store.
+//
+// k_merge_size and k_merge_emit write the two mates of every overlapping pair as ONE read into a buffer of the handle: sizes by
+// a lane per pair, places by the selection's scan, the bytes by a lane per 16-byte word of the output.
 //
 // All global stores are ordinary vector stores from plain C++.
 #include "fqgpu_internal.h"
@@ -429,6 +432,233 @@ k_pair_correct(const PairSide A, const PairSide B, unsigned count, const uint16_
   if (__any(bad) && lane == 0) *bad_out = 1u;  // (every writer stores the same value)
 }
 
+// ---- the two mates merged into one read (include/fqgpu.h, fqgpu_chunk_pair_merge).  Two kernels with the selection's scan
+// between them, and no chunk is written.  k_merge_size is lane = pair: the insert, the mark bit and -- for a pair with an insert
+// -- the two table entries; it holds the inserts against the lengths, finds the merged pairs and their records inside their
+// chunks, and leaves per pair the record's size (the header line without its '\n' + 2 I + 5, or 0), per wave the merged bits and the counters that
+// need no line.  fq_scan_u32_to_u64 turns the sizes into the records' places, 64-bit as the selection's koff.  k_merge_emit is
+// driven by the OUTPUT, as k_select_gather is: a workgroup owns an aligned 16 KiB tile of the merged bytes and finds the tile's
+// first and last record with two uniform searches; a lane owns four aligned 16-byte words of it, one in each of four rounds,
+// and finds a word's record with sel_find between those two.  A word inside the header line is one unaligned load from mate 1.  A word inside the bases or inside the
+// qualities covers the places [p0, p0 + 16): sixteen bytes of s1 and of q1 at p0 and the sixteen bytes of s2 and of q2 that END
+// at j = I - 1 - p0, read in reverse -- both kinds of word need all four lines, the base for the quality and the quality for the
+// base.  Such a window of mate 2 starts at I - 16 - p0 >= 0, inside the line, because the whole word lies in front of place I;
+// a side none of whose sixteen places exists is not loaded, and a load behind a line's end falls into the chunk or its 64 spare
+// bytes.  Every other word -- one that holds a seam: header | bases | "\n+\n" | qualities | '\n' | the next record -- is put
+// together byte by byte with mg_byte, as the gather does with sel_byte.  A place is counted and judged once, by the lane that
+// owns its BASE byte, so the sums do not depend on the tiling; a wave reduction, then one atomic per workgroup and word.
+// Stores go to the handle's merge buffer alone, which reaches to the next multiple of 16.
+constexpr unsigned MG_EMIT_THREADS = 256, MG_EMIT_WORDS = 4, MG_TILE_BYTES = MG_EMIT_THREADS * 16 * MG_EMIT_WORDS;  // (the gather's tile)
+constexpr unsigned MG_BYTES = 4, MG_OVERLAP = 5, MG_COUNTERS = 12;  // report words: bytes_out; the emit pass's first of three; all
+static_assert(FQGPU_MERGE_REPORT_WORDS <= FQGPU_TAIL_REPORT_WORDS, "the counters are the selection result's words");
+
+// the start of record i's header line in its chunk
+__device__ __forceinline__ unsigned long long mg_h0(const PairSide &s, unsigned long long i) {
+  if (!(i || s.prev)) return 0ull;
+  const fqgpu_rec before = s.recs[(long long)i - 1];
+  return (unsigned long long)before.qual_off + before.len + 1ull;
+}
+
+__global__ void __launch_bounds__(OV_THREADS)
+k_merge_size(const PairSide A, const PairSide B, unsigned count, const uint16_t *__restrict__ inserts, const unsigned long long *__restrict__ mark,
+             unsigned min_len, uint32_t *__restrict__ msize, unsigned long long *__restrict__ mbits, SelectResult *__restrict__ res) {
+  const unsigned lane = threadIdx.x;
+  const unsigned long long i = (unsigned long long)blockIdx.x * OV_WG_PAIRS + lane;
+  const bool have = i < count;
+  const unsigned ins = have ? inserts[i] : 0u;
+  const bool marked = have && (!mark || ((mark[blockIdx.x] >> lane) & 1ull));
+  fqgpu_rec ra = {0u, 0u, 0u}, rb = {0u, 0u, 0u};
+  if (ins) {  // (a pair without an insert: not its table entries either)
+    ra = A.recs[i];
+    rb = B.recs[i];
+  }
+  const bool valid = !ins || (ra.len <= FQGPU_OVERLAP_MAX_LEN && rb.len <= FQGPU_OVERLAP_MAX_LEN && ins + 1u <= ra.len + rb.len);
+  bool merged = ins && valid && marked && ins >= min_len, bad = !valid;
+  unsigned hl = 0;
+  if (merged) {
+    const auto inside = [](const fqgpu_rec &r, unsigned long long raw_len) {
+      return r.len != 0 && (unsigned long long)r.seq_off + r.len <= raw_len && (unsigned long long)r.qual_off + r.len <= raw_len;
+    };
+    const unsigned long long h0 = mg_h0(A, i);
+    merged = inside(ra, A.raw_len) && inside(rb, B.raw_len) && h0 + 2ull <= ra.seq_off;
+    bad = !merged;
+    if (merged) hl = (unsigned)(ra.seq_off - h0);
+  }
+  const unsigned size = merged ? hl + 2u * ins + 4u : 0u;
+  if (have) msize[i] = size;
+  const unsigned long long bits = __ballot(merged);
+  if (lane == 0) mbits[blockIdx.x] = bits;
+  const unsigned cnt[MG_COUNTERS] = {0u,
+                            (unsigned)__popcll(__ballot(ins != 0u)),
+                            (unsigned)__popcll(bits),
+                            cor_wave_sum(merged ? ins : 0u),
+                            cor_wave_sum(size),
+                            0u,
+                            0u,
+                            0u,
+                            cor_wave_sum(merged ? ra.len - min(ra.len, ins) : 0u),
+                            cor_wave_sum(merged ? rb.len - min(rb.len, ins) : 0u),
+                            (unsigned)__popcll(__ballot(ins != 0u && !marked)),
+                            (unsigned)__popcll(__ballot(ins != 0u && marked && ins < min_len))};
+#pragma unroll
+  for (unsigned k = 1; k < MG_COUNTERS; k++)
+    if (lane == k && cnt[k]) atomicAdd(&res->w[k], (unsigned long long)cnt[k]);
+  if (__any(bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
+}
+
+// a merged pair as the emit pass sees it: where its pieces come from
+struct MgRec {
+  unsigned long long h0;  // mate 1's header line in its chunk
+  unsigned hl, I, L1, L2, s1, q1, s2, q2;
+};
+__device__ __forceinline__ MgRec mg_rec(const PairSide &A, const PairSide &B, const uint16_t *__restrict__ inserts, unsigned r) {
+  const fqgpu_rec ra = A.recs[r], rb = B.recs[r];
+  MgRec c;
+  c.h0 = mg_h0(A, r);
+  c.hl = (unsigned)(ra.seq_off - c.h0);
+  c.I = inserts[r];
+  c.L1 = ra.len;
+  c.L2 = rb.len;
+  c.s1 = ra.seq_off;
+  c.q1 = ra.qual_off;
+  c.s2 = rb.seq_off;
+  c.q2 = rb.qual_off;
+  return c;
+}
+// one place of a merged read from its up to four bytes (b2: mate 2's base as it stands in its line)
+struct MgPlace {
+  unsigned base, qual;
+  bool both, disagree, n, bad;
+};
+__device__ __forceinline__ MgPlace mg_place(unsigned b1, unsigned c1, unsigned b2_raw, unsigned c2, bool in1, bool in2, unsigned floor_q) {
+  MgPlace o;
+  const unsigned b2 = cor_comp(b2_raw), p1 = c1 - 33u, p2 = c2 - 33u;
+  o.bad = (in1 && !(cor_is_base(b1) && p1 <= 63u)) || (in2 && !(cor_is_base(b2_raw) && p2 <= 63u));
+  const bool n1 = b1 == 'N', n2 = b2 == 'N';
+  o.both = in1 && in2;
+  o.n = o.both && (n1 || n2);
+  o.disagree = o.both && !n1 && !n2 && b1 != b2;
+  const bool take1 = !in2 || (in1 && !n1 && (n2 || p1 >= p2 || b1 == b2));  // mate 1's base stands (an equal base is either's)
+  const unsigned hi = max(p1, p2), lo = min(p1, p2);
+  const unsigned q_both = n1 && n2 ? lo : n1 ? p2 : n2 ? p1 : b1 == b2 ? hi : max(hi - lo, floor_q);
+  o.base = !o.both ? (in1 ? b1 : b2) : n1 && n2 ? (unsigned)'N' : take1 ? b1 : b2;
+  o.qual = (!o.both ? (in1 ? p1 : p2) : q_both) + 33u;
+  return o;
+}
+struct MgCounts {
+  unsigned ov, disagree, n;
+  bool bad;
+};
+__device__ __forceinline__ void mg_count(MgCounts &k, const MgPlace &o) {
+  k.ov += o.both;
+  k.disagree += o.disagree;
+  k.n += o.n;
+  k.bad = k.bad || o.bad;
+}
+// byte j of the pair's merged record; a base byte counts and judges its place
+__device__ __forceinline__ unsigned mg_byte(const PairSide &A, const PairSide &B, const MgRec &c, unsigned j, unsigned floor_q, MgCounts &k) {
+  if (j < c.hl) return A.raw[c.h0 + j];
+  j -= c.hl;
+  const bool is_base = j < c.I;
+  if (!is_base) {
+    j -= c.I;
+    if (j < 3u) return j == 1u ? '+' : '\n';
+    j -= 3u;
+    if (j >= c.I) return '\n';
+  }
+  const unsigned p = j, jj = c.I - 1u - p;
+  const bool in1 = p < c.L1, in2 = jj < c.L2;
+  unsigned b1 = 0, c1 = 0, b2 = 0, c2 = 0;
+  if (in1) {
+    b1 = A.raw[c.s1 + p];
+    c1 = A.raw[c.q1 + p];
+  }
+  if (in2) {
+    b2 = B.raw[c.s2 + jj];
+    c2 = B.raw[c.q2 + jj];
+  }
+  const MgPlace o = mg_place(b1, c1, b2, c2, in1, in2, floor_q);
+  if (is_base) mg_count(k, o);
+  return (is_base ? o.base : o.qual) & 0xFFu;
+}
+__device__ __forceinline__ uint4 mg_load16(const uint8_t *p, bool any) {
+  if (!any) return make_uint4(0, 0, 0, 0);
+  const SelU128 v = *reinterpret_cast<const SelU128 *>(p);
+  return make_uint4(v.a, v.b, v.c, v.d);
+}
+
+__global__ void __launch_bounds__(MG_EMIT_THREADS)
+k_merge_emit(const PairSide A, const PairSide B, unsigned count, const uint16_t *__restrict__ inserts, const unsigned long long *__restrict__ koff,
+             unsigned long long total, unsigned floor_q, uint8_t *__restrict__ dst, SelectResult *__restrict__ res) {
+  __shared__ unsigned wg[4];  // overlap_bases, places_disagree, places_n, refused
+  if (threadIdx.x < 4) wg[threadIdx.x] = 0;
+  __syncthreads();
+  const unsigned long long t0 = (unsigned long long)blockIdx.x * MG_TILE_BYTES;  // (below total: the grid is the tiles)
+  const unsigned long long t1 = min(total, t0 + MG_TILE_BYTES) - 1;              // the tile's last byte
+  const unsigned r_lo = sel_find(koff, 0, count - 1, t0), r_hi = sel_find(koff, r_lo, count - 1, t1);  // (uniform)
+  MgCounts k = {0u, 0u, 0u, false};
+#pragma unroll 1
+  for (unsigned word = 0; word < MG_EMIT_WORDS; word++) {  // (a round's words lie side by side: coalesced stores)
+    const unsigned long long o = t0 + 16ull * (word * MG_EMIT_THREADS + threadIdx.x);
+    if (o >= total) break;
+    unsigned r = sel_find(koff, r_lo, r_hi, o);
+    MgRec c = mg_rec(A, B, inserts, r);
+    unsigned long long base = koff[r];
+    const unsigned j0 = (unsigned)(o - base);
+    const unsigned sep0 = c.hl + c.I, q0 = sep0 + 3u, end0 = q0 + c.I;  // "\n+\n" | the qualities | the last '\n'
+    uint4 w = make_uint4(0, 0, 0, 0);
+    if (j0 + 16u <= c.hl) {
+      w = mg_load16(A.raw + c.h0 + j0, true);
+    } else if ((j0 >= c.hl && j0 + 16u <= sep0) || (j0 >= q0 && j0 + 16u <= end0)) {
+      const bool is_base = j0 < sep0;
+      const unsigned p0 = j0 - (is_base ? c.hl : q0), jlo = c.I - 16u - p0;  // place p0 + t stands beside jlo + 15 - t of mate 2
+      const bool any1 = p0 < c.L1, any2 = jlo < c.L2;
+      const uint4 s1 = mg_load16(A.raw + c.s1 + p0, any1), q1 = mg_load16(A.raw + c.q1 + p0, any1);
+      const uint4 s2 = mg_load16(B.raw + c.s2 + jlo, any2), q2 = mg_load16(B.raw + c.q2 + jlo, any2);
+      const unsigned s1w[4] = {s1.x, s1.y, s1.z, s1.w}, q1w[4] = {q1.x, q1.y, q1.z, q1.w};
+      // mate 2's words in reverse order, their bytes swapped: byte t is the line's byte jlo + 15 - t
+      const unsigned s2w[4] = {__builtin_bswap32(s2.w), __builtin_bswap32(s2.z), __builtin_bswap32(s2.y), __builtin_bswap32(s2.x)};
+      const unsigned q2w[4] = {__builtin_bswap32(q2.w), __builtin_bswap32(q2.z), __builtin_bswap32(q2.y), __builtin_bswap32(q2.x)};
+      unsigned ow[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (unsigned t = 0; t < 16; t++) {
+        const unsigned sh = 8u * (t & 3u);
+        const MgPlace pl = mg_place((s1w[t >> 2] >> sh) & 0xFFu, (q1w[t >> 2] >> sh) & 0xFFu, (s2w[t >> 2] >> sh) & 0xFFu,
+                                    (q2w[t >> 2] >> sh) & 0xFFu, p0 + t < c.L1, jlo + 15u - t < c.L2, floor_q);
+        if (is_base) mg_count(k, pl);
+        ow[t >> 2] |= ((is_base ? pl.base : pl.qual) & 0xFFu) << sh;
+      }
+      w = make_uint4(ow[0], ow[1], ow[2], ow[3]);
+    } else {  // a seam
+      unsigned long long lo = 0, hi = 0;
+      unsigned size = end0 + 1u;
+      for (unsigned t = 0; t < 16 && o + t < total; t++) {
+        if (o + t - base >= size) {  // the next merged record
+          r = sel_find(koff, r + 1, r_hi, o + t);
+          c = mg_rec(A, B, inserts, r);
+          base = koff[r];
+          size = c.hl + 2u * c.I + 4u;
+        }
+        const unsigned long long v = mg_byte(A, B, c, (unsigned)(o + t - base), floor_q, k);
+        if (t < 8) lo |= v << (8u * t); else hi |= v << (8u * (t - 8u));
+      }
+      w = make_uint4((unsigned)lo, (unsigned)(lo >> 32), (unsigned)hi, (unsigned)(hi >> 32));
+    }
+    *reinterpret_cast<uint4 *>(dst + o) = w;
+  }
+  const unsigned n_ov = cor_wave_sum(k.ov), n_dis = cor_wave_sum(k.disagree), n_n = cor_wave_sum(k.n);
+  const bool any_bad = __any(k.bad);
+  if (fq_lane() == 0) {
+    if (n_ov) atomicAdd(&wg[0], n_ov);
+    if (n_dis) atomicAdd(&wg[1], n_dis);
+    if (n_n) atomicAdd(&wg[2], n_n);
+    if (any_bad) wg[3] = 1u;  // (every writer stores the same value)
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && wg[threadIdx.x]) atomicAdd(&res->w[MG_OVERLAP + threadIdx.x], (unsigned long long)wg[threadIdx.x]);
+  if (threadIdx.x == 3 && wg[3]) res->bad = 1u;
+}
+
 }  // namespace
 
 // The read ids compared.  One kernel, one wait; the result word is word 0 of the selection's result.
@@ -523,5 +753,62 @@ int fq_pair_correct(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const 
     FQ_HIP(hipGetLastError());
     FQ_HIP(hipStreamSynchronize(st));
   }
+  return FQGPU_OK;
+}
+
+// The merge.  Two phases with a wait each, as the selection has them: the size pass and the scan say how many bytes there are
+// and whether an insert or a record is refused; the emit pass builds the records in the handle's merge buffer -- whether the
+// caller wants the bytes or not, for it also judges the lines and counts the places -- and only behind its verdict are the
+// bytes copied down, so FQGPU_E_ARG leaves `out` untouched.  Inserts and mark go up as a limited call's limits and mark do.
+int fq_pair_merge(fqgpu_ctx *ctx, hipStream_t st, const FqChunkView &a, const FqChunkView &b, const uint16_t *insert_in, const uint8_t *mark_in,
+                  const fqgpu_merge *m, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report, uint8_t *merged_out) {
+  *out_len = 0;
+  memset(report, 0, FQGPU_MERGE_REPORT_WORDS * sizeof(uint64_t));
+  if (pair_views_bad(a, b)) return FQGPU_E_ARG;
+  const size_t count = a.n_recs, n_waves = (count + OV_WG_PAIRS - 1) / OV_WG_PAIRS;
+  SelectScratch &ss = ctx->select;
+  int rc;
+  if ((rc = ss.merge_in.reserve(count * 2)) || (rc = ss.merge_size.reserve(count * 4)) || (rc = ss.merge_bits.reserve(n_waves * 8)) ||
+      (rc = ss.koff.reserve((count + 1) * 8)) || (mark_in && (rc = ss.mark.reserve(n_waves * 8))) || (rc = ss.begin(st)))
+    return rc;
+  SelectResult *const dev = ss.res.as<SelectResult>();
+  const uint16_t *const inserts = ss.merge_in.as<uint16_t>();
+  unsigned long long *const koff = ss.koff.as<unsigned long long>();
+  FQ_HIP(hipMemcpyAsync(ss.merge_in.p, insert_in, count * 2, hipMemcpyHostToDevice, st));
+  if (mark_in) {  // (its last word padded with zeros)
+    FQ_HIP(hipMemsetAsync(ss.mark.p, 0, n_waves * 8, st));
+    FQ_HIP(hipMemcpyAsync(ss.mark.p, mark_in, (count + 7) / 8, hipMemcpyHostToDevice, st));
+  }
+  const PairSide A = pair_side(a), B = pair_side(b);
+  fq_timer_span_begin(ctx, "pair_merge", st);
+  hipLaunchKernelGGL(k_merge_size, dim3((unsigned)n_waves), dim3(OV_THREADS), 0, st, A, B, (unsigned)count, inserts,
+                     mark_in ? ss.mark.as<unsigned long long>() : nullptr, m->min_len, ss.merge_size.as<uint32_t>(),
+                     ss.merge_bits.as<unsigned long long>(), dev);
+  FQ_HIP(hipGetLastError());
+  rc = fq_scan_u32_to_u64(st, ss.merge_size.as<uint32_t>(), count, koff, ss.scan_tmp);
+  fq_timer_span_end(ctx, st);
+  if (rc) return rc;
+  if (merged_out) FQ_HIP(hipMemcpyAsync(merged_out, ss.merge_bits.p, (count + 7) / 8, hipMemcpyDeviceToHost, st));
+  const SelectResult *res;
+  if ((rc = ss.finish(st, res))) return rc;
+  if (res->bad) return FQGPU_E_ARG;  // (the caller zeroes merged_out)
+  const size_t total = (size_t)res->w[MG_BYTES];
+  if (total) {  // the second phase: the records
+    if ((rc = ss.merge_out.reserve((total + 15) / 16 * 16))) return rc;
+    fq_timer_span_begin(ctx, "pair_merge", st);
+    hipLaunchKernelGGL(k_merge_emit, dim3((unsigned)((total + MG_TILE_BYTES - 1) / MG_TILE_BYTES)), dim3(MG_EMIT_THREADS), 0, st, A, B,
+                       (unsigned)count, inserts, koff, (unsigned long long)total, m->floor_q, ss.merge_out.as<uint8_t>(), dev);
+    fq_timer_span_end(ctx, st);
+    FQ_HIP(hipGetLastError());
+    if ((rc = ss.finish(st, res))) return rc;
+    if (res->bad) return FQGPU_E_ARG;
+  }
+  for (unsigned i = 1; i < MG_COUNTERS; i++) report[i] = res->w[i];
+  report[0] = count;
+  *out_len = total;
+  if (!out || !total) return FQGPU_OK;
+  if (out_cap < total) return FQGPU_E_OVERFLOW;
+  FQ_HIP(hipMemcpyAsync(out, ss.merge_out.p, total, hipMemcpyDeviceToHost, st));
+  FQ_HIP(hipStreamSynchronize(st));
   return FQGPU_OK;
 }

@@ -824,6 +824,15 @@ inline void addCorrectReport(std::vector<uint64_t> &dst, const uint64_t *src, st
   for (std::size_t i = 0; i < src_words; ++i) dst[i] += src[i];
 }
 
+/** Extension: reports of fqgpu_chunk_pair_merge add word by word, as the correction's do.  dst: empty (it becomes
+ *  FQGPU_MERGE_REPORT_WORDS zeros) or that many words; src: that many, else std::logic_error. */
+inline void addMergeReport(std::vector<uint64_t> &dst, const uint64_t *src, std::size_t src_words) {
+  if (dst.empty()) dst.assign(FQGPU_MERGE_REPORT_WORDS, 0);
+  if (!src || src_words != FQGPU_MERGE_REPORT_WORDS || dst.size() != FQGPU_MERGE_REPORT_WORDS)
+    throw std::logic_error("addMergeReport: not a merge's report");
+  for (std::size_t i = 0; i < src_words; ++i) dst[i] += src[i];
+}
+
 /** Extension: a part of a paired restore's work unit -- the mates of the records [at, at + end - first) of the unit are the
  *  records [first, end) of block `block` of archive 2 */
 struct MatePiece {
@@ -841,14 +850,17 @@ inline std::vector<MatePiece> planMateUnit(const std::vector<uint32_t> &counts2,
 
 /** Extension: what a paired restore did -- a FarmReport per mate (in: what was written; trim: the chunks' marked reports,
  *  FQGPU_TAIL_REPORT_WORDS words added word by word; index, sums and verified as in a single restore, mate 2's counted per
- *  DECODE) and the pairs: both mates kept, dropped because mate 1 alone failed, mate 2 alone, both.  decodes2: chunk decodes
- *  of archive 2 (its number of chunks when the two archives are cut at the same records). */
+ *  DECODE) and the pairs: both mates kept, dropped because mate 1 alone failed, mate 2 alone, both, and -- with a merge --
+ *  merged into one read: pairs = kept + merged + the three dropped counts.  In mate1.trim and mate2.trim a merged pair shows
+ *  under dropped_unmarked (word 20), for its bit is taken out of both mates' marks.  decodes2: chunk decodes of archive 2 (its
+ *  number of chunks when the two archives are cut at the same records). */
 struct PairedReport {
   FarmReport mate1, mate2;
-  uint64_t pairs = 0, kept = 0, dropped_mate1_only = 0, dropped_mate2_only = 0, dropped_both = 0;
+  uint64_t pairs = 0, kept = 0, dropped_mate1_only = 0, dropped_mate2_only = 0, dropped_both = 0, merged = 0;
   std::size_t blocks1 = 0, blocks2 = 0, decodes2 = 0;
   std::vector<uint64_t> overlap;  // with Selection::overlap: the units' summaries merged (FQGPU_OVERLAP_WORDS; an archive without records: zeros)
   std::vector<uint64_t> correct;  // with Selection::correct: the pieces' reports added word by word (FQGPU_CORRECT_REPORT_WORDS)
+  std::vector<uint64_t> merge;    // with Selection::merge: the pieces' reports added word by word (FQGPU_MERGE_REPORT_WORDS)
 };
 
 /** Extension: `d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq>` -- two archives whose records are mates restored in
@@ -875,11 +887,21 @@ struct PairedReport {
  *  limit pointers stay nullptr unless overlap_trim is on --, mate 1's chunk stays staged for the unit and collects every
  *  piece's corrections before its final gather, and a chunk of archive 2 that two workers decode is patched by each in its
  *  own range only.  The digests are taken at staging, before any correction; rep.correct sums the pieces' reports.
+ *  With sel.merge (and `merged_out`, the third output) the unit takes that by-piece order too -- its condition is "limits,
+ *  correction or merge" -- and per piece, behind the overlap and the optional correction: mate 1's range is judged as a size
+ *  query (the piece's mark), mate 2's piece is judged as a SIZE QUERY with that mark (the pair bits `keep`: both mates pass,
+ *  exactly as without a merge), fqgpu_chunk_pair_merge takes `keep` as its mark, appends the merged reads -- built from the
+ *  staged, untrimmed, possibly corrected mates -- to the unit's merged piece and says which pairs it merged, and mate 2 is
+ *  gathered with keep & ~merged, whose bits go into K: a merged pair is in neither mate file.  Mate 2's piece is judged twice;
+ *  no chunk is decoded more often than without.  A third OrderedPieceWriter writes the merged piece as piece `unit`, so the
+ *  merged file does not depend on how many workers there are; rep.merge sums the pieces' reports, rep.merged is its word 2.
  *  Each archive's `.fqx` is used and its `.fqs` verified as in a single restore; a failed run leaves neither output
  *  nor a `.part` file.  Throws before any output is opened when the archives' record totals differ. */
 inline PairedReport processArchivePaired(const path_t &archive1_path, const path_t &out1, const path_t &archive2_path, const path_t &out2,
-                                         const fqgpu_adapter *adapter2, const Selection &sel, const Settings &set) {
+                                         const fqgpu_adapter *adapter2, const Selection &sel, const Settings &set,
+                                         const path_t &merged_out = path_t()) {
   const std::string name("processArchivePaired");
+  if (static_cast<bool>(sel.merge) != !merged_out.empty()) throw std::invalid_argument(name + ": a merge and a merged output come together");
   Selection sel2 = sel;
   sel2.adapter = adapter2;
   sel.check(name, true);
@@ -905,6 +927,9 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
     std::vector<uint16_t> insert;                 // with a correction: the piece's insert sizes
     uint64_t correct[FQGPU_CORRECT_REPORT_WORDS];  // ... the piece's report
     std::vector<uint64_t> correct_sum;             // ... the worker's (empty until its first piece)
+    std::vector<uint8_t> merged_bits, merged_piece;  // with a merge: the piece's merged pairs, the unit's merged reads
+    uint64_t merge[FQGPU_MERGE_REPORT_WORDS];        // ... the piece's report
+    std::vector<uint64_t> merge_sum;                 // ... the worker's (empty until its first piece)
     uint64_t report[W], sum1[W] = {}, sum2[W] = {};
     InputStats in2;
     unsigned decodes2 = 0;
@@ -913,6 +938,7 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
     return Worker{{archive1.meta(), device, verifier1.on()}, {archive2.meta(), device, verifier2.on()}};
   });
   OrderedPieceWriter writer1(out1, n1), writer2(out2, n1);
+  std::unique_ptr<OrderedPieceWriter> writer_merged(sel.merge ? new OrderedPieceWriter(merged_out, n1) : nullptr);
   farm.run([&](Worker &w, std::size_t unit, StageClock &clk, InputStats &in1) {
     DecompressionWorkspace &w1 = w.m1.wksp, &w2 = w.m2.wksp;
     CompressedBuffersSrc &cbs1 = w.m1.cbs, &cbs2 = w.m2.cbs;
@@ -921,7 +947,7 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
     piece1.clear();
     piece2.clear();
     piece1.idx = piece2.idx = static_cast<unsigned>(unit);
-    std::size_t len1 = 0, len2 = 0;
+    std::size_t len1 = 0, len2 = 0, len_merged = 0;
     if (n) {
       archive1.readBlockAt(unit, cbs1);
       sidecar1.get(cbs1);
@@ -929,7 +955,7 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
       w1.stagePairedChunk(cbs1);
       verifier1.check(cbs1, w1.lastDigest());  // (before anything of the chunk reaches the file)
       const bool limited = sel.overlap && sel.overlap_trim;  // the limits stand in front of each mate's steps
-      const bool by_piece = limited || sel.correct;          // mate 1 is then judged piece by piece, behind the piece's overlap
+      const bool by_piece = limited || sel.correct || sel.merge;  // mate 1 is then judged piece by piece, behind the piece's overlap
       w.k1.assign((n + 7) / 8, 0);
       if (!by_piece) (void)w1.selectMarked(sel, 0, n, nullptr, nullptr, 0, w.report, w.k1.data());
       clk.lap("mate 1");
@@ -955,9 +981,10 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
         w.keep.assign((count + 7) / 8, 0);
         if (sel.overlap) {
           w.limit2.assign(count, 0);
-          if (sel.correct) w.insert.assign(count, 0);
+          const bool inserts = sel.correct || sel.merge;
+          if (inserts) w.insert.assign(count, 0);
           w1.pairOverlap(at, w2, pc.first, count, *sel.overlap, w.overlap.data(), w.limit1.data() + at, w.limit2.data(),
-                         sel.correct ? w.insert.data() : nullptr);
+                         inserts ? w.insert.data() : nullptr);
           if (fqgpu_overlap_merge(w.overlap_sum.data(), w.overlap_sum.size(), w.overlap.data(), w.overlap.size()) != FQGPU_OK)
             throw std::logic_error(name + ": overlap summaries of different specs");
           if (sel.correct) {  // (in front of everything that judges either mate)
@@ -967,6 +994,16 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
         }
         if (by_piece) (void)w1.selectMarked(sel, at, at + count, nullptr, nullptr, 0, w.report, w.mark.data(), limited ? w.limit1.data() + at : nullptr);
         else detail::sliceBits(w.k1.data(), at, count, w.mark.data());
+        if (sel.merge) {  // the pairs whose mates both pass; those of them that have an insert are merged and leave the mark
+          (void)w2.selectMarked(sel2, pc.first, pc.end, w.mark.data(), nullptr, 0, w.report, w.keep.data(), limited ? w.limit2.data() : nullptr);
+          const std::size_t cap = cbs1.original_size.total + cbs2.original_size.total;  // (fqgpu_chunk_pair_merge's bound)
+          w.merged_piece.resize(len_merged + cap);
+          w.merged_bits.assign((count + 7) / 8, 0);
+          len_merged += w1.pairMerge(at, w2, pc.first, count, w.insert.data(), w.keep.data(), *sel.merge, w.merged_piece.data() + len_merged, cap,
+                                     w.merge, w.merged_bits.data());
+          addMergeReport(w.merge_sum, w.merge, FQGPU_MERGE_REPORT_WORDS);
+          for (std::size_t i = 0; i < w.mark.size(); ++i) w.mark[i] = static_cast<uint8_t>(w.keep[i] & ~w.merged_bits[i]);
+        }
         piece2.raw_data.resize(len2 + cbs2.original_size.total);  // (what is kept of a chunk is never more than the chunk)
         len2 += w2.selectMarked(sel2, pc.first, pc.end, w.mark.data(), reinterpret_cast<uint8_t *>(piece2.raw_data.data()) + len2,
                                 cbs2.original_size.total, w.report, w.keep.data(), limited ? w.limit2.data() : nullptr);
@@ -988,11 +1025,13 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
     w.in2.raw += len2;
     writer1.writePiece(unit, piece1.raw_data.data(), len1);
     writer2.writePiece(unit, piece2.raw_data.data(), len2);
+    if (writer_merged) writer_merged->writePiece(unit, w.merged_piece.data(), len_merged);
     clk.lap("write");
     return true;
-  }, [&] { writer1.abort(); writer2.abort(); });
+  }, [&] { writer1.abort(); writer2.abort(); if (writer_merged) writer_merged->abort(); });
   writer1.flush();
   writer2.flush();
+  if (writer_merged) writer_merged->flush();
   PairedReport rep;
   rep.mate1 = farm.report();
   rep.mate2.seconds = rep.mate1.seconds;
@@ -1001,11 +1040,13 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   rep.mate2.trim.assign(W, 0);
   if (sel.overlap) rep.overlap.assign(FQGPU_OVERLAP_WORDS, 0);
   if (sel.correct) rep.correct.assign(FQGPU_CORRECT_REPORT_WORDS, 0);
+  if (sel.merge) rep.merge.assign(FQGPU_MERGE_REPORT_WORDS, 0);
   for (std::size_t t = 0; t < farm.workers().size(); ++t) {
     const Worker &w = *farm.workers()[t];
     if (!w.overlap_sum.empty() && fqgpu_overlap_merge(rep.overlap.data(), rep.overlap.size(), w.overlap_sum.data(), w.overlap_sum.size()) != FQGPU_OK)
       throw std::logic_error(name + ": overlap summaries of different specs");
     if (!w.correct_sum.empty()) addCorrectReport(rep.correct, w.correct_sum.data(), w.correct_sum.size());
+    if (!w.merge_sum.empty()) addMergeReport(rep.merge, w.merge_sum.data(), w.merge_sum.size());
     rep.mate2.in += w.in2;
     rep.mate2.blocks_per_worker[t] = w.decodes2;
     rep.decodes2 += w.decodes2;
@@ -1022,21 +1063,26 @@ inline PairedReport processArchivePaired(const path_t &archive1_path, const path
   rep.blocks2 = n2;
   rep.pairs = start1[n1];
   rep.kept = rep.mate1.trim[1];
-  rep.dropped_mate1_only = rep.mate2.trim[20];  // mate 2 passes, its mark -- mate 1's verdict -- says no
-  rep.dropped_mate2_only = rep.mate1.trim[20];
-  rep.dropped_both = rep.pairs - rep.kept - rep.dropped_mate1_only - rep.dropped_mate2_only;
+  rep.merged = sel.merge ? rep.merge[2] : 0;     // (a merged pair passes in both mates and is in neither mark)
+  rep.dropped_mate1_only = rep.mate2.trim[20] - rep.merged;  // mate 2 passes, its mark -- mate 1's verdict -- says no
+  rep.dropped_mate2_only = rep.mate1.trim[20] - rep.merged;
+  rep.dropped_both = rep.pairs - rep.kept - rep.merged - rep.dropped_mate1_only - rep.dropped_mate2_only;
   return rep;
 }
 
 /** Extension: the report file of a mate overlap summary (fqgpu_chunk_pair_overlap, merged) -- text, tab-separated, integers
  *  only, a pure function of the summary and the spec: the spec's three numbers, the eight summary words by name, then
  *  "insert", I and the pairs for every non-empty row; with a correction (`correct` and its summed report `cw`), and only then,
- *  six more lines behind the last row: good_q, bad_q, pairs_corrected, bases_corrected_1, bases_corrected_2, n_resolved.
- *  Written as `<path>.part` and renamed when it is complete. */
+ *  six more lines behind the last row: good_q, bad_q, pairs_corrected, bases_corrected_1, bases_corrected_2, n_resolved; with
+ *  a merge (`merge` and its summed report `mw`), and only then, nine more behind those: min_len, floor_q, pairs_merged,
+ *  bases_merged, bytes_merged, merged_overlap_bases (the merge's word 5: "overlap_bases" is the summary's line), places_disagree,
+ *  places_n, pairs_too_short.  Written as `<path>.part` and renamed when it is complete. */
 inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu_overlap &spec, const fqgpu_correct *correct = nullptr,
-                                     const std::vector<uint64_t> &cw = {}) {
+                                     const std::vector<uint64_t> &cw = {}, const fqgpu_merge *merge = nullptr,
+                                     const std::vector<uint64_t> &mw = {}) {
   if (w.size() != FQGPU_OVERLAP_WORDS) throw std::logic_error("writeOverlapReport: not an overlap summary");
   if (correct && cw.size() != FQGPU_CORRECT_REPORT_WORDS) throw std::logic_error("writeOverlapReport: not a correction's report");
+  if (merge && mw.size() != FQGPU_MERGE_REPORT_WORDS) throw std::logic_error("writeOverlapReport: not a merge's report");
   std::string out = "#fqgpu-overlap 1\n";
   const auto line = [&](const char *name, uint64_t v) { out += name; out += '\t'; out += std::to_string(v); out += '\n'; };
   line("min_overlap", spec.min_overlap);
@@ -1055,11 +1101,22 @@ inline std::string overlapReportText(const std::vector<uint64_t> &w, const fqgpu
     line("bases_corrected_2", cw[4]);
     line("n_resolved", cw[5]);
   }
+  if (merge) {  // behind the correction's lines: the merge's two numbers and what it did
+    line("min_len", merge->min_len);
+    line("floor_q", merge->floor_q);
+    line("pairs_merged", mw[2]);
+    line("bases_merged", mw[3]);
+    line("bytes_merged", mw[4]);
+    line("merged_overlap_bases", mw[5]);
+    line("places_disagree", mw[6]);
+    line("places_n", mw[7]);
+    line("pairs_too_short", mw[11]);
+  }
   return out;
 }
 inline void writeOverlapReport(const path_t &path, const std::vector<uint64_t> &w, const fqgpu_overlap &spec, const fqgpu_correct *correct = nullptr,
-                               const std::vector<uint64_t> &cw = {}) {
-  const std::string out = overlapReportText(w, spec, correct, cw);
+                               const std::vector<uint64_t> &cw = {}, const fqgpu_merge *merge = nullptr, const std::vector<uint64_t> &mw = {}) {
+  const std::string out = overlapReportText(w, spec, correct, cw, merge, mw);
   const path_t part = path.string() + ".part";
   std::FILE *f = std::fopen(part.string().c_str(), "wb");
   const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();

@@ -38,4 +38,14 @@ __device__ __forceinline__ unsigned sel_bits(int lo, int hi) {
 constexpr unsigned CLIP_GATHER = 0x00204081u;  // x * this: the bits 7, 15, 23, 31 of x side by side in the bits 28 .. 31
 struct __attribute__((packed)) SelU128 { uint32_t a, b, c, d; };  // sixteen bytes at any address
 
+// the record that holds byte o of the output: the last r in [lo, hi] with koff[r] <= o (a dropped record has no byte, so
+// koff[r] == koff[r + 1] there and the search steps over it); the caller knows koff[lo] <= o
+__device__ __forceinline__ unsigned sel_find(const unsigned long long *__restrict__ koff, unsigned lo, unsigned hi, unsigned long long o) {
+  while (lo < hi) {
+    const unsigned mid = lo + ((hi - lo + 1) >> 1);
+    if (koff[mid] <= o) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
 }  // namespace

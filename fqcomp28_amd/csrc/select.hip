@@ -1173,16 +1173,6 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   }
 }
 
-// the record that holds byte o of the output: the last r in [lo, hi] with koff[r] <= o (a dropped record has no byte, so
-// koff[r] == koff[r + 1] there and the search steps over it); the caller knows koff[lo] <= o
-__device__ __forceinline__ unsigned sel_find(const unsigned long long *__restrict__ koff, unsigned lo, unsigned hi, unsigned long long o) {
-  while (lo < hi) {
-    const unsigned mid = lo + ((hi - lo + 1) >> 1);
-    if (koff[mid] <= o) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
-
 // a kept record as the gather sees it: where its pieces come from
 struct SelRec {
   long long h0, seq, qual;  // the header line, the first kept byte of the sequence and of the quality line, in the chunk

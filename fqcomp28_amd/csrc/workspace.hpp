@@ -549,6 +549,11 @@ struct Selection {
   /** ... and, with `correct`, the mismatched bases inside every overlap are corrected (fqgpu_chunk_pair_correct) behind the
    *  analysis and in front of everything that judges either mate; PairedReport::correct sums its reports */
   const fqgpu_correct *correct = nullptr;
+  /** ... and, with `merge`, every pair that has an insert size and whose mates both pass the selection is written as ONE read
+   *  to a third output instead of the two mate files (fqgpu_chunk_pair_merge, behind the analysis and the optional
+   *  correction); PairedReport::merge sums its reports.  Positional cuts (cut_front, cut_tail, crop) have no defined meaning
+   *  on a merged read yet and are refused beside it */
+  const fqgpu_merge *merge = nullptr;
   /** something is cut: the counters are a trim report (FarmReport::trim), not a filter report (FarmReport::filter) */
   [[nodiscard]] bool trims() const { return adapter || tail || trim; }
   /** the fqgpu_chunk_* call that serves it, by the name of its first step */
@@ -569,6 +574,10 @@ struct Selection {
     if (overlap_trim && !overlap) throw std::invalid_argument(name + ": overlap_trim without an overlap spec");
     if (correct && !overlap) throw std::invalid_argument(name + ": a correction without an overlap spec");
     if (correct && fqgpu_correct_check(correct) != FQGPU_OK) throw std::invalid_argument(name + ": a correction fqgpu_correct_check refuses");
+    if (merge && !overlap) throw std::invalid_argument(name + ": a merge without an overlap spec");
+    if (merge && fqgpu_merge_check(merge) != FQGPU_OK) throw std::invalid_argument(name + ": a merge fqgpu_merge_check refuses");
+    if (merge && trim && (trim->cut_front || trim->cut_tail || trim->crop != FQGPU_FILTER_NONE))
+      throw std::invalid_argument(name + ": a merge beside cut_front, cut_tail or crop");
   }
 };
 
@@ -784,6 +793,19 @@ public:
     if (rc != FQGPU_OK)
       throw std::runtime_error("pairCorrect: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
                                fqgpu_strerror(rc));
+  }
+  /** fqgpu_chunk_pair_merge: with pairOverlap's insert sizes of the same records and the pair bits `mark` (nullptr: every
+   *  pair), the mates of every marked pair that has an insert merged into one read -> the bytes written to out (at most cap:
+   *  the two chunks' recorded sizes together are always enough), report[0, FQGPU_MERGE_REPORT_WORDS) and -- merged_bits not
+   *  nullptr -- the bits of the merged pairs.  Both staged chunks stay as they are */
+  std::size_t pairMerge(std::size_t first, DecompressionWorkspace &mate, std::size_t mate_first, std::size_t count, const uint16_t *insert,
+                        const uint8_t *mark, const fqgpu_merge &spec, uint8_t *out, std::size_t cap, uint64_t *report, uint8_t *merged_bits) {
+    std::size_t len = 0;
+    const int rc = fqgpu_chunk_pair_merge(ctx_, first, mate.ctx_, mate_first, count, insert, mark, &spec, out, cap, &len, report, merged_bits);
+    if (rc != FQGPU_OK)
+      throw std::runtime_error("pairMerge: chunk " + std::to_string(staged_idx_) + " against chunk " + std::to_string(mate.staged_idx_) + ": " +
+                               fqgpu_strerror(rc));
+    return len;
   }
 
   /** The misc pass backwards (the reference's decompressMiscBuffers, src/workspace.cpp:215-256): every

@@ -896,6 +896,61 @@ int fqgpu_dblock_pair_correct(fqgpu_ctx *ctx, fqgpu_dblock *ba, size_t first_a, 
                               const uint16_t *insert_in, const fqgpu_correct *c, uint64_t *report, uint16_t *fixed_a_out,
                               uint16_t *fixed_b_out);
 
+/* ---- Extension (nothing in the reference): MATE MERGING -- the two mates of an overlapping pair written as ONE read, the
+ * fragment from its first base to its last (fastp's --merge, FLASH, PEAR), built where both chunks lie: in HBM.  THE CALLS LEAVE
+ * BOTH CHUNKS AS THEY ARE: digest, summary and every selection give the same result before and after.
+ * For a pair with the lines s1, q1 of length L1 (mate 1), s2, q2 of length L2 (mate 2) and an insert size I -- insert_out's
+ * meaning: I = d + L2, or 0 for "no hit" --, comp the overlap rule's complement.  Integer arithmetic throughout:
+ *   eligibility  a pair is MERGED iff I != 0, its mark bit is set (no mark: every pair counts as marked) and I >= min_len.
+ *                Every other pair is left alone and none of its lines is looked at
+ *   the inserts  every pair with I != 0, marked or not, needs L1 <= 512, L2 <= 512 and 1 <= I <= L1 + L2 - 1, else FQGPU_E_ARG:
+ *                the inserts are the caller's data, as in the correction
+ *   the length   the merged read has exactly I bases (I <= 1023)
+ *   place p      in [0, I): j = I - 1 - p, in1 = (p < L1), in2 = (j < L2); at least one holds.  The bases of either mate at or
+ *                behind I belong to neither mate's fragment (adapter) and are dropped
+ *   one mate     in1 alone: base s1[p], quality q1[p].  in2 alone: base comp(s2[j]), quality q2[j]
+ *   both mates   b1 = s1[p], b2 = comp(s2[j]), p1 = q1[p] - 33, p2 = q2[j] - 33.  b1 == b2 and neither is N: b1, Phred
+ *                max(p1, p2).  Both N: N, Phred min(p1, p2).  Exactly one N: the other mate's base and Phred.  Two bases that
+ *                differ: the base with the higher Phred, mate 1's on a tie, Phred max(p_winner - p_loser, floor_q) (FLASH's
+ *                rule).  After fqgpu_*_pair_correct a corrected place agrees, so the two steps compose
+ *   the record   mate 1's header line byte for byte with its '\n' | the I bases | "\n+\n" | the I quality bytes | '\n'
+ *   the order    merged records appear in pair order; every byte is a function of the pair's own lines and I, so the result
+ *                does not depend on how the work is split
+ * For merged pairs only, s1, q1 are read and judged over [0, min(L1, I)) and s2, q2 over [0, min(L2, I)): a base outside ACGTN or
+ * a quality byte outside 33 .. 96 there is FQGPU_E_ARG, and so is a merged pair's record of length 0 or outside its chunk.
+ *   insert_in   count uint16_t, as insert_out
+ *   mark_in     NULL, or (count + 7) / 8 bytes in the selection's bit order, relative to the range
+ *   merged_out  NULL, or the same size: bit i set iff pair i was merged
+ *   out         NULL: everything is judged and counted, *out_len is set, nothing is copied.  Else *out_len bytes, when out_cap
+ *               holds them; out_cap < *out_len: FQGPU_E_OVERFLOW, nothing is written to out, *out_len, the report and
+ *               merged_out are valid.  *out_len NEVER EXCEEDS the canonical bytes of the two ranges together (a record is its
+ *               header line and 2 I + 4 <= 2 L1 + 4 + 2 L2 + 4 bytes): a buffer of that size always holds the result
+ *   report      FQGPU_MERGE_REPORT_WORDS uint64_t: 0 n_pairs | 1 pairs_with_insert | 2 pairs_merged | 3 bases_merged (the sum of
+ *               I) | 4 bytes_out | 5 overlap_bases (places with both mates, merged pairs only) | 6 places_disagree (the two bases
+ *               differ) | 7 places_n (at least one N among both-mate places) | 8 bases_dropped_a (the sum of L1 - min(L1, I)
+ *               over merged pairs) | 9 bases_dropped_b | 10 pairs_unmarked (I != 0, mark 0) | 11 pairs_too_short (marked,
+ *               0 < I < min_len) | 12 .. 15 zero.  Reports add word by word
+ *   fqgpu_merge_check        host only: floor_q in 0 .. 63, min_len in 1 .. 1023, reserved zero: FQGPU_OK, else FQGPU_E_ARG
+ *   fqgpu_chunk_pair_merge   shaped and validated exactly like fqgpu_chunk_pair_overlap -- valid in the same states, both
+ *                            handles of one device, every stream of both waited for, the kernels on ctx_a's stream, waited for;
+ *                            ctx_a == ctx_b is allowed, for nothing is patched
+ *   fqgpu_dblock_pair_merge  as fqgpu_dblock_pair_overlap; ba == bb is allowed
+ * A spec its check refuses, count == 0, a range outside either chunk, a NULL where data is expected (insert_in, m, out_len,
+ * report): FQGPU_E_ARG.  EVERY FQGPU_E_ARG leaves `out` untouched and zeroes *out_len, the report and merged_out.  Without a GPU
+ * the two device calls return FQGPU_E_NO_DEVICE before any argument is looked at; the check works. */
+#define FQGPU_MERGE_REPORT_WORDS 16
+typedef struct {
+  uint32_t floor_q, min_len;  /* 0 .. 63 | 1 .. 1023 */
+  uint32_t reserved[6];       /* zero */
+} fqgpu_merge;
+int fqgpu_merge_check(const fqgpu_merge *m);
+int fqgpu_chunk_pair_merge(fqgpu_ctx *ctx_a, size_t first_a, fqgpu_ctx *ctx_b, size_t first_b, size_t count, const uint16_t *insert_in,
+                           const uint8_t *mark_in, const fqgpu_merge *m, uint8_t *out, size_t out_cap, size_t *out_len, uint64_t *report,
+                           uint8_t *merged_out);
+int fqgpu_dblock_pair_merge(fqgpu_ctx *ctx, const fqgpu_dblock *ba, size_t first_a, const fqgpu_dblock *bb, size_t first_b, size_t count,
+                            const uint16_t *insert_in, const uint8_t *mark_in, const fqgpu_merge *m, uint8_t *out, size_t out_cap,
+                            size_t *out_len, uint64_t *report, uint8_t *merged_out);
+
 /* Pinned (page-locked) host memory for the buffers that cross PCIe: the shim's FastqChunk::raw_data
  * and CompressedBuffers::seq/qual live in it, so that fqgpu_encode_block / fqgpu_decode_block copy
  * at the full link rate and asynchronously.  Without a usable GPU the memory is ordinary heap

@@ -80,7 +80,18 @@
 //               the overlap's search and in front of every step that judges either mate.  An overlap option in its own
 //               right: it turns the analysis on, alone or beside any other option of d --mate, and the three spec options
 //               may be given with it alone.  --overlap-correct without --mate, --correct-q without --overlap-correct and a
-//               pair fqgpu_correct_check refuses (GOOD 1 .. 63, BAD below GOOD) are usage errors)
+//               pair fqgpu_correct_check refuses (GOOD 1 .. 63, BAD below GOOD) are usage errors.
+//               [--merge <merged.fastq>] [--merge-min-len N] [--merge-floor-q Q]: MATE MERGING (include/fqgpu.h, fastp's --merge,
+//               FLASH) -- a pair whose mates overlap (it has an insert size I of N or more, default 1) and both pass the
+//               selection exactly as they would without the option is written as ONE read of I bases to <merged.fastq> and to
+//               neither mate file: mate 1's header line, the fragment from its first base to its last, in the overlap the
+//               consensus of the two mates (where they differ the base with the higher Phred, its Phred the difference, Q at the
+//               least, default 2).  Built on the device from the untrimmed, possibly corrected mates; the merged file's bytes do
+//               not depend on -t, -R or .fqx.  An overlap option in its own right, as --overlap-correct is.  In "mate1" /
+//               "mate2" a merged pair shows under "dropped_unmarked".  --merge without --mate, --merge-min-len or --merge-floor-q
+//               without --merge, a spec fqgpu_merge_check refuses (N 1 .. 1023, Q 0 .. 63) and --merge with --cut-front,
+//               --cut-tail or --crop -- positional cuts have no defined meaning on a merged read yet -- are usage errors.  A
+//               failed run leaves none of the three outputs and no .part file)
 //   fqc_tool x <in.fqc> [-t threads] [-d dev,dev,...] [--index-stride Ki]
 //              (extension: builds <in.fqc>.fqx for an archive written without --index, by another writer of the format, or
 //               whose index file is lost, stale or damaged: one serial decode of every block, nothing restored; always
@@ -132,6 +143,8 @@
 // an overlap option "overlap": {"pairs_overlapped", "pairs_read_through", "bases_behind_1", "bases_behind_2",
 // "pairs_not_analysed"}; with --overlap-trim "mate1" / "mate2" are there and end in "reads_cut_limit", "bases_cut_limit"; with
 // --overlap-correct, and only then, "overlap" ends in "pairs_corrected", "bases_corrected_1", "bases_corrected_2", "n_resolved".
+// With --merge, and only then, "pairs" ends in "merged" (pairs = kept + merged + the three dropped counts) and the line has
+// "merge": {"pairs_merged", "bases_merged", "bytes_merged", "overlap_bases", "places_disagree", "places_n", "pairs_too_short"}.
 // Needs a GPU: no CPU fallback.
 #include "../fqcomp28_amd/csrc/process.hpp"
 
@@ -153,7 +166,7 @@ int main(int argc, char **argv) {
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] --adapter SEQ [--adapter-overlap N] [--adapter-err PCT] [trim options] [filter options]\n"
                          "       fqc_tool d <in.fqc> <out.fastq> [-t N] [-d 0,1,..] [--poly-g [N] | --poly-x [N]] [--poly-every K] [--poly-mism M] [--window W:Q] [adapter options] [trim options] [filter options]\n"
                          "                  (the argument behind --poly-g / --poly-x is taken as N unless it begins with '-')\n"
-                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [--overlap-trim] [--overlap-report file.tsv] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT] [--overlap-correct] [--correct-q GOOD:BAD] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
+                         "       fqc_tool d <in1.fqc> <out1.fastq> --mate <in2.fqc> <out2.fastq> [--adapter2 SEQ] [--overlap-trim] [--overlap-report file.tsv] [--overlap-min N] [--overlap-mism M] [--overlap-err PCT] [--overlap-correct] [--correct-q GOOD:BAD] [--merge merged.fastq] [--merge-min-len N] [--merge-floor-q Q] [-t N] [-d 0,1,..] [poly, window, adapter, trim and filter options]\n"
                          "                  (paired: a pair is kept only if both mates pass; the read ids of every pair are compared)\n"
                          "       fqc_tool d <in.fqc> <out.fasta> --fasta [-t N] [-d 0,1,..] [--records A:B]\n"
                          "       fqc_tool x <in.fqc> [-t N] [-d 0,1,..] [--index-stride KiSymbols]\n"
@@ -181,6 +194,9 @@ int main(int argc, char **argv) {
   std::string overlap_path;                             // --overlap-report
   fqgpu_correct correct = {30, 14, {0, 0, 0, 0, 0, 0}};  // --correct-q
   bool overlap_correct = false, correct_opt = false;    // --overlap-correct; --correct-q
+  fqgpu_merge merge = {2, 1, {0, 0, 0, 0, 0, 0}};        // --merge-floor-q, --merge-min-len
+  std::string merge_path;                               // --merge
+  bool merge_opt = false;                               // --merge-min-len or --merge-floor-q
   std::string mate_in, mate_out;
   std::string adapters_list;
   bool adapters_opt = false;
@@ -261,6 +277,16 @@ int main(int argc, char **argv) {
         return 2;
       }
       correct_opt = true;
+    } else if (a == "--merge") {
+      merge_path = val();
+      overlap_opt = true;
+    } else if (a == "--merge-min-len" || a == "--merge-floor-q") {
+      const std::string v = val();
+      if (!u32(v, a == "--merge-min-len" ? merge.min_len : merge.floor_q)) {
+        std::fprintf(stderr, "%s %s: expected a number\n", a.c_str(), v.c_str());
+        return 2;
+      }
+      merge_opt = true;
     } else if (a == "--overlap-report") {
       overlap_path = val();
       overlap_opt = true;
@@ -341,12 +367,16 @@ int main(int argc, char **argv) {
     std::fprintf(stderr, "--correct-q sets the two Phred values of --overlap-correct: it needs that option\n");
     return 2;
   }
-  if (overlap_opt && !mate) {
-    std::fprintf(stderr, "--overlap-trim, --overlap-report, --overlap-correct, --overlap-min, --overlap-mism and --overlap-err analyse the two mates of a pair: they need --mate <in2.fqc> <out2.fastq>\n");
+  if (merge_opt && merge_path.empty()) {
+    std::fprintf(stderr, "--merge-min-len and --merge-floor-q set the merge of --merge <merged.fastq>: they need that option\n");
     return 2;
   }
-  if (overlap_opt && !overlap_trim && !overlap_correct && overlap_path.empty()) {
-    std::fprintf(stderr, "--overlap-min, --overlap-mism and --overlap-err need --overlap-trim, --overlap-correct or --overlap-report <file.tsv>\n");
+  if (overlap_opt && !mate) {
+    std::fprintf(stderr, "--overlap-trim, --overlap-report, --overlap-correct, --merge, --overlap-min, --overlap-mism and --overlap-err analyse the two mates of a pair: they need --mate <in2.fqc> <out2.fastq>\n");
+    return 2;
+  }
+  if (overlap_opt && !overlap_trim && !overlap_correct && overlap_path.empty() && merge_path.empty()) {
+    std::fprintf(stderr, "--overlap-min, --overlap-mism and --overlap-err need --overlap-trim, --overlap-correct, --merge <merged.fastq> or --overlap-report <file.tsv>\n");
     return 2;
   }
   if (overlap_opt && fqgpu_overlap_check(&overlap) != FQGPU_OK) {
@@ -355,6 +385,14 @@ int main(int argc, char **argv) {
   }
   if (overlap_correct && fqgpu_correct_check(&correct) != FQGPU_OK) {
     std::fprintf(stderr, "overlap correction: expected --correct-q GOOD:BAD with GOOD 1 .. 63 and BAD below GOOD\n");
+    return 2;
+  }
+  if (!merge_path.empty() && fqgpu_merge_check(&merge) != FQGPU_OK) {
+    std::fprintf(stderr, "mate merging: expected --merge-min-len 1 .. 1023 and --merge-floor-q 0 .. 63\n");
+    return 2;
+  }
+  if (!merge_path.empty() && (trim.cut_front || trim.cut_tail || trim.crop != FQGPU_FILTER_NONE)) {
+    std::fprintf(stderr, "--merge does not go with --cut-front, --cut-tail or --crop: positional cuts have no defined meaning on a merged read yet\n");
     return 2;
   }
   if (clipped2 && !mate) {
@@ -500,9 +538,10 @@ int main(int argc, char **argv) {
       set.decode_index = false;
     }
     const Selection sel{clipped ? &adapter : nullptr, tailed ? &tail : nullptr, trimmed ? &trim : nullptr, filtered ? &filter : nullptr,
-                        overlap_opt ? &overlap : nullptr, overlap_trim, overlap_correct ? &correct : nullptr};
+                        overlap_opt ? &overlap : nullptr, overlap_trim, overlap_correct ? &correct : nullptr,
+                        merge_path.empty() ? nullptr : &merge};
     PairedReport paired;
-    if (mate) paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped2 ? &adapter2 : nullptr, sel, set);
+    if (mate) paired = processArchivePaired(argv[2], argv[3], mate_in, mate_out, clipped2 ? &adapter2 : nullptr, sel, set, merge_path);
     const FarmReport r = mate ? paired.mate1
                          : check_cmd || stats_cmd ? processArchiveCheck(argv[2], set)
                          : index_cmd ? processArchiveIndex(argv[2], set)
@@ -511,7 +550,7 @@ int main(int argc, char **argv) {
                          : fasta   ? processArchiveFasta(argv[2], argv[3], rec_a, rec_b, set)
                          : range   ? processArchiveRange(argv[2], argv[3], rec_a, rec_b, set)
                                    : processArchiveParts(argv[2], argv[3], set);
-    if (!overlap_path.empty()) writeOverlapReport(overlap_path, paired.overlap, overlap, sel.correct, paired.correct);
+    if (!overlap_path.empty()) writeOverlapReport(overlap_path, paired.overlap, overlap, sel.correct, paired.correct, sel.merge, paired.merge);
     if (!stats_path.empty() && adapters_opt) writeStatsReport(stats_path, r.stats, r.probes, probes, probe_names);
     else if (!stats_path.empty()) writeStatsReport(stats_path, r.stats);
     std::printf("{\"cmd\": \"%s\", \"threads\": %u, \"devices\": %zu, \"raw_bytes\": %zu, \"records\": %zu, \"blocks\": %zu, "
@@ -538,9 +577,10 @@ int main(int argc, char **argv) {
     }
     if (mate) {
       std::printf(", \"raw_bytes2\": %zu, \"pairs\": {\"pairs\": %llu, \"kept\": %llu, \"dropped_mate1_only\": %llu, \"dropped_mate2_only\": %llu, "
-                  "\"dropped_both\": %llu}, \"blocks1\": %zu, \"blocks2\": %zu, \"decodes2\": %zu, \"index2\": \"%s\", \"sums2\": \"%s\", \"verified2\": %zu",
+                  "\"dropped_both\": %llu%s}, \"blocks1\": %zu, \"blocks2\": %zu, \"decodes2\": %zu, \"index2\": \"%s\", \"sums2\": \"%s\", \"verified2\": %zu",
                   paired.mate2.in.raw, (unsigned long long)paired.pairs, (unsigned long long)paired.kept, (unsigned long long)paired.dropped_mate1_only,
-                  (unsigned long long)paired.dropped_mate2_only, (unsigned long long)paired.dropped_both, paired.blocks1, paired.blocks2, paired.decodes2,
+                  (unsigned long long)paired.dropped_mate2_only, (unsigned long long)paired.dropped_both,
+                  sel.merge ? (", \"merged\": " + std::to_string(paired.merged)).c_str() : "", paired.blocks1, paired.blocks2, paired.decodes2,
                   paired.mate2.indexed_blocks ? "used" : "none", paired.mate2.sums, paired.mate2.verified_blocks);
       if (overlap_opt) {
         const auto w = [&](unsigned i) { return (unsigned long long)paired.overlap[i]; };
@@ -551,6 +591,11 @@ int main(int argc, char **argv) {
           std::printf(", \"pairs_corrected\": %llu, \"bases_corrected_1\": %llu, \"bases_corrected_2\": %llu, \"n_resolved\": %llu", c(2), c(3), c(4), c(5));
         }
         std::printf("}");
+      }
+      if (sel.merge) {
+        const auto g = [&](unsigned i) { return (unsigned long long)paired.merge[i]; };
+        std::printf(", \"merge\": {\"pairs_merged\": %llu, \"bases_merged\": %llu, \"bytes_merged\": %llu, \"overlap_bases\": %llu, "
+                    "\"places_disagree\": %llu, \"places_n\": %llu, \"pairs_too_short\": %llu}", g(2), g(3), g(4), g(5), g(6), g(7), g(11));
       }
       for (int m = 0; m < 2 && (filtered || trimmed || clipped || clipped2 || tailed || overlap_trim); ++m) {
         const std::vector<uint64_t> &t = m ? paired.mate2.trim : paired.mate1.trim;
