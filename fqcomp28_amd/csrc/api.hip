@@ -17,14 +17,22 @@
 // The encode lanes use up to 16 streams (two per block in flight: sequence and quality pipelines).  ROCm maps streams onto
 // GPU_MAX_HW_QUEUES hardware queues (default 4) and kernels of streams that share a queue
 // run back to back; ask for 16 before the runtime initialises (one per stream of 8 lanes;
-// 24 helps blocks of 16 MiB and less by a fifth and costs 256 MiB blocks 2 %).  This touches the
-// host process's environment, so it is narrow and can be switched off: it never overrides a value
-// the application (or the user) set, it has no effect once HIP is initialised, and
-// FQGPU_KEEP_HW_QUEUES=1 in the environment makes the library leave the variable alone
-// ("Environment").
+// 24 helps blocks of 16 MiB and less by a fifth and costs 256 MiB blocks 2 %; 32 collapses processes
+// with many handles).  This touches the host process's environment, so it is narrow and can be
+// switched off.  A count below 16 is RAISED to 16: launchers and job schedulers write HIP's default
+// of 4 into the environment of every command, which is no choice anyone made about this library, and
+// the default lanes then ran their nine streams on four queues (DESIGN.md sections 6 and 8).  A count
+// of 16 or more, and a value that is no number, stay as they are: the library never lowers a count
+// and never writes one above 16.  It has no effect once HIP is initialised, and FQGPU_KEEP_HW_QUEUES=1
+// in the environment makes the library leave the variable alone ("Environment").
 __attribute__((constructor)) static void fq_ask_for_hw_queues() {
   if (getenv("FQGPU_KEEP_HW_QUEUES")) return;
-  setenv("GPU_MAX_HW_QUEUES", "16", 0);
+  if (const char *have = getenv("GPU_MAX_HW_QUEUES")) {
+    char *end = nullptr;
+    const long n = strtol(have, &end, 10);
+    if (end == have || *end != 0 || n < 1 || n >= 16) return;  // no number, none the rule names, or enough already
+  }
+  setenv("GPU_MAX_HW_QUEUES", "16", 1);
 }
 
 // ------------------------------------------------------------------ errors

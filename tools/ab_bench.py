@@ -1,6 +1,9 @@
 """A/B timing of library builds on ONE box: the boxes of the pool differ by +-2 % and drift, which is more than most
 single changes to the encoder are worth, so variants are never compared across gpurun calls.
     python3 tools/ab_bench.py [--data synth|real|binned|constant|config3|config4] [--rounds 3] [--steps 5] [--lanes 4] name=path/to/lib.so ...
+A variant may carry its own environment and settings, `name=path/to/lib.so@QUEUES[,keep][,lanes=L]`: GPU_MAX_HW_QUEUES
+of its children (1..32, or `env`: whatever this command was started under, untouched -- without `@` the count is 16 unless the
+environment sets one), FQGPU_KEEP_HW_QUEUES=1, a lane count of its own.
 Every variant runs in FRESH PROCESSES, one after the other, `rounds` times round-robin (A B C A B C ...): two handles
 in one process are NOT comparable -- the handle created second runs 5 % slower whatever its code is (measured with two
 copies of one library: where the driver places the second handle's scratch), a fresh process always gets the first
@@ -18,6 +21,7 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+CALLER_HW_QUEUES = os.environ.get("GPU_MAX_HW_QUEUES")   # (what a `name=lib@env` variant runs under)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np  # noqa: E402
 
@@ -78,6 +82,18 @@ def main():
     import bench
     import fqcomp28_amd as F0   # host-side helpers only (generator, parser, dataset analysis)
     libs = [(a.split("=", 1)[0], a.split("=", 1)[1]) for a in args.libs]
+    # name=lib@QUEUES[,keep][,lanes=L]: GPU_MAX_HW_QUEUES of this variant's children (`env`: the caller's environment as it
+    # comes), FQGPU_KEEP_HW_QUEUES=1, its own lane count
+    queues, opts = {}, {}
+    for i, (n, p) in enumerate(libs):
+        if "@" in p:
+            p, spec = p.rsplit("@", 1)
+            libs[i] = (n, p)
+            q, *rest = spec.split(",")
+            assert q == "env" or 1 <= int(q) <= 32, "hardware queues: 1..32"
+            queues[n] = None if q == "env" else str(int(q))
+            opts[n] = {kv.split("=")[0]: (kv.split("=") + ["1"])[1] for kv in rest}
+            assert set(opts[n]) <= {"keep", "lanes"}, opts[n]
     if args.data == "real":
         blocks = bench.make_real_workload(F0, 1 << 30, 256 << 20)
     elif args.data == "config3":
@@ -101,7 +117,15 @@ def main():
         for r in range(args.rounds):
             for n, p in libs:
                 env = dict(os.environ, FQGPU_LIB=os.path.abspath(p))
-                cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--steps", str(args.steps), "--lanes", str(args.lanes), "--reps", str(args.reps)]
+                if n in queues:
+                    env.pop("GPU_MAX_HW_QUEUES", None)
+                    if queues[n] or CALLER_HW_QUEUES:
+                        env["GPU_MAX_HW_QUEUES"] = queues[n] or CALLER_HW_QUEUES
+                o = opts.get(n, {})
+                if "keep" in o:
+                    env["FQGPU_KEEP_HW_QUEUES"] = "1"
+                cmd = [sys.executable, os.path.abspath(__file__), "--child", path, "--steps", str(args.steps), "--lanes", o.get("lanes", str(args.lanes)),
+                       "--reps", str(args.reps)]
                 if args.check and r == 0:
                     cmd.append("--check")
                 if args.spans and r == 0:
