@@ -62,8 +62,11 @@ constexpr unsigned SETS_MAX_CLASSES = 512;  // above this a segment keeps carryi
 // Hand-over of collapsed groups (two-symbol path).  After a prefix of P segments the states a group still carries are
 // few (19-40 after 2048 symbols, fewer than 10 from 8192 on), and a 64-lane gather per step walks mostly spare lanes.  A
 // wave of k_seq_setfunc that stands at n <= cap classes behind the prefix writes them out as the group's CANDIDATES and
-// takes its next group; k_seq_candwalk walks the rest of the group with one lane per candidate (64 / W groups per wave)
-// and needs nothing but the context's table in LDS; k_seq_resolve finds a group entry's candidate through F_P.
+// takes its next group; k_seq_candwalk walks the rest of the group with one lane per candidate, in rows of 16 lanes that
+// get their symbols' table rows by DPP broadcast (W / 16 rows per group, 64 / W groups per wave), and needs nothing but
+// the context's table in LDS; k_seq_resolve finds a group entry's candidate through F_P.  (The candidates keep merging --
+// a median of 16 / 10 / 7 distinct states behind 4096 / 8192 / 12288 symbols at log 11 -- and rows dealt anew at every
+// segment boundary, one per 16 distinct states, were built and measured: 45 % fewer gathers, the same step.  DESIGN.md 8.)
 constexpr unsigned SEQ_CAND_KEPT = 0xFFFFu;  // cand0[group][0] of a group that kept its functions (no state: states are even)
 constexpr unsigned CANDW_WAVES = 8;          // waves of a k_seq_candwalk workgroup
 struct SeqHandover {
@@ -487,24 +490,42 @@ k_seq_setfunc(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict
   }
 }
 
-// sets_gather2 with the row pair in a vector register (every candidate slot of a wave has its own segment's rows)
-template <int HALF>
-__device__ __forceinline__ unsigned cand_gather2(unsigned rowpair, unsigned y) {
-  unsigned addr;
-  if (HALF == 0)
-    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:DWORD" : "=v"(addr) : "v"(rowpair), "v"(y));
-  else
-    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD" : "=v"(addr) : "v"(rowpair), "v"(y));
+// One gather of the candidate walk.  The unit of the walk is a ROW of 16 lanes (a DPP row): the row's lanes hold 16 x 16
+// symbols of the row's own segment, unpacked to eight row offsets of the two-symbol table per lane, and lane N's offset
+// reaches the whole row as a modifier of the add itself (row_newbcast:N, v_add_u32_dpp): add -> ds_read_u16 -> wait, one
+// VALU instruction per gather however many groups share a wave.  (The builtin, not inline assembly: the compiler fuses the
+// DPP move into the add and places the wait states a DPP operand needs.)
+template <unsigned N>
+__device__ __forceinline__ unsigned cand_gather2(unsigned row, unsigned y) {
+  const unsigned addr = y + (unsigned)__builtin_amdgcn_update_dpp(0, (int)row, 0x150 + N, 0xF, 0xF, false);
   return *reinterpret_cast<fq_lds_u16 *>((uintptr_t)addr);
+}
+// the lane's 16 symbols as eight row offsets, one register each
+__device__ __forceinline__ void cand_rows(const uint4 cur, unsigned log, unsigned (&r)[8]) {
+  const unsigned w[4] = {cur.x, cur.y, cur.z, cur.w};
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    r[2 * i] = ((w[i] & 3u) | ((w[i] >> 6) & 0xCu)) << (log + 1);
+    r[2 * i + 1] = (((w[i] >> 16) & 3u) | ((w[i] >> 22) & 0xCu)) << (log + 1);
+  }
+}
+// the 256 symbols a row holds: lanes N .. 15 in turn (the DPP control is an immediate, so the 16 lanes are unrolled)
+template <unsigned N = 0>
+__device__ __forceinline__ unsigned cand_walk256(const unsigned (&r)[8], unsigned y) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) y = cand_gather2<N>(r[i], y);
+  if constexpr (N + 1 < 16) return cand_walk256<N + 1>(r, y);
+  else return y;
 }
 
 // Step A', two-symbol path: the handed-over groups of one k_seq_setfunc item.  A lane owns (group, candidate k): it starts
 // from cand0[group][k], walks segments P .. Q-1 of its group two symbols per gather and stores its state at every segment
-// boundary.  64 / W groups share a wave (fixed slots of W lanes; the slots behind a group's n candidates shadow the last
-// one, cand0 is padded that way).  Every walked segment is a full S: the chain's last segment belongs to no group.
+// boundary.  A group owns W / 16 rows of 16 lanes, 64 / W groups share a wave (the slots behind a group's n candidates
+// shadow the last one, cand0 is padded that way).  Every walked segment is a full S: the chain's last segment belongs to no
+// group.  Every row of a group loads the same 16 x 16 bytes of the group's segment per 256 symbols, lane l chunk l (between the
+// rows of a group these are hits on the same lines); symbols never pass through LDS.
 // LDS: the context's two-symbol table at address 0 and nothing else (64 KB at log 11), so a K3 or K6 workgroup of another
-// lane fits beside it.  W lanes of a slot hold 16 W symbols of THEIR segment; the rows of a step are read from the slot's
-// own lanes (v_readlane per slot, one v_cndmask per further slot) and are off the add -> ds_read_u16 -> wait chain.
+// lane fits beside it.
 template <unsigned W>
 __global__ void __launch_bounds__(CANDW_WAVES * 64)
 k_seq_candwalk(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restrict__ arrays, const uint32_t *__restrict__ plan,
@@ -537,8 +558,8 @@ k_seq_candwalk(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restric
     for (unsigned e = threadIdx.x; e < 2 * size; e += CANDW_WAVES * 64) dst[e] = src[e];
   }
   __syncthreads();
-  const unsigned wave = threadIdx.x >> 6, lane = fq_lane(), slot = lane / W, kk = lane % W;
-  const unsigned chunks = S / (16 * W);  // 16-byte-per-lane loads of a slot per segment (S is a multiple of 1024)
+  const unsigned wave = threadIdx.x >> 6, lane = fq_lane(), slot = lane / W, kk = lane % W, l = lane & 15u;
+  const unsigned chunks = S / 256;  // 16-byte-per-lane loads of a row per segment (S is a multiple of 1024)
   const uint8_t *run = sorted_sym + arrays[B + c];
   for (unsigned ws = wave; k0 + ws * GPW < k_end; ws += CANDW_WAVES) {
     unsigned g = k0 + ws * GPW + slot;
@@ -555,30 +576,16 @@ k_seq_candwalk(const uint8_t *__restrict__ sorted_sym, const uint32_t *__restric
     const size_t f0 = (size_t)fseg[c] + s0;
     unsigned y = H.cand0[f0 * W + kk];
     auto chunk_at = [&](unsigned j, unsigned ch) {
-      return reinterpret_cast<const uint4 *>(run + (size_t)(s0 + min(j, nseg - 1)) * S)[ch * W + kk];
+      return reinterpret_cast<const uint4 *>(run + (size_t)(s0 + min(j, nseg - 1)) * S)[ch * 16 + l];
     };
     uint4 cur = chunk_at(H.P, 0);
     for (unsigned j = H.P; j < seg_max; j++) {
       for (unsigned ch = 0; ch < chunks; ch++) {
         const bool more = ch + 1 < chunks;
         const uint4 nxt = more ? chunk_at(j, ch + 1) : j + 1 < seg_max ? chunk_at(j + 1, 0) : cur;  // lands while cur is walked
-        const uint4 rows = sets_pack_rows(cur, log);
-        for (unsigned gi = 0; gi < W; gi++) {
-          unsigned r[4] = {(unsigned)__builtin_amdgcn_readlane(rows.x, gi), (unsigned)__builtin_amdgcn_readlane(rows.y, gi),
-                           (unsigned)__builtin_amdgcn_readlane(rows.z, gi), (unsigned)__builtin_amdgcn_readlane(rows.w, gi)};
-#pragma unroll
-          for (unsigned t = 1; t < GPW; t++) {
-            const unsigned o[4] = {(unsigned)__builtin_amdgcn_readlane(rows.x, t * W + gi), (unsigned)__builtin_amdgcn_readlane(rows.y, t * W + gi),
-                                   (unsigned)__builtin_amdgcn_readlane(rows.z, t * W + gi), (unsigned)__builtin_amdgcn_readlane(rows.w, t * W + gi)};
-#pragma unroll
-            for (int i = 0; i < 4; i++) r[i] = slot == t ? o[i] : r[i];
-          }
-#pragma unroll
-          for (int i = 0; i < 4; i++) {
-            if constexpr (GPW == 1) { y = sets_gather2<0>(r[i], y); y = sets_gather2<1>(r[i], y); }
-            else { y = cand_gather2<0>(r[i], y); y = cand_gather2<1>(r[i], y); }
-          }
-        }
+        unsigned r[8];
+        cand_rows(cur, log, r);
+        y = cand_walk256(r, y);
         cur = nxt;
       }
       if (act && j < nseg) H.cand[(f0 + j) * W + kk] = (uint16_t)y;
