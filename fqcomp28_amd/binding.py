@@ -21,6 +21,9 @@ QUAL_FT_DTYPE = np.dtype(
 )
 F_WRITE_BACK_N = 1
 F_DECODE_INDEX = 2  # extension: the encode also leaves a decode index per stream
+# FQGPU_DEC_FORM_*: the kernel forms of a decode launch (Context.decode_forms)
+DEC_FORM_BOTH, DEC_FORM_QUAL_RESIDENT, DEC_FORM_QUAL_COMPACT, DEC_FORM_SEQ = 0x001, 0x002, 0x004, 0x008
+DEC_FORM_CHUNKS_QUAL_RESIDENT, DEC_FORM_CHUNKS_QUAL_COMPACT, DEC_FORM_CHUNKS_SEQ, DEC_FORM_SNAP = 0x010, 0x020, 0x040, 0x100
 
 ERRORS = {0: "OK", -1: "OVERFLOW", -2: "SHORT_READ", -3: "CORRUPT", -4: "ARG", -5: "NO_DEVICE",
           -6: "NOMEM", -7: "HIP"}
@@ -131,6 +134,7 @@ _PROTOS = {
     "fqgpu_ctx_reserve": (C.c_int, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t]),
     "fqgpu_ctx_set_seq_segment": (C.c_int, [C.c_void_p, C.c_uint]),
     "fqgpu_ctx_set_seq_group": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
+    "fqgpu_ctx_decode_forms": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_uint)] * 4),
     "fqgpu_ctx_set_seq_handover": (C.c_int, [C.c_void_p, C.c_uint, C.c_uint]),
     "fqgpu_dblock_seq_handover": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "fqgpu_dblock_fetch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -924,6 +928,13 @@ class Context:
         n, nb = C.c_size_t(0), C.c_size_t(0)
         _check(lib().fqgpu_ctx_fill_scratch(self.h, byte, C.byref(n), C.byref(nb)), "fill_scratch")
         return n.value, nb.value
+
+    def decode_forms(self):
+        """fqgpu_ctx_decode_forms (a diagnostic for tests): which kernel forms the handle's last decode launch used ->
+        dict(forms: DEC_FORM_* bits, qual_chains, qual_strides, n_cus)"""
+        f, c, s, n = C.c_uint(0), C.c_uint(0), C.c_uint(0), C.c_uint(0)
+        _check(lib().fqgpu_ctx_decode_forms(self.h, C.byref(f), C.byref(c), C.byref(s), C.byref(n)), "decode_forms")
+        return dict(forms=f.value, qual_chains=c.value, qual_strides=s.value, n_cus=n.value)
 
     def chunk_crc32(self):
         """fqgpu_chunk_crc32 -> (rc, crc, len): the chunk on the staging block -- the one encode_raw has just coded, or

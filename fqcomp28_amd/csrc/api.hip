@@ -905,6 +905,15 @@ extern "C" int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed
   return FQGPU_OK;
 }
 
+extern "C" int fqgpu_ctx_decode_forms(const fqgpu_ctx *ctx, unsigned *forms, unsigned *qual_chains, unsigned *qual_strides, unsigned *n_cus) {
+  if (!ctx) return FQGPU_E_ARG;
+  if (forms) *forms = ctx->dec_forms;
+  if (qual_chains) *qual_chains = ctx->dec_qual_chains;
+  if (qual_strides) *qual_strides = ctx->dec_qual_strides;
+  if (n_cus) *n_cus = ctx->n_cus;
+  return FQGPU_OK;
+}
+
 extern "C" int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]) {
   if (!ctx || !b || !counts) return FQGPU_E_ARG;
   counts[0] = counts[1] = counts[2] = counts[3] = 0;

@@ -907,12 +907,20 @@ bool crowded(const fqgpu_ctx *ctx, size_t chains) { return chains > 2 * (size_t)
 template <bool SNAP>
 void launch_whole_streams(fqgpu_ctx *ctx, const DecJob *jobs, const IdxJob *ijobs, size_t n, const TabView &ts, const TabView &tq) {
   const dim3 grid((unsigned)n), wave(64);
+  if (SNAP) ctx->dec_forms |= FQGPU_DEC_FORM_SNAP;
   if (all_placed(ctx, n)) {
+    ctx->dec_forms |= FQGPU_DEC_FORM_BOTH;
     hipLaunchKernelGGL(k_decode_both<SNAP>, dim3((unsigned)(2 * n)), wave, 0, ctx->stream, jobs, ijobs, (unsigned)n, ts, tq);
     return;
   }
-  if (!SNAP && crowded(ctx, n)) hipLaunchKernelGGL((k_decode<QualModel, true, false>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
-  else hipLaunchKernelGGL((k_decode<QualModel, false, SNAP>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
+  if (!SNAP && crowded(ctx, n)) {
+    ctx->dec_forms |= FQGPU_DEC_FORM_QUAL_COMPACT;
+    hipLaunchKernelGGL((k_decode<QualModel, true, false>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
+  } else {
+    ctx->dec_forms |= FQGPU_DEC_FORM_QUAL_RESIDENT;
+    hipLaunchKernelGGL((k_decode<QualModel, false, SNAP>), grid, wave, 0, ctx->stream, jobs, ijobs, tq);
+  }
+  ctx->dec_forms |= FQGPU_DEC_FORM_SEQ;
   hipLaunchKernelGGL((k_decode<SeqModel, false, SNAP>), grid, wave, 0, ctx->dec_stream2, jobs, ijobs, ts);
 }
 
@@ -1025,10 +1033,20 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
     FQ_HIP(hipMemsetAsync(blocks[i]->result, 0, sizeof(BlockResult), st));
   TabView ts = {ctx->tab[0].logs, ctx->tab[0].log_prefix, ctx->tab[0].dt, ctx->tab[0].dt_off};
   TabView tq = {ctx->tab[1].logs, ctx->tab[1].log_prefix, ctx->tab[1].dt, ctx->tab[1].dt_off};
+  // what this call launches (fqgpu_ctx_decode_forms)
+  ctx->dec_forms = 0;
+  ctx->dec_qual_chains = seq_only ? 0u : (unsigned)n_plain;
+  ctx->dec_qual_strides = (unsigned)n_qual_chunks;
   if (seq_only) {  // nothing to run beside: one stream
     fq_timer_span_begin(ctx, "decode", st);
-    if (n_plain) hipLaunchKernelGGL((k_decode<SeqModel, false, false>), dim3((unsigned)n_plain), dim3(64), 0, st, jobs, nullptr, ts);
-    if (n_seq_chunks) hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st, jobs, dch, ts);
+    if (n_plain) {
+      ctx->dec_forms |= FQGPU_DEC_FORM_SEQ;
+      hipLaunchKernelGGL((k_decode<SeqModel, false, false>), dim3((unsigned)n_plain), dim3(64), 0, st, jobs, nullptr, ts);
+    }
+    if (n_seq_chunks) {
+      ctx->dec_forms |= FQGPU_DEC_FORM_CHUNKS_SEQ;
+      hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st, jobs, dch, ts);
+    }
     fq_timer_span_end(ctx, st);
     fq_timer_span_begin(ctx, "npatch", st);
     if ((rc = launch_n_pass(ctx, jobs, n_blocks, r_tot, r_max, plan))) return rc;
@@ -1044,9 +1062,17 @@ int fq_decode_launch(fqgpu_ctx *ctx, fqgpu_dblock *const *blocks_in, size_t n_bl
   FQ_HIP(hipStreamWaitEvent(st2, ctx->dec_fork, 0));
   if (build_index) launch_whole_streams<true>(ctx, jobs, ijobs, n_plain, ts, tq);
   else if (n_plain) launch_whole_streams<false>(ctx, jobs, nullptr, n_plain, ts, tq);
-  if (crowded(ctx, n_qual_chunks)) hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
-  else if (n_qual_chunks) hipLaunchKernelGGL((k_decode_chunks<QualModel, false>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
-  if (n_seq_chunks) hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
+  if (crowded(ctx, n_qual_chunks)) {
+    ctx->dec_forms |= FQGPU_DEC_FORM_CHUNKS_QUAL_COMPACT;
+    hipLaunchKernelGGL((k_decode_chunks<QualModel, true>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
+  } else if (n_qual_chunks) {
+    ctx->dec_forms |= FQGPU_DEC_FORM_CHUNKS_QUAL_RESIDENT;
+    hipLaunchKernelGGL((k_decode_chunks<QualModel, false>), dim3((unsigned)n_qual_chunks), dim3(64), 0, st, jobs, dch, tq);
+  }
+  if (n_seq_chunks) {
+    ctx->dec_forms |= FQGPU_DEC_FORM_CHUNKS_SEQ;
+    hipLaunchKernelGGL((k_decode_chunks<SeqModel, false>), dim3((unsigned)n_seq_chunks), dim3(64), 0, st2, jobs, dch + n_qual_chunks, ts);
+  }
   FQ_HIP(hipEventRecord(ctx->dec_join, st2));
   FQ_HIP(hipStreamWaitEvent(st, ctx->dec_join, 0));
   fq_timer_span_end(ctx, st);

@@ -377,6 +377,9 @@ struct fqgpu_ctx {
   DevBuf dec_desc;    // decode job descriptors
   DevBuf dec_chunks, dec_recstart;  // chunk list and per-block rec_start of the indexed decode
   DevBuf dec_idx, dec_entries;      // indexing decode: its job descriptors, the contexts' entries at every snapshot
+  // what the last fq_decode_launch launched (fqgpu_ctx_decode_forms: a diagnostic for tests): FQGPU_DEC_FORM_* bits, the
+  // quality chains of its whole-stream walks and the quality strides of its stride walks
+  unsigned dec_forms = 0, dec_qual_chains = 0, dec_qual_strides = 0;
   KernelTimer *timer = nullptr;
   HpStage hp;                         // the staging block of the host-pointer calls and what it holds
   hipEvent_t hp_ev_h2d = nullptr;     // "the block's inputs have arrived": the lane's streams wait for it

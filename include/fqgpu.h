@@ -283,6 +283,21 @@ int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, siz
  * fqgpu_dblock_qual_segment_classes of a block coded before is meaningless.  FQGPU_E_ARG while a block of fqgpu_encode_begin
  * or its header fields are still to be collected.  Nothing in the product calls it. */
 int fqgpu_ctx_fill_scratch(fqgpu_ctx *ctx, unsigned char byte, size_t *n_buffers, size_t *n_bytes);
+/* diagnostics, for tests that must prove which decode kernel they ran: the forms the handle's last decode launch used
+ * (every decode call -- blocks, chunks, ranges, FASTA -- is one launch; a call refused before it launches leaves the last
+ * answer standing), one bit per kernel form.  The placement rules choose by the handle's compute units: one launch for
+ * both streams up to n_cus blocks, separate launches beyond, the compact quality walk beyond 2 * n_cus quality chains
+ * (whole streams) or quality strides (indexed blocks).  *qual_chains: the blocks walked from their streams' ends,
+ * *qual_strides: the quality strides walked from snapshots; any pointer may be NULL.  Nothing in the product calls it. */
+#define FQGPU_DEC_FORM_BOTH 0x001u                 /* k_decode_both: a quality and a sequence chain side by side */
+#define FQGPU_DEC_FORM_QUAL_RESIDENT 0x002u        /* k_decode<Qual>, entries and table offsets in LDS */
+#define FQGPU_DEC_FORM_QUAL_COMPACT 0x004u         /* k_decode<Qual>, entries alone in LDS */
+#define FQGPU_DEC_FORM_SEQ 0x008u                  /* k_decode<Seq> */
+#define FQGPU_DEC_FORM_CHUNKS_QUAL_RESIDENT 0x010u /* k_decode_chunks<Qual>, resident */
+#define FQGPU_DEC_FORM_CHUNKS_QUAL_COMPACT 0x020u  /* k_decode_chunks<Qual>, compact */
+#define FQGPU_DEC_FORM_CHUNKS_SEQ 0x040u           /* k_decode_chunks<Seq> */
+#define FQGPU_DEC_FORM_SNAP 0x100u                 /* the whole-stream forms above took snapshots (indexing decode) */
+int fqgpu_ctx_decode_forms(const fqgpu_ctx *ctx, unsigned *forms, unsigned *qual_chains, unsigned *qual_strides, unsigned *n_cus);
 /* copies results to the host (synchronous); any pointer may be NULL */
 int fqgpu_dblock_fetch(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint8_t *seq_out, uint8_t *qual_out,
                        uint16_t *readlens_out, uint16_t *n_count_out, uint16_t *n_pos_out,

@@ -942,13 +942,19 @@ def test_decode_index_parallel_decode(F, mode):
 
 def test_decode_batches_with_more_chains_than_places(F):
     """More than two quality chains per CU: the two streams go into separate launches and the quality
-    walk takes its compact form (entries alone in LDS, table offsets by scalar loads).  (a) one block
-    with a decode index every 4096 symbols (mixed read lengths and N's: ~600 strides per stream);
-    (b) 600 small blocks in one batch.  Both restore byte for byte."""
+    walk takes its compact form (entries alone in LDS, table offsets by scalar loads).  (a) one 6 MiB block
+    (mixed read lengths and N's) with a decode index every 65536 symbols -- the stride is a whole multiple of
+    65536, anything else is rounded up --: some 40 strides per stream, which run in the resident stride walk;
+    the same streams and indexes on as many blocks as take the quality strides past two per CU run in the
+    compact stride walk; (b) 600 small blocks in one batch (at least 2 * n_cus + 1): the compact whole-stream
+    walk.  All restore byte for byte, and the handle says which kernel form each launch used."""
+    import struct
+    from fqcomp28_amd import binding as B
     raw, recs = _synth(F, 4, 6 << 20, seed=9)
     _, _, sft, qft = O.freq_tables(raw, recs)
     ctx = F.Context(sft, qft)
-    ctx.set_index_stride(4096)
+    n_cus = ctx.decode_forms()["n_cus"]
+    ctx.set_index_stride(65536)
     b = ctx.dblock(raw, recs)
     b.encode(flags=F.F_DECODE_INDEX)
     ctx.sync()
@@ -956,14 +962,39 @@ def test_decode_batches_with_more_chains_than_places(F):
     g = b.fetch()
     for k in ("seq", "qual", "n_count", "n_pos"):
         assert np.array_equal(g[k], e[k]), k
-    assert (int(recs["len"].sum()) - 1) // 4096 > 520
+    n_sym = int(recs["len"].sum())
+    assert (n_sym - 1) // 4096 > 520
+    index = [b.fetch_index(s) for s in (0, 1)]
+    n_snap = (n_sym - 1) // 65536
+    assert n_snap >= 30
+    for s in (0, 1):  # the index the block got: magic, stream, stride, n_snap, n_sym
+        assert struct.unpack_from("<IIIIQ", index[s].tobytes(), 0) == (0x58495146, s, 65536, n_snap, n_sym)
     b.wipe()
     ctx.decode_dblocks([b])
     ctx.sync()
     assert b.status()[0] == 0 and np.array_equal(b.fetch_raw(), raw)
-    b.close()
+    d = ctx.decode_forms()
+    assert n_snap + 1 <= 2 * n_cus
+    assert d["forms"] == B.DEC_FORM_CHUNKS_QUAL_RESIDENT | B.DEC_FORM_CHUNKS_SEQ and (d["qual_chains"], d["qual_strides"]) == (0, n_snap + 1), d
+    copies = [b]
+    while len(copies) * (n_snap + 1) <= 2 * n_cus:
+        c = ctx.dblock(raw, recs)
+        c.load_streams(g["seq"], g["qual"], g["n_count"], g["n_pos"])
+        for s in (0, 1):
+            assert c.load_index(s, index[s]) == 0
+        copies.append(c)
+    for c in copies:
+        c.wipe()
+    ctx.decode_dblocks(copies)
+    ctx.sync()
+    d = ctx.decode_forms()
+    assert d["forms"] == B.DEC_FORM_CHUNKS_QUAL_COMPACT | B.DEC_FORM_CHUNKS_SEQ and d["qual_strides"] == len(copies) * (n_snap + 1) > 2 * n_cus, d
+    for c in copies:
+        assert c.status()[0] == 0 and np.array_equal(c.fetch_raw(), raw)
+        c.close()
     # (b) 600 blocks of ~40 records
-    cuts = np.linspace(0, len(recs), 601).astype(int)
+    n_small = max(600, 2 * n_cus + 1)
+    cuts = np.linspace(0, len(recs), n_small + 1).astype(int)
     blocks, originals = [], []
     for a, z in zip(cuts[:-1], cuts[1:]):
         lo = 0 if a == 0 else int(recs[a - 1]["qual_off"] + recs[a - 1]["len"] + 1)
@@ -981,6 +1012,8 @@ def test_decode_batches_with_more_chains_than_places(F):
         db.wipe()
     ctx.decode_dblocks(blocks)
     ctx.sync()
+    d = ctx.decode_forms()
+    assert d["forms"] == B.DEC_FORM_QUAL_COMPACT | B.DEC_FORM_SEQ and (d["qual_chains"], d["qual_strides"]) == (n_small, 0), d
     for db, braw in zip(blocks, originals):
         assert db.status()[0] == 0
         assert np.array_equal(db.fetch_raw(), braw)
