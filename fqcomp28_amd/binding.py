@@ -125,6 +125,8 @@ _PROTOS = {
                                       C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_longest_chain": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "fqgpu_dblock_qual_segment_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]),
+    "fqgpu_dblock_qual_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                             C.POINTER(C.c_size_t)]),
     "fqgpu_ctx_set_index_stride": (C.c_int, [C.c_void_p, C.c_uint]),
     "fqgpu_dblock_index_bytes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_size_t)]),
     "fqgpu_dblock_fetch_index": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]),
@@ -843,6 +845,19 @@ class DBlock:
         c = (C.c_size_t * 4)()
         _check(lib().fqgpu_dblock_qual_segment_classes(self.ctx.h, self.h, c), "dblock_qual_segment_classes")
         return dict(transparent=c[0], anchored=c[1], uniform=c[2], opaque=c[3])
+
+    def qual_segments(self):
+        """fqgpu_dblock_qual_segments: the segments of the quality chains of the last encode one by one -> dict(cls: uint8,
+        anchor: uint32, ctx: uint32), see include/fqgpu.h"""
+        n = C.c_size_t(0)
+        rc = lib().fqgpu_dblock_qual_segments(self.ctx.h, self.h, None, None, None, 0, C.byref(n))
+        if rc != -1:  # (FQGPU_E_OVERFLOW: there are segments, n says how many)
+            _check(rc, "dblock_qual_segments")
+        cls, anchor, ctx = np.zeros(n.value, dtype=np.uint8), np.zeros(n.value, dtype=np.uint32), np.zeros(n.value, dtype=np.uint32)
+        if n.value:
+            _check(lib().fqgpu_dblock_qual_segments(self.ctx.h, self.h, _p(cls), _p(anchor), _p(ctx), n.value, C.byref(n)),
+                   "dblock_qual_segments")
+        return dict(cls=cls, anchor=anchor, ctx=ctx)
 
     def fetch(self, raw=False):
         rc, st = self.status()

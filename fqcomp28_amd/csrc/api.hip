@@ -914,25 +914,56 @@ extern "C" int fqgpu_ctx_decode_forms(const fqgpu_ctx *ctx, unsigned *forms, uns
   return FQGPU_OK;
 }
 
-extern "C" int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]) {
-  if (!ctx || !b || !counts) return FQGPU_E_ARG;
-  counts[0] = counts[1] = counts[2] = counts[3] = 0;
-  int rc = fqgpu_sync(ctx);
-  if (rc) return rc;
+// The lane whose scratch still holds the quality segments of b's last encode, and their number: the guards and the refusals
+// of both segment diagnostics
+static int diag_lane(fqgpu_ctx *ctx, const fqgpu_dblock *b, const EncLane **lane_out, uint32_t *n_out) {
+  if (int rc = fqgpu_sync(ctx)) return rc;
   // the classes lie in the scratch of the lane that coded the block: the handle's own lane, and only while no later encode has
   // gone through it and it has not been reset (free_lane, fqgpu_ctx_set_lanes)
   if (b->owner != ctx || !b->diag_stamp || b->home_lane < 0 || b->home_lane >= FQ_MAX_LANES) return FQGPU_E_ARG;
   const EncLane &lane = ctx->lanes[b->home_lane];
-  if (lane.diag_stamp != b->diag_stamp || !lane.diag_cls || !lane.diag_n_segs) return FQGPU_E_ARG;
+  if (lane.diag_stamp != b->diag_stamp || !lane.diag_cls || !lane.diag_anchor || !lane.diag_n_segs) return FQGPU_E_ARG;
+  FQ_HIP(hipMemcpy(n_out, lane.diag_n_segs, 4, hipMemcpyDeviceToHost));
+  *lane_out = &lane;
+  return FQGPU_OK;
+}
+
+extern "C" int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]) {
+  if (!ctx || !b || !counts) return FQGPU_E_ARG;
+  counts[0] = counts[1] = counts[2] = counts[3] = 0;
+  const EncLane *lane = nullptr;
   uint32_t n = 0;
-  FQ_HIP(hipMemcpy(&n, lane.diag_n_segs, 4, hipMemcpyDeviceToHost));
+  if (int rc = diag_lane(ctx, b, &lane, &n)) return rc;
   if (!n) return FQGPU_OK;
   uint8_t *cls = static_cast<uint8_t *>(malloc(n));
   if (!cls) return FQGPU_E_NOMEM;
-  const hipError_t he = hipMemcpy(cls, lane.diag_cls, n, hipMemcpyDeviceToHost);
+  const hipError_t he = hipMemcpy(cls, lane->diag_cls, n, hipMemcpyDeviceToHost);
   if (he == hipSuccess)
     for (uint32_t i = 0; i < n; i++) counts[cls[i] == 1 ? 0 : cls[i] == 0xFF ? 2 : cls[i] == 0 ? 3 : 1]++;
   free(cls);
+  return he == hipSuccess ? FQGPU_OK : fq_hip_error(he, __FILE__, __LINE__);
+}
+
+extern "C" int fqgpu_dblock_qual_segments(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint8_t *cls_out, uint32_t *anchor_out,
+                                          uint32_t *ctx_out, size_t cap, size_t *n_out) {
+  if (!ctx || !b || !n_out || (cap && (!cls_out || !anchor_out || !ctx_out))) return FQGPU_E_ARG;
+  *n_out = 0;
+  const EncLane *lane = nullptr;
+  uint32_t n = 0;
+  if (int rc = diag_lane(ctx, b, &lane, &n)) return rc;
+  *n_out = n;
+  if (n > cap) return FQGPU_E_OVERFLOW;  // (*n_out says how many there are)
+  if (!n) return FQGPU_OK;
+  constexpr unsigned B = FQGPU_QUAL_MODELS;
+  uint32_t *seg_base = static_cast<uint32_t *>(malloc((size_t)(B + 1) * 4));
+  if (!seg_base) return FQGPU_E_NOMEM;
+  hipError_t he = hipMemcpy(seg_base, lane->diag_n_segs - B, (size_t)(B + 1) * 4, hipMemcpyDeviceToHost);
+  if (he == hipSuccess) he = hipMemcpy(cls_out, lane->diag_cls, n, hipMemcpyDeviceToHost);
+  if (he == hipSuccess) he = hipMemcpy(anchor_out, lane->diag_anchor, (size_t)n * 4, hipMemcpyDeviceToHost);
+  if (he == hipSuccess)
+    for (unsigned c = 0; c < B; c++)
+      for (uint32_t s = seg_base[c]; s < seg_base[c + 1] && s < n; s++) ctx_out[s] = c;
+  free(seg_base);
   return he == hipSuccess ? FQGPU_OK : fq_hip_error(he, __FILE__, __LINE__);
 }
 

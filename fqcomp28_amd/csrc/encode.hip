@@ -463,6 +463,7 @@ int encode_stream(fqgpu_ctx *ctx, EncLane &lane, const EncPlan &p, const EncLane
   const EncViews v = make_views<M>(lane, p, lp, b, fused);
   if (M::STREAM == 1) {  // diagnostics (fqgpu_dblock_qual_segment_classes): where this encode leaves its classes and their number
     lane.diag_cls = v.sa.cls;
+    lane.diag_anchor = v.sa.anchor;
     lane.diag_n_segs = v.seg_base + M::B;
   }
 

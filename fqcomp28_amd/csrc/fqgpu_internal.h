@@ -213,10 +213,11 @@ struct EncLane {
   // diagnostics (fqgpu_dblock_qual_segment_classes): where the lane's last encode left the classes of its quality segments
   // and their number (in enc[1], set after its buffers are reserved), and that encode's stamp (fqgpu_ctx::encodes; 0: none)
   const uint8_t *diag_cls = nullptr;
-  const uint32_t *diag_n_segs = nullptr;
+  const uint32_t *diag_anchor = nullptr;  // (fqgpu_dblock_qual_segments: SegArrays::anchor of the same encode)
+  const uint32_t *diag_n_segs = nullptr;  // = seg_base + B: the B + 1 words that end here are the contexts' first segments
   unsigned long long diag_stamp = 0;
   // whatever may move or overwrite enc[1] without being an encode (reserving ahead, set_lanes, fill_scratch) calls this first
-  void forget_diag() { diag_cls = nullptr; diag_n_segs = nullptr; diag_stamp = 0; }
+  void forget_diag() { diag_cls = nullptr; diag_anchor = nullptr; diag_n_segs = nullptr; diag_stamp = 0; }
 };
 FQ_SCRATCH_BUFS(EncLane, FQ_B(EncLane, rec_start), FQ_B(EncLane, n_cnt32), FQ_B(EncLane, n_off), FQ_B(EncLane, first_sym),
                 FQ_B(EncLane, tile_first), FQ_B(EncLane, rscan), FQ_B(EncLane, scan_tmp))

@@ -273,6 +273,15 @@ int fqgpu_dblock_seq_handover(const fqgpu_dblock *b, unsigned *handed_over, unsi
  * lane has coded another block since, and after fqgpu_ctx_set_lanes, fqgpu_ctx_reserve or
  * fqgpu_ctx_fill_scratch until b is encoded again. */
 int fqgpu_dblock_qual_segment_classes(fqgpu_ctx *ctx, const fqgpu_dblock *b, size_t counts[4]);
+/* diagnostics, for tests: the same segments one by one, in the order of the chain kernels' segment numbers (contexts
+ * ascending, the segments of a context in encode order).  cls_out[i]: 1 transparent, 2 .. 64 anchored (the number of
+ * candidates), 0xFF uniform, 0 opaque; anchor_out[i]: the offset inside the segment of its first reset symbol or its anchor
+ * symbol, the symbol of a uniform segment, 0xFFFFFFFF for an opaque one; ctx_out[i]: the segment's quality context.  cap:
+ * entries each array holds; *n_out: how many segments there are, also when cap is too small (FQGPU_E_OVERFLOW, nothing
+ * written; cap 0 with NULL arrays asks for the number alone).  Host code only: it copies what the kernels left.  Same
+ * guards and refusals as fqgpu_dblock_qual_segment_classes. */
+int fqgpu_dblock_qual_segments(fqgpu_ctx *ctx, const fqgpu_dblock *b, uint8_t *cls_out, uint32_t *anchor_out, uint32_t *ctx_out,
+                               size_t cap, size_t *n_out);
 /* diagnostics, for tests of "no result depends on what the scratch held before": waits for the handle (fqgpu_sync) and sets
  * every byte of every device scratch buffer the handle owns -- the encode lanes, the decode scratch, the device parser's,
  * header coder's and chunk decoder's, the checksum, summary and selection scratch, and the staging block of the host-pointer
