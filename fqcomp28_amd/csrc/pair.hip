@@ -220,8 +220,7 @@ k_pair_overlap(const PairSide A, const PairSide B, unsigned count, const OvSpec 
     ra = A.recs[p0 + lane];
     rb = B.recs[p0 + lane];
   }
-  const bool ok = have && ra.len != 0 && ra.len <= 65535u && (unsigned long long)ra.seq_off + ra.len <= A.raw_len && rb.len != 0 &&
-                  rb.len <= 65535u && (unsigned long long)rb.seq_off + rb.len <= B.raw_len;
+  const bool ok = have && sel_line_inside(ra.seq_off, ra.len, A.raw_len) && sel_line_inside(rb.seq_off, rb.len, B.raw_len);
   const bool analysed = ok && ra.len <= FQGPU_OVERLAP_MAX_LEN && rb.len <= FQGPU_OVERLAP_MAX_LEN;
   bool bad = have && !ok;
   unsigned my_limit_a = ra.len, my_limit_b = rb.len, my_insert = 0;  // the lane's pair: no hit so far

@@ -1,5 +1,5 @@
-// What select.hip (the selection and the probe) and pair.hip (the calls on two chunks) share: the result words and the packed
-// byte compares on the words of a line.
+// What select.hip (the selection and the probe) and pair.hip (the calls on two chunks) share: the result words, "a line of a
+// record of this chunk" and the packed byte compares on the words of a line.
 #pragma once
 #include "fqgpu_internal.h"
 
@@ -15,6 +15,11 @@ struct SelectResult {
 namespace {
 
 constexpr unsigned SW_GROUP_LANES = 8;  // lanes that read one record's lines together: select.hip's SEL_GROUP_LANES, asserted equal there
+
+// a line of a record of this chunk: it has symbols, no more than a readlen_t counts, and lies inside the chunk
+__device__ __forceinline__ bool sel_line_inside(unsigned off, unsigned len, unsigned long long raw_len) {
+  return len != 0 && len <= 65535u && (unsigned long long)off + len <= raw_len;
+}
 
 constexpr unsigned SW_H = 0x80808080u, SW_L = 0x01010101u;
 // per byte of x (every byte < 128), 0 <= k <= 128: bit 7 set where the byte is >= k

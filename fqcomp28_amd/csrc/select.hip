@@ -35,8 +35,18 @@
 // walk and forwards again for the counts, loading as it goes: a correctness path.  Without TRIM the window is the line, and a
 // long read is one loop over the rest of its requests.
 //
+// THE FRAME OF THE LINE READERS -- what the paragraph above says of the judge's way to the bytes holds for the three kernels
+// that read lines, k_adapter_find (both forms), k_tail_find and k_select_judge, and exists once: sel_wave is the wave's view
+// of its 64 records (one table load, lane = record, "a record of this chunk" by sel_line_inside of sel_words.h); sel_rounds
+// owns the eight rounds -- in round k group g's eight lanes read record 8 k + g, sel_fetch for round k + 1 issued in front
+// of the kernel's body for round k --; sel_round_steps gives the requests a round takes when a line among its eight is longer
+// than one request of 256 bytes, uniform over the wave; sel_planes turns a request's words into bit planes; sel_in_round and
+// sel_hand_back take a result back to the record's own lane.  What a kernel does with the words is its own: a lambda it
+// hands to sel_rounds.  (One exception, by measurement: the PROBE form of k_adapter_find has the loop of sel_rounds and its
+// body in line; it uses the other pieces.)
+//
 // k_adapter_find -- in front of the judge when an adapter is given (fqgpu_chunk_clip, fqgpu_dblock_clip): one pass over the
-// sequence lines in the judge's access pattern, the search itself bit-parallel -- a word's bases as four bit planes, every
+// sequence lines on that frame, the search itself bit-parallel -- a word's bases as four bit planes, every
 // place a shift, four ANDs with the adapter's planes and a population count.  It leaves one uint16_t per record, the clip
 // place, which the judge (its flag CLIP) takes for the read's length in the trim's steps; the gather sees only windows.
 // Its template flag PROBE makes it the adapter-content pass (fqgpu_chunk_probe, fqgpu_dblock_probe): the same search with up
@@ -93,7 +103,66 @@ template <bool TRIM> constexpr unsigned R_COUNTERS = TRIM ? 14 : 10;  // the wor
 constexpr unsigned R_WITH_ADAPTER = 14, R_CUT_ADAPTER = 15, R_COUNTERS_CLIP = 16;  // ... behind an adapter search
 constexpr unsigned R_WITH_POLY = 16, R_CUT_POLY = 17, R_WINDOW_CUT = 18, R_CUT_WINDOW = 19, R_COUNTERS_TAIL = 20;  // ... behind the tail trims
 
-// what a lane keeps of the record its group reads: the lines' places and the first words of both
+// ---- the frame of the line readers (the head of this file)
+
+// the first of the 64 records of this lane's wave
+__device__ __forceinline__ unsigned long long sel_wave_first() {
+  return ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+}
+
+// a wave's 64 records, lane = record
+struct SelWave {
+  unsigned long long r0, r;  // the wave's first record, this lane's
+  bool have, ok;             // r is in the table; ... and a record of this chunk
+  fqgpu_rec mine;            // its entry (zeros behind the table's end)
+  unsigned read_len;         // its length; 0 where !ok: nothing of a record outside the chunk is read, the judge refuses it
+};
+// QUAL: the quality line has to lie inside the chunk as well (a reader of the sequence line alone does not ask)
+template <bool QUAL>
+__device__ __forceinline__ SelWave sel_wave(const fqgpu_rec *__restrict__ recs, unsigned n_recs, unsigned long long raw_len, unsigned lane) {
+  SelWave wave;
+  wave.r0 = sel_wave_first();
+  wave.r = wave.r0 + lane;
+  wave.have = wave.r < n_recs;
+  wave.mine = {0u, 0u, 0u};
+  if (wave.have) wave.mine = recs[wave.r];
+  wave.ok = wave.have && sel_line_inside(wave.mine.seq_off, wave.mine.len, raw_len) && (!QUAL || sel_line_inside(wave.mine.qual_off, wave.mine.len, raw_len));
+  wave.read_len = wave.ok ? wave.mine.len : 0u;
+  return wave;
+}
+
+// the requests the lines of this lane's record take: seq, qual: the lines that are read
+__device__ __forceinline__ unsigned sel_record_steps(const SelWave &wave, bool seq, bool qual) {
+  const unsigned span = max(seq ? (wave.mine.seq_off & 15u) + wave.read_len : 0u, qual ? (wave.mine.qual_off & 15u) + wave.read_len : 0u);
+  return max((span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
+}
+
+// "this lane's record is read in round k", and what the record's own lane takes back from its group: lane 8 k + g takes what
+// group g's lanes hold
+__device__ __forceinline__ bool sel_in_round(unsigned lane, unsigned k) { return lane / SEL_ROUND_RECORDS == k; }
+__device__ __forceinline__ unsigned sel_hand_back(unsigned x, unsigned lane) {
+  return __shfl(x, (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES);
+}
+
+// The requests round k takes: those of the longest line among its eight records, my_steps being sel_record_steps of the
+// lane's own.  The same in every lane of the wave, so that the eight lanes of a record stay together through the shuffles of
+// a walk or a search while the long-read steps -- a correctness path -- are taken.
+__device__ __forceinline__ unsigned sel_round_steps(unsigned my_steps, unsigned lane, unsigned k) {
+  unsigned steps = 1;
+  if (__any(my_steps > 1 && sel_in_round(lane, k))) {  // (uniform) a long read among the eight
+    steps = sel_in_round(lane, k) ? my_steps : 1u;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
+    steps = fq_uniform(steps);
+  }
+  return steps;
+}
+
+// the fixed cuts of a read of len symbols leave [sel_cut_lo, sel_cut_hi)
+__device__ __forceinline__ unsigned sel_cut_lo(const fqgpu_trim &t, unsigned len) { return min(t.cut_front, len); }
+__device__ __forceinline__ unsigned sel_cut_hi(const fqgpu_trim &t, unsigned len) { return len - min(t.cut_tail, len - min(t.cut_front, len)); }
+
+// what a lane keeps of the record its group reads: the lines' places and the first words of the lines that are read
 struct SelStage {
   unsigned seq_off, qual_off, len;  // len 0: nothing to read (behind the table's end, or not a record of this chunk)
   uint4 s[SEL_UNROLL], q[SEL_UNROLL];
@@ -110,6 +179,31 @@ __device__ __forceinline__ void sel_load_line(uint4 (&v)[SEL_UNROLL], const uint
   for (unsigned k = 0; k < SEL_UNROLL; k++) {
     const unsigned rel = p0 + 16u * (SEL_GROUP_LANES * k + sub);
     v[k] = rel < span ? *reinterpret_cast<const uint4 *>(line + rel) : make_uint4(0, 0, 0, 0);
+  }
+}
+
+// record j of the wave's 64, for the lanes of the group that reads it: its places, and the first request of the lines asked
+// for (seq, qual; a line that is not asked for is not loaded, and one that no caller asks for costs no register)
+__device__ __forceinline__ void sel_fetch(SelStage &st, const uint8_t *__restrict__ raw, const SelWave &wave, unsigned j, unsigned sub, bool seq, bool qual) {
+  st.seq_off = __shfl(wave.mine.seq_off, j);
+  st.qual_off = __shfl(wave.mine.qual_off, j);
+  st.len = __shfl(wave.read_len, j);
+  if (seq) sel_load_line(st.s, raw, st.seq_off, st.len, 0, sub);
+  if (qual) sel_load_line(st.q, raw, st.qual_off, st.len, 0, sub);
+}
+
+// The eight rounds of a wave: in round k group g reads record j = 8 k + g, and body(stage, k, j) works on it with the words
+// of round k + 1 on their way -- the fetch stands in front of the body, which is the latency hiding.
+template <bool COPY_LAST, class Body>
+__device__ __forceinline__ void sel_rounds(const uint8_t *__restrict__ raw, const SelWave &wave, unsigned lane, bool seq, bool qual, const Body &body) {
+  const unsigned sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  SelStage cur, nxt;
+  sel_fetch(cur, raw, wave, group, sub, seq, qual);
+#pragma unroll 1
+  for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {
+    if (k + 1 < SEL_GROUP_LANES) sel_fetch(nxt, raw, wave, SEL_ROUND_RECORDS * (k + 1) + group, sub, seq, qual);
+    body(cur, k, SEL_ROUND_RECORDS * k + group);
+    if (COPY_LAST || k + 1 < SEL_GROUP_LANES) cur = nxt;
   }
 }
 
@@ -295,6 +389,19 @@ __device__ __forceinline__ ClipWord clip_planes(const uint4 v, unsigned in, bool
   r.gt = (pg & in) | (pt & in) << 16;
   return r;
 }
+// the planes of the lane's words v of the request at p0 of a record's sequence line; judge: the line is judged on the way
+// (ACGTN) and bad told; without, another kernel has done that
+__device__ __forceinline__ void sel_planes(ClipWord (&x)[SEL_UNROLL], const uint4 (&v)[SEL_UNROLL], const SelStage &st, unsigned p0, unsigned sub, bool judge,
+                                           bool &bad) {
+  const int lead = (int)(st.seq_off & 15u), span = st.len ? lead + (int)st.len : 0;
+  bool b = bad;
+#pragma unroll
+  for (unsigned k = 0; k < SEL_UNROLL; k++) {
+    const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
+    x[k] = clip_planes(v[k], sel_bits(lead - rel, span - rel), b);
+  }
+  if (judge) bad = b;
+}
 
 // the adapter as the search takes it: its planes (bit j: A[j] is that base), its length and the two limits
 struct ClipAdapter {
@@ -424,13 +531,18 @@ struct FindMany {
 template <bool PROBE> struct FindArgs { using type = FindOne; };
 template <> struct FindArgs<true> { using type = FindMany; };
 
+// the probe form's LDS table, from a function of its own so that the plain form declares none
+__device__ __forceinline__ uint32_t *probe_lds() {
+  __shared__ uint32_t lds[PROBE_LDS_WORDS];
+  return lds;
+}
+
 // clip[r] = the clip place of record r (include/fqgpu.h, step 0): the smallest place at which the adapter hits, or the
-// read's length.  The judge's access pattern -- a wave takes 64 records with one table load, eight lanes read a record's
-// sequence line as aligned 16-byte words, the next eight records' words in flight -- and nothing of its arithmetic: a word
+// read's length.  The frame of the line readers over the sequence lines, and nothing of the judge's arithmetic: a word
 // becomes bit planes once, every place of it is then tested with shifts, ANDs and a population count, a lane taking the bases
 // behind its word from its neighbours' planes by shuffles.  The line is judged over all its bytes on the way (ACGTN), so the
 // judge behind this kernel does not read it again for that.  A read longer than one request walks the requests forwards with
-// the next request's planes in hand: a correctness path.
+// the next request's planes in hand.
 // PROBE (fqgpu_chunk_probe) is the same search with many adapters: a request's planes and what lies behind the lane's words
 // are built once, and a uniform loop over the probes -- their planes and limits scalar loads from the kernel's arguments,
 // `wide` by the probe -- tests them.  A probe's first hit in a record is counted where it is found, by the first of the
@@ -441,67 +553,41 @@ template <bool PROBE>
 __global__ void __launch_bounds__(SEL_THREADS)
 k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
                const typename FindArgs<PROBE>::type arg, SelectResult *__restrict__ res) {
-  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
-  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
-  const unsigned long long r = r0 + lane;
-  const bool have = r < n_recs;
-  fqgpu_rec mine = {0u, 0u, 0u};
-  if (have) mine = recs[r];
-  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len;
-  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read; the judge refuses it)
-  const unsigned my_span = (mine.seq_off & 15u) + read_len;
-  const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
-
-  struct Stage {
-    unsigned off, len;
-    uint4 s[SEL_UNROLL];
-  };
-  const auto fetch = [&](Stage &st, unsigned j) {
-    st.off = __shfl(mine.seq_off, j);
-    st.len = __shfl(read_len, j);
-    sel_load_line(st.s, raw, st.off, st.len, 0, sub);
-  };
-  // the planes of the lane's words of the request at p0
-  const auto planes = [&](ClipWord (&x)[SEL_UNROLL], const uint4 (&v)[SEL_UNROLL], const Stage &st, unsigned p0, bool &bad) {
-    const int lead = (int)(st.off & 15u), span = st.len ? lead + (int)st.len : 0;
-#pragma unroll
-    for (unsigned k = 0; k < SEL_UNROLL; k++) {
-      const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
-      x[k] = clip_planes(v[k], sel_bits(lead - rel, span - rel), bad);
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1);
+  const SelWave wave = sel_wave<false>(recs, n_recs, raw_len, lane);
+  const unsigned my_steps = sel_record_steps(wave, true, false);
+  bool my_bad = PROBE && wave.have && !wave.ok;
+  // the planes of the request behind request s of a long read (not loaded ahead), zero behind the line's last
+  const auto next_planes = [&](ClipWord (&y)[SEL_UNROLL], const SelStage &cur, unsigned s, unsigned steps, bool &bad) {
+    y[0] = y[1] = ClipWord{0u, 0u};
+    if (s + 1 < steps) {  // (uniform)
+      uint4 v[SEL_UNROLL];
+      sel_load_line(v, raw, cur.seq_off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
+      sel_planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, sub, true, bad);
     }
   };
-  unsigned my_clip = read_len;
-  bool my_bad = PROBE && have && !ok;
-  Stage cur, nxt;
-  fetch(cur, group);
   if constexpr (PROBE) {
-    __shared__ uint32_t lds[PROBE_LDS_WORDS];
-    const unsigned n = arg.n, P = arg.P, used = 1 + (4 + PROBE_WINDOW_ROWS + 1) * (n + 1);
+    // The probe form has sel_rounds' loop and its body in line: handed over as a lambda, the loop over the probes came out
+    // 2.5 % slower with sixteen probes (The frame of the line readers).
+    uint32_t *const lds = probe_lds();
+    const unsigned n = arg.n, P = arg.P, used = 1 + (4 + PROBE_WINDOW_ROWS + 1) * (n + 1), group = lane / SEL_GROUP_LANES;
     for (unsigned i = threadIdx.x; i < used; i += SEL_THREADS) lds[i] = 0;
     __syncthreads();
+    SelStage cur, nxt;
+    sel_fetch(cur, raw, wave, group, sub, true, false);
 #pragma unroll 1
-    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
-      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
-      unsigned steps = 1;
-      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
-        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-        steps = fq_uniform(steps);
-      }
-      const int lead = (int)(cur.off & 15u);
-      const unsigned long long rec = r0 + SEL_ROUND_RECORDS * k + group;  // the record of this lane's group
+    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // (as sel_rounds)
+      if (k + 1 < SEL_GROUP_LANES) sel_fetch(nxt, raw, wave, SEL_ROUND_RECORDS * (k + 1) + group, sub, true, false);
+      const unsigned steps = sel_round_steps(my_steps, lane, k);
+      const int lead = (int)(cur.seq_off & 15u);
+      const unsigned long long rec = wave.r0 + SEL_ROUND_RECORDS * k + group;  // the record of this lane's group
       bool bad = false;
       ClipWord x[SEL_UNROLL];
-      planes(x, cur.s, cur, 0, bad);
+      sel_planes(x, cur.s, cur, 0, sub, true, bad);
       unsigned found = 0, any = CLIP_NONE;  // (the same in a record's eight lanes)
       for (unsigned s = 0; s < steps; s++) {
-        ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
-        if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
-          uint4 v[SEL_UNROLL];
-          sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
-          planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
-        }
+        ClipWord y[SEL_UNROLL];
+        next_planes(y, cur, s, steps, bad);
         const ClipBehind bh = clip_behind(x, y[0], s + 1 < steps, sub);
 #pragma unroll 1
         for (unsigned p = 0; p < n; p++) {  // (uniform)
@@ -521,14 +607,14 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
       }
       if (cur.len) {  // (a record of this chunk)
         if (any != CLIP_NONE && sub == 0) probe_count(lds, arg.out, n, P, n, any, cur.len, 0u);
-        if (arg.places)  // the probes without a hit: lane j of the record takes the probes j, j + 8
+        if (arg.places)  // the probes without a hit: lane i of the record takes the probes i, i + 8
           for (unsigned p = sub; p < n; p += SEL_GROUP_LANES)
             if (!(found >> p & 1u)) arg.places[rec * n + p] = (uint16_t)cur.len;
       }
       if (__any(bad)) my_bad = true;  // (one flag for the chunk: whose byte it was does not matter)
       if (k + 1 < SEL_GROUP_LANES) cur = nxt;
     }
-    unsigned bases = read_len;
+    unsigned bases = wave.read_len;
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) bases += __shfl_xor(bases, d);
     if (lane == 0 && bases) atomicAdd(&lds[0], bases);
@@ -539,7 +625,7 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
       if (!v) continue;
       unsigned long long at = 1;  // n_bases
       if (i >= 1 + 4 * (n + 1)) {
-        const unsigned j = i - (1 + 4 * (n + 1)), place = j / (n + 1), t = j % (n + 1);
+        const unsigned c = i - (1 + 4 * (n + 1)), place = c / (n + 1), t = c % (n + 1);
         at = probe_word(P, t, PROBE_TABLE_HEAD + (place < PROBE_WINDOW_ROWS ? place : P));
       } else if (i >= 1) {
         at = probe_word(P, (i - 1) / 4, (i - 1) % 4);
@@ -549,28 +635,17 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   } else {
     const ClipAdapter ad = {arg.plane_a, arg.plane_c, arg.plane_g, arg.plane_t, arg.m, arg.min_overlap, 100u - arg.max_err_pct};
     const bool wide = arg.m > 32u;
-#pragma unroll 1
-    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
-      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
-      unsigned steps = 1;
-      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
-        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-        steps = fq_uniform(steps);
-      }
-      const int lead = (int)(cur.off & 15u);
+    unsigned my_clip = wave.read_len;
+    sel_rounds<true>(raw, wave, lane, true, false, [&](const SelStage &cur, unsigned k, unsigned) {
+      const unsigned steps = sel_round_steps(my_steps, lane, k);
+      const int lead = (int)(cur.seq_off & 15u);
       bool bad = false;
       ClipWord x[SEL_UNROLL];
-      planes(x, cur.s, cur, 0, bad);
+      sel_planes(x, cur.s, cur, 0, sub, true, bad);
       unsigned best = CLIP_NONE;
       for (unsigned s = 0; s < steps; s++) {
-        ClipWord y[SEL_UNROLL] = {{0u, 0u}, {0u, 0u}};
-        if (s + 1 < steps) {  // (uniform) a long read: the next request, not loaded ahead
-          uint4 v[SEL_UNROLL];
-          sel_load_line(v, raw, cur.off, cur.len, (s + 1) * SEL_STEP_BYTES, sub);
-          planes(y, v, cur, (s + 1) * SEL_STEP_BYTES, bad);
-        }
+        ClipWord y[SEL_UNROLL];
+        next_planes(y, cur, s, steps, bad);
         best = min(best, clip_request(x, y[0], s + 1 < steps, ad, wide, s * SEL_STEP_BYTES, sub, lead, (int)cur.len));
 #pragma unroll
         for (unsigned i = 0; i < SEL_UNROLL; i++) x[i] = y[i];
@@ -582,15 +657,13 @@ k_adapter_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
         const unsigned o = __shfl_xor(got, d);
         got = min(got & 0x7FFFFFFFu, o & 0x7FFFFFFFu) | ((got | o) & 0x80000000u);
       }
-      // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
-      const unsigned mine_got = __shfl(got, (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES);
-      if (lane / SEL_ROUND_RECORDS == k) {
+      const unsigned mine_got = sel_hand_back(got, lane);
+      if (sel_in_round(lane, k)) {
         my_clip = mine_got & 0x7FFFFFFFu;
         my_bad = mine_got >> 31;
       }
-      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
-    }
-    if (have) arg.clip[r] = (uint16_t)my_clip;
+    });
+    if (wave.have) arg.clip[wave.r] = (uint16_t)my_clip;
   }
   if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
 }
@@ -752,7 +825,7 @@ __device__ __forceinline__ unsigned tail_low_place(const uint4 v, int pos0, int 
 
 // places[r] = a0, a1, e, e2 of record r (include/fqgpu.h, steps 0 to 1b): the clip place (clip[r] behind k_adapter_find, else
 // the read's length), the place in front of the poly-X tail, the end the fixed cuts leave and the place of the window cut.
-// The judge's access pattern as in k_adapter_find.  Poly: a word's planes (clip_planes, which judges ACGTN on the way -- left
+// The frame of the line readers over both lines.  Poly: a word's planes (sel_planes, which judges ACGTN on the way -- left
 // to k_adapter_find where that has run), per base X the mismatches counted in tail order, a prefix sum over the record's eight
 // lanes for the count a word is entered with, sixteen places tested per lane, the first violation a min-reduction and the
 // largest X place in front of it a max-reduction by shuffles.  Window: a lane takes the bytes behind its word from its
@@ -764,45 +837,17 @@ __global__ void __launch_bounds__(SEL_THREADS)
 k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const fqgpu_rec *__restrict__ recs, unsigned n_recs,
             const fqgpu_tail x, const fqgpu_trim t, const uint16_t *__restrict__ clip, uint2 *__restrict__ places,
             SelectResult *__restrict__ res) {
-  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1);
   const TailSpec sp = {x.poly_bases, x.poly_min_len, x.poly_every, x.poly_max_mism, x.window_len, x.window_q + 33u, (x.window_q + 33u) * x.window_len};
   const bool poly = sp.bases != 0, window = sp.W != 0, judge_seq = clip == nullptr;
-  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
-  const unsigned long long r = r0 + lane;
-  const bool have = r < n_recs;
-  fqgpu_rec mine = {0u, 0u, 0u};
-  if (have) mine = recs[r];
-  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len &&
-                  (unsigned long long)mine.qual_off + mine.len <= raw_len;
-  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read; the judge refuses it)
-  unsigned my_a0 = read_len;
-  if (clip != nullptr && ok) my_a0 = min((unsigned)clip[r], read_len);
-  const unsigned my_span = max(poly ? (mine.seq_off & 15u) + read_len : 0u, window ? (mine.qual_off & 15u) + read_len : 0u);
-  const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
-  const auto cut_lo = [&](unsigned len) { return min(t.cut_front, len); };
-  const auto cut_hi = [&](unsigned len) { return len - min(t.cut_tail, len - min(t.cut_front, len)); };
+  const SelWave wave = sel_wave<true>(recs, n_recs, raw_len, lane);
+  unsigned my_a0 = wave.read_len;
+  if (clip != nullptr && wave.ok) my_a0 = min((unsigned)clip[wave.r], wave.read_len);
+  const unsigned my_steps = sel_record_steps(wave, poly, window);
 
-  unsigned my_a1 = my_a0, my_e2 = cut_hi(my_a0);  // (what holds when no line is read)
+  unsigned my_a1 = my_a0, my_e2 = sel_cut_hi(t, my_a0);  // (what holds when no line is read)
   bool my_bad = false;
   if (poly || window) {  // (uniform)
-    const auto fetch = [&](SelStage &st, unsigned j) {
-      st.seq_off = __shfl(mine.seq_off, j);
-      st.qual_off = __shfl(mine.qual_off, j);
-      st.len = __shfl(read_len, j);
-      if (poly) sel_load_line(st.s, raw, st.seq_off, st.len, 0, sub);
-      if (window) sel_load_line(st.q, raw, st.qual_off, st.len, 0, sub);
-    };
-    // the planes of the lane's words of the request at p0 of the sequence line
-    const auto planes = [&](ClipWord (&y)[SEL_UNROLL], const uint4 (&v)[SEL_UNROLL], const SelStage &st, unsigned p0, bool &bad) {
-      const int lead = (int)(st.seq_off & 15u), span = st.len ? lead + (int)st.len : 0;
-      bool b = false;
-#pragma unroll
-      for (unsigned k = 0; k < SEL_UNROLL; k++) {
-        const int rel = (int)(p0 + 16u * (SEL_GROUP_LANES * k + sub));
-        y[k] = clip_planes(v[k], sel_bits(lead - rel, span - rel), b);
-      }
-      if (judge_seq) bad = bad || b;
-    };
     // the lane's words of the request at p0 of the quality line, judged: 33 .. 96
     const auto judge_qual = [&](const uint4 (&v)[SEL_UNROLL], const SelStage &st, unsigned p0, bool &bad) {
       const int lead = (int)(st.qual_off & 15u), span = st.len ? lead + (int)st.len : 0;
@@ -815,19 +860,9 @@ k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const f
       }
       bad = bad || c.bad;
     };
-    SelStage cur, nxt;
-    fetch(cur, group);
-#pragma unroll 1
-    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
-      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
-      const unsigned a0 = __shfl(my_a0, SEL_ROUND_RECORDS * k + group);
-      unsigned steps = 1;
-      if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
-        steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-        steps = fq_uniform(steps);
-      }
+    sel_rounds<false>(raw, wave, lane, poly, window, [&](const SelStage &cur, unsigned k, unsigned j) {
+      const unsigned a0 = __shfl(my_a0, j);
+      const unsigned steps = sel_round_steps(my_steps, lane, k);
       bool bad = false;
       unsigned a1 = a0;
       if (poly) {  // (uniform) from the line's last request down
@@ -837,10 +872,10 @@ k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const f
         for (unsigned s = steps - 1; s >= 1; s--) {  // a long read: not loaded ahead
           uint4 v[SEL_UNROLL];
           sel_load_line(v, raw, cur.seq_off, cur.len, s * SEL_STEP_BYTES, sub);
-          planes(y, v, cur, s * SEL_STEP_BYTES, bad);
+          sel_planes(y, v, cur, s * SEL_STEP_BYTES, sub, judge_seq, bad);
           tail_poly_step(pw, y, s * SEL_STEP_BYTES, sub, lead, (int)a0, sp);
         }
-        planes(y, cur.s, cur, 0, bad);
+        sel_planes(y, cur.s, cur, 0, sub, judge_seq, bad);
         tail_poly_step(pw, y, 0, sub, lead, (int)a0, sp);
         unsigned tl = 0;
 #pragma unroll
@@ -848,7 +883,7 @@ k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const f
           if ((sp.bases >> X) & 1u) tl = max(tl, pw.t[X] >= sp.min_len ? pw.t[X] : 0u);
         a1 = a0 - tl;
       }
-      const unsigned f = cut_lo(a1), e = cut_hi(a1);
+      const unsigned f = sel_cut_lo(t, a1), e = sel_cut_hi(t, a1);
       unsigned e2 = e;
       if (window) {  // (uniform) from the line's first request up
         const int lead = (int)(cur.qual_off & 15u);
@@ -884,17 +919,15 @@ k_tail_find(const uint8_t *__restrict__ raw, unsigned long long raw_len, const f
       unsigned got = a1 | e2 << 16, flag = bad;
 #pragma unroll
       for (unsigned d = 1; d < SEL_GROUP_LANES; d <<= 1) flag |= __shfl_xor(flag, d);
-      const unsigned from = (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES;
-      const unsigned mine_got = __shfl(got, from), mine_flag = __shfl(flag, from);
-      if (lane / SEL_ROUND_RECORDS == k) {
+      const unsigned mine_got = sel_hand_back(got, lane), mine_flag = sel_hand_back(flag, lane);
+      if (sel_in_round(lane, k)) {
         my_a1 = mine_got & 0xFFFFu;
         my_e2 = mine_got >> 16;
         my_bad = mine_flag != 0u;
       }
-      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
-    }
+    });
   }
-  if (have) places[r] = make_uint2(my_a0 | my_a1 << 16, cut_hi(my_a1) | my_e2 << 16);
+  if (wave.have) places[wave.r] = make_uint2(my_a0 | my_a1 << 16, sel_cut_hi(t, my_a1) | my_e2 << 16);
   if (__any(my_bad) && lane == 0) res->bad = 1u;  // (every writer stores the same value)
 }
 
@@ -918,30 +951,22 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
   __shared__ unsigned wg[NC];
   if (threadIdx.x < NC) wg[threadIdx.x] = 0;
   __syncthreads();
-  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1), group = lane / SEL_GROUP_LANES;
+  const unsigned lane = fq_lane(), sub = lane & (SEL_GROUP_LANES - 1);
   const bool walk_f = TRIM && t.q_front != 0, walk_t = TRIM && t.q_tail != 0;
   const bool need_seq = f.max_n != FQGPU_FILTER_NONE, need_qual = walk_f || walk_t || f.min_mean_q != 0 || f.low_q != 0;
   const unsigned level = 33u + f.low_q;
-  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
-  const unsigned long long r = r0 + lane;
-  const bool have = r < n_recs;
-  fqgpu_rec mine = {0u, 0u, 0u};
-  if (have) mine = recs[r];
+  const SelWave wave = sel_wave<true>(recs, n_recs, raw_len, lane);
+  const unsigned long long r0 = wave.r0, r = wave.r;
+  const bool have = wave.have, ok = wave.ok;
+  const fqgpu_rec mine = wave.mine;
+  const unsigned read_len = wave.read_len;
   // the start of the record's header line: behind the record in front (its entry sits in the lane in front; prev: the table
   // is a range of a chunk's and its first record has one in front of it as well)
   unsigned h0 = __shfl_up(mine.qual_off + mine.len + 1u, 1);
   if (lane == 0) h0 = have && (r || prev) ? recs[(long long)r - 1].qual_off + recs[(long long)r - 1].len + 1u : 0u;
-  const bool ok = have && mine.len != 0 && mine.len <= 65535u && (unsigned long long)mine.seq_off + mine.len <= raw_len &&
-                  (unsigned long long)mine.qual_off + mine.len <= raw_len;
   bool bad = have && !ok;
-  const unsigned read_len = ok ? mine.len : 0u;  // (nothing of a record outside the chunk is read)
 
-  // the window of a read of `len` symbols left by the fixed cuts, and by the two walks' results
-  const auto cut_lo = [&](unsigned len) { return min(t.cut_front, len); };
-  const auto cut_hi = [&](unsigned len) {
-    if constexpr (STEP0 == SEL_TAIL) return len;  // (e2: cut_tail is in it)
-    else return len - min(t.cut_tail, len - min(t.cut_front, len));
-  };
+  // the window the two walks' results leave
   const auto window = [&](unsigned start, unsigned stop) {  // -> start | n << 16
     if (start >= stop) return 0u;
     return start | min(stop - start, t.crop) << 16;
@@ -956,16 +981,12 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
     if (ok) my_places = places[r];
     eff_len = min(my_places.y >> 16, read_len);
   }
-  if constexpr (TRIM) my_win = window(cut_lo(eff_len), cut_hi(eff_len));  // (what holds when no line is read)
+  if constexpr (TRIM) {  // (what holds when no line is read)
+    unsigned hi = eff_len;  // SEL_TAIL: it is e2, and cut_tail is in that
+    if constexpr (STEP0 != SEL_TAIL) hi = sel_cut_hi(t, eff_len);
+    my_win = window(sel_cut_lo(t, eff_len), hi);
+  }
   if (need_seq || need_qual) {  // (uniform)
-    // record j of the wave's 64, for the lanes of the group that reads it
-    const auto fetch = [&](SelStage &st, unsigned j) {
-      st.seq_off = __shfl(mine.seq_off, j);
-      st.qual_off = __shfl(mine.qual_off, j);
-      st.len = __shfl(read_len, j);
-      if (need_seq) sel_load_line(st.s, raw, st.seq_off, st.len, 0, sub);
-      if (need_qual) sel_load_line(st.q, raw, st.qual_off, st.len, 0, sub);
-    };
     // the lane's words of the request at p0 of a line; [ws, we): the window, in places of the line (TRIM)
     const auto judge_words = [&](SelCounts &c, const uint4 (&v)[SEL_UNROLL], unsigned off, unsigned len, unsigned p0, int ws, int we, bool is_seq) {
       const int lead = (int)(off & 15u), span = lead + (int)len;
@@ -983,14 +1004,15 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
         else sel_judge_qual<TRIM>(c, v[k], first, last, wf, wl, level);
       }
     };
-    // steps (TRIM): the requests the longest line of the eight records in hand takes (the same in every lane of the wave, so
-    // that the eight lanes of a record stay together through the shuffles of a walk)
+    // steps (TRIM): sel_round_steps of the round
     const auto consume = [&](const SelStage &st, unsigned steps, unsigned eff) {  // eff: CLIP, the record's eff_len
       SelCounts c = {0u, 0u, 0u, false};
       unsigned w = 0;
       if constexpr (TRIM) {
         const unsigned cut_len = CLIP ? eff : st.len;
-        const int a = (int)cut_lo(cut_len), b = (int)cut_hi(cut_len), lead_q = (int)(st.qual_off & 15u);
+        unsigned hi = cut_len;  // SEL_TAIL: it is e2, and cut_tail is in that
+        if constexpr (STEP0 != SEL_TAIL) hi = sel_cut_hi(t, cut_len);
+        const int a = (int)sel_cut_lo(t, cut_len), b = (int)hi, lead_q = (int)(st.qual_off & 15u);
         unsigned start = (unsigned)a, stop = (unsigned)b;
         if (walk_f) {  // (uniform)
           SelWalk wk = {0, 0ull, false};
@@ -1050,40 +1072,23 @@ k_select_judge(const uint8_t *__restrict__ raw, unsigned long long raw_len, cons
       }
       return make_uint3(x, y, w);
     };
-    // the requests a record's lines take
-    const unsigned my_span = max(need_seq ? (mine.seq_off & 15u) + read_len : 0u, need_qual ? (mine.qual_off & 15u) + read_len : 0u);
-    const unsigned my_steps = max((my_span + SEL_STEP_BYTES - 1) / SEL_STEP_BYTES, 1u);
-    SelStage cur, nxt;
-    fetch(cur, group);
-#pragma unroll 1
-    for (unsigned k = 0; k < SEL_GROUP_LANES; k++) {  // round k: group g reads record 8 k + g
-      if (k + 1 < SEL_GROUP_LANES) fetch(nxt, SEL_ROUND_RECORDS * (k + 1) + group);
-      unsigned eff = 0;
-      if constexpr (CLIP) eff = __shfl(eff_len, SEL_ROUND_RECORDS * k + group);
-      unsigned steps = 1;
-      if constexpr (TRIM) {
-        if (__any(my_steps > 1 && lane / SEL_ROUND_RECORDS == k)) {  // (uniform) a long read among the eight
-          steps = lane / SEL_ROUND_RECORDS == k ? my_steps : 1u;
-#pragma unroll
-          for (int d = 32; d > 0; d >>= 1) steps = max(steps, (unsigned)__shfl_xor(steps, d));
-          steps = fq_uniform(steps);
-        }
-      }
+    const unsigned my_steps = sel_record_steps(wave, need_seq, need_qual);
+    sel_rounds<false>(raw, wave, lane, need_seq, need_qual, [&](const SelStage &cur, unsigned k, unsigned j) {
+      unsigned eff = 0, steps = 1;  // (without TRIM a long read is one loop over the rest of its requests: no steps)
+      if constexpr (CLIP) eff = __shfl(eff_len, j);
+      if constexpr (TRIM) steps = sel_round_steps(my_steps, lane, k);
       const uint3 got = consume(cur, steps, eff);
-      // back to the record's own lane: lane 8 k + g takes what group g's lanes hold
-      const unsigned from = (lane & (SEL_ROUND_RECORDS - 1)) * SEL_GROUP_LANES;
-      const unsigned x = __shfl(got.x, from), y = __shfl(got.y, from);
-      unsigned w = 0;
-      if constexpr (TRIM) w = __shfl(got.z, from);
-      if (lane / SEL_ROUND_RECORDS == k) {
+      const unsigned x = sel_hand_back(got.x, lane), y = sel_hand_back(got.y, lane);
+      unsigned win_back = 0;
+      if constexpr (TRIM) win_back = sel_hand_back(got.z, lane);
+      if (sel_in_round(lane, k)) {
         n_count = x & 0xFFFFu;
         low_count = x >> 16;
         q_bytes = y & 0x7FFFFFFFu;
         bad = bad || (y >> 31);
-        my_win = w;
+        my_win = win_back;
       }
-      if (k + 1 < SEL_GROUP_LANES) cur = nxt;
-    }
+    });
   }
 
   // the verdict on what is left [start, start + n): 0 kept, 1 .. 5 the first criterion that fails; a read with nothing left
@@ -1337,7 +1342,7 @@ k_select_mark(const unsigned long long *__restrict__ mark, unsigned n_recs, uint
   }
   __syncthreads();
   const unsigned lane = fq_lane();
-  const unsigned long long r0 = ((unsigned long long)blockIdx.x * (SEL_THREADS / 64) + (threadIdx.x >> 6)) * SEL_WAVE_RECORDS;
+  const unsigned long long r0 = sel_wave_first();
   if (r0 < n_recs) {  // (uniform)
     const unsigned long long kw = keep[r0 / 64], gone = kw & ~mark[r0 / 64];
     if (gone) {  // (uniform)
